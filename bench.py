@@ -21,6 +21,15 @@ MDH_OPT_FRAME_OVERLAP); `value_serial` / `ms_per_step_serial` beside it are SURV
 passes, nothing else in flight.  `roofline` prices the dominant kernel on its duration inside the
 timed region (as BENCH_r01 did), `roofline_serial` on its duration with the chip to itself (what
 BENCH_r02's `roofline` held): "schema": 3 marks lines with this meaning.
+
+A plain run sets up, pre-warms, warms up, times the steps and prints the line.  `--full` adds what takes
+runs of its own: the serial segment (`value_serial`, `roofline_serial`, `passes_serial`, `steady_state`),
+`valu_issue` and the CPU baselines.  `--dump-outputs DIR` writes the framebuffer of the last timed step
+as DIR/framebuffer.npy with its non-finite values as 0 and DIR/framebuffer_nonfinite.npy marking them (float32,
+H x W x 3; when the two would pass DUMP_MAX_BYTES = 56 MiB, the pixels of a fixed seeded sample).  The
+headline workload's frame does not depend on how many frames the time-bound pre-warm ran (its probe atlases
+settle: the same bits after 0.4 s or 1 s of pre-warm, 5 + 20 or 20 + 200 steps, measured on one MI355X:
+DESIGN.md section 6); ball_game's does, its balls move in every step.
 """
 import argparse
 import json
@@ -220,6 +229,33 @@ def cpu_baseline_exprs():
             "sample": "%d frames of 256x256 simple_scene, screen mode 1 (primary rays, normal colour), space partition on (%.1f s) after 1 warm-up frame" % (frames, dt)}
 
 
+DUMP_MAX_BYTES = 56 << 20  # both arrays together, below the 64 MB a dump may hold
+NONFINITE_CODES = {"nan": 1.0, "+inf": 2.0, "-inf": 3.0}
+
+
+def dump_outputs(path, img, rank):
+    """The framebuffer of the last timed step, finite so that any comparison can read it: `path`/framebuffer.npy holds the
+    values with every non-finite one as 0, `path`/framebuffer_nonfinite.npy (same shape) says which were not finite:
+    0 finite, else NONFINITE_CODES (the kernels keep IEEE behaviour, as the oracle does: a few pixels of a frame can
+    be NaN).  Both float32, H x W x 3; a larger frame is cut to the pixels of a fixed seeded sample (flat pixel indices
+    in ascending order, numpy default_rng(0)): N x 3."""
+    if rank != 0:
+        return
+    import numpy as np
+    img = np.ascontiguousarray(img, dtype=np.float32)
+    if 2 * img.nbytes > DUMP_MAX_BYTES:
+        n_px = img.shape[0] * img.shape[1]
+        keep = np.sort(np.random.default_rng(0).choice(n_px, DUMP_MAX_BYTES // (2 * 3 * 4), replace=False))
+        img = img.reshape(n_px, 3)[keep]
+    code = np.zeros(img.shape, dtype=np.float32)
+    code[np.isnan(img)] = NONFINITE_CODES["nan"]
+    code[img == np.inf] = NONFINITE_CODES["+inf"]
+    code[img == -np.inf] = NONFINITE_CODES["-inf"]
+    os.makedirs(path, exist_ok=True)
+    np.save(os.path.join(path, "framebuffer.npy"), np.where(code == 0, img, np.float32(0)))
+    np.save(os.path.join(path, "framebuffer_nonfinite.npy"), code)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -227,6 +263,8 @@ def main():
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--workload", default="global_illumination_1080p_ddgi8x8x8", choices=sorted(WORKLOADS))
     ap.add_argument("--atlas", default="rgb8", choices=("rgb8", "f32"))
+    ap.add_argument("--full", action="store_true", help="also the serial segment, valu_issue and the CPU baselines (runs of their own)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write the last timed step's framebuffer to DIR/framebuffer.npy (+ framebuffer_nonfinite.npy)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--prewarm-s", type=float, default=0.4, help="seconds of untimed frames before the warm-up (clock ramp)")
     ap.add_argument("--mode", type=int, default=None, help="override the screen mode (ablation runs only)")
@@ -356,6 +394,8 @@ def main():
         R.Front_Buffer(copy=False)
     sync()
     dt = vmax(time.perf_counter() - t0)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, frame.Gather_Framebuffer(dist), rank)
 
     def pass_times():
         out = {}
@@ -370,7 +410,7 @@ def main():
     exchange_ms = vmax(passes.get("exchange", {}).get("ms_avg", 0.0)) if world > 1 or "exchange" in passes else None
     overlap = R.Get_Option(B.OPT_FRAME_OVERLAP)
     passes_serial, serial_dt = None, None
-    if (overlap or rehearsal) and not args.no_serial_segment:  # (the oracle has no schedule; the rehearsal walks the segment's control flow all the same)
+    if args.full and (overlap or rehearsal) and not args.no_serial_segment:  # (the oracle has no schedule; the rehearsal walks the segment's control flow all the same)
         # Pipelined frames share the chip between kernels, which stretches every launch.  A short
         # untimed run of the strictly serial schedule gives each kernel's duration on its own.
         R.Set_Option(B.OPT_FRAME_OVERLAP, 0)
@@ -477,10 +517,10 @@ def main():
             out["steady_state"] = {"protocol": "SURVEY.md 8(d): atlases zeroed, 8 warm-up frames, frames 9..40 one device-synchronised frame at a time, median",
                                    "ms_median": round(steady_median * 1e3, 4), "value_median": round(W * H / steady_median / 1e6, 3),
                                    "ms_min": round(steady[0] * 1e3, 4), "ms_max": round(steady[-1] * 1e3, 4), "frames": len(steady)}
-        valu = measured_valu(args.workload, world, passes_serial or passes)
+        valu = measured_valu(args.workload, world, passes_serial or passes) if args.full else None
         if valu:
             out["valu_issue"] = valu
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             out["cpu_baseline"] = cpu_baseline(args.workload)
             out["cpu_baseline_exprs"] = cpu_baseline_exprs()
             # the reference's work per second: what the oracle evaluates for a frame / the GPU's frame time (the kernels do

@@ -2,7 +2,7 @@
 # on the GPU box: every bench workload plus the example programs' own benches, one line each
 cd "$(dirname "$0")/.." || exit 1
 for w in global_illumination_1080p_ddgi8x8x8 simple_scene_1080p_direct light_shafts_1080p global_illumination_4096sq_ddgi8x8x8; do
-  python bench.py --workload $w --no-cpu-baseline 2>/dev/null | tail -1 | python -c "
+  python bench.py --full --workload $w --no-cpu-baseline 2>/dev/null | tail -1 | python -c "
 import sys, json
 d = json.loads(sys.stdin.read())
 print('%-40s %8.1f Mpix/s %7.3f ms  serial passes %s' % ('$w', d['value'], d['ms_per_step'], {k: v['ms_avg'] for k, v in (d.get('passes_serial') or {}).items()}))"

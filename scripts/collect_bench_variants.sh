@@ -6,7 +6,7 @@ TAG=${1:-r02}
 cd "$(dirname "$0")/.." || exit 1
 OUT=gpurun_out/variants_$TAG
 mkdir -p $OUT
-B="timeout -k 10 200 python bench.py --no-cpu-baseline"
+B="timeout -k 10 200 python bench.py --full --no-cpu-baseline"
 $B --steps 20 --warmup 5 2>/dev/null | tail -1 > $OUT/bench_driver_20steps.json &&
 $B --steps 200 --warmup 20 --atlas f32 2>/dev/null | tail -1 > $OUT/bench_f32_atlases.json &&
 $B --steps 200 --warmup 20 --animate-light 2>/dev/null | tail -1 > $OUT/bench_animated_light.json &&

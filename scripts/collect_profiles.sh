@@ -9,7 +9,7 @@ ROOT=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}
 OUT=$ROOT/gpurun_out/profiles_$TAG
 rm -rf $OUT; mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-python3 $ROOT/bench.py --workload $WL > $OUT/bench.json 2> $OUT/bench.err || exit 1
+python3 $ROOT/bench.py --full --workload $WL > $OUT/bench.json 2> $OUT/bench.err || exit 1
 B="python3 $ROOT/bench.py --workload $WL --steps 20 --warmup 3 --prewarm-s 0.02 --no-cpu-baseline --no-serial-segment"
 # kernel durations of the default (pipelined) schedule and of the serial one
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -- $B > /dev/null 2>&1

@@ -4,7 +4,7 @@ cd "$(dirname "$0")/.." || exit 1
 OUT=gpurun_out/${1:-r04_new_workloads}
 mkdir -p $OUT
 for wl in simple_scene_1080p_full global_illumination_1080p_default_probes ball_game_1080p ball_game_1080p_ddgi8x8x8 ${EXTRA_WL}; do
-  timeout -k 10 300 python bench.py --workload $wl --no-cpu-baseline > $OUT/$wl.json 2> $OUT/$wl.err || { echo "FAILED $wl"; tail -5 $OUT/$wl.err; exit 1; }
+  timeout -k 10 300 python bench.py --full --workload $wl --no-cpu-baseline > $OUT/$wl.json 2> $OUT/$wl.err || { echo "FAILED $wl"; tail -5 $OUT/$wl.err; exit 1; }
   python - $OUT/$wl.json <<'PY'
 import json, sys
 d = json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])

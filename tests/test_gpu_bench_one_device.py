@@ -25,7 +25,7 @@ def free_port():
 def test_bench_two_ranks_on_one_gpu(world):
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(world), "--master-addr", "127.0.0.1",
            "--master-port", str(free_port()), os.path.join(ROOT, "bench.py"), "--gpus", str(world), "--one-device", "--steps", "12", "--warmup", "3",
-           "--prewarm-s", "0.05", "--no-cpu-baseline", "--comm-timeout-s", "60"]
+           "--prewarm-s", "0.05", "--full", "--no-cpu-baseline", "--comm-timeout-s", "60"]
     out = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=ROOT, env=dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0"))
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
     assert out.returncode == 0 and len(lines) == 1, out.stdout[-2000:] + out.stderr[-3000:]
