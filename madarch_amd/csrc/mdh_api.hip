@@ -14,6 +14,7 @@
 #include <hip/hiprtc.h> // types only: the library is opened on first use (no link-time dependency)
 #include <rccl/rccl.h>  // types only, likewise: librccl is opened by the first mdh_comm_* call
 
+#include <algorithm>
 #include <atomic>
 #include <cmath>
 #include <cstdio>
@@ -450,6 +451,7 @@ static int rd_i(const mdh_renderer *r, int off) { int32_t i; memcpy(&i, r->scene
 static float4 mk4(float x, float y, float z, float w) { float4 v; v.x = x; v.y = y; v.z = z; v.w = w; return v; }
 static float4 rd_v3w(const mdh_renderer *r, int off, float w) { return mk4(rd_f(r, off), rd_f(r, off + 4), rd_f(r, off + 8), w); }
 static float i_as_f(int i) { float f; memcpy(&f, &i, 4); return f; }
+static int f_as_i(float f) { int i; memcpy(&i, &f, 4); return i; }
 
 // Repack the std140 images into the float4 table the kernels stage into LDS
 // (layout in mdh_device.h) and refresh the SGPR header.
@@ -567,6 +569,34 @@ static int commit_scene(mdh_renderer *r, hipStream_t up)
          if (r->pk[k].type == PK_CUSTOM) H[H_FASTINFO] = 0;
          else H[H_TBASE + r->pk[k].type] = r->prim_base[k];
       }
+   }
+   // segment_clear's threshold EPS + delta and its coordinate bound lim (mdh_device.h, where the argument is): delta =
+   // 2^-12 (1 + lim) with lim = 2 (M + 1), M the largest magnitude the scan reads -- coordinates, offsets, radii, half-sizes.
+   // Off (0) for scenes the bound does not cover: triangles, user-defined kinds, negative radii or half-sizes, non-finite
+   // values, and a max_dist (every SDF value is at most that) not above the threshold.
+   {
+      bool on = s.tcount[PK_TRIANGLE] == 0;
+      for (int k = 0; k < r->npk; ++k) on = on && r->pk[k].type != PK_CUSTOM;
+      float M = 0.0f;
+      auto see = [&](float v) { if (std::isfinite(v)) M = std::max(M, std::fabs(v)); else on = false; };
+      for (int g = 0; g < 6; ++g)
+         if (s.axis_off[g] != INFINITY) see(s.axis_off[g]);
+      for (int i = 0; i < s.gplane_count; ++i) { const float4 p = t[s.gplane_slot + i]; see(p.x); see(p.y); see(p.z); see(p.w); }
+      for (int i = 0; i < s.tcount[PK_SPHERE]; ++i) {
+         const float4 a = t[s.tslot[PK_SPHERE] + i];
+         see(a.x); see(a.y); see(a.z); see(a.w);
+         on = on && a.w >= 0.0f;
+      }
+      for (int i = 0; i < s.tcount[PK_BOX]; ++i) {
+         const float4 c = t[s.tslot[PK_BOX] + 2 * i], e = t[s.tslot[PK_BOX] + 2 * i + 1];
+         see(c.x); see(c.y); see(c.z); see(e.x); see(e.y); see(e.z);
+         on = on && e.x >= 0.0f && e.y >= 0.0f && e.z >= 0.0f;
+      }
+      const float lim = 2.0f * (M + 1.0f);
+      const float thr = 0.001f + std::ldexp(1.0f + lim, -12); // (MDH_EPS + delta)
+      on = on && std::isfinite(lim) && std::isfinite(thr) && s.max_dist > thr;
+      H[H_VCLEAR] = f_as_i(on ? thr : 0.0f);
+      H[H_VCLEAR_LIM] = f_as_i(lim);
    }
    // material ids (int32), 4 per float4
    // the MDH_X programs of the user-defined kinds (ints, read through hdr ())

@@ -80,6 +80,9 @@ struct KScene {
 enum {
    H_NK = 0,
    H_NL = 1,
+   // segment_clear (MDH_VIS_CLEAR): the float bits of its threshold EPS + delta (0: off for this scene) and of the bound on
+   // every coordinate of a segment it may clear
+   H_VCLEAR = 2, H_VCLEAR_LIM = 3,
    H_KTYPE = 8,    // [8] PK_*
    H_KCOUNT = 16,  // [8] runtime count (prim_<K>_count, scenes.adb:560-565)
    H_KBASE = 24,   // [8] flat index base = sum of earlier DECLARED counts
@@ -1283,6 +1286,84 @@ template <int PART> MDH_DEV float sdf_info(const KScene &sc, f3 x, int &index)
    MDH_WORK(2);
    if (PART & MDH_PF_PART) return partitioning_lookup<true, (PART & MDH_PF_CUSTOM) != 0, MDH_PF_HAS_FALLBACK(PART), (PART & MDH_PF_PSMALL) != 0>(sc, x, index);
    return closest_primitive_info<(PART & MDH_PF_CUSTOM) != 0>(sc, x, index);
+}
+
+// ------------------------------------------------------------- probe-visibility clearance
+// segment_clear (MDH_VIS_CLEAR) -- proves that a probe-visibility ray ends with vis = 1 without marching it.
+//
+// raycast_visibility (raymarching.glsl:39-56) evaluates the SDF only at fl(A + fl(vd * total)) with 0 <= total < vmax
+// (A = from_off) and returns 0 only when one of those values is < MDH_EPS.  If a lower bound of the scene's SDF over the
+// segment A + vd [0, vmax] exceeds thr = MDH_EPS + delta, no evaluation is below MDH_EPS; each step then adds at least
+// MDH_EPS to total (vmax << 2^13: more than half an ulp of total), so the loop ends, with vis = 1.  The ray need not be
+// marched: the result keeps its bits.  Straight-line code, no loop over march steps:
+//   planes   (the six folded offsets and the general planes): affine along the segment, the smaller endpoint value;
+//   spheres  the centre's distance to its closest point A + vd t, t = clamp(dot(c - A, vd), 0, vmax), against r + thr
+//            (compared squared: the host turns the test off for r < 0);
+//   boxes    a separating-axis test of the segment against the box's AABB grown by thr along every axis (the box's three
+//            axes and the three vd x e_a, division-free): separated, every point of the segment is farther than thr from
+//            the box in the max norm, hence in the Euclidean one.  (A bounding sphere would clear nothing near a box on the
+//            floor among the probes.)
+// Rounding.  The host (commit_scene) sets delta = 2^-12 (1 + lim), where lim bounds every magnitude of the table, and the
+// test requires |A| and |B| = |A + vd vmax| <= lim in every coordinate, so every quantity here and in the march is a small
+// multiple of lim, and each of the following is at most a few 2^-22 lim:
+//   - the march's positions fl(A + fl(vd total)) lie that close to the segment (and the SDF is 1-Lipschitz);
+//   - the SDF's own rounding (dot, sqrt, the box's q);
+//   - the bound's own rounding: its endpoints; the closest-point t, where |vd| = 1 +- 2^-22 moves the point along the
+//     segment by ~2^-22 lim, which the distance at its minimum meets at most to first order; the products of the
+//     separating axes, whose error scales with the same |vd| terms as their margin thr (|vd_b| + |vd_c|).
+// Their sum stays far below delta.  The culls of closest_primitive skip a primitive only when it is not below the running
+// minimum, so the march's value is the minimum over all primitives and max_dist, which the host requires to exceed thr.
+// Every comparison fails closed on NaN (a non-finite A, vd or vmax fails the bound on lim): such a ray marches as before.
+// Always false for the space-partition variants and user-defined kinds; the host sets thr = 0 (off) for triangles,
+// negative radii or half-sizes and non-finite values.
+#ifndef MDH_VIS_CLEAR
+#define MDH_VIS_CLEAR 1
+#endif
+template <int PART> MDH_DEV bool segment_clear(const KScene &sc, f3 A, f3 vd, float vmax)
+{
+   if (!MDH_VIS_CLEAR || (PART & (MDH_PF_PART | MDH_PF_CUSTOM))) return false;
+   constexpr bool ROOM = (PART & MDH_PF_ROOM) != 0;
+   const float thr = __int_as_float(hdr(H_VCLEAR)), lim = __int_as_float(hdr(H_VCLEAR_LIM));
+   const f3 B = A + vd * vmax;
+   bool ok = thr > 0.0f;
+   ok = ok && __builtin_fabsf(A.x) <= lim && __builtin_fabsf(A.y) <= lim && __builtin_fabsf(A.z) <= lim;
+   ok = ok && __builtin_fabsf(B.x) <= lim && __builtin_fabsf(B.y) <= lim && __builtin_fabsf(B.z) <= lim;
+   // planes (folded offsets of absent directions are +inf)
+   float pl = min_(min_(A.x, B.x) + sc.axis_off[0], -max_(A.x, B.x) + sc.axis_off[1]);
+   pl = min_(pl, min_(min_(A.y, B.y) + sc.axis_off[2], -max_(A.y, B.y) + sc.axis_off[3]));
+   pl = min_(pl, min_(min_(A.z, B.z) + sc.axis_off[4], -max_(A.z, B.z) + sc.axis_off[5]));
+   {
+      const int n = ROOM ? 0 : sc.gplane_count, s0 = sc.gplane_slot;
+#pragma unroll 1
+      for (int i = 0; i < n; ++i) pl = min_(pl, min_(sd_plane(s_tab[s0 + i], A), sd_plane(s_tab[s0 + i], B)));
+   }
+   ok = ok && pl > thr;
+   {
+      const int n = ROOM ? 1 : sc.tcount[PK_SPHERE], s0 = sc.tslot[PK_SPHERE];
+#pragma unroll 1
+      for (int i = 0; i < n; ++i) {
+         const float4 a = s_tab[s0 + i];
+         const f3 w = xyz(a) - A;
+         const f3 q = w - vd * clamp_(dot(w, vd), 0.0f, vmax);
+         const float rt = a.w + thr;
+         ok = ok && dot2(q) > rt * rt;
+      }
+   }
+   {
+      const int n = ROOM ? 1 : sc.tcount[PK_BOX], s0 = sc.tslot[PK_BOX];
+      const f3 hv = vd * (vmax * 0.5f), ah = abs3(hv);
+#pragma unroll 1
+      for (int i = 0; i < n; ++i) {
+         const f3 m = (A + hv) - xyz(s_tab[s0 + 2 * i]);
+         const f3 e = xyz(s_tab[s0 + 2 * i + 1]) + F3s(thr);
+         const bool sep = __builtin_fabsf(m.x) > e.x + ah.x || __builtin_fabsf(m.y) > e.y + ah.y || __builtin_fabsf(m.z) > e.z + ah.z ||
+                          __builtin_fabsf(m.y * hv.z - m.z * hv.y) > e.y * ah.z + e.z * ah.y ||
+                          __builtin_fabsf(m.z * hv.x - m.x * hv.z) > e.z * ah.x + e.x * ah.z ||
+                          __builtin_fabsf(m.x * hv.y - m.y * hv.x) > e.x * ah.y + e.y * ah.x;
+         ok = ok && sep;
+      }
+   }
+   return ok;
 }
 
 // ------------------------------------------------------------------------- raymarching

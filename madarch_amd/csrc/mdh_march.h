@@ -152,6 +152,9 @@ template <int PART> MDH_DEV bool march_plain(const KScene &sc, f3 o, f3 d, float
 #ifndef MDH_QVIS_SHARED
 #define MDH_QVIS_SHARED 0 // the radiance pass's visibility queue shared by the four wavefronts of a workgroup (queued_visibility_shared)
 #endif
+#if MDH_QVIS_SHARED && MDH_VIS_CLEAR
+#error "queued_visibility_shared lists its rays without segment_clear: build it with -DMDH_VIS_CLEAR=0"
+#endif
 #if defined(MDH_PHASES) || MDH_QVIS_SHARED || defined(MDH_PARK_PAD) // (MDH_PARK_PAD: what one more row costs, measured by itself)
 #define MDH_PARK_DWORDS 20 // (row 19: the diagnostic's accumulators / the shared queue's second list and counters)
 #else
@@ -313,6 +316,7 @@ MDH_DEV int queued_visibility(const KScene &sc, const KProbes &pr, float *pk, f3
          if (!(0.0f < vmax)) bits |= 1 << i;     // the loop is never entered
          else if (sd0 < MDH_EPS) { }             // blocked at once
          else if (!(sd0 < vmax)) bits |= 1 << i; // the first step already passes the probe
+         else if (segment_clear<PART>(sc, P + (N * MDH_MIN_STEP) * 5.0f, sdiv3(hvec, length(hvec)), vmax)) bits |= 1 << i; // proved unblocked (the march's o, d, vmax)
          else need = true;
       }
       const unsigned long long m = __ballot(need);
@@ -976,6 +980,10 @@ MDH_DEV f3 shade_structured(const KScene &sc, const KProbes &pr, const MachineCf
                      // is >= 0, a probe with d <= best cannot win whatever its visibility.
                      if (!irrp && accw >= 0.0f && dot(-vd, -N) <= accw) vmax = 0.0f;
 #endif
+                     // a ray that segment_clear proves unblocked (behind the immediate outcomes: vmax <= 0, sd0 < EPS, sd0 >= vmax)
+                     // is not marched: vis stays 1
+                     if (0.0f < vmax && (!MDH_SHARE_FIRST_STEP || (!(sd0 < MDH_EPS) && sd0 < vmax)))
+                        if (segment_clear<PART>(sc, from_off, vd, vmax)) vmax = 0.0f;
                      bool first = MDH_SHARE_FIRST_STEP != 0;
                      PH_ADD(pt, 4);
 #ifdef MDH_ABL_NO_VIS
