@@ -332,6 +332,7 @@ struct mdh_renderer {
    hipStream_t own_stream = nullptr;
 #ifdef MDH_DIAG
    unsigned long long work[MDH_PASS_COUNT][4] = {{0}}; // g_work of the last run of each pass (mdh_diag_work)
+   int32_t variant[MDH_PASS_COUNT][2] = {{0}};          // run_pass's pfk and pow2 at the last run of each pass (mdh_diag_variant)
 #endif
    // the communicator of a sharded run (mdh_comm_init): one rank per process and GPU.  With it mdh_render runs the
    // exchange of the atlas slices itself, on the probe stream, between the probe passes.
@@ -1668,6 +1669,13 @@ static int window_slot(mdh_renderer *r, int rank, int world, unsigned **out)
    return MDH_OK;
 }
 
+// the census of the reference's rooms (MDH_PF_ROOM) among the scenes without partition or user-defined kinds (run_pass)
+static bool room_census(const mdh_renderer *r)
+{
+   return r->ks.n_axis > 0 && r->ks.gplane_count == 0 && r->ks.tcount[PK_SPHERE] == 1 && r->ks.tcount[PK_BOX] == 1 &&
+          r->ks.tcount[PK_TRIANGLE] == 0 && MDH_ROOM_VARIANTS;
+}
+
 // One pass on stream `st`.  The radiance pass reads the irradiance atlas of set `src` and writes the
 // radiance atlas of set `dst`; every other pass works on set `dst` (in place: src == dst == r->last).
 static int run_pass(mdh_renderer *r, int pass, hipStream_t st, int src, int dst, int fbix = -1)
@@ -1683,8 +1691,7 @@ static int run_pass(mdh_renderer *r, int pass, hipStream_t st, int src, int dst,
                   (r->part.enable != 0 && r->part.border_behavior != 0 && !has_custom ? MDH_PF_FALLBACK : 0);
    // ... bit 4 = the census of the reference's rooms (MDH_PF_ROOM, mdh_device.h: closest_primitive): every plane folded into
    // the axis offsets, one sphere, one box, nothing else, no partition -- the scan's loops as straight-line code
-   const bool room = pf == 0 && r->ks.n_axis > 0 && r->ks.gplane_count == 0 && r->ks.tcount[PK_SPHERE] == 1 && r->ks.tcount[PK_BOX] == 1 &&
-                     r->ks.tcount[PK_TRIANGLE] == 0 && MDH_ROOM_VARIANTS;
+   const bool room = pf == 0 && room_census(r);
    // ... bit 5 = the partition's small form with its census (MDH_PF_PSMALL, mdh_device.h: partitioning_closest_bits)
    const bool psmall = pf == MDH_PF_PART && r->ks.part_small && r->ks.part_tmask[PK_TRIANGLE] == 0 && r->ks.part_sp_pow2 && r->ks.part_cells < (1 << 24) && MDH_ROOM_VARIANTS;
    const int pfk = room ? MDH_PF_ROOM : (psmall ? (MDH_PF_PART | MDH_PF_PSMALL) : pf); // (the kernel variant by the scene's census)
@@ -1697,6 +1704,10 @@ static int run_pass(mdh_renderer *r, int pass, hipStream_t st, int src, int dst,
    const bool pow2 = is_pow2(r->probes.probe_count[0]) && is_pow2(r->probes.probe_count[1]) && is_pow2(r->probes.radiance_resolution) &&
                      is_pow2(r->probes.irradiance_resolution) && pcount < 65536 && pcount * rres * rres <= (1ll << 30) &&
                      pcount * ires * ires <= (1ll << 30);
+#ifdef MDH_DIAG
+   r->variant[pass][0] = pfk;
+   r->variant[pass][1] = pow2 ? 1 : 0;
+#endif
 #define MDH_LAUNCH_PF(KERNEL, GRID, BLOCK, LDS, ...)                                                      \
    do {                                                                                                   \
       switch (pfk) {                                                                                      \
@@ -3176,6 +3187,79 @@ extern "C" int32_t mdh_diag_work(mdh_renderer *r, int32_t pass, unsigned long lo
    if (!r || !out4 || pass < 0 || pass >= MDH_PASS_COUNT) return MDH_E_INVALID;
    memcpy(out4, r->work[pass], sizeof r->work[pass]);
    return MDH_OK;
+}
+// the kernel variant run_pass chose at the last run of `pass`: out[0] = pfk (MDH_PF_*: ROOM, PART | PSMALL, or the general
+// variant's PART / CUSTOM / FALLBACK bits), out[1] = 1 when the atlas addressing took the power-of-two variant
+extern "C" int32_t mdh_diag_variant(mdh_renderer *r, int32_t pass, int32_t *out2)
+{
+   if (!r || !out2 || pass < 0 || pass >= MDH_PASS_COUNT) return MDH_E_INVALID;
+   memcpy(out2, r->variant[pass], sizeof r->variant[pass]);
+   return MDH_OK;
+}
+// segment_clear_bound against the unmodified march (raycast_visibility) on the committed scene, one segment A + vd [0, vmax]
+// per lane.  A march is taken only where it must end (vmax <= 2^12: every step adds at least MDH_EPS, which exceeds half an ulp
+// of total there); other lanes report vis = -1.
+struct DiagSegArgs {
+   int n;
+   const float *A, *vd, *vmax;
+   int *clear;
+   float *vis;
+};
+template <int PART> __global__ __launch_bounds__(64) void k_diag_segments(KScene sc, DiagSegArgs a)
+{
+   stage_table(sc);
+   const int q = blockIdx.x * 64 + threadIdx.x;
+   if (q >= a.n) return;
+   const f3 A = F3(a.A[3 * q], a.A[3 * q + 1], a.A[3 * q + 2]), vd = F3(a.vd[3 * q], a.vd[3 * q + 1], a.vd[3 * q + 2]);
+   const float vmax = a.vmax[q];
+   a.clear[q] = segment_clear_bound<PART>(sc, A, vd, vmax) ? 1 : 0;
+   a.vis[q] = vmax <= 4096.0f ? raycast_visibility<PART>(sc, A, vd, vmax) : -1.0f;
+}
+// variant 0: the scan run_pass picks for the committed scene (MDH_PF_ROOM or the general scan 0); 1: the general scan forced.
+// thr_lim_out: H_VCLEAR and H_VCLEAR_LIM as commit_scene wrote them.  Scenes with a partition or user-defined kinds: MDH_E_STATE.
+extern "C" int32_t mdh_diag_segments(mdh_renderer *r, int32_t variant, int32_t n, const float *A, const float *vd, const float *vmax,
+                                     int32_t *clear_out, float *vis_out, float *thr_lim_out)
+{
+   if (!r || n < 0 || (n > 0 && (!A || !vd || !vmax || !clear_out || !vis_out)) || (variant != 0 && variant != 1)) return seterr(MDH_E_INVALID, "bad argument");
+   bool has_custom = false;
+   for (int k = 0; k < r->npk; ++k) has_custom = has_custom || r->pk[k].type == PK_CUSTOM;
+   for (int k = 0; k < r->nlk; ++k) has_custom = has_custom || r->lk[k].type == LK_CUSTOM;
+   if (r->part.enable != 0 || has_custom) return seterr(MDH_E_STATE, "mdh_diag_segments: the scan variants only (no partition, no user-defined kinds)");
+   HIP_TRY(hipSetDevice(r->device));
+   if (!r->query_stream) HIP_TRY(hipStreamCreateWithFlags(&r->query_stream, hipStreamNonBlocking));
+   hipStream_t qs = r->query_stream;
+   int rc = ensure_committed(r, qs);
+   if (rc != MDH_OK) return rc;
+   if (thr_lim_out) {
+      const int32_t *H = (const int32_t *)r->table_host.data();
+      thr_lim_out[0] = i_as_f(H[H_VCLEAR]);
+      thr_lim_out[1] = i_as_f(H[H_VCLEAR_LIM]);
+   }
+   if (n == 0) return MDH_OK;
+   const bool room = variant == 0 && room_census(r);
+   float *d = nullptr;
+   HIP_TRY(hipMalloc(&d, (size_t)n * 9 * sizeof(float)));
+   DiagSegArgs a;
+   a.n = n;
+   a.A = d; a.vd = d + 3 * (size_t)n; a.vmax = d + 6 * (size_t)n;
+   a.clear = (int *)(d + 7 * (size_t)n); a.vis = d + 8 * (size_t)n;
+   hipError_t e = hipMemcpyAsync(d, A, (size_t)n * 12, hipMemcpyHostToDevice, qs);
+   if (e == hipSuccess) e = hipMemcpyAsync(d + 3 * (size_t)n, vd, (size_t)n * 12, hipMemcpyHostToDevice, qs);
+   if (e == hipSuccess) e = hipMemcpyAsync(d + 6 * (size_t)n, vmax, (size_t)n * 4, hipMemcpyHostToDevice, qs);
+   if (e == hipSuccess && (rc = table_acquire(r, qs)) == MDH_OK) {
+      if (room) hipLaunchKernelGGL(k_diag_segments<MDH_PF_ROOM>, dim3((n + 63) / 64), dim3(64), lds_bytes(r), qs, ks_no_bits(r), a);
+      else hipLaunchKernelGGL(k_diag_segments<0>, dim3((n + 63) / 64), dim3(64), lds_bytes(r), qs, ks_no_bits(r), a);
+      e = hipGetLastError();
+      if (e == hipSuccess) rc = table_release(r, qs);
+   }
+   if (e == hipSuccess && rc == MDH_OK) e = hipMemcpyAsync(clear_out, a.clear, (size_t)n * 4, hipMemcpyDeviceToHost, qs);
+   if (e == hipSuccess && rc == MDH_OK) e = hipMemcpyAsync(vis_out, a.vis, (size_t)n * 4, hipMemcpyDeviceToHost, qs);
+   const hipError_t es = hipStreamSynchronize(qs);
+   if (e == hipSuccess) e = es;
+   const hipError_t ef = hipFree(d);
+   if (e == hipSuccess) e = ef;
+   HIP_TRY(e);
+   return rc;
 }
 // debug: read and reset the lane-utilisation counters of mdh_march.h
 extern "C" int32_t mdh_diag_read(unsigned long long *out16)

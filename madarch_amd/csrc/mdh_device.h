@@ -1319,9 +1319,10 @@ template <int PART> MDH_DEV float sdf_info(const KScene &sc, f3 x, int &index)
 #ifndef MDH_VIS_CLEAR
 #define MDH_VIS_CLEAR 1
 #endif
-template <int PART> MDH_DEV bool segment_clear(const KScene &sc, f3 A, f3 vd, float vmax)
+// segment_clear_bound: the bound itself, whatever MDH_VIS_CLEAR says (the diagnostic build's k_diag_segments, which holds it
+// against the march, calls it directly); meaningful for the built-in scan variants only (0, MDH_PF_ROOM).
+template <int PART> MDH_DEV bool segment_clear_bound(const KScene &sc, f3 A, f3 vd, float vmax)
 {
-   if (!MDH_VIS_CLEAR || (PART & (MDH_PF_PART | MDH_PF_CUSTOM))) return false;
    constexpr bool ROOM = (PART & MDH_PF_ROOM) != 0;
    const float thr = __int_as_float(hdr(H_VCLEAR)), lim = __int_as_float(hdr(H_VCLEAR_LIM));
    const f3 B = A + vd * vmax;
@@ -1364,6 +1365,11 @@ template <int PART> MDH_DEV bool segment_clear(const KScene &sc, f3 A, f3 vd, fl
       }
    }
    return ok;
+}
+template <int PART> MDH_DEV bool segment_clear(const KScene &sc, f3 A, f3 vd, float vmax)
+{
+   if (!MDH_VIS_CLEAR || (PART & (MDH_PF_PART | MDH_PF_CUSTOM))) return false;
+   return segment_clear_bound<PART>(sc, A, vd, vmax);
 }
 
 // ------------------------------------------------------------------------- raymarching

@@ -155,6 +155,46 @@ def dense_min(sc, A, vd, vmax, samples=2048):
     return out
 
 
+def segment_min64(sc, A, vd, vmax, iters=64):
+    """The minimum of the scene's SDF over each segment A + vd t, 0 <= t <= max(vmax, 0), in float64 with the float32 inputs
+    taken as exact: planes at the nearer endpoint, spheres at the exact closest point, boxes by golden-section search (each
+    primitive's SDF is convex along a line, so the search meets the minimum to ~0.618^iters of the segment's length)."""
+    A = np.asarray(A, np.float64); vd = np.asarray(vd, np.float64)
+    T = np.maximum(np.asarray(vmax, np.float64), 0.0)
+    B = A + vd * T[:, None]
+    out = np.full(len(A), float(sc["max_dist"]))
+    o = sc["off"].astype(np.float64)
+    for a in range(3):
+        out = np.minimum(out, np.minimum(np.minimum(A[:, a], B[:, a]) + o[2 * a], -np.maximum(A[:, a], B[:, a]) + o[2 * a + 1]))
+    for p in sc["gplanes"].astype(np.float64):
+        out = np.minimum(out, np.minimum(A @ p[:3] + p[3], B @ p[:3] + p[3]))
+    vv = np.einsum("ij,ij->i", vd, vd)
+    for s in sc["spheres"].astype(np.float64):
+        w = s[:3] - A
+        with np.errstate(invalid="ignore", divide="ignore"):
+            t = np.clip(np.where(vv > 0, np.einsum("ij,ij->i", w, vd) / vv, 0.0), 0.0, T)
+        out = np.minimum(out, np.linalg.norm(w - vd * t[:, None], axis=1) - s[3])
+    for b in sc["boxes"].astype(np.float64):
+        def f(t):
+            q = np.abs(A + vd * t[:, None] - b[:3]) - b[3:]
+            return np.linalg.norm(np.maximum(q, 0.0), axis=1) + np.minimum(q.max(axis=1), 0.0)
+        g = (np.sqrt(5.0) - 1.0) / 2.0
+        lo, hi = np.zeros_like(T), T.copy()
+        c, d = hi - g * (hi - lo), lo + g * (hi - lo)
+        fc, fd = f(c), f(d)
+        best = np.minimum(np.minimum(f(lo), f(hi)), np.minimum(fc, fd))
+        for _ in range(iters):
+            left = fc < fd  # the minimum lies in [lo, d]
+            hi = np.where(left, d, hi); lo = np.where(left, lo, c)
+            nc, nd = np.where(left, hi - g * (hi - lo), d), np.where(left, c, lo + g * (hi - lo))
+            fn = f(np.where(left, nc, nd))
+            fc, fd = np.where(left, fn, fd), np.where(left, fc, fn)
+            c, d = nc, nd
+            best = np.minimum(best, fn)
+        out = np.minimum(out, best)
+    return out
+
+
 def room_points(rng, n):
     """Points of the room's exposed surfaces, evenly by area, with their normals."""
     pts, nrm = [], []

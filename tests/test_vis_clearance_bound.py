@@ -1,5 +1,6 @@
 """The numpy restatement of segment_clear (scripts/vis_clearance.py): it never clears a segment on which the
-float32 march or a dense float32 walk meets an SDF value below EPS."""
+float32 march or a dense float32 walk meets an SDF value below EPS, nor one whose exact (fp64) minimum of the SDF lies
+below EPS + delta / 2 -- the bound's own rounding is a few 2^-22 lim, far below that margin."""
 import importlib.util
 import os
 
@@ -51,7 +52,7 @@ def _segments(rng, sc, n, scale):
 
 
 @pytest.mark.parametrize("seed", range(6))
-@pytest.mark.parametrize("scale", [1.0, 40.0])
+@pytest.mark.parametrize("scale", [1.0, 40.0, 300.0])
 def test_bound_never_clears_a_blocked_segment(seed, scale):
     rng = np.random.default_rng(1000 + seed)
     sc = _scene(rng, scale)
@@ -63,6 +64,9 @@ def test_bound_never_clears_a_blocked_segment(seed, scale):
     assert clear.any() and not clear.all()  # the segments straddle the bound
     Ac, vdc, vmc = A[clear], vd[clear], vmax[clear]
     assert (vc.dense_min(sc, Ac, vdc, vmc, samples=1024) >= vc.EPS).all()
+    delta = np.ldexp(1.0 + float(lim), -12)
+    m64 = vc.segment_min64(sc, Ac, vdc, vmc)
+    assert (m64 >= float(vc.EPS) + delta / 2).all(), float(m64.min() - float(vc.EPS) - delta / 2)
     vis, steps, mins = vc.march(sc, Ac, vdc, vmc, vc.sdf(sc, Ac))
     assert vis.all() and (mins >= vc.EPS).all()
     assert keep[clear].all()
@@ -97,3 +101,5 @@ def test_headline_room_clears_most_march_steps():
     vis, steps, _ = vc.march(sc, A, vd, vmax, sd0)
     assert not (clear & ~vis).any()
     assert steps[clear].sum() > 0.5 * steps.sum()
+    delta = np.ldexp(1.0 + float(lim), -12)
+    assert (vc.segment_min64(sc, A[clear], vd[clear], vmax[clear]) >= float(vc.EPS) + delta / 2).all()
