@@ -264,7 +264,15 @@ enum {
     * rank's scattered tiles of a sharded frame measured no faster).  Default 2560
     * (half the slots of an MI355X at five wavefronts per SIMD); 0 = every tile one wavefront.  Launches of 2 048 tiles and
     * more (MDH_OPT_SCREEN_ORDER's) are never split. */
-   MDH_OPT_SCREEN_SPLIT = 18
+   MDH_OPT_SCREEN_SPLIT = 18,
+   /* Where the kernels read a scene's geometry from -- no effect on any result.  A scene table that fits a workgroup's LDS
+    * beside the kernels' own rows (every scene of the reference's first three examples) is staged there whole: residency 0.
+    * A larger one (about 860 triangles and up: the obj_mesh example's 1000) keeps its geometry and material ids in device
+    * memory, read through L2, and only the header, lights, materials and decode table in LDS: residency 1.  Reading the
+    * option gives the residency of the scene as committed (pending edits are committed first).  Setting 1 FORCES residency 1
+    * for a scene that would fit (tests and A/B runs; MDH_E_INVALID at the next commit for scenes with user-defined kinds,
+    * which always live in LDS); setting 0 returns to the choice by size. */
+   MDH_OPT_TABLE_RESIDENCY = 19
 };
 
 /* passes of Renderers.Render (madarch-renderers.adb:302-321) */

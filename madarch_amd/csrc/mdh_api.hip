@@ -275,6 +275,8 @@ struct mdh_renderer {
    int last = 0;
    int opt_overlap = 2;
    int opt_irr_all = 1; // MDH_OPT_IRRADIANCE_ALL
+   int opt_residency = 0; // MDH_OPT_TABLE_RESIDENCY as set: 1 = global residency forced, 0 = chosen by the table's size (commit_scene)
+   int residency = 0;     // ... of the committed scene: 0 = the whole table in LDS, 1 = geometry and material ids read from its image in memory
    int opt_jit = 1; // user-defined kinds: 1 = compile the MDH_X programs with hiprtc, 0 = interpret them (MDH_OPT_JIT)
    std::string jit_kinds; // mdh_jit_kinds.h of this scene (generated once)
    hipStream_t probe_stream = nullptr;   // radiance + irradiance passes of pipelined frames
@@ -626,6 +628,7 @@ static int commit_scene(mdh_renderer *r, hipStream_t up)
          t.push_back(mk4(m[0], m[1], m[2], m[3]));
       }
    }
+   const size_t geo_begin = H_INTS / 4, geo_end = t.size(); // geometry, general planes, programs, material ids: what global residency leaves in memory
    for (int k = 0; k < r->nlk; ++k) {
       const Kind &kd = r->lk[k];
       int n = rd_i(r, kd.count_off);
@@ -680,18 +683,46 @@ static int commit_scene(mdh_renderer *r, hipStream_t up)
    s.u8_slot = (int)t.size();
    for (int k = 0; k < 256; k += 4) t.push_back(mk4((float)k / 255.0f, (float)(k + 1) / 255.0f, (float)(k + 2) / 255.0f, (float)(k + 3) / 255.0f));
 #endif
+   // RESIDENCY (mdh_device.h: Geo).  A table that fits the LDS budget is staged whole, as it is laid out above.  One that does
+   // not -- or any, under MDH_OPT_TABLE_RESIDENCY 1 -- is laid out with its resident part first: header ints, lights, materials,
+   // the k / 255 table, then everything the kernels read from the image in memory; every workgroup stages the first
+   // table_f4 float4 only.  User-defined kinds interpret their instances out of LDS: they keep the whole table there.
+   // (the march kernels park MDH_PARK_DWORDS floats per thread behind the table, lds_bytes_march)
+   {
+      const size_t park = (size_t)MDH_SCR_PARK_ROWS * MDH_BLOCK * sizeof(float), budget = 64 * 1024;
+      const size_t n_geo = geo_end - geo_begin, n_res = t.size() - n_geo;
+      bool has_custom = false;
+      for (int k = 0; k < r->npk; ++k) has_custom = has_custom || r->pk[k].type == PK_CUSTOM;
+      for (int k = 0; k < r->nlk; ++k) has_custom = has_custom || r->lk[k].type == LK_CUSTOM;
+      const bool fits = (t.size() + (size_t)part_bits_f4(r)) * 16 + park <= budget;
+      if (fits && r->opt_residency == 1 && has_custom)
+         return seterr(MDH_E_INVALID, "MDH_OPT_TABLE_RESIDENCY 1: scenes with user-defined kinds keep their table in LDS");
+      if (!fits && (has_custom || (n_res + (size_t)part_bits_f4(r)) * 16 + park > budget))
+         return seterr(MDH_E_INVALID, "scene tables exceed the 64 KiB LDS budget of a workgroup");
+      r->residency = !fits || r->opt_residency == 1 ? 1 : 0;
+      s.table_f4 = (int)t.size();
+      if (r->residency) {
+         std::rotate(t.begin() + geo_begin, t.begin() + geo_end, t.end());
+         const int up = (int)(n_res - geo_begin), down = (int)n_geo; // float4 the memory part moves up, the resident part down
+         for (int k = 0; k < r->npk; ++k) { H[H_KSLOT + k] += up; H[H_KMAT + k] += 4 * up; }
+         for (int ty = 0; ty < 4; ++ty) if (s.tslot[ty]) s.tslot[ty] += up; // (0: no kind of that type)
+         s.gplane_slot += up;
+         for (int k = 0; k < r->nlk; ++k) H[H_LSLOT + k] -= down;
+         s.mat_slot -= down;
+         if (s.u8_slot >= 0) s.u8_slot -= down;
+         H[H_VCLEAR] = 0; // (segment_clear reads its geometry from LDS: off, as it is for every scene with triangles or a partition)
+         s.table_f4 = (int)n_res;
+         t.push_back(mk4(0, 0, 0, 0)); t.push_back(mk4(0, 0, 0, 0)); // (the first-sphere / first-box reads of a scene without any stay inside the image)
+      }
+   }
    for (int k = 0; k < r->npk; ++k) { H[H_KQUAD + 4 * k] = H[H_KTYPE + k]; H[H_KQUAD + 4 * k + 1] = H[H_KSLOT + k]; H[H_KQUAD + 4 * k + 2] = H[H_KBASE + k]; H[H_KQUAD + 4 * k + 3] = H[H_KMAX + k]; }
    memcpy(t.data(), H, sizeof H);
-   s.table_f4 = (int)t.size();
    { // (MDH_SDF_SGPR: the words closest_primitive would read from the table; with a count of 0 they belong to the next kind and are not used)
       const size_t ss = (size_t)s.tslot[PK_SPHERE], sb = (size_t)s.tslot[PK_BOX];
       const float4 z = mk4(0, 0, 0, 0), a = ss < t.size() ? t[ss] : z, b0 = sb < t.size() ? t[sb] : z, b1 = sb + 1 < t.size() ? t[sb + 1] : z;
       const float fs[4] = {a.x, a.y, a.z, a.w}, fb[8] = {b0.x, b0.y, b0.z, b0.w, b1.x, b1.y, b1.z, b1.w};
       memcpy(s.first_sphere, fs, sizeof fs); memcpy(s.first_box, fb, sizeof fb);
    }
-   // (the march kernels park MDH_PARK_DWORDS floats per thread behind the table, lds_bytes_march)
-   if ((size_t)(s.table_f4 + part_bits_f4(r)) * 16 + (size_t)MDH_SCR_PARK_ROWS * MDH_BLOCK * sizeof(float) > 64 * 1024)
-      return seterr(MDH_E_INVALID, "scene tables exceed the 64 KiB LDS budget of a workgroup");
    if (t.size() > r->table_cap) { // grow the whole ring (rare: the table only grows with the primitive counts)
       { int dr = drain_streams(r); if (dr != MDH_OK) return dr; }
       r->table_cap = t.size() + 256;
@@ -1081,6 +1112,11 @@ extern "C" int32_t mdh_set_option(mdh_renderer *r, int32_t option, int32_t value
    case MDH_OPT_SCREEN_ORDER: r->opt_scr_order = value ? 1 : 0; r->scr_order_cur = -1; break;
    case MDH_OPT_SCREEN_SPLIT: if (value < 0) return seterr(MDH_E_INVALID, "MDH_OPT_SCREEN_SPLIT: a number of wavefronts"); r->opt_scr_split = value; break;
    case MDH_OPT_NUMERICS: if (value != (MDH_FAST_NUMERICS ? 1 : (MDH_HYBRID_NUMERICS ? 2 : 0))) return seterr(MDH_E_STATE, "the numerics are a property of the library build (make fast builds the experiment)"); break;
+   case MDH_OPT_TABLE_RESIDENCY:
+      if (value != 0 && value != 1) return seterr(MDH_E_INVALID, "table residency is 0 (by size) or 1 (global, forced)");
+      if (r->in_frame) return seterr(MDH_E_STATE, "a frame is open");
+      if (value != r->opt_residency) { r->opt_residency = value; r->table_dirty = true; } // (the next commit lays the table out again)
+      break;
    case MDH_OPT_RADIANCE_MIPS: {
       const int res = r->probes.radiance_resolution;
       if (value && (res & (res - 1)) != 0) return seterr(MDH_E_INVALID, "radiance mips need a power-of-two radiance resolution");
@@ -1120,6 +1156,15 @@ extern "C" int32_t mdh_get_option(mdh_renderer *r, int32_t option, int32_t *valu
    case MDH_OPT_SCREEN_SPLIT: *value = r->opt_scr_split; break;
    case MDH_OPT_NUMERICS: *value = MDH_FAST_NUMERICS ? 1 : (MDH_HYBRID_NUMERICS ? 2 : 0); break; // 0 exact (shipped), 1 / 2 the labelled experiments
    case MDH_OPT_RADIANCE_MIPS: *value = r->opt_mips; break;
+   case MDH_OPT_TABLE_RESIDENCY: { // of the committed scene: edits since the last commit are committed first
+      if (r->table_dirty && !r->in_frame) {
+         HIP_TRY(hipSetDevice(r->device));
+         const int rc = commit_scene(r, r->stream);
+         if (rc != MDH_OK) return rc;
+      }
+      *value = r->residency;
+      break;
+   }
    default: return seterr(MDH_E_INVALID, "unknown option");
    }
    return MDH_OK;
@@ -1546,6 +1591,19 @@ template <typename Args> static int jit_launch(hipFunction_t f, int blocks, int 
    return MDH_OK;
 }
 
+// The kernels of global residency (MDH_PF_GTAB, mdh_device.h: Geo) are named in ONE function at the end of this file and
+// launched through the pointers it returns: a kernel template is instantiated where it is first named, and the code object
+// keeps that order -- named here and there among the others they would move every existing kernel to another address, and
+// the passes of frames in flight share their CUs' instruction caches (measured: the same kernels at other addresses, each
+// as fast by itself, the headline with frames in flight 0.5 % slower).  Behind everything else they move nothing.
+enum { GK_k_visibility, GK_k_scat_march, GK_k_scattering, GK_k_radiance, GK_k_screen, GK_k_partition_build, GK_k_eval_distance };
+static const void *gtab_kernel(int family, int pfk, int x = 0, int y = 0, int z = 0); // x, y, z: the family's other template arguments
+template <typename... A> static void launch_kernel_ptr(const void *kernel, dim3 grid, dim3 block, size_t lds, hipStream_t st, A... a)
+{
+   void *args[] = {(void *)&a...}; // (by value, in the kernel's parameter types: the call sites pass exactly those)
+   (void)hipLaunchKernel(kernel, grid, block, args, lds, st); // (errors surface in hipGetLastError, as after hipLaunchKernelGGL)
+}
+
 // Update_Partitioning (renderers.adb:757-775): all three methods build the table on the device
 extern "C" int32_t mdh_update_partitioning(mdh_renderer *r, int32_t method)
 {
@@ -1595,7 +1653,8 @@ extern "C" int32_t mdh_update_partitioning(mdh_renderer *r, int32_t method)
    HIP_TRY(hipMemcpyAsync(r->d_part_ring[ns], r->d_part_ring[r->part_slot], total * 4, hipMemcpyDeviceToDevice, up));
    HIP_TRY(hipMemsetAsync(r->d_warn, 0, 4, up));
    if (cells > 0) {
-      hipLaunchKernelGGL(k_partition_build, dim3(cells), dim3(64), lds_bytes(r), up, ks_no_bits(r), a); // one wavefront per cell
+      if (r->residency) launch_kernel_ptr(gtab_kernel(GK_k_partition_build, MDH_PF_GTAB), dim3(cells), dim3(64), lds_bytes(r), up, ks_no_bits(r), a);
+      else hipLaunchKernelGGL(k_partition_build, dim3(cells), dim3(64), lds_bytes(r), up, ks_no_bits(r), a); // one wavefront per cell
       HIP_TRY(hipGetLastError());
    }
    // the lists once more as bits, for every cell (cells the builder left alone keep their lists, and so their bits)
@@ -1691,10 +1750,13 @@ static int run_pass(mdh_renderer *r, int pass, hipStream_t st, int src, int dst,
                   (r->part.enable != 0 && r->part.border_behavior != 0 && !has_custom ? MDH_PF_FALLBACK : 0);
    // ... bit 4 = the census of the reference's rooms (MDH_PF_ROOM, mdh_device.h: closest_primitive): every plane folded into
    // the axis offsets, one sphere, one box, nothing else, no partition -- the scan's loops as straight-line code
-   const bool room = pf == 0 && room_census(r);
+   // ... bit 6 = global residency of the scene table (MDH_PF_GTAB, mdh_device.h: Geo; commit_scene chose it): the general
+   // variants only -- no census, no power-of-two atlases, never user-defined kinds
+   const bool gtab = r->residency != 0;
+   const bool room = pf == 0 && room_census(r) && !gtab;
    // ... bit 5 = the partition's small form with its census (MDH_PF_PSMALL, mdh_device.h: partitioning_closest_bits)
-   const bool psmall = pf == MDH_PF_PART && r->ks.part_small && r->ks.part_tmask[PK_TRIANGLE] == 0 && r->ks.part_sp_pow2 && r->ks.part_cells < (1 << 24) && MDH_ROOM_VARIANTS;
-   const int pfk = room ? MDH_PF_ROOM : (psmall ? (MDH_PF_PART | MDH_PF_PSMALL) : pf); // (the kernel variant by the scene's census)
+   const bool psmall = pf == MDH_PF_PART && r->ks.part_small && r->ks.part_tmask[PK_TRIANGLE] == 0 && r->ks.part_sp_pow2 && r->ks.part_cells < (1 << 24) && MDH_ROOM_VARIANTS && !gtab;
+   const int pfk = gtab ? (pf | MDH_PF_GTAB) : room ? MDH_PF_ROOM : (psmall ? (MDH_PF_PART | MDH_PF_PSMALL) : pf); // (the kernel variant by the scene's census)
    // the probe-sampling kernels (radiance, mode-0 screen) have a variant for atlases whose every dimension is a power of two
    auto is_pow2 = [](int v) { return v > 0 && (v & (v - 1)) == 0; };
    // (... and small enough for what those variants assume besides: probe ids within 24-bit products, RGBA8 byte offsets
@@ -1717,6 +1779,7 @@ static int run_pass(mdh_renderer *r, int pass, hipStream_t st, int src, int dst,
       case 1: hipLaunchKernelGGL(KERNEL<1>, GRID, BLOCK, LDS, st, __VA_ARGS__); break;                     \
       case 2: hipLaunchKernelGGL(KERNEL<2>, GRID, BLOCK, LDS, st, __VA_ARGS__); break;                     \
       case 9: hipLaunchKernelGGL(KERNEL<9>, GRID, BLOCK, LDS, st, __VA_ARGS__); break;                     \
+      case MDH_PF_GTAB: case MDH_PF_GTAB | 1: case MDH_PF_GTAB | 9: launch_kernel_ptr(gtab_kernel(GK_##KERNEL, pfk), GRID, BLOCK, LDS, st, __VA_ARGS__); break; \
       default: hipLaunchKernelGGL(KERNEL<3>, GRID, BLOCK, LDS, st, __VA_ARGS__); break;                    \
       }                                                                                                   \
    } while (0)
@@ -1835,7 +1898,7 @@ static int run_pass(mdh_renderer *r, int pass, hipStream_t st, int src, int dst,
                   hipLaunchKernelGGL((k_radiance<MDH_PF_POW2, false, 2>), dim3(blocks), dim3(MDH_BLOCK), lds, st, r->ks, pr, rad_first_round(r, (const void *)(k_radiance<MDH_PF_POW2, false, 2>), nullptr, lds, blocks), ro);
                }
             } else
-            if (pow2 && !has_custom) {
+            if (pow2 && !has_custom && !gtab) {
                if (pf & MDH_PF_FALLBACK) MDH_LAUNCH_RAD(MDH_PF_PART | MDH_PF_POW2 | MDH_PF_FALLBACK);
                else if (psmall) MDH_LAUNCH_RAD(MDH_PF_PART | MDH_PF_POW2 | MDH_PF_PSMALL);
                else if (pf & MDH_PF_PART) MDH_LAUNCH_RAD(MDH_PF_PART | MDH_PF_POW2);
@@ -1849,6 +1912,11 @@ static int run_pass(mdh_renderer *r, int pass, hipStream_t st, int src, int dst,
                case 1: MDH_LAUNCH_RAD(1); break;
                case 2: MDH_LAUNCH_RAD(2); break;
                case 9: MDH_LAUNCH_RAD(9); break;
+               case MDH_PF_GTAB: case MDH_PF_GTAB | 1: case MDH_PF_GTAB | 9: {
+                  const void *k = gtab_kernel(GK_k_radiance, pfk, rad_small_launch(r) ? 1 : 0);
+                  launch_kernel_ptr(k, dim3(blocks), dim3(MDH_BLOCK), lds, st, r->ks, pr, rad_first_round(r, k, nullptr, lds, blocks), ro);
+                  break;
+               }
                default: MDH_LAUNCH_RAD(3); break;
                }
 #undef MDH_LAUNCH_RAD_
@@ -2042,6 +2110,11 @@ static int run_pass(mdh_renderer *r, int pass, hipStream_t st, int src, int dst,
          case 1: launch_screen_m<1>(r, st, pr, vol, cam, a, blocks, pow2); break;
          case 2: launch_screen_m<2>(r, st, pr, vol, cam, a, blocks, pow2); break;
          case 9: launch_screen_m<9>(r, st, pr, vol, cam, a, blocks, pow2); break;
+         case MDH_PF_GTAB: case MDH_PF_GTAB | 1: case MDH_PF_GTAB | 9: { // (launch_screen_m's choice among the general variants)
+            const bool alt = r->opt_mode == 0 && (a.spec_mode == 1 || a.spec_mode == 3 || (a.spec_mode == 2 && pr.rad_mips));
+            launch_kernel_ptr(gtab_kernel(GK_k_screen, pfk, r->opt_mode, r->opt_gbuffer ? 1 : 0, alt ? 1 : 0), dim3(blocks), dim3(MDH_BLOCK), lds_bytes_screen(r), st, r->ks, pr, vol, cam, a);
+            break;
+         }
          default: launch_screen_m<3>(r, st, pr, vol, cam, a, blocks, pow2); break;
          }
       }
@@ -3101,7 +3174,8 @@ extern "C" int32_t mdh_eval_distance_to(mdh_renderer *r, int32_t n, const float 
    for (int i = 0; i < MDH_MAX_KINDS; ++i) { a.kinds[i] = i < n_kinds ? kind_ixs[i] : 0; a.host_count[i] = r->host_count[i]; }
    a.pts = d_pts; a.normals = d_n; a.dist = d_d;
    if ((rc = table_acquire(r, qs)) != MDH_OK) return rc;
-   if (r->opt_ada_div) hipLaunchKernelGGL(k_eval_distance<true>, dim3((n + 63) / 64), dim3(64), lds_bytes(r), qs, ks_no_bits(r), a);
+   if (r->residency) launch_kernel_ptr(gtab_kernel(GK_k_eval_distance, MDH_PF_GTAB, r->opt_ada_div), dim3((n + 63) / 64), dim3(64), lds_bytes(r), qs, ks_no_bits(r), a);
+   else if (r->opt_ada_div) hipLaunchKernelGGL(k_eval_distance<true>, dim3((n + 63) / 64), dim3(64), lds_bytes(r), qs, ks_no_bits(r), a);
    else hipLaunchKernelGGL(k_eval_distance<false>, dim3((n + 63) / 64), dim3(64), lds_bytes(r), qs, ks_no_bits(r), a);
    HIP_TRY(hipGetLastError());
    if ((rc = table_release(r, qs)) != MDH_OK) return rc;
@@ -3230,6 +3304,7 @@ extern "C" int32_t mdh_diag_segments(mdh_renderer *r, int32_t variant, int32_t n
    hipStream_t qs = r->query_stream;
    int rc = ensure_committed(r, qs);
    if (rc != MDH_OK) return rc;
+   if (r->residency) return seterr(MDH_E_STATE, "mdh_diag_segments: the bound reads the scene table in LDS (MDH_OPT_TABLE_RESIDENCY 0 only)");
    if (thr_lim_out) {
       const int32_t *H = (const int32_t *)r->table_host.data();
       thr_lim_out[0] = i_as_f(H[H_VCLEAR]);
@@ -3288,3 +3363,34 @@ extern "C" int32_t mdh_diag_waves(unsigned long long *out, int32_t n_waves)
    return MDH_OK;
 }
 #endif
+
+// ------------------------------------------------------------------ the kernels of global residency
+// (the last function of the file: see the declaration of gtab_kernel)
+template <int PF> static const void *gtab_kernel_pf(int family, int x, int y, int z)
+{
+   switch (family) {
+   case GK_k_visibility: return (const void *)k_visibility<PF>;
+#if MDH_SCAT_SPLIT
+   case GK_k_scat_march: return (const void *)k_scat_march<PF>;
+#else
+   case GK_k_scattering: return (const void *)k_scattering<PF>;
+#endif
+   case GK_k_radiance: return x ? (const void *)k_radiance<PF, true> : (const void *)k_radiance<PF, false>;
+   case GK_k_screen: // x = screen mode, y = geometry buffer, z = the variant of the optional specular bodies (mode 0)
+      if (x == 0 && z) return y ? (const void *)k_screen<PF, 0, true, true> : (const void *)k_screen<PF, 0, false, true>;
+      if (x == 0) return y ? (const void *)k_screen<PF, 0, true> : (const void *)k_screen<PF, 0, false>;
+      if (x == 1) return y ? (const void *)k_screen<PF, 1, true> : (const void *)k_screen<PF, 1, false>;
+      return y ? (const void *)k_screen<PF, 2, true> : (const void *)k_screen<PF, 2, false>;
+   case GK_k_partition_build: return (const void *)k_partition_build_gtab<>;
+   case GK_k_eval_distance: return x ? (const void *)k_eval_distance_gtab<true> : (const void *)k_eval_distance_gtab<false>;
+   default: return nullptr;
+   }
+}
+static const void *gtab_kernel(int family, int pfk, int x, int y, int z)
+{
+   switch (pfk) {
+   case MDH_PF_GTAB | 1: return gtab_kernel_pf<MDH_PF_GTAB | 1>(family, x, y, z);
+   case MDH_PF_GTAB | 9: return gtab_kernel_pf<MDH_PF_GTAB | 9>(family, x, y, z);
+   default: return gtab_kernel_pf<MDH_PF_GTAB>(family, x, y, z);
+   }
+}

@@ -530,6 +530,33 @@ MDH_DEV int4 hdr4(int i)
    return make_int4(__builtin_amdgcn_readfirstlane(v.x), __builtin_amdgcn_readfirstlane(v.y), __builtin_amdgcn_readfirstlane(v.z), __builtin_amdgcn_readfirstlane(v.w));
 }
 
+// Residency of the scene table (MDH_PF_GTAB below; DESIGN.md "Scenes larger than LDS").  A kernel variant reads the
+// geometry blocks and the material ids of the built-in kinds either from the LDS copy every workgroup stages (Geo<false>:
+// what every reader did before there was a choice -- the same code) or from the table's image in device memory
+// (Geo<true>): there stage_table() has staged only the RESIDENT part, the prefix of KScene::table_f4 float4 that holds the
+// header ints, the lights, the materials and the k / 255 table, and slots behind it exist in memory alone.  Slots and int
+// indices mean the same in both: the image is the table.  A per-lane slot is a per-lane global_load_dwordx4 (lanes in one
+// partition cell share their lines); a wave-uniform slot goes through uni<> so that it is a scalar load.
+typedef float f4v __attribute__((ext_vector_type(4)));
+typedef const int __attribute__((address_space(1))) *GeoInts;
+struct GeoImage { // the image, indexed like the LDS table (float4 is a class: it is not loaded through an address-space pointer, f4v is)
+   const f4v __attribute__((address_space(1))) *p;
+   __device__ __forceinline__ float4 operator[](int slot) const { const f4v v = p[slot]; return make_float4(v.x, v.y, v.z, v.w); }
+   __device__ __forceinline__ GeoImage operator+(int slot) const { GeoImage g; g.p = p + slot; return g; }
+};
+template <bool GTAB> struct Geo {
+   typedef const float4 *F4;
+   static __device__ __forceinline__ F4 f4(const KScene &) { return s_tab; }
+   static __device__ __forceinline__ int mat_id(const KScene &, int int_index) { return tab_int(int_index); }
+};
+template <> struct Geo<true> {
+   typedef GeoImage F4;
+   static __device__ __forceinline__ F4 f4(const KScene &sc) { GeoImage g; g.p = (const f4v __attribute__((address_space(1))) *)sc.table; return g; }
+   static __device__ __forceinline__ int mat_id(const KScene &sc, int int_index) { return ((GeoInts)sc.table)[int_index]; }
+};
+// a slot every lane of the wavefront agrees on, said so to the compiler (global residency: a scalar load instead of 64 equal addresses)
+template <bool GTAB> MDH_DEV int uni(int slot) { return GTAB ? __builtin_amdgcn_readfirstlane(slot) : slot; }
+
 // ---------------------------------------------------------------------------- the SDFs
 // madarch-primitives-spheres.ads:13-14
 MDH_DEV float sd_sphere(float4 a, f3 p) { return length(xyz(a) - p) - a.w; }
@@ -709,13 +736,14 @@ MDH_DEV f3 xlight_sample(int k, int i, f3 pos, f3 normal, f3 dir, float dist)
 }
 
 // dist_to_<Kind>(prims[i], x); `slot` = first float4 of the primitive (any lane value)
-MDH_DEV float prim_dist(int type, int slot, f3 x)
+// (`tab`: Geo<>::f4 -- the LDS table or its image in memory)
+template <typename TAB> MDH_DEV float prim_dist(TAB tab, int type, int slot, f3 x)
 {
    switch (type) {
-   case PK_SPHERE: return sd_sphere(s_tab[slot], x);
-   case PK_PLANE: return sd_plane(s_tab[slot], x);
-   case PK_BOX: return sd_box(s_tab[slot], s_tab[slot + 1], x);
-   default: return sd_triangle<false>(xyz(s_tab[slot]), xyz(s_tab[slot + 1]), xyz(s_tab[slot + 2]), x);
+   case PK_SPHERE: return sd_sphere(tab[slot], x);
+   case PK_PLANE: return sd_plane(tab[slot], x);
+   case PK_BOX: return sd_box(tab[slot], tab[slot + 1], x);
+   default: return sd_triangle<false>(xyz(tab[slot]), xyz(tab[slot + 1]), xyz(tab[slot + 2]), x);
    }
 }
 
@@ -767,8 +795,9 @@ MDH_DEV float prim_dist(int type, int slot, f3 x)
 // reads them from LDS once (MDH_SDF_REGS) instead of once per evaluation.  (With a count of 0 the words
 // belong to the next kind and are not used.)
 struct SdfRegs { float4 s, b0, b1; };
-MDH_DEV SdfRegs sdf_regs(const KScene &sc)
+template <bool GTAB = false> MDH_DEV SdfRegs sdf_regs(const KScene &sc)
 {
+   const typename Geo<GTAB>::F4 s_tab = Geo<GTAB>::f4(sc); // (shadows the LDS table: global residency reads the image)
    SdfRegs r;
 #if MDH_SDF_SGPR
    r.s = r.b0 = r.b1 = make_float4(0.0f, 0.0f, 0.0f, 0.0f); // (unused: closest_primitive takes the kernel arguments)
@@ -783,8 +812,9 @@ MDH_DEV SdfRegs sdf_regs(const KScene &sc)
 // configs 3, 4, 5).  The same operations on the same operands; what goes is what a count known only at run time costs at every
 // march step -- the loops' scalar bookkeeping and branches around bodies that run once or never -- and the registers their
 // induction state holds: 96 -> 80 VGPRs in the screen kernel, six wavefronts per SIMD without a further spill.
-template <bool CUSTOM, bool ROOM = false> MDH_DEV float closest_primitive(const KScene &sc, f3 x, const SdfRegs *regs = nullptr)
+template <bool CUSTOM, bool ROOM = false, bool GTAB = false> MDH_DEV float closest_primitive(const KScene &sc, f3 x, const SdfRegs *regs = nullptr)
 {
+   const typename Geo<GTAB>::F4 s_tab = Geo<GTAB>::f4(sc); // (shadows the LDS table: global residency reads the image; every index below is wave-uniform)
    float closest = sc.max_dist;
 #if MDH_SDF_SGPR
    const float4 pf_s = make_float4(sc.first_sphere[0], sc.first_sphere[1], sc.first_sphere[2], sc.first_sphere[3]);
@@ -821,7 +851,7 @@ template <bool CUSTOM, bool ROOM = false> MDH_DEV float closest_primitive(const 
    {
       const int n = ROOM ? 0 : sc.gplane_count, s0 = sc.gplane_slot;
 #pragma unroll MDH_SDF_UNROLL
-      for (int i = 0; i < n; ++i) closest = min_(closest, sd_plane(s_tab[s0 + i], x)); // (unrolled in pairs: v_min3_f32)
+      for (int i = 0; i < n; ++i) closest = min_(closest, sd_plane(s_tab[uni<GTAB>(s0 + i)], x)); // (unrolled in pairs: v_min3_f32)
    }
    {
       const int n = ROOM ? 1 : sc.tcount[PK_SPHERE], s0 = sc.tslot[PK_SPHERE];
@@ -836,10 +866,10 @@ template <bool CUSTOM, bool ROOM = false> MDH_DEV float closest_primitive(const 
 #if MDH_SDF_PREFETCH
       if (n > 0) MDH_SPHERE_STEP(pf_s);
 #pragma unroll 1
-      for (int i = 1; i < n; ++i) MDH_SPHERE_STEP(s_tab[s0 + i]);
+      for (int i = 1; i < n; ++i) MDH_SPHERE_STEP(s_tab[uni<GTAB>(s0 + i)]);
 #else
 #pragma unroll 1
-      for (int i = 0; i < n; ++i) MDH_SPHERE_STEP(s_tab[s0 + i]);
+      for (int i = 0; i < n; ++i) MDH_SPHERE_STEP(s_tab[uni<GTAB>(s0 + i)]);
 #endif
 #undef MDH_SPHERE_STEP
    }
@@ -856,10 +886,10 @@ template <bool CUSTOM, bool ROOM = false> MDH_DEV float closest_primitive(const 
 #if MDH_SDF_PREFETCH
       if (n > 0) MDH_BOX_STEP(pf_b0, pf_b1);
 #pragma unroll 1
-      for (int i = 1; i < n; ++i) MDH_BOX_STEP(s_tab[s0 + 2 * i], s_tab[s0 + 2 * i + 1]);
+      for (int i = 1; i < n; ++i) MDH_BOX_STEP(s_tab[uni<GTAB>(s0 + 2 * i)], s_tab[uni<GTAB>(s0 + 2 * i + 1)]);
 #else
 #pragma unroll 1
-      for (int i = 0; i < n; ++i) MDH_BOX_STEP(s_tab[s0 + 2 * i], s_tab[s0 + 2 * i + 1]);
+      for (int i = 0; i < n; ++i) MDH_BOX_STEP(s_tab[uni<GTAB>(s0 + 2 * i)], s_tab[uni<GTAB>(s0 + 2 * i + 1)]);
 #endif
 #undef MDH_BOX_STEP
    }
@@ -867,7 +897,7 @@ template <bool CUSTOM, bool ROOM = false> MDH_DEV float closest_primitive(const 
       const int n = ROOM ? 0 : sc.tcount[PK_TRIANGLE], s0 = sc.tslot[PK_TRIANGLE];
 #pragma unroll 1
       for (int i = 0; i < n; ++i)
-         closest = min_raw(closest, sd_triangle<false>(xyz(s_tab[s0 + 3 * i]), xyz(s_tab[s0 + 3 * i + 1]), xyz(s_tab[s0 + 3 * i + 2]), x));
+         closest = min_raw(closest, sd_triangle<false>(xyz(s_tab[uni<GTAB>(s0 + 3 * i)]), xyz(s_tab[uni<GTAB>(s0 + 3 * i + 1)]), xyz(s_tab[uni<GTAB>(s0 + 3 * i + 2)]), x));
    }
 #ifdef MDH_JIT_CLOSEST_ALL
    if (CUSTOM) closest = jit_closest_all(x, closest); // (compiled: one loop per kind, roots culled like the built-in spheres')
@@ -887,8 +917,9 @@ template <bool CUSTOM, bool ROOM = false> MDH_DEV float closest_primitive(const 
 }
 // closest_primitive_info (scenes.adb:631-674): kinds in SCENE order (the arg-min keeps the
 // first of equal distances).  Only evaluated at hit points, so compact rather than fast.
-template <bool CUSTOM> MDH_DEV float closest_primitive_info(const KScene &sc, f3 x, int &index)
+template <bool CUSTOM, bool GTAB = false> MDH_DEV float closest_primitive_info(const KScene &sc, f3 x, int &index)
 {
+   const typename Geo<GTAB>::F4 s_tab = Geo<GTAB>::f4(sc); // (shadows the LDS table, as in closest_primitive)
    float closest = sc.max_dist;
 #if MDH_FAST_INFO
    // The same arg-min by TYPE, with the six folded axis planes and without the per-kind dispatch: a candidate wins
@@ -913,18 +944,18 @@ template <bool CUSTOM> MDH_DEV float closest_primitive_info(const KScene &sc, f3
       {
          const int n = sc.tcount[PK_SPHERE], s0 = sc.tslot[PK_SPHERE], base = hdr(H_TBASE + PK_SPHERE);
 #pragma unroll 1
-         for (int i = 0; i < n; ++i) MDH_CAND(sd_sphere(s_tab[s0 + i], x), base + i);
+         for (int i = 0; i < n; ++i) MDH_CAND(sd_sphere(s_tab[uni<GTAB>(s0 + i)], x), base + i);
       }
       {
          const int n = sc.tcount[PK_BOX], s0 = sc.tslot[PK_BOX], base = hdr(H_TBASE + PK_BOX);
 #pragma unroll 1
-         for (int i = 0; i < n; ++i) MDH_CAND(sd_box(s_tab[s0 + 2 * i], s_tab[s0 + 2 * i + 1], x), base + i);
+         for (int i = 0; i < n; ++i) MDH_CAND(sd_box(s_tab[uni<GTAB>(s0 + 2 * i)], s_tab[uni<GTAB>(s0 + 2 * i + 1)], x), base + i);
       }
       {
          const int n = sc.tcount[PK_TRIANGLE], s0 = sc.tslot[PK_TRIANGLE], base = hdr(H_TBASE + PK_TRIANGLE);
 #pragma unroll 1
          for (int i = 0; i < n; ++i)
-            MDH_CAND(sd_triangle<false>(xyz(s_tab[s0 + 3 * i]), xyz(s_tab[s0 + 3 * i + 1]), xyz(s_tab[s0 + 3 * i + 2]), x), base + i);
+            MDH_CAND(sd_triangle<false>(xyz(s_tab[uni<GTAB>(s0 + 3 * i)]), xyz(s_tab[uni<GTAB>(s0 + 3 * i + 1)]), xyz(s_tab[uni<GTAB>(s0 + 3 * i + 2)]), x), base + i);
       }
 #undef MDH_CAND
       if (best >= 0) index = best;
@@ -937,7 +968,7 @@ template <bool CUSTOM> MDH_DEV float closest_primitive_info(const KScene &sc, f3
       const int n = hdr(H_KCOUNT + k), s0 = hdr(H_KSLOT + k), base = hdr(H_KBASE + k), type = hdr(H_KTYPE + k);
 #pragma unroll MDH_INFO_UNROLL
       for (int i = 0; i < n; ++i) {
-         float d = (CUSTOM && type == PK_CUSTOM) ? xdist<false>(k, i, x) : prim_dist(type, s0 + prim_slots(type) * i, x);
+         float d = (CUSTOM && type == PK_CUSTOM) ? xdist<false>(k, i, x) : prim_dist(s_tab, type, uni<GTAB>(s0 + prim_slots(type) * i), x);
          if (d < closest) { closest = d; index = base + i; }
       }
    }
@@ -946,8 +977,9 @@ template <bool CUSTOM> MDH_DEV float closest_primitive_info(const KScene &sc, f3
 
 // material id and normal of a flat index: primitive_info (scenes.adb:676-729),
 // kind found by successive subtraction of the DECLARED counts
-template <bool CUSTOM> MDH_DEV void primitive_info(const KScene &sc, int index, f3 pos, f3 &normal, int &material_id)
+template <bool CUSTOM, bool GTAB = false> MDH_DEV void primitive_info(const KScene &sc, int index, f3 pos, f3 &normal, int &material_id)
 {
+   const typename Geo<GTAB>::F4 s_tab = Geo<GTAB>::f4(sc); // (shadows the LDS table: the hit primitive is per lane, a gather either way)
    normal = F3(0.0f, 0.0f, 0.0f);
    material_id = 0;
    const int nk = hdr(H_NK);
@@ -962,7 +994,7 @@ template <bool CUSTOM> MDH_DEV void primitive_info(const KScene &sc, int index, 
             return;
          }
          const int slot = hdr(H_KSLOT + k) + prim_slots(type) * index; // per-lane LDS gather
-         material_id = tab_int(hdr(H_KMAT + k) + index);
+         material_id = Geo<GTAB>::mat_id(sc, hdr(H_KMAT + k) + index);
          float4 a = s_tab[slot];
          switch (type) {
          case PK_SPHERE: normal = snormalize(pos - xyz(a)); break; // spheres.ads:16-17
@@ -1011,11 +1043,12 @@ template <bool PSMALL = false> MDH_DEV int partition_cell_clamped(const KScene &
 }
 // partitioning_closest[_info] (scenes.adb:839-1118): per-lane cell record from HBM/L2,
 // per-lane primitive gather from LDS
-template <bool INFO, bool CUSTOM, bool FALLBACK = true, bool PSMALL = false> MDH_DEV float partitioning_lookup(const KScene &sc, f3 x, int &index)
+template <bool INFO, bool CUSTOM, bool FALLBACK = true, bool PSMALL = false, bool GTAB = false> MDH_DEV float partitioning_lookup(const KScene &sc, f3 x, int &index)
 {
+   const typename Geo<GTAB>::F4 geo = Geo<GTAB>::f4(sc);
    bool fb = false;
    int cell = FALLBACK ? partition_cell(sc, x, fb) : partition_cell_clamped<PSMALL>(sc, x);
-   if (FALLBACK && fb) return INFO ? closest_primitive_info<CUSTOM>(sc, x, index) : closest_primitive<CUSTOM>(sc, x);
+   if (FALLBACK && fb) return INFO ? closest_primitive_info<CUSTOM, GTAB>(sc, x, index) : closest_primitive<CUSTOM, false, GTAB>(sc, x);
    float closest = sc.max_dist;
    if (cell < 0 || cell >= sc.part_cells) return closest;
    const int nk = hdr(H_NK);
@@ -1032,7 +1065,7 @@ template <bool INFO, bool CUSTOM, bool FALLBACK = true, bool PSMALL = false> MDH
       for (; i < stop; ++i) {
          const int pi = pi_next;
          pi_next = rec[nk + (i + 1 < sc.part_index_count ? i + 1 : i)]; // (inside the record; unused past the last candidate)
-         float d = (CUSTOM && type == PK_CUSTOM) ? xdist<false>(k, pi, x) : prim_dist(type, s0 + prim_slots(type) * pi, x);
+         float d = (CUSTOM && type == PK_CUSTOM) ? xdist<false>(k, pi, x) : prim_dist(geo, type, s0 + prim_slots(type) * pi, x);
          if (INFO) { if (d < closest) { closest = d; index = base + pi; } }
          else closest = min_raw(closest, d);
       }
@@ -1047,7 +1080,7 @@ template <bool INFO, bool CUSTOM, bool FALLBACK = true, bool PSMALL = false> MDH
       const int stop = min(size, sc.part_index_count);
       for (; i < stop; ++i) {
          int pi = rec[nk + i];
-         float d = (CUSTOM && type == PK_CUSTOM) ? xdist<false>(k, pi, x) : prim_dist(type, s0 + prim_slots(type) * pi, x);
+         float d = (CUSTOM && type == PK_CUSTOM) ? xdist<false>(k, pi, x) : prim_dist(geo, type, s0 + prim_slots(type) * pi, x);
          if (INFO) { if (d < closest) { closest = d; index = base + pi; } }
          else closest = min_raw(closest, d);
       }
@@ -1098,7 +1131,7 @@ template <bool INFO, bool CUSTOM, bool FALLBACK = true, bool PSMALL = false> MDH
 #ifndef MDH_PART_CELL_TRIM
 #define MDH_PART_CELL_TRIM 1
 #endif
-MDH_DEV float walk_planes_single(unsigned w, const float4 *t, f3 x, float closest)
+template <typename TAB> MDH_DEV float walk_planes_single(unsigned w, TAB t, f3 x, float closest)
 {
    while (w) { // (a cell of the reference's scenes names one or two planes: pairs evaluated most of them twice)
       MDH_DIAG_STEP(6);
@@ -1108,7 +1141,7 @@ MDH_DEV float walk_planes_single(unsigned w, const float4 *t, f3 x, float closes
    }
    return closest;
 }
-MDH_DEV float walk_spheres_merged(unsigned w, const float4 *t, f3 x, float closest)
+template <typename TAB> MDH_DEV float walk_spheres_merged(unsigned w, TAB t, f3 x, float closest)
 {
    float S = __builtin_inff(), r_cur = 0.0f;
    while (w) {
@@ -1129,7 +1162,7 @@ MDH_DEV float walk_spheres_merged(unsigned w, const float4 *t, f3 x, float close
    if (!MDH_CULL || __ballot(need) != 0ull) closest = min_raw(closest, sqrt_wave_(S) - r_cur);
    return closest;
 }
-MDH_DEV float walk_boxes_merged(unsigned w, const float4 *t, f3 x, float closest)
+template <typename TAB> MDH_DEV float walk_boxes_merged(unsigned w, TAB t, f3 x, float closest)
 {
    float S = __builtin_inff(), U = 0.0f;
    while (w) {
@@ -1148,17 +1181,37 @@ MDH_DEV float walk_boxes_merged(unsigned w, const float4 *t, f3 x, float closest
    else closest = min_raw(closest, U < 0.0f ? U : closest);
    return closest;
 }
-template <int TYPE> MDH_DEV float walk_bits(unsigned w, const float4 *t, f3 x, float closest)
+// A lane's triangle candidates out of the table's image in memory (global residency), two at a time: the six vertex loads of
+// a pair are issued before the first vertex is used, so a pair costs one round trip to L2 instead of six dependent ones
+// (sd_triangle is a call: nothing stays in flight across it, which is why the pair BEHIND it is not asked for as well).  A
+// lane's last odd candidate is loaded twice (the same lines) and evaluated once.
+MDH_DEV float walk_triangles(unsigned w, GeoImage t, f3 x, float closest)
+{
+   while (w) {
+      MDH_DIAG_STEP(6);
+      const int p0 = __builtin_ctz(w);
+      w &= w - 1u;
+      const int p1 = w ? __builtin_ctz(w) : p0;
+      w &= w - 1u; // (0 & 0xffffffff = 0)
+      const float4 a0 = t[3 * p0], b0 = t[3 * p0 + 1], c0 = t[3 * p0 + 2], a1 = t[3 * p1], b1 = t[3 * p1 + 1], c1 = t[3 * p1 + 2];
+      closest = min_raw(closest, sd_triangle<false>(xyz(a0), xyz(b0), xyz(c0), x));
+      if (p1 != p0) closest = min_raw(closest, sd_triangle<false>(xyz(a1), xyz(b1), xyz(c1), x));
+   }
+   return closest;
+}
+MDH_DEV float walk_triangles(unsigned w, const float4 *t, f3 x, float closest) // (LDS residency)
+{
+   while (w) { const int pi = __builtin_ctz(w); w &= w - 1u; closest = min_raw(closest, sd_triangle<false>(xyz(t[3 * pi]), xyz(t[3 * pi + 1]), xyz(t[3 * pi + 2]), x)); }
+   return closest;
+}
+template <int TYPE, typename TAB> MDH_DEV float walk_bits(unsigned w, TAB t, f3 x, float closest)
 {
 #if MDH_PART_MERGE_ROOTS
    if (TYPE == PK_SPHERE) return walk_spheres_merged(w, t, x, closest);
    if (TYPE == PK_BOX) return walk_boxes_merged(w, t, x, closest);
    if (TYPE == PK_PLANE && MDH_PART_PLANE_SINGLE) return walk_planes_single(w, t, x, closest);
 #endif
-   if (TYPE == PK_TRIANGLE) {
-      while (w) { const int pi = __builtin_ctz(w); w &= w - 1u; closest = min_raw(closest, sd_triangle<false>(xyz(t[3 * pi]), xyz(t[3 * pi + 1]), xyz(t[3 * pi + 2]), x)); }
-      return closest;
-   }
+   if (TYPE == PK_TRIANGLE) return walk_triangles(w, t, x, closest);
    while (w) {
       MDH_DIAG_STEP(6);
       const int p0 = __builtin_ctz(w);
@@ -1186,11 +1239,12 @@ template <int TYPE> MDH_DEV float walk_bits(unsigned w, const float4 *t, f3 x, f
 // and its census known when the kernel is built.  The same operations; what goes is the general form's loops over kinds (their
 // code, and the registers their state held across every march loop: 80 -> 69 VGPRs and 48 -> 16 bytes of scratch in the screen
 // kernel) and the tests of what a scene never changes.  A type without instances walks an empty word.
-template <bool CUSTOM, bool FALLBACK, bool PSMALL = false> MDH_DEV float partitioning_closest_bits(const KScene &sc, f3 x)
+template <bool CUSTOM, bool FALLBACK, bool PSMALL = false, bool GTAB = false> MDH_DEV float partitioning_closest_bits(const KScene &sc, f3 x)
 {
+   const typename Geo<GTAB>::F4 geo = Geo<GTAB>::f4(sc); // (the candidates are per lane: LDS gathers, or global_load_dwordx4 out of the image)
    bool fb = false;
    const int cell = FALLBACK ? partition_cell(sc, x, fb) : partition_cell_clamped<PSMALL>(sc, x);
-   if (FALLBACK && fb) return closest_primitive<CUSTOM>(sc, x);
+   if (FALLBACK && fb) return closest_primitive<CUSTOM, false, GTAB>(sc, x);
    float closest = sc.max_dist;
    if (cell < 0 || cell >= sc.part_cells) return closest;
    MDH_DIAG_STEP(5); // lookups that reach a cell
@@ -1205,10 +1259,10 @@ template <bool CUSTOM, bool FALLBACK, bool PSMALL = false> MDH_DEV float partiti
 #else
 #define MDH_TYPE_BITS(T) ((unsigned)(mm >> sc.part_tbit[T]) & sc.part_tmask[T])
 #endif
-      if (PSMALL || sc.part_tmask[PK_PLANE]) closest = walk_bits<PK_PLANE>(MDH_TYPE_BITS(PK_PLANE), s_tab + sc.tslot[PK_PLANE], x, closest);
-      if (PSMALL || sc.part_tmask[PK_SPHERE]) closest = walk_bits<PK_SPHERE>(MDH_TYPE_BITS(PK_SPHERE), s_tab + sc.tslot[PK_SPHERE], x, closest);
-      if (PSMALL || sc.part_tmask[PK_BOX]) closest = walk_bits<PK_BOX>(MDH_TYPE_BITS(PK_BOX), s_tab + sc.tslot[PK_BOX], x, closest);
-      if (!PSMALL && sc.part_tmask[PK_TRIANGLE]) closest = walk_bits<PK_TRIANGLE>(MDH_TYPE_BITS(PK_TRIANGLE), s_tab + sc.tslot[PK_TRIANGLE], x, closest);
+      if (PSMALL || sc.part_tmask[PK_PLANE]) closest = walk_bits<PK_PLANE>(MDH_TYPE_BITS(PK_PLANE), geo + sc.tslot[PK_PLANE], x, closest);
+      if (PSMALL || sc.part_tmask[PK_SPHERE]) closest = walk_bits<PK_SPHERE>(MDH_TYPE_BITS(PK_SPHERE), geo + sc.tslot[PK_SPHERE], x, closest);
+      if (PSMALL || sc.part_tmask[PK_BOX]) closest = walk_bits<PK_BOX>(MDH_TYPE_BITS(PK_BOX), geo + sc.tslot[PK_BOX], x, closest);
+      if (!PSMALL && sc.part_tmask[PK_TRIANGLE]) closest = walk_bits<PK_TRIANGLE>(MDH_TYPE_BITS(PK_TRIANGLE), geo + sc.tslot[PK_TRIANGLE], x, closest);
 #undef MDH_TYPE_BITS
       return closest;
    }
@@ -1247,10 +1301,10 @@ template <bool CUSTOM, bool FALLBACK, bool PSMALL = false> MDH_DEV float partiti
          // the type is wave-uniform: one walk per type (walk_bits)
          if (CUSTOM && type == PK_CUSTOM) {
             while (w) { const int pi = c + __builtin_ctz(w); w &= w - 1u; closest = min_raw(closest, xdist<false>(k, pi, x)); }
-         } else if (type == PK_SPHERE) closest = walk_bits<PK_SPHERE>(w, s_tab + s0 + c, x, closest);
-         else if (type == PK_PLANE) closest = walk_bits<PK_PLANE>(w, s_tab + s0 + c, x, closest);
-         else if (type == PK_BOX) closest = walk_bits<PK_BOX>(w, s_tab + s0 + 2 * c, x, closest);
-         else closest = walk_bits<PK_TRIANGLE>(w, s_tab + s0 + 3 * c, x, closest);
+         } else if (type == PK_SPHERE) closest = walk_bits<PK_SPHERE>(w, geo + (s0 + c), x, closest);
+         else if (type == PK_PLANE) closest = walk_bits<PK_PLANE>(w, geo + (s0 + c), x, closest);
+         else if (type == PK_BOX) closest = walk_bits<PK_BOX>(w, geo + (s0 + 2 * c), x, closest);
+         else closest = walk_bits<PK_TRIANGLE>(w, geo + (s0 + 3 * c), x, closest);
       }
    }
    return closest;
@@ -1261,6 +1315,7 @@ template <bool CUSTOM, bool FALLBACK, bool PSMALL = false> MDH_DEV float partiti
 #define MDH_PF_POW2 4 // bit 2 = the probe counts and both tile resolutions are powers of two (every atlas address is shifts and masks)
 #define MDH_PF_FALLBACK 8 // bit 3 = the space partition's Border_Behavior is Fallback (built-in kinds; scenes with user-defined kinds keep the run-time test)
 #define MDH_PF_PSMALL 32 // bit 5 = the space partition's small form and its census, known when the kernel is built (partitioning_closest_bits' PSMALL; with bit 0, never with bits 1 or 3)
+#define MDH_PF_GTAB 64 // bit 6 = global residency of the scene table (Geo<true> above): geometry and material ids are read from the table's image in memory, LDS holds the resident part only (built-in kinds; with or without bits 0 and 3; never with bits 1, 2, 4 or 5)
 #define MDH_PF_ROOM 16 // bit 4 = the census of the reference's rooms, known when the kernel is built (closest_primitive's ROOM; never with bits 0, 1 or 3)
 // does this variant carry the full scan of the Fallback border?
 #define MDH_PF_HAS_FALLBACK(PART) ((((PART) & MDH_PF_FALLBACK) != 0) || (((PART) & MDH_PF_CUSTOM) != 0))
@@ -1269,8 +1324,8 @@ template <int PART> MDH_DEV float sdf(const KScene &sc, f3 x)
    MDH_WORK(2);
    int dummy;
    (void)dummy;
-   if (PART & MDH_PF_PART) return MDH_PART_BITS ? partitioning_closest_bits<(PART & MDH_PF_CUSTOM) != 0, MDH_PF_HAS_FALLBACK(PART), (PART & MDH_PF_PSMALL) != 0>(sc, x) : partitioning_lookup<false, (PART & MDH_PF_CUSTOM) != 0, MDH_PF_HAS_FALLBACK(PART), (PART & MDH_PF_PSMALL) != 0>(sc, x, dummy);
-   return closest_primitive<(PART & MDH_PF_CUSTOM) != 0, (PART & MDH_PF_ROOM) != 0>(sc, x);
+   if (PART & MDH_PF_PART) return MDH_PART_BITS ? partitioning_closest_bits<(PART & MDH_PF_CUSTOM) != 0, MDH_PF_HAS_FALLBACK(PART), (PART & MDH_PF_PSMALL) != 0, (PART & MDH_PF_GTAB) != 0>(sc, x) : partitioning_lookup<false, (PART & MDH_PF_CUSTOM) != 0, MDH_PF_HAS_FALLBACK(PART), (PART & MDH_PF_PSMALL) != 0, (PART & MDH_PF_GTAB) != 0>(sc, x, dummy);
+   return closest_primitive<(PART & MDH_PF_CUSTOM) != 0, (PART & MDH_PF_ROOM) != 0, (PART & MDH_PF_GTAB) != 0>(sc, x);
 }
 // the same with the first sphere and box already in registers (sdf_regs)
 template <int PART> MDH_DEV float sdf(const KScene &sc, f3 x, const SdfRegs &regs)
@@ -1278,14 +1333,14 @@ template <int PART> MDH_DEV float sdf(const KScene &sc, f3 x, const SdfRegs &reg
    MDH_WORK(2);
    int dummy;
    (void)dummy;
-   if (PART & MDH_PF_PART) return MDH_PART_BITS ? partitioning_closest_bits<(PART & MDH_PF_CUSTOM) != 0, MDH_PF_HAS_FALLBACK(PART), (PART & MDH_PF_PSMALL) != 0>(sc, x) : partitioning_lookup<false, (PART & MDH_PF_CUSTOM) != 0, MDH_PF_HAS_FALLBACK(PART), (PART & MDH_PF_PSMALL) != 0>(sc, x, dummy);
-   return closest_primitive<(PART & MDH_PF_CUSTOM) != 0, (PART & MDH_PF_ROOM) != 0>(sc, x, &regs);
+   if (PART & MDH_PF_PART) return MDH_PART_BITS ? partitioning_closest_bits<(PART & MDH_PF_CUSTOM) != 0, MDH_PF_HAS_FALLBACK(PART), (PART & MDH_PF_PSMALL) != 0, (PART & MDH_PF_GTAB) != 0>(sc, x) : partitioning_lookup<false, (PART & MDH_PF_CUSTOM) != 0, MDH_PF_HAS_FALLBACK(PART), (PART & MDH_PF_PSMALL) != 0, (PART & MDH_PF_GTAB) != 0>(sc, x, dummy);
+   return closest_primitive<(PART & MDH_PF_CUSTOM) != 0, (PART & MDH_PF_ROOM) != 0, (PART & MDH_PF_GTAB) != 0>(sc, x, &regs);
 }
 template <int PART> MDH_DEV float sdf_info(const KScene &sc, f3 x, int &index)
 {
    MDH_WORK(2);
-   if (PART & MDH_PF_PART) return partitioning_lookup<true, (PART & MDH_PF_CUSTOM) != 0, MDH_PF_HAS_FALLBACK(PART), (PART & MDH_PF_PSMALL) != 0>(sc, x, index);
-   return closest_primitive_info<(PART & MDH_PF_CUSTOM) != 0>(sc, x, index);
+   if (PART & MDH_PF_PART) return partitioning_lookup<true, (PART & MDH_PF_CUSTOM) != 0, MDH_PF_HAS_FALLBACK(PART), (PART & MDH_PF_PSMALL) != 0, (PART & MDH_PF_GTAB) != 0>(sc, x, index);
+   return closest_primitive_info<(PART & MDH_PF_CUSTOM) != 0, (PART & MDH_PF_GTAB) != 0>(sc, x, index);
 }
 
 // ------------------------------------------------------------- probe-visibility clearance
@@ -1368,7 +1423,7 @@ template <int PART> MDH_DEV bool segment_clear_bound(const KScene &sc, f3 A, f3 
 }
 template <int PART> MDH_DEV bool segment_clear(const KScene &sc, f3 A, f3 vd, float vmax)
 {
-   if (!MDH_VIS_CLEAR || (PART & (MDH_PF_PART | MDH_PF_CUSTOM))) return false;
+   if (!MDH_VIS_CLEAR || (PART & (MDH_PF_PART | MDH_PF_CUSTOM | MDH_PF_GTAB))) return false; // (global residency: the bound reads the LDS table, which holds no geometry there)
    return segment_clear_bound<PART>(sc, A, vd, vmax);
 }
 

@@ -1613,10 +1613,12 @@ struct PartBuildArgs {
 
 // distance of primitive i of kind k through the table; ADA_DIV for the CPU builders, which
 // go through Primitives.Eval_Dist (madarch-primitives.adb:90-108)
-template <bool ADA_DIV> MDH_DEV float part_dist(const KScene &sc, int k, int i, f3 x)
+// GTAB: global residency of the scene table (mdh_device.h: Geo); UNI (with it): k and i are wave-uniform, and said to be
+template <bool ADA_DIV, bool GTAB = false, bool UNI = false> MDH_DEV float part_dist(const KScene &sc, int k, int i, f3 x)
 {
+   const typename Geo<GTAB>::F4 s_tab = Geo<GTAB>::f4(sc); // (shadows the LDS table)
    // k may differ per lane here (candidate lists): plain per-lane header reads, not hdr()
-   const int type = tab_int(H_KTYPE + k), slot = tab_int(H_KSLOT + k) + prim_slots(type) * i;
+   const int type = uni<UNI>(tab_int(H_KTYPE + k)), slot = uni<UNI>(tab_int(H_KSLOT + k) + prim_slots(type) * i);
    if (type == PK_CUSTOM) { // the program must be wave-uniform: one round per user-defined kind, its lanes active
       float r = 0.0f;
       const int nk = hdr(H_NK);
@@ -1625,7 +1627,7 @@ template <bool ADA_DIV> MDH_DEV float part_dist(const KScene &sc, int k, int i, 
       return r;
    }
    if (type == PK_TRIANGLE) return sd_triangle<ADA_DIV>(xyz(s_tab[slot]), xyz(s_tab[slot + 1]), xyz(s_tab[slot + 2]), x);
-   return prim_dist(type, slot, x);
+   return prim_dist(s_tab, type, slot, x);
 }
 
 // ONE WAVEFRONT PER GRID CELL (round 4; until round 3 one LANE per cell walked every loop below by itself, its candidate
@@ -1646,7 +1648,7 @@ MDH_DEV float wave_min(float v)
    for (int o = 32; o > 0; o >>= 1) v = min_(v, __shfl_xor(v, o));
    return v;
 }
-__global__ __launch_bounds__(64) void k_partition_build(KScene sc, PartBuildArgs a)
+template <bool GTAB> MDH_DEV void partition_build(const KScene &sc, const PartBuildArgs &a)
 {
    __shared__ unsigned short s_pre[MDH_PART_MAX_PRE]; // (kind << 12) | index, in scene order
    __shared__ unsigned char s_acc[MDH_PART_MAX_PRE];  // method 0: the candidate's acceptance number (0: not accepted)
@@ -1667,7 +1669,7 @@ __global__ __launch_bounds__(64) void k_partition_build(KScene sc, PartBuildArgs
       for (int c = 0; c < n; c += 64) {                                                                                     \
          const int i = c + lane;                                                                                            \
          const bool in = i < n;                                                                                             \
-         const float d = part_dist<ADA_>(sc, k, in ? i : 0, center_);                                                       \
+         const float d = part_dist<ADA_, GTAB>(sc, k, in ? i : 0, center_);                                                 \
          const bool take = in && d < (thr_);                                                                                \
          const unsigned long long m = __ballot(take);                                                                       \
          const int at = npre + (int)__builtin_amdgcn_mbcnt_hi((unsigned)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m, 0u)); \
@@ -1677,7 +1679,7 @@ __global__ __launch_bounds__(64) void k_partition_build(KScene sc, PartBuildArgs
    }
    if (a.method == 2) {
       const f3 center = (F3((float)X, (float)Y, (float)Z) + F3s(0.5f)) * sp + off;
-      const float thr = closest_primitive<true>(sc, center) + a.gpu_diag;
+      const float thr = closest_primitive<!GTAB, false, GTAB>(sc, center) + a.gpu_diag; // (global residency: no user-defined kinds, commit_scene)
       MDH_PART_COLLECT(false, center, thr)
    } else {
       const f3 grid_pos = F3((float)X, (float)Y, (float)Z) * sp + off;
@@ -1687,7 +1689,7 @@ __global__ __launch_bounds__(64) void k_partition_build(KScene sc, PartBuildArgs
       for (int k = 0; k < nk; ++k) {
          const int n = hdr(H_KCOUNT + k);
          for (int c = 0; c < n; c += 64)
-            if (c + lane < n) closest = min_(closest, part_dist<true>(sc, k, c + lane, center));
+            if (c + lane < n) closest = min_(closest, part_dist<true, GTAB>(sc, k, c + lane, center));
       }
       closest = wave_min(closest);
       MDH_PART_COLLECT(true, center, closest + cell_diag)
@@ -1699,7 +1701,7 @@ __global__ __launch_bounds__(64) void k_partition_build(KScene sc, PartBuildArgs
          int ci = -1;
          for (int q = 0; q < npre; ++q) {
             const int e = __builtin_amdgcn_readfirstlane((int)s_pre[q]);
-            const float d = part_dist<true>(sc, e >> 12, e & 0xfff, pt);
+            const float d = part_dist<true, GTAB, GTAB>(sc, e >> 12, e & 0xfff, pt); // (one pre-candidate for all 27 points: a scalar load out of the image)
             if (d < c) { c = d; ci = q; }
          }
          // acceptance ORDER defines the order of a kind's indices: the points accept in the reference's loop order
@@ -1735,6 +1737,8 @@ __global__ __launch_bounds__(64) void k_partition_build(KScene sc, PartBuildArgs
       written += n;
    }
 }
+__global__ __launch_bounds__(64) void k_partition_build(KScene sc, PartBuildArgs a) { partition_build<false>(sc, a); }
+template <int = 0> __global__ __launch_bounds__(64) void k_partition_build_gtab(KScene sc, PartBuildArgs a) { partition_build<true>(sc, a); } // global residency of the scene table (a template: built where it is first named, mdh_api.hip: gtab_kernel)
 
 // The candidate lists of every cell once more as one bit per declared primitive (partitioning_closest_bits,
 // mdh_device.h), derived from the lists exactly as the lookup walks them: kind by kind, a kind's entries up to its
@@ -1770,8 +1774,9 @@ struct EvalArgs {
    float *normals;
    float *dist;
 };
-template <bool ADA_DIV> __global__ __launch_bounds__(64) void k_eval_distance(KScene sc, EvalArgs a)
+template <bool ADA_DIV, bool GTAB> MDH_DEV void eval_distance(const KScene &sc, const EvalArgs &a)
 {
+   const typename Geo<GTAB>::F4 s_tab = Geo<GTAB>::f4(sc); // (shadows the LDS table)
    stage_table(sc);
    const int q = blockIdx.x * 64 + threadIdx.x;
    if (q >= a.n) return;
@@ -1781,11 +1786,11 @@ template <bool ADA_DIV> __global__ __launch_bounds__(64) void k_eval_distance(KS
    for (int kk = 0; kk < a.n_kinds; ++kk) {
       const int k = a.kinds[kk], type = hdr(H_KTYPE + k);
       for (int i = 0; i < a.host_count[k]; ++i) {
-         float d = part_dist<ADA_DIV>(sc, k, i, p);
+         float d = part_dist<ADA_DIV, GTAB, GTAB>(sc, k, i, p);
          if (d < closest) {
             closest = d;
             const int slot = hdr(H_KSLOT + k) + prim_slots(type) * i;
-            float4 A = s_tab[slot];
+            float4 A = s_tab[uni<GTAB>(slot)];
             switch (type) {
             case PK_CUSTOM: normal = xnormal<ADA_DIV>(k, i, p); break;
             case PK_SPHERE: normal = normalize(p - xyz(A)); break;
@@ -1799,6 +1804,8 @@ template <bool ADA_DIV> __global__ __launch_bounds__(64) void k_eval_distance(KS
    a.dist[q] = closest;
    if (a.normals) { a.normals[3 * q] = normal.x; a.normals[3 * q + 1] = normal.y; a.normals[3 * q + 2] = normal.z; }
 }
+template <bool ADA_DIV> __global__ __launch_bounds__(64) void k_eval_distance(KScene sc, EvalArgs a) { eval_distance<ADA_DIV, false>(sc, a); }
+template <bool ADA_DIV> __global__ __launch_bounds__(64) void k_eval_distance_gtab(KScene sc, EvalArgs a) { eval_distance<ADA_DIV, true>(sc, a); } // global residency of the scene table
 
 // ---------------------------------------------------------------------- the window's pixels
 // What Swap_Buffers (renderers.adb:320) puts on screen: the screen pass writes float colours and

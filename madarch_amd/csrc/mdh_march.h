@@ -115,7 +115,7 @@ template <int PART> MDH_DEV bool march_plain(const KScene &sc, f3 o, f3 d, float
    float total = 0.0f;
    // the first sphere and box stay in registers for the whole march (measured: +0.7 %; the same in the shadow,
    // visibility-queue and occlusion marches ±0, in the per-corner visibility march -1 %: register pressure)
-   const SdfRegs regs = sdf_regs(sc);
+   const SdfRegs regs = sdf_regs<(PART & MDH_PF_GTAB) != 0>(sc);
    MDH_WORK(0);
    while (total < tmax) {
       MDH_DIAG_STEP(0);
@@ -785,7 +785,7 @@ MDH_DEV f3 shade_structured(const KScene &sc, const KProbes &pr, const MachineCf
             else {
             MDH_WORK(3);
             (void)sdf_info<PART>(sc, P, index);
-            primitive_info<(PART & MDH_PF_CUSTOM) != 0>(sc, index, P, N, pm);
+            primitive_info<(PART & MDH_PF_CUSTOM) != 0, (PART & MDH_PF_GTAB) != 0>(sc, index, P, N, pm);
             }
             if (ctx == 0) {
                park_store1<PARK_MAT>(pk, wb, __int_as_float(pm));

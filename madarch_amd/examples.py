@@ -1,18 +1,19 @@
-"""The three benchmark scenes of BASELINE.json, written as the reference's example
-programs write them (same data, same call order), minus the window loop.
+"""The three benchmark scenes of BASELINE.json and the reference's mesh example, written as the
+reference's example programs write them (same data, same call order), minus the window loop.
 
   simple_scene        -- reference examples/simple_scene/main.adb:28-122
   global_illumination -- reference examples/global_illumination/main.adb:29-74,149-161
   light_shafts        -- reference examples/light_shafts/main.adb:29-59,140-155
+  obj_mesh            -- reference examples/obj_mesh/main.adb:30-75,139-169 (a procedural mesh for suzanne.obj)
 
 Each returns the Renderer after the last call the example makes before its
 first `Renderers.Render`.  `Binding=None` is the HIP library.
 """
 import numpy as np
 
-from . import lights, materials, primitives, renderers, scenes, windows
+from . import lights, materials, meshes, primitives, renderers, scenes, windows
 from .lights import point_lights, spot_lights
-from .primitives import boxes, planes, spheres
+from .primitives import boxes, planes, spheres, triangles
 
 # BASELINE config 3: DDGI 8x8x8 probe grid = 512 probes as a 32x16 atlas; the grid
 # has no offset (glsl/probe_utils.glsl:38-40), this spacing keeps it in the room
@@ -111,6 +112,41 @@ def light_shafts(Width=1000, Height=1000, Probes=None, Volumetrics=None, Binding
     return R
 
 
+OBJ_MESH_TRIANGLES = 1000  # main.adb:46
+OBJ_MESH_OFFSET = (1.5, 1.0, 1.0)  # Suzanne_Offset, main.adb:139-140
+
+
+def obj_mesh(Width=1000, Height=1000, Probes=None, Binding=None, Device=0,
+             Partitioning_Method=renderers.GPU_Fast, Mesh=None, Index_Count=150):
+    """examples/obj_mesh/main.adb: 1000 triangles behind a 30 x 20 x 20 partition of 0.1 cells, one point
+    light, the default probes (the example declares probe settings and does not pass them).  `Mesh`
+    ([n, 3, 3] vertex triples about the origin, n <= 1000) stands for media/suzanne.obj -- there is no
+    loader; the default is meshes.torus (25, 20): exactly 1000 triangles.  The scene's table is larger
+    than a workgroup's LDS: the HIP library reads its geometry from device memory (OPT_TABLE_RESIDENCY)."""
+    Partitioning_Settings = scenes.Partitioning_Settings(
+        Enable=True, Index_Count=Index_Count, Border_Behavior=scenes.Clamp, Grid_Dimensions=(30, 20, 20),
+        Grid_Spacing=(0.1, 0.1, 0.1), Grid_Offset=(0.0, 0.0, 0.0))
+    Scene = scenes.Compile(
+        All_Primitives=[(triangles.Triangle, OBJ_MESH_TRIANGLES)],
+        All_Lights=[(point_lights.Point_Light, 4)],
+        Partitioning=Partitioning_Settings)
+    Window = windows.Open(Width, Height, "Obj_Mesh")
+    R = renderers.Create(Window, Scene, Probes=Probes, Volumetrics=renderers.No_Volumetrics,
+                         Device=Device, Binding=Binding)
+    Point_Light_Instance = point_lights.Create((0.0, 1.0, -5.0), (0.9, 0.9, 0.9))
+    Mesh_Mat = R.Add_Material(materials.Create((0.8, 0.2, 0.1), 0.0, 1.0))
+    if Mesh is None:
+        Mesh = meshes.torus(25, 20)
+    Offset = np.asarray(OBJ_MESH_OFFSET, dtype=np.float32)
+    for A, B, C in np.asarray(Mesh, dtype=np.float32):  # Add_Triangle, main.adb:142-153
+        R.Add_Primitive(triangles.Triangle, triangles.Create(A + Offset, B + Offset, C + Offset, Mesh_Mat))
+    if Partitioning_Method is not None:
+        R.Update_Partitioning(Method=Partitioning_Method)
+    R.Set_Light(1, point_lights.Point_Light, Point_Light_Instance)
+    R.Set_Camera_Position((0.0, 1.0, -5.0))  # Move_Camera with a zero offset, main.adb:70-75,133
+    return R
+
+
 class Ball_Game:
     """examples/ball_game/main.adb: the global_illumination room with the default space partition, balls
     thrown from the camera that bounce off planes and boxes.  The physics step is the reference's: per
@@ -179,4 +215,4 @@ def ball_game(Width=1000, Height=1000, Probes=None, Binding=None, Device=0):
 
 
 SCENES = {"simple_scene": simple_scene, "global_illumination": global_illumination,
-          "light_shafts": light_shafts}
+          "light_shafts": light_shafts, "obj_mesh": obj_mesh}
