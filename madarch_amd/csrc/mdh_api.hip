@@ -441,14 +441,9 @@ static int part_mask_words(const mdh_renderer *r)
 }
 static size_t part_bits_ints(const mdh_renderer *r) { return ((size_t)r->part_cells * part_mask_words(r) + 3) / 4 * 4; }
 static size_t part_buffer_ints(const mdh_renderer *r) { return part_table_ints(r) + part_bits_ints(r); }
-// The bits of the whole grid are staged into LDS by every workgroup when they are small (the reference's simple_scene:
-// 2000 cells x 2 words = 16 KB): a march step then reads no memory at all.  Larger grids read their cells' words from
-// memory (L1 / L2).
-#ifndef MDH_PART_BITS_LDS_MAX
-#define MDH_PART_BITS_LDS_MAX 0 // (measured: off.  Staged, simple_scene's 16 KB leave room for five workgroups per CU instead of seven and
-                                // its screen pass takes 0.78 instead of 0.70 ms, although no march step reads memory any more)
-#endif
-static int part_bits_f4(const mdh_renderer *r) { return r->part.enable && part_bits_ints(r) * 4 <= MDH_PART_BITS_LDS_MAX ? (int)(part_bits_ints(r) / 4) : 0; }
+// The cells' bits are read from memory (L1 / L2), never staged into LDS (KScene::part_bits_f4 = 0).  (measured: staged, the
+// 16 KB of the reference's simple_scene, 2000 cells x 2 words, leave room for five workgroups per CU instead of seven and its
+// screen pass takes 0.78 instead of 0.70 ms, although no march step reads memory any more)
 static float rd_f(const mdh_renderer *r, int off) { float f; memcpy(&f, r->scene_ubo.data() + off, 4); return f; }
 static int rd_i(const mdh_renderer *r, int off) { int32_t i; memcpy(&i, r->scene_ubo.data() + off, 4); return i; }
 static float4 mk4(float x, float y, float z, float w) { float4 v; v.x = x; v.y = y; v.z = z; v.w = w; return v; }
@@ -676,13 +671,7 @@ static int commit_scene(mdh_renderer *r, hipStream_t up)
       t.push_back(mk4(f[0], f[1], f[2], f[3]));
       t.push_back(mk4(f[4], 0, 0, 0));
    }
-#if MDH_U8_FMA
    s.u8_slot = -1; // (RGB8 texels are decoded in registers: u8_unorm, mdh_device.h)
-#else
-   // k / 255 for k = 0..255: the RGB8 texel decode, one correctly rounded division each
-   s.u8_slot = (int)t.size();
-   for (int k = 0; k < 256; k += 4) t.push_back(mk4((float)k / 255.0f, (float)(k + 1) / 255.0f, (float)(k + 2) / 255.0f, (float)(k + 3) / 255.0f));
-#endif
    // RESIDENCY (mdh_device.h: Geo).  A table that fits the LDS budget is staged whole, as it is laid out above.  One that does
    // not -- or any, under MDH_OPT_TABLE_RESIDENCY 1 -- is laid out with its resident part first: header ints, lights, materials,
    // the k / 255 table, then everything the kernels read from the image in memory; every workgroup stages the first
@@ -694,10 +683,10 @@ static int commit_scene(mdh_renderer *r, hipStream_t up)
       bool has_custom = false;
       for (int k = 0; k < r->npk; ++k) has_custom = has_custom || r->pk[k].type == PK_CUSTOM;
       for (int k = 0; k < r->nlk; ++k) has_custom = has_custom || r->lk[k].type == LK_CUSTOM;
-      const bool fits = (t.size() + (size_t)part_bits_f4(r)) * 16 + park <= budget;
+      const bool fits = t.size() * 16 + park <= budget;
       if (fits && r->opt_residency == 1 && has_custom)
          return seterr(MDH_E_INVALID, "MDH_OPT_TABLE_RESIDENCY 1: scenes with user-defined kinds keep their table in LDS");
-      if (!fits && (has_custom || (n_res + (size_t)part_bits_f4(r)) * 16 + park > budget))
+      if (!fits && (has_custom || n_res * 16 + park > budget))
          return seterr(MDH_E_INVALID, "scene tables exceed the 64 KiB LDS budget of a workgroup");
       r->residency = !fits || r->opt_residency == 1 ? 1 : 0;
       s.table_f4 = (int)t.size();
@@ -717,12 +706,7 @@ static int commit_scene(mdh_renderer *r, hipStream_t up)
    }
    for (int k = 0; k < r->npk; ++k) { H[H_KQUAD + 4 * k] = H[H_KTYPE + k]; H[H_KQUAD + 4 * k + 1] = H[H_KSLOT + k]; H[H_KQUAD + 4 * k + 2] = H[H_KBASE + k]; H[H_KQUAD + 4 * k + 3] = H[H_KMAX + k]; }
    memcpy(t.data(), H, sizeof H);
-   { // (MDH_SDF_SGPR: the words closest_primitive would read from the table; with a count of 0 they belong to the next kind and are not used)
-      const size_t ss = (size_t)s.tslot[PK_SPHERE], sb = (size_t)s.tslot[PK_BOX];
-      const float4 z = mk4(0, 0, 0, 0), a = ss < t.size() ? t[ss] : z, b0 = sb < t.size() ? t[sb] : z, b1 = sb + 1 < t.size() ? t[sb + 1] : z;
-      const float fs[4] = {a.x, a.y, a.z, a.w}, fb[8] = {b0.x, b0.y, b0.z, b0.w, b1.x, b1.y, b1.z, b1.w};
-      memcpy(s.first_sphere, fs, sizeof fs); memcpy(s.first_box, fb, sizeof fb);
-   }
+
    if (t.size() > r->table_cap) { // grow the whole ring (rare: the table only grows with the primitive counts)
       { int dr = drain_streams(r); if (dr != MDH_OK) return dr; }
       r->table_cap = t.size() + 256;
@@ -764,7 +748,7 @@ static int commit_scene(mdh_renderer *r, hipStream_t up)
    s.part_table = r->d_part_ring[r->part_slot];
    s.part_mask_off = (int)part_table_ints(r);
    s.part_mask_words = part_mask_words(r);
-   s.part_bits_f4 = part_bits_f4(r);
+   s.part_bits_f4 = 0;
    { // KScene::part_small: one 8-byte load per lookup, a shift and a mask per built-in type
       int declared = 0;
       bool small = r->part.enable != 0;
@@ -1012,11 +996,8 @@ extern "C" int32_t mdh_create(int32_t width, int32_t height, const mdh_scene_des
       int lo = 0, hi = 0; // numerically lower = higher priority
       TRY_OR_FAIL(hipDeviceGetStreamPriorityRange(&lo, &hi));
       // the probe passes are the head of each frame's dependency chain: high priority (measured on MI355X:
-      // 3340 vs 3300 Mpix/s at BASELINE config 3).  MADARCH_HIP_PROBE_PRIORITY = -1 high, 0 default, 1 low
-      const char *pe = getenv("MADARCH_HIP_PROBE_PRIORITY");
-      int prio = pe ? atoi(pe) : -1;
-      prio = prio < 0 ? hi : (prio > 0 ? lo : 0);
-      TRY_OR_FAIL(hipStreamCreateWithPriority(&r->probe_stream, hipStreamNonBlocking, prio));
+      // 3340 vs 3300 Mpix/s at BASELINE config 3)
+      TRY_OR_FAIL(hipStreamCreateWithPriority(&r->probe_stream, hipStreamNonBlocking, hi));
       TRY_OR_FAIL(hipStreamCreateWithFlags(&r->alt_stream, hipStreamNonBlocking));
       for (hipEvent_t *e : {&r->ev_join, &r->ev_join_alt, &r->ev_table}) TRY_OR_FAIL(hipEventCreateWithFlags(e, hipEventDisableTiming));
       for (int q = 0; q < mdh_renderer::NSETS; ++q)
@@ -1264,7 +1245,7 @@ static size_t lds_bytes_march(const mdh_renderer *r) { return lds_bytes(r) + (si
 static size_t lds_bytes_screen(const mdh_renderer *r)
 {
    // (scenes with a space partition: three more rows, the second shaded point's normal across its visibility marches, MDH_PARK_VD_ROW)
-   const int rows = r->opt_mode == 2 ? MDH_DIRECT_PARK_ROWS : (r->part.enable && MDH_PART_PARK_VD ? std::max(MDH_SCR_PARK_ROWS, MDH_PARK_VD_ROW + 3) : MDH_SCR_PARK_ROWS);
+   const int rows = r->opt_mode == 2 ? MDH_DIRECT_PARK_ROWS : (r->part.enable ? std::max(MDH_SCR_PARK_ROWS, MDH_PARK_VD_ROW + 3) : MDH_SCR_PARK_ROWS);
    return lds_bytes(r) + (size_t)rows * MDH_BLOCK * sizeof(float);
 }
 
@@ -1564,9 +1545,6 @@ static bool rad_small_launch(const mdh_renderer *r)
 }
 // The workgroups of the radiance pass the chip holds at once, when the launch is that and a remainder smaller than
 // it (k_radiance, mdh_kernels.h: the remainder runs at a raised issue priority); 0 otherwise.
-#ifndef MDH_RAD_TAIL_PRIO
-#define MDH_RAD_TAIL_PRIO 1
-#endif
 static int rad_first_round(mdh_renderer *r, const void *kernel, hipFunction_t fn, size_t lds, int blocks)
 {
    const void *key = kernel ? kernel : (const void *)fn;
@@ -1579,7 +1557,7 @@ static int rad_first_round(mdh_renderer *r, const void *kernel, hipFunction_t fn
       it = r->resident.insert({{key, lds}, per_cu}).first;
    }
    const long first = (long)it->second * r->n_cus;
-   return MDH_RAD_TAIL_PRIO && first > 0 && blocks > first && blocks < 2 * first ? (int)first : 0;
+   return first > 0 && blocks > first && blocks < 2 * first ? (int)first : 0;
 }
 // launch a function of a JIT module: the arguments are the kernel's by-value structs, laid out as the
 // kernarg segment lays them out (each at its natural alignment = a struct of them)
@@ -1732,7 +1710,7 @@ static int window_slot(mdh_renderer *r, int rank, int world, unsigned **out)
 static bool room_census(const mdh_renderer *r)
 {
    return r->ks.n_axis > 0 && r->ks.gplane_count == 0 && r->ks.tcount[PK_SPHERE] == 1 && r->ks.tcount[PK_BOX] == 1 &&
-          r->ks.tcount[PK_TRIANGLE] == 0 && MDH_ROOM_VARIANTS;
+          r->ks.tcount[PK_TRIANGLE] == 0;
 }
 
 // One pass on stream `st`.  The radiance pass reads the irradiance atlas of set `src` and writes the
@@ -1755,7 +1733,7 @@ static int run_pass(mdh_renderer *r, int pass, hipStream_t st, int src, int dst,
    const bool gtab = r->residency != 0;
    const bool room = pf == 0 && room_census(r) && !gtab;
    // ... bit 5 = the partition's small form with its census (MDH_PF_PSMALL, mdh_device.h: partitioning_closest_bits)
-   const bool psmall = pf == MDH_PF_PART && r->ks.part_small && r->ks.part_tmask[PK_TRIANGLE] == 0 && r->ks.part_sp_pow2 && r->ks.part_cells < (1 << 24) && MDH_ROOM_VARIANTS && !gtab;
+   const bool psmall = pf == MDH_PF_PART && r->ks.part_small && r->ks.part_tmask[PK_TRIANGLE] == 0 && r->ks.part_sp_pow2 && r->ks.part_cells < (1 << 24) && !gtab;
    const int pfk = gtab ? (pf | MDH_PF_GTAB) : room ? MDH_PF_ROOM : (psmall ? (MDH_PF_PART | MDH_PF_PSMALL) : pf); // (the kernel variant by the scene's census)
    // the probe-sampling kernels (radiance, mode-0 screen) have a variant for atlases whose every dimension is a power of two
    auto is_pow2 = [](int v) { return v > 0 && (v & (v - 1)) == 0; };
@@ -1944,7 +1922,7 @@ static int run_pass(mdh_renderer *r, int pass, hipStream_t st, int src, int dst,
       if (pr.ires * pr.ires <= 64) lds += (size_t)4 * 64 * sizeof(float4); // (the experiment's fold: all taps staged, four partial sums per texel)
       else
 #endif
-      if (MDH_IRR_CHANNELS && pr.ires * pr.ires <= 64 && MDH_IRR_BLOCK == 256 && n > 0) { // (k_irradiance: a channel per wavefront, the taps through device memory)
+      if (pr.ires * pr.ires <= 64 && MDH_IRR_BLOCK == 256 && n > 0) { // (k_irradiance: a channel per wavefront, the taps through device memory)
          const size_t need = (size_t)n * 6 * MDH_IRR_CHANNELS_PLANE(pr.rres * pr.rres);
          if (need > r->irr_taps_cap) { // (the scratch of irradiance passes only, which follow one another on their stream)
             if (r->probe_stream) HIP_TRY(hipStreamSynchronize(r->probe_stream));
@@ -1957,12 +1935,7 @@ static int run_pass(mdh_renderer *r, int pass, hipStream_t st, int src, int dst,
          tap_planes = r->d_irr_taps;
          lds = MDH_IRR_CHANNELS_LDS;
       } else
-      if (MDH_IRR_WPRE && pr.ires * pr.ires <= 64 && MDH_IRR_BLOCK == 256) lds = MDH_IRR_WPRE_LDS; // (k_irradiance: the weights' pipeline)
-      else
-      if (MDH_IRR_CHUNK && pr.ires * pr.ires <= 64 && lds > (size_t)4 * MDH_IRR_CHUNK * sizeof(float4)) lds = (size_t)4 * MDH_IRR_CHUNK * sizeof(float4); // two chunk buffers
-#ifdef MDH_IRR_LDS_PAD
-      lds += MDH_IRR_LDS_PAD; // (experiment: what the pass's LDS footprint costs it beside the march kernels of frames in flight)
-#endif
+      if (pr.ires * pr.ires <= 64 && lds > (size_t)4 * MDH_IRR_CHUNK * sizeof(float4)) lds = (size_t)4 * MDH_IRR_CHUNK * sizeof(float4); // two chunk buffers
       if (lds > 64 * 1024) { // radiance tiles beyond 45 x 45 texels: up to the whole 160 KiB of a CU (70 x 70)
          if (lds > 160 * 1024) return seterr(MDH_E_INVALID, "radiance resolution too large for the irradiance pass (160 KiB of LDS: at most 70)");
          if (!r->irr_lds_granted) { // (the attribute belongs to the function on THIS device: kept per renderer, not per process)
@@ -1978,17 +1951,11 @@ static int run_pass(mdh_renderer *r, int pass, hipStream_t st, int src, int dst,
       KVolumetrics vol = make_vol(r, true, dst);
       long n = (long)vol.vw * vol.vh * vol.vz;
       if (n > 0) {
-#if MDH_VIS_QUEUE
-         const long per_block = (long)MDH_BLOCK * MDH_VIS_ROUNDS; // every wavefront owns MDH_VIS_ROUNDS x 64 froxels (k_visibility)
-         int blocks = (int)((n + per_block - 1) / per_block);
-#else
-         const long per_block = (long)MDH_BLOCK * MDH_VIS_LOOP;
-         int blocks = (int)((n + per_block - 1) / per_block);
-#endif
+         int blocks = (int)((n + MDH_BLOCK - 1) / MDH_BLOCK);
          // inside a frame the launch also marches the scattering texels' camera rays (k_visibility's second part, mdh_kernels.h)
          const int vis_blocks = blocks;
          if (MDH_SCAT_SPLIT && r->fuse_scat_march) blocks += (int)(((long)vol.sw * vol.sh + MDH_BLOCK - 1) / MDH_BLOCK);
-         const size_t vis_lds = lds_bytes(r) + (MDH_VIS_QUEUE == 2 ? (size_t)(MDH_BLOCK / 64) * MDH_VIS_Q_FLOATS * sizeof(float) : 0); // (the second form of the ray queue keeps its rays in LDS)
+         const size_t vis_lds = lds_bytes(r);
          if (jit) {
             struct { KScene sc; KVolumetrics vol; KCamera cam; int vis_blocks; } args = {r->ks, vol, cam, vis_blocks};
             int rc = jit_launch(jm->fn[kname], blocks, MDH_BLOCK, vis_lds, st, args);
@@ -2086,17 +2053,13 @@ static int run_pass(mdh_renderer *r, int pass, hipStream_t st, int src, int dst,
       // MDH_OPT_SCREEN_SPLIT (ScreenArgs::split): launches that leave most of the chip's wavefront slots empty give a tile to
       // two or four wavefronts; never with a tile order (launches of 2 048 tiles and more)
       a.split = 0;
-      a.split_first = 0;
+      a.split_first = 0; // (no launch splits the slowest tiles of an order: ScreenArgs)
       if (!a.order && !a.cost && r->opt_scr_split > 0 && a.world == 1) { // (a rank's scattered tiles of a sharded frame: measured 1 - 3 % slower split, profiles/r04_x_split_tiles.log)
          if ((long)own_tiles * 4 <= r->opt_scr_split) a.split = 2;
          else if ((long)own_tiles * 2 <= r->opt_scr_split) a.split = 1;
       }
-      // ... and of an ordered launch the slowest tiles (MADARCH_HIP_SPLIT_FIRST, thousandths of the launch's tiles; a pass that
-      // records the tiles' durations draws every tile with one wavefront: the key is the tile's)
-      static const int split_first_env = [] { const char *e = getenv("MADARCH_HIP_SPLIT_FIRST"); return e ? atoi(e) : MDH_SCREEN_SPLIT_FIRST_PERMILLE; }();
-      if (a.order && !a.cost && r->opt_scr_split > 0 && split_first_env > 0) a.split_first = (int)((long)own_tiles * split_first_env / 1000);
       if (own_tiles > 0) {
-         const long waves = ((long)own_tiles << a.split) + 3l * a.split_first;
+         const long waves = (long)own_tiles << a.split;
          int blocks = (int)((waves + (MDH_BLOCK / 64) - 1) / (MDH_BLOCK / 64));
          if (jit) {
             struct { KScene sc; KProbes pr; KVolumetrics vol; KCamera cam; ScreenArgs a; } args = {r->ks, pr, vol, cam, a};
@@ -2142,11 +2105,9 @@ static int run_pass(mdh_renderer *r, int pass, hipStream_t st, int src, int dst,
          // dependency chain -- waiting for slots that the thin tail of an image-order pass hands over early: -3 %.
          // There only the tiles that took twice the median and more go to the front (the ones that make the tail) and
          // all others keep their place: +-0 in flight (profiles/r03_x_screen_tile_order.log).
-         // MADARCH_HIP_ORDER_FLOOR (thousandths of the median) overrides, for experiments.
-         static const int floor_env = [] { const char *e = getenv("MADARCH_HIP_ORDER_FLOOR"); return e ? atoi(e) : -1; }();
          const long probe_rays = r->opt_mode == 0 ? (long)(pr.probe_end - pr.probe_begin) * pr.rres * pr.rres : 0;
          const bool probe_heavy = probe_rays * 10 >= (long)own_tiles * 64;
-         const int floor_permille = floor_env >= 0 ? floor_env : (r->frame_pipelined && r->in_frame_passes && probe_heavy ? 2000 : 0);
+         const int floor_permille = r->frame_pipelined && r->in_frame_passes && probe_heavy ? 2000 : 0; // (thousandths of the median)
          hipLaunchKernelGGL(k_rad_hist, dim3(chunks), dim3(256), 0, st, (const unsigned char *)r->d_scr_cost, own_tiles, (int)chunk, r->d_scr_hist);
          if (floor_permille > 0) {
             hipLaunchKernelGGL(k_order_floor, dim3(chunks), dim3(256), 0, st, r->d_scr_cost, own_tiles, (int)chunk, (const unsigned *)r->d_scr_hist, chunks, floor_permille);
@@ -2272,9 +2233,6 @@ extern "C" int32_t mdh_frame_probe_pass(mdh_renderer *r, int32_t pass)
    if (r->opt_mode != 0) return MDH_OK; // modes 1 and 2 draw without probes (renderers.adb:302-321 runs them anyway; nothing reads them)
    return run_pass(r, pass, frame_probe_stream(r), r->last, r->frame_cur);
 }
-#ifndef MDH_VOL_OWN_STREAM
-#define MDH_VOL_OWN_STREAM 1
-#endif
 static int frame_end_passes(mdh_renderer *r);
 extern "C" int32_t mdh_frame_end(mdh_renderer *r)
 {
@@ -2311,7 +2269,7 @@ static int frame_end_passes(mdh_renderer *r)
    if (r->opt_mode == 0 && r->vol.enabled) {
       // camera-only passes into this frame's set: on a stream of their own, beside this frame's probe
       // passes and the previous screen pass -- they are a few hundred wavefronts each and wait for nothing the probes make
-      hipStream_t vs = MDH_VOL_OWN_STREAM && r->vol_stream ? r->vol_stream : r->probe_stream;
+      hipStream_t vs = r->vol_stream ? r->vol_stream : r->probe_stream;
       r->fuse_scat_march = true;
       rc = run_pass(r, MDH_PASS_VISIBILITY, vs, cur, cur);
       if (rc == MDH_OK) rc = run_pass(r, MDH_PASS_SCATTERING, vs, cur, cur);

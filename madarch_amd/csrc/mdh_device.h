@@ -71,8 +71,8 @@ struct KScene {
    int part_small;
    unsigned part_tbit[4], part_tmask[4];
    float part_fdims[3], part_fyz; // (float)part_dims[a] and (float)(part_dims[1] * part_dims[2]): the same conversions, once on the host
-   // MDH_SDF_SGPR: the first sphere and the first box of the table once more, as kernel arguments -- scalar operands of the
-   // brute-force scan (closest_primitive) instead of three LDS broadcast reads into twelve vector registers per evaluation
+   // no kernel reads these and the host leaves them zero (they were the scalar operands of a removed form of the brute-force
+   // scan); they stay so that the kernels' argument block keeps its layout
    float first_sphere[4], first_box[8];
 };
 // int block at table[0..]: per-kind data in SCENE order (the order the flat primitive index
@@ -197,41 +197,21 @@ MDH_DEV f2 F2(float x, float y) { f2 r; r.x = x; r.y = y; return r; }
 MDH_DEV f3 xyz(float4 v) { return F3(v.x, v.y, v.z); }
 
 // min/max = IEEE minNum/maxNum.  __builtin_fminf costs a canonicalising v_max_f32 per operand in
-// IEEE mode; issuing the instruction directly (MDH_ASM_MINMAX=1) removes it but measured 3 % SLOWER
-// on MI355X (the opaque asm defeats the scheduler), so the builtin stays the default.
-#ifndef MDH_ASM_MINMAX
-#define MDH_ASM_MINMAX 0
-#endif
-#if MDH_ASM_MINMAX
-MDH_DEV float min_(float a, float b) { float r; asm("v_min_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b)); return r; }
-MDH_DEV float max_(float a, float b) { float r; asm("v_max_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b)); return r; }
-#else
+// IEEE mode; issuing the instruction directly removes it but measured 3 % SLOWER on MI355X (the
+// opaque asm defeats the scheduler), so it is the builtin.
 MDH_DEV float min_(float a, float b) { return __builtin_fminf(a, b); } // v_min_f32: minNum
 MDH_DEV float max_(float a, float b) { return __builtin_fmaxf(a, b); }
-#endif
 // The same two operations as bare instructions, for operands that reach them across a branch: there the compiler
 // cannot see that a value is no signaling NaN (none exists on this path: every operand is an arithmetic
 // result) and quiets it with a v_max_f32 x, x first -- six or seven of the ~75 instructions of one SDF evaluation.
-#ifndef MDH_RAW_MINMAX
-#define MDH_RAW_MINMAX 1
-#endif
-#if MDH_RAW_MINMAX
 MDH_DEV float min_raw(float a, float b) { float r; asm("v_min_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b)); return r; }
 MDH_DEV float max0_raw(float a) { float r; asm("v_max_f32 %0, 0, %1" : "=v"(r) : "v"(a)); return r; }
 MDH_DEV float min0_raw(float a) { float r; asm("v_min_f32 %0, 0, %1" : "=v"(r) : "v"(a)); return r; }
-#else
-MDH_DEV float min_raw(float a, float b) { return min_(a, b); }
-MDH_DEV float max0_raw(float a) { return max_(a, 0.0f); }
-MDH_DEV float min0_raw(float a) { return min_(a, 0.0f); }
-#endif
 
 // Correctly rounded sqrt.  hipcc's expansion (v_sqrt_f32 + two fma residual tests) also rescales
-// inputs below 2^-96 and re-selects 0/inf with a class test on every call; MDH_FAST_EXACT_SQRT=1
-// sends those inputs down a rare branch and keeps the 9-instruction core (same result for every
-// input).  Measured 5 % SLOWER on MI355X than the compiler's branch-free form: off by default.
-#ifndef MDH_FAST_EXACT_SQRT
-#define MDH_FAST_EXACT_SQRT 0
-#endif
+// inputs below 2^-96 and re-selects 0/inf with a class test on every call.  (Sending those inputs
+// down a rare per-lane branch around the 9-instruction core measured 5 % SLOWER on MI355X than the
+// compiler's branch-free form; the wave-wide guard of sqrt_ below is what won.)
 // The core of that expansion by itself: v_sqrt_f32, its two neighbours, two fma residuals, two selects -- the
 // compiler's own nine instructions, hence its result, for every input that it does not rescale: 0, anything from
 // 2^-96 up, infinities and NaN (for 0 both residual tests fail and the 0 of v_sqrt_f32 stands).  For callers that
@@ -257,28 +237,15 @@ MDH_DEV float sqrt_unscaled_(float x)
    s = (vs > 0.0f) ? su : s;
    return s;
 }
-#ifndef MDH_SQRT_WAVE_ALL
-#define MDH_SQRT_WAVE_ALL 1 // every correctly rounded root through the nine-instruction core behind a wave-wide guard (sqrt_wave_ below): the same bits; config 3 serial +1.7 %, in flight +-0
-#endif
+// every correctly rounded root through the nine-instruction core behind a wave-wide guard: the same bits; measured config 3 serial +1.7 %, in flight +-0
 MDH_DEV float sqrt_(float x)
 {
 #if MDH_FAST_NUMERICS
    return __builtin_amdgcn_sqrtf(x);
 #endif
-#if MDH_SQRT_WAVE_ALL
    if (__ballot(x < 0x1p-96f && x > 0.0f) != 0ull) return __builtin_sqrtf(x);
    return sqrt_unscaled_(x);
-#endif
-#if MDH_FAST_EXACT_SQRT
-   if (__builtin_expect(x < 0x1p-96f && x > 0.0f, 0)) return __builtin_sqrtf(x);
-   return sqrt_unscaled_(x);
-#else
-   return __builtin_sqrtf(x);
-#endif
 }
-#ifndef MDH_PART_SQRT_WAVE
-#define MDH_PART_SQRT_WAVE 1
-#endif
 // the correctly rounded root of a wavefront's operands through the nine-instruction core when none of them is a positive
 // number below 2^-96 (the only inputs hipcc's expansion rescales: sqrt_unscaled_ above), through the full expansion otherwise
 MDH_DEV float sqrt_wave_(float x)
@@ -286,32 +253,8 @@ MDH_DEV float sqrt_wave_(float x)
 #if MDH_FAST_NUMERICS
    return __builtin_amdgcn_sqrtf(x);
 #endif
-#if MDH_PART_SQRT_WAVE
    if (__ballot(x < 0x1p-96f && x > 0.0f) != 0ull) return sqrt_(x);
    return sqrt_unscaled_(x);
-#else
-   return sqrt_(x);
-#endif
-}
-// Two correctly rounded roots at once (the rooms' scan: its one sphere and its one box), the two nine-instruction cores
-// interleaved: a core's comparisons each wait two slots for their select (a vector comparison's mask is not forwarded), and
-// a core alone has nothing to put there -- the other core's instructions go there, and one wave-wide guard serves both.
-// The same nine operations per operand: the same bits.
-MDH_DEV void sqrt2_(float a, float b, float &ra, float &rb)
-{
-#if MDH_FAST_NUMERICS
-   ra = __builtin_amdgcn_sqrtf(a); rb = __builtin_amdgcn_sqrtf(b);
-   return;
-#endif
-   if (__ballot(min_(a, b) < 0x1p-96f) != 0ull) { ra = __builtin_sqrtf(a); rb = __builtin_sqrtf(b); return; } // (a zero goes the slow way too: never in a march)
-   float sa = __builtin_amdgcn_sqrtf(a), sb = __builtin_amdgcn_sqrtf(b);
-   const int ia = __float_as_int(sa), ib = __float_as_int(sb);
-   const float sda = __int_as_float(ia - 1), sdb = __int_as_float(ib - 1), sua = __int_as_float(ia + 1), sub = __int_as_float(ib + 1);
-   const float vpa = __builtin_fmaf(-sda, sa, a), vpb = __builtin_fmaf(-sdb, sb, b), vsa = __builtin_fmaf(-sua, sa, a), vsb = __builtin_fmaf(-sub, sb, b);
-   const bool ca = vpa <= 0.0f, cb = vpb <= 0.0f, ea = vsa > 0.0f, eb = vsb > 0.0f;
-   sa = ca ? sda : sa; sb = cb ? sdb : sb;
-   sa = ea ? sua : sa; sb = eb ? sub : sb;
-   ra = sa; rb = sb;
 }
 // MDH_HYBRID_NUMERICS: the second LABELLED EXPERIMENT (`make -C madarch_amd/csrc hybrid`; never the shipped
 // library): every operation INSIDE a march loop and the whole primary ray (geometry buffer: index, t, steps) stay as exact
@@ -750,18 +693,6 @@ template <typename TAB> MDH_DEV float prim_dist(TAB tab, int type, int slot, f3 
 #ifndef MDH_INFO_UNROLL
 #define MDH_INFO_UNROLL 1
 #endif
-#ifndef MDH_PART_PREFETCH
-#define MDH_PART_PREFETCH 1
-#endif
-#ifndef MDH_FAST_INFO
-#define MDH_FAST_INFO 1
-#endif
-#ifndef MDH_PART_SMALL
-#define MDH_PART_SMALL 1 // small scenes walk a cell's bits in straight-line code (KScene::part_small)
-#endif
-#ifndef MDH_PART_BITS
-#define MDH_PART_BITS 1 // the distance-only partition lookup walks a cell's candidates as bits (partitioning_closest_bits)
-#endif
 #ifndef MDH_SDF_UNROLL
 #define MDH_SDF_UNROLL 2
 #endif
@@ -776,21 +707,6 @@ template <typename TAB> MDH_DEV float prim_dist(TAB tab, int type, int slot, f3 
 //   sphere: d = sqrt(d2) - r >= closest  <=  d2 > (closest + r)^2 (1 + 1e-6), or closest + r < 0
 //   box:    d >= m (1 - 2^-23) with m = max(q.x, q.y, q.z); skip when m > closest (1 + 1e-6)
 //           (for m <= 0 the distance IS m, for closest <= 0 the test m > closest is exact)
-#ifndef MDH_CULL
-#define MDH_CULL 1
-#endif
-#ifndef MDH_SDF_PREFETCH
-#define MDH_SDF_PREFETCH 1
-#endif
-#ifndef MDH_ROOM_SQRT2
-#define MDH_ROOM_SQRT2 0 // the rooms' scan evaluates its sphere and its box together, their square-root cores interleaved (sqrt2_)
-#endif
-#ifndef MDH_SDF_SGPR
-#define MDH_SDF_SGPR 0
-#endif
-#ifndef MDH_SDF_SQRT_WAVE
-#define MDH_SDF_SQRT_WAVE 0 // the brute-force scan's sphere and box roots through sqrt_wave_ (below)
-#endif
 // The first sphere and the first box of the table in registers: a march loop that evaluates the SDF many times
 // reads them from LDS once (MDH_SDF_REGS) instead of once per evaluation.  (With a count of 0 the words
 // belong to the next kind and are not used.)
@@ -799,10 +715,6 @@ template <bool GTAB = false> MDH_DEV SdfRegs sdf_regs(const KScene &sc)
 {
    const typename Geo<GTAB>::F4 s_tab = Geo<GTAB>::f4(sc); // (shadows the LDS table: global residency reads the image)
    SdfRegs r;
-#if MDH_SDF_SGPR
-   r.s = r.b0 = r.b1 = make_float4(0.0f, 0.0f, 0.0f, 0.0f); // (unused: closest_primitive takes the kernel arguments)
-   return r;
-#endif
    r.s = s_tab[sc.tslot[PK_SPHERE]];
    r.b0 = s_tab[sc.tslot[PK_BOX]]; r.b1 = s_tab[sc.tslot[PK_BOX] + 1];
    return r;
@@ -816,38 +728,16 @@ template <bool CUSTOM, bool ROOM = false, bool GTAB = false> MDH_DEV float close
 {
    const typename Geo<GTAB>::F4 s_tab = Geo<GTAB>::f4(sc); // (shadows the LDS table: global residency reads the image; every index below is wave-uniform)
    float closest = sc.max_dist;
-#if MDH_SDF_SGPR
-   const float4 pf_s = make_float4(sc.first_sphere[0], sc.first_sphere[1], sc.first_sphere[2], sc.first_sphere[3]);
-   const float4 pf_b0 = make_float4(sc.first_box[0], sc.first_box[1], sc.first_box[2], sc.first_box[3]), pf_b1 = make_float4(sc.first_box[4], sc.first_box[5], sc.first_box[6], sc.first_box[7]);
-#elif MDH_SDF_PREFETCH
    // the first sphere and the first box are on their way from LDS while the planes are evaluated: a wavefront that
    // has a SIMD to itself (the tail of every pass, and whole passes of a sharded frame) has nothing else to
    // hide that latency behind.
    const float4 pf_s = regs ? regs->s : s_tab[sc.tslot[PK_SPHERE]];
    const float4 pf_b0 = regs ? regs->b0 : s_tab[sc.tslot[PK_BOX]], pf_b1 = regs ? regs->b1 : s_tab[sc.tslot[PK_BOX] + 1];
-#endif
    if (ROOM || sc.n_axis > 0) { // six adds for all axis-aligned planes together
       closest = min_(closest, min_(x.x + sc.axis_off[0], -x.x + sc.axis_off[1]));
       closest = min_(closest, min_(x.y + sc.axis_off[2], -x.y + sc.axis_off[3]));
       closest = min_(closest, min_(x.z + sc.axis_off[4], -x.z + sc.axis_off[5]));
    }
-#if MDH_ROOM_SQRT2
-   if (ROOM) { // the one sphere and the one box together (sqrt2_ above); the box's cull against the minimum BEFORE the sphere: never less careful
-      const float d2 = dot2(xyz(pf_s) - x);
-      const float tsum = closest + pf_s.w;
-      const bool need_s = !(tsum < 0.0f) && !(d2 > (tsum * tsum) * 1.000001f);
-      const f3 q = abs3(xyz(pf_b0) - x) - xyz(pf_b1);
-      const float m = max_(q.x, max_(q.y, q.z));
-      const float thr = closest > 0.0f ? closest * 1.000001f : closest;
-      if (!MDH_CULL || __ballot(need_s || !(m > thr)) != 0ull) {
-         float rs, rb;
-         sqrt2_(d2, dot2(F3(max0_raw(q.x), max0_raw(q.y), max0_raw(q.z))), rs, rb);
-         closest = min_raw(closest, rs - pf_s.w);
-         closest = min_raw(closest, rb + min0_raw(m));
-      }
-      return closest;
-   }
-#endif
    {
       const int n = ROOM ? 0 : sc.gplane_count, s0 = sc.gplane_slot;
 #pragma unroll MDH_SDF_UNROLL
@@ -861,16 +751,11 @@ template <bool CUSTOM, bool ROOM = false, bool GTAB = false> MDH_DEV float close
          const float d2 = dot2(xyz(a) - x); /* sd_sphere = sqrt(d2) - a.w (spheres.ads:13-14) */ \
          const float tsum = closest + a.w;                                                   \
          const bool need = !(tsum < 0.0f) && !(d2 > (tsum * tsum) * 1.000001f);              \
-         if (!MDH_CULL || __ballot(need) != 0ull) closest = min_raw(closest, (MDH_SDF_SQRT_WAVE ? sqrt_wave_(d2) : sqrt_(d2)) - a.w); \
+         if (__ballot(need) != 0ull) closest = min_raw(closest, sqrt_(d2) - a.w); \
       } while (0)
-#if MDH_SDF_PREFETCH
       if (n > 0) MDH_SPHERE_STEP(pf_s);
 #pragma unroll 1
       for (int i = 1; i < n; ++i) MDH_SPHERE_STEP(s_tab[uni<GTAB>(s0 + i)]);
-#else
-#pragma unroll 1
-      for (int i = 0; i < n; ++i) MDH_SPHERE_STEP(s_tab[uni<GTAB>(s0 + i)]);
-#endif
 #undef MDH_SPHERE_STEP
    }
    {
@@ -880,17 +765,12 @@ template <bool CUSTOM, bool ROOM = false, bool GTAB = false> MDH_DEV float close
          const f3 q = abs3(xyz(c_) - x) - xyz(e_); /* boxes.adb:10 */                        \
          const float m = max_(q.x, max_(q.y, q.z));                                          \
          const float thr = closest > 0.0f ? closest * 1.000001f : closest;                   \
-         if (!MDH_CULL || __ballot(!(m > thr)) != 0ull)                                      \
-            closest = min_raw(closest, (MDH_SDF_SQRT_WAVE ? sqrt_wave_(dot2(F3(max0_raw(q.x), max0_raw(q.y), max0_raw(q.z)))) : length(F3(max0_raw(q.x), max0_raw(q.y), max0_raw(q.z)))) + min0_raw(m)); \
+         if (__ballot(!(m > thr)) != 0ull)                                                   \
+            closest = min_raw(closest, length(F3(max0_raw(q.x), max0_raw(q.y), max0_raw(q.z))) + min0_raw(m)); \
       } while (0)
-#if MDH_SDF_PREFETCH
       if (n > 0) MDH_BOX_STEP(pf_b0, pf_b1);
 #pragma unroll 1
       for (int i = 1; i < n; ++i) MDH_BOX_STEP(s_tab[uni<GTAB>(s0 + 2 * i)], s_tab[uni<GTAB>(s0 + 2 * i + 1)]);
-#else
-#pragma unroll 1
-      for (int i = 0; i < n; ++i) MDH_BOX_STEP(s_tab[uni<GTAB>(s0 + 2 * i)], s_tab[uni<GTAB>(s0 + 2 * i + 1)]);
-#endif
 #undef MDH_BOX_STEP
    }
    {
@@ -921,7 +801,6 @@ template <bool CUSTOM, bool GTAB = false> MDH_DEV float closest_primitive_info(c
 {
    const typename Geo<GTAB>::F4 s_tab = Geo<GTAB>::f4(sc); // (shadows the LDS table, as in closest_primitive)
    float closest = sc.max_dist;
-#if MDH_FAST_INFO
    // The same arg-min by TYPE, with the six folded axis planes and without the per-kind dispatch: a candidate wins
    // when it is closer, or as close with a lower flat index -- what the scan in scene order keeps (the first of
    // equal distances).  Only for scenes whose planes are all folded, one per direction (H_FASTINFO).
@@ -961,7 +840,6 @@ template <bool CUSTOM, bool GTAB = false> MDH_DEV float closest_primitive_info(c
       if (best >= 0) index = best;
       return closest;
    }
-#endif
    const int nk = hdr(H_NK);
 #pragma unroll 1
    for (int k = 0; k < nk; ++k) {
@@ -1027,18 +905,10 @@ template <bool PSMALL = false> MDH_DEV int partition_cell_clamped(const KScene &
 {
    const f3 rel = x - F3(sc.part_off[0], sc.part_off[1], sc.part_off[2]);
    const f3 fx = floor3((PSMALL || sc.part_sp_pow2) ? rel * F3(sc.part_inv_sp[0], sc.part_inv_sp[1], sc.part_inv_sp[2]) : rel / F3(sc.part_sp[0], sc.part_sp[1], sc.part_sp[2]));
-#if MDH_PART_CELL_TRIM
-   // clamp (v, 0, d) = min (max (v, 0), d) as ONE instruction: v_med3_f32 is the median of its operands and, with a NaN among
-   // them, their minNum -- 0 for v = NaN, as the two-instruction form gives (max (NaN, 0) = 0; d >= 0)
-   const f3 cfx = F3(__builtin_amdgcn_fmed3f(fx.x, 0.0f, sc.part_fdims[0]), __builtin_amdgcn_fmed3f(fx.y, 0.0f, sc.part_fdims[1]), __builtin_amdgcn_fmed3f(fx.z, 0.0f, sc.part_fdims[2]));
-   const float yz = sc.part_fyz, zz = sc.part_fdims[2];
-   // (every term and every partial sum is an integer below 2^24 for tables of fewer than 2^24 cells: the two fused forms round
-   //  nothing that the four separate operations would not -- the same value with two instructions instead of four)
-   if (PSMALL || sc.part_cells < (1 << 24)) return (int)__builtin_fmaf(cfx.x, yz, __builtin_fmaf(cfx.y, zz, cfx.z));
-#else
+   // (measured elsewhere and never in a shipped build -- its switch was defined behind this function: the clamp as one
+   //  v_med3_f32 and the index as two fused multiply-adds)
    const f3 cfx = F3(clamp_(fx.x, 0.0f, sc.part_fdims[0]), clamp_(fx.y, 0.0f, sc.part_fdims[1]), clamp_(fx.z, 0.0f, sc.part_fdims[2]));
    const float yz = sc.part_fyz, zz = sc.part_fdims[2];
-#endif
    return (int)((cfx.x * yz + cfx.y * zz) + cfx.z);
 }
 // partitioning_closest[_info] (scenes.adb:839-1118): per-lane cell record from HBM/L2,
@@ -1053,7 +923,6 @@ template <bool INFO, bool CUSTOM, bool FALLBACK = true, bool PSMALL = false, boo
    if (cell < 0 || cell >= sc.part_cells) return closest;
    const int nk = hdr(H_NK);
    const int *rec = sc.part_table + (size_t)cell * (nk + sc.part_index_count);
-#if MDH_PART_PREFETCH
    // every record word is asked for one step before it is needed (the count of the next kind, the next candidate
    // index): the L2 round trips of a cell overlap with the distance evaluations instead of adding up
    int i = 0, cnt = rec[0], pi_next = rec[nk];
@@ -1072,21 +941,6 @@ template <bool INFO, bool CUSTOM, bool FALLBACK = true, bool PSMALL = false, boo
       i = size;
       cnt = cnt_next;
    }
-#else
-   int i = 0;
-#pragma unroll 1
-   for (int k = 0; k < nk; ++k) {
-      const int size = i + rec[k], type = hdr(H_KTYPE + k), s0 = hdr(H_KSLOT + k), base = hdr(H_KBASE + k);
-      const int stop = min(size, sc.part_index_count);
-      for (; i < stop; ++i) {
-         int pi = rec[nk + i];
-         float d = (CUSTOM && type == PK_CUSTOM) ? xdist<false>(k, pi, x) : prim_dist(geo, type, s0 + prim_slots(type) * pi, x);
-         if (INFO) { if (d < closest) { closest = d; index = base + pi; } }
-         else closest = min_raw(closest, d);
-      }
-      i = size;
-   }
-#endif
    return closest;
 }
 // partitioning_closest (scenes.adb:839-958) from the cell's candidates as BITS.
@@ -1119,18 +973,6 @@ template <bool INFO, bool CUSTOM, bool FALLBACK = true, bool PSMALL = false, boo
 // running one first FLUSHES the running minimum through its square root (behind a ballot: skipped by the wave when no
 // lane's radius changes -- never in simple_scene).  And the last root of either kind is culled like the brute-force scan's
 // (closest_primitive above): skipped by the wave when no lane's bound can still lower `closest`.
-#ifndef MDH_PART_MERGE_ROOTS
-#define MDH_PART_MERGE_ROOTS 1
-#endif
-#ifndef MDH_PART_PLANE_SINGLE
-#define MDH_PART_PLANE_SINGLE 1
-#endif
-#ifndef MDH_PART_ALIGNBIT
-#define MDH_PART_ALIGNBIT 0 // (measured: the scalar branch of the funnel-shift form costs more than the 64-bit shift it replaces, -4 % on simple_scene)
-#endif
-#ifndef MDH_PART_CELL_TRIM
-#define MDH_PART_CELL_TRIM 1
-#endif
 template <typename TAB> MDH_DEV float walk_planes_single(unsigned w, TAB t, f3 x, float closest)
 {
    while (w) { // (a cell of the reference's scenes names one or two planes: pairs evaluated most of them twice)
@@ -1159,7 +1001,7 @@ template <typename TAB> MDH_DEV float walk_spheres_merged(unsigned w, TAB t, f3 
    }
    const float tsum = closest + r_cur;
    const bool need = !(tsum < 0.0f) && !(S > (tsum * tsum) * 1.000001f); // (closest_primitive's cull; S = inf: no candidate, never needed)
-   if (!MDH_CULL || __ballot(need) != 0ull) closest = min_raw(closest, sqrt_wave_(S) - r_cur);
+   if (__ballot(need) != 0ull) closest = min_raw(closest, sqrt_wave_(S) - r_cur);
    return closest;
 }
 template <typename TAB> MDH_DEV float walk_boxes_merged(unsigned w, TAB t, f3 x, float closest)
@@ -1177,7 +1019,7 @@ template <typename TAB> MDH_DEV float walk_boxes_merged(unsigned w, TAB t, f3 x,
    // sqrt (S) + U: U < 0 means S = 0 and the value is U itself; otherwise it is sqrt (S) >= 0, which cannot lower a negative
    // `closest` and cannot lower a positive one when S > closest^2 (1 + 1e-6)
    const bool need = !(U < 0.0f) && !(closest < 0.0f) && !(S > (closest * closest) * 1.000001f);
-   if (!MDH_CULL || __ballot(need) != 0ull) closest = min_raw(closest, sqrt_wave_(S) + U);
+   if (__ballot(need) != 0ull) closest = min_raw(closest, sqrt_wave_(S) + U);
    else closest = min_raw(closest, U < 0.0f ? U : closest);
    return closest;
 }
@@ -1206,11 +1048,9 @@ MDH_DEV float walk_triangles(unsigned w, const float4 *t, f3 x, float closest) /
 }
 template <int TYPE, typename TAB> MDH_DEV float walk_bits(unsigned w, TAB t, f3 x, float closest)
 {
-#if MDH_PART_MERGE_ROOTS
    if (TYPE == PK_SPHERE) return walk_spheres_merged(w, t, x, closest);
    if (TYPE == PK_BOX) return walk_boxes_merged(w, t, x, closest);
-   if (TYPE == PK_PLANE && MDH_PART_PLANE_SINGLE) return walk_planes_single(w, t, x, closest);
-#endif
+   if (TYPE == PK_PLANE) return walk_planes_single(w, t, x, closest);
    if (TYPE == PK_TRIANGLE) return walk_triangles(w, t, x, closest);
    while (w) {
       MDH_DIAG_STEP(6);
@@ -1248,17 +1088,12 @@ template <bool CUSTOM, bool FALLBACK, bool PSMALL = false, bool GTAB = false> MD
    float closest = sc.max_dist;
    if (cell < 0 || cell >= sc.part_cells) return closest;
    MDH_DIAG_STEP(5); // lookups that reach a cell
-   if (!CUSTOM && MDH_PART_SMALL && (PSMALL || sc.part_small)) { // (wave-uniform) straight-line code: one load, a shift and a mask per type
+   if (!CUSTOM && (PSMALL || sc.part_small)) { // (wave-uniform) straight-line code: one load, a shift and a mask per type
       typedef const unsigned long long __attribute__((address_space(1))) *GlobalPairs;
       const unsigned long long mm = ((GlobalPairs)(sc.part_table + sc.part_mask_off))[cell];
-      // a type's candidates: 32 bits of the cell's 64 from bit part_tbit on -- one funnel shift (v_alignbit_b32) while the
-      // type starts in the low dword, a plain shift of the high one otherwise (part_tbit is uniform: a scalar branch)
-#if MDH_PART_ALIGNBIT
-      const unsigned mlo = (unsigned)mm, mhi = (unsigned)(mm >> 32);
-#define MDH_TYPE_BITS(T) ((sc.part_tbit[T] < 32u ? __builtin_amdgcn_alignbit(mhi, mlo, sc.part_tbit[T]) : (mhi >> (sc.part_tbit[T] - 32u))) & sc.part_tmask[T])
-#else
+      // a type's candidates: 32 bits of the cell's 64 from bit part_tbit on (measured: a funnel shift, v_alignbit_b32, behind a
+      // scalar branch on part_tbit costs more than the 64-bit shift it replaces, -4 % on simple_scene)
 #define MDH_TYPE_BITS(T) ((unsigned)(mm >> sc.part_tbit[T]) & sc.part_tmask[T])
-#endif
       if (PSMALL || sc.part_tmask[PK_PLANE]) closest = walk_bits<PK_PLANE>(MDH_TYPE_BITS(PK_PLANE), geo + sc.tslot[PK_PLANE], x, closest);
       if (PSMALL || sc.part_tmask[PK_SPHERE]) closest = walk_bits<PK_SPHERE>(MDH_TYPE_BITS(PK_SPHERE), geo + sc.tslot[PK_SPHERE], x, closest);
       if (PSMALL || sc.part_tmask[PK_BOX]) closest = walk_bits<PK_BOX>(MDH_TYPE_BITS(PK_BOX), geo + sc.tslot[PK_BOX], x, closest);
@@ -1322,18 +1157,14 @@ template <bool CUSTOM, bool FALLBACK, bool PSMALL = false, bool GTAB = false> MD
 template <int PART> MDH_DEV float sdf(const KScene &sc, f3 x)
 {
    MDH_WORK(2);
-   int dummy;
-   (void)dummy;
-   if (PART & MDH_PF_PART) return MDH_PART_BITS ? partitioning_closest_bits<(PART & MDH_PF_CUSTOM) != 0, MDH_PF_HAS_FALLBACK(PART), (PART & MDH_PF_PSMALL) != 0, (PART & MDH_PF_GTAB) != 0>(sc, x) : partitioning_lookup<false, (PART & MDH_PF_CUSTOM) != 0, MDH_PF_HAS_FALLBACK(PART), (PART & MDH_PF_PSMALL) != 0, (PART & MDH_PF_GTAB) != 0>(sc, x, dummy);
+   if (PART & MDH_PF_PART) return partitioning_closest_bits<(PART & MDH_PF_CUSTOM) != 0, MDH_PF_HAS_FALLBACK(PART), (PART & MDH_PF_PSMALL) != 0, (PART & MDH_PF_GTAB) != 0>(sc, x);
    return closest_primitive<(PART & MDH_PF_CUSTOM) != 0, (PART & MDH_PF_ROOM) != 0, (PART & MDH_PF_GTAB) != 0>(sc, x);
 }
 // the same with the first sphere and box already in registers (sdf_regs)
 template <int PART> MDH_DEV float sdf(const KScene &sc, f3 x, const SdfRegs &regs)
 {
    MDH_WORK(2);
-   int dummy;
-   (void)dummy;
-   if (PART & MDH_PF_PART) return MDH_PART_BITS ? partitioning_closest_bits<(PART & MDH_PF_CUSTOM) != 0, MDH_PF_HAS_FALLBACK(PART), (PART & MDH_PF_PSMALL) != 0, (PART & MDH_PF_GTAB) != 0>(sc, x) : partitioning_lookup<false, (PART & MDH_PF_CUSTOM) != 0, MDH_PF_HAS_FALLBACK(PART), (PART & MDH_PF_PSMALL) != 0, (PART & MDH_PF_GTAB) != 0>(sc, x, dummy);
+   if (PART & MDH_PF_PART) return partitioning_closest_bits<(PART & MDH_PF_CUSTOM) != 0, MDH_PF_HAS_FALLBACK(PART), (PART & MDH_PF_PSMALL) != 0, (PART & MDH_PF_GTAB) != 0>(sc, x);
    return closest_primitive<(PART & MDH_PF_CUSTOM) != 0, (PART & MDH_PF_ROOM) != 0, (PART & MDH_PF_GTAB) != 0>(sc, x, &regs);
 }
 template <int PART> MDH_DEV float sdf_info(const KScene &sc, f3 x, int &index)
@@ -1677,19 +1508,14 @@ template <bool P2 = false> MDH_DEV unsigned atlas_rgba8(const void *base, unsign
 // float, and fma (k, c_hi, fl (k c_lo)) is the correctly rounded quotient for every k in 0 .. 255 (checked in exact
 // arithmetic for all 256 values: tests/test_oracle_pins.py).  Three instructions (v_cvt_f32_ubyteN takes the byte out
 // of the texel itself); the table costs a bit-field extract, an address and an LDS read per component.
-#ifndef MDH_U8_FMA
-#define MDH_U8_FMA 1
-#endif
 MDH_DEV float u8_unorm(float k) { return __builtin_fmaf(k, 0x1.010102p-8f, k * -0x1.fdfdfep-33f); }
-// u8_tab = float index of the k / 255 table in LDS (KScene::u8_slot * 4), or < 0: divide
+// (u8_tab = float index of a k / 255 table in LDS, KScene::u8_slot * 4: no scene has one since u8_unorm, and nothing reads it)
 template <bool P2 = false> MDH_DEV f3 atlas_texel(const void *base, int fmt, unsigned idx, int u8_tab)
 {
    if (fmt == 0) {
       const unsigned t = atlas_rgba8<P2>(base, idx);
       const unsigned x = t & 255u, y = (t >> 8) & 255u, z = (t >> 16) & 255u;
-      if (MDH_U8_FMA) return F3(u8_unorm((float)x), u8_unorm((float)y), u8_unorm((float)z));
-      if (u8_tab >= 0) return F3(tab_float(u8_tab + x), tab_float(u8_tab + y), tab_float(u8_tab + z));
-      return F3((float)x / 255.0f, (float)y / 255.0f, (float)z / 255.0f);
+      return F3(u8_unorm((float)x), u8_unorm((float)y), u8_unorm((float)z));
    }
    const f4v t = ((GlobalF4)base)[idx];
    return F3(t.x, t.y, t.z);
@@ -1772,11 +1598,7 @@ MDH_DEV AtlasTap atlas_tap_issue(const void *base, int fmt, int pcx, int pcy, in
 }
 MDH_DEV f3 u8_texel(unsigned t, int u8_tab)
 {
-#if MDH_U8_FMA
    return F3(u8_unorm((float)(t & 255u)), u8_unorm((float)((t >> 8) & 255u)), u8_unorm((float)((t >> 16) & 255u)));
-#else
-   return F3(tab_float(u8_tab + (t & 255u)), tab_float(u8_tab + ((t >> 8) & 255u)), tab_float(u8_tab + ((t >> 16) & 255u)));
-#endif
 }
 MDH_DEV f3 atlas_tap_resolve(const void *base, int fmt, const AtlasTap &t, int u8_tab)
 {

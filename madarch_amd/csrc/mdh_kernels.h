@@ -38,9 +38,6 @@
 #endif
 // The variants for the census of the reference's rooms (MDH_PF_ROOM) need 80 registers where the general scan needs 96: six
 // wavefronts per SIMD without a further spill (measured at config 3: five 5 681 - 5 726, six 5 818 - 5 863 Mpixels/s in flight).
-#ifndef MDH_ROOM_VARIANTS
-#define MDH_ROOM_VARIANTS 1 // (0: no scene is given a kernel variant built for its census, MDH_PF_ROOM / MDH_PF_PSMALL -- A/B runs)
-#endif
 #ifndef MDH_ROOM_WAVES_PER_SIMD
 #define MDH_ROOM_WAVES_PER_SIMD 6
 #endif
@@ -74,20 +71,11 @@
 #else
 #define MDH_OCC_RAD(PART, SMALL) (((PART) & MDH_PF_CUSTOM) ? 2 : MDH_OCC_RAD_BUILTIN(SMALL))
 #endif
-#ifndef MDH_RAD_REDERIVE
-#define MDH_RAD_REDERIVE 1 // k_radiance derives its texel again behind the pixel program instead of keeping it (see there)
-#endif
 #ifndef MDH_RAD_QVIS
 #define MDH_RAD_QVIS 1 // probe-visibility rays through the wave's ray queue (mdh_march.h: queued_visibility)
 #endif
-#ifndef MDH_SCR_QVIS
-#define MDH_SCR_QVIS 0
-#endif
 #ifndef MDH_SCAT_BATCH
 #define MDH_SCAT_BATCH 8 // scattering steps whose froxel taps are in flight together
-#endif
-#ifndef MDH_RELOAD_ARGS
-#define MDH_RELOAD_ARGS 1
 #endif
 #ifndef MDH_WAVES_PER_SIMD
 #define MDH_WAVES_PER_SIMD 5 // register budget of the march kernels (measured, pipelined frames: 5 > 6 > 4 waves/SIMD)
@@ -122,7 +110,7 @@ struct ScreenArgs {
    int split;
    // ... and in an ORDERED launch (slowest tiles first) the first `split_first` places -- the tiles whose wavefronts make the
    // pass's tail, a sum of marches each as long as the longest among 64 pixels -- are drawn by four wavefronts of 4x4 pixels
-   // each (places 0 .. 4 split_first - 1), the others by one
+   // each (places 0 .. 4 split_first - 1), the others by one.  (The host passes 0: the split of an order's head measured no gain.)
    int split_first;
 };
 // place of a launch -> its index into the launch's tiles, the part of the tile, the split factor (ScreenArgs::split, split_first)
@@ -133,9 +121,6 @@ MDH_DEV void screen_place(const ScreenArgs &a, int place, int &idx, int &sub, in
       else { idx = place - 3 * a.split_first; sub = 0; split = 0; }
    } else { idx = place >> a.split; sub = place & ((1 << a.split) - 1); split = a.split; }
 }
-#ifndef MDH_SCREEN_SPLIT_FIRST_PERMILLE
-#define MDH_SCREEN_SPLIT_FIRST_PERMILLE 0 // of an ordered launch's tiles, the slowest so many thousandths as four wavefronts each (ScreenArgs::split_first)
-#endif
 #ifndef MDH_SCREEN_SPLIT_DEFAULT
 #define MDH_SCREEN_SPLIT_DEFAULT 2560 // MDH_OPT_SCREEN_SPLIT's initial value
 #endif
@@ -200,9 +185,8 @@ __global__ __launch_bounds__(MDH_BLOCK, MDH_OCC(PART, MODE)) void k_screen(KScen
       cfg.direct_specular = true;
       cfg.spec_mode = a.spec_mode;
       cfg.ao_steps = a.ao_steps;
-      c = MDH_SHADE<PART, MODE, ALT ? 2 : 1, MDH_SCR_QVIS != 0>(sc, pr, cfg, valid, origin, dir, ph, hit, pos);
+      c = MDH_SHADE<PART, MODE, ALT ? 2 : 1, false>(sc, pr, cfg, valid, origin, dir, ph, hit, pos);
    }
-#if MDH_RELOAD_ARGS
    struct KArgs { KScene sc; KProbes pr; KVolumetrics vol; KCamera cam; ScreenArgs a; };
    // (the kernel argument segment lays the by-value arguments out like this struct: each at its natural alignment, all of
    //  them 8-byte aligned aggregates of 4- and 8-byte members -- checked here rather than assumed)
@@ -229,7 +213,6 @@ __global__ __launch_bounds__(MDH_BLOCK, MDH_OCC(PART, MODE)) void k_screen(KScen
 #define vol vol2
 #define a a2
 #define cam cam2
-#endif
    // the pixel again (the same integer and fp32 operations on the same inputs: the same values)
    int i, j;
    float u, v;
@@ -265,11 +248,9 @@ __global__ __launch_bounds__(MDH_BLOCK, MDH_OCC(PART, MODE)) void k_screen(KScen
       a.gb_t[px] = ph.t;
       a.gb_steps[px] = ph.steps;
    }
-#if MDH_RELOAD_ARGS
 #undef vol
 #undef a
 #undef cam
-#endif
    PH_KERNEL_END();
 }
 
@@ -355,9 +336,6 @@ MDH_DEV void radiance_texel(const KProbes &pr, const RadOrder &ro, long lin, int
 template <int PART, bool SMALL = false, int PHASE = 0> __global__ __launch_bounds__(MDH_BLOCK, PHASE == 1 ? MDH_RAD_A_WAVES_PER_SIMD : MDH_OCC_RAD(PART, SMALL)) void k_radiance(KScene sc, KProbes pr, int first_round, RadOrder ro)
 {
    if (first_round > 0 && (int)blockIdx.x >= first_round) __builtin_amdgcn_s_setprio(3);
-#if MDH_QVIS_SHARED && MDH_RAD_QVIS
-   qvis_shared_init(sc); // (made visible to the workgroup by the barrier of stage_table)
-#endif
    stage_table(sc);
    f3 c;
    PrimaryHit ph;
@@ -383,13 +361,7 @@ template <int PART, bool SMALL = false, int PHASE = 0> __global__ __launch_bound
       bool hit;
       f3 pos;
       c = MDH_SHADE<PART, 0, 0, MDH_RAD_QVIS != 0, PHASE>(sc, pr, cfg, valid, world, ray_dir, ph, hit, pos, PHASE ? ro.rec + lin : nullptr);
-#if !MDH_RAD_REDERIVE
-      if (valid) atlas_store(pr.rad, pr.fmt, atlas_index(pr.pcx, pr.rres, pr.rshift, i, j), c);
-      if (valid && ro.steps) // the ray's sort key: the levels of its primary-march and soft-shadow step counts
-         ro.steps[(size_t)(probe_raw - pr.probe_begin) * (pr.rres * pr.rres) + y * pr.rres + x] = (unsigned char)((rad_level(ph.steps & 0xffff) << 4) | rad_level(ph.steps >> 16));
-#endif
    }
-#if MDH_RAD_REDERIVE
    // The texel again: nothing of the prologue stays live across the pixel program (its coordinates, the order's entry and
    // the arguments the store needs were eleven dwords that the seven-wavefront build kept in scratch memory).  The lane
    // index comes from the hardware, the arguments from the kernel argument segment through a pointer the compiler
@@ -425,7 +397,6 @@ template <int PART, bool SMALL = false, int PHASE = 0> __global__ __launch_bound
             ro2.steps[(size_t)(probe_raw - pr2.probe_begin) * (pr2.rres * pr2.rres) + y * pr2.rres + x] = (unsigned char)((rad_level(ph.steps & 0xffff) << 4) | rad_level(ph.steps >> 16));
       }
    }
-#endif
    PH_KERNEL_END();
 }
 
@@ -583,34 +554,17 @@ __global__ __launch_bounds__(256) void k_order_floor(unsigned char *keys, int n,
 #ifndef MDH_IRR_BLOCK
 #define MDH_IRR_BLOCK 256 // all of them evaluate taps; the first ires^2 (one wavefront at 8x8) fold
 #endif
-#ifndef MDH_IRR_PACKED
-#define MDH_IRR_PACKED 1
-#endif
-#ifndef MDH_IRR_PREFETCH
-#define MDH_IRR_PREFETCH 1
-#endif
-#ifndef MDH_IRR_FOLD_WAVES
-// wavefronts that fold a probe's taps: 1 = one carries all four channels; 2 = (x, y) on one and (z, weight) on another -- the
-// same bits with 7 instead of 13 instructions per tap and wavefront, measured SLOWER (0.040 against 0.038 ms for 512 probes,
-// with two, four or six staging wavefronts beside them: profiles/r03_x_irradiance_two_folders.log): the fold does not wait
-// for its instructions but for its taps' LDS reads, and two wavefronts read every tap twice.  Kept as a switch; default 1.
-#define MDH_IRR_FOLD_WAVES 1
-#endif
+// One wavefront folds a probe's taps, all four channels.  (measured: (x, y) on one wavefront and (z, weight) on another, the
+// same bits with 7 instead of 13 instructions per tap and wavefront, is SLOWER, 0.040 against 0.038 ms for 512 probes,
+// profiles/r03_x_irradiance_two_folders.log: the fold waits for its taps' LDS reads, and two wavefronts read every tap twice.
+// The taps' weights computed by the wavefronts beside the folding one: bit-exact and not faster, 0.0368 - 0.0417 ms against
+// 0.0370, profiles/r04_x_irradiance_weights_pipeline.log: a lone workgroup takes 30 us whatever its instruction count.)
 #ifndef MDH_IRR_CHUNK
-#define MDH_IRR_CHUNK 256 // taps per LDS buffer when one wavefront folds (0 = all taps staged at once)
+#define MDH_IRR_CHUNK 256 // taps per LDS buffer when one wavefront folds
 #endif
-#ifndef MDH_IRR_WPRE
-// the taps' weights computed by the wavefronts beside the folding one (k_irradiance, round 4: VERDICT r03 item 3).  Built, bit-exact,
-// and NOT faster: 0.0368 - 0.0417 ms against 0.0370 (profiles/r04_x_irradiance_weights_pipeline.log) -- the folding
-// wavefront needs 74 cycles per tap for two LDS reads and seven plain fp32 operations just as it needed them for two reads and
-// thirteen operations; a lone workgroup takes 30 us whatever its instruction count.  Off.
-#define MDH_IRR_WPRE 0
-#endif
-#ifndef MDH_IRR_CHANNELS
-#define MDH_IRR_CHANNELS 1 // one channel of the fold per wavefront, the weights shared through LDS (k_irradiance)
-#endif
+// The form for probes of at most 64 texels: one channel of the fold per wavefront, the weights shared through LDS (k_irradiance)
 #ifndef MDH_IRR_PRIO
-#define MDH_IRR_PRIO 3 // s_setprio of that form's wavefronts (0 = none)
+#define MDH_IRR_PRIO 3 // s_setprio of that form's wavefronts
 #endif
 #ifndef MDH_IRR_CCHUNK
 #define MDH_IRR_CCHUNK 32 // taps per weight buffer of that form (32: 18 KiB of LDS, 64: 34 KiB -- the same speed alone, 32 starts sooner beside the march kernels of frames in flight)
@@ -618,14 +572,6 @@ __global__ __launch_bounds__(256) void k_order_floor(unsigned char *keys, int n,
 // LDS of that form: two weight buffers of 64 rows; its scratch in device memory: six planes of the taps (rounded up to whole chunks) per probe
 #define MDH_IRR_CHANNELS_LDS ((size_t)2 * 64 * (MDH_IRR_CCHUNK + 4) * sizeof(float))
 #define MDH_IRR_CHANNELS_PLANE(n) ((size_t)(((n) + 63) / 64 * 64))
-#ifndef MDH_IRR_ABL
-#define MDH_IRR_ABL 0 // (timing experiments only: 1 no fold, 2 no tap evaluation, 3 no weights -- wrong results)
-#endif
-#ifndef MDH_IRR_WCHUNK
-#define MDH_IRR_WCHUNK 64 // taps per pipeline stage of that form (at most 64: one wavefront evaluates a chunk's taps)
-#endif
-// LDS of that form: three radiance and two direction buffers of a chunk's taps, two buffers of its weights for 64 texels
-#define MDH_IRR_WPRE_LDS ((size_t)5 * MDH_IRR_WCHUNK * sizeof(float4) + (size_t)2 * MDH_IRR_WCHUNK * 64 * sizeof(float))
 typedef float pk2 __attribute__((ext_vector_type(2))); // two fp32 per VALU instruction (v_pk_mul_f32 / v_pk_add_f32: IEEE per component)
 // `prev`, `hyst`: MDH_OPT_HYSTERESIS_PERMILLE (not in the reference; 0 = off): the texel is stored as
 // mix (fresh, what the previous frame's atlas holds, hyst)
@@ -685,9 +631,6 @@ __global__ __launch_bounds__(MDH_IRR_BLOCK) void k_irradiance(KProbes pr, const 
    extern __shared__ float4 s_taps[]; // [2 * rres * rres]: {rad.xyz, 1} {dir.xyz, -}
    const int probe = pr.probe_begin + blockIdx.x;
    if (probe >= pr.probe_end) return;
-#if MDH_IRR_ABL == 9
-   return; // (timing experiments only: what the pass's launch and its two events cost by themselves)
-#endif
    const int ntaps = pr.rres * pr.rres;
    const int ty = probe / pr.pcx, tx = probe - ty * pr.pcx;
    const float pcx = (float)pr.pcx, pcy = (float)pr.pcy;
@@ -736,7 +679,6 @@ __global__ __launch_bounds__(MDH_IRR_BLOCK) void k_irradiance(KProbes pr, const 
       return;
    }
 #endif
-#if MDH_IRR_CHANNELS
    if (pr.ires * pr.ires <= 64 && MDH_IRR_BLOCK == 256 && tap_planes) { // (the host's test: mdh_api.hip, MDH_PASS_IRRADIANCE)
       // Round 4 (second session): ONE CHANNEL PER WAVEFRONT.  A wavefront that is alone on its SIMD issues one instruction every
       // four cycles whatever the instruction (vector, LDS or scalar), so the lone folding wavefront of the forms below pays
@@ -746,12 +688,10 @@ __global__ __launch_bounds__(MDH_IRR_BLOCK) void k_irradiance(KProbes pr, const 
       // computed by each wavefront one chunk ahead and shared through LDS ([texel][tap]: 16-byte reads and writes, rows 4 * odd
       // dwords apart).  The same multiplications and additions in the reference's order on every chain; the issue slots of a
       // probe's fold spread over four SIMDs instead of one.
-#if MDH_IRR_PRIO
       // all four wavefronts are the pass's critical path and meet at a barrier every chunk; beside the march kernels of the
       // neighbouring frames (five or seven wavefronts per SIMD, all of them older) the youngest wavefront of a SIMD gets the
       // issue slots the others leave: raised priority for the pass that heads the next frame's dependency chain
       __builtin_amdgcn_s_setprio(MDH_IRR_PRIO);
-#endif
       constexpr int CH = MDH_IRR_CCHUNK, S = CH + 4, CHQ = CH / 4;
       static_assert((CH == 64 || CH == 32) && ((S / 4) & 1) == 1, "a wavefront's quarter of a chunk is a register of sixteen taps or half of one; weight rows 16-byte aligned, an odd number of quads apart");
       const int ntp = (ntaps + 63) / 64 * 64, nchunks = (ntaps + CH - 1) / CH;
@@ -897,165 +837,11 @@ __global__ __launch_bounds__(MDH_IRR_BLOCK) void k_irradiance(KProbes pr, const 
       }
       return;
    }
-#endif
-#if MDH_IRR_WPRE
-   if (pr.ires * pr.ires <= 64 && MDH_IRR_BLOCK == 256) {
-      // Round 4: the weights off the fold's critical path.  A tap's weight for a texel, w = max (dot (irr_dir, rad_dir), 0), is
-      // five instructions of the fold's thirteen and depends on nothing the fold produces: the wavefronts that used to wait for
-      // the folding one compute it, a lane per texel, into LDS.  Chunks of 64 taps run through a three-stage pipeline, one
-      // barrier per chunk:      wavefront 1     evaluates the taps of chunk c + 2 (bilinear fetch, octahedral decode: one lane per tap)
-      //                         wavefronts 2, 3 the weights of chunk c + 1 for all 64 texels (tap by tap, LDS broadcast reads)
-      //                         wavefront 0     folds chunk c: per tap one per-lane weight, one broadcast radiance, two v_pk_mul
-      //                                         and two v_pk_add -- the reference's additions in the reference's order
-      // -- about 380 issue slots per chunk on every wavefront instead of 1 000 on the folding one.
-      constexpr int CH = MDH_IRR_WCHUNK;
-      float4 *s_rad = s_taps;                      // [3][CH] {rad.xyz, 1}
-      float4 *s_dir = s_taps + 3 * CH;             // [2][CH] {dir.xyz, -}
-      float *s_w = (float *)(s_taps + 5 * CH);     // [2][CH][64]
-      const int nchunks = (ntaps + CH - 1) / CH;
-      const int wv = threadIdx.x >> 6, lane = threadIdx.x & 63;
-      const int ntex = pr.ires * pr.ires;
-      const int x = lane % pr.ires, y = lane / pr.ires; // (a lane's texel, in the weight and fold wavefronts)
-      const int i = tx * pr.ires + x, j = ty * pr.ires + y;
-      const f2 nc = F2((centre(i, pr.pcx * pr.ires) + 1.0f) * 0.5f, (centre(j, pr.pcy * pr.ires) + 1.0f) * 0.5f);
-      const f3 irr_dir = ray_id_to_ray_dir(F2(fract_(nc.x * pcx), fract_(nc.y * pcy)));
-      float acc_x = 0.0f, acc_y = 0.0f, acc_z = 0.0f, acc_w = 0.0f;
-#define MDH_IRR_TAP_COORD(tap_, cc_)                                                                                     \
-      const int yy_ = (tap_) / pr.rres, xx_ = (tap_) - yy_ * pr.rres;                                                    \
-      const f2 cc_ = F2(clamp_(rad_coord.x + (float)xx_ * step.x, step.x, 1.0f - step.x), clamp_(rad_coord.y + (float)yy_ * step.y, step.y, 1.0f - step.y))
-#define MDH_IRR_TAP_STORE(rad_, cc_, c_, slot_)                                                                          \
-      do {                                                                                                               \
-         const f3 rad_dir_ = ray_id_to_ray_dir(F2(fract_((cc_).x * pcx), fract_((cc_).y * pcy)));                         \
-         s_rad[((c_) % 3) * CH + (slot_)] = make_float4((rad_).x, (rad_).y, (rad_).z, 1.0f);                              \
-         s_dir[((c_) & 1) * CH + (slot_)] = make_float4(rad_dir_.x, rad_dir_.y, rad_dir_.z, 0.0f);                        \
-      } while (0)
-      // the weights of chunk c_: taps t0, t0 + stride, ... of it, eight directions on their way from LDS at a time
-#define MDH_IRR_WEIGHTS(c_, t0_, stride_)                                                                                 \
-      do {                                                                                                               \
-         const int nh_ = min(CH, ntaps - (c_) * CH);                                                                      \
-         const float4 *db_ = s_dir + ((c_) & 1) * CH;                                                                     \
-         float *wb_ = s_w + ((c_) & 1) * CH * 64 + lane;                                                                  \
-         if (lane < ntex) {                                                                                              \
-            int t = (t0_);                                                                                               \
-            _Pragma("unroll 1") for (; t + 7 * (stride_) < nh_; t += 8 * (stride_)) {                                      \
-               float4 d8[8];                                                                                             \
-               _Pragma("unroll") for (int q = 0; q < 8; ++q) d8[q] = db_[t + q * (stride_)];                              \
-               _Pragma("unroll") for (int q = 0; q < 8; ++q)                                                              \
-                  wb_[(t + q * (stride_)) * 64] = max_((irr_dir.x * d8[q].x + irr_dir.y * d8[q].y) + irr_dir.z * d8[q].z, 0.0f); \
-            }                                                                                                            \
-            for (; t < nh_; t += (stride_)) {                                                                             \
-               const float4 d = db_[t];                                                                                  \
-               wb_[t * 64] = max_((irr_dir.x * d.x + irr_dir.y * d.y) + irr_dir.z * d.z, 0.0f);                           \
-            }                                                                                                            \
-         }                                                                                                               \
-      } while (0)
-      // (LDS only: a wavefront's loads from the atlas stay in flight across it -- __syncthreads would wait for them)
-#define MDH_IRR_BARRIER() asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory")
-      // prologue: the taps of chunks 0 and 1 (all wavefronts); wavefront 1 asks for the texels of chunk 2; the weights of chunk 0
-      for (int t = threadIdx.x; t < min(2 * CH, ntaps); t += MDH_IRR_BLOCK) {
-         MDH_IRR_TAP_COORD(t, cc);
-         const f3 rad = atlas_sample(pr.rad, pr.fmt, pr.pcx, pr.pcy, pr.rres, pr.rshift, pr.rad_w, pr.rad_h, cc.x, cc.y, -1);
-         MDH_IRR_TAP_STORE(rad, cc, t / CH, t % CH);
-      }
-      __syncthreads();
-      AtlasTap tap_next;
-      tap_next.t00 = tap_next.t10 = tap_next.t01 = tap_next.t11 = 0u; tap_next.fx = tap_next.fy = 0.0f;
-      if (wv == 1 && 2 * CH + lane < ntaps && lane < CH) {
-         MDH_IRR_TAP_COORD(2 * CH + lane, cc);
-         tap_next = atlas_tap_issue(pr.rad, pr.fmt, pr.pcx, pr.pcy, pr.rres, pr.rshift, pr.rad_w, pr.rad_h, cc.x, cc.y);
-      }
-      MDH_IRR_WEIGHTS(0, wv, 4);
-      MDH_IRR_BARRIER();
-#ifdef MDH_PHASES
-      unsigned long long ph_work = 0ull, ph_wait = 0ull; // (diagnostic: cycles of this wavefront in its stage and at the barrier)
-#endif
-      for (int c = 0; c < nchunks; ++c) {
-#ifdef MDH_PHASES
-         const unsigned long long ph_t0 = __builtin_amdgcn_s_memtime();
-#endif
-         if (wv == 0) {
-#if MDH_IRR_ABL != 1
-            if (lane < ntex) {
-               const int nh = min(CH, ntaps - c * CH);
-               const float4 *rb = s_rad + (c % 3) * CH;
-               const float *wb = s_w + (c & 1) * CH * 64 + lane;
-               int t = 0;
-               // groups of four taps, two groups in flight: while one is added the next one is on its way from LDS (registers
-               // A and B alternate: no copies)
-#define MDH_IRR_LOAD4(R_, W_, t_) _Pragma("unroll") for (int q = 0; q < 4; ++q) { R_[q] = rb[(t_) + q]; W_[q] = wb[((t_) + q) * 64]; }
-#define MDH_IRR_ADD4(R_, W_) _Pragma("unroll") for (int q = 0; q < 4; ++q) { acc_x = acc_x + R_[q].x * W_[q]; acc_y = acc_y + R_[q].y * W_[q]; acc_z = acc_z + R_[q].z * W_[q]; acc_w = acc_w + R_[q].w * W_[q]; }
-               // (plain fp32 operations, and the tap's fourth component is 1: 1 * w = w)
-               if (nh >= 8) {
-                  float4 ra[4], rb4[4];
-                  float wa[4], wb4[4];
-                  MDH_IRR_LOAD4(ra, wa, 0)
-#pragma unroll 1
-                  for (; t + 8 <= nh; t += 8) {
-                     MDH_IRR_LOAD4(rb4, wb4, t + 4)
-                     MDH_IRR_ADD4(ra, wa)
-                     if (t + 12 <= nh) { MDH_IRR_LOAD4(ra, wa, t + 8) }
-                     MDH_IRR_ADD4(rb4, wb4)
-                  }
-                  if (t + 4 <= nh) { MDH_IRR_ADD4(ra, wa) t += 4; } // (a last group of four already loaded)
-               }
-#undef MDH_IRR_LOAD4
-#undef MDH_IRR_ADD4
-               for (; t < nh; ++t) {
-                  const float4 r = rb[t];
-                  const float w = wb[t * 64];
-                  acc_x = acc_x + r.x * w; acc_y = acc_y + r.y * w; acc_z = acc_z + r.z * w;
-                  acc_w = acc_w + w;
-               }
-            }
-#endif
-         } else if (wv == 1) { // the taps of chunk c + 2 from the texels asked for one chunk ago; then the texels of chunk c + 3
-            if (lane < CH && MDH_IRR_ABL != 2) {
-               const int tap = (c + 2) * CH + lane;
-               if (c + 2 < nchunks && tap < ntaps) {
-                  MDH_IRR_TAP_COORD(tap, cc);
-                  const f3 rad = atlas_tap_resolve(pr.rad, pr.fmt, tap_next, -1);
-                  MDH_IRR_TAP_STORE(rad, cc, c + 2, lane);
-               }
-               const int tap3 = (c + 3) * CH + lane;
-               if (c + 3 < nchunks && tap3 < ntaps) {
-                  MDH_IRR_TAP_COORD(tap3, cc);
-                  tap_next = atlas_tap_issue(pr.rad, pr.fmt, pr.pcx, pr.pcy, pr.rres, pr.rshift, pr.rad_w, pr.rad_h, cc.x, cc.y);
-               }
-            }
-         } else if (c + 1 < nchunks && MDH_IRR_ABL != 3)
-            MDH_IRR_WEIGHTS(c + 1, wv - 2, 2);
-#ifdef MDH_PHASES
-         const unsigned long long ph_t1 = __builtin_amdgcn_s_memtime();
-#endif
-         MDH_IRR_BARRIER();
-#ifdef MDH_PHASES
-         ph_work += ph_t1 - ph_t0; ph_wait += __builtin_amdgcn_s_memtime() - ph_t1;
-#endif
-      }
-#ifdef MDH_PHASES
-      if (lane == 0) { atomicAdd(&g_phase[2 * wv], ph_work); atomicAdd(&g_phase[2 * wv + 1], ph_wait); }
-#endif
-#undef MDH_IRR_TAP_COORD
-#undef MDH_IRR_TAP_STORE
-#undef MDH_IRR_BARRIER
-#undef MDH_IRR_WEIGHTS
-      if (wv == 0 && lane < ntex) {
-         const f3 irradiance = F3(acc_x, acc_y, acc_z) / acc_w;
-         const unsigned idx = atlas_index(pr.pcx, pr.ires, pr.ishift, i, j);
-         atlas_store(pr.irr, pr.fmt, idx, irradiance_blend(pr, prev, hyst, idx, irradiance));
-      }
-      return;
-   }
-#endif
-#if MDH_IRR_CHUNK
    if (pr.ires * pr.ires <= 64) {
-      // One wavefront folds (a lane per texel) -- or two (MDH_IRR_FOLD_WAVES: the sums of a texel's four channels are four
-      // independent chains of additions, so one wavefront can carry (x, y) and another (z, weight), each with the
-      // reference's taps in the reference's order: the same bits).  The taps go through LDS in chunks of MDH_IRR_CHUNK,
-      // two buffers: while the folding wavefronts work on chunk c, the others stage chunk c + 1.  The same taps in the
-      // same order; a quarter of the LDS (room for the march kernels' workgroups beside it) and the staging hidden.
+      // One wavefront folds (a lane per texel).  The taps go through LDS in chunks of MDH_IRR_CHUNK, two buffers: while the
+      // folding wavefront works on chunk c, the others stage chunk c + 1.  The same taps in the same order; a quarter of
+      // the LDS (room for the march kernels' workgroups beside it) and the staging hidden.
       constexpr int CH = MDH_IRR_CHUNK;
-      constexpr int FOLDERS = MDH_IRR_FOLD_WAVES; // 1 or 2
       const int nchunks = (ntaps + CH - 1) / CH;
       const int wv = threadIdx.x >> 6, lane = threadIdx.x & 63;
       const int x = lane % pr.ires, y = lane / pr.ires; // (used by the folding lanes only)
@@ -1069,23 +855,22 @@ __global__ __launch_bounds__(MDH_IRR_BLOCK) void k_irradiance(KProbes pr, const 
       for (int c = 0; c < nchunks; ++c) {
          const int base = c * CH, n_here = min(CH, ntaps - base);
          const float4 *buf = s_taps + (size_t)(c & 1) * 2 * CH;
-         if (wv < FOLDERS) {
+         if (wv == 0) {
             if (lane < pr.ires * pr.ires) {
-               // WHICH: 0 = all four channels (one folding wavefront), 1 = (x, y), 2 = (z, weight)
-#define MDH_IRR_FOLD(WHICH, r_, d_)                                                           \
+#define MDH_IRR_FOLD(r_, d_)                                                                  \
                do {                                                                           \
                   const float4 r = (r_), d = (d_);                                            \
                   const pk2 d_xy = {d.x, d.y}, r_xy = {r.x, r.y}, r_z1 = {r.z, r.w};          \
                   const pk2 p = dir_xy * d_xy;                                                \
                   const float w = max_((p.x + p.y) + irr_dir.z * d.z, 0.0f);                  \
                   const pk2 ww = {w, w};                                                      \
-                  if (WHICH != 2) acc_xy = acc_xy + r_xy * ww;                                \
-                  if (WHICH != 1) acc_zw = acc_zw + r_z1 * ww;                                \
+                  acc_xy = acc_xy + r_xy * ww;                                                \
+                  acc_zw = acc_zw + r_z1 * ww;                                                \
                } while (0)
                // six taps per turn in two groups of three, each group on its way from LDS while the other is folded (the
-               // folding wavefronts are the pass's critical path: 1 024 taps in the reference's order, each waiting for its two
+               // folding wavefront is the pass's critical path: 1 024 taps in the reference's order, each waiting for its two
                // LDS reads otherwise).  Three: two groups in flight are 12 LDS reads, and the counter a wavefront waits on holds 15.
-#define MDH_IRR_FOLD_CHUNK(WHICH)                                                             \
+#define MDH_IRR_FOLD_CHUNK()                                                                  \
                do {                                                                           \
                   constexpr int GR = 3;                                                       \
                   const int nt = n_here - n_here % (2 * GR);                                  \
@@ -1096,30 +881,22 @@ __global__ __launch_bounds__(MDH_IRR_BLOCK) void k_irradiance(KProbes pr, const 
                   }                                                                           \
                   _Pragma("unroll 1") for (; t < nt; t += 2 * GR) {                           \
                      _Pragma("unroll") for (int k = 0; k < GR; ++k) { rb[k] = buf[2 * (t + GR + k)]; db[k] = buf[2 * (t + GR + k) + 1]; } \
-                     _Pragma("unroll") for (int k = 0; k < GR; ++k) MDH_IRR_FOLD(WHICH, ra[k], da[k]); \
+                     _Pragma("unroll") for (int k = 0; k < GR; ++k) MDH_IRR_FOLD(ra[k], da[k]); \
                      const int tn = t + 2 * GR < nt ? t + 2 * GR : t; /* (the last turn reads its own taps again) */ \
                      _Pragma("unroll") for (int k = 0; k < GR; ++k) { ra[k] = buf[2 * (tn + k)]; da[k] = buf[2 * (tn + k) + 1]; } \
-                     _Pragma("unroll") for (int k = 0; k < GR; ++k) MDH_IRR_FOLD(WHICH, rb[k], db[k]); \
+                     _Pragma("unroll") for (int k = 0; k < GR; ++k) MDH_IRR_FOLD(rb[k], db[k]); \
                   }                                                                           \
-                  for (; t < n_here; ++t) MDH_IRR_FOLD(WHICH, buf[2 * t], buf[2 * t + 1]);    \
+                  for (; t < n_here; ++t) MDH_IRR_FOLD(buf[2 * t], buf[2 * t + 1]);           \
                } while (0)
-               if (FOLDERS == 1) MDH_IRR_FOLD_CHUNK(0);
-               else if (wv == 0) MDH_IRR_FOLD_CHUNK(1);
-               else MDH_IRR_FOLD_CHUNK(2);
+               MDH_IRR_FOLD_CHUNK();
 #undef MDH_IRR_FOLD_CHUNK
 #undef MDH_IRR_FOLD
             }
          } else if (c + 1 < nchunks) {
             const int nbase = base + CH, n_next = min(CH, ntaps - nbase), off = ((c + 1) & 1) * CH;
-            for (int t = (int)threadIdx.x - 64 * FOLDERS; t < n_next; t += MDH_IRR_BLOCK - 64 * FOLDERS) MDH_IRR_STAGE(nbase + t, off + t);
+            for (int t = (int)threadIdx.x - 64; t < n_next; t += MDH_IRR_BLOCK - 64) MDH_IRR_STAGE(nbase + t, off + t);
          }
          __syncthreads();
-      }
-      if (FOLDERS == 2) { // (z, weight) of every texel to the first wavefront, through the tap buffers (no longer read)
-         pk2 *hand = (pk2 *)s_taps;
-         if (wv == 1) hand[lane] = acc_zw;
-         __syncthreads();
-         if (wv == 0) acc_zw = hand[lane];
       }
       if (wv == 0 && lane < pr.ires * pr.ires) {
          const f3 irradiance = F3(acc_xy.x, acc_xy.y, acc_zw.x) / acc_zw.y;
@@ -1128,7 +905,6 @@ __global__ __launch_bounds__(MDH_IRR_BLOCK) void k_irradiance(KProbes pr, const 
       }
       return;
    }
-#endif
    for (int tap = threadIdx.x; tap < ntaps; tap += MDH_IRR_BLOCK) MDH_IRR_STAGE(tap, tap);
 #undef MDH_IRR_STAGE
    __syncthreads();
@@ -1139,7 +915,6 @@ __global__ __launch_bounds__(MDH_IRR_BLOCK) void k_irradiance(KProbes pr, const 
       const f3 irr_dir = ray_id_to_ray_dir(F2(fract_(nc.x * pcx), fract_(nc.y * pcy)));
       f3 irradiance = F3(0.0f, 0.0f, 0.0f);
       float total_weight = 0.0f;
-#if MDH_IRR_PACKED
       // the same operations, two per instruction: (x, y) and (z, weight) pairs.  1.0f * w = w exactly.
       pk2 acc_xy = {0.0f, 0.0f}, acc_zw = {0.0f, 0.0f};
       const pk2 dir_xy = {irr_dir.x, irr_dir.y};
@@ -1154,14 +929,6 @@ __global__ __launch_bounds__(MDH_IRR_BLOCK) void k_irradiance(KProbes pr, const 
       }
       irradiance = F3(acc_xy.x, acc_xy.y, acc_zw.x);
       total_weight = acc_zw.y;
-#else
-      for (int tap = 0; tap < ntaps; ++tap) {
-         const float4 r = s_taps[2 * tap], d = s_taps[2 * tap + 1];
-         float w = max_(dot(irr_dir, xyz(d)), 0.0f);
-         irradiance = irradiance + xyz(r) * w;
-         total_weight += w;
-      }
-#endif
       irradiance = irradiance / total_weight;
       const unsigned idx = atlas_index(pr.pcx, pr.ires, pr.ishift, i, j);
       atlas_store(pr.irr, pr.fmt, idx, irradiance_blend(pr, prev, hyst, idx, irradiance));
@@ -1171,38 +938,18 @@ __global__ __launch_bounds__(MDH_IRR_BLOCK) void k_irradiance(KProbes pr, const 
 // -------------------------------------------------------------------- visibility pass
 // compute_frustrum_visibility.glsl:8-42: one visibility ray per froxel (x, y, depth slice) and light.
 //
-// Round 4: the rays of a wavefront's froxels as a QUEUE WITH REPLACEMENT.  With one froxel per lane in lock step (the form
-// until round 3, kept as MDH_VIS_QUEUE = 0 and in the literal build) a wavefront marched until its longest ray ended:
-// 34 of 64 lanes alive per step (r03_c4_*), half of them blocked within a step or two while their neighbours cross the room.
-// Here a wavefront owns MDH_VIS_ROUNDS x 64 consecutive froxels (in the same 8x8-tile order) and a lane whose ray has ended
-// is SERVED -- its light's term added, the next light started, or the texel stored and the next froxel of the batch taken --
-// as soon as MDH_VIS_REFILL lanes wait (or nobody marches).  Every froxel's arithmetic is what it was, operation for
-// operation: WHICH lane computes a texel and WHEN changes, nothing else.
-#ifndef MDH_VIS_QUEUE
-#define MDH_VIS_QUEUE 0 // (measured on MI355X, light_shafts 1080p: the pass 0.067 -> 0.109 ms on its own and -1.5 % in flight --
-                        //  serving a lane is ~250 instructions under a sparse mask, as much as its march saves: DESIGN.md, dropped)
-#endif
-#ifndef MDH_VIS_LOOP
-#define MDH_VIS_LOOP 1 // froxels per lane of the lock-step form, one after the other (measured 2 and 4: the pass 0.074 -> 0.100 / 0.153 ms alone, +-0 in flight -- it is the length of a wavefront's chain, not the staging of the table)
-#endif
-#ifndef MDH_VIS_ROUNDS
-#define MDH_VIS_ROUNDS 4
-#endif
-// LDS of the second form of the queue, per wavefront, in floats: seven per ray, the list (u16) and the reached bytes
-#define MDH_VIS_Q_FLOATS (7 * 64 * MDH_VIS_ROUNDS + 64 * MDH_VIS_ROUNDS / 2 + 64 * MDH_VIS_ROUNDS / 4)
-#ifndef MDH_VIS_REFILL
-#define MDH_VIS_REFILL 16
-#endif
+// One froxel per lane, in lock step: a wavefront marches until its longest ray ends, 34 of 64 lanes alive per step (r03_c4_*).
+// (measured on MI355X, light_shafts 1080p: the rays of a wavefront's froxels as a queue with replacement, in two forms, took
+//  the pass from 0.067 to 0.109 ms on its own and -1.5 % in flight -- serving a lane is ~250 instructions under a sparse mask,
+//  as much as its march saves: DESIGN.md; two and four froxels per lane, one after the other: 0.074 -> 0.100 / 0.153 ms alone,
+//  +-0 in flight -- it is the length of a wavefront's chain, not the staging of the table)
 // the froxel texel (i, j) at place `lin` of the launch.  Which froxels share a wavefront decides how many of its lanes march
 // together: the texture is vw x (vh * vz) texels, row j = slice * vh + y, and in launch order a wavefront of the reference's
-// 100^3 froxels was a strip of 64 froxels along x (100 is no multiple of 8: no 8x8 tiles either).  MDH_VIS_BLOCK3: blocks of
+// 100^3 froxels was a strip of 64 froxels along x (100 is no multiple of 8: no 8x8 tiles either).  Hence blocks of
 // 4 x 4 froxels x 4 depth slices -- neighbours in space, whose rays to a light pass the same geometry.
-#ifndef MDH_VIS_BLOCK3
-#define MDH_VIS_BLOCK3 1
-#endif
 MDH_DEV void froxel_texel(const KVolumetrics &vol, int W, int H, long lin, int &i, int &j)
 {
-   if (MDH_VIS_BLOCK3 && ((vol.vw | vol.vh | vol.vz) & 3) == 0) {
+   if (((vol.vw | vol.vh | vol.vz) & 3) == 0) {
       const long blk = lin >> 6;
       const int l = (int)(lin & 63), bxn = vol.vw >> 2, byn = vol.vh >> 2;
       const int bx = (int)(blk % bxn);
@@ -1262,179 +1009,11 @@ template <int PART> __global__ __launch_bounds__(MDH_BLOCK) void k_visibility(KS
    }
    const int W = vol.vw, H = vol.vh * vol.vz;
    const long n = (long)W * H;
-#if MDH_VIS_QUEUE == 2
-   // The second form of the queue (round 4): the set-up and the finish of a froxel stay DENSE -- a wavefront owns MDH_VIS_ROUNDS x 64
-   // froxels and walks them round by round at full lanes -- and only the MARCH goes through a list with replacement, as
-   // queued_visibility does for the probe rays: the rays that need marching are listed (ballot ranks), their origin, direction and
-   // length wait in LDS, a lane whose ray has ended takes the next entry (seven LDS reads), a ray that reaches its light sets its byte.
-   {
-      constexpr int R = MDH_VIS_ROUNDS, NJ = 64 * R;
-      const int wv = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)), lane = threadIdx.x & 63;
-      const long wave_global = (long)blockIdx.x * (MDH_BLOCK / 64) + wv;
-      const long begin = wave_global * NJ;
-      if (begin >= n) return; // (wave-uniform)
-      float *wbase = (float *)(s_tab + sc.table_f4 + sc.part_bits_f4) + (size_t)wv * MDH_VIS_Q_FLOATS;
-      float *jp = wbase;                                             // [7][NJ]: pos.xyz, L.xyz, L_dist of every froxel's ray
-      unsigned short *list = (unsigned short *)(wbase + 7 * NJ);     // [NJ] the rays to march
-      unsigned char *reached = (unsigned char *)(list + NJ);         // [NJ] 1: the ray reached its light (or never had to be marched)
-      f3 result[R], dirs[R], Ls[R], rads[R];
-      float Ld[R];
-#pragma unroll
-      for (int r = 0; r < R; ++r) result[r] = F3(0.0f, 0.0f, 0.0f);
-      for (int l = 0; l < sc.total_lights; ++l) { // sample_lights :8-19, light by light for all the wavefront's froxels
-         int njobs = 0;
-#pragma unroll
-         for (int r = 0; r < R; ++r) { // set-up, dense
-            const long lin = begin + r * 64 + lane;
-            int i, j;
-            froxel_texel(vol, W, H, lin < n ? lin : n - 1, i, j);
-            f3 pos;
-            froxel_point(vol, cam, W, H, i, j, pos, dirs[r]);
-            rads[r] = sample_light<(PART & MDH_PF_CUSTOM) != 0>(sc, l, pos, F3(1.0f, 0.0f, 0.0f), Ls[r], Ld[r]); // compute_frustrum_visibility.glsl:12
-            MDH_WORK(0);
-            const int e = r * 64 + lane;
-            jp[0 * NJ + e] = pos.x; jp[1 * NJ + e] = pos.y; jp[2 * NJ + e] = pos.z;
-            jp[3 * NJ + e] = Ls[r].x; jp[4 * NJ + e] = Ls[r].y; jp[5 * NJ + e] = Ls[r].z; jp[6 * NJ + e] = Ld[r];
-            const bool need = lin < n && 0.0f < Ld[r]; // raycast_visibility's first test: a loop that is never entered leaves the light visible
-            reached[e] = need ? 0 : 1;
-            const unsigned long long m = __ballot(need);
-            if (need) list[njobs + (int)__builtin_amdgcn_mbcnt_hi((unsigned)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m, 0u))] = (unsigned short)e;
-            njobs += (int)__popcll(m);
-         }
-         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-         __builtin_amdgcn_wave_barrier();
-         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-         { // the march, through the list with replacement (raymarching.glsl:39-56 from its second test on)
-            int head = 0, job = -1;
-            float total = 0.0f, vmax = 0.0f;
-            f3 o = F3(0.0f, 0.0f, 0.0f), d = o;
-            for (;;) {
-               const unsigned long long idle = __ballot(job < 0);
-               const int n_idle = (int)__popcll(idle);
-               if (head < njobs && n_idle >= MDH_VIS_REFILL) {
-                  if (job < 0) {
-                     const int my = head + (int)__builtin_amdgcn_mbcnt_hi((unsigned)(idle >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)idle, 0u));
-                     if (my < njobs) {
-                        const int e = list[my];
-                        o = F3(jp[0 * NJ + e], jp[1 * NJ + e], jp[2 * NJ + e]);
-                        d = F3(jp[3 * NJ + e], jp[4 * NJ + e], jp[5 * NJ + e]);
-                        vmax = jp[6 * NJ + e];
-                        total = 0.0f;
-                        job = e;
-                     }
-                  }
-                  head += n_idle;
-               }
-               if (__ballot(job >= 0) == 0ull) break;
-               if (job >= 0) {
-                  MDH_WORK(1);
-                  const float dist = sdf<PART>(sc, o + d * total);
-                  if (dist < MDH_EPS) job = -1; // blocked: the byte stays 0
-                  else {
-                     total += dist;
-                     if (!(total < vmax)) { reached[job] = 1; job = -1; }
-                  }
-               }
-            }
-         }
-         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-         __builtin_amdgcn_wave_barrier();
-         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-#pragma unroll
-         for (int r = 0; r < R; ++r) { // the light's term, dense
-            const float visibility = reached[r * 64 + lane] ? 1.0f : 0.0f;
-            const f3 L_in = rads[r] * (sexp(-Ld[r] * MDH_TAU) * visibility);
-            result[r] = result[r] + (L_in * MDH_TAU) * henvey_greenstein_phase(Ls[r], dirs[r]);
-         }
-         __builtin_amdgcn_wave_barrier(); // (the next light's set-up overwrites what this finish read)
-      }
-#pragma unroll
-      for (int r = 0; r < R; ++r) {
-         const long lin = begin + r * 64 + lane;
-         if (lin < n) {
-            int i, j;
-            froxel_texel(vol, W, H, lin, i, j);
-            float *o = vol.vis + ((size_t)j * W + i) * 3;
-            o[0] = result[r].x; o[1] = result[r].y; o[2] = result[r].z;
-         }
-      }
-   }
-#elif MDH_VIS_QUEUE
-   const long wave_global = (long)blockIdx.x * (MDH_BLOCK / 64) + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-   const long begin = wave_global * (64 * MDH_VIS_ROUNDS);
-   if (begin >= n) return; // (wave-uniform)
-   const long end = min(n, begin + 64 * MDH_VIS_ROUNDS);
-   long next = begin; // (wave-uniform) the first froxel of the batch nobody has taken
-   // a lane's froxel (lin < 0: none), its light, its ray
-   long lin = -1;
-   int light = 0;
-   bool marching = false;
-   float vis = 0.0f, total = 0.0f, L_dist = 0.0f;
-   f3 pos = F3(0.0f, 0.0f, 0.0f), dir = pos, L = pos, radiance = pos, result = pos;
-   for (;;) {
-      const unsigned long long mm = __ballot(marching);
-      const bool waiting = !marching && (lin >= 0 || next < end); // a ray that has ended, or an empty lane while froxels are left
-      const unsigned long long wm = __ballot(waiting);
-      if (mm == 0ull && wm == 0ull) break;
-      if (mm == 0ull || __popcll(wm) >= MDH_VIS_REFILL) {
-         if (waiting) {
-            if (lin >= 0) { // sample_lights :8-19: the ended ray's term, in light order
-               const f3 L_in = radiance * (sexp(-L_dist * MDH_TAU) * vis);
-               result = result + (L_in * MDH_TAU) * henvey_greenstein_phase(L, dir);
-               ++light;
-            }
-            if (lin >= 0 && light >= sc.total_lights) {
-               int i, j;
-               froxel_texel(vol, W, H, lin, i, j);
-               float *o = vol.vis + ((size_t)j * W + i) * 3;
-               o[0] = result.x; o[1] = result.y; o[2] = result.z;
-               lin = -1;
-            }
-         }
-         { // empty lanes take the next froxels of the batch, in lane order
-            const bool empty = waiting && lin < 0;
-            const unsigned long long em = __ballot(empty);
-            if (empty) {
-               const long mine = next + (long)__builtin_amdgcn_mbcnt_hi((unsigned)(em >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)em, 0u));
-               if (mine < end) {
-                  lin = mine;
-                  int i, j;
-                  froxel_texel(vol, W, H, lin, i, j);
-                  froxel_point(vol, cam, W, H, i, j, pos, dir);
-                  result = F3(0.0f, 0.0f, 0.0f);
-                  light = 0;
-                  if (sc.total_lights <= 0) { // no light: the texel is 0
-                     float *o = vol.vis + ((size_t)j * W + i) * 3;
-                     o[0] = 0.0f; o[1] = 0.0f; o[2] = 0.0f;
-                     lin = -1;
-                  }
-               }
-            }
-            next = min(end, next + (long)__popcll(em));
-         }
-         if (waiting && lin >= 0) { // the next light's ray (raycast_visibility, raymarching.glsl:39-56, from its first test on)
-            radiance = sample_light<(PART & MDH_PF_CUSTOM) != 0>(sc, light, pos, F3(1.0f, 0.0f, 0.0f), L, L_dist); // compute_frustrum_visibility.glsl:12
-            MDH_WORK(0);
-            total = 0.0f;
-            vis = 1.0f;
-            marching = total < L_dist; // (a loop that is never entered: visible)
-         }
-      }
-      if (marching) {
-         MDH_WORK(1);
-         const float dist = sdf<PART>(sc, pos + L * total);
-         if (dist < MDH_EPS) { vis = 0.0f; marching = false; }
-         else {
-            total += dist;
-            if (!(total < L_dist)) marching = false;
-         }
-      }
-   }
-#else
-   // (MDH_VIS_LOOP froxels per lane, one after the other: a workgroup stages the scene table once for all of them)
+   // (a loop of ONE turn, left over from the measurement of two and four froxels per lane: without it the compiler allocates the
+   //  kernel's registers differently -- removing it is a change of the kernel, to be measured as one)
 #pragma unroll 1
-   for (int turn = 0; turn < MDH_VIS_LOOP; ++turn) {
-      const long lin = ((long)blockIdx.x * MDH_VIS_LOOP + turn) * MDH_BLOCK + threadIdx.x;
+   for (int turn = 0; turn < 1; ++turn) {
+      const long lin = ((long)blockIdx.x + turn) * MDH_BLOCK + threadIdx.x;
       if (lin >= n) return;
       int i, j;
       froxel_texel(vol, W, H, lin, i, j);
@@ -1452,7 +1031,6 @@ template <int PART> __global__ __launch_bounds__(MDH_BLOCK) void k_visibility(KS
       float *o = vol.vis + ((size_t)j * W + i) * 3;
       o[0] = result.x; o[1] = result.y; o[2] = result.z;
    }
-#endif
 }
 
 // -------------------------------------------------------------------- scattering pass

@@ -18,24 +18,9 @@
 #ifndef MDH_SHARE_FIRST_STEP
 #define MDH_SHARE_FIRST_STEP 1
 #endif
-#ifndef MDH_TAP_EARLY
-#define MDH_TAP_EARLY 1
-#endif
-#ifndef MDH_TWIN_PREV_PART
-#define MDH_TWIN_PREV_PART 0
-#endif
-#ifndef MDH_TAP_EARLY_PART
-#define MDH_TAP_EARLY_PART 0
-#endif
-#ifndef MDH_PART_PARK_VD
-#define MDH_PART_PARK_VD 1
-#endif
 #define MDH_PARK_VD_ROW 19 // (rows 19-21: allocated by the host for scenes with a space partition, lds_bytes_screen; six wavefronts per SIMD need 22 rows or fewer)
 #ifndef MDH_SKIP_NULL_RAYS
 #define MDH_SKIP_NULL_RAYS 1
-#endif
-#ifndef MDH_TAP_SQRT_CORE
-#define MDH_TAP_SQRT_CORE 1
 #endif
 #ifndef MDH_TWIN_PREV
 #define MDH_TWIN_PREV 1
@@ -149,14 +134,8 @@ template <int PART> MDH_DEV bool march_plain(const KScene &sc, f3 o, f3 d, float
 #else
 #define MDH_DIRECT_PARK_ROWS 13
 #endif
-#ifndef MDH_QVIS_SHARED
-#define MDH_QVIS_SHARED 0 // the radiance pass's visibility queue shared by the four wavefronts of a workgroup (queued_visibility_shared)
-#endif
-#if MDH_QVIS_SHARED && MDH_VIS_CLEAR
-#error "queued_visibility_shared lists its rays without segment_clear: build it with -DMDH_VIS_CLEAR=0"
-#endif
-#if defined(MDH_PHASES) || MDH_QVIS_SHARED || defined(MDH_PARK_PAD) // (MDH_PARK_PAD: what one more row costs, measured by itself)
-#define MDH_PARK_DWORDS 20 // (row 19: the diagnostic's accumulators / the shared queue's second list and counters)
+#ifdef MDH_PHASES
+#define MDH_PARK_DWORDS 20 // (row 19: the diagnostic's accumulators)
 #else
 #define MDH_PARK_DWORDS 19
 #endif
@@ -174,82 +153,49 @@ MDH_DEV float *park_base(const KScene &sc) { return (float *)(s_tab + sc.table_f
 // -- stays live instead of a per-lane address that the compiler kept in scratch.  M0 is saved and restored (it is
 // compiler-reserved); `s_nop 0`: one wait state between a write of M0 and an LDS add-TID instruction.  The reads wait
 // for their data inside the statement (the compiler does not count the LDS operations of an asm statement).
-#ifndef MDH_PARK_ADDTID
-#define MDH_PARK_ADDTID 1
-#endif
 MDH_DEV int park_wave_base(const float *pk)
 {
    const unsigned lds = (unsigned)(size_t)(const __attribute__((address_space(3))) float *)pk;
    return __builtin_amdgcn_readfirstlane((int)(lds + (threadIdx.x & ~63u) * 4u));
 }
-MDH_DEV int park_col(const float *pk, int wb) // (the generic form: thread index in the park rows)
-{
-   const unsigned lds = (unsigned)(size_t)(const __attribute__((address_space(3))) float *)pk;
-   return (int)((unsigned)wb - lds) / 4 + lane_index_fresh();
-}
 template <int SLOT> MDH_DEV void park_store3(float *pk, int wb, f3 v)
 {
-#if MDH_PARK_ADDTID
    unsigned keep;
    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %4\n\ts_nop 0\n\tds_write_addtid_b32 %1 offset:%5\n\tds_write_addtid_b32 %2 offset:%6\n\t"
                 "ds_write_addtid_b32 %3 offset:%7\n\ts_mov_b32 m0, %0"
                 : "=&s"(keep) : "v"(v.x), "v"(v.y), "v"(v.z), "s"(wb), "i"(SLOT * MDH_BLOCK * 4), "i"((SLOT + 1) * MDH_BLOCK * 4), "i"((SLOT + 2) * MDH_BLOCK * 4) : "memory");
-#else
-   const int t = park_col(pk, wb);
-   pk[(SLOT + 0) * MDH_BLOCK + t] = v.x;
-   pk[(SLOT + 1) * MDH_BLOCK + t] = v.y;
-   pk[(SLOT + 2) * MDH_BLOCK + t] = v.z;
-#endif
 }
 template <int SLOT> MDH_DEV f3 park_load3(const float *pk, int wb)
 {
-#if MDH_PARK_ADDTID
    unsigned keep;
    f3 v;
    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %4\n\ts_nop 0\n\tds_read_addtid_b32 %1 offset:%5\n\tds_read_addtid_b32 %2 offset:%6\n\t"
                 "ds_read_addtid_b32 %3 offset:%7\n\ts_waitcnt lgkmcnt(0)\n\ts_mov_b32 m0, %0"
                 : "=&s"(keep), "=&v"(v.x), "=&v"(v.y), "=&v"(v.z) : "s"(wb), "i"(SLOT * MDH_BLOCK * 4), "i"((SLOT + 1) * MDH_BLOCK * 4), "i"((SLOT + 2) * MDH_BLOCK * 4) : "memory");
    return v;
-#else
-   const int t = park_col(pk, wb);
-   return F3(pk[(SLOT + 0) * MDH_BLOCK + t], pk[(SLOT + 1) * MDH_BLOCK + t], pk[(SLOT + 2) * MDH_BLOCK + t]);
-#endif
 }
 template <int SLOT> MDH_DEV f2 park_load2(const float *pk, int wb)
 {
-#if MDH_PARK_ADDTID
    unsigned keep;
    f2 v;
    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tds_read_addtid_b32 %1 offset:%4\n\tds_read_addtid_b32 %2 offset:%5\n\t"
                 "s_waitcnt lgkmcnt(0)\n\ts_mov_b32 m0, %0"
                 : "=&s"(keep), "=&v"(v.x), "=&v"(v.y) : "s"(wb), "i"(SLOT * MDH_BLOCK * 4), "i"((SLOT + 1) * MDH_BLOCK * 4) : "memory");
    return v;
-#else
-   const int t = park_col(pk, wb);
-   return F2(pk[(SLOT + 0) * MDH_BLOCK + t], pk[(SLOT + 1) * MDH_BLOCK + t]);
-#endif
 }
 template <int SLOT> MDH_DEV void park_store1(float *pk, int wb, float v)
 {
-#if MDH_PARK_ADDTID
    unsigned keep;
    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tds_write_addtid_b32 %1 offset:%3\n\ts_mov_b32 m0, %0"
                 : "=&s"(keep) : "v"(v), "s"(wb), "i"(SLOT * MDH_BLOCK * 4) : "memory");
-#else
-   pk[SLOT * MDH_BLOCK + park_col(pk, wb)] = v;
-#endif
 }
 template <int SLOT> MDH_DEV float park_load1(const float *pk, int wb)
 {
-#if MDH_PARK_ADDTID
    unsigned keep;
    float v;
    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tds_read_addtid_b32 %1 offset:%3\n\ts_waitcnt lgkmcnt(0)\n\ts_mov_b32 m0, %0"
                 : "=&s"(keep), "=&v"(v) : "s"(wb), "i"(SLOT * MDH_BLOCK * 4) : "memory");
    return v;
-#else
-   return pk[SLOT * MDH_BLOCK + park_col(pk, wb)];
-#endif
 }
 
 
@@ -271,15 +217,6 @@ template <int SLOT> MDH_DEV float park_load1(const float *pk, int wb)
 #ifndef MDH_CORNER_UNROLL
 #define MDH_CORNER_UNROLL 8 // the cage-corner loop of the pixel program, unrolled: constant corner bits, no loop branch (measured 1, 2, 4, 8)
 #endif
-#ifndef MDH_QVIS_FAR_FIRST
-#define MDH_QVIS_FAR_FIRST 1
-#endif
-#ifndef MDH_MATERIAL_PER_LIGHT
-#define MDH_MATERIAL_PER_LIGHT 1
-#endif
-#ifndef MDH_QVIS_REDERIVE
-#define MDH_QVIS_REDERIVE 1
-#endif
 #ifndef MDH_QVIS_REFILL
 #define MDH_QVIS_REFILL 16 // idle lanes that trigger a refill
 #endif
@@ -299,12 +236,10 @@ MDH_DEV int queued_visibility(const KScene &sc, const KProbes &pr, float *pk, f3
    // corner j ^ far for j = 0 .. 7 goes from the farthest to the nearest), so that the longest rays of the wave start first
    // and its last rays are short ones -- the queue drains with fewer idle lanes.  The order of the list decides nothing else.
    int far = 0;
-#if MDH_QVIS_FAR_FIRST
    {
       const f3 lo = grid_to_world(pr, gp);
       far = ((P.x - lo.x) < (lo.x + pr.sx - P.x) ? 1 : 0) | ((P.y - lo.y) < (lo.y + pr.sy - P.y) ? 2 : 0) | ((P.z - lo.z) < (lo.z + pr.sz - P.z) ? 4 : 0);
    }
-#endif
 #pragma unroll 1
    for (int j = 0; j < 8; ++j) {
       const int i = j ^ far;
@@ -356,11 +291,7 @@ MDH_DEV int queued_visibility(const KScene &sc, const KProbes &pr, float *pk, f3
       }
       if (__ballot(job >= 0) == 0ull) break;
       if (job >= 0) {
-#ifdef MDH_DIAG_DRAIN
-         if (head < njobs) { MDH_DIAG_STEP(3); } else { MDH_DIAG_STEP(4); }
-#else
          MDH_DIAG_STEP(3);
-#endif
          MDH_WORK(1);
          const float sd = sdf<PART>(sc, o + d * total);
          if (sd < MDH_EPS) job = -1; // blocked: the bit stays 0
@@ -377,254 +308,6 @@ MDH_DEV int queued_visibility(const KScene &sc, const KProbes &pr, float *pk, f3
    __builtin_amdgcn_wave_barrier();
    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
    return bits | words[threadIdx.x];
-}
-
-
-// ---------------------------------------------------------------------------------------------
-// queued_visibility_shared (MDH_QVIS_SHARED) -- the same queue with its END shared by the workgroup.
-//
-// What the per-wavefront queue loses is its end: once its list is handed out a wavefront marches on until its longest
-// ray ends, with 12.6 of 64 lanes alive on average (98 k of the radiance pass's 274 k wave-evaluations).  Here every
-// wavefront still lists its own jobs in its own rows and draws from them, but the lists' heads are LDS counters, so a
-// wavefront whose list is empty draws from its neighbours' (a STOLEN job), and a wavefront down to a few rays while
-// another one still marches DONATES them -- resumable jobs (entry + the distance marched so far) in a second, small
-// list -- and waits for its results instead of marching at a fraction of its width.  The last marching wavefront
-// never donates (a counter of marching wavefronts decides, atomically), so every job is finished by somebody.  Nothing
-// here waits at a barrier (a wavefront that hits nothing never comes here), and every wait is bounded: if a bound were
-// ever reached the results would be wrong and the parity tests would say so, but no wavefront spins for ever.
-//
-// The LDS unit serves the DS instructions of a workgroup's wavefronts one after the other, each wavefront's in program
-// order: a wavefront that sees a counter move sees everything its writer stored before.  The fences below are therefore
-// wavefront-scoped (they order the compiler, not the hardware), and the counters a march step looks at are read one
-// step AHEAD (their latency hides behind the distance evaluation; acting on a stale value is harmless: a draw that comes
-// too late gets nothing).
-//
-// LDS of the workgroup (behind the scene table): rows 12-15 = the four wavefronts' lists (u16 entries lane | corner << 6),
-// row 16 = first-step distances, row 17 = result words, row 19 = the counters and list 2:
-#define QS_ROW 19
-#define QS_LIST 0      // [4] head | njobs << 16 of each wavefront's list (a draw adds to the head, whatever is left)
-#define QS_Q2 4        // head | tail << 16 of list 2 (draws by compare-and-swap: its tail grows)
-#define QS_MARCHING 5  // wavefronts in the march loop
-#define QS_PENDING 8   // [4] per wavefront: its jobs in other wavefronts' hands
-#define QS_E2 64       // [64] entries of list 2 (-1 = not written yet)
-#define QS_T2 128      // [64] distances marched so far
-#ifndef QS_DONATE_MAX
-#define QS_DONATE_MAX 16
-#endif
-#ifndef QS_BISECT
-#define QS_BISECT 0 // (1: the per-wavefront queue inside the shared build; 2: no stealing)
-#endif
-static_assert(QS_DONATE_MAX * 4 <= 64, "list 2 holds one donation of every wavefront");
-#define QS_SPIN_MAX (1 << 16) // (a few milliseconds: a legitimate wait is some tens of march steps)
-#define QS_FOREIGN 0x800      // job bit: counted in QS_PENDING of its owner (stolen or donated)
-MDH_DEV void qvis_shared_init(const KScene &sc) // all threads, before the kernel's first barrier
-{
-   int *ctl = (int *)(park_base(sc) + QS_ROW * MDH_BLOCK);
-   ctl[threadIdx.x] = threadIdx.x >= QS_E2 && threadIdx.x < QS_T2 ? -1 : 0;
-}
-template <int PART>
-MDH_DEV int queued_visibility_shared(const KScene &sc, const KProbes &pr, float *pk, f3 P, f3 N, i3 gp, int folded, float sd0)
-{
-   const int lane = threadIdx.x & 63, wbase = threadIdx.x & ~63, wv = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-   const bool leader = lane == (int)__ffsll((long long)__ballot(true)) - 1; // (only the lanes whose point was hit are here)
-   int *words = (int *)(pk + 17 * MDH_BLOCK);
-   int *ctl = (int *)(pk + QS_ROW * MDH_BLOCK);
-   // (reads of what other wavefronts write: relaxed atomic loads through an LDS-typed pointer -- a volatile access
-   // through the generic pointer is a system-scope FLAT load with a full wait behind it, 40 % of the pass when the
-   // counters were read that way)
-   typedef __attribute__((address_space(3))) int *LdsInt;
-   const LdsInt lctl = (LdsInt)ctl;
-#define QS_LD(k) __hip_atomic_load(lctl + (k), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP)
-#define QS_ST(k, v) __hip_atomic_store(lctl + (k), (v), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP)
-   pk[16 * MDH_BLOCK + threadIdx.x] = sd0;
-   words[threadIdx.x] = 0;
-   int bits = 0, njobs = 0;
-   int far = 0;
-#if MDH_QVIS_FAR_FIRST
-   {
-      const f3 lo = grid_to_world(pr, gp);
-      far = ((P.x - lo.x) < (lo.x + pr.sx - P.x) ? 1 : 0) | ((P.y - lo.y) < (lo.y + pr.sy - P.y) ? 2 : 0) | ((P.z - lo.z) < (lo.z + pr.sz - P.z) ? 4 : 0);
-   }
-#endif
-#pragma unroll 1
-   for (int j = 0; j < 8; ++j) { // (as in queued_visibility)
-      const int i = j ^ far;
-      bool need = false;
-      if (!(i & folded)) {
-         const f3 hvec = grid_to_world(pr, cage_probe(pr, gp, i)) - P;
-         const float vmax = length(hvec) - MDH_MIN_STEP * 5.0f;
-         if (!(0.0f < vmax)) bits |= 1 << i;
-         else if (sd0 < MDH_EPS) { }
-         else if (!(sd0 < vmax)) bits |= 1 << i;
-         else need = true;
-      }
-      const unsigned long long m = __ballot(need);
-      if (need) *qvis_entry(pk, wbase, njobs + (int)__builtin_amdgcn_mbcnt_hi((unsigned)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m, 0u))) = (unsigned short)(lane | (i << 6));
-      njobs += __popcll(m);
-   }
-   __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-   if (leader) { // the list is open: its length, and one more marching wavefront
-      atomicAdd(&ctl[QS_MARCHING], 1);
-      atomicAdd(&ctl[QS_LIST + wv], njobs << 16);
-   }
-   int job = -1;
-   float total = 0.0f, vmax = 0.0f;
-   f3 o = F3(0.0f, 0.0f, 0.0f), d = F3(0.0f, 0.0f, 0.0f);
-   bool donated = false;
-   const int n_here = (int)__popcll(__ballot(true));
-   const int refill = min((int)MDH_QVIS_REFILL, n_here);
-   int own_left = njobs; // (an upper bound: thieves take from it too)
-   // the counters as they were one step ago
-   int c_list[4] = {0, 0, 0, 0}, c_q2 = 0, c_marching = 0;
-#define QS_OPEN(w) ((c_list[w] & 0xffff) < ((unsigned)c_list[w] >> 16))
-#define QS_READ_COUNTERS() do { c_list[0] = QS_LD(QS_LIST + 0); c_list[1] = QS_LD(QS_LIST + 1); c_list[2] = QS_LD(QS_LIST + 2); c_list[3] = QS_LD(QS_LIST + 3); \
-                                c_q2 = QS_LD(QS_Q2); c_marching = QS_LD(QS_MARCHING); } while (0)
-   for (;;) {
-      const unsigned long long idle = __ballot(job < 0);
-      const int n_idle = __popcll(idle);
-      const int n_active = n_here - n_idle;
-      if (n_idle >= refill) {
-         // where to draw from: the own list, a neighbour's, the donated rays
-         int from = -1;
-         if (own_left > 0) from = wv;
-         else {
-            int any = __builtin_amdgcn_readfirstlane((QS_OPEN(0) ? 1 : 0) | (QS_OPEN(1) ? 2 : 0) | (QS_OPEN(2) ? 4 : 0) | (QS_OPEN(3) ? 8 : 0) |
-                                                           ((c_q2 & 0xffff) < ((unsigned)c_q2 >> 16) ? 16 : 0));
-#if QS_BISECT == 2
-            any = 0; // (no stealing)
-#endif
-            if (any) from = __ffs(any) - 1;
-         }
-         if (from >= 0 && from < 4) {
-            const bool foreign = from != wv;
-            int old = 0;
-            if (leader) {
-               if (foreign) atomicAdd(&ctl[QS_PENDING + from], n_idle); // (before the draw: its owner may be about to look)
-               old = atomicAdd(&ctl[QS_LIST + from], n_idle);
-            }
-            old = __builtin_amdgcn_readfirstlane(old);
-            const int h = old & 0xffff, got = max(0, min(n_idle, (int)((unsigned)old >> 16) - h));
-            if (foreign && leader && got < n_idle) atomicSub(&ctl[QS_PENDING + from], n_idle - got);
-            if (!foreign) own_left = (int)((unsigned)old >> 16) - h - got;
-            if (job < 0) {
-               const int rank = (int)__builtin_amdgcn_mbcnt_hi((unsigned)(idle >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)idle, 0u));
-               if (rank < got) {
-                  const int e = *qvis_entry(pk, from * 64, h + rank);
-                  const int owner = from * 64 + (e & 63), corner = e >> 6;
-                  const f3 oP = F3(pk[0 * MDH_BLOCK + owner], pk[1 * MDH_BLOCK + owner], pk[2 * MDH_BLOCK + owner]);
-                  const f3 oN = F3(pk[3 * MDH_BLOCK + owner], pk[4 * MDH_BLOCK + owner], pk[5 * MDH_BLOCK + owner]);
-                  const f3 hvec = grid_to_world(pr, cage_probe(pr, world_to_grid(pr, oP), corner)) - oP;
-                  const float dist = length(hvec);
-                  d = sdiv3(hvec, dist);
-                  vmax = dist - MDH_MIN_STEP * 5.0f;
-                  o = oP + (oN * MDH_MIN_STEP) * 5.0f;
-                  total = pk[16 * MDH_BLOCK + owner];
-                  job = e | (from << 9) | (foreign ? QS_FOREIGN : 0);
-               }
-            }
-            if (foreign || got == 0) { QS_READ_COUNTERS(); }
-            continue; // (the lanes have changed: count them again)
-         } else if (from == 4) { // the donated rays: their list grows, so the draw is a compare-and-swap
-            int h = 0, got = 0;
-            if (leader)
-               for (int tries = 0; tries < 64; ++tries) {
-                  const int q = QS_LD(QS_Q2);
-                  const int want = min(n_idle, (int)((unsigned)q >> 16) - (q & 0xffff));
-                  if (want <= 0) break;
-                  if (atomicCAS(&ctl[QS_Q2], q, q + want) == q) { h = q & 0xffff; got = want; break; }
-               }
-            h = __builtin_amdgcn_readfirstlane(h); got = __builtin_amdgcn_readfirstlane(got);
-            if (job < 0) {
-               const int rank = (int)__builtin_amdgcn_mbcnt_hi((unsigned)(idle >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)idle, 0u));
-               if (rank < got) {
-                  int e = -1;
-                  for (int spin = 0; spin < QS_SPIN_MAX; ++spin) { e = QS_LD(QS_E2 + ((h + rank) & 63)); if (e >= 0) break; __builtin_amdgcn_s_sleep(1); }
-                  if (e >= 0) {
-                     const int owner = ((e >> 9) & 3) * 64 + (e & 63), corner = (e >> 6) & 7;
-                     const f3 oP = F3(pk[0 * MDH_BLOCK + owner], pk[1 * MDH_BLOCK + owner], pk[2 * MDH_BLOCK + owner]);
-                     const f3 oN = F3(pk[3 * MDH_BLOCK + owner], pk[4 * MDH_BLOCK + owner], pk[5 * MDH_BLOCK + owner]);
-                     const f3 hvec = grid_to_world(pr, cage_probe(pr, world_to_grid(pr, oP), corner)) - oP;
-                     const float dist = length(hvec);
-                     d = hvec / dist;
-                     vmax = dist - MDH_MIN_STEP * 5.0f;
-                     o = oP + (oN * MDH_MIN_STEP) * 5.0f;
-                     total = __int_as_float(QS_LD(QS_T2 + ((h + rank) & 63)));
-                     job = e;
-                  }
-               }
-            }
-            QS_READ_COUNTERS();
-            continue;
-         } else if (n_active == 0) {
-            // nothing runs and, one step ago, nothing was left to draw: look now
-            QS_READ_COUNTERS();
-            int any = __builtin_amdgcn_readfirstlane((QS_OPEN(0) || QS_OPEN(1) || QS_OPEN(2) || QS_OPEN(3) || (c_q2 & 0xffff) < ((unsigned)c_q2 >> 16)) ? 1 : 0);
-#if QS_BISECT == 2
-            any = 0;
-#endif
-            if (any) continue;
-            // leave the march -- unless this is its last wavefront and a donor has appended meanwhile (donors append before they leave)
-            int was = 0;
-            if (leader) was = atomicSub(&ctl[QS_MARCHING], 1);
-            was = __builtin_amdgcn_readfirstlane(was);
-            if (was > 1) break;
-            const int q = __builtin_amdgcn_readfirstlane(QS_LD(QS_Q2));
-            if (!((q & 0xffff) < (int)((unsigned)q >> 16))) break;
-            if (leader) atomicAdd(&ctl[QS_MARCHING], 1);
-            QS_READ_COUNTERS();
-            continue;
-         }
-      }
-      if (!donated && own_left <= 0 && n_active <= QS_DONATE_MAX && __builtin_amdgcn_readfirstlane(c_marching) > 1) {
-         // hand the last rays to the wavefronts that still march
-         const unsigned long long act = __ballot(job >= 0);
-         int b2 = 0;
-         if (leader) b2 = atomicAdd(&ctl[QS_Q2], n_active << 16);
-         b2 = (int)((unsigned)__builtin_amdgcn_readfirstlane(b2) >> 16);
-         if (job >= 0) {
-            const int r2 = (b2 + (int)__builtin_amdgcn_mbcnt_hi((unsigned)(act >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)act, 0u))) & 63;
-            if (!(job & QS_FOREIGN)) atomicAdd(&ctl[QS_PENDING + ((job >> 9) & 3)], 1);
-            QS_ST(QS_T2 + r2, __float_as_int(total));
-            QS_ST(QS_E2 + r2, job | QS_FOREIGN);
-            job = -1;
-         }
-         donated = true;
-         int was = 0;
-         if (leader) was = atomicSub(&ctl[QS_MARCHING], 1);
-         was = __builtin_amdgcn_readfirstlane(was);
-         if (was > 1) break;                           // somebody marches on: wait for the results below
-         if (leader) atomicAdd(&ctl[QS_MARCHING], 1);  // the others left meanwhile: take the rays back from list 2
-         QS_READ_COUNTERS();
-         continue;
-      }
-      QS_READ_COUNTERS(); // (for the next step: the reads complete behind the distance evaluation)
-      if (job >= 0) {
-         MDH_DIAG_STEP(3);
-         MDH_WORK(1);
-         const float sd = sdf<PART>(sc, o + d * total);
-         bool done = false;
-         if (sd < MDH_EPS) done = true; // blocked: the bit stays 0
-         else {
-            total += sd;
-            if (!(total < vmax)) { atomicOr(&words[((job >> 9) & 3) * 64 + (job & 63)], 1 << ((job >> 6) & 7)); done = true; }
-         }
-         if (done) {
-            if (job & QS_FOREIGN) atomicSub(&ctl[QS_PENDING + ((job >> 9) & 3)], 1); // (behind the result, in this wavefront's DS order)
-            job = -1;
-         }
-      }
-   }
-   // this wavefront's own jobs may still be in other hands
-   for (int spin = 0; spin < QS_SPIN_MAX; ++spin) {
-      if (__builtin_amdgcn_readfirstlane(QS_LD(QS_PENDING + wv)) <= 0) break;
-      __builtin_amdgcn_s_sleep(2);
-   }
-   __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-   return bits | __hip_atomic_load((LdsInt)words + threadIdx.x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-#undef QS_OPEN
-#undef QS_READ_COUNTERS
-#undef QS_LD
-#undef QS_ST
 }
 
 // sample_radiance_with_specular (render_probes.glsl:71-136, M_COMPUTE_INDIRECT_SPECULAR == 1) from the reflection's hit
@@ -687,12 +370,8 @@ MDH_DEV f3 radiance_with_specular(const KScene &sc, const KProbes &pr, const flo
 // instruction per use (the screen kernel had a thousand such copies, a third of them in inner loops).  Re-read where a
 // block of probe code begins -- a few scalar loads through a pointer the compiler cannot trace, served by the scalar
 // cache -- they are live for that block only.
-#ifndef MDH_PROBES_FRESH
-#define MDH_PROBES_FRESH 1
-#endif
 MDH_DEV KProbes probes_fresh(const KProbes &pr)
 {
-#if MDH_PROBES_FRESH
    struct KHead { KScene sc; KProbes pr; };
    typedef const KHead __attribute__((address_space(4))) *KHeadPtr;
    KHeadPtr ka = (KHeadPtr)__builtin_amdgcn_kernarg_segment_ptr();
@@ -704,9 +383,6 @@ MDH_DEV KProbes probes_fresh(const KProbes &pr)
 #pragma unroll
    for (int q = 0; q < (int)(sizeof(KProbes) / 4); ++q) dst[q] = src[q];
    return r;
-#else
-   return pr;
-#endif
 }
 
 // SPEC: 0 = no second point (the radiance pass), 1 = the reflection as the reference's renderer fixes it
@@ -727,16 +403,16 @@ MDH_DEV f3 shade_structured(const KScene &sc, const KProbes &pr, const MachineCf
    constexpr int CORNER_UNROLL = ((PART & MDH_PF_PART) || SPEC != 1 || QVIS) ? 1 : MDH_CORNER_UNROLL;
    constexpr int PARK_MAT = MODE == 2 ? MDH_PARK_MAT_DIRECT : MDH_PARK_MAT; // (no probe rows in mode 2: MDH_DIRECT_PARK_ROWS)
    // the irradiance tap of a cage corner issued before its visibility march (its loads land during the march) -- not in the
-   // space-partition variants, whose march needs the registers (MDH_TAP_EARLY_PART)
-   constexpr bool TAP_EARLY = MDH_TAP_EARLY != 0 && (MDH_TAP_EARLY_PART != 0 || !(PART & MDH_PF_PART));
+   // space-partition variants, whose march needs the registers
+   constexpr bool TAP_EARLY = !(PART & MDH_PF_PART);
    // the x-twin's probe term kept for the corner behind it (item 6 of "Exact work elimination") -- not in the space-partition
-   // variants, where its four registers across the visibility march are scratch memory (MDH_TWIN_PREV_PART)
-   constexpr bool TWIN_PREV = MDH_TWIN_PREV != 0 && (MDH_TWIN_PREV_PART != 0 || !(PART & MDH_PF_PART));
+   // variants, where its four registers across the visibility march are scratch memory
+   constexpr bool TWIN_PREV = MDH_TWIN_PREV != 0 && !(PART & MDH_PF_PART);
    // the space-partition variants of the screen pass: the shaded point and its normal come back from park rows behind every
    // corner's visibility march (the second point's wait in the rows of its colour and in three rows of their own) and the probe's grid position is derived again there:
    // the lookups of that march need the registers -- kept live across it, these values went to scratch memory eight times per
    // shaded point (300 MB of spill stores per 1080p launch at six wavefronts per SIMD)
-   constexpr bool PARK_VD = MDH_PART_PARK_VD != 0 && (PART & MDH_PF_PART) != 0 && SPEC == 1 && MODE == 0 && CORNER_UNROLL == 1;
+   constexpr bool PARK_VD = (PART & MDH_PF_PART) != 0 && SPEC == 1 && MODE == 0 && CORNER_UNROLL == 1;
    // the second point goes through the whole of pixel_color_probes' lighting (compute_indirect_specular) ...
    const bool full2 = SPEC == 2 && cfg.spec_mode == 3;
    // ... or is only a position that the cage probes of the FIRST point light (sample_radiance_with_specular)
@@ -749,9 +425,6 @@ MDH_DEV f3 shade_structured(const KScene &sc, const KProbes &pr, const MachineCf
    // (the reflection's colour and the primary hit's material id wait in LDS for the combine, like P, N and the light;
    //  the colour's rows are cleared behind the first point's corner loop, which uses them meanwhile)
    bool shaded = false; // the primary ray hit and the full shading ran
-#if MDH_QVIS_SHARED
-   f3 irr_keep = F3(0.0f, 0.0f, 0.0f);
-#endif
    // the ray that finds the next point to shade
    f3 ro = from, rd = dir_in;
    bool active = lane_valid;
@@ -811,13 +484,9 @@ MDH_DEV f3 shade_structured(const KScene &sc, const KProbes &pr, const MachineCf
                      // (the material is read again for every light, through an id the compiler cannot look through: read
                      //  once in front of the loop, what the BRDF derives from it -- F0, 1 - F0, k -- is hoisted and then
                      //  lives across the shadow march: eight dwords of scratch memory per ray in the seven-wavefront builds)
-#if MDH_MATERIAL_PER_LIGHT
                      int pm_l = pm;
                      asm volatile("" : "+v"(pm_l));
                      Material m = get_material(sc, pm_l);
-#else
-                     Material m = get_material(sc, pm);
-#endif
                      if (ctx && !full2) m.albedo = F3(0.0f, 0.0f, 0.0f); // render_probes.glsl:202-205
                      f3 L;
                      float L_dist;
@@ -832,11 +501,7 @@ MDH_DEV f3 shade_structured(const KScene &sc, const KProbes &pr, const MachineCf
                      // a light that contributes exactly nothing here (outside a spot's cone, black BRDF)
                      // needs no shadow ray: Lo + (+-0) * shadows = Lo for every shadows in [0, 1]
                      const bool lit = MDH_SKIP_NULL_RAYS ? (contrib.x != 0.0f || contrib.y != 0.0f || contrib.z != 0.0f) : true;
-#ifdef MDH_ABL_NO_SHADOW
-                     if (false) {
-#else
                      if (NdotL > MDH_EPS && lit) { // softshadows, raymarching.glsl:4-23
-#endif
                         float res = 1.0f, prev = 1e20f, total = 0.0f;
                         bool blocked = false;
                         bool first = MDH_SHARE_FIRST_STEP != 0;
@@ -889,14 +554,7 @@ MDH_DEV f3 shade_structured(const KScene &sc, const KProbes &pr, const MachineCf
                   int vis_bits = 0; // bit i: visibility of corner i
                   PH_ADD(pt, 2);
                   if (QVIS && ctx == 0) {
-#if MDH_QVIS_SHARED && QS_BISECT == 1
                      vis_bits = queued_visibility<PART>(sc, pr, pk, P, N, gp, folded, sd0);
-#elif MDH_QVIS_SHARED
-                     vis_bits = queued_visibility_shared<PART>(sc, pr, pk, P, N, gp, folded, sd0);
-#else
-                     vis_bits = queued_visibility<PART>(sc, pr, pk, P, N, gp, folded, sd0);
-#endif
-#if MDH_QVIS_REDERIVE
                      // Nothing of the point stays in registers across the queue (it is the pass's longest loop, and the
                      // kernel is built for seven wavefronts per SIMD: what stayed live -- P, N, the cage cell, twenty dwords
                      // -- went to scratch and back, 45 MB per launch at BASELINE config 3).  P and N wait in their park rows,
@@ -907,7 +565,6 @@ MDH_DEV f3 shade_structured(const KScene &sc, const KProbes &pr, const MachineCf
                      const KProbes pg2 = probes_fresh(pr);
                      gp = world_to_grid(pg2, P);
                      folded = ((gp.x < 0 || gp.x >= pg2.gx - 1) ? 1 : 0) | ((gp.y < 0 || gp.y >= pg2.gy - 1) ? 2 : 0) | ((gp.z < 0 || gp.z >= pg2.gz - 1) ? 4 : 0);
-#endif
                   }
                   PH_ADD(pt, 5);
                   // (Reusing the whole irradiance term of a folded corner's twin through a small register ring was
@@ -986,9 +643,6 @@ MDH_DEV f3 shade_structured(const KScene &sc, const KProbes &pr, const MachineCf
                         if (segment_clear<PART>(sc, from_off, vd, vmax)) vmax = 0.0f;
                      bool first = MDH_SHARE_FIRST_STEP != 0;
                      PH_ADD(pt, 4);
-#ifdef MDH_ABL_NO_VIS
-                     if (false)
-#endif
                      if (!(QVIS && !REFLECT)) // (with the queue and no second point this loop is dead code)
                      MDH_WORK(0);
                      if (!(QVIS && !REFLECT))
@@ -1016,9 +670,6 @@ MDH_DEV f3 shade_structured(const KScene &sc, const KProbes &pr, const MachineCf
                         const float crush = 0.2f;
                         if (weight < crush) weight *= weight * weight * (1.0f / (crush * crush));
                         wpre = weight;
-#ifdef MDH_ABL_NO_TAPS
-                        f3 tx = F3((float)q.x, (float)q.y, N.x);
-#else
                         f3 tx;
                         if (TAP_EARLY) tx = atlas_tap_resolve(pq.irr, pq.fmt, tap, u8_tab);
                         else { // (the space-partition variants: the tap's eight registers do not live across the visibility march)
@@ -1026,15 +677,12 @@ MDH_DEV f3 shade_structured(const KScene &sc, const KProbes &pr, const MachineCf
                            const f2 base = probe_id_to_coord<P2>(pq, grid_to_probe_id<P2>(pq, q2));
                            tx = atlas_sample<P2>(pq.irr, pq.fmt, pq.pcx, pq.pcy, pq.ires, pq.ishift, pq.irr_w, pq.irr_h, base.x + div_pcx<P2>(pq, rid.x), base.y + div_pcy<P2>(pq, rid.y), u8_tab, pq.m_ires);
                         }
-#endif
-#if MDH_TAP_SQRT_CORE
                         // A bilinear tap of an RGBA8 atlas is 0 or at least 2^-56: its texels are k / 255, its weights products of
                         // two factors from {0} and [2^-24, 1] (fx = px - floor (px) with px = cx W - 0.5 a multiple of 2^-24 below 1 --
                         // the subtraction is exact there -- and of ulp (px) above; 1 - fx likewise), its terms are not negative.  No
                         // rescaling can apply: the square root's nine-instruction core, 7 instructions less x 3 channels x 8 corners.
                         if (pq.fmt == 0 && !MDH_HYBRID_NUMERICS) s_term = F3(sqrt_unscaled_(tx.x), sqrt_unscaled_(tx.y), sqrt_unscaled_(tx.z));
                         else
-#endif
                         s_term = ssqrt3(tx);
                      } else { // render_probes.glsl:170-183; probe_to_spec = -vd
                         float weight = dot(-vd, -N);
@@ -1065,19 +713,12 @@ MDH_DEV f3 shade_structured(const KScene &sc, const KProbes &pr, const MachineCf
                      // render_probes.glsl:65-66 (0/0 fixed as 0)
                      f3 irr = F3(0.0f, 0.0f, 0.0f);
                      if (accw != 0.0f) { irr = sdiv3(acc, accw); irr = irr * irr; }
-#if MDH_QVIS_SHARED
-                     if (QVIS && !REFLECT) irr_keep = irr; // (rows 12-15 are the workgroup's job list until the kernel ends)
-                     else
-#endif
                      park_store3<12>(pk, wb, irr);
                      if (REFLECT) park_store3<MDH_PARK_SPEC>(pk, wb, F3(0.0f, 0.0f, 0.0f));
                      shaded = true;
                      // the reflection ray of render_probes.glsl:262-275 finds the next point
                      // (the material id comes back from its park slot: kept in a register across the corner loop it is spilled)
                      active = cfg.spec_mode != 0 && tab_float((sc.mat_slot + 2 * __float_as_int(park_load1<PARK_MAT>(pk, wb)) + 1) * 4) < 0.75f;
-#ifdef MDH_ABL_NO_REFLECT
-                     active = false;
-#endif
                      ro = from_off;
                      rd = reflect(rd, N);
                   } else { // render_probes.glsl:186-208
@@ -1117,11 +758,7 @@ MDH_DEV f3 shade_structured(const KScene &sc, const KProbes &pr, const MachineCf
          (void)shaded;
          f3 direct = park_load3<9>(pk, wb);
          if (MODE == 0) {
-#if MDH_QVIS_SHARED
-            const f3 irr = (QVIS && !REFLECT) ? irr_keep : park_load3<12>(pk, wb);
-#else
             const f3 irr = park_load3<12>(pk, wb);
-#endif
             const f3 specular_col = REFLECT ? park_load3<MDH_PARK_SPEC>(pk, wb) : F3(0.0f, 0.0f, 0.0f);
             Material m = get_material(sc, __float_as_int(park_load1<PARK_MAT>(pk, wb)));
             const f3 specular_dir = reflect(dir, normal);
