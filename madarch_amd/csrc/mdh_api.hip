@@ -288,7 +288,6 @@ struct mdh_renderer {
    // an open frame (mdh_frame_begin .. mdh_frame_end)
    bool in_frame = false, frame_pipelined = false;
    bool in_frame_passes = false; // run_pass is called for the passes that end an open frame (frame_end_passes)
-   void *d_rad_rec = nullptr; size_t rad_rec_bytes = 0; // MADARCH_HIP_RAD_SPLIT: the per-ray records between the radiance pass's two kernels
    bool fuse_scat_march = false; // the frame's visibility launch also marches the scattering texels' camera rays (k_visibility)
    int frame_cur = 0;
    int scr_parity = 0; // which screen stream / framebuffer the last pipelined frame drew on
@@ -334,7 +333,7 @@ struct mdh_renderer {
    hipStream_t own_stream = nullptr;
 #ifdef MDH_DIAG
    unsigned long long work[MDH_PASS_COUNT][4] = {{0}}; // g_work of the last run of each pass (mdh_diag_work)
-   int32_t variant[MDH_PASS_COUNT][2] = {{0}};          // run_pass's pfk and pow2 at the last run of each pass (mdh_diag_variant)
+   int32_t variant[MDH_PASS_COUNT][2] = {{0}};          // pick_kernel's pfk and pow2 at the last run of each pass (mdh_diag_variant)
 #endif
    // the communicator of a sharded run (mdh_comm_init): one rank per process and GPU.  With it mdh_render runs the
    // exchange of the atlas slices itself, on the probe stream, between the probe passes.
@@ -479,6 +478,14 @@ static int table_release(mdh_renderer *r, hipStream_t st)
       r->part_used[r->part_slot][si] = true;
    }
    return MDH_OK;
+}
+
+static bool has_custom_kinds(const mdh_renderer *r)
+{
+   bool c = false;
+   for (int k = 0; k < r->npk; ++k) c = c || r->pk[k].type == PK_CUSTOM;
+   for (int k = 0; k < r->nlk; ++k) c = c || r->lk[k].type == LK_CUSTOM;
+   return c;
 }
 
 static int commit_scene(mdh_renderer *r, hipStream_t up)
@@ -680,9 +687,7 @@ static int commit_scene(mdh_renderer *r, hipStream_t up)
    {
       const size_t park = (size_t)MDH_SCR_PARK_ROWS * MDH_BLOCK * sizeof(float), budget = 64 * 1024;
       const size_t n_geo = geo_end - geo_begin, n_res = t.size() - n_geo;
-      bool has_custom = false;
-      for (int k = 0; k < r->npk; ++k) has_custom = has_custom || r->pk[k].type == PK_CUSTOM;
-      for (int k = 0; k < r->nlk; ++k) has_custom = has_custom || r->lk[k].type == LK_CUSTOM;
+      const bool has_custom = has_custom_kinds(r);
       const bool fits = t.size() * 16 + park <= budget;
       if (fits && r->opt_residency == 1 && has_custom)
          return seterr(MDH_E_INVALID, "MDH_OPT_TABLE_RESIDENCY 1: scenes with user-defined kinds keep their table in LDS");
@@ -748,7 +753,7 @@ static int commit_scene(mdh_renderer *r, hipStream_t up)
    s.part_table = r->d_part_ring[r->part_slot];
    s.part_mask_off = (int)part_table_ints(r);
    s.part_mask_words = part_mask_words(r);
-   s.part_bits_f4 = 0;
+   s.part_bits_f4 = 0; // (the bits are never staged into LDS: mdh_device.h, KScene::part_bits_f4)
    { // KScene::part_small: one 8-byte load per lookup, a shift and a mask per built-in type
       int declared = 0;
       bool small = r->part.enable != 0;
@@ -795,7 +800,7 @@ static KProbes make_probes(const mdh_renderer *r)
    p.m_rres = small && p.rres > 1 ? magic(p.rres) : 0u;
    p.m_ires = small && p.ires > 1 ? magic(p.ires) : 0u;
    p.m_pcx = small && p.pcx > 1 ? magic(p.pcx) : 0u;
-   p.rad_mips = nullptr; // (the screen pass sets it: run_pass)
+   p.rad_mips = nullptr; // (the screen pass sets it: pass_screen)
    return p;
 }
 static KCamera make_camera(const mdh_renderer *r)
@@ -877,7 +882,6 @@ extern "C" int32_t mdh_destroy(mdh_renderer *r)
    if (r->vol_stream) (void)hipStreamSynchronize(r->vol_stream);
    if (r->comm) { ncclComm_t c = r->comm; r->comm = nullptr; (void)rccl_api_destroy(c); }
    if (r->d_comm_scratch) (void)hipFree(r->d_comm_scratch);
-   if (r->d_rad_rec) (void)hipFree(r->d_rad_rec);
    peer_drop(r);
    void *ptrs[] = {r->d_table_ring[0], r->d_table_ring[1], r->d_table_ring[2], r->d_table_ring[3], r->d_part_ring[0], r->d_part_ring[1], r->d_part_ring[2], r->d_part_ring[3], r->d_warn, r->d_query, r->d_irr_taps, r->d_rad_steps, r->d_rad_order, r->d_rad_hist, r->d_scr_cost, r->d_scr_order[0], r->d_scr_order[1], r->d_scr_hist, r->d_fb2[0], r->d_fb2[1], r->d_gb2[0][0], r->d_gb2[0][1], r->d_gb2[0][2], r->d_gb2[1][0], r->d_gb2[1][1], r->d_gb2[1][2]};
    for (void *p : ptrs)
@@ -1235,8 +1239,6 @@ static int ensure_committed(mdh_renderer *r, hipStream_t up = nullptr)
    if (r->table_dirty) return commit_scene(r, up ? up : r->stream);
    return MDH_OK;
 }
-// for kernels that never look a cell up (the builders, the distance query): no bits staged behind the scene table
-static KScene ks_no_bits(const mdh_renderer *r) { KScene k = r->ks; k.part_bits_f4 = 0; return k; }
 static size_t lds_bytes(const mdh_renderer *r) { return (size_t)(r->ks.table_f4 + r->ks.part_bits_f4) * sizeof(float4); }
 // the march kernels park MDH_PARK_DWORDS floats per thread behind the table (mdh_march.h)
 static size_t lds_bytes_march(const mdh_renderer *r) { return lds_bytes(r) + (size_t)MDH_PARK_DWORDS * MDH_BLOCK * sizeof(float); }
@@ -1569,17 +1571,42 @@ template <typename Args> static int jit_launch(hipFunction_t f, int blocks, int 
    return MDH_OK;
 }
 
-// The kernels of global residency (MDH_PF_GTAB, mdh_device.h: Geo) are named in ONE function at the end of this file and
-// launched through the pointers it returns: a kernel template is instantiated where it is first named, and the code object
-// keeps that order -- named here and there among the others they would move every existing kernel to another address, and
-// the passes of frames in flight share their CUs' instruction caches (measured: the same kernels at other addresses, each
-// as fast by itself, the headline with frames in flight 0.5 % slower).  Behind everything else they move nothing.
-enum { GK_k_visibility, GK_k_scat_march, GK_k_scattering, GK_k_radiance, GK_k_screen, GK_k_partition_build, GK_k_eval_distance };
-static const void *gtab_kernel(int family, int pfk, int x = 0, int y = 0, int z = 0); // x, y, z: the family's other template arguments
-template <typename... A> static void launch_kernel_ptr(const void *kernel, dim3 grid, dim3 block, size_t lds, hipStream_t st, A... a)
+// Every kernel template is named in ONE function at the end of this file, kernel_ptr, and launched through the pointer it
+// returns: a kernel template is instantiated where it is first named, and the code object keeps that order -- the passes of
+// frames in flight share their CUs' instruction caches (measured: the same kernels at other addresses, each as fast by itself,
+// the headline with frames in flight 0.5 % slower).  The kernels of global residency (MDH_PF_GTAB, mdh_device.h: Geo) come
+// last there: behind everything else they move nothing.
+enum { GK_k_visibility, GK_k_scat_march, GK_k_scattering, GK_k_radiance, GK_k_screen, GK_k_partition_build, GK_k_eval_distance, GK_k_diag_segments };
+// WHICH KERNEL A PASS RUNS ("One place that picks a pass's kernel"): every template argument of the
+// pass's kernel, computed once by pick_kernel; kernel_name and kernel_ptr turn the same description into the name hiprtc
+// instantiates and into the kernel of this library.
+struct PassKernel {
+   int family = -1; // GK_*
+   int pf = 0;      // the kernel's MDH_PF_* word
+   int mode = 0;    // k_screen: the screen mode, ...
+   bool gbuf = false, alt = false; // ... the geometry buffer, the variant of the optional specular bodies
+   bool small = false;             // k_radiance: SMALL
+   bool ada_div = false;           // k_eval_distance: MDH_OPT_ADA_DIVISION
+   bool jit = false; // a function of the scene's hiprtc module (user-defined kinds under MDH_OPT_JIT), not a kernel of this library
+   int pfk = 0;      // the variant by the scene's census, before the pass's own choices, and the power-of-two addressing
+   bool pow2 = false; // ... of the atlases: what mdh_diag_variant reports
+};
+static const void *kernel_ptr(const PassKernel &k);
+template <typename... A> static int launch_kernel_ptr(const void *kernel, dim3 grid, dim3 block, size_t lds, hipStream_t st, A... a)
 {
+   if (!kernel) return seterr(MDH_E_INVALID, "no kernel built for this variant"); // (kernel_ptr lists no such instantiation)
    void *args[] = {(void *)&a...}; // (by value, in the kernel's parameter types: the call sites pass exactly those)
    (void)hipLaunchKernel(kernel, grid, block, args, lds, st); // (errors surface in hipGetLastError, as after hipLaunchKernelGGL)
+   return MDH_OK;
+}
+// the kernels outside the passes that stage the scene table (the partition's builder, the distance query), by its residency
+static const void *table_kernel(const mdh_renderer *r, int family)
+{
+   PassKernel k;
+   k.family = family;
+   k.pf = r->residency ? MDH_PF_GTAB : 0;
+   k.ada_div = r->opt_ada_div != 0;
+   return kernel_ptr(k);
 }
 
 // Update_Partitioning (renderers.adb:757-775): all three methods build the table on the device
@@ -1631,12 +1658,11 @@ extern "C" int32_t mdh_update_partitioning(mdh_renderer *r, int32_t method)
    HIP_TRY(hipMemcpyAsync(r->d_part_ring[ns], r->d_part_ring[r->part_slot], total * 4, hipMemcpyDeviceToDevice, up));
    HIP_TRY(hipMemsetAsync(r->d_warn, 0, 4, up));
    if (cells > 0) {
-      if (r->residency) launch_kernel_ptr(gtab_kernel(GK_k_partition_build, MDH_PF_GTAB), dim3(cells), dim3(64), lds_bytes(r), up, ks_no_bits(r), a);
-      else hipLaunchKernelGGL(k_partition_build, dim3(cells), dim3(64), lds_bytes(r), up, ks_no_bits(r), a); // one wavefront per cell
+      if ((rc = launch_kernel_ptr(table_kernel(r, GK_k_partition_build), dim3(cells), dim3(64), lds_bytes(r), up, r->ks, a)) != MDH_OK) return rc; // one wavefront per cell
       HIP_TRY(hipGetLastError());
    }
    // the lists once more as bits, for every cell (cells the builder left alone keep their lists, and so their bits)
-   hipLaunchKernelGGL(k_partition_bits, dim3((r->part_cells + 63) / 64), dim3(64), lds_bytes(r), up, ks_no_bits(r), r->d_part_ring[ns]);
+   hipLaunchKernelGGL(k_partition_bits, dim3((r->part_cells + 63) / 64), dim3(64), lds_bytes(r), up, r->ks, r->d_part_ring[ns]);
    HIP_TRY(hipGetLastError());
    if ((rc = table_release(r, up)) != MDH_OK) return rc; // (the copy read the current buffer)
    HIP_TRY(hipMemcpyAsync(r->h_warn, r->d_warn, 4, hipMemcpyDeviceToHost, up));
@@ -1649,36 +1675,6 @@ extern "C" int32_t mdh_update_partitioning(mdh_renderer *r, int32_t method)
    r->part_slot = ns;
    r->ks.part_table = r->d_part_ring[ns];
    return MDH_OK;
-}
-
-template <int PART, int MODE> static void launch_screen_g(mdh_renderer *r, hipStream_t st, const KProbes &pr, const KVolumetrics &vol, const KCamera &cam, const ScreenArgs &a, int blocks)
-{
-   if (r->opt_gbuffer) hipLaunchKernelGGL((k_screen<PART, MODE, true>), dim3(blocks), dim3(MDH_BLOCK), lds_bytes_screen(r), st, r->ks, pr, vol, cam, a);
-   else hipLaunchKernelGGL((k_screen<PART, MODE, false>), dim3(blocks), dim3(MDH_BLOCK), lds_bytes_screen(r), st, r->ks, pr, vol, cam, a);
-}
-// (pow2: mode 0 with probe counts and tile resolutions that are all powers of two runs the MDH_PF_POW2 variant;
-//  built for scenes without user-defined kinds only -- those compile their own variant at run time, or interpret)
-template <int PART_> static void launch_screen_m(mdh_renderer *r, hipStream_t st, const KProbes &pr, const KVolumetrics &vol, const KCamera &cam, const ScreenArgs &a, int blocks, bool pow2)
-{
-   // (the census variants are built for the renderer's own pixel program only: the optional specular modes and screen modes 1 and 2
-   //  run the general scan)
-   constexpr int CENSUS = PART_ & (MDH_PF_ROOM | MDH_PF_PSMALL), PART = PART_ & ~CENSUS;
-   if (CENSUS && r->opt_mode == 0 && !(a.spec_mode == 1 || a.spec_mode == 3 || (a.spec_mode == 2 && pr.rad_mips))) {
-      if (pow2) launch_screen_g<PART_ | MDH_PF_POW2, 0>(r, st, pr, vol, cam, a, blocks);
-      else launch_screen_g<PART_, 0>(r, st, pr, vol, cam, a, blocks);
-      return;
-   }
-   if ((CENSUS & MDH_PF_PSMALL) && r->opt_mode == 2) { launch_screen_g<PART_, 2>(r, st, pr, vol, cam, a, blocks); return; } // (simple_scene's direct light + occlusion: BASELINE config 2)
-   if (r->opt_mode == 0) {
-      if (a.spec_mode == 1 || a.spec_mode == 3 || (a.spec_mode == 2 && pr.rad_mips)) { // the other two bodies of render_probes.glsl:264-272 (and mode 2 over a mip chain): a variant of their own
-         if (r->opt_gbuffer) hipLaunchKernelGGL((k_screen<PART, 0, true, true>), dim3(blocks), dim3(MDH_BLOCK), lds_bytes_screen(r), st, r->ks, pr, vol, cam, a);
-         else hipLaunchKernelGGL((k_screen<PART, 0, false, true>), dim3(blocks), dim3(MDH_BLOCK), lds_bytes_screen(r), st, r->ks, pr, vol, cam, a);
-      }
-      else if (pow2 && !(PART & MDH_PF_CUSTOM)) launch_screen_g<(PART & MDH_PF_CUSTOM) ? PART : (PART | MDH_PF_POW2), 0>(r, st, pr, vol, cam, a, blocks);
-      else launch_screen_g<PART, 0>(r, st, pr, vol, cam, a, blocks);
-   }
-   else if (r->opt_mode == 1) launch_screen_g<PART, 1>(r, st, pr, vol, cam, a, blocks);
-   else launch_screen_g<PART, 2>(r, st, pr, vol, cam, a, blocks);
 }
 
 // MDH_OPT_WINDOW: the pinned host buffer the next screen pass stores the window's pixels in.  A ring: the pixels
@@ -1706,446 +1702,444 @@ static int window_slot(mdh_renderer *r, int rank, int world, unsigned **out)
    return MDH_OK;
 }
 
-// the census of the reference's rooms (MDH_PF_ROOM) among the scenes without partition or user-defined kinds (run_pass)
+// the census of the reference's rooms (MDH_PF_ROOM) among the scenes without partition or user-defined kinds (pick_kernel)
 static bool room_census(const mdh_renderer *r)
 {
    return r->ks.n_axis > 0 && r->ks.gplane_count == 0 && r->ks.tcount[PK_SPHERE] == 1 && r->ks.tcount[PK_BOX] == 1 &&
           r->ks.tcount[PK_TRIANGLE] == 0;
 }
+// MDH_OPT_RADIANCE_MIPS: does the screen pass over atlas set `set` read the levels of its radiance atlas (KProbes::rad_mips)?
+static bool rad_mips_used(const mdh_renderer *r, int set) { return r->opt_mips && r->opt_mode == 0 && r->opt_spec != 0 && r->d_rad_mips[set]; }
+
+static PassKernel pick_kernel(const mdh_renderer *r, int pass, int set)
+{
+   PassKernel k;
+   const bool custom = has_custom_kinds(r);
+   // bit 0 = space partition, bit 1 = user-defined kinds, bit 3 = the partition's border falls back to the full scan
+   // (built-in kinds: a variant of its own; with user-defined kinds the kernels test the setting at run time)
+   const int pf = (r->part.enable != 0 ? MDH_PF_PART : 0) | (custom ? MDH_PF_CUSTOM : 0) |
+                  (r->part.enable != 0 && r->part.border_behavior != 0 && !custom ? MDH_PF_FALLBACK : 0);
+   // bit 6 = global residency of the scene table (mdh_device.h: Geo; commit_scene chose it, never with user-defined kinds):
+   // the general variants only -- no census, no power-of-two atlases
+   const bool gtab = r->residency != 0;
+   // bit 4 = the census of the reference's rooms (mdh_device.h: closest_primitive): every plane folded into the axis offsets,
+   // one sphere, one box, nothing else, no partition -- the scan's loops as straight-line code
+   const bool room = pf == 0 && room_census(r) && !gtab;
+   // bit 5 = the partition's small form with its census (mdh_device.h: partitioning_closest_bits)
+   const bool psmall = pf == MDH_PF_PART && r->ks.part_small && r->ks.part_tmask[PK_TRIANGLE] == 0 && r->ks.part_sp_pow2 && r->ks.part_cells < (1 << 24) && !gtab;
+   k.pfk = gtab ? (pf | MDH_PF_GTAB) : room ? MDH_PF_ROOM : (psmall ? (MDH_PF_PART | MDH_PF_PSMALL) : pf);
+   // bit 2: the probe-sampling kernels (radiance, mode-0 screen) have a variant for atlases whose every dimension is a power
+   // of two (and small enough for what it assumes besides: probe ids within 24-bit products, RGBA8 byte offsets within 32
+   // bits -- mdh_device.h: grid_to_probe_id, atlas_rgba8)
+   auto is_pow2 = [](int v) { return v > 0 && (v & (v - 1)) == 0; };
+   const long long pcount = (long long)r->probes.probe_count[0] * r->probes.probe_count[1];
+   const long long rres = r->probes.radiance_resolution, ires = r->probes.irradiance_resolution;
+   k.pow2 = is_pow2(r->probes.probe_count[0]) && is_pow2(r->probes.probe_count[1]) && is_pow2(r->probes.radiance_resolution) &&
+            is_pow2(r->probes.irradiance_resolution) && pcount < 65536 && pcount * rres * rres <= (1ll << 30) && pcount * ires * ires <= (1ll << 30);
+   // user-defined kinds compiled into the kernels (MDH_OPT_JIT), or interpreted by the kernels of this library -- which are
+   // built without the power-of-two variant for them: scenes with user-defined kinds get it from hiprtc only
+   k.jit = custom && r->opt_jit && pass != MDH_PASS_IRRADIANCE;
+   const bool p2 = k.pow2 && !gtab && (!custom || k.jit);
+   k.pf = k.pfk;
+   switch (pass) {
+   case MDH_PASS_RADIANCE:
+      k.family = GK_k_radiance;
+      if (p2) k.pf |= MDH_PF_POW2;
+      k.small = rad_small_launch(r);
+      break;
+   case MDH_PASS_VISIBILITY: k.family = GK_k_visibility; break;
+   case MDH_PASS_SCATTERING: k.family = MDH_SCAT_SPLIT ? GK_k_scat_march : GK_k_scattering; break;
+   case MDH_PASS_SCREEN: {
+      k.family = GK_k_screen;
+      k.mode = r->opt_mode;
+      k.gbuf = r->opt_gbuffer != 0;
+      // the other two bodies of render_probes.glsl:264-272, and mode 2 over a mip chain that really exists: a variant of their own
+      k.alt = k.mode == 0 && (r->opt_spec == 1 || r->opt_spec == 3 || (r->opt_spec == 2 && rad_mips_used(r, set)));
+      // the census variants are built for the renderer's own pixel program (mode 0 without the optional bodies) and, the
+      // partition's, for simple_scene's direct light + occlusion (mode 2, BASELINE config 2): everything else runs the general scan
+      const int census = k.pf & (MDH_PF_ROOM | MDH_PF_PSMALL);
+      if (!((k.mode == 0 && !k.alt) || ((census & MDH_PF_PSMALL) && k.mode == 2))) k.pf &= ~census;
+      if (p2 && k.mode == 0 && !k.alt) k.pf |= MDH_PF_POW2;
+      break;
+   }
+   default: break; // (the irradiance pass has one kernel)
+   }
+   return k;
+}
+// the name hiprtc instantiates for a scene's module
+static std::string kernel_name(const PassKernel &k)
+{
+   char s[64] = "";
+   switch (k.family) {
+   case GK_k_radiance: snprintf(s, sizeof s, "k_radiance<%d, %s>", k.pf, k.small ? "true" : "false"); break;
+   case GK_k_visibility: snprintf(s, sizeof s, "k_visibility<%d>", k.pf); break;
+   case GK_k_scat_march: snprintf(s, sizeof s, "k_scat_march<%d>", k.pf); break;
+   case GK_k_scattering: snprintf(s, sizeof s, "k_scattering<%d>", k.pf); break;
+   case GK_k_screen: snprintf(s, sizeof s, "k_screen<%d, %d, %s, %s>", k.pf, k.mode, k.gbuf ? "true" : "false", k.alt ? "true" : "false"); break;
+   default: break;
+   }
+   return s;
+}
 
 // One pass on stream `st`.  The radiance pass reads the irradiance atlas of set `src` and writes the
 // radiance atlas of set `dst`; every other pass works on set `dst` (in place: src == dst == r->last).
-static int run_pass(mdh_renderer *r, int pass, hipStream_t st, int src, int dst, int fbix = -1)
+struct PassRun {
+   mdh_renderer *r;
+   int pass;
+   hipStream_t st;
+   int src, dst, fbix;
+   PassKernel k;
+   const void *kernel = nullptr; // the kernel of this library, or ...
+   hipFunction_t fn = nullptr;   // ... the function of the scene's hiprtc module (k.jit)
+   KProbes pr;
+   KCamera cam;
+   hipEvent_t e0 = nullptr, e1 = nullptr; // MDH_OPT_TIMING
+};
+// A pass's kernel with its by-value arguments `a`.  Args is the struct of the kernel's parameters in their order: the kernel
+// argument segment, as the function of a hiprtc module takes it (jit_launch).
+template <typename Args, typename... A> static int launch_pass(const PassRun &p, int blocks, size_t lds, A... a)
 {
-   if (fbix < 0) fbix = r->fb_last;
-   // kernel variant: bit 0 = space partition, bit 1 = user-defined kinds (mdh_device.h, MDH_PF_*)
-   bool has_custom = false;
-   for (int k = 0; k < r->npk; ++k) has_custom = has_custom || r->pk[k].type == PK_CUSTOM;
-   for (int k = 0; k < r->nlk; ++k) has_custom = has_custom || r->lk[k].type == LK_CUSTOM;
-   // ... bit 3 = the space partition's border falls back to the full scan (built-in kinds: a variant of its own; with
-   // user-defined kinds the kernels test the setting at run time)
-   const int pf = (r->part.enable != 0 ? MDH_PF_PART : 0) | (has_custom ? MDH_PF_CUSTOM : 0) |
-                  (r->part.enable != 0 && r->part.border_behavior != 0 && !has_custom ? MDH_PF_FALLBACK : 0);
-   // ... bit 4 = the census of the reference's rooms (MDH_PF_ROOM, mdh_device.h: closest_primitive): every plane folded into
-   // the axis offsets, one sphere, one box, nothing else, no partition -- the scan's loops as straight-line code
-   // ... bit 6 = global residency of the scene table (MDH_PF_GTAB, mdh_device.h: Geo; commit_scene chose it): the general
-   // variants only -- no census, no power-of-two atlases, never user-defined kinds
-   const bool gtab = r->residency != 0;
-   const bool room = pf == 0 && room_census(r) && !gtab;
-   // ... bit 5 = the partition's small form with its census (MDH_PF_PSMALL, mdh_device.h: partitioning_closest_bits)
-   const bool psmall = pf == MDH_PF_PART && r->ks.part_small && r->ks.part_tmask[PK_TRIANGLE] == 0 && r->ks.part_sp_pow2 && r->ks.part_cells < (1 << 24) && !gtab;
-   const int pfk = gtab ? (pf | MDH_PF_GTAB) : room ? MDH_PF_ROOM : (psmall ? (MDH_PF_PART | MDH_PF_PSMALL) : pf); // (the kernel variant by the scene's census)
-   // the probe-sampling kernels (radiance, mode-0 screen) have a variant for atlases whose every dimension is a power of two
-   auto is_pow2 = [](int v) { return v > 0 && (v & (v - 1)) == 0; };
-   // (... and small enough for what those variants assume besides: probe ids within 24-bit products, RGBA8 byte offsets
-   //  within 32 bits -- mdh_device.h: grid_to_probe_id, atlas_rgba8)
-   const long long pcount = (long long)r->probes.probe_count[0] * r->probes.probe_count[1];
-   const long long rres = r->probes.radiance_resolution, ires = r->probes.irradiance_resolution;
-   const bool pow2 = is_pow2(r->probes.probe_count[0]) && is_pow2(r->probes.probe_count[1]) && is_pow2(r->probes.radiance_resolution) &&
-                     is_pow2(r->probes.irradiance_resolution) && pcount < 65536 && pcount * rres * rres <= (1ll << 30) &&
-                     pcount * ires * ires <= (1ll << 30);
+   if (p.fn) {
+      Args args = {a...};
+      return jit_launch(p.fn, blocks, MDH_BLOCK, lds, p.st, args);
+   }
+   return launch_kernel_ptr(p.kernel, dim3(blocks), dim3(MDH_BLOCK), lds, p.st, a...);
+}
+
+static int pass_begin(PassRun &p)
+{
+   mdh_renderer *r = p.r;
+   if (p.fbix < 0) p.fbix = r->fb_last;
+   p.pr = make_probes(r);
+   p.pr.rad = r->d_rad2[p.dst];
+   p.pr.irr = r->d_irr2[p.pass == MDH_PASS_RADIANCE ? p.src : p.dst];
+   p.cam = make_camera(r);
+   p.k = pick_kernel(r, p.pass, p.dst);
+   if (p.k.jit) { // a scene hiprtc cannot build falls back to the interpreter for good (the reason stays in mdh_last_error, MDH_OPT_JIT reads 0 afterwards)
+      const std::string name = kernel_name(p.k);
+      if (JitModule *jm = jit_module(r, {name})) p.fn = jm->fn[name];
+      else { r->opt_jit = 0; p.k = pick_kernel(r, p.pass, p.dst); }
+   }
+   if (!p.k.jit && p.pass != MDH_PASS_IRRADIANCE && !(p.kernel = kernel_ptr(p.k))) return seterr(MDH_E_INVALID, "no kernel built for this pass's variant"); // (before anything is acquired)
+   if (p.pass != MDH_PASS_IRRADIANCE) { // (the irradiance pass does not stage the scene table)
+      int trc = table_acquire(r, p.st);
+      if (trc != MDH_OK) return trc;
+   }
 #ifdef MDH_DIAG
-   r->variant[pass][0] = pfk;
-   r->variant[pass][1] = pow2 ? 1 : 0;
+   r->variant[p.pass][0] = p.k.pfk;
+   r->variant[p.pass][1] = p.k.pow2 ? 1 : 0;
 #endif
-#define MDH_LAUNCH_PF(KERNEL, GRID, BLOCK, LDS, ...)                                                      \
-   do {                                                                                                   \
-      switch (pfk) {                                                                                      \
-      case 0: hipLaunchKernelGGL(KERNEL<0>, GRID, BLOCK, LDS, st, __VA_ARGS__); break;                     \
-      case MDH_PF_ROOM: hipLaunchKernelGGL(KERNEL<MDH_PF_ROOM>, GRID, BLOCK, LDS, st, __VA_ARGS__); break; \
-      case MDH_PF_PART | MDH_PF_PSMALL: hipLaunchKernelGGL(KERNEL<MDH_PF_PART | MDH_PF_PSMALL>, GRID, BLOCK, LDS, st, __VA_ARGS__); break; \
-      case 1: hipLaunchKernelGGL(KERNEL<1>, GRID, BLOCK, LDS, st, __VA_ARGS__); break;                     \
-      case 2: hipLaunchKernelGGL(KERNEL<2>, GRID, BLOCK, LDS, st, __VA_ARGS__); break;                     \
-      case 9: hipLaunchKernelGGL(KERNEL<9>, GRID, BLOCK, LDS, st, __VA_ARGS__); break;                     \
-      case MDH_PF_GTAB: case MDH_PF_GTAB | 1: case MDH_PF_GTAB | 9: launch_kernel_ptr(gtab_kernel(GK_##KERNEL, pfk), GRID, BLOCK, LDS, st, __VA_ARGS__); break; \
-      default: hipLaunchKernelGGL(KERNEL<3>, GRID, BLOCK, LDS, st, __VA_ARGS__); break;                    \
-      }                                                                                                   \
-   } while (0)
-   KProbes pr = make_probes(r);
-   pr.rad = r->d_rad2[dst];
-   pr.irr = r->d_irr2[pass == MDH_PASS_RADIANCE ? src : dst];
-   KCamera cam = make_camera(r);
-   // user-defined kinds compiled into the kernels (MDH_OPT_JIT); a scene hiprtc cannot build falls back to the
-   // interpreter for good (the reason stays in mdh_last_error, MDH_OPT_JIT reads 0 afterwards)
-   if (pass != MDH_PASS_IRRADIANCE) { // (the irradiance pass does not stage the scene table)
-      int trc = table_acquire(r, st);
-      if (trc != MDH_OK) return trc;
-   }
-   bool jit = has_custom && r->opt_jit;
-   char kname[64] = "";
-   JitModule *jm = nullptr;
-   if (jit) {
-      switch (pass) {
-      case MDH_PASS_RADIANCE: snprintf(kname, sizeof kname, "k_radiance<%d, %s>", pf | (pow2 ? MDH_PF_POW2 : 0), rad_small_launch(r) ? "true" : "false"); break;
-      case MDH_PASS_VISIBILITY: snprintf(kname, sizeof kname, "k_visibility<%d>", pf); break;
-      case MDH_PASS_SCATTERING: snprintf(kname, sizeof kname, MDH_SCAT_SPLIT ? "k_scat_march<%d>" : "k_scattering<%d>", pf); break;
-      case MDH_PASS_SCREEN: {
-         // (the predicate of launch_screen_m below: mode 2 runs the variant of the optional paths only when a mip chain really exists)
-         const bool alt = r->opt_mode == 0 && (r->opt_spec == 1 || r->opt_spec == 3 || (r->opt_spec == 2 && r->opt_mips && r->d_rad_mips[dst]));
-         snprintf(kname, sizeof kname, "k_screen<%d, %d, %s, %s>", pf | (pow2 && r->opt_mode == 0 && !alt ? MDH_PF_POW2 : 0), r->opt_mode, r->opt_gbuffer ? "true" : "false", alt ? "true" : "false");
-         break;
-      }
-      default: jit = false; break;
-      }
-      if (jit && !(jm = jit_module(r, {kname}))) { r->opt_jit = 0; jit = false; }
-   }
-   hipEvent_t e0 = nullptr, e1 = nullptr;
    if (r->opt_timing) {
-      e0 = get_event(r);
-      e1 = get_event(r);
-      if (!e0 || !e1) return seterr(MDH_E_DEVICE, "hipEventCreate failed");
-      HIP_TRY(hipEventRecord(e0, st));
+      p.e0 = get_event(r);
+      p.e1 = get_event(r);
+      if (!p.e0 || !p.e1) return seterr(MDH_E_DEVICE, "hipEventCreate failed");
+      HIP_TRY(hipEventRecord(p.e0, p.st));
    }
-   switch (pass) {
-   case MDH_PASS_RADIANCE: {
-      long n = (long)(pr.probe_end - pr.probe_begin) * pr.rres * pr.rres;
-      {
-         const int G = MDH_RAD_PROBES_PER_WAVE, T = (G == 1) ? 8 : (G == 4) ? 4 : (G == 16) ? 2 : 1;
-         if (pr.rres % T == 0) n = (long)((pr.probe_end - pr.probe_begin + G - 1) / G) * G * pr.rres * pr.rres;
-      }
-      if (n > 0) {
-         // the rays in the order of the previous pass's primary-march lengths (RadOrder, mdh_kernels.h)
-         const long rays = (long)(pr.probe_end - pr.probe_begin) * pr.rres * pr.rres;
-         RadOrder ro = {nullptr, nullptr, (int)rays, 64, nullptr};
-         // (chunks of whole workgroup strides, at most MDH_RO_MAX_CHUNKS of them)
-         const long ro_chunk = std::max(2048l, ((rays + MDH_RO_MAX_CHUNKS - 1) / MDH_RO_MAX_CHUNKS + 1023) / 1024 * 1024);
-         const int ro_chunks = (int)((rays + ro_chunk - 1) / ro_chunk);
-         if (r->opt_rad_order && rays >= 8192 && rays < (1l << 31)) {
-            if (rays > r->rad_rays_cap) {
-               // (the buffers are only ever used by radiance passes, on the probe stream or the main stream)
-               if (r->probe_stream) HIP_TRY(hipStreamSynchronize(r->probe_stream));
-               HIP_TRY(hipStreamSynchronize(r->stream));
-               r->rad_rays_cap = 0;
-               r->rad_order_rays = 0;
-               { void *q = r->d_rad_steps; r->d_rad_steps = nullptr; if (q) HIP_TRY(hipFree(q)); }
-               { void *q = r->d_rad_order; r->d_rad_order = nullptr; if (q) HIP_TRY(hipFree(q)); }
-               { void *q = r->d_rad_hist; r->d_rad_hist = nullptr; if (q) HIP_TRY(hipFree(q)); }
-               HIP_TRY(hipMalloc(&r->d_rad_steps, rays));
-               HIP_TRY(hipMalloc(&r->d_rad_order, rays * sizeof(unsigned)));
-               HIP_TRY(hipMalloc(&r->d_rad_hist, 256 * MDH_RO_MAX_CHUNKS * sizeof(unsigned)));
-               r->rad_rays_cap = rays;
-               r->rad_order_rays = 0;
-            }
-            const bool have = r->rad_order_rays == rays && r->rad_order_begin == pr.probe_begin;
-            if (have) { ro.order = r->d_rad_order; n = rays; }
-            // A probe ray's march changes with the scene's geometry, not with time, lights or materials: the rays are sorted
-            // again when primitives were set or added since (at most every MDH_RAD_RESORT_MOVING passes: a stale order costs
-            // speed only, and three more launches per frame cost the host of a 0.4 ms frame 10 %) and every MDH_RAD_RESORT
-            // passes besides -- the sort kernels (20 us) are out of almost every frame.
-            ++r->rad_order_age;
-            if (!have || r->rad_order_age >= MDH_RAD_RESORT || (r->rad_order_scene != r->geometry_edits && r->rad_order_age >= MDH_RAD_RESORT_MOVING)) ro.steps = r->d_rad_steps;
-         }
-         // RadOrder::fill: quarter or half filled wavefronts for launches that leave most slots of the chip empty.  Measured
-         // (rank 0's radiance slice of an 8-way sharded frame, 1 024 full wavefronts on 1 024 SIMDs): 0.094 ms full, 0.096 ms
-         // half filled, 0.125 ms quarter filled (profiles/r03_x_radiance_partial_fill.log) -- the rays are sorted by their
-         // march lengths already, so a wavefront's lanes end together whatever their number, and four wavefronts of 16 issue
-         // four times the instructions.  Dropped: full wavefronts unless MADARCH_HIP_RAD_FILL says otherwise.
-         {
-            static const int fill_env = [] { const char *e = getenv("MADARCH_HIP_RAD_FILL"); return e ? atoi(e) : 0; }();
-            ro.fill = fill_env == 16 || fill_env == 32 ? fill_env : 64;
-            n = (n + ro.fill - 1) / ro.fill * 64;
-         }
-         int blocks = (int)((n + MDH_BLOCK - 1) / MDH_BLOCK);
-         const size_t lds = lds_bytes_march(r);
-         if (jit) {
-            struct { KScene sc; KProbes pr; int first_round; RadOrder ro; } args = {r->ks, pr, rad_first_round(r, nullptr, jm->fn[kname], lds, blocks), ro};
-            int rc = jit_launch(jm->fn[kname], blocks, MDH_BLOCK, lds, st, args);
-            if (rc != MDH_OK) return rc;
-         } else {
-#define MDH_LAUNCH_RAD_(...) hipLaunchKernelGGL((__VA_ARGS__), dim3(blocks), dim3(MDH_BLOCK), lds, st, r->ks, pr, rad_first_round(r, (const void *)(__VA_ARGS__), nullptr, lds, blocks), ro)
-#define MDH_LAUNCH_RAD(P) do { if (rad_small_launch(r)) MDH_LAUNCH_RAD_(k_radiance<P, true>); else MDH_LAUNCH_RAD_(k_radiance<P, false>); } while (0)
-            // MADARCH_HIP_RAD_SPLIT=1 (an experiment; the brute-force power-of-two variant only): the pass as two
-            // kernels -- marches and direct light into per-ray records, then the probe code from the records
-            static const bool rad_split = [] { const char *e = getenv("MADARCH_HIP_RAD_SPLIT"); return e && atoi(e) == 1; }();
-            if (rad_split && pow2 && !has_custom && !(pf & MDH_PF_PART)) {
-               const size_t need = (size_t)blocks * MDH_BLOCK * sizeof(RadRecord);
-               if (need > r->rad_rec_bytes) {
-                  if (r->probe_stream) HIP_TRY(hipStreamSynchronize(r->probe_stream));
-                  HIP_TRY(hipStreamSynchronize(r->stream));
-                  if (r->d_rad_rec) HIP_TRY(hipFree(r->d_rad_rec));
-                  r->d_rad_rec = nullptr; r->rad_rec_bytes = 0;
-                  HIP_TRY(hipMalloc(&r->d_rad_rec, need));
-                  r->rad_rec_bytes = need;
-               }
-               ro.rec = (RadRecord *)r->d_rad_rec;
-               if (rad_small_launch(r)) {
-                  hipLaunchKernelGGL((k_radiance<MDH_PF_POW2, true, 1>), dim3(blocks), dim3(MDH_BLOCK), lds, st, r->ks, pr, 0, ro);
-                  hipLaunchKernelGGL((k_radiance<MDH_PF_POW2, true, 2>), dim3(blocks), dim3(MDH_BLOCK), lds, st, r->ks, pr, 0, ro);
-               } else {
-                  hipLaunchKernelGGL((k_radiance<MDH_PF_POW2, false, 1>), dim3(blocks), dim3(MDH_BLOCK), lds, st, r->ks, pr, rad_first_round(r, (const void *)(k_radiance<MDH_PF_POW2, false, 1>), nullptr, lds, blocks), ro);
-                  hipLaunchKernelGGL((k_radiance<MDH_PF_POW2, false, 2>), dim3(blocks), dim3(MDH_BLOCK), lds, st, r->ks, pr, rad_first_round(r, (const void *)(k_radiance<MDH_PF_POW2, false, 2>), nullptr, lds, blocks), ro);
-               }
-            } else
-            if (pow2 && !has_custom && !gtab) {
-               if (pf & MDH_PF_FALLBACK) MDH_LAUNCH_RAD(MDH_PF_PART | MDH_PF_POW2 | MDH_PF_FALLBACK);
-               else if (psmall) MDH_LAUNCH_RAD(MDH_PF_PART | MDH_PF_POW2 | MDH_PF_PSMALL);
-               else if (pf & MDH_PF_PART) MDH_LAUNCH_RAD(MDH_PF_PART | MDH_PF_POW2);
-               else if (room) MDH_LAUNCH_RAD(MDH_PF_POW2 | MDH_PF_ROOM);
-               else MDH_LAUNCH_RAD(MDH_PF_POW2);
-            } else
-               switch (pfk) {
-               case MDH_PF_ROOM: MDH_LAUNCH_RAD(MDH_PF_ROOM); break;
-               case MDH_PF_PART | MDH_PF_PSMALL: MDH_LAUNCH_RAD(MDH_PF_PART | MDH_PF_PSMALL); break;
-               case 0: MDH_LAUNCH_RAD(0); break;
-               case 1: MDH_LAUNCH_RAD(1); break;
-               case 2: MDH_LAUNCH_RAD(2); break;
-               case 9: MDH_LAUNCH_RAD(9); break;
-               case MDH_PF_GTAB: case MDH_PF_GTAB | 1: case MDH_PF_GTAB | 9: {
-                  const void *k = gtab_kernel(GK_k_radiance, pfk, rad_small_launch(r) ? 1 : 0);
-                  launch_kernel_ptr(k, dim3(blocks), dim3(MDH_BLOCK), lds, st, r->ks, pr, rad_first_round(r, k, nullptr, lds, blocks), ro);
-                  break;
-               }
-               default: MDH_LAUNCH_RAD(3); break;
-               }
-#undef MDH_LAUNCH_RAD_
-#undef MDH_LAUNCH_RAD
-         }
-         if (ro.steps) { // the next pass's order from this pass's step counts
-            hipLaunchKernelGGL(k_rad_hist, dim3(ro_chunks), dim3(256), 0, st, (const unsigned char *)r->d_rad_steps, (int)rays, (int)ro_chunk, r->d_rad_hist);
-            hipLaunchKernelGGL(k_rad_scan, dim3(1), dim3(256), 0, st, r->d_rad_hist, ro_chunks);
-            hipLaunchKernelGGL(k_rad_scatter, dim3(ro_chunks), dim3(256), 0, st, (const unsigned char *)r->d_rad_steps, (int)rays, (int)ro_chunk, (const unsigned *)r->d_rad_hist, r->d_rad_order);
-            r->rad_order_rays = rays;
-            r->rad_order_begin = pr.probe_begin;
-            r->rad_order_age = 0;
-            r->rad_order_scene = r->geometry_edits;
-         } else if (!ro.order)
-            r->rad_order_rays = 0;
-      }
-      break;
-   }
-   case MDH_PASS_IRRADIANCE: {
-      if (r->opt_world > 1 && r->opt_irr_all) { pr.probe_begin = 0; pr.probe_end = probe_total(r); } // every rank, every probe
-      int n = pr.probe_end - pr.probe_begin; // one workgroup per probe, its taps staged in LDS
-      size_t lds = (size_t)2 * pr.rres * pr.rres * sizeof(float4);
-      float *tap_planes = nullptr;
-#if MDH_FAST_NUMERICS
-      if (pr.ires * pr.ires <= 64) lds += (size_t)4 * 64 * sizeof(float4); // (the experiment's fold: all taps staged, four partial sums per texel)
-      else
-#endif
-      if (pr.ires * pr.ires <= 64 && MDH_IRR_BLOCK == 256 && n > 0) { // (k_irradiance: a channel per wavefront, the taps through device memory)
-         const size_t need = (size_t)n * 6 * MDH_IRR_CHANNELS_PLANE(pr.rres * pr.rres);
-         if (need > r->irr_taps_cap) { // (the scratch of irradiance passes only, which follow one another on their stream)
-            if (r->probe_stream) HIP_TRY(hipStreamSynchronize(r->probe_stream));
-            HIP_TRY(hipStreamSynchronize(r->stream));
-            r->irr_taps_cap = 0;
-            { void *q = r->d_irr_taps; r->d_irr_taps = nullptr; if (q) HIP_TRY(hipFree(q)); }
-            HIP_TRY(hipMalloc(&r->d_irr_taps, need * sizeof(float)));
-            r->irr_taps_cap = need;
-         }
-         tap_planes = r->d_irr_taps;
-         lds = MDH_IRR_CHANNELS_LDS;
-      } else
-      if (pr.ires * pr.ires <= 64 && lds > (size_t)4 * MDH_IRR_CHUNK * sizeof(float4)) lds = (size_t)4 * MDH_IRR_CHUNK * sizeof(float4); // two chunk buffers
-      if (lds > 64 * 1024) { // radiance tiles beyond 45 x 45 texels: up to the whole 160 KiB of a CU (70 x 70)
-         if (lds > 160 * 1024) return seterr(MDH_E_INVALID, "radiance resolution too large for the irradiance pass (160 KiB of LDS: at most 70)");
-         if (!r->irr_lds_granted) { // (the attribute belongs to the function on THIS device: kept per renderer, not per process)
-            HIP_TRY(hipFuncSetAttribute((const void *)k_irradiance, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-            r->irr_lds_granted = true;
-         }
-      }
-      // (hysteresis: the previous frame's irradiance is set `src` -- the same set when the pass runs in place)
-      if (n > 0) hipLaunchKernelGGL(k_irradiance, dim3(n), dim3(MDH_IRR_BLOCK), lds, st, pr, (const void *)r->d_irr2[src], (float)r->opt_hyst / 1000.0f, tap_planes);
-      break;
-   }
-   case MDH_PASS_VISIBILITY: {
-      KVolumetrics vol = make_vol(r, true, dst);
-      long n = (long)vol.vw * vol.vh * vol.vz;
-      if (n > 0) {
-         int blocks = (int)((n + MDH_BLOCK - 1) / MDH_BLOCK);
-         // inside a frame the launch also marches the scattering texels' camera rays (k_visibility's second part, mdh_kernels.h)
-         const int vis_blocks = blocks;
-         if (MDH_SCAT_SPLIT && r->fuse_scat_march) blocks += (int)(((long)vol.sw * vol.sh + MDH_BLOCK - 1) / MDH_BLOCK);
-         const size_t vis_lds = lds_bytes(r);
-         if (jit) {
-            struct { KScene sc; KVolumetrics vol; KCamera cam; int vis_blocks; } args = {r->ks, vol, cam, vis_blocks};
-            int rc = jit_launch(jm->fn[kname], blocks, MDH_BLOCK, vis_lds, st, args);
-            if (rc != MDH_OK) return rc;
-         } else
-            MDH_LAUNCH_PF(k_visibility, dim3(blocks), dim3(MDH_BLOCK), vis_lds, r->ks, vol, cam, vis_blocks);
-      }
-      break;
-   }
-   case MDH_PASS_SCATTERING: {
-      KVolumetrics vol = make_vol(r, true, dst);
-      long n = (long)vol.sw * vol.sh;
-      if (n > 0) {
-         int blocks = (int)((n + MDH_BLOCK - 1) / MDH_BLOCK);
-         if (jit) {
-            if (!(MDH_SCAT_SPLIT && r->fuse_scat_march)) {
-               struct { KScene sc; KVolumetrics vol; KCamera cam; } args = {r->ks, vol, cam};
-               int rc = jit_launch(jm->fn[kname], blocks, MDH_BLOCK, lds_bytes(r), st, args);
-               if (rc != MDH_OK) return rc;
-            }
-         } else
-#if MDH_SCAT_SPLIT
-            { if (!r->fuse_scat_march) MDH_LAUNCH_PF(k_scat_march, dim3(blocks), dim3(MDH_BLOCK), lds_bytes(r), r->ks, vol, cam); } // (inside a frame the visibility pass's launch has marched them)
-#else
-            MDH_LAUNCH_PF(k_scattering, dim3(blocks), dim3(MDH_BLOCK), lds_bytes(r), r->ks, vol, cam);
-#endif
-#if MDH_SCAT_SPLIT
-         // the texels' lengths are in place: their steps, spread over lanes and folded in step order (k_scat_fold, mdh_kernels.h)
-         HIP_TRY(hipGetLastError());
-         hipLaunchKernelGGL(k_scat_fold, dim3((unsigned)((n + MDH_SCAT_TEXELS - 1) / MDH_SCAT_TEXELS)), dim3(MDH_SCAT_BLOCK), 0, st, vol);
-#endif
-      }
-      break;
-   }
-   case MDH_PASS_SCREEN: {
-      KVolumetrics vol = make_vol(r, r->vol.enabled != 0 && r->opt_mode == 0, dst);
-      ScreenArgs a;
-      a.W = r->W; a.H = r->H;
-      a.tiles_x = (r->W + 7) / 8;
-      a.n_tiles = a.tiles_x * ((r->H + 7) / 8);
-      a.rank = r->opt_rank; a.world = r->opt_world;
-      a.ao_steps = r->opt_ao;
-      a.spec_mode = r->opt_spec;
-      if (r->opt_mips && r->opt_mode == 0 && r->opt_spec != 0 && r->d_rad_mips[dst]) { // MDH_OPT_RADIANCE_MIPS: the levels of the atlas this pass reads
-         int mrc = build_rad_mips(r, dst, st);
-         if (mrc != MDH_OK) return mrc;
-         pr.rad_mips = r->d_rad_mips[dst];
-      }
-      a.fb = r->d_fb2[fbix]; a.gb_index = (int *)r->d_gb2[fbix][0]; a.gb_t = (float *)r->d_gb2[fbix][1]; a.gb_steps = (int *)r->d_gb2[fbix][2];
-      a.window = nullptr;
-      if (r->opt_window == 1 || (r->opt_window == 2 && r->swaps > 0)) { // the window's pixels straight into pinned host memory (mdh_swap_buffers)
-         int wrc = window_slot(r, a.rank, a.world, &a.window);
-         if (wrc != MDH_OK) return wrc;
-      }
-      // other ranks' tiles read 0: cleared when the buffer last held another rank's (or a whole) frame, not every frame
-      if (a.world > 1 && (r->fb_owner[fbix][0] != a.rank || r->fb_owner[fbix][1] != a.world))
-         HIP_TRY(hipMemsetAsync(r->d_fb2[fbix], 0, (size_t)r->W * r->H * sizeof(float4), st));
-      r->fb_owner[fbix][0] = a.rank; r->fb_owner[fbix][1] = a.world;
-      int own_tiles = (a.n_tiles - a.rank + a.world - 1) / a.world;
-      a.n_own = own_tiles;
-      a.order = nullptr;
-      a.cost = nullptr;
-      // MDH_OPT_SCREEN_ORDER: the tiles in the order of an earlier pass's wavefront durations, slowest first
-      bool sort_after = false;
-      const int si_st = stream_index(r, st);
-      if (r->opt_scr_order && own_tiles >= 2048) {
-         if (!r->d_scr_cost) {
-            HIP_TRY(hipMalloc(&r->d_scr_cost, a.n_tiles));
-            for (int q = 0; q < 2; ++q) HIP_TRY(hipMalloc(&r->d_scr_order[q], (size_t)a.n_tiles * sizeof(unsigned)));
-            HIP_TRY(hipMalloc(&r->d_scr_hist, 256 * MDH_RO_MAX_CHUNKS * sizeof(unsigned)));
-            HIP_TRY(hipEventCreateWithFlags(&r->ev_scr_sort, hipEventDisableTiming));
-            HIP_TRY(hipEventCreateWithFlags(&r->ev_scr_other, hipEventDisableTiming));
-         }
-         float cam_now[12];
-         memcpy(cam_now, r->cam_pos, 12); memcpy(cam_now + 3, r->cam_m, 36);
-         const bool have = r->scr_order_cur >= 0 && r->scr_order_n == own_tiles && r->scr_order_rank == a.rank && r->scr_order_world == a.world;
-         if (have) {
-            a.order = r->d_scr_order[r->scr_order_cur];
-            if (r->scr_sort_seen[si_st] != r->scr_sort_version) { // the sort ran on another stream
-               HIP_TRY(hipStreamWaitEvent(st, r->ev_scr_sort, 0));
-               r->scr_sort_seen[si_st] = r->scr_sort_version;
-            }
-         }
-         // which tiles are slow follows the camera and the geometry: sorted again when either changed since (at most every
-         // MDH_RAD_RESORT_MOVING passes: a stale order costs speed only) and every MDH_RAD_RESORT passes besides
-         ++r->scr_order_age;
-         const bool moved = memcmp(cam_now, r->scr_order_cam, sizeof cam_now) != 0 || r->scr_order_geom != r->geometry_edits;
-         if (!have || r->scr_order_age >= MDH_RAD_RESORT || (moved && r->scr_order_age >= MDH_RAD_RESORT_MOVING)) {
-            sort_after = true;
-            a.cost = r->d_scr_cost;
-            memcpy(r->scr_order_cam, cam_now, sizeof cam_now);
-         }
-      } else
-         r->scr_order_cur = -1;
-      // MDH_OPT_SCREEN_SPLIT (ScreenArgs::split): launches that leave most of the chip's wavefront slots empty give a tile to
-      // two or four wavefronts; never with a tile order (launches of 2 048 tiles and more)
-      a.split = 0;
-      a.split_first = 0; // (no launch splits the slowest tiles of an order: ScreenArgs)
-      if (!a.order && !a.cost && r->opt_scr_split > 0 && a.world == 1) { // (a rank's scattered tiles of a sharded frame: measured 1 - 3 % slower split, profiles/r04_x_split_tiles.log)
-         if ((long)own_tiles * 4 <= r->opt_scr_split) a.split = 2;
-         else if ((long)own_tiles * 2 <= r->opt_scr_split) a.split = 1;
-      }
-      if (own_tiles > 0) {
-         const long waves = (long)own_tiles << a.split;
-         int blocks = (int)((waves + (MDH_BLOCK / 64) - 1) / (MDH_BLOCK / 64));
-         if (jit) {
-            struct { KScene sc; KProbes pr; KVolumetrics vol; KCamera cam; ScreenArgs a; } args = {r->ks, pr, vol, cam, a};
-            int rc = jit_launch(jm->fn[kname], blocks, MDH_BLOCK, lds_bytes_screen(r), st, args);
-            if (rc != MDH_OK) return rc;
-         } else
-         switch (pfk) {
-         case MDH_PF_ROOM: launch_screen_m<MDH_PF_ROOM>(r, st, pr, vol, cam, a, blocks, pow2); break;
-         case MDH_PF_PART | MDH_PF_PSMALL: launch_screen_m<MDH_PF_PART | MDH_PF_PSMALL>(r, st, pr, vol, cam, a, blocks, pow2); break;
-         case 0: launch_screen_m<0>(r, st, pr, vol, cam, a, blocks, pow2); break;
-         case 1: launch_screen_m<1>(r, st, pr, vol, cam, a, blocks, pow2); break;
-         case 2: launch_screen_m<2>(r, st, pr, vol, cam, a, blocks, pow2); break;
-         case 9: launch_screen_m<9>(r, st, pr, vol, cam, a, blocks, pow2); break;
-         case MDH_PF_GTAB: case MDH_PF_GTAB | 1: case MDH_PF_GTAB | 9: { // (launch_screen_m's choice among the general variants)
-            const bool alt = r->opt_mode == 0 && (a.spec_mode == 1 || a.spec_mode == 3 || (a.spec_mode == 2 && pr.rad_mips));
-            launch_kernel_ptr(gtab_kernel(GK_k_screen, pfk, r->opt_mode, r->opt_gbuffer ? 1 : 0, alt ? 1 : 0), dim3(blocks), dim3(MDH_BLOCK), lds_bytes_screen(r), st, r->ks, pr, vol, cam, a);
-            break;
-         }
-         default: launch_screen_m<3>(r, st, pr, vol, cam, a, blocks, pow2); break;
-         }
-      }
-      if (sort_after) { // later passes' order from this pass's durations, into the buffer no pass in flight reads
-         HIP_TRY(hipGetLastError());
-         if (r->opt_timing && e1) { // (the sort is no part of the pass's time: ADVICE r03)
-            HIP_TRY(hipEventRecord(e1, st));
-            r->pending.push_back({pass, e0, e1});
-            e0 = e1 = nullptr;
-         }
-         const int nb = r->scr_order_cur == 0 ? 1 : 0;
-         // (passes that read that buffer were launched before the previous sort; on the other screen stream nothing
-         //  orders them against this stream when no probe passes run: wait for what that stream holds)
-         hipStream_t other = st == r->alt_stream ? r->stream : r->alt_stream;
-         if (other && other != st && r->scr_order_cur >= 0) {
-            HIP_TRY(hipEventRecord(r->ev_scr_other, other));
-            HIP_TRY(hipStreamWaitEvent(st, r->ev_scr_other, 0));
-         }
-         const long chunk = std::max(2048l, (((long)own_tiles + MDH_RO_MAX_CHUNKS - 1) / MDH_RO_MAX_CHUNKS + 1023) / 1024 * 1024);
-         const int chunks = (int)((own_tiles + chunk - 1) / chunk);
-         // Sorted as a whole every screen pass measured is faster on its own (BASELINE config 3: +4.5 %, config 2: +59 %,
-         // config 5's frame on one GPU: +7 %) and, with frames in flight, every frame but one kind: where the probe passes
-         // are a large share of the frame (config 3 at 1080p: 524 288 probe rays for 2 M pixels), a screen pass that
-         // holds every wavefront slot to its very end keeps the NEXT frame's probe passes -- the head of that frame's
-         // dependency chain -- waiting for slots that the thin tail of an image-order pass hands over early: -3 %.
-         // There only the tiles that took twice the median and more go to the front (the ones that make the tail) and
-         // all others keep their place: +-0 in flight (profiles/r03_x_screen_tile_order.log).
-         const long probe_rays = r->opt_mode == 0 ? (long)(pr.probe_end - pr.probe_begin) * pr.rres * pr.rres : 0;
-         const bool probe_heavy = probe_rays * 10 >= (long)own_tiles * 64;
-         const int floor_permille = r->frame_pipelined && r->in_frame_passes && probe_heavy ? 2000 : 0; // (thousandths of the median)
-         hipLaunchKernelGGL(k_rad_hist, dim3(chunks), dim3(256), 0, st, (const unsigned char *)r->d_scr_cost, own_tiles, (int)chunk, r->d_scr_hist);
-         if (floor_permille > 0) {
-            hipLaunchKernelGGL(k_order_floor, dim3(chunks), dim3(256), 0, st, r->d_scr_cost, own_tiles, (int)chunk, (const unsigned *)r->d_scr_hist, chunks, floor_permille);
-            hipLaunchKernelGGL(k_rad_hist, dim3(chunks), dim3(256), 0, st, (const unsigned char *)r->d_scr_cost, own_tiles, (int)chunk, r->d_scr_hist);
-         }
-         hipLaunchKernelGGL(k_rad_scan, dim3(1), dim3(256), 0, st, r->d_scr_hist, chunks);
-         hipLaunchKernelGGL(k_order_scatter_stable, dim3(chunks), dim3(256), 0, st, (const unsigned char *)r->d_scr_cost, own_tiles, (int)chunk, (const unsigned *)r->d_scr_hist, r->d_scr_order[nb]);
-         HIP_TRY(hipGetLastError());
-         HIP_TRY(hipEventRecord(r->ev_scr_sort, st));
-         ++r->scr_sort_version;
-         r->scr_sort_seen[si_st] = r->scr_sort_version;
-         r->scr_order_cur = nb;
-         r->scr_order_n = own_tiles; r->scr_order_rank = a.rank; r->scr_order_world = a.world;
-         r->scr_order_age = 0;
-         r->scr_order_geom = r->geometry_edits;
-      }
-      break;
-   }
-   default: return seterr(MDH_E_INVALID, "bad pass");
-   }
+   return MDH_OK;
+}
+static int pass_end(PassRun &p)
+{
+   mdh_renderer *r = p.r;
    HIP_TRY(hipGetLastError());
-   if (pass != MDH_PASS_IRRADIANCE) {
-      int trc = table_release(r, st);
+   if (p.pass != MDH_PASS_IRRADIANCE) {
+      int trc = table_release(r, p.st);
       if (trc != MDH_OK) return trc;
    }
-   if (r->opt_timing && e1) {
-      HIP_TRY(hipEventRecord(e1, st));
-      r->pending.push_back({pass, e0, e1}); // (folded at frame boundaries: bound_timing)
+   if (r->opt_timing && p.e1) {
+      HIP_TRY(hipEventRecord(p.e1, p.st));
+      r->pending.push_back({p.pass, p.e0, p.e1}); // (folded at frame boundaries: bound_timing)
    }
 #ifdef MDH_DIAG
    { // the diagnostic build waits for every pass and takes its work counters
-      HIP_TRY(hipStreamSynchronize(st));
-      HIP_TRY(hipMemcpyFromSymbol(r->work[pass], HIP_SYMBOL(g_work), sizeof r->work[pass]));
+      HIP_TRY(hipStreamSynchronize(p.st));
+      HIP_TRY(hipMemcpyFromSymbol(r->work[p.pass], HIP_SYMBOL(g_work), sizeof r->work[p.pass]));
       unsigned long long z[4] = {0, 0, 0, 0};
       HIP_TRY(hipMemcpyToSymbol(HIP_SYMBOL(g_work), z, sizeof z));
    }
 #endif
    return MDH_OK;
+}
+
+static int pass_radiance(PassRun &p)
+{
+   mdh_renderer *r = p.r;
+   const KProbes &pr = p.pr;
+   hipStream_t st = p.st;
+   const long rays = (long)(pr.probe_end - pr.probe_begin) * pr.rres * pr.rres;
+   long n = rays;
+   {
+      const int G = MDH_RAD_PROBES_PER_WAVE, T = (G == 1) ? 8 : (G == 4) ? 4 : (G == 16) ? 2 : 1;
+      if (pr.rres % T == 0) n = (long)((pr.probe_end - pr.probe_begin + G - 1) / G) * G * pr.rres * pr.rres;
+   }
+   if (n <= 0) return MDH_OK;
+   // the rays in the order of the previous pass's primary-march lengths (RadOrder, mdh_kernels.h)
+   RadOrder ro = {nullptr, nullptr, (int)rays};
+   // (chunks of whole workgroup strides, at most MDH_RO_MAX_CHUNKS of them)
+   const long ro_chunk = std::max(2048l, ((rays + MDH_RO_MAX_CHUNKS - 1) / MDH_RO_MAX_CHUNKS + 1023) / 1024 * 1024);
+   const int ro_chunks = (int)((rays + ro_chunk - 1) / ro_chunk);
+   if (r->opt_rad_order && rays >= 8192 && rays < (1l << 31)) {
+      if (rays > r->rad_rays_cap) {
+         // (the buffers are only ever used by radiance passes, on the probe stream or the main stream)
+         if (r->probe_stream) HIP_TRY(hipStreamSynchronize(r->probe_stream));
+         HIP_TRY(hipStreamSynchronize(r->stream));
+         r->rad_rays_cap = 0;
+         r->rad_order_rays = 0;
+         { void *q = r->d_rad_steps; r->d_rad_steps = nullptr; if (q) HIP_TRY(hipFree(q)); }
+         { void *q = r->d_rad_order; r->d_rad_order = nullptr; if (q) HIP_TRY(hipFree(q)); }
+         { void *q = r->d_rad_hist; r->d_rad_hist = nullptr; if (q) HIP_TRY(hipFree(q)); }
+         HIP_TRY(hipMalloc(&r->d_rad_steps, rays));
+         HIP_TRY(hipMalloc(&r->d_rad_order, rays * sizeof(unsigned)));
+         HIP_TRY(hipMalloc(&r->d_rad_hist, 256 * MDH_RO_MAX_CHUNKS * sizeof(unsigned)));
+         r->rad_rays_cap = rays;
+         r->rad_order_rays = 0;
+      }
+      const bool have = r->rad_order_rays == rays && r->rad_order_begin == pr.probe_begin;
+      if (have) { ro.order = r->d_rad_order; n = rays; }
+      // A probe ray's march changes with the scene's geometry, not with time, lights or materials: the rays are sorted
+      // again when primitives were set or added since (at most every MDH_RAD_RESORT_MOVING passes: a stale order costs
+      // speed only, and three more launches per frame cost the host of a 0.4 ms frame 10 %) and every MDH_RAD_RESORT
+      // passes besides -- the sort kernels (20 us) are out of almost every frame.
+      ++r->rad_order_age;
+      if (!have || r->rad_order_age >= MDH_RAD_RESORT || (r->rad_order_scene != r->geometry_edits && r->rad_order_age >= MDH_RAD_RESORT_MOVING)) ro.steps = r->d_rad_steps;
+   }
+   n = (n + 63) / 64 * 64;
+   const int blocks = (int)((n + MDH_BLOCK - 1) / MDH_BLOCK);
+   const size_t lds = lds_bytes_march(r);
+   struct Args { KScene sc; KProbes pr; int first_round; RadOrder ro; };
+   const int rc = launch_pass<Args>(p, blocks, lds, r->ks, pr, rad_first_round(r, p.kernel, p.fn, lds, blocks), ro);
+   if (rc != MDH_OK) return rc;
+   if (ro.steps) { // the next pass's order from this pass's step counts
+      hipLaunchKernelGGL(k_rad_hist, dim3(ro_chunks), dim3(256), 0, st, (const unsigned char *)r->d_rad_steps, (int)rays, (int)ro_chunk, r->d_rad_hist);
+      hipLaunchKernelGGL(k_rad_scan, dim3(1), dim3(256), 0, st, r->d_rad_hist, ro_chunks);
+      hipLaunchKernelGGL(k_rad_scatter, dim3(ro_chunks), dim3(256), 0, st, (const unsigned char *)r->d_rad_steps, (int)rays, (int)ro_chunk, (const unsigned *)r->d_rad_hist, r->d_rad_order);
+      r->rad_order_rays = rays;
+      r->rad_order_begin = pr.probe_begin;
+      r->rad_order_age = 0;
+      r->rad_order_scene = r->geometry_edits;
+   } else if (!ro.order)
+      r->rad_order_rays = 0;
+   return MDH_OK;
+}
+
+static int pass_irradiance(PassRun &p)
+{
+   mdh_renderer *r = p.r;
+   KProbes &pr = p.pr;
+   if (r->opt_world > 1 && r->opt_irr_all) { pr.probe_begin = 0; pr.probe_end = probe_total(r); } // every rank, every probe
+   int n = pr.probe_end - pr.probe_begin; // one workgroup per probe, its taps staged in LDS
+   size_t lds = (size_t)2 * pr.rres * pr.rres * sizeof(float4);
+   float *tap_planes = nullptr;
+#if MDH_FAST_NUMERICS
+   if (pr.ires * pr.ires <= 64) lds += (size_t)4 * 64 * sizeof(float4); // (the experiment's fold: all taps staged, four partial sums per texel)
+   else
+#endif
+   if (pr.ires * pr.ires <= 64 && MDH_IRR_BLOCK == 256 && n > 0) { // (k_irradiance: a channel per wavefront, the taps through device memory)
+      const size_t need = (size_t)n * 6 * MDH_IRR_CHANNELS_PLANE(pr.rres * pr.rres);
+      if (need > r->irr_taps_cap) { // (the scratch of irradiance passes only, which follow one another on their stream)
+         if (r->probe_stream) HIP_TRY(hipStreamSynchronize(r->probe_stream));
+         HIP_TRY(hipStreamSynchronize(r->stream));
+         r->irr_taps_cap = 0;
+         { void *q = r->d_irr_taps; r->d_irr_taps = nullptr; if (q) HIP_TRY(hipFree(q)); }
+         HIP_TRY(hipMalloc(&r->d_irr_taps, need * sizeof(float)));
+         r->irr_taps_cap = need;
+      }
+      tap_planes = r->d_irr_taps;
+      lds = MDH_IRR_CHANNELS_LDS;
+   } else
+   if (pr.ires * pr.ires <= 64 && lds > (size_t)4 * MDH_IRR_CHUNK * sizeof(float4)) lds = (size_t)4 * MDH_IRR_CHUNK * sizeof(float4); // two chunk buffers
+   if (lds > 64 * 1024) { // radiance tiles beyond 45 x 45 texels: up to the whole 160 KiB of a CU (70 x 70)
+      if (lds > 160 * 1024) return seterr(MDH_E_INVALID, "radiance resolution too large for the irradiance pass (160 KiB of LDS: at most 70)");
+      if (!r->irr_lds_granted) { // (the attribute belongs to the function on THIS device: kept per renderer, not per process)
+         HIP_TRY(hipFuncSetAttribute((const void *)k_irradiance, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+         r->irr_lds_granted = true;
+      }
+   }
+   // (hysteresis: the previous frame's irradiance is set `src` -- the same set when the pass runs in place)
+   if (n > 0) hipLaunchKernelGGL(k_irradiance, dim3(n), dim3(MDH_IRR_BLOCK), lds, p.st, pr, (const void *)r->d_irr2[p.src], (float)r->opt_hyst / 1000.0f, tap_planes);
+   return MDH_OK;
+}
+
+static int pass_visibility(PassRun &p)
+{
+   mdh_renderer *r = p.r;
+   KVolumetrics vol = make_vol(r, true, p.dst);
+   const long n = (long)vol.vw * vol.vh * vol.vz;
+   if (n <= 0) return MDH_OK;
+   // inside a frame the launch also marches the scattering texels' camera rays (k_visibility's second part, mdh_kernels.h)
+   const int vis_blocks = (int)((n + MDH_BLOCK - 1) / MDH_BLOCK);
+   int blocks = vis_blocks;
+   if (MDH_SCAT_SPLIT && r->fuse_scat_march) blocks += (int)(((long)vol.sw * vol.sh + MDH_BLOCK - 1) / MDH_BLOCK);
+   struct Args { KScene sc; KVolumetrics vol; KCamera cam; int vis_blocks; };
+   return launch_pass<Args>(p, blocks, lds_bytes(r), r->ks, vol, p.cam, vis_blocks);
+}
+
+static int pass_scattering(PassRun &p)
+{
+   mdh_renderer *r = p.r;
+   KVolumetrics vol = make_vol(r, true, p.dst);
+   const long n = (long)vol.sw * vol.sh;
+   if (n <= 0) return MDH_OK;
+   const int blocks = (int)((n + MDH_BLOCK - 1) / MDH_BLOCK);
+   struct Args { KScene sc; KVolumetrics vol; KCamera cam; };
+   if (!(MDH_SCAT_SPLIT && r->fuse_scat_march)) { // (inside a frame the visibility pass's launch has marched them)
+      const int rc = launch_pass<Args>(p, blocks, lds_bytes(r), r->ks, vol, p.cam);
+      if (rc != MDH_OK) return rc;
+   }
+#if MDH_SCAT_SPLIT
+   // the texels' lengths are in place: their steps, spread over lanes and folded in step order (k_scat_fold, mdh_kernels.h)
+   HIP_TRY(hipGetLastError());
+   hipLaunchKernelGGL(k_scat_fold, dim3((unsigned)((n + MDH_SCAT_TEXELS - 1) / MDH_SCAT_TEXELS)), dim3(MDH_SCAT_BLOCK), 0, p.st, vol);
+#endif
+   return MDH_OK;
+}
+
+// later screen passes' tile order from this pass's durations (ScreenArgs::cost), into the buffer no pass in flight reads
+static int screen_sort_tiles(PassRun &p, const ScreenArgs &a)
+{
+   mdh_renderer *r = p.r;
+   hipStream_t st = p.st;
+   const KProbes &pr = p.pr;
+   const int own_tiles = a.n_own, si_st = stream_index(r, st);
+   HIP_TRY(hipGetLastError());
+   if (r->opt_timing && p.e1) { // (the sort is no part of the pass's time: ADVICE r03)
+      HIP_TRY(hipEventRecord(p.e1, st));
+      r->pending.push_back({p.pass, p.e0, p.e1});
+      p.e0 = p.e1 = nullptr;
+   }
+   const int nb = r->scr_order_cur == 0 ? 1 : 0;
+   // (passes that read that buffer were launched before the previous sort; on the other screen stream nothing
+   //  orders them against this stream when no probe passes run: wait for what that stream holds)
+   hipStream_t other = st == r->alt_stream ? r->stream : r->alt_stream;
+   if (other && other != st && r->scr_order_cur >= 0) {
+      HIP_TRY(hipEventRecord(r->ev_scr_other, other));
+      HIP_TRY(hipStreamWaitEvent(st, r->ev_scr_other, 0));
+   }
+   const long chunk = std::max(2048l, (((long)own_tiles + MDH_RO_MAX_CHUNKS - 1) / MDH_RO_MAX_CHUNKS + 1023) / 1024 * 1024);
+   const int chunks = (int)((own_tiles + chunk - 1) / chunk);
+   // Sorted as a whole every screen pass measured is faster on its own (BASELINE config 3: +4.5 %, config 2: +59 %,
+   // config 5's frame on one GPU: +7 %) and, with frames in flight, every frame but one kind: where the probe passes
+   // are a large share of the frame (config 3 at 1080p: 524 288 probe rays for 2 M pixels), a screen pass that
+   // holds every wavefront slot to its very end keeps the NEXT frame's probe passes -- the head of that frame's
+   // dependency chain -- waiting for slots that the thin tail of an image-order pass hands over early: -3 %.
+   // There only the tiles that took twice the median and more go to the front (the ones that make the tail) and
+   // all others keep their place: +-0 in flight (profiles/r03_x_screen_tile_order.log).
+   const long probe_rays = r->opt_mode == 0 ? (long)(pr.probe_end - pr.probe_begin) * pr.rres * pr.rres : 0;
+   const bool probe_heavy = probe_rays * 10 >= (long)own_tiles * 64;
+   const int floor_permille = r->frame_pipelined && r->in_frame_passes && probe_heavy ? 2000 : 0; // (thousandths of the median)
+   hipLaunchKernelGGL(k_rad_hist, dim3(chunks), dim3(256), 0, st, (const unsigned char *)r->d_scr_cost, own_tiles, (int)chunk, r->d_scr_hist);
+   if (floor_permille > 0) {
+      hipLaunchKernelGGL(k_order_floor, dim3(chunks), dim3(256), 0, st, r->d_scr_cost, own_tiles, (int)chunk, (const unsigned *)r->d_scr_hist, chunks, floor_permille);
+      hipLaunchKernelGGL(k_rad_hist, dim3(chunks), dim3(256), 0, st, (const unsigned char *)r->d_scr_cost, own_tiles, (int)chunk, r->d_scr_hist);
+   }
+   hipLaunchKernelGGL(k_rad_scan, dim3(1), dim3(256), 0, st, r->d_scr_hist, chunks);
+   hipLaunchKernelGGL(k_order_scatter_stable, dim3(chunks), dim3(256), 0, st, (const unsigned char *)r->d_scr_cost, own_tiles, (int)chunk, (const unsigned *)r->d_scr_hist, r->d_scr_order[nb]);
+   HIP_TRY(hipGetLastError());
+   HIP_TRY(hipEventRecord(r->ev_scr_sort, st));
+   ++r->scr_sort_version;
+   r->scr_sort_seen[si_st] = r->scr_sort_version;
+   r->scr_order_cur = nb;
+   r->scr_order_n = own_tiles; r->scr_order_rank = a.rank; r->scr_order_world = a.world;
+   r->scr_order_age = 0;
+   r->scr_order_geom = r->geometry_edits;
+   return MDH_OK;
+}
+
+static int pass_screen(PassRun &p)
+{
+   mdh_renderer *r = p.r;
+   hipStream_t st = p.st;
+   KProbes &pr = p.pr;
+   const int fbix = p.fbix;
+   KVolumetrics vol = make_vol(r, r->vol.enabled != 0 && r->opt_mode == 0, p.dst);
+   ScreenArgs a;
+   a.W = r->W; a.H = r->H;
+   a.tiles_x = (r->W + 7) / 8;
+   a.n_tiles = a.tiles_x * ((r->H + 7) / 8);
+   a.rank = r->opt_rank; a.world = r->opt_world;
+   a.ao_steps = r->opt_ao;
+   a.spec_mode = r->opt_spec;
+   if (rad_mips_used(r, p.dst)) { // MDH_OPT_RADIANCE_MIPS: the levels of the atlas this pass reads
+      int mrc = build_rad_mips(r, p.dst, st);
+      if (mrc != MDH_OK) return mrc;
+      pr.rad_mips = r->d_rad_mips[p.dst];
+   }
+   a.fb = r->d_fb2[fbix]; a.gb_index = (int *)r->d_gb2[fbix][0]; a.gb_t = (float *)r->d_gb2[fbix][1]; a.gb_steps = (int *)r->d_gb2[fbix][2];
+   a.window = nullptr;
+   if (r->opt_window == 1 || (r->opt_window == 2 && r->swaps > 0)) { // the window's pixels straight into pinned host memory (mdh_swap_buffers)
+      int wrc = window_slot(r, a.rank, a.world, &a.window);
+      if (wrc != MDH_OK) return wrc;
+   }
+   // other ranks' tiles read 0: cleared when the buffer last held another rank's (or a whole) frame, not every frame
+   if (a.world > 1 && (r->fb_owner[fbix][0] != a.rank || r->fb_owner[fbix][1] != a.world))
+      HIP_TRY(hipMemsetAsync(r->d_fb2[fbix], 0, (size_t)r->W * r->H * sizeof(float4), st));
+   r->fb_owner[fbix][0] = a.rank; r->fb_owner[fbix][1] = a.world;
+   const int own_tiles = (a.n_tiles - a.rank + a.world - 1) / a.world;
+   a.n_own = own_tiles;
+   a.order = nullptr;
+   a.cost = nullptr;
+   // MDH_OPT_SCREEN_ORDER: the tiles in the order of an earlier pass's wavefront durations, slowest first
+   bool sort_after = false;
+   if (r->opt_scr_order && own_tiles >= 2048) {
+      const int si_st = stream_index(r, st);
+      if (!r->d_scr_cost) {
+         HIP_TRY(hipMalloc(&r->d_scr_cost, a.n_tiles));
+         for (int q = 0; q < 2; ++q) HIP_TRY(hipMalloc(&r->d_scr_order[q], (size_t)a.n_tiles * sizeof(unsigned)));
+         HIP_TRY(hipMalloc(&r->d_scr_hist, 256 * MDH_RO_MAX_CHUNKS * sizeof(unsigned)));
+         HIP_TRY(hipEventCreateWithFlags(&r->ev_scr_sort, hipEventDisableTiming));
+         HIP_TRY(hipEventCreateWithFlags(&r->ev_scr_other, hipEventDisableTiming));
+      }
+      float cam_now[12];
+      memcpy(cam_now, r->cam_pos, 12); memcpy(cam_now + 3, r->cam_m, 36);
+      const bool have = r->scr_order_cur >= 0 && r->scr_order_n == own_tiles && r->scr_order_rank == a.rank && r->scr_order_world == a.world;
+      if (have) {
+         a.order = r->d_scr_order[r->scr_order_cur];
+         if (r->scr_sort_seen[si_st] != r->scr_sort_version) { // the sort ran on another stream
+            HIP_TRY(hipStreamWaitEvent(st, r->ev_scr_sort, 0));
+            r->scr_sort_seen[si_st] = r->scr_sort_version;
+         }
+      }
+      // which tiles are slow follows the camera and the geometry: sorted again when either changed since (at most every
+      // MDH_RAD_RESORT_MOVING passes: a stale order costs speed only) and every MDH_RAD_RESORT passes besides
+      ++r->scr_order_age;
+      const bool moved = memcmp(cam_now, r->scr_order_cam, sizeof cam_now) != 0 || r->scr_order_geom != r->geometry_edits;
+      if (!have || r->scr_order_age >= MDH_RAD_RESORT || (moved && r->scr_order_age >= MDH_RAD_RESORT_MOVING)) {
+         sort_after = true;
+         a.cost = r->d_scr_cost;
+         memcpy(r->scr_order_cam, cam_now, sizeof cam_now);
+      }
+   } else
+      r->scr_order_cur = -1;
+   // MDH_OPT_SCREEN_SPLIT (ScreenArgs::split): launches that leave most of the chip's wavefront slots empty give a tile to
+   // two or four wavefronts; never with a tile order (launches of 2 048 tiles and more)
+   a.split = 0;
+   if (!a.order && !a.cost && r->opt_scr_split > 0 && a.world == 1) { // (a rank's scattered tiles of a sharded frame: measured 1 - 3 % slower split, profiles/r04_x_split_tiles.log)
+      if ((long)own_tiles * 4 <= r->opt_scr_split) a.split = 2;
+      else if ((long)own_tiles * 2 <= r->opt_scr_split) a.split = 1;
+   }
+   if (own_tiles > 0) {
+      const long waves = (long)own_tiles << a.split;
+      const int blocks = (int)((waves + (MDH_BLOCK / 64) - 1) / (MDH_BLOCK / 64));
+      struct Args { KScene sc; KProbes pr; KVolumetrics vol; KCamera cam; ScreenArgs a; };
+      const int rc = launch_pass<Args>(p, blocks, lds_bytes_screen(r), r->ks, pr, vol, p.cam, a);
+      if (rc != MDH_OK) return rc;
+   }
+   return sort_after ? screen_sort_tiles(p, a) : MDH_OK;
+}
+
+static int run_pass(mdh_renderer *r, int pass, hipStream_t st, int src, int dst, int fbix = -1)
+{
+   if (pass < MDH_PASS_RADIANCE || pass > MDH_PASS_SCREEN) return seterr(MDH_E_INVALID, "bad pass");
+   PassRun p = {r, pass, st, src, dst, fbix};
+   int rc = pass_begin(p);
+   if (rc != MDH_OK) return rc;
+   switch (pass) {
+   case MDH_PASS_RADIANCE: rc = pass_radiance(p); break;
+   case MDH_PASS_IRRADIANCE: rc = pass_irradiance(p); break;
+   case MDH_PASS_VISIBILITY: rc = pass_visibility(p); break;
+   case MDH_PASS_SCATTERING: rc = pass_scattering(p); break;
+   default: rc = pass_screen(p); break;
+   }
+   return rc != MDH_OK ? rc : pass_end(p);
 }
 
 extern "C" int32_t mdh_render_pass(mdh_renderer *r, int32_t pass)
@@ -3132,9 +3126,7 @@ extern "C" int32_t mdh_eval_distance_to(mdh_renderer *r, int32_t n, const float 
    for (int i = 0; i < MDH_MAX_KINDS; ++i) { a.kinds[i] = i < n_kinds ? kind_ixs[i] : 0; a.host_count[i] = r->host_count[i]; }
    a.pts = d_pts; a.normals = d_n; a.dist = d_d;
    if ((rc = table_acquire(r, qs)) != MDH_OK) return rc;
-   if (r->residency) launch_kernel_ptr(gtab_kernel(GK_k_eval_distance, MDH_PF_GTAB, r->opt_ada_div), dim3((n + 63) / 64), dim3(64), lds_bytes(r), qs, ks_no_bits(r), a);
-   else if (r->opt_ada_div) hipLaunchKernelGGL(k_eval_distance<true>, dim3((n + 63) / 64), dim3(64), lds_bytes(r), qs, ks_no_bits(r), a);
-   else hipLaunchKernelGGL(k_eval_distance<false>, dim3((n + 63) / 64), dim3(64), lds_bytes(r), qs, ks_no_bits(r), a);
+   if ((rc = launch_kernel_ptr(table_kernel(r, GK_k_eval_distance), dim3((n + 63) / 64), dim3(64), lds_bytes(r), qs, r->ks, a)) != MDH_OK) return rc;
    HIP_TRY(hipGetLastError());
    if ((rc = table_release(r, qs)) != MDH_OK) return rc;
    HIP_TRY(hipMemcpyAsync(dist_out, d_d, (size_t)n * 4, hipMemcpyDeviceToHost, qs));
@@ -3220,7 +3212,7 @@ extern "C" int32_t mdh_diag_work(mdh_renderer *r, int32_t pass, unsigned long lo
    memcpy(out4, r->work[pass], sizeof r->work[pass]);
    return MDH_OK;
 }
-// the kernel variant run_pass chose at the last run of `pass`: out[0] = pfk (MDH_PF_*: ROOM, PART | PSMALL, or the general
+// the kernel variant pick_kernel chose at the last run of `pass`: out[0] = pfk (MDH_PF_*: ROOM, PART | PSMALL, or the general
 // variant's PART / CUSTOM / FALLBACK bits), out[1] = 1 when the atlas addressing took the power-of-two variant
 extern "C" int32_t mdh_diag_variant(mdh_renderer *r, int32_t pass, int32_t *out2)
 {
@@ -3247,16 +3239,13 @@ template <int PART> __global__ __launch_bounds__(64) void k_diag_segments(KScene
    a.clear[q] = segment_clear_bound<PART>(sc, A, vd, vmax) ? 1 : 0;
    a.vis[q] = vmax <= 4096.0f ? raycast_visibility<PART>(sc, A, vd, vmax) : -1.0f;
 }
-// variant 0: the scan run_pass picks for the committed scene (MDH_PF_ROOM or the general scan 0); 1: the general scan forced.
+// variant 0: the scan pick_kernel picks for the committed scene (MDH_PF_ROOM or the general scan 0); 1: the general scan forced.
 // thr_lim_out: H_VCLEAR and H_VCLEAR_LIM as commit_scene wrote them.  Scenes with a partition or user-defined kinds: MDH_E_STATE.
 extern "C" int32_t mdh_diag_segments(mdh_renderer *r, int32_t variant, int32_t n, const float *A, const float *vd, const float *vmax,
                                      int32_t *clear_out, float *vis_out, float *thr_lim_out)
 {
    if (!r || n < 0 || (n > 0 && (!A || !vd || !vmax || !clear_out || !vis_out)) || (variant != 0 && variant != 1)) return seterr(MDH_E_INVALID, "bad argument");
-   bool has_custom = false;
-   for (int k = 0; k < r->npk; ++k) has_custom = has_custom || r->pk[k].type == PK_CUSTOM;
-   for (int k = 0; k < r->nlk; ++k) has_custom = has_custom || r->lk[k].type == LK_CUSTOM;
-   if (r->part.enable != 0 || has_custom) return seterr(MDH_E_STATE, "mdh_diag_segments: the scan variants only (no partition, no user-defined kinds)");
+   if (r->part.enable != 0 || has_custom_kinds(r)) return seterr(MDH_E_STATE, "mdh_diag_segments: the scan variants only (no partition, no user-defined kinds)");
    HIP_TRY(hipSetDevice(r->device));
    if (!r->query_stream) HIP_TRY(hipStreamCreateWithFlags(&r->query_stream, hipStreamNonBlocking));
    hipStream_t qs = r->query_stream;
@@ -3280,10 +3269,12 @@ extern "C" int32_t mdh_diag_segments(mdh_renderer *r, int32_t variant, int32_t n
    if (e == hipSuccess) e = hipMemcpyAsync(d + 3 * (size_t)n, vd, (size_t)n * 12, hipMemcpyHostToDevice, qs);
    if (e == hipSuccess) e = hipMemcpyAsync(d + 6 * (size_t)n, vmax, (size_t)n * 4, hipMemcpyHostToDevice, qs);
    if (e == hipSuccess && (rc = table_acquire(r, qs)) == MDH_OK) {
-      if (room) hipLaunchKernelGGL(k_diag_segments<MDH_PF_ROOM>, dim3((n + 63) / 64), dim3(64), lds_bytes(r), qs, ks_no_bits(r), a);
-      else hipLaunchKernelGGL(k_diag_segments<0>, dim3((n + 63) / 64), dim3(64), lds_bytes(r), qs, ks_no_bits(r), a);
+      PassKernel k;
+      k.family = GK_k_diag_segments;
+      k.pf = room ? MDH_PF_ROOM : 0;
+      rc = launch_kernel_ptr(kernel_ptr(k), dim3((n + 63) / 64), dim3(64), lds_bytes(r), qs, r->ks, a);
       e = hipGetLastError();
-      if (e == hipSuccess) rc = table_release(r, qs);
+      if (e == hipSuccess && rc == MDH_OK) rc = table_release(r, qs);
    }
    if (e == hipSuccess && rc == MDH_OK) e = hipMemcpyAsync(clear_out, a.clear, (size_t)n * 4, hipMemcpyDeviceToHost, qs);
    if (e == hipSuccess && rc == MDH_OK) e = hipMemcpyAsync(vis_out, a.vis, (size_t)n * 4, hipMemcpyDeviceToHost, qs);
@@ -3322,33 +3313,45 @@ extern "C" int32_t mdh_diag_waves(unsigned long long *out, int32_t n_waves)
 }
 #endif
 
-// ------------------------------------------------------------------ the kernels of global residency
-// (the last function of the file: see the declaration of gtab_kernel)
-template <int PF> static const void *gtab_kernel_pf(int family, int x, int y, int z)
+// ------------------------------------------------------------------ the kernels of this library
+// (the last function of the file: see the declaration of kernel_ptr).  Exactly the instantiations that are built, in the
+// order the code object holds them; a description that names none of them is an error of the caller, never another kernel.
+// (k_screen<16, 2>, <6, 0> and <7, 0> are built and never picked: the census of the rooms has no mode-2 variant of its own and
+//  scenes with user-defined kinds get the power-of-two addressing from hiprtc only -- pick_kernel)
+static const void *kernel_ptr(const PassKernel &k)
 {
-   switch (family) {
-   case GK_k_visibility: return (const void *)k_visibility<PF>;
+#define MDH_K(FAMILY, PF, ...) if (k.family == GK_##FAMILY && k.pf == (PF)) return (const void *)(__VA_ARGS__);
+#define MDH_RAD(PF) MDH_K(k_radiance, PF, k.small ? k_radiance<PF, true> : k_radiance<PF, false>)
+#define MDH_VIS(PF) MDH_K(k_visibility, PF, k_visibility<PF>)
 #if MDH_SCAT_SPLIT
-   case GK_k_scat_march: return (const void *)k_scat_march<PF>;
+#define MDH_SCAT(PF) MDH_K(k_scat_march, PF, k_scat_march<PF>)
 #else
-   case GK_k_scattering: return (const void *)k_scattering<PF>;
+#define MDH_SCAT(PF) MDH_K(k_scattering, PF, k_scattering<PF>)
 #endif
-   case GK_k_radiance: return x ? (const void *)k_radiance<PF, true> : (const void *)k_radiance<PF, false>;
-   case GK_k_screen: // x = screen mode, y = geometry buffer, z = the variant of the optional specular bodies (mode 0)
-      if (x == 0 && z) return y ? (const void *)k_screen<PF, 0, true, true> : (const void *)k_screen<PF, 0, false, true>;
-      if (x == 0) return y ? (const void *)k_screen<PF, 0, true> : (const void *)k_screen<PF, 0, false>;
-      if (x == 1) return y ? (const void *)k_screen<PF, 1, true> : (const void *)k_screen<PF, 1, false>;
-      return y ? (const void *)k_screen<PF, 2, true> : (const void *)k_screen<PF, 2, false>;
-   case GK_k_partition_build: return (const void *)k_partition_build_gtab<>;
-   case GK_k_eval_distance: return x ? (const void *)k_eval_distance_gtab<true> : (const void *)k_eval_distance_gtab<false>;
-   default: return nullptr;
-   }
-}
-static const void *gtab_kernel(int family, int pfk, int x, int y, int z)
-{
-   switch (pfk) {
-   case MDH_PF_GTAB | 1: return gtab_kernel_pf<MDH_PF_GTAB | 1>(family, x, y, z);
-   case MDH_PF_GTAB | 9: return gtab_kernel_pf<MDH_PF_GTAB | 9>(family, x, y, z);
-   default: return gtab_kernel_pf<MDH_PF_GTAB>(family, x, y, z);
-   }
+#define MDH_SCR(PF, MODE, ALT) if (k.family == GK_k_screen && k.pf == (PF) && k.mode == MODE && k.alt == ALT) return k.gbuf ? (const void *)k_screen<PF, MODE, true, ALT> : (const void *)k_screen<PF, MODE, false, ALT>;
+#define MDH_GTAB(PF) MDH_VIS(PF) MDH_SCAT(PF) MDH_RAD(PF) MDH_SCR(PF, 0, true) MDH_SCR(PF, 0, false) MDH_SCR(PF, 1, false) MDH_SCR(PF, 2, false)
+   MDH_RAD(13) MDH_RAD(37) MDH_RAD(5) MDH_RAD(20) MDH_RAD(4) MDH_RAD(16) MDH_RAD(33) MDH_RAD(0) MDH_RAD(1) MDH_RAD(2) MDH_RAD(9) MDH_RAD(3)
+   MDH_VIS(0) MDH_VIS(16) MDH_VIS(33) MDH_VIS(1) MDH_VIS(2) MDH_VIS(9) MDH_VIS(3)
+   MDH_SCAT(0) MDH_SCAT(16) MDH_SCAT(33) MDH_SCAT(1) MDH_SCAT(2) MDH_SCAT(9) MDH_SCAT(3)
+   MDH_SCR(20, 0, false) MDH_SCR(16, 0, false) MDH_SCR(16, 2, false) MDH_SCR(0, 0, true) MDH_SCR(4, 0, false) MDH_SCR(0, 0, false) MDH_SCR(0, 1, false) MDH_SCR(0, 2, false)
+   MDH_SCR(37, 0, false) MDH_SCR(33, 0, false) MDH_SCR(33, 2, false) MDH_SCR(1, 0, true) MDH_SCR(5, 0, false) MDH_SCR(1, 0, false) MDH_SCR(1, 1, false) MDH_SCR(1, 2, false)
+   MDH_SCR(6, 0, false) MDH_SCR(2, 0, false) MDH_SCR(2, 2, false) MDH_SCR(2, 0, true) MDH_SCR(2, 1, false)
+   MDH_SCR(13, 0, false) MDH_SCR(9, 0, false) MDH_SCR(9, 2, false) MDH_SCR(9, 0, true) MDH_SCR(9, 1, false)
+   MDH_SCR(7, 0, false) MDH_SCR(3, 0, false) MDH_SCR(3, 2, false) MDH_SCR(3, 0, true) MDH_SCR(3, 1, false)
+   MDH_K(k_partition_build, 0, k_partition_build)
+   MDH_K(k_eval_distance, 0, k.ada_div ? k_eval_distance<true> : k_eval_distance<false>)
+#ifdef MDH_DIAG
+   MDH_K(k_diag_segments, MDH_PF_ROOM, k_diag_segments<MDH_PF_ROOM>) MDH_K(k_diag_segments, 0, k_diag_segments<0>)
+#endif
+   MDH_GTAB(65)
+   MDH_K(k_partition_build, MDH_PF_GTAB, k_partition_build_gtab<>)
+   MDH_K(k_eval_distance, MDH_PF_GTAB, k.ada_div ? k_eval_distance_gtab<true> : k_eval_distance_gtab<false>)
+   MDH_GTAB(73) MDH_GTAB(64)
+   return nullptr;
+#undef MDH_K
+#undef MDH_RAD
+#undef MDH_VIS
+#undef MDH_SCAT
+#undef MDH_SCR
+#undef MDH_GTAB
 }

@@ -63,7 +63,13 @@ struct KScene {
    const float4 *table;   // HBM image of the table (staged to LDS by every workgroup)
    const int *part_table; // [cell][nk + index_count], then the same lists as bits: [cell][part_mask_words] at int part_mask_off
    int part_mask_off, part_mask_words; // (partitioning_closest_bits below)
-   int part_bits_f4; // float4 count of the bits when every workgroup stages them into LDS behind the scene table (0: read from memory)
+   // float4 count of the bits when every workgroup stages them into LDS behind the scene table.  The host always passes 0: the
+   // bits are read from memory (measured, mdh_api.hip: part_bits_ints).  The field, the staging loop of stage_table and the
+   // select in partitioning_closest_bits stay because the compiler allocates registers differently without them (without the
+   // select k_screen<MDH_PF_PART | MDH_PF_FALLBACK, 0, true, true> spills 176 instead of 160 bytes per lane; without the loop
+   // k_screen<MDH_PF_GTAB | MDH_PF_PART | MDH_PF_FALLBACK, 2, false> 64 instead of 48, and k_visibility<MDH_PF_PART |
+   // MDH_PF_FALLBACK> takes 68 instead of 67 VGPRs) -- the same kind of dependence as the one-turn loop in k_visibility
+   int part_bits_f4;
    // Small scenes (no user-defined kinds, at most 64 declared primitives, at most 32 of a kind -- every scene of the
    // reference's examples): a cell's bits are ONE 8-byte load and every built-in TYPE's candidates one shift and mask of
    // it -- part_tbit = the first bit of the type's kind, part_tmask = its declared count as a mask (0: no such kind) --
@@ -71,9 +77,6 @@ struct KScene {
    int part_small;
    unsigned part_tbit[4], part_tmask[4];
    float part_fdims[3], part_fyz; // (float)part_dims[a] and (float)(part_dims[1] * part_dims[2]): the same conversions, once on the host
-   // no kernel reads these and the host leaves them zero (they were the scalar operands of a removed form of the brute-force
-   // scan); they stay so that the kernels' argument block keeps its layout
-   float first_sphere[4], first_box[8];
 };
 // int block at table[0..]: per-kind data in SCENE order (the order the flat primitive index
 // and the arg-min tie-break follow, scenes.adb:656-666) and the light kinds
@@ -455,7 +458,7 @@ extern __shared__ float4 s_tab[];
 MDH_DEV void stage_table(const KScene &sc)
 {
    for (int i = threadIdx.x; i < sc.table_f4; i += blockDim.x) s_tab[i] = sc.table[i];
-   if (sc.part_bits_f4 > 0) { // the space partition's candidate bits of every cell (partitioning_closest_bits), when they are small enough
+   if (sc.part_bits_f4 > 0) { // (never: KScene::part_bits_f4 says why this stays)
       const float4 *bits = (const float4 *)(sc.part_table + sc.part_mask_off);
       for (int i = threadIdx.x; i < sc.part_bits_f4; i += blockDim.x) s_tab[sc.table_f4 + i] = bits[i];
    }
@@ -1104,7 +1107,7 @@ template <bool CUSTOM, bool FALLBACK, bool PSMALL = false, bool GTAB = false> MD
    if (PSMALL) return closest; // (never reached: the variant is only launched for scenes of the small form)
    typedef const unsigned __attribute__((address_space(1))) *GlobalWords;
    const int nk = hdr(H_NK), nw = sc.part_mask_words;
-   const bool in_lds = sc.part_bits_f4 > 0; // (wave-uniform: the whole grid's bits are staged behind the scene table)
+   const bool in_lds = sc.part_bits_f4 > 0; // (wave-uniform, and never true: KScene::part_bits_f4 says why the select stays)
    GlobalWords gwords = (GlobalWords)(sc.part_table + sc.part_mask_off) + (size_t)cell * nw;
    const unsigned *lwords = (const unsigned *)(s_tab + sc.table_f4) + cell * nw;
    auto word = [&](int dw) -> unsigned { return in_lds ? lwords[dw] : gwords[dw]; };
@@ -1395,7 +1398,7 @@ MDH_DEV i3 world_to_grid(const KProbes &pr, f3 p)
    g.x = (int)f.x; g.y = (int)f.y; g.z = (int)f.z;
    return g;
 }
-// (P2: the kernel variants for power-of-two atlases run on fewer than 65 536 probes -- run_pass -- where the products fit
+// (P2: the kernel variants for power-of-two atlases run on fewer than 65 536 probes -- pick_kernel, mdh_api.hip -- where the products fit
 // the 24-bit multiplier, which issues at the full rate)
 template <bool P2 = false> MDH_DEV int grid_to_probe_id(const KProbes &pr, i3 g)
 {
@@ -1493,7 +1496,7 @@ template <bool P2> MDH_DEV unsigned atlas_row(int pcx, int res, int shift, int Y
 }
 // Atlas reads are GLOBAL loads: through the generic pointer of the argument block they are flat loads, which count as
 // LDS operations too -- every wait for an LDS read (each step of a march) then also waits for the texels in flight.
-// P2: the byte offset of an RGBA8 texel fits 32 bits (run_pass starts these variants on atlases below 4 GiB only), the
+// P2: the byte offset of an RGBA8 texel fits 32 bits (pick_kernel starts these variants on atlases below 4 GiB only), the
 // load takes the base from scalar registers and needs no 64-bit address arithmetic.
 typedef const unsigned __attribute__((address_space(1))) *GlobalU32;
 typedef const char __attribute__((address_space(1))) *GlobalBytes;

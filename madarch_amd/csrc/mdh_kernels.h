@@ -107,19 +107,13 @@ struct ScreenArgs {
    // gives a tile to two wavefronts of 8x4 pixels or four of 4x4 (32 / 16 lanes each, the others idle from the start) -- every
    // wavefront marches only as long as ITS pixels need and the tile's work runs on several SIMDs.  A pixel's operations do not
    // depend on which lanes march beside it: the same bits (tests/test_gpu_parity.py::test_split_tiles_change_no_pixel).
+   // (measured: splitting only the slowest tiles at the head of an ORDERED launch, four wavefronts of 4x4 pixels each, gained nothing)
    int split;
-   // ... and in an ORDERED launch (slowest tiles first) the first `split_first` places -- the tiles whose wavefronts make the
-   // pass's tail, a sum of marches each as long as the longest among 64 pixels -- are drawn by four wavefronts of 4x4 pixels
-   // each (places 0 .. 4 split_first - 1), the others by one.  (The host passes 0: the split of an order's head measured no gain.)
-   int split_first;
 };
-// place of a launch -> its index into the launch's tiles, the part of the tile, the split factor (ScreenArgs::split, split_first)
+// place of a launch -> its index into the launch's tiles, the part of the tile, the split factor (ScreenArgs::split)
 MDH_DEV void screen_place(const ScreenArgs &a, int place, int &idx, int &sub, int &split)
 {
-   if (a.split_first > 0) { // (wave-uniform)
-      if (place < 4 * a.split_first) { idx = place >> 2; sub = place & 3; split = 2; }
-      else { idx = place - 3 * a.split_first; sub = 0; split = 0; }
-   } else { idx = place >> a.split; sub = place & ((1 << a.split) - 1); split = a.split; }
+   idx = place >> a.split; sub = place & ((1 << a.split) - 1); split = a.split;
 }
 #ifndef MDH_SCREEN_SPLIT_DEFAULT
 #define MDH_SCREEN_SPLIT_DEFAULT 2560 // MDH_OPT_SCREEN_SPLIT's initial value
@@ -272,12 +266,10 @@ struct RadOrder {
    const unsigned *order; // [n_rays] ray at every place, or nullptr: rays in probe order
    unsigned char *steps;  // [n_rays] every ray's sort key (rad_level of its primary-march and shadow steps), written by the pass; or nullptr
    int n_rays;
-   // Lanes of every wavefront that carry a ray: 64, or 32 / 16 for launches that would leave most wavefront slots of
-   // the chip empty (a rank's slice of a sharded frame: 1 024 full wavefronts on 1 024 SIMDs, each alone on its SIMD and
-   // paying every latency of its dependency chain in full).  Spread over four times as many wavefronts the same rays
-   // hide each other's latencies, and a wavefront's marches end with the longest of 16 rays instead of 64.
-   int fill;
-   RadRecord *rec; // [launch lanes] MADARCH_HIP_RAD_SPLIT: what the first kernel leaves for the second (null: one kernel)
+   // Every wavefront is full, also in launches that leave most wavefront slots of the chip empty.  (measured, rank 0's radiance
+   // slice of an 8-way sharded frame, 1 024 full wavefronts on 1 024 SIMDs: 0.094 ms full, 0.096 ms half filled, 0.125 ms quarter
+   // filled, profiles/r03_x_radiance_partial_fill.log -- the rays are sorted by their march lengths already, so a wavefront's
+   // lanes end together whatever their number, and four wavefronts of 16 issue four times the instructions)
 };
 // `first_round`: the workgroups the chip holds at once (0: not told).  The pass is ONE round of wavefronts and a
 // remainder -- 8 192 wavefronts on 7 168 slots at the headline size -- and ends with its slowest wavefront.  A SIMD
@@ -290,11 +282,6 @@ struct RadOrder {
 MDH_DEV void radiance_texel(const KProbes &pr, const RadOrder &ro, long lin, int &x, int &y, int &probe_raw)
 {
    const int per_probe = pr.rres * pr.rres;
-   if (ro.fill < 64) { // the launch's lanes that carry rays, renumbered: wavefront w holds rays w * fill .. w * fill + fill - 1
-      const int l = (int)(lin & 63);
-      if (l >= ro.fill) { x = y = 0; probe_raw = pr.probe_end; return; }
-      lin = (lin >> 6) * ro.fill + l;
-   }
    // a wavefront = a TxT texel tile (T*T = 64 / G) of the octahedral maps of G consecutive probes:
    // G = 1 is one 8x8 tile of one probe, G = 64 the same ray direction from 64 probes
    constexpr int G = MDH_RAD_PROBES_PER_WAVE, T = (G == 1) ? 8 : (G == 4) ? 4 : (G == 16) ? 2 : 1;
@@ -327,13 +314,10 @@ MDH_DEV void radiance_texel(const KProbes &pr, const RadOrder &ro, long lin, int
       x = rem - y * pr.rres;
    }
 }
-// PHASE 1 / 2: the pass as two kernels (an experiment, MADARCH_HIP_RAD_SPLIT): 1 = every ray's primary and
-// shadow marches, its hit point and direct light into ro.rec[launch lane] (no probe code: eight wavefronts per SIMD); 2 = the
-// probe visibility queue, the irradiance taps and the store, from the records.  The same arithmetic per ray: the same texels.
-#ifndef MDH_RAD_A_WAVES_PER_SIMD
-#define MDH_RAD_A_WAVES_PER_SIMD 8
-#endif
-template <int PART, bool SMALL = false, int PHASE = 0> __global__ __launch_bounds__(MDH_BLOCK, PHASE == 1 ? MDH_RAD_A_WAVES_PER_SIMD : MDH_OCC_RAD(PART, SMALL)) void k_radiance(KScene sc, KProbes pr, int first_round, RadOrder ro)
+// The pass is ONE kernel.  (measured: as two -- every ray's marches, hit point and direct light into per-ray records at eight
+// wavefronts per SIMD, then the probe visibility queue, the irradiance taps and the store from the records -- 0.180 instead of
+// 0.125 ms)
+template <int PART, bool SMALL = false> __global__ __launch_bounds__(MDH_BLOCK, MDH_OCC_RAD(PART, SMALL)) void k_radiance(KScene sc, KProbes pr, int first_round, RadOrder ro)
 {
    if (first_round > 0 && (int)blockIdx.x >= first_round) __builtin_amdgcn_s_setprio(3);
    stage_table(sc);
@@ -360,7 +344,7 @@ template <int PART, bool SMALL = false, int PHASE = 0> __global__ __launch_bound
       cfg.ao_steps = 0;
       bool hit;
       f3 pos;
-      c = MDH_SHADE<PART, 0, 0, MDH_RAD_QVIS != 0, PHASE>(sc, pr, cfg, valid, world, ray_dir, ph, hit, pos, PHASE ? ro.rec + lin : nullptr);
+      c = MDH_SHADE<PART, 0, 0, MDH_RAD_QVIS != 0>(sc, pr, cfg, valid, world, ray_dir, ph, hit, pos);
    }
    // The texel again: nothing of the prologue stays live across the pixel program (its coordinates, the order's entry and
    // the arguments the store needs were eleven dwords that the seven-wavefront build kept in scratch memory).  The lane
@@ -392,8 +376,8 @@ template <int PART, bool SMALL = false, int PHASE = 0> __global__ __launch_bound
       if (probe_raw < pr2.probe_end) {
          const int ty = probe_raw / pr2.pcx, tx = probe_raw - ty * pr2.pcx;
          const int i = tx * pr2.rres + x, j = ty * pr2.rres + y;
-         if (PHASE != 1) atlas_store(pr2.rad, pr2.fmt, atlas_index(pr2.pcx, pr2.rres, pr2.rshift, i, j), c);
-         if (ro2.steps && PHASE != 2) // the ray's sort key: the levels of its primary-march and soft-shadow step counts
+         atlas_store(pr2.rad, pr2.fmt, atlas_index(pr2.pcx, pr2.rres, pr2.rshift, i, j), c);
+         if (ro2.steps) // the ray's sort key: the levels of its primary-march and soft-shadow step counts
             ro2.steps[(size_t)(probe_raw - pr2.probe_begin) * (pr2.rres * pr2.rres) + y * pr2.rres + x] = (unsigned char)((rad_level(ph.steps & 0xffff) << 4) | rad_level(ph.steps >> 16));
       }
    }
@@ -996,7 +980,7 @@ template <int PART> MDH_DEV float scattering_length(const KScene &sc, const KVol
 // `vis_blocks`: the workgroups of the launch that work on froxels; the ones behind them march the camera rays of the
 // SCATTERING texels (k_scat_march's work: the texels' lengths, which depend on the camera and the scene only).  That march is
 // a thousand wavefronts whose longest ray alone takes 40 us: inside this launch it hides under the froxels' rays (frames
-// only: a single visibility pass leaves the scattering texture alone, run_pass).
+// only: a single visibility pass leaves the scattering texture alone, pass_scattering).
 template <int PART> __global__ __launch_bounds__(MDH_BLOCK) void k_visibility(KScene sc, KVolumetrics vol, KCamera cam, int vis_blocks)
 {
    stage_table(sc);
@@ -1316,7 +1300,7 @@ template <bool GTAB> MDH_DEV void partition_build(const KScene &sc, const PartBu
    }
 }
 __global__ __launch_bounds__(64) void k_partition_build(KScene sc, PartBuildArgs a) { partition_build<false>(sc, a); }
-template <int = 0> __global__ __launch_bounds__(64) void k_partition_build_gtab(KScene sc, PartBuildArgs a) { partition_build<true>(sc, a); } // global residency of the scene table (a template: built where it is first named, mdh_api.hip: gtab_kernel)
+template <int = 0> __global__ __launch_bounds__(64) void k_partition_build_gtab(KScene sc, PartBuildArgs a) { partition_build<true>(sc, a); } // global residency of the scene table (a template: built where it is first named, mdh_api.hip: kernel_ptr)
 
 // The candidate lists of every cell once more as one bit per declared primitive (partitioning_closest_bits,
 // mdh_device.h), derived from the lists exactly as the lookup walks them: kind by kind, a kind's entries up to its
