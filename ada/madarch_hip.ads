@@ -128,6 +128,14 @@ package Madarch_HIP is
    function Finish (R : Handle) return Status
      with Import, Convention => C, External_Name => "mdh_finish";
 
+   --  MDH_OPT_* switches of madarch_hip.h.  Opt_Triangle_BVH: 1 = the triangles are walked through
+   --  a bounding-volume hierarchy (the same bits; scenes with Partitioning => (Enable => False)
+   --  and without user-defined kinds, Status 7 otherwise), 0 (default) = scanned one by one.
+   Opt_Triangle_BVH : constant int := 20;
+
+   function Set_Option (R : Handle; Option, Value : int) return Status
+     with Import, Convention => C, External_Name => "mdh_set_option";
+
    function Read_Framebuffer (R : Handle; RGB_Out : System.Address) return Status
      with Import, Convention => C, External_Name => "mdh_read_framebuffer";
 

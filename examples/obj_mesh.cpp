@@ -2,12 +2,15 @@
 // mirror: 1000 triangles behind a 30x20x20 partition of 0.1 cells built with GPU_Fast, one point light, the default
 // probes.  There is no mesh loader: a torus of 25 x 20 quads (exactly 1000 triangles) stands for media/suzanne.obj.
 // The scene's table does not fit a workgroup's LDS: the library reads its geometry from device memory
-// (MDH_OPT_TABLE_RESIDENCY reads 1).  Usage: obj_mesh W H FRAMES [out.f32 [out.ppm]]
+// (MDH_OPT_TABLE_RESIDENCY reads 1).  Usage: obj_mesh [--bvh] W H FRAMES [out.f32 [out.ppm]]
+// --bvh: the same mesh without the partition (Partitioning => (Enable => False)) and MDH_OPT_TRIANGLE_BVH on -- the exact
+// scan over all 1000 triangles, walked through the library's bounding-volume hierarchy.
 #include "madarch.hpp"
 
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
+#include <string>
 
 using namespace Madarch;
 
@@ -20,10 +23,17 @@ static Vector3 Torus_Vertex(int i, int j, int nu, int nv, double R, double r)
 
 int main(int argc, char **argv)
 {
+   bool Triangle_BVH = false;
+   for (int i = 1; i < argc; ++i)
+      if (std::string(argv[i]) == "--bvh") { // (anywhere among the arguments; the others keep their order)
+         Triangle_BVH = true;
+         for (int j = i; j + 1 < argc; ++j) argv[j] = argv[j + 1];
+         --argc; --i;
+      }
    const int W = argc > 1 ? atoi(argv[1]) : 1000, H = argc > 2 ? atoi(argv[2]) : 1000, frames = argc > 3 ? atoi(argv[3]) : 1;
    try {
       Scenes::Partitioning_Settings Partitioning_Settings;
-      Partitioning_Settings.Enable = true;
+      Partitioning_Settings.Enable = !Triangle_BVH;
       Partitioning_Settings.Index_Count = 150;
       Partitioning_Settings.Border_Behavior = Scenes::Clamp;
       Partitioning_Settings.Grid_Dimensions = {30, 20, 20};
@@ -31,6 +41,7 @@ int main(int argc, char **argv)
       Partitioning_Settings.Grid_Offset = {0.0f, 0.0f, 0.0f};
       Scenes::Scene Scene = Scenes::Compile({{Primitives::Triangles::Triangle, 1000}}, {{Lights::Point_Lights::Point_Light, 4}}, Partitioning_Settings);
       Renderers::Renderer Renderer = Renderers::Create(Windows::Open(W, H, "Obj_Mesh"), Scene, {}, Renderers::No_Volumetrics);
+      if (Triangle_BVH) Renderer.Set_Option(Renderers::Renderer::Opt_Triangle_BVH, 1);
       Entities::Entity Point_Light_Instance = Lights::Point_Lights::Create({0.0f, 1.0f, -5.0f}, {0.9f, 0.9f, 0.9f});
       Materials::Id Mesh_Mat = Renderer.Add_Material(Materials::Create({0.8f, 0.2f, 0.1f}, 0.0f, 1.0f));
 
@@ -47,7 +58,7 @@ int main(int argc, char **argv)
             Add_Triangle(a, b, c);
             Add_Triangle(a, c, d);
          }
-      Renderer.Update_Partitioning(Renderers::GPU_Fast);
+      if (!Triangle_BVH) Renderer.Update_Partitioning(Renderers::GPU_Fast);
       Renderer.Set_Light(1, Lights::Point_Lights::Point_Light, Point_Light_Instance);
       Renderer.Set_Camera_Position({0.0f, 1.0f, -5.0f});
 

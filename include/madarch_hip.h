@@ -272,7 +272,15 @@ enum {
     * option gives the residency of the scene as committed (pending edits are committed first).  Setting 1 FORCES residency 1
     * for a scene that would fit (tests and A/B runs; MDH_E_INVALID at the next commit for scenes with user-defined kinds,
     * which always live in LDS); setting 0 returns to the choice by size. */
-   MDH_OPT_TABLE_RESIDENCY = 19
+   MDH_OPT_TABLE_RESIDENCY = 19,
+   /* 1 = the triangles of the scene are walked through a bounding-volume hierarchy instead of being scanned one by one
+    * (default 0) -- no effect on any result: a subtree is skipped only where no triangle in it can lower the running
+    * minimum, so every pass keeps the bits of the scan ("A BVH over the triangles").  The library
+    * builds the hierarchy when the scene is committed and rebuilds it when a Triangle instance or their count changed;
+    * the scene then runs in global residency (MDH_OPT_TABLE_RESIDENCY reads 1).  For scenes without a space partition,
+    * without user-defined kinds and with at most one Triangle kind: MDH_E_STATE otherwise; other values MDH_E_INVALID.
+    * A scene that declares no triangles accepts it and nothing changes. */
+   MDH_OPT_TRIANGLE_BVH = 20
 };
 
 /* passes of Renderers.Render (madarch-renderers.adb:302-321) */
@@ -493,6 +501,21 @@ int32_t mdh_read_partitioning(mdh_renderer *r, int32_t *out, int32_t n_ints);
  * (the reference prints "Warning : partition size too small", renderers.adb:593-598);
  * waits for that build */
 int32_t mdh_partition_warnings(mdh_renderer *r);
+
+/* MDH_OPT_TRIANGLE_BVH.  The builder by itself -- no renderer, no device: a top-down build (median of the centroids
+ * along the longest axis, leaves of at most four triangles) over n_tris triangles of 9 floats (v1, v2, v3).
+ *   nodes_out  the nodes in depth-first order as the kernels read them, 32 bytes each: float lo[3], int32 skip, float
+ *              hi[3], int32 leaf -- skip = the node that follows this subtree (the root's is the node count), leaf = -1
+ *              for an inner node (its first child is the next node), first * 8 + count for a leaf's range of perm_out.
+ *              Room for max (1, 2 n_tris) nodes.
+ *   perm_out   n_tris instance indices: the walked triangles in leaf order, then the always-evaluated list -- the
+ *              triangles no geometric bound is trusted for (non-finite or huge vertices, tiny edges, slivers).
+ *   delta_out  [0] = delta, [1] = rho: a subtree is skipped when its box is farther than closest (1 + rho) + delta.
+ * Returns the length of the always-evaluated list (>= 0), or -MDH_E_INVALID.  The same input gives the same bytes. */
+int32_t mdh_bvh_build(const float *tri_xyz, int32_t n_tris, void *nodes_out, int32_t *n_nodes, int32_t *perm_out, float *delta_out);
+/* ... and the hierarchy of the renderer's committed scene (pending edits are committed first): node count, leaf count,
+ * depth, length of the always-evaluated list; all 0 while the option is off or no Triangle kind is declared. */
+int32_t mdh_triangle_bvh_info(mdh_renderer *r, int32_t *nodes, int32_t *leaves, int32_t *depth, int32_t *always);
 
 const char *mdh_last_error(void);
 const char *mdh_version(void);

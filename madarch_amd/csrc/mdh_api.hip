@@ -164,6 +164,110 @@ static float image_roundtrip(float x)
    return strtof(buf, nullptr);
 }
 
+// ------------------------------------------------------ the triangle BVH (MDH_OPT_TRIANGLE_BVH)
+// Host side of bvh_triangles (mdh_device.h, where the layout and the margin argument are): a top-down build over the
+// triangles of the committed scene, median of the centroids along the longest axis of their bounds, leaves of at most four
+// triangles, nodes in depth-first order with skip links.  Deterministic: ties of the sort go to the lower index.
+// Plain C++, no device: mdh_bvh_build hands it to tests.
+struct BvhImage {
+   std::vector<float4> nodes;  // two per node: {lo.xyz, skip} {hi.xyz, leaf}
+   std::vector<int32_t> perm;  // the walked triangles in leaf order, then the always-evaluated ones in index order
+   int n_always = 0, leaves = 0, depth = 0;
+   float delta = 0.0f;
+};
+// Does the margin argument cover this triangle (9 floats)?  Finite, every coordinate within 2^20, no edge below 2^-12, and
+// |nor| >= 2^-6 L^2 with L its longest edge; evaluated in double on the float vertices.
+static bool bvh_covers(const float *v)
+{
+   for (int i = 0; i < 9; ++i)
+      if (!(std::fabs(v[i]) <= 0x1p20f)) return false; // (NaN fails too)
+   double e[3][3], l2[3];
+   for (int a = 0; a < 3; ++a) { e[0][a] = (double)v[3 + a] - v[a]; e[1][a] = (double)v[6 + a] - v[3 + a]; e[2][a] = (double)v[a] - v[6 + a]; }
+   for (int k = 0; k < 3; ++k) l2[k] = e[k][0] * e[k][0] + e[k][1] * e[k][1] + e[k][2] * e[k][2];
+   const double lmax2 = std::max(l2[0], std::max(l2[1], l2[2])), lmin2 = std::min(l2[0], std::min(l2[1], l2[2]));
+   if (!(lmin2 >= 0x1p-24)) return false;
+   const double n[3] = {e[0][1] * e[2][2] - e[0][2] * e[2][1], e[0][2] * e[2][0] - e[0][0] * e[2][2], e[0][0] * e[2][1] - e[0][1] * e[2][0]};
+   const double n2 = n[0] * n[0] + n[1] * n[1] + n[2] * n[2];
+   return n2 >= 0x1p-12 * lmax2 * lmax2;
+}
+struct BvhBuilder {
+   const float *tri;
+   BvhImage &out;
+   std::vector<int32_t> ids;
+   std::vector<float> cen; // 3 per triangle
+   int node(int lo, int hi, int depth)
+   {
+      const int at = (int)out.nodes.size() / 2;
+      out.nodes.resize(out.nodes.size() + 2);
+      out.depth = std::max(out.depth, depth);
+      float bl[3] = {INFINITY, INFINITY, INFINITY}, bh[3] = {-INFINITY, -INFINITY, -INFINITY}, cl[3] = {INFINITY, INFINITY, INFINITY}, ch[3] = {-INFINITY, -INFINITY, -INFINITY};
+      for (int q = lo; q < hi; ++q) {
+         const float *v = tri + 9 * (size_t)ids[q];
+         for (int c = 0; c < 9; ++c) { bl[c % 3] = std::min(bl[c % 3], v[c]); bh[c % 3] = std::max(bh[c % 3], v[c]); }
+         for (int a = 0; a < 3; ++a) { cl[a] = std::min(cl[a], cen[3 * (size_t)ids[q] + a]); ch[a] = std::max(ch[a], cen[3 * (size_t)ids[q] + a]); }
+      }
+      int32_t leaf = -1;
+      if (hi - lo <= 4) {
+         leaf = (int32_t)out.perm.size() * 8 + (hi - lo);
+         for (int q = lo; q < hi; ++q) out.perm.push_back(ids[q]);
+         ++out.leaves;
+      } else {
+         int axis = 0;
+         for (int a = 1; a < 3; ++a) if (ch[a] - cl[a] > ch[axis] - cl[axis]) axis = a;
+         std::sort(ids.begin() + lo, ids.begin() + hi, [&](int32_t x, int32_t y) {
+            const float cx = cen[3 * (size_t)x + axis], cy = cen[3 * (size_t)y + axis];
+            return cx < cy || (cx == cy && x < y);
+         });
+         const int mid = lo + (hi - lo) / 2;
+         node(lo, mid, depth + 1);
+         node(mid, hi, depth + 1);
+      }
+      const int32_t skip = (int32_t)out.nodes.size() / 2;
+      float fs, fl;
+      memcpy(&fs, &skip, 4); memcpy(&fl, &leaf, 4);
+      float4 a, b;
+      a.x = bl[0]; a.y = bl[1]; a.z = bl[2]; a.w = fs;
+      b.x = bh[0]; b.y = bh[1]; b.z = bh[2]; b.w = fl;
+      out.nodes[2 * (size_t)at] = a; out.nodes[2 * (size_t)at + 1] = b;
+      return at;
+   }
+};
+static void bvh_build(const float *tri, int n, BvhImage &out)
+{
+   out = BvhImage();
+   BvhBuilder b{tri, out, {}, {}};
+   std::vector<int32_t> always;
+   float lim = 0.0f;
+   b.cen.resize(3 * (size_t)n);
+   for (int i = 0; i < n; ++i) {
+      const float *v = tri + 9 * (size_t)i;
+      if (!bvh_covers(v)) { always.push_back(i); continue; }
+      b.ids.push_back(i);
+      for (int c = 0; c < 9; ++c) lim = std::max(lim, std::fabs(v[c]));
+      for (int a = 0; a < 3; ++a) b.cen[3 * (size_t)i + a] = (float)(((double)v[a] + v[3 + a] + v[6 + a]) / 3.0);
+   }
+   out.perm.reserve(n);
+   if (!b.ids.empty()) b.node(0, (int)b.ids.size(), 1);
+   out.perm.insert(out.perm.end(), always.begin(), always.end());
+   out.n_always = (int)always.size();
+   out.delta = std::ldexp(1.0f + lim, -10);
+}
+// The builder by itself, without a renderer or a device: `tri_xyz` = n_tris x 9 floats (v1, v2, v3).  nodes_out takes the
+// nodes as the kernels read them, 32 bytes each (room for max (1, 2 n_tris) of them), perm_out n_tris ints -- the walked
+// triangles in leaf order, then the always-evaluated list --, delta_out[0] the margin delta and delta_out[1] rho.
+// Returns the length of the always-evaluated list, or -MDH_E_INVALID.
+extern "C" int32_t mdh_bvh_build(const float *tri_xyz, int32_t n_tris, void *nodes_out, int32_t *n_nodes, int32_t *perm_out, float *delta_out)
+{
+   if (n_tris < 0 || (n_tris > 0 && (!tri_xyz || !perm_out)) || !nodes_out || !n_nodes || !delta_out) { seterr(MDH_E_INVALID, "bad argument"); return -MDH_E_INVALID; }
+   BvhImage im;
+   bvh_build(tri_xyz, n_tris, im);
+   if (!im.nodes.empty()) memcpy(nodes_out, im.nodes.data(), im.nodes.size() * sizeof(float4));
+   if (n_tris > 0) memcpy(perm_out, im.perm.data(), (size_t)n_tris * 4);
+   *n_nodes = (int32_t)im.nodes.size() / 2;
+   delta_out[0] = im.delta; delta_out[1] = MDH_BVH_RHO;
+   return im.n_always;
+}
+
 // -------------------------------------------------------------------- the renderer
 #define MAX_MATERIALS 20 // glsl/materials.glsl:9
 #ifndef MDH_ATLAS_SETS
@@ -277,6 +381,11 @@ struct mdh_renderer {
    int opt_irr_all = 1; // MDH_OPT_IRRADIANCE_ALL
    int opt_residency = 0; // MDH_OPT_TABLE_RESIDENCY as set: 1 = global residency forced, 0 = chosen by the table's size (commit_scene)
    int residency = 0;     // ... of the committed scene: 0 = the whole table in LDS, 1 = geometry and material ids read from its image in memory
+   int opt_tri_bvh = 0;   // MDH_OPT_TRIANGLE_BVH as set
+   bool bvh_active = false; // ... and of the committed scene: the option is on and a Triangle kind is declared (global residency, the MDH_PF_BVH kernels)
+   BvhImage bvh;            // the hierarchy over bvh_tris, the triangles it was built from (commit_scene rebuilds it when they change)
+   std::vector<float> bvh_tris;
+   bool bvh_built = false;
    int opt_jit = 1; // user-defined kinds: 1 = compile the MDH_X programs with hiprtc, 0 = interpret them (MDH_OPT_JIT)
    std::string jit_kinds; // mdh_jit_kinds.h of this scene (generated once)
    hipStream_t probe_stream = nullptr;   // radiance + irradiance passes of pipelined frames
@@ -693,7 +802,11 @@ static int commit_scene(mdh_renderer *r, hipStream_t up)
          return seterr(MDH_E_INVALID, "MDH_OPT_TABLE_RESIDENCY 1: scenes with user-defined kinds keep their table in LDS");
       if (!fits && (has_custom || n_res * 16 + park > budget))
          return seterr(MDH_E_INVALID, "scene tables exceed the 64 KiB LDS budget of a workgroup");
-      r->residency = !fits || r->opt_residency == 1 ? 1 : 0;
+      // MDH_OPT_TRIANGLE_BVH: the walk reads nodes and triangles from the image -- global residency, whatever the size
+      int tri_kinds = 0;
+      for (int k = 0; k < r->npk; ++k) tri_kinds += r->pk[k].type == PK_TRIANGLE;
+      r->bvh_active = r->opt_tri_bvh != 0 && tri_kinds == 1 && !has_custom && r->part.enable == 0;
+      r->residency = !fits || r->opt_residency == 1 || r->bvh_active ? 1 : 0;
       s.table_f4 = (int)t.size();
       if (r->residency) {
          std::rotate(t.begin() + geo_begin, t.begin() + geo_end, t.end());
@@ -707,6 +820,26 @@ static int commit_scene(mdh_renderer *r, hipStream_t up)
          H[H_VCLEAR] = 0; // (segment_clear reads its geometry from LDS: off, as it is for every scene with triangles or a partition)
          s.table_f4 = (int)n_res;
          t.push_back(mk4(0, 0, 0, 0)); t.push_back(mk4(0, 0, 0, 0)); // (the first-sphere / first-box reads of a scene without any stay inside the image)
+      }
+   }
+   if (r->bvh_active) { // the hierarchy behind everything else of the image: nodes, then the permutation (rebuilt when a triangle or their count changed)
+      const int n = s.tcount[PK_TRIANGLE];
+      std::vector<float> tris(9 * (size_t)n);
+      for (int i = 0; i < 3 * n; ++i) { const float4 v = t[s.tslot[PK_TRIANGLE] + i]; tris[3 * (size_t)i] = v.x; tris[3 * (size_t)i + 1] = v.y; tris[3 * (size_t)i + 2] = v.z; }
+      if (!r->bvh_built || tris.size() != r->bvh_tris.size() || (n > 0 && memcmp(tris.data(), r->bvh_tris.data(), tris.size() * 4) != 0)) {
+         bvh_build(tris.data(), n, r->bvh);
+         r->bvh_tris.swap(tris);
+         r->bvh_built = true;
+      }
+      H[H_BVH_NODES] = (int)t.size();
+      H[H_BVH_COUNT] = (int)r->bvh.nodes.size() / 2;
+      H[H_BVH_ALWAYS] = r->bvh.n_always;
+      H[H_BVH_DELTA] = f_as_i(r->bvh.delta);
+      t.insert(t.end(), r->bvh.nodes.begin(), r->bvh.nodes.end());
+      for (int i0 = 0; i0 < n; i0 += 4) {
+         float m[4] = {0, 0, 0, 0};
+         for (int j = 0; j < 4 && i0 + j < n; ++j) m[j] = i_as_f(r->bvh.perm[i0 + j]);
+         t.push_back(mk4(m[0], m[1], m[2], m[3]));
       }
    }
    for (int k = 0; k < r->npk; ++k) { H[H_KQUAD + 4 * k] = H[H_KTYPE + k]; H[H_KQUAD + 4 * k + 1] = H[H_KSLOT + k]; H[H_KQUAD + 4 * k + 2] = H[H_KBASE + k]; H[H_KQUAD + 4 * k + 3] = H[H_KMAX + k]; }
@@ -1102,6 +1235,16 @@ extern "C" int32_t mdh_set_option(mdh_renderer *r, int32_t option, int32_t value
       if (r->in_frame) return seterr(MDH_E_STATE, "a frame is open");
       if (value != r->opt_residency) { r->opt_residency = value; r->table_dirty = true; } // (the next commit lays the table out again)
       break;
+   case MDH_OPT_TRIANGLE_BVH: {
+      if (value != 0 && value != 1) return seterr(MDH_E_INVALID, "the triangle BVH is 0 (off) or 1 (on)");
+      if (r->in_frame) return seterr(MDH_E_STATE, "a frame is open");
+      int tri_kinds = 0;
+      for (int k = 0; k < r->npk; ++k) tri_kinds += r->pk[k].type == PK_TRIANGLE;
+      if (value && (r->part.enable != 0 || has_custom_kinds(r) || tri_kinds > 1))
+         return seterr(MDH_E_STATE, "MDH_OPT_TRIANGLE_BVH: scenes without a space partition, without user-defined kinds and with one Triangle kind only");
+      if (value != r->opt_tri_bvh) { r->opt_tri_bvh = value; r->table_dirty = true; } // (the next commit lays the table out again)
+      break;
+   }
    case MDH_OPT_RADIANCE_MIPS: {
       const int res = r->probes.radiance_resolution;
       if (value && (res & (res - 1)) != 0) return seterr(MDH_E_INVALID, "radiance mips need a power-of-two radiance resolution");
@@ -1141,6 +1284,7 @@ extern "C" int32_t mdh_get_option(mdh_renderer *r, int32_t option, int32_t *valu
    case MDH_OPT_SCREEN_SPLIT: *value = r->opt_scr_split; break;
    case MDH_OPT_NUMERICS: *value = MDH_FAST_NUMERICS ? 1 : (MDH_HYBRID_NUMERICS ? 2 : 0); break; // 0 exact (shipped), 1 / 2 the labelled experiments
    case MDH_OPT_RADIANCE_MIPS: *value = r->opt_mips; break;
+   case MDH_OPT_TRIANGLE_BVH: *value = r->opt_tri_bvh; break;
    case MDH_OPT_TABLE_RESIDENCY: { // of the committed scene: edits since the last commit are committed first
       if (r->table_dirty && !r->in_frame) {
          HIP_TRY(hipSetDevice(r->device));
@@ -1606,6 +1750,8 @@ static const void *table_kernel(const mdh_renderer *r, int family)
    k.family = family;
    k.pf = r->residency ? MDH_PF_GTAB : 0;
    k.ada_div = r->opt_ada_div != 0;
+   // the distance query walks the triangle BVH too -- unless it divides as Madarch.Values."/" does (L + R: no distance, no bound)
+   if (family == GK_k_eval_distance && r->bvh_active && !k.ada_div) k.pf |= MDH_PF_BVH;
    return kernel_ptr(k);
 }
 
@@ -1727,7 +1873,8 @@ static PassKernel pick_kernel(const mdh_renderer *r, int pass, int set)
    const bool room = pf == 0 && room_census(r) && !gtab;
    // bit 5 = the partition's small form with its census (mdh_device.h: partitioning_closest_bits)
    const bool psmall = pf == MDH_PF_PART && r->ks.part_small && r->ks.part_tmask[PK_TRIANGLE] == 0 && r->ks.part_sp_pow2 && r->ks.part_cells < (1 << 24) && !gtab;
-   k.pfk = gtab ? (pf | MDH_PF_GTAB) : room ? MDH_PF_ROOM : (psmall ? (MDH_PF_PART | MDH_PF_PSMALL) : pf);
+   // bit 7 = the triangle BVH (MDH_OPT_TRIANGLE_BVH; commit_scene: global residency, no partition, no user-defined kinds)
+   k.pfk = gtab ? (pf | MDH_PF_GTAB | (r->bvh_active ? MDH_PF_BVH : 0)) : room ? MDH_PF_ROOM : (psmall ? (MDH_PF_PART | MDH_PF_PSMALL) : pf);
    // bit 2: the probe-sampling kernels (radiance, mode-0 screen) have a variant for atlases whose every dimension is a power
    // of two (and small enough for what it assumes besides: probe ids within 24-bit products, RGBA8 byte offsets within 32
    // bits -- mdh_device.h: grid_to_probe_id, atlas_rgba8)
@@ -3135,6 +3282,34 @@ extern "C" int32_t mdh_eval_distance_to(mdh_renderer *r, int32_t n, const float 
    return MDH_OK;
 }
 
+// the hierarchy of the committed scene (pending edits are committed first): its nodes, leaves, depth and the length of the
+// always-evaluated list; all 0 while MDH_OPT_TRIANGLE_BVH is off or the scene declares no triangles
+extern "C" int32_t mdh_triangle_bvh_info(mdh_renderer *r, int32_t *nodes, int32_t *leaves, int32_t *depth, int32_t *always)
+{
+   if (!r) return seterr(MDH_E_INVALID, "null renderer");
+   if (r->table_dirty && !r->in_frame) {
+      HIP_TRY(hipSetDevice(r->device));
+      const int rc = commit_scene(r, r->stream);
+      if (rc != MDH_OK) return rc;
+   }
+   const bool on = r->bvh_active;
+   if (nodes) *nodes = on ? (int32_t)r->bvh.nodes.size() / 2 : 0;
+   if (leaves) *leaves = on ? r->bvh.leaves : 0;
+   if (depth) *depth = on ? r->bvh.depth : 0;
+   if (always) *always = on ? r->bvh.n_always : 0;
+   return MDH_OK;
+}
+#ifdef MDH_BVH_STATS
+// the counter build: node visits and skipped nodes (wavefronts) since the last call
+extern "C" int32_t mdh_diag_bvh(unsigned long long *out2)
+{
+   if (hipMemcpyFromSymbol(out2, HIP_SYMBOL(g_bvh_stats), sizeof(unsigned long long) * 2) != hipSuccess) return MDH_E_DEVICE;
+   unsigned long long z[2] = {0, 0};
+   if (hipMemcpyToSymbol(HIP_SYMBOL(g_bvh_stats), z, sizeof z) != hipSuccess) return MDH_E_DEVICE;
+   return MDH_OK;
+}
+#endif
+
 extern "C" int32_t mdh_pass_time(mdh_renderer *r, int32_t pass, double *ms, int64_t *launches)
 {
    if (!r || pass < 0 || pass >= MDH_PASS_COUNT) return seterr(MDH_E_INVALID, "bad argument");
@@ -3347,6 +3522,8 @@ static const void *kernel_ptr(const PassKernel &k)
    MDH_K(k_partition_build, MDH_PF_GTAB, k_partition_build_gtab<>)
    MDH_K(k_eval_distance, MDH_PF_GTAB, k.ada_div ? k_eval_distance_gtab<true> : k_eval_distance_gtab<false>)
    MDH_GTAB(73) MDH_GTAB(64)
+   MDH_GTAB(192) // MDH_PF_GTAB | MDH_PF_BVH: the newest last, so that nothing older moves
+   MDH_K(k_eval_distance, MDH_PF_GTAB | MDH_PF_BVH, k_eval_distance_bvh<>)
    return nullptr;
 #undef MDH_K
 #undef MDH_RAD

@@ -86,6 +86,9 @@ enum {
    // segment_clear (MDH_VIS_CLEAR): the float bits of its threshold EPS + delta (0: off for this scene) and of the bound on
    // every coordinate of a segment it may clear
    H_VCLEAR = 2, H_VCLEAR_LIM = 3,
+   // the triangle BVH (MDH_PF_BVH, bvh_triangles below): first float4 of its nodes in the table's image (the permutation
+   // follows them), the number of nodes, the size of the always-evaluated list, the float bits of the pruning margin delta
+   H_BVH_NODES = 4, H_BVH_COUNT = 5, H_BVH_ALWAYS = 6, H_BVH_DELTA = 7,
    H_KTYPE = 8,    // [8] PK_*
    H_KCOUNT = 16,  // [8] runtime count (prim_<K>_count, scenes.adb:560-565)
    H_KBASE = 24,   // [8] flat index base = sum of earlier DECLARED counts
@@ -693,6 +696,102 @@ template <typename TAB> MDH_DEV float prim_dist(TAB tab, int type, int slot, f3 
    }
 }
 
+// ------------------------------------------------------------------ triangle BVH (MDH_PF_BVH)
+// The triangle loop of closest_primitive[_info] as a walk through a bounding-volume hierarchy the host builds
+// (mdh_api.hip: bvh_build; MDH_OPT_TRIANGLE_BVH).  min is order-free and a triangle whose distance is not below the running
+// minimum contributes nothing, so a subtree whose box is provably farther than that minimum for every lane of the
+// wavefront is skipped, and the result keeps the bits of the scan over all triangles.
+//
+// Image (behind the geometry in the table's image, read through address space 1 like Geo<true>): nodes in depth-first
+// order, two float4 each -- {lo.xyz, skip} {hi.xyz, leaf} with skip = the next node once this subtree is done (the walk
+// needs no stack; the root's skip is the node count) and leaf = -1 for an inner node, first * 8 + count (count <= 4) for a
+// leaf's range of the permutation; then the permutation, ints: the instance indices of the walked triangles in leaf order
+// and, behind them, the H_BVH_ALWAYS instances of the ALWAYS-EVALUATED list, which no test guards.
+// The walk is wave-uniform: node index and node are scalar (scalar loads through readfirstlane), the box test is one
+// squared point-box distance per lane against thr = closest (1 + rho) + delta, and one ballot decides for the wavefront.
+//
+// THE MARGIN.  Let D be the true distance of x to the triangle and d = sd_triangle's fp32 value.  A triangle is pruned only
+// if d >= closest -- then min (closest, d) = closest (a NaN d changes nothing either).  sd_triangle takes one of two branches:
+//   edges  e_k = |v t - p|^2 with t CLAMPED to [0, 1] -- whatever the quotient gave (0 / 0, overflow, rounding), v t - p is
+//          the offset to SOME point of the edge, so sqrt (e_k) >= D up to the rounding of three subtractions, a product and
+//          a dot: a few 2^-24 of (|v| + |p|) <= a few 2^-24 (D + 2 diam).  (Underflow of e_k to 0 means D < 2^-60.)
+//   face   |dot (nor, p1)| / |nor|, the distance to the plane of the computed normal, taken when at least two of the three
+//          side tests are positive and the third not negative.  nor = cross (v21, v13) carries an absolute error of at most
+//          2^-22 L^2 per component (L = the longest edge); the host admits a triangle to the walk only when |nor| >= 2^-6 L^2
+//          (the sine of every angle is at least that), so the computed normal, and with it every side plane, is tilted by
+//          phi <= sqrt (3) 2^-16 < 2^-15.  With the foot point inside the triangle up to the tilt and the rounding of the
+//          side tests (both relative to |p1| <= D + L) the value is >= D cos (phi) - (L + ...) sin (phi) - a few 2^-22 (D + L)
+//          >= D (1 - 2^-20) - 2^-14 L; where two side tests are in doubt at once (x above a corner, within h phi 2^6 of it in
+//          the plane, h the height) D <= h sqrt (1 + 2^-18), again far inside the relative margin.
+// With every coordinate of the walked triangles bounded by lim, L <= 2 sqrt (3) lim, so d >= D (1 - 2^-19) - 2^-12 lim.  The
+// box distance b computed here has b <= (true box distance) (1 + 2^-21) <= D (1 + 2^-21).  A node is skipped only if
+// b > thr in every lane: then d > (closest (1 + 2^-8) + delta) (1 - 2^-18) - 2^-12 lim > closest for delta = 2^-10 (1 + lim)
+// and closest >= 0; for closest < 0 every triangle is skipped rightly (d >= 0).  rho = 2^-8 and delta cost nothing that can
+// be measured: they widen a box by 0.4 % of the running minimum plus a thousandth of the scene's size.
+// What the argument does not cover goes to the always-evaluated list on the host (mdh_api.hip: bvh_covers): a non-finite
+// vertex, a coordinate above 2^20 in magnitude (with the points below, every product of the side tests and dot2 (nor) stay
+// finite), an edge below 2^-12 (nothing of nor underflows) and |nor| < 2^-6 L^2 (slivers and zero-area triangles, whose
+// computed normal is rounding noise: the face branch may return anything below D).  And a lane whose point has a
+// coordinate of 2^40 or more (the side tests' sums can overflow to the wrong sign from about 2^60 on) needs every node.
+// The comparisons are written so that NaN visits: a NaN point evaluates every triangle.
+// INFO (closest_primitive_info): a candidate wins when it is closer, or as close with a lower flat index and `best` is a
+// candidate of this scan (>= 0) -- what a scan in index order keeps, the first of equal distances; a skipped triangle is
+// strictly farther than the running minimum (delta > 0), so no tie is lost.
+#define MDH_BVH_RHO 0x1p-8f              // rho: the one definition, the host's mdh_bvh_build reports it too
+#define MDH_BVH_RHO1 (1.0f + MDH_BVH_RHO) // (exact: folded when the kernels are built)
+// Cost.  The four header ints come out of LDS (one read, four readfirstlane) at every evaluation, and a leaf's triangle
+// is two dependent scalar loads, its permutation entry and then its vertices.  Neither was measured by itself; DESIGN.md
+// section 4 "A BVH over the triangles" has the walk's rates as a whole.
+#ifdef MDH_BVH_STATS // the counter build (make bvhstats): nodes visited and nodes skipped, per wavefront
+__device__ unsigned long long g_bvh_stats[2];
+#define MDH_BVH_STAT(slot) do { if (lane_index_fresh() == __ffsll((long long)__ballot(1)) - 1) atomicAdd(&g_bvh_stats[slot], 1ull); } while (0)
+#else
+#define MDH_BVH_STAT(slot) do { } while (0)
+#endif
+template <bool INFO> MDH_DEV void bvh_triangles(const KScene &sc, f3 x, float &closest, int &best, int base)
+{
+   const GeoImage img = Geo<true>::f4(sc);
+   const GeoInts ints = (GeoInts)sc.table;
+   const int n = sc.tcount[PK_TRIANGLE], s0 = sc.tslot[PK_TRIANGLE];
+   const int4 h = hdr4(H_BVH_NODES);
+   const int nodes = h.x, n_nodes = h.y, n_always = h.z, perm = (nodes + 2 * n_nodes) * 4;
+   const float delta = __int_as_float(h.w);
+   const bool wild = !(max_(max_(__builtin_fabsf(x.x), __builtin_fabsf(x.y)), __builtin_fabsf(x.z)) < 0x1p40f);
+#define MDH_BVH_TRI(j_)                                                                            \
+   do {                                                                                            \
+      const int i_ = __builtin_amdgcn_readfirstlane(ints[__builtin_amdgcn_readfirstlane(perm + (j_))]); \
+      const int t_ = __builtin_amdgcn_readfirstlane(s0 + 3 * i_);                                  \
+      const float d_ = sd_triangle<false>(xyz(img[t_]), xyz(img[t_ + 1]), xyz(img[t_ + 2]), x);    \
+      if (INFO) { if (d_ < closest || (d_ == closest && best >= 0 && base + i_ < best)) { closest = d_; best = base + i_; } } \
+      else closest = min_raw(closest, d_);                                                         \
+   } while (0)
+#pragma unroll 1
+   for (int j = n - n_always; j < n; ++j) MDH_BVH_TRI(j);
+   int node = 0;
+#pragma unroll 1
+   while (node < n_nodes) {
+      const int at = __builtin_amdgcn_readfirstlane(nodes + 2 * node);
+      const float4 lo = img[at], hi = img[at + 1];
+      const f3 q = max3s(F3(max_(lo.x - x.x, x.x - hi.x), max_(lo.y - x.y, x.y - hi.y), max_(lo.z - x.z, x.z - hi.z)), 0.0f);
+      const float d2 = dot2(q), thr = closest * MDH_BVH_RHO1 + delta;
+      const bool need = wild || (!(thr < 0.0f) && !(d2 > thr * thr));
+      MDH_BVH_STAT(0);
+      if (__ballot(need) == 0ull) {
+         MDH_BVH_STAT(1);
+         node = __builtin_amdgcn_readfirstlane(__float_as_int(lo.w));
+         continue;
+      }
+      const int leaf = __builtin_amdgcn_readfirstlane(__float_as_int(hi.w));
+      if (leaf >= 0) {
+         const int first = leaf >> 3, count = leaf & 7;
+#pragma unroll 1
+         for (int j = 0; j < count; ++j) MDH_BVH_TRI(first + j);
+      }
+      ++node; // (depth first: an inner node's first child follows it, and a leaf's skip link is the next node)
+   }
+#undef MDH_BVH_TRI
+}
+
 #ifndef MDH_INFO_UNROLL
 #define MDH_INFO_UNROLL 1
 #endif
@@ -727,7 +826,7 @@ template <bool GTAB = false> MDH_DEV SdfRegs sdf_regs(const KScene &sc)
 // configs 3, 4, 5).  The same operations on the same operands; what goes is what a count known only at run time costs at every
 // march step -- the loops' scalar bookkeeping and branches around bodies that run once or never -- and the registers their
 // induction state holds: 96 -> 80 VGPRs in the screen kernel, six wavefronts per SIMD without a further spill.
-template <bool CUSTOM, bool ROOM = false, bool GTAB = false> MDH_DEV float closest_primitive(const KScene &sc, f3 x, const SdfRegs *regs = nullptr)
+template <bool CUSTOM, bool ROOM = false, bool GTAB = false, bool BVH = false> MDH_DEV float closest_primitive(const KScene &sc, f3 x, const SdfRegs *regs = nullptr)
 {
    const typename Geo<GTAB>::F4 s_tab = Geo<GTAB>::f4(sc); // (shadows the LDS table: global residency reads the image; every index below is wave-uniform)
    float closest = sc.max_dist;
@@ -776,7 +875,10 @@ template <bool CUSTOM, bool ROOM = false, bool GTAB = false> MDH_DEV float close
       for (int i = 1; i < n; ++i) MDH_BOX_STEP(s_tab[uni<GTAB>(s0 + 2 * i)], s_tab[uni<GTAB>(s0 + 2 * i + 1)]);
 #undef MDH_BOX_STEP
    }
-   {
+   if (BVH) { // (last of the built-in types: what planes, spheres and boxes left of `closest` seeds the pruning)
+      int none = -1;
+      bvh_triangles<false>(sc, x, closest, none, 0);
+   } else {
       const int n = ROOM ? 0 : sc.tcount[PK_TRIANGLE], s0 = sc.tslot[PK_TRIANGLE];
 #pragma unroll 1
       for (int i = 0; i < n; ++i)
@@ -800,7 +902,7 @@ template <bool CUSTOM, bool ROOM = false, bool GTAB = false> MDH_DEV float close
 }
 // closest_primitive_info (scenes.adb:631-674): kinds in SCENE order (the arg-min keeps the
 // first of equal distances).  Only evaluated at hit points, so compact rather than fast.
-template <bool CUSTOM, bool GTAB = false> MDH_DEV float closest_primitive_info(const KScene &sc, f3 x, int &index)
+template <bool CUSTOM, bool GTAB = false, bool BVH = false> MDH_DEV float closest_primitive_info(const KScene &sc, f3 x, int &index)
 {
    const typename Geo<GTAB>::F4 s_tab = Geo<GTAB>::f4(sc); // (shadows the LDS table, as in closest_primitive)
    float closest = sc.max_dist;
@@ -833,7 +935,8 @@ template <bool CUSTOM, bool GTAB = false> MDH_DEV float closest_primitive_info(c
 #pragma unroll 1
          for (int i = 0; i < n; ++i) MDH_CAND(sd_box(s_tab[uni<GTAB>(s0 + 2 * i)], s_tab[uni<GTAB>(s0 + 2 * i + 1)], x), base + i);
       }
-      {
+      if (BVH) bvh_triangles<true>(sc, x, closest, best, hdr(H_TBASE + PK_TRIANGLE)); // (MDH_CAND's rule: the arg-min does not depend on the order of the visits)
+      else {
          const int n = sc.tcount[PK_TRIANGLE], s0 = sc.tslot[PK_TRIANGLE], base = hdr(H_TBASE + PK_TRIANGLE);
 #pragma unroll 1
          for (int i = 0; i < n; ++i)
@@ -847,6 +950,13 @@ template <bool CUSTOM, bool GTAB = false> MDH_DEV float closest_primitive_info(c
 #pragma unroll 1
    for (int k = 0; k < nk; ++k) {
       const int n = hdr(H_KCOUNT + k), s0 = hdr(H_KSLOT + k), base = hdr(H_KBASE + k), type = hdr(H_KTYPE + k);
+      if (BVH && type == PK_TRIANGLE && s0 == sc.tslot[PK_TRIANGLE]) { // the kind the hierarchy was built over
+         // the first of equal distances: an earlier kind keeps a tie (best < 0), among the triangles the lower index does
+         int best = -1;
+         bvh_triangles<true>(sc, x, closest, best, base);
+         if (best >= 0) index = best;
+         continue;
+      }
 #pragma unroll MDH_INFO_UNROLL
       for (int i = 0; i < n; ++i) {
          float d = (CUSTOM && type == PK_CUSTOM) ? xdist<false>(k, i, x) : prim_dist(s_tab, type, uni<GTAB>(s0 + prim_slots(type) * i), x);
@@ -1154,6 +1264,7 @@ template <bool CUSTOM, bool FALLBACK, bool PSMALL = false, bool GTAB = false> MD
 #define MDH_PF_FALLBACK 8 // bit 3 = the space partition's Border_Behavior is Fallback (built-in kinds; scenes with user-defined kinds keep the run-time test)
 #define MDH_PF_PSMALL 32 // bit 5 = the space partition's small form and its census, known when the kernel is built (partitioning_closest_bits' PSMALL; with bit 0, never with bits 1 or 3)
 #define MDH_PF_GTAB 64 // bit 6 = global residency of the scene table (Geo<true> above): geometry and material ids are read from the table's image in memory, LDS holds the resident part only (built-in kinds; with or without bits 0 and 3; never with bits 1, 2, 4 or 5)
+#define MDH_PF_BVH 128 // bit 7 = the triangles are walked through their bounding-volume hierarchy (bvh_triangles above; MDH_OPT_TRIANGLE_BVH): with bit 6 only -- no partition, no user-defined kinds, no census, no power-of-two addressing
 #define MDH_PF_ROOM 16 // bit 4 = the census of the reference's rooms, known when the kernel is built (closest_primitive's ROOM; never with bits 0, 1 or 3)
 // does this variant carry the full scan of the Fallback border?
 #define MDH_PF_HAS_FALLBACK(PART) ((((PART) & MDH_PF_FALLBACK) != 0) || (((PART) & MDH_PF_CUSTOM) != 0))
@@ -1161,20 +1272,20 @@ template <int PART> MDH_DEV float sdf(const KScene &sc, f3 x)
 {
    MDH_WORK(2);
    if (PART & MDH_PF_PART) return partitioning_closest_bits<(PART & MDH_PF_CUSTOM) != 0, MDH_PF_HAS_FALLBACK(PART), (PART & MDH_PF_PSMALL) != 0, (PART & MDH_PF_GTAB) != 0>(sc, x);
-   return closest_primitive<(PART & MDH_PF_CUSTOM) != 0, (PART & MDH_PF_ROOM) != 0, (PART & MDH_PF_GTAB) != 0>(sc, x);
+   return closest_primitive<(PART & MDH_PF_CUSTOM) != 0, (PART & MDH_PF_ROOM) != 0, (PART & MDH_PF_GTAB) != 0, (PART & MDH_PF_BVH) != 0>(sc, x);
 }
 // the same with the first sphere and box already in registers (sdf_regs)
 template <int PART> MDH_DEV float sdf(const KScene &sc, f3 x, const SdfRegs &regs)
 {
    MDH_WORK(2);
    if (PART & MDH_PF_PART) return partitioning_closest_bits<(PART & MDH_PF_CUSTOM) != 0, MDH_PF_HAS_FALLBACK(PART), (PART & MDH_PF_PSMALL) != 0, (PART & MDH_PF_GTAB) != 0>(sc, x);
-   return closest_primitive<(PART & MDH_PF_CUSTOM) != 0, (PART & MDH_PF_ROOM) != 0, (PART & MDH_PF_GTAB) != 0>(sc, x, &regs);
+   return closest_primitive<(PART & MDH_PF_CUSTOM) != 0, (PART & MDH_PF_ROOM) != 0, (PART & MDH_PF_GTAB) != 0, (PART & MDH_PF_BVH) != 0>(sc, x, &regs);
 }
 template <int PART> MDH_DEV float sdf_info(const KScene &sc, f3 x, int &index)
 {
    MDH_WORK(2);
    if (PART & MDH_PF_PART) return partitioning_lookup<true, (PART & MDH_PF_CUSTOM) != 0, MDH_PF_HAS_FALLBACK(PART), (PART & MDH_PF_PSMALL) != 0, (PART & MDH_PF_GTAB) != 0>(sc, x, index);
-   return closest_primitive_info<(PART & MDH_PF_CUSTOM) != 0, (PART & MDH_PF_GTAB) != 0>(sc, x, index);
+   return closest_primitive_info<(PART & MDH_PF_CUSTOM) != 0, (PART & MDH_PF_GTAB) != 0, (PART & MDH_PF_BVH) != 0>(sc, x, index);
 }
 
 // ------------------------------------------------------------- probe-visibility clearance

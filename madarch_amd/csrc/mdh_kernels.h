@@ -1336,7 +1336,7 @@ struct EvalArgs {
    float *normals;
    float *dist;
 };
-template <bool ADA_DIV, bool GTAB> MDH_DEV void eval_distance(const KScene &sc, const EvalArgs &a)
+template <bool ADA_DIV, bool GTAB, bool BVH = false> MDH_DEV void eval_distance(const KScene &sc, const EvalArgs &a)
 {
    const typename Geo<GTAB>::F4 s_tab = Geo<GTAB>::f4(sc); // (shadows the LDS table)
    stage_table(sc);
@@ -1347,6 +1347,17 @@ template <bool ADA_DIV, bool GTAB> MDH_DEV void eval_distance(const KScene &sc, 
    f3 normal = F3(0.0f, 0.0f, 0.0f);
    for (int kk = 0; kk < a.n_kinds; ++kk) {
       const int k = a.kinds[kk], type = hdr(H_KTYPE + k);
+      // MDH_PF_BVH: the committed triangles through their hierarchy (bvh_triangles, mdh_device.h) -- the arg-min keeps the
+      // lowest index of equal distances, as the loop below does, and the normal is computed once, for the winner
+      if (BVH && !ADA_DIV && type == PK_TRIANGLE && hdr(H_KSLOT + k) == sc.tslot[PK_TRIANGLE] && a.host_count[k] == sc.tcount[PK_TRIANGLE]) {
+         int best = -1;
+         bvh_triangles<true>(sc, p, closest, best, 0);
+         if (best >= 0) {
+            const int slot = hdr(H_KSLOT + k) + 3 * best;
+            normal = nrm_triangle<ADA_DIV>(xyz(s_tab[slot]), xyz(s_tab[slot + 1]), xyz(s_tab[slot + 2]), p);
+         }
+         continue;
+      }
       for (int i = 0; i < a.host_count[k]; ++i) {
          float d = part_dist<ADA_DIV, GTAB, GTAB>(sc, k, i, p);
          if (d < closest) {
@@ -1368,6 +1379,7 @@ template <bool ADA_DIV, bool GTAB> MDH_DEV void eval_distance(const KScene &sc, 
 }
 template <bool ADA_DIV> __global__ __launch_bounds__(64) void k_eval_distance(KScene sc, EvalArgs a) { eval_distance<ADA_DIV, false>(sc, a); }
 template <bool ADA_DIV> __global__ __launch_bounds__(64) void k_eval_distance_gtab(KScene sc, EvalArgs a) { eval_distance<ADA_DIV, true>(sc, a); } // global residency of the scene table
+template <int = 0> __global__ __launch_bounds__(64) void k_eval_distance_bvh(KScene sc, EvalArgs a) { eval_distance<false, true, true>(sc, a); } // ... with the triangle BVH (the Ada division of MDH_OPT_ADA_EVAL_DIV is no distance: such queries scan)
 
 // ---------------------------------------------------------------------- the window's pixels
 // What Swap_Buffers (renderers.adb:320) puts on screen: the screen pass writes float colours and

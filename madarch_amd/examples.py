@@ -11,7 +11,7 @@ first `Renderers.Render`.  `Binding=None` is the HIP library.
 """
 import numpy as np
 
-from . import lights, materials, meshes, primitives, renderers, scenes, windows
+from . import _binding, lights, materials, meshes, primitives, renderers, scenes, windows
 from .lights import point_lights, spot_lights
 from .primitives import boxes, planes, spheres, triangles
 
@@ -117,14 +117,16 @@ OBJ_MESH_OFFSET = (1.5, 1.0, 1.0)  # Suzanne_Offset, main.adb:139-140
 
 
 def obj_mesh(Width=1000, Height=1000, Probes=None, Binding=None, Device=0,
-             Partitioning_Method=renderers.GPU_Fast, Mesh=None, Index_Count=150):
+             Partitioning_Method=renderers.GPU_Fast, Mesh=None, Index_Count=150, Triangle_BVH=False):
     """examples/obj_mesh/main.adb: 1000 triangles behind a 30 x 20 x 20 partition of 0.1 cells, one point
     light, the default probes (the example declares probe settings and does not pass them).  `Mesh`
     ([n, 3, 3] vertex triples about the origin, n <= 1000) stands for media/suzanne.obj -- there is no
     loader; the default is meshes.torus (25, 20): exactly 1000 triangles.  The scene's table is larger
-    than a workgroup's LDS: the HIP library reads its geometry from device memory (OPT_TABLE_RESIDENCY)."""
+    than a workgroup's LDS: the HIP library reads its geometry from device memory (OPT_TABLE_RESIDENCY).
+    `Triangle_BVH` (HIP library only): the same mesh with `Partitioning => (Enable => False)` and
+    OPT_TRIANGLE_BVH on -- the exact scan over all 1000 triangles, walked through a bounding-volume hierarchy."""
     Partitioning_Settings = scenes.Partitioning_Settings(
-        Enable=True, Index_Count=Index_Count, Border_Behavior=scenes.Clamp, Grid_Dimensions=(30, 20, 20),
+        Enable=not Triangle_BVH, Index_Count=Index_Count, Border_Behavior=scenes.Clamp, Grid_Dimensions=(30, 20, 20),
         Grid_Spacing=(0.1, 0.1, 0.1), Grid_Offset=(0.0, 0.0, 0.0))
     Scene = scenes.Compile(
         All_Primitives=[(triangles.Triangle, OBJ_MESH_TRIANGLES)],
@@ -133,6 +135,8 @@ def obj_mesh(Width=1000, Height=1000, Probes=None, Binding=None, Device=0,
     Window = windows.Open(Width, Height, "Obj_Mesh")
     R = renderers.Create(Window, Scene, Probes=Probes, Volumetrics=renderers.No_Volumetrics,
                          Device=Device, Binding=Binding)
+    if Triangle_BVH:
+        R.Set_Option(_binding.OPT_TRIANGLE_BVH, 1)
     Point_Light_Instance = point_lights.Create((0.0, 1.0, -5.0), (0.9, 0.9, 0.9))
     Mesh_Mat = R.Add_Material(materials.Create((0.8, 0.2, 0.1), 0.0, 1.0))
     if Mesh is None:
@@ -140,7 +144,7 @@ def obj_mesh(Width=1000, Height=1000, Probes=None, Binding=None, Device=0,
     Offset = np.asarray(OBJ_MESH_OFFSET, dtype=np.float32)
     for A, B, C in np.asarray(Mesh, dtype=np.float32):  # Add_Triangle, main.adb:142-153
         R.Add_Primitive(triangles.Triangle, triangles.Create(A + Offset, B + Offset, C + Offset, Mesh_Mat))
-    if Partitioning_Method is not None:
+    if Partitioning_Method is not None and not Triangle_BVH:
         R.Update_Partitioning(Method=Partitioning_Method)
     R.Set_Light(1, point_lights.Point_Light, Point_Light_Instance)
     R.Set_Camera_Position((0.0, 1.0, -5.0))  # Move_Camera with a zero offset, main.adb:70-75,133
