@@ -132,6 +132,9 @@ package Madarch_HIP is
    --  a bounding-volume hierarchy (the same bits; scenes with Partitioning => (Enable => False)
    --  and without user-defined kinds, Status 7 otherwise), 0 (default) = scanned one by one.
    Opt_Triangle_BVH : constant int := 20;
+   --  Opt_Radiance_Replay: 1 (default) = probe rays' hits and cage visibility are replayed from
+   --  per-ray records while the scene's geometry stands still (the same bits), 0 = marched every pass.
+   Opt_Radiance_Replay : constant int := 21;
 
    function Set_Option (R : Handle; Option, Value : int) return Status
      with Import, Convention => C, External_Name => "mdh_set_option";

@@ -280,7 +280,18 @@ enum {
     * the scene then runs in global residency (MDH_OPT_TABLE_RESIDENCY reads 1).  For scenes without a space partition,
     * without user-defined kinds and with at most one Triangle kind: MDH_E_STATE otherwise; other values MDH_E_INVALID.
     * A scene that declares no triangles accepts it and nothing changes. */
-   MDH_OPT_TRIANGLE_BVH = 20
+   MDH_OPT_TRIANGLE_BVH = 20,
+   /* 1 (default) = probe rays are not marched again while the scene's geometry stands still -- no effect on any texel.
+    * A probe ray starts at a fixed probe in a fixed direction: whether and where it hits, the nearest primitive there, its
+    * step count, the first step of the hit point's shadow and visibility rays and the visibility of its eight cage probes
+    * follow from the geometry alone.  The first radiance pass over geometry that did not change since the pass before
+    * writes them to a 16-byte record per ray; later passes read the records and compute only what lights, materials and
+    * the irradiance atlas change (direct light with its shadow rays, the eight taps), from the same values with the same
+    * operations.  Set_Primitive, Add_Primitive, Update_Partitioning and every option or slice change that a march depends
+    * on end it: the next pass marches, the one after records again.  The brute-force and room-census kernels replay; scenes
+    * with a space partition, user-defined kinds or global residency keep marching ("Exact work
+    * elimination", item 11).  0 = march every pass; the records are dropped.  mdh_radiance_replay_stats counts the passes. */
+   MDH_OPT_RADIANCE_REPLAY = 21
 };
 
 /* passes of Renderers.Render (madarch-renderers.adb:302-321) */
@@ -486,6 +497,9 @@ int32_t mdh_eval_distance_to(mdh_renderer *r, int32_t n, const float *points_xyz
 
 /* accumulated HIP-event time and launch count of one pass (MDH_OPT_TIMING) */
 int32_t mdh_pass_time(mdh_renderer *r, int32_t pass, double *total_ms, int64_t *launches);
+/* MDH_OPT_RADIANCE_REPLAY: the radiance passes launched since mdh_create that marched their rays (`plain`), marched them
+ * and wrote the rays' records (`recording`), and read the records instead of marching (`replaying`).  Any pointer may be null. */
+int32_t mdh_radiance_replay_stats(mdh_renderer *r, int64_t *plain, int64_t *recording, int64_t *replaying);
 int32_t mdh_reset_pass_times(mdh_renderer *r);
 
 /* std140 layout queries = Scenes.Get_Primitives_Location / Get_Lights_Location

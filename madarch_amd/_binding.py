@@ -24,6 +24,7 @@ OPT_RANK, OPT_WORLD, OPT_TIMING, OPT_ADA_EVAL_DIV, OPT_FRAME_OVERLAP, OPT_JIT, O
 OPT_INDIRECT_SPECULAR, OPT_HYSTERESIS_PERMILLE, OPT_RADIANCE_ORDER, OPT_SCREEN_ORDER, OPT_NUMERICS, OPT_RADIANCE_MIPS, OPT_SCREEN_SPLIT = 12, 13, 14, 15, 16, 17, 18
 OPT_TABLE_RESIDENCY = 19  # read: 0 = the scene table in LDS, 1 = geometry in device memory (large scenes); write 1: force it
 OPT_TRIANGLE_BVH = 20  # 1: the triangles are walked through a bounding-volume hierarchy (the same bits; HIP library only)
+OPT_RADIANCE_REPLAY = 21  # 1 (default): probe rays' hits and cage visibility are replayed while the geometry stands still (the same bits; HIP library only)
 
 PASS_RADIANCE, PASS_IRRADIANCE, PASS_VISIBILITY, PASS_SCATTERING, PASS_SCREEN, PASS_EXCHANGE = range(6)
 PASS_NAMES = ("radiance", "irradiance", "visibility", "scattering", "screen", "exchange")
@@ -147,6 +148,8 @@ HIP_ONLY_ABI = {
     # OPT_TRIANGLE_BVH: the builder by itself (no renderer, no device) and the hierarchy of a renderer's committed scene
     "bvh_build": (_I, [_P, _I, _P, _PI, _P, _P]),
     "triangle_bvh_info": (_I, [_P, _PI, _PI, _PI, _PI]),
+    # OPT_RADIANCE_REPLAY: radiance passes that marched, recorded, replayed
+    "radiance_replay_stats": (_I, [_P, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
 }
 
 

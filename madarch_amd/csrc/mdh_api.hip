@@ -275,6 +275,7 @@ extern "C" int32_t mdh_bvh_build(const float *tri_xyz, int32_t n_tris, void *nod
 #endif
 // how often the probe rays (MDH_OPT_RADIANCE_ORDER) and the screen tiles (MDH_OPT_SCREEN_ORDER) are sorted again: every
 // MDH_RAD_RESORT passes, and after MDH_RAD_RESORT_MOVING passes when the geometry (or, for the tiles, the camera) changed
+#define MDH_LDS_WORKGROUP_BUDGET ((size_t)64 * 1024) // the LDS a workgroup may allocate: commit_scene fits the scene table into it, rad_replay_pick the recording kernel's rows
 #ifndef MDH_RAD_RESORT
 #define MDH_RAD_RESORT 64
 #endif
@@ -362,6 +363,35 @@ struct mdh_renderer {
    int rad_order_age = 0;                  // radiance passes since the rays were sorted
    unsigned long rad_order_scene = 0, geometry_edits = 0; // primitives set or added when the rays were sorted / so far
    int opt_rad_order = MDH_RAD_ORDER_DEFAULT;
+   // MDH_OPT_RADIANCE_REPLAY (mdh_march.h: RayRecord): one record per probe ray of the slice, indexed by the ray.
+   // ONE buffer serves all three atlas sets: a record holds nothing of an atlas, and it is written and read by radiance
+   // passes only.  Those run on the probe stream, one behind the other, or on the main stream after the join that orders a
+   // single pass against the frames in flight (join_main; the probe stream is ordered after the main stream's work when
+   // frames go in flight again) -- the order that d_rad_order relies on between the pass that sorts and the pass that reads.
+   // It is allocated, grown and freed like d_rad_steps / d_rad_order: with both streams drained.
+   RayRecord *d_rad_rec = nullptr;
+   long rad_rec_cap = 0;                   // rays the buffer is sized for
+   struct RadRecKey {                      // everything a probe ray's marches read (rad_rec_key): records are valid for one value of it
+      unsigned long geometry, inputs;      // geometry_edits, march_inputs
+      unsigned long long part_version;     // Update_Partitioning's builds
+      long rays;
+      int grid[3], res[2], pc[2], probe_begin, probe_end;
+      float spacing[3], max_dist;
+      int pf, small, jit, residency, bvh, table_f4, part_bits_f4;
+      bool operator==(const RadRecKey &o) const
+      {
+         return geometry == o.geometry && inputs == o.inputs && part_version == o.part_version && rays == o.rays &&
+                memcmp(grid, o.grid, sizeof grid) == 0 && memcmp(res, o.res, sizeof res) == 0 && memcmp(pc, o.pc, sizeof pc) == 0 &&
+                probe_begin == o.probe_begin && probe_end == o.probe_end && memcmp(spacing, o.spacing, sizeof spacing) == 0 && // (bits: a NaN spacing still equals itself)
+                memcmp(&max_dist, &o.max_dist, sizeof max_dist) == 0 && pf == o.pf && small == o.small && jit == o.jit && residency == o.residency &&
+                bvh == o.bvh && table_f4 == o.table_f4 && part_bits_f4 == o.part_bits_f4;
+      }
+   };
+   RadRecKey rad_rec_key, rad_seen_key;    // what the records are of / what the previous radiance pass marched through
+   bool rad_rec_valid = false, rad_seen_valid = false;
+   unsigned long march_inputs = 0;         // edits besides geometry_edits that change what a march kernel reads or which one runs (options, partition builds)
+   long long rad_replay_stats[3] = {0, 0, 0}; // radiance passes launched marching, recording, replaying
+   int opt_rad_replay = 1;
    // MDH_OPT_SCREEN_ORDER (ScreenArgs, mdh_kernels.h): the screen pass's tiles in the order of their wavefronts' durations
    unsigned char *d_scr_cost = nullptr;          // [tiles] sort keys, written by the pass that is followed by a sort
    unsigned *d_scr_order[2] = {nullptr, nullptr}; // [tiles] two buffers: passes in flight keep reading the one they were launched with
@@ -794,7 +824,7 @@ static int commit_scene(mdh_renderer *r, hipStream_t up)
    // table_f4 float4 only.  User-defined kinds interpret their instances out of LDS: they keep the whole table there.
    // (the march kernels park MDH_PARK_DWORDS floats per thread behind the table, lds_bytes_march)
    {
-      const size_t park = (size_t)MDH_SCR_PARK_ROWS * MDH_BLOCK * sizeof(float), budget = 64 * 1024;
+      const size_t park = (size_t)MDH_SCR_PARK_ROWS * MDH_BLOCK * sizeof(float), budget = MDH_LDS_WORKGROUP_BUDGET;
       const size_t n_geo = geo_end - geo_begin, n_res = t.size() - n_geo;
       const bool has_custom = has_custom_kinds(r);
       const bool fits = t.size() * 16 + park <= budget;
@@ -1016,7 +1046,7 @@ extern "C" int32_t mdh_destroy(mdh_renderer *r)
    if (r->comm) { ncclComm_t c = r->comm; r->comm = nullptr; (void)rccl_api_destroy(c); }
    if (r->d_comm_scratch) (void)hipFree(r->d_comm_scratch);
    peer_drop(r);
-   void *ptrs[] = {r->d_table_ring[0], r->d_table_ring[1], r->d_table_ring[2], r->d_table_ring[3], r->d_part_ring[0], r->d_part_ring[1], r->d_part_ring[2], r->d_part_ring[3], r->d_warn, r->d_query, r->d_irr_taps, r->d_rad_steps, r->d_rad_order, r->d_rad_hist, r->d_scr_cost, r->d_scr_order[0], r->d_scr_order[1], r->d_scr_hist, r->d_fb2[0], r->d_fb2[1], r->d_gb2[0][0], r->d_gb2[0][1], r->d_gb2[0][2], r->d_gb2[1][0], r->d_gb2[1][1], r->d_gb2[1][2]};
+   void *ptrs[] = {r->d_table_ring[0], r->d_table_ring[1], r->d_table_ring[2], r->d_table_ring[3], r->d_part_ring[0], r->d_part_ring[1], r->d_part_ring[2], r->d_part_ring[3], r->d_warn, r->d_query, r->d_irr_taps, r->d_rad_steps, r->d_rad_order, r->d_rad_rec, r->d_rad_hist, r->d_scr_cost, r->d_scr_order[0], r->d_scr_order[1], r->d_scr_hist, r->d_fb2[0], r->d_fb2[1], r->d_gb2[0][0], r->d_gb2[0][1], r->d_gb2[0][2], r->d_gb2[1][0], r->d_gb2[1][1], r->d_gb2[1][2]};
    for (void *p : ptrs)
       if (p) (void)hipFree(p);
    for (int q = 0; q < mdh_renderer::NSETS; ++q)
@@ -1213,7 +1243,7 @@ extern "C" int32_t mdh_set_option(mdh_renderer *r, int32_t option, int32_t value
    case MDH_OPT_WORLD: if (value < 1) return seterr(MDH_E_INVALID, "world < 1"); r->opt_world = value; break;
    case MDH_OPT_TIMING: r->opt_timing = value ? 1 : 0; break;
    case MDH_OPT_ADA_EVAL_DIV: r->opt_ada_div = value ? 1 : 0; break;
-   case MDH_OPT_JIT: r->opt_jit = value ? 1 : 0; break;
+   case MDH_OPT_JIT: r->opt_jit = value ? 1 : 0; ++r->march_inputs; break;
    case MDH_OPT_IRRADIANCE_ALL: r->opt_irr_all = value ? 1 : 0; break;
    case MDH_OPT_WINDOW:
       if (value < 0 || value > 2) return seterr(MDH_E_INVALID, "bad value");
@@ -1233,7 +1263,7 @@ extern "C" int32_t mdh_set_option(mdh_renderer *r, int32_t option, int32_t value
    case MDH_OPT_TABLE_RESIDENCY:
       if (value != 0 && value != 1) return seterr(MDH_E_INVALID, "table residency is 0 (by size) or 1 (global, forced)");
       if (r->in_frame) return seterr(MDH_E_STATE, "a frame is open");
-      if (value != r->opt_residency) { r->opt_residency = value; r->table_dirty = true; } // (the next commit lays the table out again)
+      if (value != r->opt_residency) { r->opt_residency = value; r->table_dirty = true; ++r->march_inputs; } // (the next commit lays the table out again)
       break;
    case MDH_OPT_TRIANGLE_BVH: {
       if (value != 0 && value != 1) return seterr(MDH_E_INVALID, "the triangle BVH is 0 (off) or 1 (on)");
@@ -1242,7 +1272,7 @@ extern "C" int32_t mdh_set_option(mdh_renderer *r, int32_t option, int32_t value
       for (int k = 0; k < r->npk; ++k) tri_kinds += r->pk[k].type == PK_TRIANGLE;
       if (value && (r->part.enable != 0 || has_custom_kinds(r) || tri_kinds > 1))
          return seterr(MDH_E_STATE, "MDH_OPT_TRIANGLE_BVH: scenes without a space partition, without user-defined kinds and with one Triangle kind only");
-      if (value != r->opt_tri_bvh) { r->opt_tri_bvh = value; r->table_dirty = true; } // (the next commit lays the table out again)
+      if (value != r->opt_tri_bvh) { r->opt_tri_bvh = value; r->table_dirty = true; ++r->march_inputs; } // (the next commit lays the table out again)
       break;
    }
    case MDH_OPT_RADIANCE_MIPS: {
@@ -1257,6 +1287,19 @@ extern "C" int32_t mdh_set_option(mdh_renderer *r, int32_t option, int32_t value
       }
       break;
    }
+   case MDH_OPT_RADIANCE_REPLAY:
+      r->opt_rad_replay = value ? 1 : 0;
+      if (!r->opt_rad_replay) { // the records are dropped (the buffer itself with the streams drained: never under an open frame)
+         r->rad_rec_valid = false;
+         if (r->d_rad_rec && !r->in_frame) {
+            HIP_TRY(hipSetDevice(r->device));
+            if (r->probe_stream) HIP_TRY(hipStreamSynchronize(r->probe_stream));
+            HIP_TRY(hipStreamSynchronize(r->stream));
+            void *q = r->d_rad_rec; r->d_rad_rec = nullptr; r->rad_rec_cap = 0;
+            HIP_TRY(hipFree(q));
+         }
+      }
+      break;
    default: return seterr(MDH_E_INVALID, "unknown option");
    }
    return MDH_OK;
@@ -1280,6 +1323,7 @@ extern "C" int32_t mdh_get_option(mdh_renderer *r, int32_t option, int32_t *valu
    case MDH_OPT_INDIRECT_SPECULAR: *value = r->opt_spec; break;
    case MDH_OPT_HYSTERESIS_PERMILLE: *value = r->opt_hyst; break;
    case MDH_OPT_RADIANCE_ORDER: *value = r->opt_rad_order; break;
+   case MDH_OPT_RADIANCE_REPLAY: *value = r->opt_rad_replay; break;
    case MDH_OPT_SCREEN_ORDER: *value = r->opt_scr_order; break;
    case MDH_OPT_SCREEN_SPLIT: *value = r->opt_scr_split; break;
    case MDH_OPT_NUMERICS: *value = MDH_FAST_NUMERICS ? 1 : (MDH_HYBRID_NUMERICS ? 2 : 0); break; // 0 exact (shipped), 1 / 2 the labelled experiments
@@ -1730,6 +1774,7 @@ struct PassKernel {
    int mode = 0;    // k_screen: the screen mode, ...
    bool gbuf = false, alt = false; // ... the geometry buffer, the variant of the optional specular bodies
    bool small = false;             // k_radiance: SMALL
+   int rec = 0;                    // k_radiance: REC (0 marches, 1 marches and records, 2 replays the records: rad_replay_pick)
    bool ada_div = false;           // k_eval_distance: MDH_OPT_ADA_DIVISION
    bool jit = false; // a function of the scene's hiprtc module (user-defined kinds under MDH_OPT_JIT), not a kernel of this library
    int pfk = 0;      // the variant by the scene's census, before the pass's own choices, and the power-of-two addressing
@@ -1816,6 +1861,7 @@ extern "C" int32_t mdh_update_partitioning(mdh_renderer *r, int32_t method)
    r->warn_pending = true;
    HIP_TRY(hipEventRecord(r->ev_part, up));
    r->part_stream = up;
+   ++r->march_inputs; // (the partition variants march through the new table: any record of their rays would be stale)
    ++r->part_version;
    r->part_seen[sup] = r->part_version;
    r->part_slot = ns;
@@ -1857,6 +1903,42 @@ static bool room_census(const mdh_renderer *r)
 // MDH_OPT_RADIANCE_MIPS: does the screen pass over atlas set `set` read the levels of its radiance atlas (KProbes::rad_mips)?
 static bool rad_mips_used(const mdh_renderer *r, int set) { return r->opt_mips && r->opt_mode == 0 && r->opt_spec != 0 && r->d_rad_mips[set]; }
 
+// MDH_OPT_RADIANCE_REPLAY.  The variants built with record and replay kernels: the brute-force scan and the census of the rooms,
+// with and without power-of-two atlases (kernel_ptr).  The partition, global-residency / BVH and user-defined-kind variants
+// keep marching.
+#define MDH_RAD_REPLAY_BUILT (MDH_RAD_REPLAY && MDH_RAD_QVIS && MDH_SHARE_FIRST_STEP)
+static bool rad_replay_built(const PassKernel &k) { return MDH_RAD_REPLAY_BUILT && !k.jit && (k.pf & ~(MDH_PF_ROOM | MDH_PF_POW2)) == 0; }
+// everything the marches of this renderer's probe rays read, and the kernel that runs them
+static mdh_renderer::RadRecKey rad_rec_key(const mdh_renderer *r, const PassKernel &k)
+{
+   mdh_renderer::RadRecKey q = {};
+   const KProbes p = make_probes(r);
+   q.geometry = r->geometry_edits; q.inputs = r->march_inputs; q.part_version = r->part_version;
+   q.grid[0] = p.gx; q.grid[1] = p.gy; q.grid[2] = p.gz;
+   q.spacing[0] = p.sx; q.spacing[1] = p.sy; q.spacing[2] = p.sz;
+   q.res[0] = p.rres; q.res[1] = p.ires; q.pc[0] = p.pcx; q.pc[1] = p.pcy;
+   q.probe_begin = p.probe_begin; q.probe_end = p.probe_end;
+   q.rays = (long)(p.probe_end - p.probe_begin) * p.rres * p.rres;
+   q.max_dist = r->ks.max_dist;
+   q.pf = k.pf; q.small = k.small ? 1 : 0; q.jit = k.jit ? 1 : 0; q.residency = r->residency; q.bvh = r->bvh_active ? 1 : 0;
+   q.table_f4 = r->ks.table_f4; q.part_bits_f4 = r->ks.part_bits_f4;
+   return q;
+}
+// The schedule: geometry that changed since the previous radiance pass is marched by the plain kernel; geometry that stood
+// still for one pass is marched once more, by the recording kernel; valid records are replayed.
+static int rad_replay_pick(const mdh_renderer *r, const PassKernel &k)
+{
+   if (!r->opt_rad_replay || !rad_replay_built(k)) return 0;
+   const mdh_renderer::RadRecKey now = rad_rec_key(r, k);
+   if (r->rad_rec_valid && r->d_rad_rec && now == r->rad_rec_key) return 2;
+   // (the recording kernel parks five rows more than the marching one: a table that commit_scene fitted into the workgroup's LDS
+   //  budget beside MDH_PARK_DWORDS rows may not fit beside these -- such a scene keeps marching, and the counters say so)
+   if (r->rad_seen_valid && now == r->rad_seen_key && now.rays > 0 && now.rays < (1l << 31) &&
+       lds_bytes(r) + (size_t)MDH_RECORD_PARK_ROWS * MDH_BLOCK * sizeof(float) <= MDH_LDS_WORKGROUP_BUDGET)
+      return 1;
+   return 0;
+}
+
 static PassKernel pick_kernel(const mdh_renderer *r, int pass, int set)
 {
    PassKernel k;
@@ -1893,6 +1975,7 @@ static PassKernel pick_kernel(const mdh_renderer *r, int pass, int set)
       k.family = GK_k_radiance;
       if (p2) k.pf |= MDH_PF_POW2;
       k.small = rad_small_launch(r);
+      k.rec = rad_replay_pick(r, k);
       break;
    case MDH_PASS_VISIBILITY: k.family = GK_k_visibility; break;
    case MDH_PASS_SCATTERING: k.family = MDH_SCAT_SPLIT ? GK_k_scat_march : GK_k_scattering; break;
@@ -2020,7 +2103,18 @@ static int pass_radiance(PassRun &p)
    }
    if (n <= 0) return MDH_OK;
    // the rays in the order of the previous pass's primary-march lengths (RadOrder, mdh_kernels.h)
-   RadOrder ro = {nullptr, nullptr, (int)rays};
+   RadOrder ro = {nullptr, nullptr, (int)rays, nullptr};
+   // MDH_OPT_RADIANCE_REPLAY: the pass that writes the rays' records, or reads them (pick_kernel chose: p.k.rec)
+   if (p.k.rec == 1 && rays > r->rad_rec_cap) { // (the buffer is only ever used by radiance passes, on the probe stream or the main stream)
+      if (r->probe_stream) HIP_TRY(hipStreamSynchronize(r->probe_stream));
+      HIP_TRY(hipStreamSynchronize(r->stream));
+      r->rad_rec_cap = 0;
+      r->rad_rec_valid = false;
+      { void *q = r->d_rad_rec; r->d_rad_rec = nullptr; if (q) HIP_TRY(hipFree(q)); }
+      HIP_TRY(hipMalloc(&r->d_rad_rec, (size_t)rays * sizeof(RayRecord)));
+      r->rad_rec_cap = rays;
+   }
+   if (p.k.rec) ro.rec = r->d_rad_rec;
    // (chunks of whole workgroup strides, at most MDH_RO_MAX_CHUNKS of them)
    const long ro_chunk = std::max(2048l, ((rays + MDH_RO_MAX_CHUNKS - 1) / MDH_RO_MAX_CHUNKS + 1023) / 1024 * 1024);
    const int ro_chunks = (int)((rays + ro_chunk - 1) / ro_chunk);
@@ -2051,10 +2145,19 @@ static int pass_radiance(PassRun &p)
    }
    n = (n + 63) / 64 * 64;
    const int blocks = (int)((n + MDH_BLOCK - 1) / MDH_BLOCK);
-   const size_t lds = lds_bytes_march(r);
+   const size_t lds = p.k.rec == 2 ? lds_bytes(r) + (size_t)MDH_REPLAY_PARK_ROWS * MDH_BLOCK * sizeof(float)
+                    : p.k.rec == 1 ? lds_bytes(r) + (size_t)MDH_RECORD_PARK_ROWS * MDH_BLOCK * sizeof(float) : lds_bytes_march(r);
    struct Args { KScene sc; KProbes pr; int first_round; RadOrder ro; };
    const int rc = launch_pass<Args>(p, blocks, lds, r->ks, pr, rad_first_round(r, p.kernel, p.fn, lds, blocks), ro);
    if (rc != MDH_OK) return rc;
+   { // what this pass marched through (or replayed), for the next pass's choice
+      const mdh_renderer::RadRecKey now = rad_rec_key(r, p.k);
+      if (p.k.rec == 1) { r->rad_rec_key = now; r->rad_rec_valid = true; }
+      else if (p.k.rec == 0) r->rad_rec_valid = false; // (the geometry moved, the option is off or this variant only marches)
+      r->rad_seen_key = now;
+      r->rad_seen_valid = true;
+      ++r->rad_replay_stats[p.k.rec];
+   }
    if (ro.steps) { // the next pass's order from this pass's step counts
       hipLaunchKernelGGL(k_rad_hist, dim3(ro_chunks), dim3(256), 0, st, (const unsigned char *)r->d_rad_steps, (int)rays, (int)ro_chunk, r->d_rad_hist);
       hipLaunchKernelGGL(k_rad_scan, dim3(1), dim3(256), 0, st, r->d_rad_hist, ro_chunks);
@@ -3310,6 +3413,15 @@ extern "C" int32_t mdh_diag_bvh(unsigned long long *out2)
 }
 #endif
 
+// MDH_OPT_RADIANCE_REPLAY: radiance passes launched since creation that marched, marched and recorded, replayed
+extern "C" int32_t mdh_radiance_replay_stats(mdh_renderer *r, int64_t *plain, int64_t *recording, int64_t *replaying)
+{
+   if (!r) return seterr(MDH_E_INVALID, "null renderer");
+   if (plain) *plain = r->rad_replay_stats[0];
+   if (recording) *recording = r->rad_replay_stats[1];
+   if (replaying) *replaying = r->rad_replay_stats[2];
+   return MDH_OK;
+}
 extern "C" int32_t mdh_pass_time(mdh_renderer *r, int32_t pass, double *ms, int64_t *launches)
 {
    if (!r || pass < 0 || pass >= MDH_PASS_COUNT) return seterr(MDH_E_INVALID, "bad argument");
@@ -3496,7 +3608,10 @@ extern "C" int32_t mdh_diag_waves(unsigned long long *out, int32_t n_waves)
 static const void *kernel_ptr(const PassKernel &k)
 {
 #define MDH_K(FAMILY, PF, ...) if (k.family == GK_##FAMILY && k.pf == (PF)) return (const void *)(__VA_ARGS__);
-#define MDH_RAD(PF) MDH_K(k_radiance, PF, k.small ? k_radiance<PF, true> : k_radiance<PF, false>)
+#define MDH_RAD(PF) if (k.family == GK_k_radiance && k.pf == (PF) && k.rec == 0) return (const void *)(k.small ? k_radiance<PF, true> : k_radiance<PF, false>);
+// (MDH_OPT_RADIANCE_REPLAY: the recording and the replaying kernel of a variant, behind everything older)
+#define MDH_RAD_REC(PF) if (k.family == GK_k_radiance && k.pf == (PF) && k.rec == 1) return (const void *)(k.small ? k_radiance<PF, true, 1> : k_radiance<PF, false, 1>); \
+                        if (k.family == GK_k_radiance && k.pf == (PF) && k.rec == 2) return (const void *)(k.small ? k_radiance<PF, true, 2> : k_radiance<PF, false, 2>);
 #define MDH_VIS(PF) MDH_K(k_visibility, PF, k_visibility<PF>)
 #if MDH_SCAT_SPLIT
 #define MDH_SCAT(PF) MDH_K(k_scat_march, PF, k_scat_march<PF>)
@@ -3524,9 +3639,13 @@ static const void *kernel_ptr(const PassKernel &k)
    MDH_GTAB(73) MDH_GTAB(64)
    MDH_GTAB(192) // MDH_PF_GTAB | MDH_PF_BVH: the newest last, so that nothing older moves
    MDH_K(k_eval_distance, MDH_PF_GTAB | MDH_PF_BVH, k_eval_distance_bvh<>)
+#if MDH_RAD_REPLAY_BUILT
+   MDH_RAD_REC(20) MDH_RAD_REC(16) MDH_RAD_REC(4) MDH_RAD_REC(0)
+#endif
    return nullptr;
 #undef MDH_K
 #undef MDH_RAD
+#undef MDH_RAD_REC
 #undef MDH_VIS
 #undef MDH_SCAT
 #undef MDH_SCR

@@ -266,6 +266,9 @@ struct RadOrder {
    const unsigned *order; // [n_rays] ray at every place, or nullptr: rays in probe order
    unsigned char *steps;  // [n_rays] every ray's sort key (rad_level of its primary-march and shadow steps), written by the pass; or nullptr
    int n_rays;
+   // MDH_OPT_RADIANCE_REPLAY (mdh_march.h: RayRecord): [n_rays] the rays' records, written by k_radiance<.., 1>, read by
+   // k_radiance<.., 2>, indexed by the ray; nullptr for the kernel that only marches
+   RayRecord *rec;
    // Every wavefront is full, also in launches that leave most wavefront slots of the chip empty.  (measured, rank 0's radiance
    // slice of an 8-way sharded frame, 1 024 full wavefronts on 1 024 SIMDs: 0.094 ms full, 0.096 ms half filled, 0.125 ms quarter
    // filled, profiles/r03_x_radiance_partial_fill.log -- the rays are sorted by their march lengths already, so a wavefront's
@@ -317,8 +320,13 @@ MDH_DEV void radiance_texel(const KProbes &pr, const RadOrder &ro, long lin, int
 // The pass is ONE kernel.  (measured: as two -- every ray's marches, hit point and direct light into per-ray records at eight
 // wavefronts per SIMD, then the probe visibility queue, the irradiance taps and the store from the records -- 0.180 instead of
 // 0.125 ms)
-template <int PART, bool SMALL = false> __global__ __launch_bounds__(MDH_BLOCK, MDH_OCC_RAD(PART, SMALL)) void k_radiance(KScene sc, KProbes pr, int first_round, RadOrder ro)
+// REC: 0 = the pass as it marches, 1 = the same and every real ray's RayRecord stored, 2 = the pass from the records (lanes
+// past the ray count, in a launch padded to whole wavefronts and probe groups, read and write none).  The replaying kernel
+// is built for the register budget of the marching one (measured: DESIGN.md section 4, item 11) and takes
+// MDH_REPLAY_PARK_ROWS rows of LDS instead of MDH_PARK_DWORDS.
+template <int PART, bool SMALL = false, int REC = 0> __global__ __launch_bounds__(MDH_BLOCK, MDH_OCC_RAD(PART, SMALL)) void k_radiance(KScene sc, KProbes pr, int first_round, RadOrder ro)
 {
+   static_assert(REC == 0 || (MDH_RAD_REPLAY && MDH_RAD_QVIS && MDH_SHARE_FIRST_STEP), "the records hold the queue's bits and the shared first step");
    if (first_round > 0 && (int)blockIdx.x >= first_round) __builtin_amdgcn_s_setprio(3);
    stage_table(sc);
    f3 c;
@@ -344,7 +352,13 @@ template <int PART, bool SMALL = false> __global__ __launch_bounds__(MDH_BLOCK, 
       cfg.ao_steps = 0;
       bool hit;
       f3 pos;
-      c = MDH_SHADE<PART, 0, 0, MDH_RAD_QVIS != 0>(sc, pr, cfg, valid, world, ray_dir, ph, hit, pos);
+      if (REC == 2) {
+         RayRecord rec = {0u, 0u, -1, 0u};
+         if (valid) rec = ro.rec[(size_t)(probe_raw - pr.probe_begin) * (pr.rres * pr.rres) + y * pr.rres + x];
+         c = MDH_SHADE<PART, 0, 0, true, 2>(sc, pr, cfg, valid, world, ray_dir, ph, hit, pos, rec);
+      } else
+      c = MDH_SHADE<PART, 0, 0, MDH_RAD_QVIS != 0, REC>(sc, pr, cfg, valid, world, ray_dir, ph, hit, pos);
+      if (REC == 1) ph.index = hit ? 1 : 0; // (the one bit of the record that must stay live: in the register of the arg-min, which the pass does not use)
    }
    // The texel again: nothing of the prologue stays live across the pixel program (its coordinates, the order's entry and
    // the arguments the store needs were eleven dwords that the seven-wavefront build kept in scratch memory).  The lane
@@ -379,6 +393,19 @@ template <int PART, bool SMALL = false> __global__ __launch_bounds__(MDH_BLOCK, 
          atlas_store(pr2.rad, pr2.fmt, atlas_index(pr2.pcx, pr2.rres, pr2.rshift, i, j), c);
          if (ro2.steps) // the ray's sort key: the levels of its primary-march and soft-shadow step counts
             ro2.steps[(size_t)(probe_raw - pr2.probe_begin) * (pr2.rres * pr2.rres) + y * pr2.rres + x] = (unsigned char)((rad_level(ph.steps & 0xffff) << 4) | rad_level(ph.steps >> 16));
+         if (REC == 1) { // the ray's record: its parked parts (a miss parked its steps only)
+            float *pk = (float *)(s_tab + ka->sc.table_f4 + ka->sc.part_bits_f4); // (park_base, from the argument segment)
+            const int wb = park_wave_base(pk);
+            RayRecord rec = {0u, 0u, -1, 0u};
+            int vis = 0;
+            if (ph.index) {
+               const f3 v = park_load3<MDH_PARK_REC>(pk, wb);
+               rec.t = (unsigned)__float_as_int(v.x); rec.index = __float_as_int(v.y); rec.sd0 = (unsigned)__float_as_int(v.z);
+               vis = __float_as_int(park_load1<MDH_PARK_REC + 3>(pk, wb));
+            }
+            rec.word = ray_record_word(ph.index != 0, __float_as_int(park_load1<MDH_PARK_REC + 4>(pk, wb)), vis);
+            ro2.rec[(size_t)(probe_raw - pr2.probe_begin) * (pr2.rres * pr2.rres) + y * pr2.rres + x] = rec;
+         }
       }
    }
    PH_KERNEL_END();

@@ -126,6 +126,13 @@ template <int PART> MDH_DEV bool march_plain(const KScene &sc, f3 o, f3 d, float
 // before the irradiance is parked
 #define MDH_PARK_SPEC 15
 #define MDH_PARK_MAT 18
+// the radiance pass's kernel that replays its rays' records (RayRecord below) runs no visibility queue: its material id waits in
+// row 15, behind the irradiance, and the workgroup takes 16 rows
+#define MDH_PARK_MAT_REPLAY 15
+#define MDH_REPLAY_PARK_ROWS 16
+// ... and the one that writes them parks what the record holds in five rows of its own (read back by the kernel's store)
+#define MDH_PARK_REC 19 // t, arg-min index, first step, visibility bits, the primary march's steps
+#define MDH_RECORD_PARK_ROWS 24
 // mode 2 (direct light and occlusion only: no probes, no reflection) parks P, N, view direction, direct light and the
 // material id: 13 rows, so that eight of its workgroups fit a CU's LDS
 #define MDH_PARK_MAT_DIRECT 12
@@ -385,20 +392,56 @@ MDH_DEV KProbes probes_fresh(const KProbes &pr)
    return r;
 }
 
+// ---------------------------------------------------------------------------------------------
+// RayRecord -- what a probe ray's marches find, which follows from the scene's geometry alone (MDH_OPT_RADIANCE_REPLAY,
+// DESIGN.md section 4, "Exact work elimination", item 11).  A probe ray starts at a fixed probe in a fixed octahedral
+// direction: whether it hits, where (t), which primitive is nearest there (sdf_info's arg-min), how many steps it took,
+// the first-step distance sd0 at the hit point's offset and the visibility of the hit point's eight cage probes do not
+// change with lights, materials or atlases.  The pass that follows a pass over the same geometry writes one record per ray
+// (REC = 1), the passes behind it read it back (REC = 2) and feed the same values into the same operations: P = ro + rd * t,
+// primitive_info, the light loop with its shadow rays, the eight taps.  16 bytes, indexed by the RAY (probe of the slice *
+// texels + texel), never by the lane: RadOrder moves rays between lanes.
+// ---------------------------------------------------------------------------------------------
+#ifndef MDH_RAD_REPLAY
+#if defined(MDH_DIAG) || defined(MDH_PHASES)
+#define MDH_RAD_REPLAY 0 // (the diagnostic builds count or time the work of the marches: they keep marching)
+#else
+#define MDH_RAD_REPLAY 1
+#endif
+#endif
+#if MDH_RAD_REPLAY && defined(MDH_PHASES)
+#error "MDH_PHASES keeps its accumulators in park row 19 (MDH_PH_SLOT): the recording kernel's rows start there and the replaying kernel allocates 16 rows -- build the phase timers with MDH_RAD_REPLAY=0"
+#endif
+struct RayRecord {
+   unsigned t;     // the primary march's t, bit for bit
+   unsigned sd0;   // sdf at P + 5 MIN_STEP N, bit for bit
+   int index;      // sdf_info's arg-min at P
+   unsigned word;  // bits 0-22 the primary march's steps, 23-30 queued_visibility's bits, 31 hit
+};
+static_assert(sizeof(RayRecord) == 16, "one 16-byte store per ray");
+#define MDH_REC_STEPS_MASK 0x7fffffu
+MDH_DEV unsigned ray_record_word(bool hit, int steps, int vis_bits)
+{
+   return min((unsigned)steps, MDH_REC_STEPS_MASK) | ((unsigned)(vis_bits & 255) << 23) | (hit ? 0x80000000u : 0u);
+}
+
 // SPEC: 0 = no second point (the radiance pass), 1 = the reflection as the reference's renderer fixes it
 // (M_COMPUTE_INDIRECT_SPECULAR = 2, or none), 2 = the kernel variant that holds the two other bodies of
 // render_probes.glsl:264-272 (cfg.spec_mode 1 or 3; MDH_OPT_INDIRECT_SPECULAR)
-template <int PART, int MODE, int SPEC, bool QVIS>
+// REC (the radiance pass with the queue only): 0 = march, 1 = march and park what a RayRecord holds (rows MDH_PARK_REC ..)
+// for the kernel's store, 2 = take the record `rec` instead of the primary march, the arg-min scan, the first step and the queue
+template <int PART, int MODE, int SPEC, bool QVIS, int REC = 0>
 MDH_DEV f3 shade_structured(const KScene &sc, const KProbes &pr, const MachineCfg cfg, bool lane_valid, f3 from, f3 dir_in,
-                            PrimaryHit &ph, bool &hit, f3 &pos_out)
+                            PrimaryHit &ph, bool &hit, f3 &pos_out, const RayRecord rec = RayRecord{0u, 0u, -1, 0u})
 {
+   static_assert(REC == 0 || (SPEC == 0 && QVIS && MODE == 0), "records are of the radiance pass's rays");
    constexpr bool P2 = (PART & MDH_PF_POW2) != 0;
    constexpr bool REFLECT = SPEC != 0 && MODE == 0; // (modes 1 and 2 never shade a second point: no loop, and nothing kept for one)
    // The cage-corner loop unrolled where the registers allow it (the brute-force screen kernel of the reference's fixed mode:
    // 96 VGPRs with and without; the partition variants and the one for the optional specular modes would spill 80 - 200 bytes
    // per lane, the radiance kernel gains nothing): constant corner bits, no loop branch, the x-twin's terms at hand.
    constexpr int CORNER_UNROLL = ((PART & MDH_PF_PART) || SPEC != 1 || QVIS) ? 1 : MDH_CORNER_UNROLL;
-   constexpr int PARK_MAT = MODE == 2 ? MDH_PARK_MAT_DIRECT : MDH_PARK_MAT; // (no probe rows in mode 2: MDH_DIRECT_PARK_ROWS)
+   constexpr int PARK_MAT = MODE == 2 ? MDH_PARK_MAT_DIRECT : REC == 2 ? MDH_PARK_MAT_REPLAY : MDH_PARK_MAT; // (no probe rows in mode 2: MDH_DIRECT_PARK_ROWS)
    // the irradiance tap of a cage corner issued before its visibility march (its loads land during the march) -- not in the
    // space-partition variants, whose march needs the registers
    constexpr bool TAP_EARLY = !(PART & MDH_PF_PART);
@@ -432,7 +475,14 @@ MDH_DEV f3 shade_structured(const KScene &sc, const KProbes &pr, const MachineCf
          float t;
          int steps;
          PH_T0(pt);
-         const bool h = march_plain<PART>(sc, ro, rd, sc.max_dist, t, steps);
+         bool h;
+         if (REC == 2) { // the march's three results as recorded
+            h = (rec.word >> 31) != 0u;
+            t = __int_as_float((int)rec.t);
+            steps = (int)(rec.word & MDH_REC_STEPS_MASK);
+         } else
+         h = march_plain<PART>(sc, ro, rd, sc.max_dist, t, steps);
+         if (REC == 1) park_store1<MDH_PARK_REC + 4>(pk, wb, __int_as_float(steps)); // (hit or miss: the sort key needs them)
          PH_ADD(pt, 0);
          if (ctx == 0) { hit = h; ph.steps = steps; }
          active = false; // a miss ends the chain (ctx 1: specular_col stays 0, render_probes.glsl:142-144)
@@ -449,6 +499,8 @@ MDH_DEV f3 shade_structured(const KScene &sc, const KProbes &pr, const MachineCf
             f3 N;
             int pm;
             MDH_WORK(3);
+            if (REC == 2) index = rec.index;
+            else
             (void)sdf_info<PART>(sc, P, index);
             primitive_info<(PART & MDH_PF_CUSTOM) != 0, (PART & MDH_PF_GTAB) != 0>(sc, index, P, N, pm);
             if (ctx == 0) {
@@ -466,7 +518,10 @@ MDH_DEV f3 shade_structured(const KScene &sc, const KProbes &pr, const MachineCf
                // Every shadow and probe-visibility ray of this point starts AT from_off with t = 0, so
                // their first SDF evaluation is at the same position (from_off + dir * 0): it is done
                // once here and each ray replays its first iteration with this value.
-               const float sd0 = MDH_SHARE_FIRST_STEP ? sdf<PART>(sc, from_off) : 0.0f;
+               const float sd0 = REC == 2 ? __int_as_float((int)rec.sd0) : MDH_SHARE_FIRST_STEP ? sdf<PART>(sc, from_off) : 0.0f;
+               if (REC == 1) { // (t and the arg-min are dead from here on, the first step behind the queue: nothing more stays live for the record)
+                  park_store3<MDH_PARK_REC>(pk, wb, F3(t, __int_as_float(index), sd0));
+               }
                // ---- compute_direct_lighting (lighting.glsl:1-40) at P, seen along rd
                f3 Lo = F3(0.0f, 0.0f, 0.0f);
 #pragma unroll 1
@@ -536,8 +591,11 @@ MDH_DEV f3 shade_structured(const KScene &sc, const KProbes &pr, const MachineCf
                                ((gp.z < 0 || gp.z >= pg.gz - 1) ? 4 : 0);
                   int vis_bits = 0; // bit i: visibility of corner i
                   PH_ADD(pt, 2);
+                  if (REC == 2) vis_bits = (int)((rec.word >> 23) & 255u); // (P, N, the cage cell and its folds are still in registers)
+                  else
                   if (QVIS && ctx == 0) {
                      vis_bits = queued_visibility<PART>(sc, pr, pk, P, N, gp, folded, sd0);
+                     if (REC == 1) park_store1<MDH_PARK_REC + 3>(pk, wb, __int_as_float(vis_bits));
                      // Nothing of the point stays in registers across the queue (it is the pass's longest loop, and the
                      // kernel is built for seven wavefronts per SIMD: what stayed live -- P, N, the cage cell, twenty dwords
                      // -- went to scratch and back, 45 MB per launch at BASELINE config 3).  P and N wait in their park rows,
