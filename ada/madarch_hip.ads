@@ -135,6 +135,9 @@ package Madarch_HIP is
    --  Opt_Radiance_Replay: 1 (default) = probe rays' hits and cage visibility are replayed from
    --  per-ray records while the scene's geometry stands still (the same bits), 0 = marched every pass.
    Opt_Radiance_Replay : constant int := 21;
+   --  Opt_Screen_Replay: 1 = the screen pass's hits and cage visibility are replayed from per-pixel
+   --  records while camera and geometry stand still (the same bits), 0 (default) = marched every pass.
+   Opt_Screen_Replay : constant int := 22;
 
    function Set_Option (R : Handle; Option, Value : int) return Status
      with Import, Convention => C, External_Name => "mdh_set_option";

@@ -291,7 +291,21 @@ enum {
     * on end it: the next pass marches, the one after records again.  The brute-force and room-census kernels replay; scenes
     * with a space partition, user-defined kinds or global residency keep marching ("Exact work
     * elimination", item 11).  0 = march every pass; the records are dropped.  mdh_radiance_replay_stats counts the passes. */
-   MDH_OPT_RADIANCE_REPLAY = 21
+   MDH_OPT_RADIANCE_REPLAY = 21,
+   /* 1 = the screen pass's marches are not run again while camera and geometry stand still -- no effect on any pixel; 0
+    * (default) = marched every pass.  A pixel's primary hit, its reflection ray's hit, the nearest primitive at both, the
+    * first step and the eight cage-visibility bits of both shaded points and the occlusion term follow from the camera ray,
+    * the geometry and the probe grid alone.  The first screen pass over an unchanged camera and scene writes them to a
+    * 32-byte record per pixel; later passes read the records and compute only what lights, materials and the atlases
+    * change (direct light with its shadow rays, the taps, the combine, volumetrics), from the same values with the same
+    * operations: framebuffer, window pixels, geometry buffer and atlases keep every bit.  A camera setter with a new
+    * value, Set_Primitive, Add_Primitive, Update_Partitioning, a material in use that goes below the reflection's roughness threshold
+    * and every option that a screen march or the pixels' places depend on end it: the next pass marches, the one after
+    * records again.  The fixed mode (MDH_OPT_SCREEN_MODE 0, MDH_OPT_INDIRECT_SPECULAR 0 or 2 without mips) of scenes
+    * without a space partition, user-defined kinds or global residency replays; everything
+    * else keeps marching ("Exact work elimination", item 12).  0 drops the records.
+    * mdh_screen_replay_stats counts the passes. */
+   MDH_OPT_SCREEN_REPLAY = 22
 };
 
 /* passes of Renderers.Render (madarch-renderers.adb:302-321) */
@@ -500,6 +514,10 @@ int32_t mdh_pass_time(mdh_renderer *r, int32_t pass, double *total_ms, int64_t *
 /* MDH_OPT_RADIANCE_REPLAY: the radiance passes launched since mdh_create that marched their rays (`plain`), marched them
  * and wrote the rays' records (`recording`), and read the records instead of marching (`replaying`).  Any pointer may be null. */
 int32_t mdh_radiance_replay_stats(mdh_renderer *r, int64_t *plain, int64_t *recording, int64_t *replaying);
+/* MDH_OPT_SCREEN_REPLAY: the same count of the screen passes.  Any pointer may be null. */
+int32_t mdh_screen_replay_stats(mdh_renderer *r, int64_t *plain, int64_t *recording, int64_t *replaying);
+/* ... and the bytes of one pixel's record (32) */
+int32_t mdh_screen_record_bytes(void);
 int32_t mdh_reset_pass_times(mdh_renderer *r);
 
 /* std140 layout queries = Scenes.Get_Primitives_Location / Get_Lights_Location

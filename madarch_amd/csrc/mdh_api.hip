@@ -392,6 +392,34 @@ struct mdh_renderer {
    unsigned long march_inputs = 0;         // edits besides geometry_edits that change what a march kernel reads or which one runs (options, partition builds)
    long long rad_replay_stats[3] = {0, 0, 0}; // radiance passes launched marching, recording, replaying
    int opt_rad_replay = 1;
+   // MDH_OPT_SCREEN_REPLAY (mdh_march.h: PixelRecord): one record per pixel of the rank's tiles, indexed by the pixel
+   // (mdh_kernels.h: screen_record_index).  ONE buffer: a record holds nothing of an atlas, a framebuffer or a light.  Screen
+   // passes of frames in flight alternate between the main and the alternate stream and nothing else orders them against each
+   // other, so the buffer carries its own order: every pass that reads it leaves an event on its stream (ev_scr_rec_read), the
+   // pass that writes it waits for the readers on the other streams and leaves ev_scr_rec_write, and a reader on a stream that
+   // has not seen the latest write waits for that event.  Allocated, grown and freed with every stream drained.
+   PixelRecord *d_scr_rec = nullptr;
+   long scr_rec_cap = 0;                   // pixels (own tiles * 64) the buffer is sized for
+   hipEvent_t ev_scr_rec_write = nullptr, ev_scr_rec_read[NSTREAMS] = {nullptr, nullptr, nullptr, nullptr, nullptr};
+   bool scr_rec_read_pending[NSTREAMS] = {false, false, false, false, false};
+   unsigned long long scr_rec_version = 0, scr_rec_seen[NSTREAMS] = {0, 0, 0, 0, 0};
+   struct ScrRecKey {                      // everything a screen march reads, and what decides which pixel holds what (scr_rec_key)
+      RadRecKey march;                     // geometry, probe grid, max_dist, table layout, residency, BVH, JIT, the kernel's variant word
+      float cam[12];                       // position and orientation BY VALUE: setting the camera to where it is changes nothing
+      int W, H, rank, world, mode, spec, ao, gbuffer, window, split;
+      unsigned long reflect_edits;         // Set_Material calls that took a material in use below the reflection's roughness threshold
+      bool operator==(const ScrRecKey &o) const
+      {
+         return march == o.march && memcmp(cam, o.cam, sizeof cam) == 0 && W == o.W && H == o.H && rank == o.rank && world == o.world && mode == o.mode &&
+                spec == o.spec && ao == o.ao && gbuffer == o.gbuffer && window == o.window && split == o.split && reflect_edits == o.reflect_edits;
+      }
+   };
+   ScrRecKey scr_rec_key, scr_seen_key;    // what the records are of / what the previous screen pass marched through
+   bool scr_rec_valid = false, scr_seen_valid = false;
+   unsigned long reflect_edits = 0;
+   bool scr_rec_no_memory = false;         // the records' allocation failed: no further attempt until the key or the option changes
+   long long scr_replay_stats[3] = {0, 0, 0}; // screen passes launched marching, recording, replaying
+   int opt_scr_replay = 0;
    // MDH_OPT_SCREEN_ORDER (ScreenArgs, mdh_kernels.h): the screen pass's tiles in the order of their wavefronts' durations
    unsigned char *d_scr_cost = nullptr;          // [tiles] sort keys, written by the pass that is followed by a sort
    unsigned *d_scr_order[2] = {nullptr, nullptr}; // [tiles] two buffers: passes in flight keep reading the one they were launched with
@@ -1046,7 +1074,7 @@ extern "C" int32_t mdh_destroy(mdh_renderer *r)
    if (r->comm) { ncclComm_t c = r->comm; r->comm = nullptr; (void)rccl_api_destroy(c); }
    if (r->d_comm_scratch) (void)hipFree(r->d_comm_scratch);
    peer_drop(r);
-   void *ptrs[] = {r->d_table_ring[0], r->d_table_ring[1], r->d_table_ring[2], r->d_table_ring[3], r->d_part_ring[0], r->d_part_ring[1], r->d_part_ring[2], r->d_part_ring[3], r->d_warn, r->d_query, r->d_irr_taps, r->d_rad_steps, r->d_rad_order, r->d_rad_rec, r->d_rad_hist, r->d_scr_cost, r->d_scr_order[0], r->d_scr_order[1], r->d_scr_hist, r->d_fb2[0], r->d_fb2[1], r->d_gb2[0][0], r->d_gb2[0][1], r->d_gb2[0][2], r->d_gb2[1][0], r->d_gb2[1][1], r->d_gb2[1][2]};
+   void *ptrs[] = {r->d_table_ring[0], r->d_table_ring[1], r->d_table_ring[2], r->d_table_ring[3], r->d_part_ring[0], r->d_part_ring[1], r->d_part_ring[2], r->d_part_ring[3], r->d_warn, r->d_query, r->d_irr_taps, r->d_rad_steps, r->d_rad_order, r->d_rad_rec, r->d_scr_rec, r->d_rad_hist, r->d_scr_cost, r->d_scr_order[0], r->d_scr_order[1], r->d_scr_hist, r->d_fb2[0], r->d_fb2[1], r->d_gb2[0][0], r->d_gb2[0][1], r->d_gb2[0][2], r->d_gb2[1][0], r->d_gb2[1][1], r->d_gb2[1][2]};
    for (void *p : ptrs)
       if (p) (void)hipFree(p);
    for (int q = 0; q < mdh_renderer::NSETS; ++q)
@@ -1069,6 +1097,9 @@ extern "C" int32_t mdh_destroy(mdh_renderer *r)
          if (r->part_done[q][si]) (void)hipEventDestroy(r->part_done[q][si]);
    if (r->ev_scr_sort) (void)hipEventDestroy(r->ev_scr_sort);
    if (r->ev_scr_other) (void)hipEventDestroy(r->ev_scr_other);
+   if (r->ev_scr_rec_write) (void)hipEventDestroy(r->ev_scr_rec_write);
+   for (hipEvent_t e : r->ev_scr_rec_read)
+      if (e) (void)hipEventDestroy(e);
    if (r->ev_part) (void)hipEventDestroy(r->ev_part);
    if (r->ev_warn) (void)hipEventDestroy(r->ev_warn);
    if (r->h_warn) (void)hipHostFree(r->h_warn);
@@ -1300,6 +1331,22 @@ extern "C" int32_t mdh_set_option(mdh_renderer *r, int32_t option, int32_t value
          }
       }
       break;
+   case MDH_OPT_SCREEN_REPLAY:
+      r->opt_scr_replay = value ? 1 : 0;
+      r->scr_rec_no_memory = false;
+      if (!r->opt_scr_replay) { // the records are dropped (the buffer itself with the streams drained: never under an open frame)
+         r->scr_rec_valid = false;
+         r->scr_seen_valid = false;
+         if (r->d_scr_rec && !r->in_frame) {
+            HIP_TRY(hipSetDevice(r->device));
+            int drc = drain_streams(r);
+            if (drc != MDH_OK) return drc;
+            void *q = r->d_scr_rec; r->d_scr_rec = nullptr; r->scr_rec_cap = 0;
+            for (bool &b : r->scr_rec_read_pending) b = false;
+            HIP_TRY(hipFree(q));
+         }
+      }
+      break;
    default: return seterr(MDH_E_INVALID, "unknown option");
    }
    return MDH_OK;
@@ -1324,6 +1371,7 @@ extern "C" int32_t mdh_get_option(mdh_renderer *r, int32_t option, int32_t *valu
    case MDH_OPT_HYSTERESIS_PERMILLE: *value = r->opt_hyst; break;
    case MDH_OPT_RADIANCE_ORDER: *value = r->opt_rad_order; break;
    case MDH_OPT_RADIANCE_REPLAY: *value = r->opt_rad_replay; break;
+   case MDH_OPT_SCREEN_REPLAY: *value = r->opt_scr_replay; break;
    case MDH_OPT_SCREEN_ORDER: *value = r->opt_scr_order; break;
    case MDH_OPT_SCREEN_SPLIT: *value = r->opt_scr_split; break;
    case MDH_OPT_NUMERICS: *value = MDH_FAST_NUMERICS ? 1 : (MDH_HYBRID_NUMERICS ? 2 : 0); break; // 0 exact (shipped), 1 / 2 the labelled experiments
@@ -1349,6 +1397,14 @@ extern "C" int32_t mdh_set_material(mdh_renderer *r, int32_t id0, const float al
    if (!r || !albedo) return seterr(MDH_E_INVALID, "bad argument");
    if (id0 < 0 || id0 >= MAX_MATERIALS) return seterr(MDH_E_INDEX, "material index out of range");
    uint8_t *p = r->materials_ubo + 16 + 32 * id0;
+   { // MDH_OPT_SCREEN_REPLAY: a pixel's reflection ray is traced when its material's roughness is below 0.75
+     // (render_probes.glsl:262).  The replaying kernel tests the live roughness as the marching one does and traces only
+     // what the record also traced: a material that turns rough switches its reflections off in both kernels alike, a
+     // material in use that turns smooth needs rays no record holds and ends the replay.  Any other edit of it does not.
+      float was;
+      memcpy(&was, p + 16, 4);
+      if (id0 < r->last_material_index && !(was < 0.75f) && roughness < 0.75f) ++r->reflect_edits;
+   }
    memcpy(p, albedo, 12);
    memcpy(p + 12, &metallic, 4);
    memcpy(p + 16, &roughness, 4);
@@ -1774,7 +1830,7 @@ struct PassKernel {
    int mode = 0;    // k_screen: the screen mode, ...
    bool gbuf = false, alt = false; // ... the geometry buffer, the variant of the optional specular bodies
    bool small = false;             // k_radiance: SMALL
-   int rec = 0;                    // k_radiance: REC (0 marches, 1 marches and records, 2 replays the records: rad_replay_pick)
+   int rec = 0;                    // k_radiance, k_screen: REC (0 marches, 1 marches and records, 2 replays the records: rad_replay_pick, scr_replay_pick)
    bool ada_div = false;           // k_eval_distance: MDH_OPT_ADA_DIVISION
    bool jit = false; // a function of the scene's hiprtc module (user-defined kinds under MDH_OPT_JIT), not a kernel of this library
    int pfk = 0;      // the variant by the scene's census, before the pass's own choices, and the power-of-two addressing
@@ -1939,6 +1995,55 @@ static int rad_replay_pick(const mdh_renderer *r, const PassKernel &k)
    return 0;
 }
 
+// MDH_OPT_SCREEN_REPLAY ("Exact work elimination", item 12).  The variants built with record and replay
+// kernels: the fixed mode (mode 0, no optional specular body) over the brute-force scan and the census of the rooms, for
+// and without power-of-two atlases, with and without the geometry buffer (kernel_ptr: sixteen kernels; the build time is in
+// DESIGN.md).  Everything else keeps marching.
+#define MDH_SCR_REPLAY_BUILT (MDH_SCR_REPLAY && MDH_SHARE_FIRST_STEP && MDH_REUSE_FOLDED)
+static bool scr_replay_built(const PassKernel &k) { return MDH_SCR_REPLAY_BUILT && !k.jit && k.mode == 0 && !k.alt && (k.pf & ~(MDH_PF_ROOM | MDH_PF_POW2)) == 0; }
+// What the key holds, and what every entry point does to it:
+//   mdh_set_primitive, mdh_add_primitive                 geometry_edits                       end the replay
+//   mdh_update_partitioning, MDH_OPT_JIT, _TABLE_RESIDENCY, _TRIANGLE_BVH   march_inputs / part_version   end it (and pick a variant that only marches)
+//   mdh_set_camera_position / _orientation               cam, by value                        a new value ends it, the held value does not
+//   MDH_OPT_RANK, _WORLD, _SCREEN_MODE, _INDIRECT_SPECULAR, _AO_STEPS, _GBUFFER, _WINDOW, _SCREEN_SPLIT   by value   a new value ends it
+//   mdh_set_material                                     reflect_edits                        only when a material in use goes below roughness 0.75
+//   mdh_add_material, mdh_set_light, mdh_write_texture, mdh_write_atlas_slice, MDH_OPT_ATLAS_FORMAT, _HYSTERESIS_PERMILLE,
+//   _SCREEN_ORDER, _FRAME_OVERLAP, _TIMING, _RADIANCE_*   nothing: a record holds nothing they change
+// (width, height, probe grid, spacing, resolutions and max_dist are fixed at mdh_create; the key holds them all the same)
+static mdh_renderer::ScrRecKey scr_rec_key(const mdh_renderer *r, const PassKernel &k)
+{
+   mdh_renderer::ScrRecKey q = {};
+   q.march = rad_rec_key(r, k);
+   q.march.small = k.gbuf ? 1 : 0; // (k_radiance's SMALL has no meaning here: the kernel's other template argument)
+   q.march.probe_begin = q.march.probe_end = 0; q.march.rays = 0; // (the radiance pass's slice: a screen march reads every probe's place, none of its rays)
+   memcpy(q.cam, r->cam_pos, 12); memcpy(q.cam + 3, r->cam_m, 36);
+   q.W = r->W; q.H = r->H; q.rank = r->opt_rank; q.world = r->opt_world;
+   q.mode = r->opt_mode; q.spec = r->opt_spec; q.ao = r->opt_ao; q.gbuffer = r->opt_gbuffer; q.window = r->opt_window; q.split = r->opt_scr_split;
+   q.reflect_edits = r->reflect_edits;
+   return q;
+}
+static long scr_rec_pixels(const mdh_renderer *r)
+{
+   const long tiles = (long)((r->W + 7) / 8) * ((r->H + 7) / 8);
+   return r->opt_rank < r->opt_world ? (tiles - r->opt_rank + r->opt_world - 1) / r->opt_world * 64 : 0;
+}
+// The schedule: what changed since the previous screen pass is marched by the plain kernel; what stood still for one pass is
+// marched once more, by the recording kernel; valid records are replayed.
+static int scr_replay_pick(const mdh_renderer *r, const PassKernel &k)
+{
+   if (!r->opt_scr_replay || !scr_replay_built(k)) return 0;
+   const mdh_renderer::ScrRecKey now = scr_rec_key(r, k);
+   if (r->scr_rec_valid && r->d_scr_rec && now == r->scr_rec_key) return 2;
+   if (r->scr_rec_no_memory && r->scr_seen_valid && now == r->scr_seen_key) return 0; // (the allocation failed for this key: not tried again, and no stream drained, in every frame)
+   // (the recording kernel parks eleven rows more than the marching one: a table that commit_scene fitted into the workgroup's
+   //  LDS budget beside MDH_PARK_DWORDS rows may not fit beside these -- such a scene keeps marching, and the counters say so;
+   //  the second point's arg-min index shares a word: tables of 2^22 entries and more keep marching too)
+   if (r->scr_seen_valid && now == r->scr_seen_key && scr_rec_pixels(r) > 0 && r->ks.table_f4 < (int)MDH_REC2_INDEX_MASK &&
+       lds_bytes(r) + (size_t)MDH_SCR_RECORD_PARK_ROWS * MDH_BLOCK * sizeof(float) <= MDH_LDS_WORKGROUP_BUDGET)
+      return 1;
+   return 0;
+}
+
 static PassKernel pick_kernel(const mdh_renderer *r, int pass, int set)
 {
    PassKernel k;
@@ -1990,6 +2095,7 @@ static PassKernel pick_kernel(const mdh_renderer *r, int pass, int set)
       const int census = k.pf & (MDH_PF_ROOM | MDH_PF_PSMALL);
       if (!((k.mode == 0 && !k.alt) || ((census & MDH_PF_PSMALL) && k.mode == 2))) k.pf &= ~census;
       if (p2 && k.mode == 0 && !k.alt) k.pf |= MDH_PF_POW2;
+      k.rec = scr_replay_pick(r, k);
       break;
    }
    default: break; // (the irradiance pass has one kernel)
@@ -2366,12 +2472,66 @@ static int pass_screen(PassRun &p)
       if ((long)own_tiles * 4 <= r->opt_scr_split) a.split = 2;
       else if ((long)own_tiles * 2 <= r->opt_scr_split) a.split = 1;
    }
+   // MDH_OPT_SCREEN_REPLAY: the pass that writes the pixels' records, or reads them (pick_kernel chose: p.k.rec)
+   a.rec = nullptr;
+   if (own_tiles <= 0) p.k.rec = 0;
+   if (p.k.rec == 1 && (long)own_tiles * 64 > r->scr_rec_cap) {
+      int drc = drain_streams(r);
+      if (drc != MDH_OK) return drc;
+      r->scr_rec_cap = 0;
+      r->scr_rec_valid = false;
+      for (bool &b : r->scr_rec_read_pending) b = false;
+      { void *q = r->d_scr_rec; r->d_scr_rec = nullptr; if (q) HIP_TRY(hipFree(q)); }
+      if (!r->ev_scr_rec_write) {
+         HIP_TRY(hipEventCreateWithFlags(&r->ev_scr_rec_write, hipEventDisableTiming));
+         for (hipEvent_t &e : r->ev_scr_rec_read) HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+      }
+      if (hipMalloc(&r->d_scr_rec, (size_t)own_tiles * 64 * sizeof(PixelRecord)) == hipSuccess) r->scr_rec_cap = (long)own_tiles * 64;
+      else { // no memory for the records: the renderer keeps marching, and the counters say so
+         r->scr_rec_no_memory = true;
+         (void)hipGetLastError();
+         r->d_scr_rec = nullptr;
+         p.k.rec = 0;
+         if (!(p.kernel = kernel_ptr(p.k))) return seterr(MDH_E_INVALID, "no kernel built for this pass's variant");
+      }
+   }
+   if (p.k.rec) {
+      const int si_st = stream_index(r, st);
+      a.rec = r->d_scr_rec;
+      if (r->scr_rec_version && r->scr_rec_seen[si_st] != r->scr_rec_version) { // the records were written on another stream
+         HIP_TRY(hipStreamWaitEvent(st, r->ev_scr_rec_write, 0));
+         r->scr_rec_seen[si_st] = r->scr_rec_version;
+      }
+      if (p.k.rec == 1) // ... and may still be read on another
+         for (int si = 0; si < mdh_renderer::NSTREAMS; ++si)
+            if (r->scr_rec_read_pending[si]) {
+               if (si != si_st) HIP_TRY(hipStreamWaitEvent(st, r->ev_scr_rec_read[si], 0));
+               r->scr_rec_read_pending[si] = false;
+            }
+   }
    if (own_tiles > 0) {
       const long waves = (long)own_tiles << a.split;
       const int blocks = (int)((waves + (MDH_BLOCK / 64) - 1) / (MDH_BLOCK / 64));
       struct Args { KScene sc; KProbes pr; KVolumetrics vol; KCamera cam; ScreenArgs a; };
-      const int rc = launch_pass<Args>(p, blocks, lds_bytes_screen(r), r->ks, pr, vol, p.cam, a);
+      const size_t lds = p.k.rec == 1 ? lds_bytes(r) + (size_t)MDH_SCR_RECORD_PARK_ROWS * MDH_BLOCK * sizeof(float) : lds_bytes_screen(r);
+      const int rc = launch_pass<Args>(p, blocks, lds, r->ks, pr, vol, p.cam, a);
       if (rc != MDH_OK) return rc;
+   }
+   { // what this pass marched through (or replayed), for the next pass's choice
+      const int si_st = stream_index(r, st);
+      const mdh_renderer::ScrRecKey now = scr_rec_key(r, p.k);
+      if (p.k.rec == 1) {
+         r->scr_rec_key = now; r->scr_rec_valid = true;
+         HIP_TRY(hipEventRecord(r->ev_scr_rec_write, st));
+         r->scr_rec_seen[si_st] = ++r->scr_rec_version;
+      } else if (p.k.rec == 2) {
+         HIP_TRY(hipEventRecord(r->ev_scr_rec_read[si_st], st));
+         r->scr_rec_read_pending[si_st] = true;
+      } else r->scr_rec_valid = false; // (something moved, the option is off or this variant only marches)
+      if (!(r->scr_seen_valid && now == r->scr_seen_key)) r->scr_rec_no_memory = false; // (a new key: the allocation may be tried again)
+      r->scr_seen_key = now;
+      r->scr_seen_valid = r->opt_scr_replay != 0;
+      ++r->scr_replay_stats[p.k.rec];
    }
    return sort_after ? screen_sort_tiles(p, a) : MDH_OK;
 }
@@ -3413,6 +3573,17 @@ extern "C" int32_t mdh_diag_bvh(unsigned long long *out2)
 }
 #endif
 
+// MDH_OPT_SCREEN_REPLAY: screen passes launched since creation that marched, marched and recorded, replayed
+extern "C" int32_t mdh_screen_replay_stats(mdh_renderer *r, int64_t *plain, int64_t *recording, int64_t *replaying)
+{
+   if (!r) return seterr(MDH_E_INVALID, "null renderer");
+   if (plain) *plain = r->scr_replay_stats[0];
+   if (recording) *recording = r->scr_replay_stats[1];
+   if (replaying) *replaying = r->scr_replay_stats[2];
+   return MDH_OK;
+}
+// the size of a pixel's record (tests/test_screen_replay_host.py holds DESIGN.md's figure against it)
+extern "C" int32_t mdh_screen_record_bytes(void) { return (int32_t)sizeof(PixelRecord); }
 // MDH_OPT_RADIANCE_REPLAY: radiance passes launched since creation that marched, marched and recorded, replayed
 extern "C" int32_t mdh_radiance_replay_stats(mdh_renderer *r, int64_t *plain, int64_t *recording, int64_t *replaying)
 {
@@ -3612,13 +3783,16 @@ static const void *kernel_ptr(const PassKernel &k)
 // (MDH_OPT_RADIANCE_REPLAY: the recording and the replaying kernel of a variant, behind everything older)
 #define MDH_RAD_REC(PF) if (k.family == GK_k_radiance && k.pf == (PF) && k.rec == 1) return (const void *)(k.small ? k_radiance<PF, true, 1> : k_radiance<PF, false, 1>); \
                         if (k.family == GK_k_radiance && k.pf == (PF) && k.rec == 2) return (const void *)(k.small ? k_radiance<PF, true, 2> : k_radiance<PF, false, 2>);
+// (MDH_OPT_SCREEN_REPLAY: the recording and the replaying kernel of a fixed-mode variant, behind everything older)
+#define MDH_SCR_REC(PF) if (k.family == GK_k_screen && k.pf == (PF) && k.mode == 0 && !k.alt && k.rec == 1) return k.gbuf ? (const void *)k_screen<PF, 0, true, false, 1> : (const void *)k_screen<PF, 0, false, false, 1>; \
+                        if (k.family == GK_k_screen && k.pf == (PF) && k.mode == 0 && !k.alt && k.rec == 2) return k.gbuf ? (const void *)k_screen<PF, 0, true, false, 2> : (const void *)k_screen<PF, 0, false, false, 2>;
 #define MDH_VIS(PF) MDH_K(k_visibility, PF, k_visibility<PF>)
 #if MDH_SCAT_SPLIT
 #define MDH_SCAT(PF) MDH_K(k_scat_march, PF, k_scat_march<PF>)
 #else
 #define MDH_SCAT(PF) MDH_K(k_scattering, PF, k_scattering<PF>)
 #endif
-#define MDH_SCR(PF, MODE, ALT) if (k.family == GK_k_screen && k.pf == (PF) && k.mode == MODE && k.alt == ALT) return k.gbuf ? (const void *)k_screen<PF, MODE, true, ALT> : (const void *)k_screen<PF, MODE, false, ALT>;
+#define MDH_SCR(PF, MODE, ALT) if (k.family == GK_k_screen && k.pf == (PF) && k.mode == MODE && k.alt == ALT && k.rec == 0) return k.gbuf ? (const void *)k_screen<PF, MODE, true, ALT> : (const void *)k_screen<PF, MODE, false, ALT>;
 #define MDH_GTAB(PF) MDH_VIS(PF) MDH_SCAT(PF) MDH_RAD(PF) MDH_SCR(PF, 0, true) MDH_SCR(PF, 0, false) MDH_SCR(PF, 1, false) MDH_SCR(PF, 2, false)
    MDH_RAD(13) MDH_RAD(37) MDH_RAD(5) MDH_RAD(20) MDH_RAD(4) MDH_RAD(16) MDH_RAD(33) MDH_RAD(0) MDH_RAD(1) MDH_RAD(2) MDH_RAD(9) MDH_RAD(3)
    MDH_VIS(0) MDH_VIS(16) MDH_VIS(33) MDH_VIS(1) MDH_VIS(2) MDH_VIS(9) MDH_VIS(3)
@@ -3642,10 +3816,14 @@ static const void *kernel_ptr(const PassKernel &k)
 #if MDH_RAD_REPLAY_BUILT
    MDH_RAD_REC(20) MDH_RAD_REC(16) MDH_RAD_REC(4) MDH_RAD_REC(0)
 #endif
+#if MDH_SCR_REPLAY_BUILT
+   MDH_SCR_REC(20) MDH_SCR_REC(16) MDH_SCR_REC(4) MDH_SCR_REC(0)
+#endif
    return nullptr;
 #undef MDH_K
 #undef MDH_RAD
 #undef MDH_RAD_REC
+#undef MDH_SCR_REC
 #undef MDH_VIS
 #undef MDH_SCAT
 #undef MDH_SCR

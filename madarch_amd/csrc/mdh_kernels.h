@@ -109,7 +109,12 @@ struct ScreenArgs {
    // depend on which lanes march beside it: the same bits (tests/test_gpu_parity.py::test_split_tiles_change_no_pixel).
    // (measured: splitting only the slowest tiles at the head of an ORDERED launch, four wavefronts of 4x4 pixels each, gained nothing)
    int split;
+   // MDH_OPT_SCREEN_REPLAY (mdh_march.h: PixelRecord): [n_own * 64] the records of the launch's pixels, written by
+   // k_screen<.., 1>, read by k_screen<.., 2>; nullptr for the kernel that only marches.  A pixel's record is at
+   // own index * 64 + (y & 7) * 8 + (x & 7): whichever place, wavefront or lane draws the pixel (screen_record_index)
+   PixelRecord *rec;
 };
+MDH_DEV size_t screen_record_index(int own, int i, int j) { return (size_t)own * 64 + (size_t)((j & 7) * 8 + (i & 7)); }
 // place of a launch -> its index into the launch's tiles, the part of the tile, the split factor (ScreenArgs::split)
 MDH_DEV void screen_place(const ScreenArgs &a, int place, int &idx, int &sub, int &split)
 {
@@ -150,9 +155,15 @@ MDH_DEV void tile_pixel(const ScreenArgs &a, int tile, int sub, int split, int l
    v = -centre(j, a.H); // row 0 = top
 }
 // ALT: the variant whose second shaded point runs render_probes.glsl's other two indirect-specular bodies (modes 1 and 3)
-template <int PART, int MODE, bool GBUF, bool ALT = false>
+// REC (MDH_OPT_SCREEN_REPLAY): 0 = the pass as it marches, 1 = the same and every pixel's PixelRecord stored, 2 = the pass from
+// the records.  Lanes outside the image (partial tiles, the idle lanes of a split tile) read and write none; a launch
+// draws its own rank's tiles only, so no other rank's record is touched.  The recording kernel takes
+// MDH_SCR_RECORD_PARK_ROWS rows of LDS, the replaying one the marching kernel's.
+template <int PART, int MODE, bool GBUF, bool ALT = false, int REC = 0>
 __global__ __launch_bounds__(MDH_BLOCK, MDH_OCC(PART, MODE)) void k_screen(KScene sc, KProbes pr, KVolumetrics vol, KCamera cam, ScreenArgs a)
 {
+   static_assert(REC == 0 || (MDH_SCR_REPLAY && MODE == 0 && !ALT && (PART & ~(MDH_PF_ROOM | MDH_PF_POW2)) == 0),
+                 "records are of the fixed mode's pixel program over the brute-force scan or the rooms' census");
    stage_table(sc);
    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
    const int place = blockIdx.x * (MDH_BLOCK / 64) + wave;
@@ -179,7 +190,15 @@ __global__ __launch_bounds__(MDH_BLOCK, MDH_OCC(PART, MODE)) void k_screen(KScen
       cfg.direct_specular = true;
       cfg.spec_mode = a.spec_mode;
       cfg.ao_steps = a.ao_steps;
-      c = MDH_SHADE<PART, MODE, ALT ? 2 : 1, false>(sc, pr, cfg, valid, origin, dir, ph, hit, pos);
+      if (REC == 2) {
+         RayRecord rec = {0u, 0u, -1, 0u}, rec2 = {0u, 0u, -1, 0u};
+         if (valid) {
+            const PixelRecord *q = a.rec + screen_record_index(own, i, j);
+            rec = q->first; rec2 = q->second;
+         }
+         c = MDH_SHADE<PART, MODE, ALT ? 2 : 1, false, REC>(sc, pr, cfg, valid, origin, dir, ph, hit, pos, rec, rec2);
+      } else
+      c = MDH_SHADE<PART, MODE, ALT ? 2 : 1, false, REC>(sc, pr, cfg, valid, origin, dir, ph, hit, pos);
    }
    struct KArgs { KScene sc; KProbes pr; KVolumetrics vol; KCamera cam; ScreenArgs a; };
    // (the kernel argument segment lays the by-value arguments out like this struct: each at its natural alignment, all of
@@ -227,6 +246,32 @@ __global__ __launch_bounds__(MDH_BLOCK, MDH_OCC(PART, MODE)) void k_screen(KScen
    if (!valid) { PH_KERNEL_END(); return; }
 #endif
    if (!valid) return;
+   if (REC == 1) { // the pixel's record from its parked parts (a miss parked its steps only; no reflection ray: flags 0)
+      float *pk = (float *)(s_tab + ka->sc.table_f4 + ka->sc.part_bits_f4); // (park_base, from the argument segment)
+      const int wb = park_wave_base(pk);
+      PixelRecord q = {{0u, 0u, -1, 0u}, {0u, 0u, -1, 0u}};
+      int vis = 0, flags = 0, vis2 = 0, index2 = -1;
+      if (hit) {
+         const f3 p1 = park_load3<MDH_PARK_REC>(pk, wb);
+         q.first.t = (unsigned)__float_as_int(p1.x); q.first.index = __float_as_int(p1.y); q.first.sd0 = (unsigned)__float_as_int(p1.z);
+         vis = __float_as_int(park_load1<MDH_PARK_REC + 3>(pk, wb));
+         flags = __float_as_int(park_load1<MDH_PARK_REC2 + 4>(pk, wb));
+         if (flags & 2) {
+            const f3 p2 = park_load3<MDH_PARK_REC2>(pk, wb);
+            q.second.t = (unsigned)__float_as_int(p2.x); index2 = __float_as_int(p2.y); q.second.sd0 = (unsigned)__float_as_int(p2.z);
+            vis2 = __float_as_int(park_load1<MDH_PARK_REC2 + 3>(pk, wb));
+         }
+         q.second.index = a.ao_steps > 0 ? __float_as_int(park_load1<MDH_PARK_REC_AO>(pk, wb)) : 0;
+      }
+      q.first.word = ray_record_word(hit, __float_as_int(park_load1<MDH_PARK_REC + 4>(pk, wb)), vis);
+      q.second.word = pixel_record_word2((flags & 2) != 0, (flags & 1) != 0, index2, vis2);
+      int wave3 = wave;
+      asm volatile("" : "+s"(wave3));
+      int pidx3, psub3, psplit3;
+      screen_place(a, (int)blockIdx.x * (MDH_BLOCK / 64) + wave3, pidx3, psub3, psplit3);
+      const int own3 = a.order ? (int)a.order[pidx3] : pidx3;
+      a.rec[screen_record_index(own3, i, j)] = q;
+   }
    if (MODE == 0 && vol.enabled) {
       f3 origin, dir;
       camera_ray(cam, u, v, origin, dir);

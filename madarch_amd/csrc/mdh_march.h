@@ -425,23 +425,66 @@ MDH_DEV unsigned ray_record_word(bool hit, int steps, int vis_bits)
    return min((unsigned)steps, MDH_REC_STEPS_MASK) | ((unsigned)(vis_bits & 255) << 23) | (hit ? 0x80000000u : 0u);
 }
 
+// ---------------------------------------------------------------------------------------------
+// MDH_OPT_SCREEN_REPLAY ("Exact work elimination", item 12): the same for the screen pass's two shaded
+// points.  A pixel of a standing camera over standing geometry finds the same primary hit, the same reflection hit, the same
+// first steps and the same cage visibility in every frame; its occlusion term reads the geometry only.  One PixelRecord per
+// pixel, indexed by the PIXEL (the tile's place among the rank's tiles * 64 + the pixel's place in its tile), never by the
+// lane: MDH_OPT_SCREEN_ORDER moves tiles between launch places, MDH_OPT_SCREEN_SPLIT hands a tile to several wavefronts.
+//   first:   RayRecord of the primary ray and its hit point, as above (word bits 23-30: the corner loop's eight bits)
+//   second:  the reflection ray and its hit point: t and sd0 as above; `word` bits 0-21 the arg-min index + 1, bit 22 a
+//            reflection ray was traced, 23-30 the corner loop's bits, 31 hit; `index` holds the 32 bits of the occlusion
+//            term of the FIRST point (0 when no occlusion step is set)
+// ---------------------------------------------------------------------------------------------
+#ifndef MDH_SCR_REPLAY
+#if defined(MDH_DIAG) || defined(MDH_PHASES)
+#define MDH_SCR_REPLAY 0 // (the diagnostic builds count or time the work of the marches: they keep marching)
+#else
+#define MDH_SCR_REPLAY 1
+#endif
+#endif
+#if MDH_SCR_REPLAY && defined(MDH_PHASES)
+#error "MDH_PHASES keeps its accumulators in park row 19 (MDH_PH_SLOT), where the recording screen kernel's rows start -- build the phase timers with MDH_SCR_REPLAY=0"
+#endif
+struct PixelRecord { RayRecord first, second; };
+static_assert(sizeof(PixelRecord) == 32, "two 16-byte loads or stores per pixel");
+#define MDH_PIXEL_RECORD_BYTES 32
+#define MDH_REC2_INDEX_MASK 0x3fffffu // the second point's arg-min index + 1 (a flat index into a table that fits LDS: below 4 096)
+#define MDH_REC2_TRACED 0x400000u
+// the recording screen kernel's park rows: MDH_PARK_REC + 0 .. 4 the first point's t, arg-min index, first step, visibility
+// bits and the primary march's steps; + 5 .. 8 the same of the second point, + 9 its flags (bit 0 traced, bit 1 hit);
+// + 10 the occlusion term
+#define MDH_PARK_REC2 (MDH_PARK_REC + 5)
+#define MDH_PARK_REC_AO (MDH_PARK_REC + 10)
+#define MDH_SCR_RECORD_PARK_ROWS (MDH_PARK_REC + 11)
+MDH_DEV unsigned pixel_record_word2(bool hit, bool traced, int index, int vis_bits)
+{
+   return min((unsigned)(index + 1), MDH_REC2_INDEX_MASK) | (traced ? MDH_REC2_TRACED : 0u) | ((unsigned)(vis_bits & 255) << 23) | (hit ? 0x80000000u : 0u);
+}
+
 // SPEC: 0 = no second point (the radiance pass), 1 = the reflection as the reference's renderer fixes it
 // (M_COMPUTE_INDIRECT_SPECULAR = 2, or none), 2 = the kernel variant that holds the two other bodies of
 // render_probes.glsl:264-272 (cfg.spec_mode 1 or 3; MDH_OPT_INDIRECT_SPECULAR)
 // REC (the radiance pass with the queue only): 0 = march, 1 = march and park what a RayRecord holds (rows MDH_PARK_REC ..)
 // for the kernel's store, 2 = take the record `rec` instead of the primary march, the arg-min scan, the first step and the queue
+// REC with SPEC = 1 (the screen pass of the reference's fixed mode, brute-force scan or room census): the same for both
+// shaded points -- 1 parks what a PixelRecord holds, 2 takes `rec` and `rec2` instead of both marches, both arg-min scans,
+// both first steps, every visibility march of both corner loops and the occlusion steps
 template <int PART, int MODE, int SPEC, bool QVIS, int REC = 0>
 MDH_DEV f3 shade_structured(const KScene &sc, const KProbes &pr, const MachineCfg cfg, bool lane_valid, f3 from, f3 dir_in,
-                            PrimaryHit &ph, bool &hit, f3 &pos_out, const RayRecord rec = RayRecord{0u, 0u, -1, 0u})
+                            PrimaryHit &ph, bool &hit, f3 &pos_out, const RayRecord rec = RayRecord{0u, 0u, -1, 0u},
+                            const RayRecord rec2 = RayRecord{0u, 0u, -1, 0u})
 {
-   static_assert(REC == 0 || (SPEC == 0 && QVIS && MODE == 0), "records are of the radiance pass's rays");
+   static_assert(REC == 0 || (SPEC == 0 && QVIS && MODE == 0) || (SPEC == 1 && !QVIS && MODE == 0 && !(PART & MDH_PF_PART) && MDH_SHARE_FIRST_STEP),
+                 "records are of the radiance pass's rays or of the screen pass's fixed mode without a space partition");
+   constexpr bool SREC = REC != 0 && SPEC == 1; // the screen pass's records
    constexpr bool P2 = (PART & MDH_PF_POW2) != 0;
    constexpr bool REFLECT = SPEC != 0 && MODE == 0; // (modes 1 and 2 never shade a second point: no loop, and nothing kept for one)
    // The cage-corner loop unrolled where the registers allow it (the brute-force screen kernel of the reference's fixed mode:
    // 96 VGPRs with and without; the partition variants and the one for the optional specular modes would spill 80 - 200 bytes
    // per lane, the radiance kernel gains nothing): constant corner bits, no loop branch, the x-twin's terms at hand.
    constexpr int CORNER_UNROLL = ((PART & MDH_PF_PART) || SPEC != 1 || QVIS) ? 1 : MDH_CORNER_UNROLL;
-   constexpr int PARK_MAT = MODE == 2 ? MDH_PARK_MAT_DIRECT : REC == 2 ? MDH_PARK_MAT_REPLAY : MDH_PARK_MAT; // (no probe rows in mode 2: MDH_DIRECT_PARK_ROWS)
+   constexpr int PARK_MAT = MODE == 2 ? MDH_PARK_MAT_DIRECT : (REC == 2 && SPEC == 0) ? MDH_PARK_MAT_REPLAY : MDH_PARK_MAT; // (no probe rows in mode 2: MDH_DIRECT_PARK_ROWS)
    // the irradiance tap of a cage corner issued before its visibility march (its loads land during the march) -- not in the
    // space-partition variants, whose march needs the registers
    constexpr bool TAP_EARLY = !(PART & MDH_PF_PART);
@@ -469,6 +512,7 @@ MDH_DEV f3 shade_structured(const KScene &sc, const KProbes &pr, const MachineCf
    f3 ro = from, rd = dir_in;
    bool active = lane_valid;
    park_store3<6>(pk, wb, dir_in);
+   if (SREC && REC == 1) park_store1<MDH_PARK_REC2 + 4>(pk, wb, __int_as_float(0)); // (no reflection ray so far)
 #pragma unroll 1
    for (int ctx = 0; ctx < (REFLECT ? 2 : 1); ++ctx) {
       if (active) {
@@ -477,12 +521,14 @@ MDH_DEV f3 shade_structured(const KScene &sc, const KProbes &pr, const MachineCf
          PH_T0(pt);
          bool h;
          if (REC == 2) { // the march's three results as recorded
-            h = (rec.word >> 31) != 0u;
-            t = __int_as_float((int)rec.t);
-            steps = (int)(rec.word & MDH_REC_STEPS_MASK);
+            const RayRecord &q = (SREC && ctx) ? rec2 : rec;
+            h = (q.word >> 31) != 0u;
+            t = __int_as_float((int)q.t);
+            steps = (int)(q.word & MDH_REC_STEPS_MASK); // (the second point's are read by nobody)
          } else
          h = march_plain<PART>(sc, ro, rd, sc.max_dist, t, steps);
-         if (REC == 1) park_store1<MDH_PARK_REC + 4>(pk, wb, __int_as_float(steps)); // (hit or miss: the sort key needs them)
+         if (REC == 1 && !(SREC && ctx)) park_store1<MDH_PARK_REC + 4>(pk, wb, __int_as_float(steps)); // (hit or miss: the sort key needs them)
+         if (REC == 1 && SREC && ctx) park_store1<MDH_PARK_REC2 + 4>(pk, wb, __int_as_float(h ? 3 : 1)); // traced, and hit
          PH_ADD(pt, 0);
          if (ctx == 0) { hit = h; ph.steps = steps; }
          active = false; // a miss ends the chain (ctx 1: specular_col stays 0, render_probes.glsl:142-144)
@@ -499,7 +545,7 @@ MDH_DEV f3 shade_structured(const KScene &sc, const KProbes &pr, const MachineCf
             f3 N;
             int pm;
             MDH_WORK(3);
-            if (REC == 2) index = rec.index;
+            if (REC == 2) index = (SREC && ctx) ? (int)(rec2.word & MDH_REC2_INDEX_MASK) - 1 : rec.index;
             else
             (void)sdf_info<PART>(sc, P, index);
             primitive_info<(PART & MDH_PF_CUSTOM) != 0, (PART & MDH_PF_GTAB) != 0>(sc, index, P, N, pm);
@@ -518,8 +564,10 @@ MDH_DEV f3 shade_structured(const KScene &sc, const KProbes &pr, const MachineCf
                // Every shadow and probe-visibility ray of this point starts AT from_off with t = 0, so
                // their first SDF evaluation is at the same position (from_off + dir * 0): it is done
                // once here and each ray replays its first iteration with this value.
-               const float sd0 = REC == 2 ? __int_as_float((int)rec.sd0) : MDH_SHARE_FIRST_STEP ? sdf<PART>(sc, from_off) : 0.0f;
+               const float sd0 = REC == 2 ? __int_as_float((int)((SREC && ctx) ? rec2.sd0 : rec.sd0)) : MDH_SHARE_FIRST_STEP ? sdf<PART>(sc, from_off) : 0.0f;
                if (REC == 1) { // (t and the arg-min are dead from here on, the first step behind the queue: nothing more stays live for the record)
+                  if (SREC && ctx) park_store3<MDH_PARK_REC2>(pk, wb, F3(t, __int_as_float(index), sd0));
+                  else
                   park_store3<MDH_PARK_REC>(pk, wb, F3(t, __int_as_float(index), sd0));
                }
                // ---- compute_direct_lighting (lighting.glsl:1-40) at P, seen along rd
@@ -591,7 +639,7 @@ MDH_DEV f3 shade_structured(const KScene &sc, const KProbes &pr, const MachineCf
                                ((gp.z < 0 || gp.z >= pg.gz - 1) ? 4 : 0);
                   int vis_bits = 0; // bit i: visibility of corner i
                   PH_ADD(pt, 2);
-                  if (REC == 2) vis_bits = (int)((rec.word >> 23) & 255u); // (P, N, the cage cell and its folds are still in registers)
+                  if (REC == 2) vis_bits = (int)((((SREC && ctx) ? rec2.word : rec.word) >> 23) & 255u); // (P, N, the cage cell and its folds are still in registers)
                   else
                   if (QVIS && ctx == 0) {
                      vis_bits = queued_visibility<PART>(sc, pr, pk, P, N, gp, folded, sd0);
@@ -666,6 +714,12 @@ MDH_DEV f3 shade_structured(const KScene &sc, const KProbes &pr, const MachineCf
                         vis = ((vis_bits >> (i & ~folded)) & 1) ? 1.0f : 0.0f;
                         vmax = 0.0f;
                      }
+                     // the screen pass's record holds the loop's own bits: bit i is what `vis` was behind corner i's march (or
+                     // behind the decision not to march it: folded, the twin's, no candidate, proved clear, an immediate outcome)
+                     if (SREC && REC == 2) {
+                        vis = ((vis_bits >> i) & 1) ? 1.0f : 0.0f;
+                        vmax = 0.0f;
+                     }
 #if MDH_REUSE_FOLDED
                      if (i & folded) { // same probe as corner i & ~folded, already traced
                         vis = ((vis_bits >> (i & ~folded)) & 1) ? 1.0f : 0.0f;
@@ -680,13 +734,14 @@ MDH_DEV f3 shade_structured(const KScene &sc, const KProbes &pr, const MachineCf
 #endif
                      // a ray that segment_clear proves unblocked (behind the immediate outcomes: vmax <= 0, sd0 < EPS, sd0 >= vmax)
                      // is not marched: vis stays 1
+                     if (!(SREC && REC == 2))
                      if (0.0f < vmax && (!MDH_SHARE_FIRST_STEP || (!(sd0 < MDH_EPS) && sd0 < vmax)))
                         if (segment_clear<PART>(sc, from_off, vd, vmax)) vmax = 0.0f;
                      bool first = MDH_SHARE_FIRST_STEP != 0;
                      PH_ADD(pt, 4);
                      if (!(QVIS && !REFLECT)) // (with the queue and no second point this loop is dead code)
                      MDH_WORK(0);
-                     if (!(QVIS && !REFLECT))
+                     if (!(QVIS && !REFLECT) && !(SREC && REC == 2))
                      while (total < vmax) {
                         MDH_DIAG_STEP(3 + ctx);
                         MDH_WORK(1);
@@ -743,6 +798,10 @@ MDH_DEV f3 shade_structured(const KScene &sc, const KProbes &pr, const MachineCf
                      }
                      PH_ADD(pt, 6);
                   }
+                  if (SREC && REC == 1) { // the loop's eight bits
+                     if (ctx) park_store1<MDH_PARK_REC2 + 3>(pk, wb, __int_as_float(vis_bits));
+                     else park_store1<MDH_PARK_REC + 3>(pk, wb, __int_as_float(vis_bits));
+                  }
                   if (SPEC == 2 && ctx == 1 && full2) { // render_probes.glsl:233-243: indirect (no specular of its own) + direct
                      f3 irr = F3(0.0f, 0.0f, 0.0f);
                      if (accw != 0.0f) { irr = sdiv3(acc, accw); irr = irr * irr; }
@@ -760,6 +819,7 @@ MDH_DEV f3 shade_structured(const KScene &sc, const KProbes &pr, const MachineCf
                      // the reflection ray of render_probes.glsl:262-275 finds the next point
                      // (the material id comes back from its park slot: kept in a register across the corner loop it is spilled)
                      active = cfg.spec_mode != 0 && tab_float((sc.mat_slot + 2 * __float_as_int(park_load1<PARK_MAT>(pk, wb)) + 1) * 4) < 0.75f;
+                     if (SREC && REC == 2) active = active && (rec2.word & MDH_REC2_TRACED) != 0u; // (the same bit: ScrRecKey holds what decides it)
                      ro = from_off;
                      rd = reflect(rd, N);
                   } else { // render_probes.glsl:186-208
@@ -806,6 +866,9 @@ MDH_DEV f3 shade_structured(const KScene &sc, const KProbes &pr, const MachineCf
             direct = direct + compute_indirect_lighting(irr, specular_col, -dir, normal, specular_dir, m.albedo, m.metallic, m.roughness);
          }
          float ao = 1.0f;
+         if (SREC && REC == 2) { // the term as recorded: its steps read the geometry, pos and normal only
+            if (cfg.ao_steps > 0) ao = __int_as_float(rec2.index);
+         } else
          if (cfg.ao_steps > 0) {
             float ao_sum = 0.0f, max_ao_sum = 0.0f, factor = 1.0f;
 #pragma unroll 1
@@ -816,6 +879,7 @@ MDH_DEV f3 shade_structured(const KScene &sc, const KProbes &pr, const MachineCf
                factor = factor * 0.5f;
             }
             ao = 0.6f + sdiv(0.4f * ao_sum, max_ao_sum);
+            if (SREC && REC == 1) park_store1<MDH_PARK_REC_AO>(pk, wb, ao);
          }
          result = direct * ao;
       }

@@ -260,6 +260,12 @@ class Renderer:
         self._b.check(self._b.radiance_replay_stats(self._h, *[C.byref(x) for x in v]))
         return tuple(x.value for x in v)
 
+    def Screen_Replay_Stats(self):
+        """OPT_SCREEN_REPLAY: screen passes since creation that (marched, marched and recorded, replayed)."""
+        v = [C.c_int64(0) for _ in range(3)]
+        self._b.check(self._b.screen_replay_stats(self._h, *[C.byref(x) for x in v]))
+        return tuple(x.value for x in v)
+
     def Reset_Pass_Times(self):
         self._b.check(self._b.reset_pass_times(self._h))
 
