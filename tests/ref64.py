@@ -2,7 +2,9 @@
 of the oracle or of the HIP library against it.
 
 It shares no code with oracle/ or madarch_amd/csrc/ and calls neither: plain numpy, vectorised over rays with masks.
-Every function cites the text it restates.  There is no space partition and there are no volumetrics here.
+Every function cites the text it restates.  Besides the screen and the radiance pass it restates the irradiance fold
+(irradiance_texels), the optional mip chain (radiance_mips), the two volumetric passes (froxel_texels,
+scattering_texels) and the volumetric composition of a pixel.  There is no space partition here.
 
 The scene is a plain description (a dict; every number is rounded to binary32 first, as the scene buffer holds it):
 
@@ -15,6 +17,8 @@ The scene is a plain description (a dict; every number is rounded to binary32 fi
   lights     [("point", position, colour) | ("spot", position, direction, aperture, colour)] as the light loop meets them
   max_dist, cam_pos, cam_m (cam_m[i][j] = row i, column j), ao_steps, spec_mode (0 or 2),
   probes     dict (rres, ires, count (x, y), dims (x, y, z), spacing (x, y, z))
+  vol        (optional) dict (vres (x, y, z), vstep, sres (x, y), sstep): the volumetric settings; with them and a
+             scattering texture, a mode-0 pixel is composed with the fog (volumetrics.glsl:34-54)
 
 Where the reference leaves a value undefined, the project's stated choice is taken and named:
 marches are cut after 4096 steps (Q3), an irradiance with no weight at all is 0 (Q11), textureLod (.., 1.0) on the
@@ -33,11 +37,19 @@ MAX_STEPS = 4096
 JITTER = 2.0 ** -18           # relative jitter of every ray's origin and direction in the two extra runs
 EPS_MARGIN = 2.0 ** -20       # times max (1, largest coordinate): see hold, threshold_margin
 KIND_NAMES = ("Sphere", "Plane", "Box", "Triangle")
+TAU = 0.1                     # volumetrics.glsl:12
+NEAR_SURFACE = 0.02           # test_oracle_pins64.py:180: a froxel's sample point this close to a surface (or inside one)
 
 
 def r32(x):
     """a number as the scene buffer holds it: rounded to binary32, then exact in float64"""
     return np.asarray(x, dtype=np.float32).astype(np.float64)
+
+
+def image6(x):
+    """a number that travels through the generated GLSL text: Single'Image keeps six significant digits
+    (madarch-renderers.adb:119-134), and the compiler reads them back as a binary32 literal"""
+    return float(np.float32(float("%.5E" % float(np.float32(x)))))
 
 
 def _dot(a, b):
@@ -87,8 +99,14 @@ class Scene:
     """the description compiled into arrays, primitives in the order the generated scan meets them: kind by kind in
     declared order, each kind in the order its entities were added (madarch-scenes.adb:602-674)"""
 
-    def __init__(self, desc):
+    def __init__(self, desc, vol=None):
         self.desc = desc
+        vol = desc.get("vol") if vol is None else vol
+        if vol is not None:  # volumetrics.glsl:1-10 from madarch-renderers.adb:119-134
+            self.vres, self.sres = np.array(vol["vres"], dtype=int), np.array(vol["sres"], dtype=int)
+            self.vstep, self.sstep = image6(vol["vstep"]), image6(vol["sstep"])
+            # visibility_max_depth (volumetrics.glsl:3-4) is a constant of the shader: the product of two binary32 constants
+            self.max_depth = float(np.float32(self.vstep) * np.float32(self.vres[2]))
         self.max_dist = float(r32(desc.get("max_dist", 20.0)))
         base, b = {}, 0
         for name, count in desc["kinds"]:
@@ -172,8 +190,9 @@ class Scene:
 class Run:
     """one rendering: the scene, the atlases it reads and the jitter of its rays (seed None: as stated)"""
 
-    def __init__(self, scene, seed=None, irradiance=None, radiance=None):
+    def __init__(self, scene, seed=None, irradiance=None, radiance=None, scattering=None):
         self.sc = scene
+        self.scat = None if scattering is None else np.asarray(scattering, dtype=np.float64)
         self.rng = None if seed is None else np.random.RandomState(seed)
         self.irr = None if irradiance is None else np.asarray(irradiance, dtype=np.float64)
         self.rad = None if radiance is None else np.asarray(radiance, dtype=np.float64)
@@ -347,7 +366,31 @@ class Run:
         out[rows] = self.tap(self.rad, bq, sc.rres, bdir) + self.direct(S, sn, Dir, zero, sc.m_metallic[smat], sc.m_rough[smat], True)
         return out
 
-    def pixel_color_probes(self, O, D, mode, specular, indirect_specular, ao_steps):
+    def render_volumetrics(self, colour, O, P, hit, frag):
+        """volumetrics.glsl:34-54: of the 3 x 3 scattering texels round the fragment (x outer, y inner), the first whose stored
+        length is strictly closer to this pixel's than every one before, starting from max_dist; a miss has len = max_dist
+        (SURVEY.md Q13).  -> colour, and `near`: another candidate's |a - len| is within 2 T_ATOL of the best one's, so that
+        the pick is a coin toss between precisions -- unless the two carry the same fog (within half COLOUR_ATOL): at the
+        texture's edge the mirrored repeat makes two offsets read the same texels, and then the pick does not show"""
+        sc = self.sc
+        tc = (frag + 1.0) * 0.5
+        length = np.where(hit, _norm(P - O), sc.max_dist)
+        rgb, a = self.scat[..., :3], np.repeat(self.scat[..., 3:], 3, axis=2)
+        dists, fogs = [], []
+        for x in (-1, 0, 1):
+            for y in (-1, 0, 1):
+                cx, cy = tc[:, 0] + x / sc.sres[0], tc[:, 1] + y / sc.sres[1]
+                dists.append(np.abs(bilinear(a, cx, cy)[:, 0] - length))
+                fogs.append(bilinear(rgb, cx, cy))
+        dists, fogs = np.stack(dists, axis=1), np.stack(fogs, axis=1)
+        best = np.argmin(dists, axis=1)  # (the first of equal ones, as `dist < closest` keeps it)
+        rows = np.arange(len(O))
+        closest, fog = dists[rows, best], fogs[rows, best]
+        fog[~(closest < sc.max_dist)] = 0.0  # (no candidate closer than max_dist: fog_L is undefined; no case comes near)
+        rival = (dists - closest[:, None] < 2.0 * T_ATOL) & (np.abs(fogs - fog[:, None, :]).max(axis=2) > 0.5 * COLOUR_ATOL)
+        return colour * np.exp(-length * TAU)[:, None] + fog, rival.any(axis=1)
+
+    def pixel_color_probes(self, O, D, mode, specular, indirect_specular, ao_steps, frag=None):
         """render_probes.glsl:246-291.  mode 0 is the reference's; 1 and 2 are this project's BASELINE configs 1 and 2:
         0.5 n + 0.5, and direct light times the ambient occlusion.  -> dict of hit, index, t, pos, normal, colour,
         near (the primary march came near the threshold), tri (near, or the march behind the specular term did, or a
@@ -388,6 +431,9 @@ class Run:
                     c = self.ambient_occlusion(Ph, N, ao_steps)[:, None] * (direct + indirect)
             colour[rows] = c
             tri[rows] |= flags
+        if frag is not None and self.scat is not None and mode == 0:  # render_probes.glsl:289 (M_RENDER_VOLUMETRICS)
+            colour, coin = self.render_volumetrics(colour, O, P, hit, frag)
+            tri = tri | coin  # (fragile for its colour only, like a triangle's normal)
         index = np.where(hit, sc.number[np.maximum(arg, 0)], -1)
         return {"hit": hit, "index": index, "t": np.where(hit, t, 0.0), "pos": P, "normal": normal, "colour": colour, "tri": tri, "near": near}
 
@@ -421,14 +467,22 @@ def bilinear(img, cx, cy):
 
 
 # ------------------------------------------------------------------------------------------- the passes
-def camera_rays(sc, W, H):
+def camera(sc, u, v):
     """draw_screen.glsl:20-24: the matrix acts on the direction AND on the fragment's position"""
-    j, i = np.mgrid[0:H, 0:W]
-    u = (2.0 * i.ravel() + 1.0) / W - 1.0
-    v = -((2.0 * j.ravel() + 1.0) / H - 1.0)  # row 0 is the top of the window
     frag = np.stack([u, v, np.zeros_like(u)], axis=1)
     d = _unit(frag - np.array([0.0, 0.0, -1.5]))
     return frag @ sc.cam_m.T + sc.cam_pos, d @ sc.cam_m.T
+
+
+def centres(W, H):
+    """the centres of a W x H image's texels in [-1, 1], row by row (a pass's `pos.xy`)"""
+    j, i = np.mgrid[0:H, 0:W]
+    return (2.0 * i.ravel() + 1.0) / W - 1.0, (2.0 * j.ravel() + 1.0) / H - 1.0
+
+
+def camera_rays(sc, W, H):
+    u, v = centres(W, H)
+    return camera(sc, u, -v)  # row 0 is the top of the window
 
 
 def _shape(out, H, W):
@@ -445,13 +499,15 @@ def primary(desc, W, H, seed=None):
     return _shape({"near": near, "hit": hit, "index": np.where(hit, sc.number[np.maximum(arg, 0)], -1), "t": np.where(hit, t, 0.0), "pos": P, "normal": N}, H, W)
 
 
-def screen(desc, W, H, mode, irradiance_atlas=None, radiance_atlas=None, seed=None):
+def screen(desc, W, H, mode, irradiance_atlas=None, radiance_atlas=None, seed=None, scattering=None):
     """the LINEAR colour per pixel (before draw_screen.glsl:29) with the primary hit behind it; the screen shader's
-    defines are those of madarch-renderers.adb:136-143 with ao_steps and spec_mode from the description"""
+    defines are those of madarch-renderers.adb:136-143 with ao_steps and spec_mode from the description.  With volumetric
+    settings in the description and a `scattering` texture, the fog is composed in (volumetrics.glsl:34-54)."""
     sc = Scene(desc)
-    run = Run(sc, seed, irradiance_atlas, radiance_atlas)
+    run = Run(sc, seed, irradiance_atlas, radiance_atlas, scattering if desc.get("vol") else None)
     O, D = camera_rays(sc, W, H)
-    return _shape(run.pixel_color_probes(O, D, mode, True, desc.get("spec_mode", 2), desc.get("ao_steps", 3)), H, W)
+    u, v = centres(W, H)
+    return _shape(run.pixel_color_probes(O, D, mode, True, desc.get("spec_mode", 2), desc.get("ao_steps", 3), frag=np.stack([u, -v], axis=1)), H, W)
 
 
 def radiance_texels(desc, irradiance_atlas, radiance_atlas=None, seed=None):
@@ -473,6 +529,107 @@ def radiance_texels(desc, irradiance_atlas, radiance_atlas=None, seed=None):
     world = np.stack([gx, gy, gz], axis=1) * sc.spacing
     ray_id = nc * sc.pc - np.floor(nc * sc.pc)
     return _shape(run.pixel_color_probes(world, oct_decode(ray_id), 0, False, 0, 0), H, W)
+
+
+def irradiance_texels(desc, radiance_atlas, previous=None, hysteresis=0.0):
+    """the whole irradiance atlas after one irradiance pass (update_probe_irradiance.glsl:8-43 with probe_utils.glsl): a
+    texel's centre decides its probe (coord_to_probe_id :19-25, probe_id_to_coord :52-56) and its direction
+    (coord_to_ray_id, ray_id_to_ray_dir :80-87); the taps sit at the CORNERS of the probe's radiance texels, clamped to
+    [step, 1 - step] (:19,26-31), each filtered bilinearly and weighted by max (dot, 0) with the direction of where it sits
+    (:32-38); summed in the shader's y, x order and divided by the total weight (:42).
+    hysteresis h > 0 (not in the reference; the library's irradiance_blend): GLSL mix (fresh, previous, h)."""
+    sc = Scene(desc)
+    rad = np.asarray(radiance_atlas, dtype=np.float64)
+    W, H = sc.pc[0] * sc.ires, sc.pc[1] * sc.ires
+    u, v = centres(W, H)
+    nc = (np.stack([u, v], axis=1) + 1.0) * 0.5
+    tile = np.floor(nc * sc.pc)
+    irr_dir = oct_decode(nc * sc.pc - tile)
+    rad_coord = tile / sc.pc
+    step = 1.0 / sc.pc / sc.rres
+    acc, total = np.zeros((len(nc), 3)), np.zeros(len(nc))
+    for y in range(sc.rres):
+        for x in range(sc.rres):
+            c = np.clip(rad_coord + np.array([x, y]) * step, step, 1.0 - step)
+            w = np.maximum(_dot(irr_dir, oct_decode(c * sc.pc - np.floor(c * sc.pc))), 0.0)
+            acc += bilinear(rad, c[:, 0], c[:, 1]) * w[:, None]
+            total += w
+    out = (acc / total[:, None]).reshape(H, W, 3)
+    if hysteresis > 0.0:
+        h = float(r32(hysteresis))
+        out = out * (1.0 - h) + np.asarray(previous, dtype=np.float64) * h  # GLSL 4.30 section 8.3, mix
+    return out
+
+
+def radiance_mips(atlas, lods):
+    """MDH_OPT_RADIANCE_MIPS (not in the reference): levels 0 .. lods of the atlas image, each the 2 x 2 box of the one
+    below; with lods = log2 (radiance resolution) the last has one texel per probe"""
+    levels = [np.asarray(atlas, dtype=np.float64)]
+    for _ in range(lods):
+        a = levels[-1]
+        assert a.shape[0] % 2 == 0 and a.shape[1] % 2 == 0
+        levels.append((a[0::2, 0::2] + a[0::2, 1::2] + a[1::2, 0::2] + a[1::2, 1::2]) / 4.0)
+    return levels
+
+
+def hg_phase(a, b):  # volumetrics.glsl:21-30
+    return (1.0 - TAU * TAU) / (4.0 * PI * (1.0 + TAU * TAU - 2.0 * TAU * _dot(a, b)) ** 1.5)
+
+
+def froxel_texels(desc, vol, seed=None):
+    """the froxel texture after one visibility pass (compute_frustrum_visibility.glsl:8-42): texel (x, y) of the
+    (vw, vh * vz) image is slice floor (y / vh), its sample point the camera ray through (x, fract height) advanced by
+    slice * step (:28-39); there, over all lights in the light loop's order, exp (-L_dist tau) * raycast_visibility * radiance *
+    tau * henvey_greenstein_phase (L, dir) (:8-19).  -> colour, and `near`: the sample point lies within NEAR_SURFACE of a surface
+    or inside a primitive, where the visibility ray is blocked at once in one precision only."""
+    sc = Scene(desc, vol)
+    run = Run(sc, seed)
+    vw, vh, vz = (int(n) for n in sc.vres)
+    px, py = centres(vw, vh * vz)
+    tex_height = (py + 1.0) * 0.5 * vz
+    depth = np.floor(tex_height)
+    O, D = camera(sc, px, (tex_height - depth) * 2.0 - 1.0)
+    P = O + D * (depth * sc.vstep)[:, None]
+    out = np.zeros((len(P), 3))
+    for light in sc.lights:
+        radiance, L, Ld = run.sample_light(light, P)
+        out += radiance * (np.exp(-Ld * TAU) * run.visibility(P, L, Ld) * TAU * hg_phase(L, D))[:, None]
+    return _shape({"colour": out, "near": sc.closest(P)[0] < NEAR_SURFACE}, vh * vz, vw)
+
+
+def scattering_texels(desc, vol, froxels, seed=None):
+    """the scattering texture after one scattering pass (accumulate_scattering.glsl:9-48) over the froxel texture given:
+    len = min (|hit - origin|, max_depth), a miss keeping the far point (:18-21); L = step_s * sum over f = 0, step_s, .. < len of
+    bilinear (froxels, (nx, (ny + floor (f / step_v)) / vz)) * exp (-f tau) (:9-15,22-27), GL_LINEAR with mirrored repeat.
+    The sequence f_k and floor (f_k / step_v) are the shader's DISCRETE decisions and are taken in binary32
+    (test_oracle_pins64.py, test_scattering_texels_against_float64); so is f_k < len where len is the cap, a binary32
+    constant of the shader.  -> colour (L), len, and `near`: len comes from the march and some f_k lies within T_ATOL
+    of it, so that the march's last ulp decides the number of steps."""
+    sc = Scene(desc, vol)
+    run = Run(sc, seed)
+    sw, sh = (int(n) for n in sc.sres)
+    vz = int(sc.vres[2])
+    u, v = centres(sw, sh)
+    O, D = camera(sc, u, v)
+    hit, _, _, P, _ = run.raycast(O, D)
+    d = np.where(hit, _norm(P - O), np.inf)
+    length = np.minimum(d, sc.max_depth)
+    F, f, s = [], np.float32(0.0), np.float32(sc.sstep)
+    while float(f) <= sc.max_depth + float(s):
+        F.append(f)
+        f = np.float32(f + s)
+    marched = d < sc.max_depth + T_ATOL
+    near = marched & (np.abs(np.array(F, dtype=np.float64)[None, :] - length[:, None]) <= T_ATOL).any(axis=1)
+    vis = np.asarray(froxels, dtype=np.float64)
+    nx, ny = 0.5 * (u + 1.0), 0.5 * (v + 1.0)
+    L = np.zeros((len(O), 3))
+    for f in F:
+        m = float(f) < length
+        if not m.any():
+            break
+        rel = float(np.floor(f / np.float32(sc.vstep)))  # (binary32: sample_visibility :10)
+        L[m] += bilinear(vis, nx[m], (ny[m] + rel) / vz) * np.exp(-float(f) * TAU)
+    return _shape({"colour": L * sc.sstep, "len": length, "near": near}, sh, sw)
 
 
 def distance(desc, kinds, points):
@@ -566,8 +723,50 @@ def hold(name, runs, colour=None, index=None, t=None, rtol=COLOUR_RTOL, atol=COL
         # anywhere else, on however dark a pixel, is an error
         ok |= np.isnan(got) & (want < 0.0) & ~ref["hit"][..., None]
         bad = ~ok.all(axis=-1) & ~col
+        with np.errstate(invalid="ignore"):
+            ratio = np.where(ok, np.abs(got - want) / (atol + more_atol + rtol * np.abs(want)), np.inf).max(axis=-1)
+        print("%s: largest error %.3f of its tolerance" % (name, float(np.where(col, 0.0, np.nan_to_num(ratio, nan=0.0, posinf=np.inf)).max())))
         if bad.any():
             where = tuple(np.argwhere(bad)[0])
             raise AssertionError("%s: %d of %d pixels outside the tolerance, first at %s: got %s, float64 %s, index %d" % (
                 name, bad.sum(), bad.size, where, got[where], want[where], ref["index"][where]))
     return share
+
+
+def hold_values(name, runs, got, rtol, atol, more_atol=0.0, clamp=False, length=None, cap=FRAGILE_CAP):
+    """hold's sibling for a texture that has no hit and no index (an atlas, the froxel and the scattering texture): `runs`
+    are dicts of `colour` and, where the pass has them, `near` and `len`.  A texel is fragile if a run flags it `near` or
+    if, between any two runs, its colour differs by more than half the tolerance or its len by more than half T_ATOL; at
+    most `cap` of the texels may be, every other one must agree: the colour within atol + more_atol + rtol |float64|,
+    `length` (the fourth component of the texture under test) within T_ATOL.  Prints the fragile share and the largest
+    error of a held texel as a fraction of its tolerance, and returns both."""
+    ref = runs[0]
+    bad = np.zeros(ref["colour"].shape[:-1], dtype=bool)
+    for r in runs:
+        if "near" in r:
+            bad |= r["near"]
+    for a in range(len(runs)):
+        for b in range(a + 1, len(runs)):
+            ca, cb = runs[a]["colour"], runs[b]["colour"]
+            bad |= ~(np.abs(ca - cb) <= 0.5 * (atol + rtol * np.minimum(np.abs(ca), np.abs(cb)))).all(axis=-1)
+            if "len" in ref:
+                bad |= np.abs(runs[a]["len"] - runs[b]["len"]) > 0.5 * T_ATOL
+    share = float(bad.mean())
+    want = np.clip(ref["colour"], 0.0, 1.0) if clamp else ref["colour"]
+    got = np.asarray(got, dtype=np.float64)
+    assert got.shape == want.shape, "%s: shape %s, float64 %s" % (name, got.shape, want.shape)
+    with np.errstate(invalid="ignore"):
+        ratio = np.abs(got - want) / (atol + more_atol + rtol * np.abs(want))
+    ratio = np.where(np.isfinite(got), ratio, np.inf).max(axis=-1)
+    if length is not None:
+        lr = np.abs(np.asarray(length, dtype=np.float64) - ref["len"]) / T_ATOL
+        ratio = np.maximum(ratio, np.where(np.isfinite(lr), lr, np.inf))
+    worst = float(np.where(bad, 0.0, ratio).max())
+    print("%s: fragile share %.4f (%d of %d), largest error %.3f of its tolerance" % (name, share, int(bad.sum()), bad.size, worst))
+    assert share <= cap, "%s: %.4f of the inputs are fragile in float64 alone" % (name, share)
+    off = (ratio > 1.0) & ~bad
+    if off.any():
+        where = tuple(np.argwhere(off)[0])
+        raise AssertionError("%s: %d of %d texels outside the tolerance (largest error %.3g of it), first at %s: got %s, float64 %s" % (
+            name, off.sum(), off.size, worst, where, got[where], want[where]))
+    return share, worst

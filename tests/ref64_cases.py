@@ -4,7 +4,7 @@ ref64.hold.  The float64 results are cached per process, so the two files never 
 import numpy as np
 
 import ref64
-from helpers import SEED, SMALL_PROBES
+from helpers import ODD_PROBES, SEED, SMALL_PROBES
 from madarch_amd import _binding as B
 from madarch_amd import materials, renderers, scenes, windows
 from madarch_amd.lights import point_lights, spot_lights
@@ -53,6 +53,15 @@ def open_scene(probes=SMALL_PROBES):
             "max_dist": 20.0, "cam_pos": (2.5, 1.5, -1.0), "cam_m": np.eye(3), "ao_steps": 3, "spec_mode": 2, "probes": probes_of(probes)}
 
 
+def vol_of(V):
+    return {"vres": V.Visibility_Resolution, "vstep": V.Visibility_Step_Size, "sres": V.Scattering_Resolution, "sstep": V.Scattering_Step_Size,
+            "settings": V}
+
+
+def volume(vres=(8, 8, 8), vstep=0.1, sres=(24, 24), sstep=0.1):
+    return renderers.Volumetrics_Settings(Visibility_Resolution=vres, Visibility_Step_Size=vstep, Scattering_Resolution=sres, Scattering_Step_Size=sstep)
+
+
 def rotation():
     """a rotation about two axes; the matrix is not symmetric, so its transpose is another camera"""
     a, b = 0.35, -0.2
@@ -80,7 +89,8 @@ def make_renderer(desc, W, H, binding, mode=0, atlas=1):
     assert desc["max_dist"] == 20.0  # scenes.ads:51, the default every case keeps
     scene = scenes.Compile([(KINDS[k][0], n) for k, n in desc["kinds"]], [(LIGHTS[k][0], n) for k, n in desc["light_kinds"]],
                            Partitioning=scenes.Partitioning_Settings(Enable=False))
-    R = renderers.Create(windows.Open(W, H, "ref64"), scene, Probes=desc["probes"]["settings"], Volumetrics=renderers.No_Volumetrics, Binding=binding)
+    volumetrics = desc["vol"]["settings"] if desc.get("vol") else renderers.No_Volumetrics
+    R = renderers.Create(windows.Open(W, H, "ref64"), scene, Probes=desc["probes"]["settings"], Volumetrics=volumetrics, Binding=binding)
     for i, (a, m, r) in enumerate(desc["materials"]):
         R.Set_Material(i, materials.Create(a, m, r))
     for p in desc["prims"]:
@@ -132,15 +142,30 @@ def cached(key, compute):
 
 
 # ---------------------------------------------------------------------------------------------------- frames
-def run_screen(binding, name, scene, W, H, mode, camera="identity", ao=3, spec=2, scene_kw=None, prepare=None, frames=1, burst=0):
+def scattering_texture(vol, seed):
+    """the pin's distribution (test_oracle_pins64.py:230-231): rgb uniform (0, 1), the stored length uniform (0.5, 9)"""
+    rng = np.random.RandomState(seed)
+    sw, sh = vol.Scattering_Resolution
+    scat = rng.uniform(0.0, 1.0, size=(sh, sw, 4)).astype(np.float32)
+    scat[..., 3] = rng.uniform(0.5, 9.0, size=(sh, sw))
+    return scat
+
+
+def run_screen(binding, name, scene, W, H, mode, camera="identity", ao=3, spec=2, scene_kw=None, prepare=None, frames=1, burst=0, vol=None):
     """one screen pass (modes 1 and 2: `frames` whole frames through Render; mode 0: Render_Pass (PASS_SCREEN) alone over
     written atlases, so that the probe feedback does not compound and every tap reads known data) against ref64.screen.
+    `vol` (mode 0): volumetric settings; the scattering texture is written as well and composed into every pixel.
     `burst` whole frames through Render come first and are not waited for: what is read afterwards is ordered behind them."""
     scene_kw = scene_kw or {}
     desc = describe(scene, camera, ao, spec, **scene_kw)
     irr, rad = atlases(desc, SEED % 1000 + 3) if mode == 0 else (None, None)
-    key = ("screen", scene, W, H, mode, camera, ao, spec, tuple(sorted(scene_kw.items())))
-    runs = cached(key, lambda: ref64.three_runs(lambda seed: ref64.screen(desc, W, H, mode, irr, rad, seed=seed)))
+    scat = None
+    if vol is not None:
+        assert mode == 0
+        desc["vol"] = vol_of(vol)
+        scat = scattering_texture(vol, SEED % 1000 + 13)
+    key = ("screen", scene, W, H, mode, camera, ao, spec, tuple(sorted(scene_kw.items())), vol and tuple(vol.Scattering_Resolution))
+    runs = cached(key, lambda: ref64.three_runs(lambda seed: ref64.screen(desc, W, H, mode, irr, rad, seed=seed, scattering=scat)))
     R = make_renderer(desc, W, H, binding, mode=mode)
     if prepare is not None:
         prepare(R)
@@ -149,6 +174,8 @@ def run_screen(binding, name, scene, W, H, mode, camera="identity", ao=3, spec=2
     if mode == 0:
         R.Write_Texture(B.TEX_IRRADIANCE, irr)
         R.Write_Texture(B.TEX_RADIANCE, rad)
+        if scat is not None:
+            R.Write_Texture(B.TEX_SCATTERING, scat)
         R.Render_Pass(B.PASS_SCREEN)
     else:
         for _ in range(frames):
@@ -185,6 +212,196 @@ def run_radiance(binding, name, probes, atlas, prepare=None):
     if atlas == 0:
         return ref64.hold(name, runs, got, more_atol=0.5 / 255.0, clamp=True)
     return ref64.hold(name, runs, got)
+
+
+# ---------------------------------------------------------------------------------------- the irradiance fold
+def grid_probes(rres, ires, count=(4, 2), dims=(2, 2, 2), spacing=(2.0, 3.0, 3.0)):
+    return renderers.Probe_Settings(Radiance_Resolution=rres, Irradiance_Resolution=ires, Probe_Count=count, Grid_Dimensions=dims, Grid_Spacing=spacing)
+
+
+# (rres, ires): see tests/test_gpu_ref64_passes.py for what each reaches
+IRRADIANCE_SHAPES = [(8, 8), (16, 8), (5, 2), (12, 6), (10, 3), (8, 10), (8, 17), (48, 16)]
+
+
+def irradiance_probes(rres, ires):
+    """eight probes, (4, 2) tiles over a 2 x 2 x 2 grid; (12, 6) is ODD_PROBES, 15 x 5 tiles"""
+    return ODD_PROBES if (rres, ires) == (12, 6) else grid_probes(rres, ires)
+
+
+def tap_ray_ids(probes, dtype):
+    """fract (c * probe_count) of every tap of every probe (update_probe_irradiance.glsl:19,26-33, probe_utils.glsl:52-56,80-82),
+    each operation once in `dtype`"""
+    f = dtype
+    rres = probes.Radiance_Resolution
+    out = []
+    for axis in (0, 1):
+        pc = probes.Probe_Count[axis]
+        step = f(f(f(1.0) / f(pc)) / f(rres))
+        base = (np.arange(pc).astype(f) / f(pc)).astype(f)
+        c = (base[:, None] + (np.arange(rres).astype(f) * step).astype(f)[None, :]).astype(f)
+        c = np.clip(c, step, f(f(1.0) - step)).astype(f)
+        x = (c * f(pc)).astype(f)
+        out.append((x - np.floor(x)).astype(np.float64))
+    return out
+
+
+def assert_taps_on_one_side(probes):
+    """The input condition of run_irradiance.  A tap sits on a texel CORNER, and the corner of a tile's first texel is the tile's
+    border: there fract (c * probe_count) is 0 on one side and nearly 1 on the other, and the two decode to different
+    directions.  Which side a tap lands on is decided by one rounding; a setting is held only if float64 and binary32 land
+    every tap on the same side (no ray id differs by more than 1e-3)."""
+    for a, b in zip(tap_ray_ids(probes, np.float64), tap_ray_ids(probes, np.float32)):
+        assert np.abs(a - b).max() <= 1e-3, "a tap of %r lands on the other side of its tile's border in binary32" % (probes.Probe_Count,)
+
+
+def run_irradiance(binding, name, probes, atlas, hysteresis=0, sparse=False, passes=1):
+    """Render_Pass (PASS_IRRADIANCE) over a written radiance atlas, the whole irradiance atlas against ref64.irradiance_texels.
+    The input: uniform (0, 1) (RGB8: multiples of 1 / 255, exact in the format), or `sparse` (fp32 only): 15 of 16 texels 0, the
+    rest uniform (0, 64) -- a tap taken from the wrong lane, chunk or turn then moves a texel by tens of per cent, not by 1 / ntaps.
+    `hysteresis` (per mille): a seeded irradiance atlas is written as the previous frame's.
+    `passes` > 1: that many passes on one renderer, each over another atlas (the kernel's scratch is reused); the last is held.
+
+    Tolerance: numerator and denominator are sequential binary32 sums of non-negative terms, each with a relative error of at
+    most (ntaps - 1) 2^-24, plus a few ulps per tap for the filter and the decode; whatever the values, non-negative terms
+    keep that bound relative to the sum.  The pin's rtol = 2e-4, atol = 1e-6 (test_oracle_pins.py:457) holds at 1024 taps; for
+    larger tiles rtol = 4 ntaps 2^-24 (twice the two sums' bound).  RGB8 adds half a step of the format and the clamp to
+    [0, 1]; mix () is a convex combination and adds nothing."""
+    assert not (sparse and atlas == 0)
+    assert_taps_on_one_side(probes)
+    desc = room(probes=probes)
+    ntaps = probes.Radiance_Resolution ** 2
+    rtol = max(2e-4, 4.0 * ntaps * 2.0 ** -24)
+    rng = np.random.RandomState(SEED % 1000 + 17)
+    P = desc["probes"]
+    R = make_renderer(desc, 8, 8, binding, atlas=atlas)
+    R.Set_Option(B.OPT_HYSTERESIS_PERMILLE, hysteresis)
+    for _ in range(passes):
+        irr, rad = atlases(desc, rng.randint(1 << 30), levels=255 if atlas == 0 else None)
+        if sparse:
+            rad = (rng.uniform(0.0, 64.0, size=rad.shape) * (rng.randint(0, 16, size=rad.shape[:2]) == 0)[..., None]).astype(np.float32)
+        R.Write_Texture(B.TEX_RADIANCE, rad)
+        if hysteresis:
+            R.Write_Texture(B.TEX_IRRADIANCE, irr)
+        R.Render_Pass(B.PASS_IRRADIANCE)
+        got = R.Read_Texture(B.TEX_IRRADIANCE)
+    R.Destroy()
+    key = ("irradiance", P["rres"], P["ires"], tuple(P["count"]), atlas, hysteresis, sparse, passes)
+    want = cached(key, lambda: ref64.irradiance_texels(desc, rad, irr, hysteresis / 1000.0))
+    if atlas == 0:
+        return ref64.hold_values(name, [{"colour": want}], got, rtol, 1e-6, more_atol=0.5 / 255.0, clamp=True)
+    return ref64.hold_values(name, [{"colour": want}], got, rtol, 1e-6)
+
+
+def run_mips(binding, name, atlas):
+    """MDH_OPT_RADIANCE_MIPS over a written atlas of SMALL_PROBES: every level read back against the float64 box of the level
+    below AS READ BACK (level 0: the atlas written), which holds the whole chain by induction and lets the bound be a
+    single box's: fp32, (a + b) + (c + d) then * 0.25 is three roundings, at most 1 ulp of the largest input -- held to 2;
+    RGB8, half a step of the format (and the fp32 sum's ulp)."""
+    desc = room()
+    _, rad = atlases(desc, SEED % 1000 + 19, levels=255 if atlas == 0 else None)
+    R = make_renderer(desc, 8, 8, binding, atlas=atlas)
+    R.Write_Texture(B.TEX_RADIANCE, rad)
+    R.Set_Option(B.OPT_RADIANCE_MIPS, 1)
+    lods = int(np.log2(desc["probes"]["rres"]))
+    below, worst = rad, 0.0
+    for l in range(1, lods + 1):
+        got = R.Read_Texture(B.TEX_RADIANCE_MIP0 + l)
+        want = ref64.radiance_mips(below, 1)[1]
+        assert got.shape == want.shape
+        b = below.astype(np.float64)
+        largest = np.maximum(np.maximum(b[0::2, 0::2], b[0::2, 1::2]), np.maximum(b[1::2, 0::2], b[1::2, 1::2]))
+        tol = 2.0 * ulp32(largest) if atlas == 1 else 0.5 / 255.0 + 2.0 * ulp32(largest)
+        err = np.abs(got.astype(np.float64) - want) / tol
+        worst = max(worst, float(err.max()))
+        assert (err <= 1.0).all(), "%s: level %d off at %s" % (name, l, np.argwhere(err > 1.0)[0])
+        below = got
+    R.Destroy()
+    assert below.shape[:2] == (desc["probes"]["count"][1], desc["probes"]["count"][0])  # one texel per probe
+    print("%s: %d levels, largest error %.3f of its tolerance" % (name, lods, worst))
+    return worst
+
+
+# ---------------------------------------------------------------------------------------- the volumetric passes
+SHAFT = ("point", (5.0, 3.0, 6.0), (0.9, 0.9, 0.9))  # examples/light_shafts/main.adb:59
+# a spot light above the camera's frustum that looks down into it (SPOT looks along +x, past every froxel volume here); its
+# direction is a unit vector to four digits: the light's code does not normalise it, and neither side does here
+DOWN_SPOT = ("spot", (3.5, 5.0, 2.0), (-0.4423, -0.8847, -0.1474), 3.1415 / 4.0, (0.9, 0.9, 0.8))
+FROXEL_RTOL, FROXEL_ATOL = 3e-4, 1e-7                # test_oracle_pins64.py:186
+SCATTER_RTOL, SCATTER_ATOL = 5e-4, 1e-7              # test_oracle_pins64.py:220
+
+
+def vol_scene(scene, camera="identity"):
+    """the scene with two lights, a point light (the light_shafts example's) and the spot light: the pins only see one point light"""
+    d = describe(scene, camera)
+    d["light_kinds"], d["lights"] = [("point", 4), ("spot", 4)], [SHAFT if scene == "room" else d["lights"][0], DOWN_SPOT]
+    return d
+
+
+def run_froxels(binding, name, vol, scene="room", camera="identity"):
+    """Render_Pass (PASS_VISIBILITY), the whole froxel texture against ref64.froxel_texels; fragile: the three runs and `near`"""
+    desc = vol_scene(scene, camera)
+    key = ("froxels", scene, camera, vol.Visibility_Resolution, vol.Visibility_Step_Size)
+    runs = cached(key, lambda: ref64.three_runs(lambda seed: ref64.froxel_texels(desc, vol_of(vol), seed=seed)))
+    desc["vol"] = vol_of(vol)
+    R = make_renderer(desc, 8, 8, binding)
+    R.Render_Pass(B.PASS_VISIBILITY)
+    got = R.Read_Texture(B.TEX_VISIBILITY)
+    R.Destroy()
+    lit = (runs[0]["colour"].max(axis=-1) > 0.0).mean()
+    assert 0.3 < lit, "%s: only %.2f of the froxels are lit" % (name, lit)
+    return ref64.hold_values(name, runs, got, FROXEL_RTOL, FROXEL_ATOL)
+
+
+def run_scattering(binding, name, vol, scene="room", camera="identity", written=True, moved=False):
+    """written: a seeded froxel texture (uniform 0 .. 1) is written and Render_Pass (PASS_SCATTERING) runs alone, so that no
+    froxel's fragility leaks in.  Otherwise one whole Render () -- the only way to the march fused into the visibility
+    pass's launch -- or, `moved`, the pair Render_Pass (PASS_VISIBILITY), Render_Pass (PASS_SCATTERING) after a camera move
+    (outside a frame the scattering pass marches its own rays); the scattering texture is then held against
+    ref64.scattering_texels over the froxel texture READ BACK from the binding, as the pins isolate passes."""
+    desc = vol_scene(scene, camera)
+    desc["vol"] = vol_of(vol)
+    vw, vh, vz = vol.Visibility_Resolution
+    R = make_renderer(desc, 8, 8, binding)
+    if written:
+        vis = np.random.RandomState(SEED % 1000 + 23).uniform(0.0, 1.0, size=(vh * vz, vw, 3)).astype(np.float32)
+        R.Write_Texture(B.TEX_VISIBILITY, vis)
+        R.Render_Pass(B.PASS_SCATTERING)
+    elif moved:
+        R.Render()
+        desc["cam_pos"] = tuple(np.asarray(desc["cam_pos"]) + np.array([0.4, -0.3, 0.5]))
+        R.Set_Camera_Position(desc["cam_pos"])
+        R.Render_Pass(B.PASS_VISIBILITY)
+        R.Render_Pass(B.PASS_SCATTERING)
+        vis = R.Read_Texture(B.TEX_VISIBILITY)
+    else:
+        R.Render()
+        vis = R.Read_Texture(B.TEX_VISIBILITY)
+    got = R.Read_Texture(B.TEX_SCATTERING)
+    R.Destroy()
+    key = ("scattering", scene, camera, vol.Visibility_Resolution, vol.Visibility_Step_Size, vol.Scattering_Resolution, vol.Scattering_Step_Size, moved)
+    # (the marches do not depend on the froxel texture: the three runs' lengths are cached, the fold is over `vis`)
+    runs = ref64.three_runs(lambda seed: ref64.scattering_texels(desc, vol_of(vol), vis, seed=seed)) if not written else cached(
+        key, lambda: ref64.three_runs(lambda seed: ref64.scattering_texels(desc, vol_of(vol), vis, seed=seed)))
+    return ref64.hold_values(name, runs, got[..., :3], SCATTER_RTOL, SCATTER_ATOL, length=got[..., 3])
+
+
+# the froxel volumes: each reaches one of the three froxel-to-lane layouts (tests/test_gpu_ref64_passes.py)
+# (the steps are as deep as the room allows with at most 5 % of the sample points within NEAR_SURFACE of a surface or inside the
+#  sphere or the box; about a third of the froxels are in shadow or outside the spot light's cone)
+FROXEL_CASES = {"blocks 8x8x8": {"vol": volume((8, 8, 8), 0.4)}, "tiles 24x6x4": {"vol": volume((24, 6, 4), 0.9)},
+                "rows 10x7x3": {"vol": volume((10, 7, 3), 1.2)}, "rows 10x7x3 open": {"vol": volume((10, 7, 3), 1.6), "scene": "open"},
+                "blocks 8x8x8 rotated": {"vol": volume((8, 8, 8), 0.4), "camera": "rotated"}}
+SCATTERING_CASES = {
+    "23x21": {"vol": volume((6, 5, 8), 0.5, (23, 21), 0.1)},
+    "17x5 ten coarse steps": {"vol": volume((6, 5, 8), 0.5, (17, 5), 0.4)},
+    "128 steps": {"vol": volume((6, 5, 16), 0.1, (17, 5), 0.0125)},
+    "several chunks": {"vol": volume((6, 5, 16), 0.2, (17, 5), 0.007)},
+    "equal steps": {"vol": volume((6, 5, 24), 0.2, (17, 5), 0.2)},
+    "frame room": {"vol": volume((8, 8, 8), 0.5, (23, 21), 0.1), "written": False},
+    "frame open": {"vol": volume((10, 7, 3), 1.5, (17, 5), 0.1), "scene": "open", "written": False},
+    "passes after a move": {"vol": volume((8, 8, 8), 0.5, (23, 21), 0.1), "written": False, "moved": True},
+    "frame room rotated": {"vol": volume((8, 8, 8), 0.5, (23, 21), 0.1), "camera": "rotated", "written": False},
+}
 
 
 # ---------------------------------------------------------------------------------------- Eval_Distances_To

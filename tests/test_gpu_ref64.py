@@ -3,7 +3,8 @@ cases of test_ref64_oracle.py through the `hip` fixture with the same masks and 
 shapes and variants where a kernel, not the oracle, goes wrong: frame sizes down to one pixel and through
 MDH_OPT_SCREEN_SPLIT's halves and quadrants, the room's census kernels and the general ones, both atlas formats on
 power-of-two and odd probe settings, frames in flight, Eval_Distances_To's point counts round a wavefront, and the
-table residency forced.  The float64 results are computed here, on the GPU machine, inside the tests."""
+table residency forced.  The float64 results are computed here, on the GPU machine, inside the tests.
+The irradiance fold, the mip chain and the volumetric passes are held in tests/test_gpu_ref64_passes.py."""
 import pytest
 
 import ref64_cases as cases
@@ -73,7 +74,8 @@ def test_frames_in_flight(hip, overlap):
     the probe stream and rotate the atlas sets, their screen passes alternate between two streams and two framebuffers.
     The atlases must land in the set the last frame left current, behind that frame's passes; the screen pass must read
     that set and draw, behind the alternate stream's frame, the framebuffer that the read-back then takes.  What the
-    pipelined probe passes compute is not held here (ref64 has no irradiance fold): see test_gpu_parity.py."""
+    pipelined probe passes compute is not held here (the passes alone are, in test_gpu_ref64_passes.py; what they compute
+    with frames in flight is held against the oracle in test_gpu_parity.py)."""
     def prepare(R):
         R.Set_Option(B.OPT_FRAME_OVERLAP, overlap)
         assert R.Get_Option(B.OPT_FRAME_OVERLAP) == overlap

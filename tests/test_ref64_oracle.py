@@ -5,8 +5,16 @@ composition of pixel_color_probes, the radiance pass's addressing, screen modes 
 the geometric one, and Eval_Distances_To on thousands of points.
 
 Fragile pixels are decided by the float64 renderer alone (ref64.fragile: three runs, two of them with every ray
-jittered by 2^-18) and are at most 5 % of a case; every other pixel must agree (ref64.hold).  Not covered: the space
-partition, volumetrics, user-defined kinds, indirect-specular modes 1 and 3 (restated in test_oracle_pins64.py)."""
+jittered by 2^-18) and are at most 5 % of a case; every other pixel must agree (ref64.hold).
+
+The second half holds the passes the pins only hold in pieces, whole and with no share that may fail: the irradiance
+fold over every texel of the atlas (with hysteresis, in both formats, over a sparse atlas), the optional mip chain, the
+froxel texture under two lights (one a spot light), the scattering texture over written froxels and inside a whole
+frame, and the volumetric composition of a pixel.  The shapes are those of tests/test_gpu_ref64_passes.py, where the
+kernels change form; here they prove ref64's new code and show that the fragile caps hold for the reference alone.
+
+Not covered: the space partition, user-defined kinds, indirect-specular modes 1 and 3 (restated in
+test_oracle_pins64.py)."""
 import pytest
 
 import ref64_cases as cases
@@ -52,3 +60,49 @@ def test_eval_distances_to(orc, kinds):
     """Eval_Distance_To (madarch-renderers.adb:499-526) on several thousand seeded points, the triangle against the
     GEOMETRIC distance (closest point by barycentric regions), with a long thin and a nearly degenerate triangle"""
     cases.run_distance(orc, "distance " + "-".join(kinds), kinds)
+
+
+# ---------------------------------------------------------------------------------------- the irradiance fold
+@pytest.mark.parametrize("sparse", [False, True], ids=["uniform", "sparse"])
+@pytest.mark.parametrize("rres,ires", cases.IRRADIANCE_SHAPES, ids=["%dx%d" % s for s in cases.IRRADIANCE_SHAPES])
+def test_irradiance_fold_whole_atlas(orc, rres, ires, sparse):
+    """update_probe_irradiance.glsl:8-43 with probe_utils.glsl, every texel of the atlas"""
+    cases.run_irradiance(orc, "irradiance %dx%d%s" % (rres, ires, " sparse" if sparse else ""), cases.irradiance_probes(rres, ires), 1, sparse=sparse)
+
+
+@pytest.mark.parametrize("rres,ires", [(16, 8), (12, 6)])
+def test_irradiance_fold_rgb8(orc, rres, ires):
+    cases.run_irradiance(orc, "irradiance %dx%d rgb8" % (rres, ires), cases.irradiance_probes(rres, ires), 0)
+
+
+@pytest.mark.parametrize("atlas", [1, 0], ids=["f32", "rgb8"])
+@pytest.mark.parametrize("rres,ires", [(16, 8), (12, 6), (8, 10)])
+def test_irradiance_fold_with_hysteresis(orc, rres, ires, atlas):
+    """stored = mix (fresh, previous, 0.35) over a written previous atlas (not in the reference: irradiance_blend)"""
+    cases.run_irradiance(orc, "irradiance %dx%d hysteresis %s" % (rres, ires, "rgb8" if atlas == 0 else "f32"), cases.irradiance_probes(rres, ires),
+                         atlas, hysteresis=350)
+
+
+@pytest.mark.parametrize("atlas", [1, 0], ids=["f32", "rgb8"])
+def test_radiance_mip_chain(orc, atlas):
+    cases.run_mips(orc, "mips %s" % ("rgb8" if atlas == 0 else "f32"), atlas)
+
+
+# ---------------------------------------------------------------------------------------- the volumetric passes
+@pytest.mark.parametrize("case", sorted(cases.FROXEL_CASES), ids=lambda c: c.replace(" ", "-"))
+def test_froxel_texture(orc, case):
+    """compute_frustrum_visibility.glsl:8-42 whole, a point light and a spot light"""
+    cases.run_froxels(orc, "froxels " + case, **cases.FROXEL_CASES[case])
+
+
+@pytest.mark.parametrize("case", sorted(cases.SCATTERING_CASES), ids=lambda c: c.replace(" ", "-"))
+def test_scattering_texture(orc, case):
+    """accumulate_scattering.glsl:9-48 whole: over written froxels, inside a whole frame, and as a pass of its own"""
+    cases.run_scattering(orc, "scattering " + case, **cases.SCATTERING_CASES[case])
+
+
+@pytest.mark.parametrize("sres", [(24, 24), (23, 21)], ids=["24x24", "23x21"])
+@pytest.mark.parametrize("size", [(36, 24), (1, 1)], ids=["36x24", "1x1"])
+def test_pixel_with_volumetrics(orc, size, sres):
+    """volumetrics.glsl:34-54 inside pixel_color_probes: the 3 x 3 depth-aware pick over a written scattering texture"""
+    cases.run_screen(orc, "volumetric pixel %dx%d over %dx%d" % (size + sres), "room", size[0], size[1], 0, camera="rotated", vol=cases.volume(sres=sres))
