@@ -7,6 +7,7 @@
 // gfx950 device mdh_create fails with MDH_E_NO_DEVICE.
 #include "../../include/madarch_hip.h"
 #include "mdh_kernels.h"
+#include "mdh_host.h" // DevBuf, Event, Fence, RingUse: what owns the buffers, events and orderings below
 #include "mdh_jit_sources.inc" // the three device headers as string literals (Makefile), for the hiprtc build of user-defined kinds
 
 #include <dlfcn.h>
@@ -310,37 +311,32 @@ struct mdh_renderer {
    // The scene table lives in a ring of buffers: an edit (Set_Light every frame in the reference's examples) is
    // packed into the NEXT buffer and uploaded asynchronously from pinned memory while the frames in flight keep
    // reading theirs -- a scene edit does not drain the frame pipeline.  A buffer is rewritten only after the last
-   // kernels that were launched with it have finished (tab_done, per stream).
+   // kernels that were launched with it have finished (tab_use, per stream).
    static const int TAB_RING = 4;
-   float4 *d_table_ring[TAB_RING] = {nullptr, nullptr, nullptr, nullptr};
-   float4 *h_table_ring[TAB_RING] = {nullptr, nullptr, nullptr, nullptr}; // pinned
+   DevBuf<float4> d_table_ring[TAB_RING];
+   PinnedBuf<float4> h_table_ring[TAB_RING];
    int tab_slot = 0;
-   static const int NSTREAMS = 5; // main, probe, alternate, query, volumetric (stream_index)
-   hipEvent_t tab_done[TAB_RING][NSTREAMS] = {{nullptr}};
-   bool tab_used[TAB_RING][NSTREAMS] = {{false}};
-   hipEvent_t ev_table = nullptr;       // recorded after the last upload, on table_stream
-   hipStream_t table_stream = nullptr;
-   unsigned long long table_version = 0, tab_seen[NSTREAMS] = {0, 0, 0, 0, 0}; // per stream: has it waited for ev_table
-   size_t table_cap = 0;
+   static const int NSTREAMS = HOST_NSTREAMS; // main, probe, alternate, query, volumetric (stream_index)
+   RingUse<TAB_RING> tab_use;
+   Fence table_fence;     // signalled after the last upload, on the stream that made it
+   size_t table_cap = 0;  // float4 every buffer of the ring holds
    bool table_dirty = true;
    // The space-partition table, in a ring like the scene table: Update_Partitioning builds into the next buffer
    // on the stream that uses it first and returns; frames in flight keep the buffer they were launched with
    // (KScene::part_table travels by value).  The builders' warning count comes back through pinned memory
    // and is waited for only when somebody asks (mdh_partition_warnings).
    static const int PART_RING = 4;
-   int *d_part_ring[PART_RING] = {nullptr, nullptr, nullptr, nullptr};
+   DevBuf<int> d_part_ring[PART_RING];
    int part_slot = 0;
-   hipEvent_t part_done[PART_RING][NSTREAMS] = {{nullptr}};
-   bool part_used[PART_RING][NSTREAMS] = {{false}};
-   hipEvent_t ev_part = nullptr, ev_warn = nullptr; // the last build, the last read-back of its warning count
-   hipStream_t part_stream = nullptr;
-   unsigned long long part_version = 0, part_seen[NSTREAMS] = {0, 0, 0, 0, 0};
-   int *d_warn = nullptr, *h_warn = nullptr;
+   RingUse<PART_RING> part_use;
+   Fence part_fence; // the last build (its version counts Update_Partitioning's builds)
+   Event ev_warn;    // the last read-back of its warning count
+   DevBuf<int> d_warn;
+   PinnedBuf<int> h_warn;
    bool warn_pending = false;
    hipStream_t query_stream = nullptr; // Eval_Distance_To: beside the frames in flight, not behind them
    hipStream_t vol_stream = nullptr;   // the camera-only volumetric passes of pipelined frames, beside their probe passes
-   float *d_query = nullptr; // Eval_Distance_To: points, normals, distances of the largest batch so far
-   size_t query_cap = 0;
+   DevBuf<float> d_query; // Eval_Distance_To: points, normals, distances of the largest batch so far (7 floats a query)
    // Two sets of probe atlases.  `last` is the set the most recent frame wrote: every read, write and
    // single pass works on it in place.  A pipelined mdh_render (frame overlap, see mdh_render) writes the
    // other set while the previous frame's screen pass still reads this one, then flips.
@@ -348,16 +344,14 @@ struct mdh_renderer {
    //  frame N - 1 still reads and wait for it -- the chain screen (N - 1) -> probes (N + 1) -> screen (N + 1) bound the frame
    //  rate of pipelined frames; with three they wait for the screen pass of frame N - 2, long gone)
    static const int NSETS = MDH_ATLAS_SETS;
-   void *d_rad2[NSETS] = {nullptr}, *d_irr2[NSETS] = {nullptr};
-   void *d_rad_mips[NSETS] = {nullptr}; // MDH_OPT_RADIANCE_MIPS: levels 1 .. radiance_lods of each set's radiance atlas, one behind the other
+   DevBuf<> d_rad2[NSETS], d_irr2[NSETS];
+   DevBuf<> d_rad_mips[NSETS]; // MDH_OPT_RADIANCE_MIPS: levels 1 .. radiance_lods of each set's radiance atlas, one behind the other
    int opt_mips = 0;
    int n_cus = 0;                          // compute units of the device
    // RadOrder (mdh_kernels.h): every ray's primary-march steps, the rays sorted by them, the sort's histograms
-   float *d_irr_taps = nullptr;  // k_irradiance's scratch: the taps of the pass's probes (mdh_kernels.h)
-   size_t irr_taps_cap = 0;      // in floats
-   unsigned char *d_rad_steps = nullptr;
-   unsigned *d_rad_order = nullptr, *d_rad_hist = nullptr;
-   long rad_rays_cap = 0;                  // rays the three buffers are sized for
+   DevBuf<float> d_irr_taps;     // k_irradiance's scratch: the taps of the pass's probes (mdh_kernels.h)
+   DevBuf<unsigned char> d_rad_steps;      // one group, sized for d_rad_steps.cap rays (pass_radiance)
+   DevBuf<unsigned> d_rad_order, d_rad_hist;
    long rad_order_rays = 0;                // rays the stored order is of (0: none)
    int rad_order_begin = -1;               // ... and the first probe of their slice
    int rad_order_age = 0;                  // radiance passes since the rays were sorted
@@ -369,8 +363,7 @@ struct mdh_renderer {
    // single pass against the frames in flight (join_main; the probe stream is ordered after the main stream's work when
    // frames go in flight again) -- the order that d_rad_order relies on between the pass that sorts and the pass that reads.
    // It is allocated, grown and freed like d_rad_steps / d_rad_order: with both streams drained.
-   RayRecord *d_rad_rec = nullptr;
-   long rad_rec_cap = 0;                   // rays the buffer is sized for
+   DevBuf<RayRecord> d_rad_rec;            // (its capacity: rays)
    struct RadRecKey {                      // everything a probe ray's marches read (rad_rec_key): records are valid for one value of it
       unsigned long geometry, inputs;      // geometry_edits, march_inputs
       unsigned long long part_version;     // Update_Partitioning's builds
@@ -395,14 +388,12 @@ struct mdh_renderer {
    // MDH_OPT_SCREEN_REPLAY (mdh_march.h: PixelRecord): one record per pixel of the rank's tiles, indexed by the pixel
    // (mdh_kernels.h: screen_record_index).  ONE buffer: a record holds nothing of an atlas, a framebuffer or a light.  Screen
    // passes of frames in flight alternate between the main and the alternate stream and nothing else orders them against each
-   // other, so the buffer carries its own order: every pass that reads it leaves an event on its stream (ev_scr_rec_read), the
-   // pass that writes it waits for the readers on the other streams and leaves ev_scr_rec_write, and a reader on a stream that
-   // has not seen the latest write waits for that event.  Allocated, grown and freed with every stream drained.
-   PixelRecord *d_scr_rec = nullptr;
-   long scr_rec_cap = 0;                   // pixels (own tiles * 64) the buffer is sized for
-   hipEvent_t ev_scr_rec_write = nullptr, ev_scr_rec_read[NSTREAMS] = {nullptr, nullptr, nullptr, nullptr, nullptr};
-   bool scr_rec_read_pending[NSTREAMS] = {false, false, false, false, false};
-   unsigned long long scr_rec_version = 0, scr_rec_seen[NSTREAMS] = {0, 0, 0, 0, 0};
+   // other, so the buffer carries its own order: every pass that reads it marks its stream (scr_rec_reads), the pass
+   // that writes it retires the readers on the other streams and signals scr_rec_written, and a reader on a stream that
+   // has not seen the latest write waits for that.  Allocated, grown and freed with every stream drained.
+   DevBuf<PixelRecord> d_scr_rec;          // (its capacity: pixels, own tiles * 64)
+   Fence scr_rec_written;                  // one group, created with the first records (pass_screen)
+   RingUse<1> scr_rec_reads;
    struct ScrRecKey {                      // everything a screen march reads, and what decides which pixel holds what (scr_rec_key)
       RadRecKey march;                     // geometry, probe grid, max_dist, table layout, residency, BVH, JIT, the kernel's variant word
       float cam[12];                       // position and orientation BY VALUE: setting the camera to where it is changes nothing
@@ -421,16 +412,17 @@ struct mdh_renderer {
    long long scr_replay_stats[3] = {0, 0, 0}; // screen passes launched marching, recording, replaying
    int opt_scr_replay = 0;
    // MDH_OPT_SCREEN_ORDER (ScreenArgs, mdh_kernels.h): the screen pass's tiles in the order of their wavefronts' durations
-   unsigned char *d_scr_cost = nullptr;          // [tiles] sort keys, written by the pass that is followed by a sort
-   unsigned *d_scr_order[2] = {nullptr, nullptr}; // [tiles] two buffers: passes in flight keep reading the one they were launched with
-   unsigned *d_scr_hist = nullptr;
+   // (the three buffers and the two events are one group, created by the first pass that sorts: pass_screen)
+   DevBuf<unsigned char> d_scr_cost;             // [tiles] sort keys, written by the pass that is followed by a sort
+   DevBuf<unsigned> d_scr_order[2];              // [tiles] two buffers: passes in flight keep reading the one they were launched with
+   DevBuf<unsigned> d_scr_hist;
    int scr_order_cur = -1;                       // the buffer that holds the order (-1: none)
    int scr_order_n = 0, scr_order_rank = -1, scr_order_world = -1; // what that order is of
    int scr_order_age = 0;                        // screen passes since the tiles were sorted
    unsigned long scr_order_geom = 0;             // geometry_edits when they were
    float scr_order_cam[12] = {0};                // the camera then
-   hipEvent_t ev_scr_sort = nullptr, ev_scr_other = nullptr;
-   unsigned long long scr_sort_version = 0, scr_sort_seen[NSTREAMS] = {0, 0, 0, 0, 0};
+   Fence scr_sorted;                             // the last sort
+   Event ev_scr_other;
    int opt_scr_order = 1;
    int opt_scr_split = MDH_SCREEN_SPLIT_DEFAULT; // MDH_OPT_SCREEN_SPLIT: the wavefronts a split screen launch may have (0: never split)
    std::map<std::pair<const void *, size_t>, int> resident; // workgroups per CU of (kernel, LDS bytes): rad_first_round
@@ -448,8 +440,8 @@ struct mdh_renderer {
    std::string jit_kinds; // mdh_jit_kinds.h of this scene (generated once)
    hipStream_t probe_stream = nullptr;   // radiance + irradiance passes of pipelined frames
    hipStream_t alt_stream = nullptr;     // screen pass of every other pipelined frame
-   hipEvent_t ev_screen[NSETS] = {nullptr}, ev_probe[NSETS] = {nullptr}, ev_join = nullptr, ev_join_alt = nullptr;
-   hipEvent_t ev_vol[NSETS] = {nullptr}; // the camera-only volumetric passes of a pipelined frame (on vol_stream, beside its probe passes)
+   Event ev_screen[NSETS], ev_probe[NSETS], ev_join, ev_join_alt;
+   Event ev_vol[NSETS]; // the camera-only volumetric passes of a pipelined frame (on vol_stream, beside its probe passes)
    bool ev_screen_valid[NSETS] = {false};
    bool alt_pending = false; // work on alt_stream that `stream` has not been ordered after yet
    // an open frame (mdh_frame_begin .. mdh_frame_end)
@@ -461,35 +453,35 @@ struct mdh_renderer {
    bool main_dirty = true; // work went to `stream` outside a pipelined frame since the probe stream last joined it
    // froxel and scattering textures, one per atlas set: the volumetric passes of a pipelined frame run on the
    // probe stream into the set that frame produces
-   float *d_vis2[NSETS] = {nullptr};
-   float4 *d_scat2[NSETS] = {nullptr};
-   float4 *d_fb2[2] = {nullptr, nullptr}; // two framebuffers: consecutive pipelined frames draw on two streams
+   DevBuf<float> d_vis2[NSETS];
+   DevBuf<float4> d_scat2[NSETS];
+   DevBuf<float4> d_fb2[2]; // two framebuffers: consecutive pipelined frames draw on two streams
    int fb_last = 0;                       // the one the most recent frame drew
    // mdh_swap_buffers: a ring of RGBA8 copies of a framebuffer, each a device buffer (written on the stream that
    // drew the frame) and a pinned host buffer (filled on a stream of its own, so no screen pass queues behind a copy)
    static constexpr int FRONT_RING = 3;
-   unsigned *d_front[FRONT_RING] = {nullptr, nullptr, nullptr};
-   unsigned char *h_front[FRONT_RING] = {nullptr, nullptr, nullptr};
-   hipEvent_t ev_front[FRONT_RING] = {nullptr, nullptr, nullptr}; // slot's host copy done
-   hipEvent_t ev_packed = nullptr;
+   DevBuf<unsigned> d_front[FRONT_RING];
+   PinnedBuf<unsigned char> h_front[FRONT_RING];
+   Event ev_front[FRONT_RING]; // slot's host copy done
+   Event ev_packed;
    hipStream_t copy_stream = nullptr;
    // MDH_OPT_WINDOW: the screen pass itself stores the RGBA8 pixels into a ring of pinned host buffers (over PCIe,
    // no copy and no extra kernel); a swap then only marks the last one with an event
    static constexpr int WIN_RING = 4;
    int opt_window = 2; // MDH_OPT_WINDOW: 0 never, 1 always, 2 from the first mdh_swap_buffers on
-   unsigned *h_win[WIN_RING] = {nullptr, nullptr, nullptr, nullptr};
-   hipEvent_t ev_win[WIN_RING] = {nullptr, nullptr, nullptr, nullptr};
+   PinnedBuf<unsigned> h_win[WIN_RING];
+   Event ev_win[WIN_RING];
    long long win_passes = 0; // screen passes that wrote a window slot; the last one wrote slot (win_passes - 1) % WIN_RING
    bool win_valid = false;   // the last screen pass wrote a window slot
    int win_owner[2] = {0, 1};
    // what mdh_front_buffer returns: set by mdh_swap_buffers
    const unsigned char *front_ptr = nullptr;
-   hipEvent_t front_ev = nullptr;
+   hipEvent_t front_ev = nullptr; // (borrowed: the ev_win or ev_front of that slot)
    long long swaps = 0; // mdh_swap_buffers calls so far; the last one went to slot (swaps - 1) % FRONT_RING
    // (rank, world) whose tiles are the only non-zero pixels of a framebuffer; {0, 1}: every pixel may be set
    int fb_owner[2][2] = {{-1, -1}, {-1, -1}};
    // geometry buffer: [which framebuffer] x {index, t, steps} (int32 / float / int32 per pixel)
-   void *d_gb2[2][3] = {{nullptr, nullptr, nullptr}, {nullptr, nullptr, nullptr}};
+   DevBuf<> d_gb2[2][3];
    KScene ks{};
    // timing: event pairs recorded around every pass, resolved lazily (no host sync per pass)
    struct Pending { int pass; hipEvent_t e0, e1; };
@@ -510,7 +502,7 @@ struct mdh_renderer {
    // call returns.  With nobody inside, the aborting thread owns the state and drops everything itself.
    std::atomic<bool> comm_aborted{false};
    std::atomic<int> comm_busy{0};
-   double *d_comm_scratch = nullptr; // barrier / max reductions
+   DevBuf<double> d_comm_scratch; // barrier / max reductions
    struct PeerState *peer = nullptr; // the peer exchange (mdh_peer_init): the same sharded frame, its exchange as copies
    bool irr_lds_granted = false; // k_irradiance may use up to 160 KiB of dynamic LDS on this renderer's device
 };
@@ -520,19 +512,23 @@ struct mdh_renderer {
 static int join_main(mdh_renderer *r)
 {
    if (!r->alt_pending) return MDH_OK;
-   HIP_TRY(hipEventRecord(r->ev_join_alt, r->alt_stream));
-   HIP_TRY(hipStreamWaitEvent(r->stream, r->ev_join_alt, 0));
+   HIP_TRY(hipEventRecord(r->ev_join_alt.ev, r->alt_stream));
+   HIP_TRY(hipStreamWaitEvent(r->stream, r->ev_join_alt.ev, 0));
    r->alt_pending = false;
    return MDH_OK;
 }
-// host wait for everything this renderer has enqueued anywhere (its own streams only: other renderers of the process run on)
-static int drain_streams(mdh_renderer *r)
+// Host wait for a set of this renderer's streams: bit si of `mask` is the stream that stream_index calls si (those that
+// do not exist yet are skipped), SYNC_OWN the renderer's own main stream while the caller has supplied another.
+enum : unsigned { SYNC_MAIN = 1, SYNC_PROBE = 2, SYNC_ALT = 4, SYNC_QUERY = 8, SYNC_VOL = 16, SYNC_OWN = 32, SYNC_ALL = 63 };
+static int sync_streams(mdh_renderer *r, unsigned mask)
 {
-   for (hipStream_t st : {r->probe_stream, r->alt_stream, r->query_stream, r->vol_stream, r->own_stream})
-      if (st) HIP_TRY(hipStreamSynchronize(st));
-   if (r->stream && r->stream != r->own_stream) HIP_TRY(hipStreamSynchronize(r->stream));
+   const hipStream_t sts[] = {r->stream, r->probe_stream, r->alt_stream, r->query_stream, r->vol_stream, r->own_stream != r->stream ? r->own_stream : nullptr};
+   for (int si = 0; si < 6; ++si)
+      if ((mask >> si & 1u) && sts[si]) HIP_TRY(hipStreamSynchronize(sts[si]));
    return MDH_OK;
 }
+// host wait for everything this renderer has enqueued anywhere (its own streams only: other renderers of the process run on)
+static int drain_streams(mdh_renderer *r) { return sync_streams(r, SYNC_ALL); }
 static hipEvent_t get_event(mdh_renderer *r)
 {
    if (!r->free_events.empty()) { hipEvent_t e = r->free_events.back(); r->free_events.pop_back(); return e; }
@@ -549,11 +545,7 @@ static int resolve_timing(mdh_renderer *r, bool wait = true)
    if (r->pending.empty()) return MDH_OK;
    if (wait) {
       { int jr = join_main(r); if (jr != MDH_OK) return jr; }
-      if (r->probe_stream) HIP_TRY(hipStreamSynchronize(r->probe_stream));
-      if (r->alt_stream) HIP_TRY(hipStreamSynchronize(r->alt_stream));
-      if (r->vol_stream) HIP_TRY(hipStreamSynchronize(r->vol_stream)); // (timed volumetric passes of pipelined frames)
-      if (r->own_stream && r->own_stream != r->stream) HIP_TRY(hipStreamSynchronize(r->own_stream));
-      HIP_TRY(hipStreamSynchronize(r->stream));
+      { int sr = sync_streams(r, SYNC_MAIN | SYNC_PROBE | SYNC_ALT | SYNC_VOL | SYNC_OWN); if (sr != MDH_OK) return sr; } // (SYNC_VOL: timed volumetric passes of pipelined frames)
    }
    int rc = MDH_OK;
    size_t keep = 0;
@@ -624,26 +616,16 @@ static int stream_index(const mdh_renderer *r, hipStream_t st) { return st == r-
 static int table_acquire(mdh_renderer *r, hipStream_t st)
 {
    const int si = stream_index(r, st);
-   if (r->tab_seen[si] != r->table_version) {
-      if (st != r->table_stream) HIP_TRY(hipStreamWaitEvent(st, r->ev_table, 0));
-      r->tab_seen[si] = r->table_version;
-   }
-   if (r->part.enable && r->part_seen[si] != r->part_version) { // ... and after the build of the partition table
-      if (st != r->part_stream) HIP_TRY(hipStreamWaitEvent(st, r->ev_part, 0));
-      r->part_seen[si] = r->part_version;
-   }
+   HIP_TRY(r->table_fence.wait(st, si));
+   if (r->part.enable) HIP_TRY(r->part_fence.wait(st, si)); // ... and after the build of the partition table
    return MDH_OK;
 }
 // after it: the table buffer is in use on `st` until this point of the stream
 static int table_release(mdh_renderer *r, hipStream_t st)
 {
    const int si = stream_index(r, st);
-   HIP_TRY(hipEventRecord(r->tab_done[r->tab_slot][si], st));
-   r->tab_used[r->tab_slot][si] = true;
-   if (r->part.enable) {
-      HIP_TRY(hipEventRecord(r->part_done[r->part_slot][si], st));
-      r->part_used[r->part_slot][si] = true;
-   }
+   HIP_TRY(r->tab_use.mark(r->tab_slot, st, si));
+   if (r->part.enable) HIP_TRY(r->part_use.mark(r->part_slot, st, si));
    return MDH_OK;
 }
 
@@ -905,26 +887,20 @@ static int commit_scene(mdh_renderer *r, hipStream_t up)
 
    if (t.size() > r->table_cap) { // grow the whole ring (rare: the table only grows with the primitive counts)
       { int dr = drain_streams(r); if (dr != MDH_OK) return dr; }
-      r->table_cap = t.size() + 256;
+      r->tab_use.forget();
       for (int q = 0; q < mdh_renderer::TAB_RING; ++q) {
-         if (r->d_table_ring[q]) HIP_TRY(hipFree(r->d_table_ring[q]));
-         if (r->h_table_ring[q]) HIP_TRY(hipHostFree(r->h_table_ring[q]));
-         HIP_TRY(hipMalloc(&r->d_table_ring[q], r->table_cap * sizeof(float4)));
-         HIP_TRY(hipHostMalloc((void **)&r->h_table_ring[q], r->table_cap * sizeof(float4), hipHostMallocDefault));
-         for (int si = 0; si < mdh_renderer::NSTREAMS; ++si) r->tab_used[q][si] = false;
+         HIP_TRY(r->d_table_ring[q].grow(t.size() + 256));
+         HIP_TRY(r->h_table_ring[q].grow(t.size() + 256));
       }
+      r->table_cap = t.size() + 256; // (last: after a failure the next commit grows the rest)
    }
    const int ns = (r->tab_slot + 1) % mdh_renderer::TAB_RING;
-   for (int si = 0; si < mdh_renderer::NSTREAMS; ++si)
-      if (r->tab_used[ns][si]) { HIP_TRY(hipEventSynchronize(r->tab_done[ns][si])); r->tab_used[ns][si] = false; }
-   memcpy(r->h_table_ring[ns], t.data(), t.size() * sizeof(float4));
-   HIP_TRY(hipMemcpyAsync(r->d_table_ring[ns], r->h_table_ring[ns], t.size() * sizeof(float4), hipMemcpyHostToDevice, up));
-   HIP_TRY(hipEventRecord(r->ev_table, up));
-   r->table_stream = up;
-   ++r->table_version;
-   r->tab_seen[stream_index(r, up)] = r->table_version;
+   HIP_TRY(r->tab_use.retire_on_host(ns));
+   memcpy(r->h_table_ring[ns].ptr, t.data(), t.size() * sizeof(float4));
+   HIP_TRY(hipMemcpyAsync(r->d_table_ring[ns].ptr, r->h_table_ring[ns].ptr, t.size() * sizeof(float4), hipMemcpyHostToDevice, up));
+   HIP_TRY(r->table_fence.signal(up, stream_index(r, up)));
    r->tab_slot = ns;
-   s.table = r->d_table_ring[ns];
+   s.table = r->d_table_ring[ns].ptr;
    s.part_enable = r->part.enable;
    s.part_border = r->part.border_behavior;
    s.part_index_count = r->part.index_count;
@@ -941,7 +917,7 @@ static int commit_scene(mdh_renderer *r, hipStream_t up)
    // the grid's dimensions as the fp32 values the cell index is computed with (uniform conversions the kernels would repeat at every march step)
    for (int a = 0; a < 3; ++a) s.part_fdims[a] = (float)r->part.grid_dimensions[a];
    s.part_fyz = (float)(r->part.grid_dimensions[1] * r->part.grid_dimensions[2]);
-   s.part_table = r->d_part_ring[r->part_slot];
+   s.part_table = r->d_part_ring[r->part_slot].ptr;
    s.part_mask_off = (int)part_table_ints(r);
    s.part_mask_words = part_mask_words(r);
    s.part_bits_f4 = 0; // (the bits are never staged into LDS: mdh_device.h, KScene::part_bits_f4)
@@ -974,7 +950,7 @@ static KProbes make_probes(const mdh_renderer *r)
    p.rshift = log2_or_neg(p.rres); p.ishift = log2_or_neg(p.ires); p.pcx_shift = log2_or_neg(p.pcx);
    p.inv_pcx = log2_or_neg(p.pcx) >= 0 ? 1.0f / (float)p.pcx : 0.0f;
    p.inv_pcy = log2_or_neg(p.pcy) >= 0 ? 1.0f / (float)p.pcy : 0.0f;
-   p.rad = r->d_rad2[r->last]; p.irr = r->d_irr2[r->last];
+   p.rad = r->d_rad2[r->last].ptr; p.irr = r->d_irr2[r->last].ptr;
    own_probes(r, &p.probe_begin, &p.probe_end);
    // the uniform fp32 values of the atlas taps: the kernels' own expressions, evaluated here once (IEEE, one rounding each)
    p.irr_lo = 0.5f / (float)p.ires; p.irr_hi = 1.0f - p.irr_lo;
@@ -1008,21 +984,20 @@ static KVolumetrics make_vol(const mdh_renderer *r, bool enabled, int set)
    v.vw = r->vol.visibility_resolution[0]; v.vh = r->vol.visibility_resolution[1]; v.vz = r->vol.visibility_resolution[2];
    v.sw = r->vol.scattering_resolution[0]; v.sh = r->vol.scattering_resolution[1];
    v.vstep = r->vstep; v.sstep = r->sstep;
-   v.vis = r->d_vis2[set]; v.scat = r->d_scat2[set];
+   v.vis = r->d_vis2[set].ptr; v.scat = r->d_scat2[set].ptr;
    return v;
 }
 
 static int alloc_atlases(mdh_renderer *r)
 {
    for (int s = 0; s < mdh_renderer::NSETS; ++s) {
-      if (r->d_rad2[s]) HIP_TRY(hipFree(r->d_rad2[s]));
-      if (r->d_irr2[s]) HIP_TRY(hipFree(r->d_irr2[s]));
-      r->d_rad2[s] = r->d_irr2[s] = nullptr;
-      HIP_TRY(hipMalloc(&r->d_rad2[s], atlas_bytes(r, MDH_TEX_RADIANCE)));
-      HIP_TRY(hipMalloc(&r->d_irr2[s], atlas_bytes(r, MDH_TEX_IRRADIANCE)));
+      HIP_TRY(r->d_rad2[s].release()); // (released, not only grown: the other format's atlases are smaller or larger)
+      HIP_TRY(r->d_irr2[s].release());
+      HIP_TRY(r->d_rad2[s].grow(atlas_bytes(r, MDH_TEX_RADIANCE)));
+      HIP_TRY(r->d_irr2[s].grow(atlas_bytes(r, MDH_TEX_IRRADIANCE)));
       // Load_Empty_Texture (render_passes.adb:115-116): contents start as zeros here
-      HIP_TRY(hipMemsetAsync(r->d_rad2[s], 0, atlas_bytes(r, MDH_TEX_RADIANCE), r->stream));
-      HIP_TRY(hipMemsetAsync(r->d_irr2[s], 0, atlas_bytes(r, MDH_TEX_IRRADIANCE), r->stream));
+      HIP_TRY(hipMemsetAsync(r->d_rad2[s].ptr, 0, atlas_bytes(r, MDH_TEX_RADIANCE), r->stream));
+      HIP_TRY(hipMemsetAsync(r->d_irr2[s].ptr, 0, atlas_bytes(r, MDH_TEX_IRRADIANCE), r->stream));
    }
    r->main_dirty = true;
    return MDH_OK;
@@ -1038,16 +1013,16 @@ static size_t rad_mips_texels(const mdh_renderer *r)
 static int alloc_rad_mips(mdh_renderer *r)
 {
    for (int s = 0; s < mdh_renderer::NSETS; ++s) {
-      if (r->d_rad_mips[s]) { void *q = r->d_rad_mips[s]; r->d_rad_mips[s] = nullptr; HIP_TRY(hipFree(q)); }
-      if (r->opt_mips && rad_mips_texels(r) > 0) HIP_TRY(hipMalloc(&r->d_rad_mips[s], rad_mips_texels(r) * texel_bytes(r)));
+      HIP_TRY(r->d_rad_mips[s].release());
+      if (r->opt_mips) HIP_TRY(r->d_rad_mips[s].grow(rad_mips_texels(r) * texel_bytes(r))); // (no texels: stays empty)
    }
    return MDH_OK;
 }
 // the levels of set `set`'s radiance atlas on stream st (before the screen pass that reads them)
 static int build_rad_mips(mdh_renderer *r, int set, hipStream_t st)
 {
-   const char *src = (const char *)r->d_rad2[set];
-   char *dst = (char *)r->d_rad_mips[set];
+   const char *src = (const char *)r->d_rad2[set].ptr;
+   char *dst = (char *)r->d_rad_mips[set].ptr;
    for (int res = r->probes.radiance_resolution >> 1; res >= 1; res >>= 1) {
       const long n = (long)probe_total(r) * res * res;
       hipLaunchKernelGGL(k_radiance_mips, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, (const void *)src, (void *)dst, r->opt_atlas, res, (int)n);
@@ -1066,60 +1041,17 @@ extern "C" int32_t mdh_destroy(mdh_renderer *r)
 {
    if (!r) return MDH_OK;
    (void)hipSetDevice(r->device);
-   if (r->probe_stream) (void)hipStreamSynchronize(r->probe_stream);
-   if (r->alt_stream) (void)hipStreamSynchronize(r->alt_stream);
-   if (r->stream) (void)hipStreamSynchronize(r->stream);
-   if (r->query_stream) (void)hipStreamSynchronize(r->query_stream);
-   if (r->vol_stream) (void)hipStreamSynchronize(r->vol_stream);
+   (void)sync_streams(r, SYNC_MAIN | SYNC_PROBE | SYNC_ALT | SYNC_QUERY | SYNC_VOL);
+   if (r->copy_stream) (void)hipStreamSynchronize(r->copy_stream);
    if (r->comm) { ncclComm_t c = r->comm; r->comm = nullptr; (void)rccl_api_destroy(c); }
-   if (r->d_comm_scratch) (void)hipFree(r->d_comm_scratch);
    peer_drop(r);
-   void *ptrs[] = {r->d_table_ring[0], r->d_table_ring[1], r->d_table_ring[2], r->d_table_ring[3], r->d_part_ring[0], r->d_part_ring[1], r->d_part_ring[2], r->d_part_ring[3], r->d_warn, r->d_query, r->d_irr_taps, r->d_rad_steps, r->d_rad_order, r->d_rad_rec, r->d_scr_rec, r->d_rad_hist, r->d_scr_cost, r->d_scr_order[0], r->d_scr_order[1], r->d_scr_hist, r->d_fb2[0], r->d_fb2[1], r->d_gb2[0][0], r->d_gb2[0][1], r->d_gb2[0][2], r->d_gb2[1][0], r->d_gb2[1][1], r->d_gb2[1][2]};
-   for (void *p : ptrs)
-      if (p) (void)hipFree(p);
-   for (int q = 0; q < mdh_renderer::NSETS; ++q)
-      for (void *p : {(void *)r->d_rad2[q], (void *)r->d_irr2[q], (void *)r->d_vis2[q], (void *)r->d_scat2[q], (void *)r->d_rad_mips[q]})
-         if (p) (void)hipFree(p);
    for (auto &p : r->pending) { (void)hipEventDestroy(p.e0); (void)hipEventDestroy(p.e1); }
    for (auto e : r->free_events) (void)hipEventDestroy(e);
-   for (hipEvent_t e : {r->ev_join, r->ev_join_alt, r->ev_table})
-      if (e) (void)hipEventDestroy(e);
-   for (int q = 0; q < mdh_renderer::NSETS; ++q)
-      for (hipEvent_t e : {r->ev_screen[q], r->ev_probe[q], r->ev_vol[q]})
-         if (e) (void)hipEventDestroy(e);
-   for (int q = 0; q < mdh_renderer::TAB_RING; ++q) {
-      if (r->h_table_ring[q]) (void)hipHostFree(r->h_table_ring[q]);
-      for (int si = 0; si < mdh_renderer::NSTREAMS; ++si)
-         if (r->tab_done[q][si]) (void)hipEventDestroy(r->tab_done[q][si]);
-   }
-   for (int q = 0; q < mdh_renderer::PART_RING; ++q)
-      for (int si = 0; si < mdh_renderer::NSTREAMS; ++si)
-         if (r->part_done[q][si]) (void)hipEventDestroy(r->part_done[q][si]);
-   if (r->ev_scr_sort) (void)hipEventDestroy(r->ev_scr_sort);
-   if (r->ev_scr_other) (void)hipEventDestroy(r->ev_scr_other);
-   if (r->ev_scr_rec_write) (void)hipEventDestroy(r->ev_scr_rec_write);
-   for (hipEvent_t e : r->ev_scr_rec_read)
-      if (e) (void)hipEventDestroy(e);
-   if (r->ev_part) (void)hipEventDestroy(r->ev_part);
-   if (r->ev_warn) (void)hipEventDestroy(r->ev_warn);
-   if (r->h_warn) (void)hipHostFree(r->h_warn);
-   if (r->query_stream) (void)hipStreamDestroy(r->query_stream);
-   if (r->vol_stream) (void)hipStreamDestroy(r->vol_stream);
-   for (int q = 0; q < mdh_renderer::WIN_RING; ++q) {
-      if (r->h_win[q]) (void)hipHostFree(r->h_win[q]);
-      if (r->ev_win[q]) (void)hipEventDestroy(r->ev_win[q]);
-   }
-   if (r->copy_stream) { (void)hipStreamSynchronize(r->copy_stream); (void)hipStreamDestroy(r->copy_stream); }
-   if (r->ev_packed) (void)hipEventDestroy(r->ev_packed);
-   for (int q = 0; q < mdh_renderer::FRONT_RING; ++q) {
-      if (r->d_front[q]) (void)hipFree(r->d_front[q]);
-      if (r->h_front[q]) (void)hipHostFree(r->h_front[q]);
-      if (r->ev_front[q]) (void)hipEventDestroy(r->ev_front[q]);
-   }
-   if (r->probe_stream) (void)hipStreamDestroy(r->probe_stream);
-   if (r->alt_stream) (void)hipStreamDestroy(r->alt_stream);
-   if (r->own_stream) (void)hipStreamDestroy(r->own_stream);
+   // the members release what they own; the streams go last, behind every event that was recorded on one
+   const hipStream_t streams[] = {r->query_stream, r->vol_stream, r->copy_stream, r->probe_stream, r->alt_stream, r->own_stream};
    delete r;
+   for (hipStream_t st : streams)
+      if (st) (void)hipStreamDestroy(st);
    return MDH_OK;
 }
 
@@ -1197,45 +1129,40 @@ extern "C" int32_t mdh_create(int32_t width, int32_t height, const mdh_scene_des
       // 3340 vs 3300 Mpix/s at BASELINE config 3)
       TRY_OR_FAIL(hipStreamCreateWithPriority(&r->probe_stream, hipStreamNonBlocking, hi));
       TRY_OR_FAIL(hipStreamCreateWithFlags(&r->alt_stream, hipStreamNonBlocking));
-      for (hipEvent_t *e : {&r->ev_join, &r->ev_join_alt, &r->ev_table}) TRY_OR_FAIL(hipEventCreateWithFlags(e, hipEventDisableTiming));
-      for (int q = 0; q < mdh_renderer::NSETS; ++q)
-         for (hipEvent_t *e : {&r->ev_screen[q], &r->ev_probe[q], &r->ev_vol[q]}) TRY_OR_FAIL(hipEventCreateWithFlags(e, hipEventDisableTiming));
+      TRY_OR_FAIL(create_all(r->ev_join, r->ev_join_alt, r->table_fence));
+      for (int q = 0; q < mdh_renderer::NSETS; ++q) TRY_OR_FAIL(create_all(r->ev_screen[q], r->ev_probe[q], r->ev_vol[q]));
       // (HIP maps a process's streams onto a few hardware queues, four by default: a fifth stream shares one with another
       //  and their work serialises -- measured: light_shafts lost a fifth of its frame rate.  So the volumetric stream exists
       //  only with volumetrics, and the query stream from the first Eval_Distance_To on.)
       if (vol->enabled) TRY_OR_FAIL(hipStreamCreateWithFlags(&r->vol_stream, hipStreamNonBlocking));
-      for (hipEvent_t *e : {&r->ev_part, &r->ev_warn}) TRY_OR_FAIL(hipEventCreateWithFlags(e, hipEventDisableTiming));
-      for (int q = 0; q < mdh_renderer::TAB_RING; ++q)
-         for (int si = 0; si < mdh_renderer::NSTREAMS; ++si) TRY_OR_FAIL(hipEventCreateWithFlags(&r->tab_done[q][si], hipEventDisableTiming));
-      for (int q = 0; q < mdh_renderer::PART_RING; ++q)
-         for (int si = 0; si < mdh_renderer::NSTREAMS; ++si) TRY_OR_FAIL(hipEventCreateWithFlags(&r->part_done[q][si], hipEventDisableTiming));
+      TRY_OR_FAIL(create_all(r->part_fence, r->ev_warn, r->tab_use, r->part_use));
    }
    if ((rc = alloc_atlases(r)) != MDH_OK) return fail(rc);
    size_t px = (size_t)width * height;
    for (int s = 0; s < 2; ++s) {
-      TRY_OR_FAIL(hipMalloc(&r->d_fb2[s], px * sizeof(float4)));
-      TRY_OR_FAIL(hipMemsetAsync(r->d_fb2[s], 0, px * sizeof(float4), r->stream));
+      TRY_OR_FAIL(r->d_fb2[s].grow(px));
+      TRY_OR_FAIL(hipMemsetAsync(r->d_fb2[s].ptr, 0, px * sizeof(float4), r->stream));
    }
    for (int s = 0; s < 2; ++s)
-      for (int q = 0; q < 3; ++q) TRY_OR_FAIL(hipMalloc(&r->d_gb2[s][q], px * 4));
-   TRY_OR_FAIL(hipMalloc(&r->d_warn, 4));
-   TRY_OR_FAIL(hipHostMalloc((void **)&r->h_warn, 4, hipHostMallocDefault));
-   *r->h_warn = 0;
+      for (int q = 0; q < 3; ++q) TRY_OR_FAIL(r->d_gb2[s][q].grow(px * 4));
+   TRY_OR_FAIL(r->d_warn.grow(1));
+   TRY_OR_FAIL(r->h_warn.grow(1));
+   *r->h_warn.ptr = 0;
    size_t vis_n = (size_t)vol->visibility_resolution[0] * vol->visibility_resolution[1] * vol->visibility_resolution[2] * 3;
    size_t scat_n = (size_t)vol->scattering_resolution[0] * vol->scattering_resolution[1];
    if (vis_n / 3 >= (1ull << 32) || scat_n >= (1ull << 32)) { seterr(MDH_E_INVALID, "a volumetrics texture of 2^32 texels or more"); return fail(MDH_E_INVALID); } // (tex_sample: 32-bit texel index)
    for (int s = 0; s < mdh_renderer::NSETS; ++s) {
-      TRY_OR_FAIL(hipMalloc(&r->d_vis2[s], (vis_n ? vis_n : 1) * 4));
-      TRY_OR_FAIL(hipMemsetAsync(r->d_vis2[s], 0, (vis_n ? vis_n : 1) * 4, r->stream));
-      TRY_OR_FAIL(hipMalloc(&r->d_scat2[s], (scat_n ? scat_n : 1) * sizeof(float4)));
-      TRY_OR_FAIL(hipMemsetAsync(r->d_scat2[s], 0, (scat_n ? scat_n : 1) * sizeof(float4), r->stream));
+      TRY_OR_FAIL(r->d_vis2[s].grow(vis_n ? vis_n : 1));
+      TRY_OR_FAIL(hipMemsetAsync(r->d_vis2[s].ptr, 0, (vis_n ? vis_n : 1) * 4, r->stream));
+      TRY_OR_FAIL(r->d_scat2[s].grow(scat_n ? scat_n : 1));
+      TRY_OR_FAIL(hipMemsetAsync(r->d_scat2[s].ptr, 0, (scat_n ? scat_n : 1) * sizeof(float4), r->stream));
    }
    if (r->part.enable) {
       if (part_buffer_ints(r) >= (1ull << 31)) { seterr(MDH_E_INVALID, "a partition table of 2^31 ints or more"); return fail(MDH_E_INVALID); }
       size_t n = part_buffer_ints(r);
       for (int q = 0; q < mdh_renderer::PART_RING; ++q) {
-         TRY_OR_FAIL(hipMalloc(&r->d_part_ring[q], n * 4));
-         TRY_OR_FAIL(hipMemsetAsync(r->d_part_ring[q], 0, n * 4, r->stream));
+         TRY_OR_FAIL(r->d_part_ring[q].grow(n));
+         TRY_OR_FAIL(hipMemsetAsync(r->d_part_ring[q].ptr, 0, n * 4, r->stream));
       }
    }
    TRY_OR_FAIL(hipStreamSynchronize(r->stream));
@@ -1322,12 +1249,10 @@ extern "C" int32_t mdh_set_option(mdh_renderer *r, int32_t option, int32_t value
       r->opt_rad_replay = value ? 1 : 0;
       if (!r->opt_rad_replay) { // the records are dropped (the buffer itself with the streams drained: never under an open frame)
          r->rad_rec_valid = false;
-         if (r->d_rad_rec && !r->in_frame) {
+         if (r->d_rad_rec.ptr && !r->in_frame) {
             HIP_TRY(hipSetDevice(r->device));
-            if (r->probe_stream) HIP_TRY(hipStreamSynchronize(r->probe_stream));
-            HIP_TRY(hipStreamSynchronize(r->stream));
-            void *q = r->d_rad_rec; r->d_rad_rec = nullptr; r->rad_rec_cap = 0;
-            HIP_TRY(hipFree(q));
+            { int sr = sync_streams(r, SYNC_PROBE | SYNC_MAIN); if (sr != MDH_OK) return sr; }
+            HIP_TRY(r->d_rad_rec.release());
          }
       }
       break;
@@ -1337,13 +1262,12 @@ extern "C" int32_t mdh_set_option(mdh_renderer *r, int32_t option, int32_t value
       if (!r->opt_scr_replay) { // the records are dropped (the buffer itself with the streams drained: never under an open frame)
          r->scr_rec_valid = false;
          r->scr_seen_valid = false;
-         if (r->d_scr_rec && !r->in_frame) {
+         if (r->d_scr_rec.ptr && !r->in_frame) {
             HIP_TRY(hipSetDevice(r->device));
             int drc = drain_streams(r);
             if (drc != MDH_OK) return drc;
-            void *q = r->d_scr_rec; r->d_scr_rec = nullptr; r->scr_rec_cap = 0;
-            for (bool &b : r->scr_rec_read_pending) b = false;
-            HIP_TRY(hipFree(q));
+            r->scr_rec_reads.forget();
+            HIP_TRY(r->d_scr_rec.release());
          }
       }
       break;
@@ -1865,7 +1789,7 @@ extern "C" int32_t mdh_update_partitioning(mdh_renderer *r, int32_t method)
    if (r->in_frame) return seterr(MDH_E_STATE, "a frame is open");
    // The build goes where the table is used first -- the probe stream when frames are kept in flight -- into the
    // next buffer of the ring, and nothing waits on the host: frames in flight keep their buffer, later launches
-   // on any stream are ordered after ev_part (table_acquire).
+   // on any stream are ordered after part_fence (table_acquire).
    const bool piped = r->opt_overlap && r->stream == r->own_stream && r->opt_mode == 0;
    hipStream_t up = piped ? r->probe_stream : r->stream;
    int rc = ensure_committed(r, up);
@@ -1876,13 +1800,9 @@ extern "C" int32_t mdh_update_partitioning(mdh_renderer *r, int32_t method)
    }
    const int sup = stream_index(r, up);
    const int ns = (r->part_slot + 1) % mdh_renderer::PART_RING;
-   for (int si = 0; si < mdh_renderer::NSTREAMS; ++si)
-      if (r->part_used[ns][si]) { // the last kernels that read that buffer (four builds ago)
-         if (si != sup) HIP_TRY(hipStreamWaitEvent(up, r->part_done[ns][si], 0));
-         r->part_used[ns][si] = false;
-      }
+   HIP_TRY(r->part_use.retire_on_stream(ns, up, sup)); // the last kernels that read that buffer (four builds ago)
    // the warning counter is shared by consecutive builds: behind the previous build and its read-back
-   if (r->part_version && r->part_stream != up) HIP_TRY(hipStreamWaitEvent(up, r->ev_warn, 0));
+   if (r->part_fence.version && r->part_fence.by != up) HIP_TRY(hipStreamWaitEvent(up, r->ev_warn.ev, 0));
    PartBuildArgs a;
    a.method = method;
    const int *d = r->part.grid_dimensions;
@@ -1894,34 +1814,31 @@ extern "C" int32_t mdh_update_partitioning(mdh_renderer *r, int32_t method)
       a.off[i] = method == 2 ? r->pg_offset[i] : r->part.grid_offset[i];
    }
    a.gpu_diag = r->part_gpu_diag;
-   a.table = r->d_part_ring[ns];
-   a.warnings = r->d_warn;
+   a.table = r->d_part_ring[ns].ptr;
+   a.warnings = r->d_warn.ptr;
    // The builders write a cell's counts and the candidates it found, nothing else: entries behind them and cells
    // outside the builder's grid (GPU_Fast on odd dimensions) keep what the table held before, in the
    // reference's single buffer.  So the next buffer starts as a copy of the current one (tens of KiB).
    const size_t total = part_buffer_ints(r); // (the lists and their bits)
    const int cells = a.gx * a.gy * a.gz;
    if ((rc = table_acquire(r, up)) != MDH_OK) return rc; // (also orders `up` after the previous build)
-   HIP_TRY(hipMemcpyAsync(r->d_part_ring[ns], r->d_part_ring[r->part_slot], total * 4, hipMemcpyDeviceToDevice, up));
-   HIP_TRY(hipMemsetAsync(r->d_warn, 0, 4, up));
+   HIP_TRY(hipMemcpyAsync(r->d_part_ring[ns].ptr, r->d_part_ring[r->part_slot].ptr, total * 4, hipMemcpyDeviceToDevice, up));
+   HIP_TRY(hipMemsetAsync(r->d_warn.ptr, 0, 4, up));
    if (cells > 0) {
       if ((rc = launch_kernel_ptr(table_kernel(r, GK_k_partition_build), dim3(cells), dim3(64), lds_bytes(r), up, r->ks, a)) != MDH_OK) return rc; // one wavefront per cell
       HIP_TRY(hipGetLastError());
    }
    // the lists once more as bits, for every cell (cells the builder left alone keep their lists, and so their bits)
-   hipLaunchKernelGGL(k_partition_bits, dim3((r->part_cells + 63) / 64), dim3(64), lds_bytes(r), up, r->ks, r->d_part_ring[ns]);
+   hipLaunchKernelGGL(k_partition_bits, dim3((r->part_cells + 63) / 64), dim3(64), lds_bytes(r), up, r->ks, r->d_part_ring[ns].ptr);
    HIP_TRY(hipGetLastError());
    if ((rc = table_release(r, up)) != MDH_OK) return rc; // (the copy read the current buffer)
-   HIP_TRY(hipMemcpyAsync(r->h_warn, r->d_warn, 4, hipMemcpyDeviceToHost, up));
-   HIP_TRY(hipEventRecord(r->ev_warn, up));
+   HIP_TRY(hipMemcpyAsync(r->h_warn.ptr, r->d_warn.ptr, 4, hipMemcpyDeviceToHost, up));
+   HIP_TRY(hipEventRecord(r->ev_warn.ev, up));
    r->warn_pending = true;
-   HIP_TRY(hipEventRecord(r->ev_part, up));
-   r->part_stream = up;
+   HIP_TRY(r->part_fence.signal(up, sup));
    ++r->march_inputs; // (the partition variants march through the new table: any record of their rays would be stale)
-   ++r->part_version;
-   r->part_seen[sup] = r->part_version;
    r->part_slot = ns;
-   r->ks.part_table = r->d_part_ring[ns];
+   r->ks.part_table = r->d_part_ring[ns].ptr;
    return MDH_OK;
 }
 
@@ -1932,21 +1849,19 @@ static int window_slot(mdh_renderer *r, int rank, int world, unsigned **out)
    const size_t bytes = (size_t)r->W * r->H * 4;
    const bool owner_changed = r->win_owner[0] != rank || r->win_owner[1] != world;
    if (owner_changed) { // other ranks' tiles read 0, as in the framebuffer: clear every slot once nothing writes them any more
-      if (r->probe_stream) HIP_TRY(hipStreamSynchronize(r->probe_stream));
-      if (r->alt_stream) HIP_TRY(hipStreamSynchronize(r->alt_stream));
-      HIP_TRY(hipStreamSynchronize(r->stream));
+      { int sr = sync_streams(r, SYNC_PROBE | SYNC_ALT | SYNC_MAIN); if (sr != MDH_OK) return sr; }
       for (int q = 0; q < mdh_renderer::WIN_RING; ++q)
-         if (r->h_win[q]) memset(r->h_win[q], 0, bytes);
+         if (r->h_win[q].ptr) memset(r->h_win[q].ptr, 0, bytes);
       r->win_owner[0] = rank; r->win_owner[1] = world;
    }
    const int slot = (int)(r->win_passes % mdh_renderer::WIN_RING);
-   if (!r->h_win[slot]) {
-      HIP_TRY(hipHostMalloc((void **)&r->h_win[slot], bytes, hipHostMallocDefault));
-      memset(r->h_win[slot], 0, bytes);
+   if (!r->h_win[slot].ptr) {
+      HIP_TRY(r->h_win[slot].grow(bytes / 4));
+      memset(r->h_win[slot].ptr, 0, bytes);
    }
    r->win_passes += 1;
    r->win_valid = true;
-   *out = r->h_win[slot];
+   *out = r->h_win[slot].ptr;
    return MDH_OK;
 }
 
@@ -1957,7 +1872,7 @@ static bool room_census(const mdh_renderer *r)
           r->ks.tcount[PK_TRIANGLE] == 0;
 }
 // MDH_OPT_RADIANCE_MIPS: does the screen pass over atlas set `set` read the levels of its radiance atlas (KProbes::rad_mips)?
-static bool rad_mips_used(const mdh_renderer *r, int set) { return r->opt_mips && r->opt_mode == 0 && r->opt_spec != 0 && r->d_rad_mips[set]; }
+static bool rad_mips_used(const mdh_renderer *r, int set) { return r->opt_mips && r->opt_mode == 0 && r->opt_spec != 0 && r->d_rad_mips[set].ptr; }
 
 // MDH_OPT_RADIANCE_REPLAY.  The variants built with record and replay kernels: the brute-force scan and the census of the rooms,
 // with and without power-of-two atlases (kernel_ptr).  The partition, global-residency / BVH and user-defined-kind variants
@@ -1969,7 +1884,7 @@ static mdh_renderer::RadRecKey rad_rec_key(const mdh_renderer *r, const PassKern
 {
    mdh_renderer::RadRecKey q = {};
    const KProbes p = make_probes(r);
-   q.geometry = r->geometry_edits; q.inputs = r->march_inputs; q.part_version = r->part_version;
+   q.geometry = r->geometry_edits; q.inputs = r->march_inputs; q.part_version = r->part_fence.version;
    q.grid[0] = p.gx; q.grid[1] = p.gy; q.grid[2] = p.gz;
    q.spacing[0] = p.sx; q.spacing[1] = p.sy; q.spacing[2] = p.sz;
    q.res[0] = p.rres; q.res[1] = p.ires; q.pc[0] = p.pcx; q.pc[1] = p.pcy;
@@ -1986,7 +1901,7 @@ static int rad_replay_pick(const mdh_renderer *r, const PassKernel &k)
 {
    if (!r->opt_rad_replay || !rad_replay_built(k)) return 0;
    const mdh_renderer::RadRecKey now = rad_rec_key(r, k);
-   if (r->rad_rec_valid && r->d_rad_rec && now == r->rad_rec_key) return 2;
+   if (r->rad_rec_valid && r->d_rad_rec.ptr && now == r->rad_rec_key) return 2;
    // (the recording kernel parks five rows more than the marching one: a table that commit_scene fitted into the workgroup's LDS
    //  budget beside MDH_PARK_DWORDS rows may not fit beside these -- such a scene keeps marching, and the counters say so)
    if (r->rad_seen_valid && now == r->rad_seen_key && now.rays > 0 && now.rays < (1l << 31) &&
@@ -2003,7 +1918,7 @@ static int rad_replay_pick(const mdh_renderer *r, const PassKernel &k)
 static bool scr_replay_built(const PassKernel &k) { return MDH_SCR_REPLAY_BUILT && !k.jit && k.mode == 0 && !k.alt && (k.pf & ~(MDH_PF_ROOM | MDH_PF_POW2)) == 0; }
 // What the key holds, and what every entry point does to it:
 //   mdh_set_primitive, mdh_add_primitive                 geometry_edits                       end the replay
-//   mdh_update_partitioning, MDH_OPT_JIT, _TABLE_RESIDENCY, _TRIANGLE_BVH   march_inputs / part_version   end it (and pick a variant that only marches)
+//   mdh_update_partitioning, MDH_OPT_JIT, _TABLE_RESIDENCY, _TRIANGLE_BVH   march_inputs / part_fence.version   end it (and pick a variant that only marches)
 //   mdh_set_camera_position / _orientation               cam, by value                        a new value ends it, the held value does not
 //   MDH_OPT_RANK, _WORLD, _SCREEN_MODE, _INDIRECT_SPECULAR, _AO_STEPS, _GBUFFER, _WINDOW, _SCREEN_SPLIT   by value   a new value ends it
 //   mdh_set_material                                     reflect_edits                        only when a material in use goes below roughness 0.75
@@ -2033,7 +1948,7 @@ static int scr_replay_pick(const mdh_renderer *r, const PassKernel &k)
 {
    if (!r->opt_scr_replay || !scr_replay_built(k)) return 0;
    const mdh_renderer::ScrRecKey now = scr_rec_key(r, k);
-   if (r->scr_rec_valid && r->d_scr_rec && now == r->scr_rec_key) return 2;
+   if (r->scr_rec_valid && r->d_scr_rec.ptr && now == r->scr_rec_key) return 2;
    if (r->scr_rec_no_memory && r->scr_seen_valid && now == r->scr_seen_key) return 0; // (the allocation failed for this key: not tried again, and no stream drained, in every frame)
    // (the recording kernel parks eleven rows more than the marching one: a table that commit_scene fitted into the workgroup's
    //  LDS budget beside MDH_PARK_DWORDS rows may not fit beside these -- such a scene keeps marching, and the counters say so;
@@ -2147,8 +2062,8 @@ static int pass_begin(PassRun &p)
    mdh_renderer *r = p.r;
    if (p.fbix < 0) p.fbix = r->fb_last;
    p.pr = make_probes(r);
-   p.pr.rad = r->d_rad2[p.dst];
-   p.pr.irr = r->d_irr2[p.pass == MDH_PASS_RADIANCE ? p.src : p.dst];
+   p.pr.rad = r->d_rad2[p.dst].ptr;
+   p.pr.irr = r->d_irr2[p.pass == MDH_PASS_RADIANCE ? p.src : p.dst].ptr;
    p.cam = make_camera(r);
    p.k = pick_kernel(r, p.pass, p.dst);
    if (p.k.jit) { // a scene hiprtc cannot build falls back to the interpreter for good (the reason stays in mdh_last_error, MDH_OPT_JIT reads 0 afterwards)
@@ -2211,43 +2126,30 @@ static int pass_radiance(PassRun &p)
    // the rays in the order of the previous pass's primary-march lengths (RadOrder, mdh_kernels.h)
    RadOrder ro = {nullptr, nullptr, (int)rays, nullptr};
    // MDH_OPT_RADIANCE_REPLAY: the pass that writes the rays' records, or reads them (pick_kernel chose: p.k.rec)
-   if (p.k.rec == 1 && rays > r->rad_rec_cap) { // (the buffer is only ever used by radiance passes, on the probe stream or the main stream)
-      if (r->probe_stream) HIP_TRY(hipStreamSynchronize(r->probe_stream));
-      HIP_TRY(hipStreamSynchronize(r->stream));
-      r->rad_rec_cap = 0;
+   if (p.k.rec == 1 && (size_t)rays > r->d_rad_rec.cap) { // (the buffer is only ever used by radiance passes, on the probe stream or the main stream)
+      { int sr = sync_streams(r, SYNC_PROBE | SYNC_MAIN); if (sr != MDH_OK) return sr; }
       r->rad_rec_valid = false;
-      { void *q = r->d_rad_rec; r->d_rad_rec = nullptr; if (q) HIP_TRY(hipFree(q)); }
-      HIP_TRY(hipMalloc(&r->d_rad_rec, (size_t)rays * sizeof(RayRecord)));
-      r->rad_rec_cap = rays;
+      HIP_TRY(r->d_rad_rec.grow((size_t)rays));
    }
-   if (p.k.rec) ro.rec = r->d_rad_rec;
+   if (p.k.rec) ro.rec = r->d_rad_rec.ptr;
    // (chunks of whole workgroup strides, at most MDH_RO_MAX_CHUNKS of them)
    const long ro_chunk = std::max(2048l, ((rays + MDH_RO_MAX_CHUNKS - 1) / MDH_RO_MAX_CHUNKS + 1023) / 1024 * 1024);
    const int ro_chunks = (int)((rays + ro_chunk - 1) / ro_chunk);
    if (r->opt_rad_order && rays >= 8192 && rays < (1l << 31)) {
-      if (rays > r->rad_rays_cap) {
+      if ((size_t)rays > r->d_rad_steps.cap) {
          // (the buffers are only ever used by radiance passes, on the probe stream or the main stream)
-         if (r->probe_stream) HIP_TRY(hipStreamSynchronize(r->probe_stream));
-         HIP_TRY(hipStreamSynchronize(r->stream));
-         r->rad_rays_cap = 0;
+         { int sr = sync_streams(r, SYNC_PROBE | SYNC_MAIN); if (sr != MDH_OK) return sr; }
          r->rad_order_rays = 0;
-         { void *q = r->d_rad_steps; r->d_rad_steps = nullptr; if (q) HIP_TRY(hipFree(q)); }
-         { void *q = r->d_rad_order; r->d_rad_order = nullptr; if (q) HIP_TRY(hipFree(q)); }
-         { void *q = r->d_rad_hist; r->d_rad_hist = nullptr; if (q) HIP_TRY(hipFree(q)); }
-         HIP_TRY(hipMalloc(&r->d_rad_steps, rays));
-         HIP_TRY(hipMalloc(&r->d_rad_order, rays * sizeof(unsigned)));
-         HIP_TRY(hipMalloc(&r->d_rad_hist, 256 * MDH_RO_MAX_CHUNKS * sizeof(unsigned)));
-         r->rad_rays_cap = rays;
-         r->rad_order_rays = 0;
+         HIP_TRY(create_all(r->d_rad_steps.sized((size_t)rays), r->d_rad_order.sized((size_t)rays), r->d_rad_hist.sized(256 * MDH_RO_MAX_CHUNKS)));
       }
       const bool have = r->rad_order_rays == rays && r->rad_order_begin == pr.probe_begin;
-      if (have) { ro.order = r->d_rad_order; n = rays; }
+      if (have) { ro.order = r->d_rad_order.ptr; n = rays; }
       // A probe ray's march changes with the scene's geometry, not with time, lights or materials: the rays are sorted
       // again when primitives were set or added since (at most every MDH_RAD_RESORT_MOVING passes: a stale order costs
       // speed only, and three more launches per frame cost the host of a 0.4 ms frame 10 %) and every MDH_RAD_RESORT
       // passes besides -- the sort kernels (20 us) are out of almost every frame.
       ++r->rad_order_age;
-      if (!have || r->rad_order_age >= MDH_RAD_RESORT || (r->rad_order_scene != r->geometry_edits && r->rad_order_age >= MDH_RAD_RESORT_MOVING)) ro.steps = r->d_rad_steps;
+      if (!have || r->rad_order_age >= MDH_RAD_RESORT || (r->rad_order_scene != r->geometry_edits && r->rad_order_age >= MDH_RAD_RESORT_MOVING)) ro.steps = r->d_rad_steps.ptr;
    }
    n = (n + 63) / 64 * 64;
    const int blocks = (int)((n + MDH_BLOCK - 1) / MDH_BLOCK);
@@ -2265,9 +2167,9 @@ static int pass_radiance(PassRun &p)
       ++r->rad_replay_stats[p.k.rec];
    }
    if (ro.steps) { // the next pass's order from this pass's step counts
-      hipLaunchKernelGGL(k_rad_hist, dim3(ro_chunks), dim3(256), 0, st, (const unsigned char *)r->d_rad_steps, (int)rays, (int)ro_chunk, r->d_rad_hist);
-      hipLaunchKernelGGL(k_rad_scan, dim3(1), dim3(256), 0, st, r->d_rad_hist, ro_chunks);
-      hipLaunchKernelGGL(k_rad_scatter, dim3(ro_chunks), dim3(256), 0, st, (const unsigned char *)r->d_rad_steps, (int)rays, (int)ro_chunk, (const unsigned *)r->d_rad_hist, r->d_rad_order);
+      hipLaunchKernelGGL(k_rad_hist, dim3(ro_chunks), dim3(256), 0, st, (const unsigned char *)r->d_rad_steps.ptr, (int)rays, (int)ro_chunk, r->d_rad_hist.ptr);
+      hipLaunchKernelGGL(k_rad_scan, dim3(1), dim3(256), 0, st, r->d_rad_hist.ptr, ro_chunks);
+      hipLaunchKernelGGL(k_rad_scatter, dim3(ro_chunks), dim3(256), 0, st, (const unsigned char *)r->d_rad_steps.ptr, (int)rays, (int)ro_chunk, (const unsigned *)r->d_rad_hist.ptr, r->d_rad_order.ptr);
       r->rad_order_rays = rays;
       r->rad_order_begin = pr.probe_begin;
       r->rad_order_age = 0;
@@ -2291,15 +2193,11 @@ static int pass_irradiance(PassRun &p)
 #endif
    if (pr.ires * pr.ires <= 64 && MDH_IRR_BLOCK == 256 && n > 0) { // (k_irradiance: a channel per wavefront, the taps through device memory)
       const size_t need = (size_t)n * 6 * MDH_IRR_CHANNELS_PLANE(pr.rres * pr.rres);
-      if (need > r->irr_taps_cap) { // (the scratch of irradiance passes only, which follow one another on their stream)
-         if (r->probe_stream) HIP_TRY(hipStreamSynchronize(r->probe_stream));
-         HIP_TRY(hipStreamSynchronize(r->stream));
-         r->irr_taps_cap = 0;
-         { void *q = r->d_irr_taps; r->d_irr_taps = nullptr; if (q) HIP_TRY(hipFree(q)); }
-         HIP_TRY(hipMalloc(&r->d_irr_taps, need * sizeof(float)));
-         r->irr_taps_cap = need;
+      if (need > r->d_irr_taps.cap) { // (the scratch of irradiance passes only, which follow one another on their stream)
+         { int sr = sync_streams(r, SYNC_PROBE | SYNC_MAIN); if (sr != MDH_OK) return sr; }
+         HIP_TRY(r->d_irr_taps.grow(need));
       }
-      tap_planes = r->d_irr_taps;
+      tap_planes = r->d_irr_taps.ptr;
       lds = MDH_IRR_CHANNELS_LDS;
    } else
    if (pr.ires * pr.ires <= 64 && lds > (size_t)4 * MDH_IRR_CHUNK * sizeof(float4)) lds = (size_t)4 * MDH_IRR_CHUNK * sizeof(float4); // two chunk buffers
@@ -2311,7 +2209,7 @@ static int pass_irradiance(PassRun &p)
       }
    }
    // (hysteresis: the previous frame's irradiance is set `src` -- the same set when the pass runs in place)
-   if (n > 0) hipLaunchKernelGGL(k_irradiance, dim3(n), dim3(MDH_IRR_BLOCK), lds, p.st, pr, (const void *)r->d_irr2[p.src], (float)r->opt_hyst / 1000.0f, tap_planes);
+   if (n > 0) hipLaunchKernelGGL(k_irradiance, dim3(n), dim3(MDH_IRR_BLOCK), lds, p.st, pr, (const void *)r->d_irr2[p.src].ptr, (float)r->opt_hyst / 1000.0f, tap_planes);
    return MDH_OK;
 }
 
@@ -2367,8 +2265,8 @@ static int screen_sort_tiles(PassRun &p, const ScreenArgs &a)
    //  orders them against this stream when no probe passes run: wait for what that stream holds)
    hipStream_t other = st == r->alt_stream ? r->stream : r->alt_stream;
    if (other && other != st && r->scr_order_cur >= 0) {
-      HIP_TRY(hipEventRecord(r->ev_scr_other, other));
-      HIP_TRY(hipStreamWaitEvent(st, r->ev_scr_other, 0));
+      HIP_TRY(hipEventRecord(r->ev_scr_other.ev, other));
+      HIP_TRY(hipStreamWaitEvent(st, r->ev_scr_other.ev, 0));
    }
    const long chunk = std::max(2048l, (((long)own_tiles + MDH_RO_MAX_CHUNKS - 1) / MDH_RO_MAX_CHUNKS + 1023) / 1024 * 1024);
    const int chunks = (int)((own_tiles + chunk - 1) / chunk);
@@ -2382,17 +2280,15 @@ static int screen_sort_tiles(PassRun &p, const ScreenArgs &a)
    const long probe_rays = r->opt_mode == 0 ? (long)(pr.probe_end - pr.probe_begin) * pr.rres * pr.rres : 0;
    const bool probe_heavy = probe_rays * 10 >= (long)own_tiles * 64;
    const int floor_permille = r->frame_pipelined && r->in_frame_passes && probe_heavy ? 2000 : 0; // (thousandths of the median)
-   hipLaunchKernelGGL(k_rad_hist, dim3(chunks), dim3(256), 0, st, (const unsigned char *)r->d_scr_cost, own_tiles, (int)chunk, r->d_scr_hist);
+   hipLaunchKernelGGL(k_rad_hist, dim3(chunks), dim3(256), 0, st, (const unsigned char *)r->d_scr_cost.ptr, own_tiles, (int)chunk, r->d_scr_hist.ptr);
    if (floor_permille > 0) {
-      hipLaunchKernelGGL(k_order_floor, dim3(chunks), dim3(256), 0, st, r->d_scr_cost, own_tiles, (int)chunk, (const unsigned *)r->d_scr_hist, chunks, floor_permille);
-      hipLaunchKernelGGL(k_rad_hist, dim3(chunks), dim3(256), 0, st, (const unsigned char *)r->d_scr_cost, own_tiles, (int)chunk, r->d_scr_hist);
+      hipLaunchKernelGGL(k_order_floor, dim3(chunks), dim3(256), 0, st, r->d_scr_cost.ptr, own_tiles, (int)chunk, (const unsigned *)r->d_scr_hist.ptr, chunks, floor_permille);
+      hipLaunchKernelGGL(k_rad_hist, dim3(chunks), dim3(256), 0, st, (const unsigned char *)r->d_scr_cost.ptr, own_tiles, (int)chunk, r->d_scr_hist.ptr);
    }
-   hipLaunchKernelGGL(k_rad_scan, dim3(1), dim3(256), 0, st, r->d_scr_hist, chunks);
-   hipLaunchKernelGGL(k_order_scatter_stable, dim3(chunks), dim3(256), 0, st, (const unsigned char *)r->d_scr_cost, own_tiles, (int)chunk, (const unsigned *)r->d_scr_hist, r->d_scr_order[nb]);
+   hipLaunchKernelGGL(k_rad_scan, dim3(1), dim3(256), 0, st, r->d_scr_hist.ptr, chunks);
+   hipLaunchKernelGGL(k_order_scatter_stable, dim3(chunks), dim3(256), 0, st, (const unsigned char *)r->d_scr_cost.ptr, own_tiles, (int)chunk, (const unsigned *)r->d_scr_hist.ptr, r->d_scr_order[nb].ptr);
    HIP_TRY(hipGetLastError());
-   HIP_TRY(hipEventRecord(r->ev_scr_sort, st));
-   ++r->scr_sort_version;
-   r->scr_sort_seen[si_st] = r->scr_sort_version;
+   HIP_TRY(r->scr_sorted.signal(st, si_st));
    r->scr_order_cur = nb;
    r->scr_order_n = own_tiles; r->scr_order_rank = a.rank; r->scr_order_world = a.world;
    r->scr_order_age = 0;
@@ -2417,9 +2313,9 @@ static int pass_screen(PassRun &p)
    if (rad_mips_used(r, p.dst)) { // MDH_OPT_RADIANCE_MIPS: the levels of the atlas this pass reads
       int mrc = build_rad_mips(r, p.dst, st);
       if (mrc != MDH_OK) return mrc;
-      pr.rad_mips = r->d_rad_mips[p.dst];
+      pr.rad_mips = r->d_rad_mips[p.dst].ptr;
    }
-   a.fb = r->d_fb2[fbix]; a.gb_index = (int *)r->d_gb2[fbix][0]; a.gb_t = (float *)r->d_gb2[fbix][1]; a.gb_steps = (int *)r->d_gb2[fbix][2];
+   a.fb = r->d_fb2[fbix].ptr; a.gb_index = (int *)r->d_gb2[fbix][0].ptr; a.gb_t = (float *)r->d_gb2[fbix][1].ptr; a.gb_steps = (int *)r->d_gb2[fbix][2].ptr;
    a.window = nullptr;
    if (r->opt_window == 1 || (r->opt_window == 2 && r->swaps > 0)) { // the window's pixels straight into pinned host memory (mdh_swap_buffers)
       int wrc = window_slot(r, a.rank, a.world, &a.window);
@@ -2427,7 +2323,7 @@ static int pass_screen(PassRun &p)
    }
    // other ranks' tiles read 0: cleared when the buffer last held another rank's (or a whole) frame, not every frame
    if (a.world > 1 && (r->fb_owner[fbix][0] != a.rank || r->fb_owner[fbix][1] != a.world))
-      HIP_TRY(hipMemsetAsync(r->d_fb2[fbix], 0, (size_t)r->W * r->H * sizeof(float4), st));
+      HIP_TRY(hipMemsetAsync(r->d_fb2[fbix].ptr, 0, (size_t)r->W * r->H * sizeof(float4), st));
    r->fb_owner[fbix][0] = a.rank; r->fb_owner[fbix][1] = a.world;
    const int own_tiles = (a.n_tiles - a.rank + a.world - 1) / a.world;
    a.n_own = own_tiles;
@@ -2437,22 +2333,15 @@ static int pass_screen(PassRun &p)
    bool sort_after = false;
    if (r->opt_scr_order && own_tiles >= 2048) {
       const int si_st = stream_index(r, st);
-      if (!r->d_scr_cost) {
-         HIP_TRY(hipMalloc(&r->d_scr_cost, a.n_tiles));
-         for (int q = 0; q < 2; ++q) HIP_TRY(hipMalloc(&r->d_scr_order[q], (size_t)a.n_tiles * sizeof(unsigned)));
-         HIP_TRY(hipMalloc(&r->d_scr_hist, 256 * MDH_RO_MAX_CHUNKS * sizeof(unsigned)));
-         HIP_TRY(hipEventCreateWithFlags(&r->ev_scr_sort, hipEventDisableTiming));
-         HIP_TRY(hipEventCreateWithFlags(&r->ev_scr_other, hipEventDisableTiming));
-      }
+      if (!r->d_scr_cost.ptr)
+         HIP_TRY(create_all(r->d_scr_cost.sized(a.n_tiles), r->d_scr_order[0].sized(a.n_tiles), r->d_scr_order[1].sized(a.n_tiles),
+                            r->d_scr_hist.sized(256 * MDH_RO_MAX_CHUNKS), r->scr_sorted, r->ev_scr_other));
       float cam_now[12];
       memcpy(cam_now, r->cam_pos, 12); memcpy(cam_now + 3, r->cam_m, 36);
       const bool have = r->scr_order_cur >= 0 && r->scr_order_n == own_tiles && r->scr_order_rank == a.rank && r->scr_order_world == a.world;
       if (have) {
-         a.order = r->d_scr_order[r->scr_order_cur];
-         if (r->scr_sort_seen[si_st] != r->scr_sort_version) { // the sort ran on another stream
-            HIP_TRY(hipStreamWaitEvent(st, r->ev_scr_sort, 0));
-            r->scr_sort_seen[si_st] = r->scr_sort_version;
-         }
+         a.order = r->d_scr_order[r->scr_order_cur].ptr;
+         HIP_TRY(r->scr_sorted.wait(st, si_st)); // (the sort may have run on another stream)
       }
       // which tiles are slow follows the camera and the geometry: sorted again when either changed since (at most every
       // MDH_RAD_RESORT_MOVING passes: a stale order costs speed only) and every MDH_RAD_RESORT passes besides
@@ -2460,7 +2349,7 @@ static int pass_screen(PassRun &p)
       const bool moved = memcmp(cam_now, r->scr_order_cam, sizeof cam_now) != 0 || r->scr_order_geom != r->geometry_edits;
       if (!have || r->scr_order_age >= MDH_RAD_RESORT || (moved && r->scr_order_age >= MDH_RAD_RESORT_MOVING)) {
          sort_after = true;
-         a.cost = r->d_scr_cost;
+         a.cost = r->d_scr_cost.ptr;
          memcpy(r->scr_order_cam, cam_now, sizeof cam_now);
       }
    } else
@@ -2475,39 +2364,24 @@ static int pass_screen(PassRun &p)
    // MDH_OPT_SCREEN_REPLAY: the pass that writes the pixels' records, or reads them (pick_kernel chose: p.k.rec)
    a.rec = nullptr;
    if (own_tiles <= 0) p.k.rec = 0;
-   if (p.k.rec == 1 && (long)own_tiles * 64 > r->scr_rec_cap) {
+   if (p.k.rec == 1 && (size_t)own_tiles * 64 > r->d_scr_rec.cap) {
       int drc = drain_streams(r);
       if (drc != MDH_OK) return drc;
-      r->scr_rec_cap = 0;
       r->scr_rec_valid = false;
-      for (bool &b : r->scr_rec_read_pending) b = false;
-      { void *q = r->d_scr_rec; r->d_scr_rec = nullptr; if (q) HIP_TRY(hipFree(q)); }
-      if (!r->ev_scr_rec_write) {
-         HIP_TRY(hipEventCreateWithFlags(&r->ev_scr_rec_write, hipEventDisableTiming));
-         for (hipEvent_t &e : r->ev_scr_rec_read) HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-      }
-      if (hipMalloc(&r->d_scr_rec, (size_t)own_tiles * 64 * sizeof(PixelRecord)) == hipSuccess) r->scr_rec_cap = (long)own_tiles * 64;
-      else { // no memory for the records: the renderer keeps marching, and the counters say so
+      r->scr_rec_reads.forget();
+      HIP_TRY(create_all(r->scr_rec_written, r->scr_rec_reads)); // (only with the first records: events are scarce, mdh_create)
+      if (r->d_scr_rec.grow((size_t)own_tiles * 64) != hipSuccess) { // no memory for the records: the renderer keeps marching, and the counters say so
          r->scr_rec_no_memory = true;
          (void)hipGetLastError();
-         r->d_scr_rec = nullptr;
          p.k.rec = 0;
          if (!(p.kernel = kernel_ptr(p.k))) return seterr(MDH_E_INVALID, "no kernel built for this pass's variant");
       }
    }
    if (p.k.rec) {
       const int si_st = stream_index(r, st);
-      a.rec = r->d_scr_rec;
-      if (r->scr_rec_version && r->scr_rec_seen[si_st] != r->scr_rec_version) { // the records were written on another stream
-         HIP_TRY(hipStreamWaitEvent(st, r->ev_scr_rec_write, 0));
-         r->scr_rec_seen[si_st] = r->scr_rec_version;
-      }
-      if (p.k.rec == 1) // ... and may still be read on another
-         for (int si = 0; si < mdh_renderer::NSTREAMS; ++si)
-            if (r->scr_rec_read_pending[si]) {
-               if (si != si_st) HIP_TRY(hipStreamWaitEvent(st, r->ev_scr_rec_read[si], 0));
-               r->scr_rec_read_pending[si] = false;
-            }
+      a.rec = r->d_scr_rec.ptr;
+      HIP_TRY(r->scr_rec_written.wait(st, si_st)); // (the records may have been written on another stream)
+      if (p.k.rec == 1) HIP_TRY(r->scr_rec_reads.retire_on_stream(0, st, si_st)); // ... and may still be read on another
    }
    if (own_tiles > 0) {
       const long waves = (long)own_tiles << a.split;
@@ -2522,11 +2396,9 @@ static int pass_screen(PassRun &p)
       const mdh_renderer::ScrRecKey now = scr_rec_key(r, p.k);
       if (p.k.rec == 1) {
          r->scr_rec_key = now; r->scr_rec_valid = true;
-         HIP_TRY(hipEventRecord(r->ev_scr_rec_write, st));
-         r->scr_rec_seen[si_st] = ++r->scr_rec_version;
+         HIP_TRY(r->scr_rec_written.signal(st, si_st));
       } else if (p.k.rec == 2) {
-         HIP_TRY(hipEventRecord(r->ev_scr_rec_read[si_st], st));
-         r->scr_rec_read_pending[si_st] = true;
+         HIP_TRY(r->scr_rec_reads.mark(0, st, si_st));
       } else r->scr_rec_valid = false; // (something moved, the option is off or this variant only marches)
       if (!(r->scr_seen_valid && now == r->scr_seen_key)) r->scr_rec_no_memory = false; // (a new key: the allocation may be tried again)
       r->scr_seen_key = now;
@@ -2605,14 +2477,14 @@ extern "C" int32_t mdh_frame_begin(mdh_renderer *r)
       const int cur = r->opt_mode == 0 ? (r->last + 1) % mdh_renderer::NSETS : r->last;
       if (r->main_dirty) { // the other streams have to see everything that went to the main stream meanwhile
          if ((rc = join_main(r)) != MDH_OK) return rc;
-         HIP_TRY(hipEventRecord(r->ev_join, r->stream));
-         HIP_TRY(hipStreamWaitEvent(r->probe_stream, r->ev_join, 0));
-         HIP_TRY(hipStreamWaitEvent(r->alt_stream, r->ev_join, 0));
-         if (r->vol_stream) HIP_TRY(hipStreamWaitEvent(r->vol_stream, r->ev_join, 0)); // (the volumetric passes of pipelined frames: frame_end_passes)
+         HIP_TRY(hipEventRecord(r->ev_join.ev, r->stream));
+         HIP_TRY(hipStreamWaitEvent(r->probe_stream, r->ev_join.ev, 0));
+         HIP_TRY(hipStreamWaitEvent(r->alt_stream, r->ev_join.ev, 0));
+         if (r->vol_stream) HIP_TRY(hipStreamWaitEvent(r->vol_stream, r->ev_join.ev, 0)); // (the volumetric passes of pipelined frames: frame_end_passes)
          r->main_dirty = false;
       } else if (r->opt_mode == 0 && r->ev_screen_valid[cur]) { // the last screen pass that read atlas set cur
-         HIP_TRY(hipStreamWaitEvent(r->probe_stream, r->ev_screen[cur], 0));
-         if (r->vol_stream) HIP_TRY(hipStreamWaitEvent(r->vol_stream, r->ev_screen[cur], 0)); // (it read the froxels of set cur as well)
+         HIP_TRY(hipStreamWaitEvent(r->probe_stream, r->ev_screen[cur].ev, 0));
+         if (r->vol_stream) HIP_TRY(hipStreamWaitEvent(r->vol_stream, r->ev_screen[cur].ev, 0)); // (it read the froxels of set cur as well)
       }
       r->frame_cur = cur;
    }
@@ -2680,14 +2552,14 @@ static int frame_end_passes(mdh_renderer *r)
       r->fuse_scat_march = false;
       if (rc != MDH_OK) return rc;
       if (vs != r->probe_stream) {
-         HIP_TRY(hipEventRecord(r->ev_vol[cur], vs));
-         HIP_TRY(hipStreamWaitEvent(screen_stream, r->ev_vol[cur], 0));
+         HIP_TRY(hipEventRecord(r->ev_vol[cur].ev, vs));
+         HIP_TRY(hipStreamWaitEvent(screen_stream, r->ev_vol[cur].ev, 0));
       }
    }
-   HIP_TRY(hipEventRecord(r->ev_probe[cur], r->probe_stream));
-   HIP_TRY(hipStreamWaitEvent(screen_stream, r->ev_probe[cur], 0));
+   HIP_TRY(hipEventRecord(r->ev_probe[cur].ev, r->probe_stream));
+   HIP_TRY(hipStreamWaitEvent(screen_stream, r->ev_probe[cur].ev, 0));
    if ((rc = run_pass(r, MDH_PASS_SCREEN, screen_stream, cur, cur, fbix)) != MDH_OK) return rc;
-   HIP_TRY(hipEventRecord(r->ev_screen[cur], screen_stream));
+   HIP_TRY(hipEventRecord(r->ev_screen[cur].ev, screen_stream));
    r->ev_screen_valid[cur] = true;
    r->last = cur;
    r->fb_last = fbix;
@@ -2891,7 +2763,7 @@ extern "C" int32_t mdh_peer_export(mdh_renderer *r, uint8_t blob_out[MDH_PEER_BL
    b.pid = (int32_t)getpid(); b.device = r->device; b.nsets = MDH_ATLAS_SETS;
    b.rad_bytes = atlas_bytes(r, MDH_TEX_RADIANCE);
    b.serial = p->serial;
-   for (int s = 0; s < MDH_ATLAS_SETS; ++s) HIP_TRY(hipIpcGetMemHandle(&b.rad[s], r->d_rad2[s]));
+   for (int s = 0; s < MDH_ATLAS_SETS; ++s) HIP_TRY(hipIpcGetMemHandle(&b.rad[s], r->d_rad2[s].ptr));
    HIP_TRY(hipIpcGetMemHandle(&b.flags, p->d_flags));
    memset(blob_out, 0, MDH_PEER_BLOB_BYTES);
    memcpy(blob_out, &b, sizeof b);
@@ -2953,7 +2825,7 @@ static int peer_exchange(mdh_renderer *r, int tex)
    const unsigned n = ++p->seq[s];
    hipLaunchKernelGGL(k_peer_publish, dim3(1), dim3(1), 0, st, p->d_flags + s, n);
    HIP_TRY(hipGetLastError());
-   char *mine = (char *)r->d_rad2[s];
+   char *mine = (char *)r->d_rad2[s].ptr;
    for (long long k = 1; k < world; ++k) { // (peers in a rotated order: the ranks do not all read the same peer at once)
       const long long q = (p->rank + k) % world;
       const long long b = P * q / world, e = P * (q + 1) / world; // own_probes () of rank q
@@ -2996,7 +2868,7 @@ extern "C" int32_t mdh_comm_init(mdh_renderer *r, const uint8_t id_in[MDH_COMM_I
    memcpy(&id, id_in, sizeof id);
    ncclComm_t comm = nullptr;
    RCCL_TRY(rccl_api().CommInitRank(&comm, world, id, rank));
-   if (!r->d_comm_scratch && hipMalloc(&r->d_comm_scratch, 2 * sizeof(double)) != hipSuccess) {
+   if (r->d_comm_scratch.grow(2) != hipSuccess) {
       (void)rccl_api().CommAbort(comm);
       return seterr(MDH_E_DEVICE, "hipMalloc failed");
    }
@@ -3091,7 +2963,7 @@ extern "C" int32_t mdh_frame_exchange(mdh_renderer *r, int32_t tex)
    CommBusy busy(r);
    const RcclApi &n = rccl_api();
    hipStream_t st = frame_probe_stream(r);
-   char *buf = (char *)(tex == MDH_TEX_RADIANCE ? r->d_rad2[r->frame_cur] : r->d_irr2[r->frame_cur]);
+   char *buf = (char *)(tex == MDH_TEX_RADIANCE ? r->d_rad2[r->frame_cur].ptr : r->d_irr2[r->frame_cur].ptr);
    const int res = tex == MDH_TEX_RADIANCE ? r->probes.radiance_resolution : r->probes.irradiance_resolution;
    const size_t per = (size_t)res * res * texel_bytes(r);
    const long long P = probe_total(r), world = r->opt_world;
@@ -3142,8 +3014,8 @@ extern "C" int32_t mdh_comm_barrier(mdh_renderer *r)
    if (rc != MDH_OK || !r->comm) return rc;
    if (r->comm_aborted) return comm_gone(r);
    CommBusy busy(r);
-   HIP_TRY(hipMemsetAsync(r->d_comm_scratch, 0, sizeof(double), r->stream));
-   RCCL_TRY(rccl_api().AllReduce(r->d_comm_scratch, r->d_comm_scratch, 1, ncclFloat64, ncclSum, r->comm, r->stream));
+   HIP_TRY(hipMemsetAsync(r->d_comm_scratch.ptr, 0, sizeof(double), r->stream));
+   RCCL_TRY(rccl_api().AllReduce(r->d_comm_scratch.ptr, r->d_comm_scratch.ptr, 1, ncclFloat64, ncclSum, r->comm, r->stream));
    HIP_TRY(hipStreamSynchronize(r->stream));
    return comm_check(r);
 }
@@ -3157,9 +3029,9 @@ extern "C" int32_t mdh_comm_max_f64(mdh_renderer *r, double *value)
    CommBusy busy(r);
    HIP_TRY(hipSetDevice(r->device));
    { int jr = join_main(r); if (jr != MDH_OK) return jr; }
-   HIP_TRY(hipMemcpyAsync(r->d_comm_scratch + 1, value, sizeof(double), hipMemcpyHostToDevice, r->stream));
-   RCCL_TRY(rccl_api().AllReduce(r->d_comm_scratch + 1, r->d_comm_scratch + 1, 1, ncclFloat64, ncclMax, r->comm, r->stream));
-   HIP_TRY(hipMemcpyAsync(value, r->d_comm_scratch + 1, sizeof(double), hipMemcpyDeviceToHost, r->stream));
+   HIP_TRY(hipMemcpyAsync(r->d_comm_scratch.ptr + 1, value, sizeof(double), hipMemcpyHostToDevice, r->stream));
+   RCCL_TRY(rccl_api().AllReduce(r->d_comm_scratch.ptr + 1, r->d_comm_scratch.ptr + 1, 1, ncclFloat64, ncclMax, r->comm, r->stream));
+   HIP_TRY(hipMemcpyAsync(value, r->d_comm_scratch.ptr + 1, sizeof(double), hipMemcpyDeviceToHost, r->stream));
    HIP_TRY(hipStreamSynchronize(r->stream));
    return comm_check(r);
 }
@@ -3175,7 +3047,7 @@ extern "C" int32_t mdh_comm_reduce_framebuffer(mdh_renderer *r, int32_t root)
    HIP_TRY(hipSetDevice(r->device));
    { int jr = join_main(r); if (jr != MDH_OK) return jr; }
    r->main_dirty = true;
-   float4 *fb = r->d_fb2[r->fb_last];
+   float4 *fb = r->d_fb2[r->fb_last].ptr;
    RCCL_TRY(rccl_api().Reduce(fb, fb, (size_t)r->W * r->H * 4, ncclFloat32, ncclSum, root, r->comm, r->stream));
    // the root's buffer now holds every rank's tiles: its next sharded screen pass clears it first
    if (r->opt_rank == root) r->fb_owner[r->fb_last][0] = -1;
@@ -3208,7 +3080,7 @@ extern "C" int32_t mdh_read_framebuffer(mdh_renderer *r, float *rgb_out)
    size_t px = (size_t)r->W * r->H;
    std::vector<float4> tmp(px);
    { int jr = join_main(r); if (jr != MDH_OK) return jr; }
-   HIP_TRY(hipMemcpyAsync(tmp.data(), r->d_fb2[r->fb_last], px * sizeof(float4), hipMemcpyDeviceToHost, r->stream));
+   HIP_TRY(hipMemcpyAsync(tmp.data(), r->d_fb2[r->fb_last].ptr, px * sizeof(float4), hipMemcpyDeviceToHost, r->stream));
    HIP_TRY(hipStreamSynchronize(r->stream));
    for (size_t i = 0; i < px; ++i) { rgb_out[3 * i] = tmp[i].x; rgb_out[3 * i + 1] = tmp[i].y; rgb_out[3 * i + 2] = tmp[i].z; }
    return MDH_OK;
@@ -3231,30 +3103,30 @@ extern "C" int32_t mdh_swap_buffers(mdh_renderer *r)
    hipStream_t st = on_alt ? r->alt_stream : r->stream;
    if (r->opt_window && r->win_valid) {
       const int slot = (int)((r->win_passes - 1) % mdh_renderer::WIN_RING);
-      if (!r->ev_win[slot]) HIP_TRY(hipEventCreateWithFlags(&r->ev_win[slot], hipEventDisableTiming));
-      HIP_TRY(hipEventRecord(r->ev_win[slot], st));
-      r->front_ptr = (const unsigned char *)r->h_win[slot];
-      r->front_ev = r->ev_win[slot];
+      HIP_TRY(r->ev_win[slot].create());
+      HIP_TRY(hipEventRecord(r->ev_win[slot].ev, st));
+      r->front_ptr = (const unsigned char *)r->h_win[slot].ptr;
+      r->front_ev = r->ev_win[slot].ev;
       r->swaps += 1;
       return MDH_OK;
    }
    const int slot = (int)(r->swaps % mdh_renderer::FRONT_RING);
    if (!r->copy_stream) HIP_TRY(hipStreamCreateWithFlags(&r->copy_stream, hipStreamNonBlocking));
-   if (!r->ev_packed) HIP_TRY(hipEventCreateWithFlags(&r->ev_packed, hipEventDisableTiming));
-   if (!r->d_front[slot]) HIP_TRY(hipMalloc(&r->d_front[slot], px * 4));
-   if (!r->h_front[slot]) HIP_TRY(hipHostMalloc((void **)&r->h_front[slot], px * 4, hipHostMallocDefault));
-   if (!r->ev_front[slot]) HIP_TRY(hipEventCreateWithFlags(&r->ev_front[slot], hipEventDisableTiming));
-   else HIP_TRY(hipStreamWaitEvent(st, r->ev_front[slot], 0)); // the copy that read this slot's device buffer three swaps ago
-   hipLaunchKernelGGL(k_present, dim3((unsigned)((px + 255) / 256)), dim3(256), 0, st, r->d_fb2[r->fb_last], r->d_front[slot], (int)px);
+   HIP_TRY(r->ev_packed.create());
+   HIP_TRY(r->d_front[slot].grow(px));
+   HIP_TRY(r->h_front[slot].grow(px * 4));
+   if (!r->ev_front[slot].ev) HIP_TRY(r->ev_front[slot].create());
+   else HIP_TRY(hipStreamWaitEvent(st, r->ev_front[slot].ev, 0)); // the copy that read this slot's device buffer three swaps ago
+   hipLaunchKernelGGL(k_present, dim3((unsigned)((px + 255) / 256)), dim3(256), 0, st, r->d_fb2[r->fb_last].ptr, r->d_front[slot].ptr, (int)px);
    HIP_TRY(hipGetLastError());
-   HIP_TRY(hipEventRecord(r->ev_packed, st));
-   HIP_TRY(hipStreamWaitEvent(r->copy_stream, r->ev_packed, 0));
-   HIP_TRY(hipMemcpyAsync(r->h_front[slot], r->d_front[slot], px * 4, hipMemcpyDeviceToHost, r->copy_stream));
-   HIP_TRY(hipEventRecord(r->ev_front[slot], r->copy_stream));
+   HIP_TRY(hipEventRecord(r->ev_packed.ev, st));
+   HIP_TRY(hipStreamWaitEvent(r->copy_stream, r->ev_packed.ev, 0));
+   HIP_TRY(hipMemcpyAsync(r->h_front[slot].ptr, r->d_front[slot].ptr, px * 4, hipMemcpyDeviceToHost, r->copy_stream));
+   HIP_TRY(hipEventRecord(r->ev_front[slot].ev, r->copy_stream));
    // framebuffer 1 read from the main stream: its next writer (the alternate stream) has to come after this
    if (r->fb_last == 1 && !on_alt) r->main_dirty = true;
-   r->front_ptr = r->h_front[slot];
-   r->front_ev = r->ev_front[slot];
+   r->front_ptr = r->h_front[slot].ptr;
+   r->front_ev = r->ev_front[slot].ev;
    r->swaps += 1;
    return MDH_OK;
 }
@@ -3274,9 +3146,9 @@ extern "C" int32_t mdh_read_gbuffer(mdh_renderer *r, int32_t *index_out, float *
    HIP_TRY(hipSetDevice(r->device));
    size_t n = (size_t)r->W * r->H * 4;
    { int jr = join_main(r); if (jr != MDH_OK) return jr; }
-   if (index_out) HIP_TRY(hipMemcpyAsync(index_out, r->d_gb2[r->fb_last][0], n, hipMemcpyDeviceToHost, r->stream));
-   if (t_out) HIP_TRY(hipMemcpyAsync(t_out, r->d_gb2[r->fb_last][1], n, hipMemcpyDeviceToHost, r->stream));
-   if (steps_out) HIP_TRY(hipMemcpyAsync(steps_out, r->d_gb2[r->fb_last][2], n, hipMemcpyDeviceToHost, r->stream));
+   if (index_out) HIP_TRY(hipMemcpyAsync(index_out, r->d_gb2[r->fb_last][0].ptr, n, hipMemcpyDeviceToHost, r->stream));
+   if (t_out) HIP_TRY(hipMemcpyAsync(t_out, r->d_gb2[r->fb_last][1].ptr, n, hipMemcpyDeviceToHost, r->stream));
+   if (steps_out) HIP_TRY(hipMemcpyAsync(steps_out, r->d_gb2[r->fb_last][2].ptr, n, hipMemcpyDeviceToHost, r->stream));
    HIP_TRY(hipStreamSynchronize(r->stream));
    return MDH_OK;
 }
@@ -3292,7 +3164,7 @@ static int atlas_to_host(mdh_renderer *r, int tex, std::vector<float> &rgb, size
 {
    int res = tex == MDH_TEX_RADIANCE ? r->probes.radiance_resolution : r->probes.irradiance_resolution;
    if (n == 0 && first == 0) n = (size_t)probe_total(r) * res * res;
-   const char *src = (const char *)(tex == MDH_TEX_RADIANCE ? r->d_rad2[atlas_set(r)] : r->d_irr2[atlas_set(r)]) + first * texel_bytes(r);
+   const char *src = (const char *)(tex == MDH_TEX_RADIANCE ? r->d_rad2[atlas_set(r)].ptr : r->d_irr2[atlas_set(r)].ptr) + first * texel_bytes(r);
    if (n == 0) { rgb.clear(); return MDH_OK; }
    hipStream_t st = atlas_stream(r);
    if (!r->in_frame) { int jr = join_main(r); if (jr != MDH_OK) return jr; }
@@ -3319,7 +3191,7 @@ static float unorm8_host(float x)
 // upload texels [first, first + n) of a probe-major atlas from float RGB
 static int atlas_from_host(mdh_renderer *r, int tex, size_t first, size_t n, const float *rgb)
 {
-   void *dst = tex == MDH_TEX_RADIANCE ? r->d_rad2[atlas_set(r)] : r->d_irr2[atlas_set(r)];
+   void *dst = tex == MDH_TEX_RADIANCE ? r->d_rad2[atlas_set(r)].ptr : r->d_irr2[atlas_set(r)].ptr;
    hipStream_t st = atlas_stream(r);
    if (!r->in_frame) {
       int jr = join_main(r);
@@ -3361,7 +3233,7 @@ extern "C" int32_t mdh_read_texture(mdh_renderer *r, int32_t tex, float *out, in
          for (int k = 1; k < l; ++k) off += (size_t)probe_total(r) * (r->probes.radiance_resolution >> k) * (r->probes.radiance_resolution >> k);
          const size_t n = (size_t)probe_total(r) * res * res;
          std::vector<float> rgb(n * 3);
-         const char *src = (const char *)r->d_rad_mips[set] + off * texel_bytes(r);
+         const char *src = (const char *)r->d_rad_mips[set].ptr + off * texel_bytes(r);
          if (r->opt_atlas == 0) {
             std::vector<uchar4> tmp(n);
             HIP_TRY(hipMemcpyAsync(tmp.data(), src, n * 4, hipMemcpyDeviceToHost, r->stream));
@@ -3406,10 +3278,10 @@ extern "C" int32_t mdh_read_texture(mdh_renderer *r, int32_t tex, float *out, in
       }
    } else if (tex == MDH_TEX_VISIBILITY) {
       W = r->vol.visibility_resolution[0]; H = r->vol.visibility_resolution[1] * r->vol.visibility_resolution[2]; C = 3;
-      if (out) { HIP_TRY(hipMemcpyAsync(out, r->d_vis2[atlas_set(r)], (size_t)W * H * 12, hipMemcpyDeviceToHost, r->stream)); HIP_TRY(hipStreamSynchronize(r->stream)); }
+      if (out) { HIP_TRY(hipMemcpyAsync(out, r->d_vis2[atlas_set(r)].ptr, (size_t)W * H * 12, hipMemcpyDeviceToHost, r->stream)); HIP_TRY(hipStreamSynchronize(r->stream)); }
    } else {
       W = r->vol.scattering_resolution[0]; H = r->vol.scattering_resolution[1]; C = 4;
-      if (out) { HIP_TRY(hipMemcpyAsync(out, r->d_scat2[atlas_set(r)], (size_t)W * H * 16, hipMemcpyDeviceToHost, r->stream)); HIP_TRY(hipStreamSynchronize(r->stream)); }
+      if (out) { HIP_TRY(hipMemcpyAsync(out, r->d_scat2[atlas_set(r)].ptr, (size_t)W * H * 16, hipMemcpyDeviceToHost, r->stream)); HIP_TRY(hipStreamSynchronize(r->stream)); }
    }
    if (w) *w = W;
    if (h) *h = H;
@@ -3438,7 +3310,7 @@ extern "C" int32_t mdh_write_texture(mdh_renderer *r, int32_t tex, const float *
          }
       return atlas_from_host(r, tex, 0, (size_t)W * H, rgb.data());
    }
-   void *dst = tex == MDH_TEX_VISIBILITY ? (void *)r->d_vis2[atlas_set(r)] : (void *)r->d_scat2[atlas_set(r)];
+   void *dst = tex == MDH_TEX_VISIBILITY ? (void *)r->d_vis2[atlas_set(r)].ptr : (void *)r->d_scat2[atlas_set(r)].ptr;
    HIP_TRY(hipMemcpyAsync(dst, in, (size_t)W * H * C * 4, hipMemcpyHostToDevice, r->stream));
    HIP_TRY(hipStreamSynchronize(r->stream));
    return MDH_OK;
@@ -3478,7 +3350,7 @@ extern "C" int32_t mdh_atlas_device_ptr(mdh_renderer *r, int32_t tex, void **dpt
       if (jr != MDH_OK) return jr;
       r->main_dirty = true; // the caller may write through the pointer
    }
-   if (dptr) *dptr = tex == MDH_TEX_RADIANCE ? r->d_rad2[atlas_set(r)] : r->d_irr2[atlas_set(r)];
+   if (dptr) *dptr = tex == MDH_TEX_RADIANCE ? r->d_rad2[atlas_set(r)].ptr : r->d_irr2[atlas_set(r)].ptr;
    if (total_bytes) *total_bytes = (int64_t)atlas_bytes(r, tex);
    if (own_offset) *own_offset = per * b;
    if (own_bytes) *own_bytes = per * (e - b);
@@ -3500,13 +3372,11 @@ extern "C" int32_t mdh_set_stream(mdh_renderer *r, void *stream)
    HIP_TRY(hipStreamSynchronize(r->stream));
    int rc = resolve_timing(r);
    if (rc != MDH_OK) return rc;
-   if (r->probe_stream) HIP_TRY(hipStreamSynchronize(r->probe_stream));
-   if (r->alt_stream) HIP_TRY(hipStreamSynchronize(r->alt_stream));
-   if (r->query_stream) HIP_TRY(hipStreamSynchronize(r->query_stream));
-   if (r->vol_stream) HIP_TRY(hipStreamSynchronize(r->vol_stream));
+   if ((rc = sync_streams(r, SYNC_PROBE | SYNC_ALT | SYNC_QUERY | SYNC_VOL)) != MDH_OK) return rc;
    r->stream = stream ? (hipStream_t)stream : r->own_stream;
    // the new main stream has not waited for anything: uploads and earlier work are complete (synchronised above)
-   for (int si = 0; si < mdh_renderer::NSTREAMS; ++si) { r->tab_seen[si] = r->table_version; r->part_seen[si] = r->part_version; }
+   r->table_fence.mark_all_seen();
+   r->part_fence.mark_all_seen();
    return MDH_OK;
 }
 
@@ -3524,12 +3394,13 @@ extern "C" int32_t mdh_eval_distance_to(mdh_renderer *r, int32_t n, const float 
    hipStream_t qs = r->query_stream;
    int rc = ensure_committed(r, qs);
    if (rc != MDH_OK) return rc;
-   if ((size_t)n > r->query_cap) { // 7 floats per query: point, normal, distance
-      if (r->d_query) { HIP_TRY(hipStreamSynchronize(qs)); HIP_TRY(hipFree(r->d_query)); r->d_query = nullptr; }
-      r->query_cap = (size_t)n < 256 ? 256 : (size_t)n;
-      HIP_TRY(hipMalloc(&r->d_query, r->query_cap * 7 * sizeof(float)));
+   const size_t want = ((size_t)n < 256 ? 256 : (size_t)n) * 7; // 7 floats per query: point, normal, distance
+   if (want > r->d_query.cap) {
+      if (r->d_query.ptr) HIP_TRY(hipStreamSynchronize(qs));
+      HIP_TRY(r->d_query.grow(want));
    }
-   float *d_pts = r->d_query, *d_n = d_pts + 3 * r->query_cap, *d_d = d_n + 3 * r->query_cap;
+   const size_t query_cap = r->d_query.cap / 7;
+   float *d_pts = r->d_query.ptr, *d_n = d_pts + 3 * query_cap, *d_d = d_n + 3 * query_cap;
    HIP_TRY(hipMemcpyAsync(d_pts, pts, (size_t)n * 12, hipMemcpyHostToDevice, qs));
    EvalArgs a;
    a.n = n; a.n_kinds = n_kinds;
@@ -3644,8 +3515,8 @@ extern "C" int32_t mdh_read_partitioning(mdh_renderer *r, int32_t *out, int32_t 
    size_t total = (size_t)r->part_cells * (r->npk + r->part.index_count);
    if ((size_t)n_ints != total) return seterr(MDH_E_INVALID, "size mismatch");
    HIP_TRY(hipSetDevice(r->device));
-   if (r->part_version) HIP_TRY(hipEventSynchronize(r->ev_part)); // the last build
-   HIP_TRY(hipMemcpy(out, r->d_part_ring[r->part_slot], total * 4, hipMemcpyDeviceToHost));
+   if (r->part_fence.version) HIP_TRY(hipEventSynchronize(r->part_fence.ev.ev)); // the last build
+   HIP_TRY(hipMemcpy(out, r->d_part_ring[r->part_slot].ptr, total * 4, hipMemcpyDeviceToHost));
    return MDH_OK;
 }
 // the warnings of the last Update_Partitioning (scenes.adb:861-867 prints them): waits for that build only
@@ -3654,8 +3525,8 @@ extern "C" int32_t mdh_partition_warnings(mdh_renderer *r)
    if (!r) return 0;
    if (r->warn_pending) {
       (void)hipSetDevice(r->device);
-      if (hipEventSynchronize(r->ev_warn) != hipSuccess) return -1;
-      r->part_warnings = *r->h_warn;
+      if (hipEventSynchronize(r->ev_warn.ev) != hipSuccess) return -1;
+      r->part_warnings = *r->h_warn.ptr;
       r->warn_pending = false;
    }
    return r->part_warnings;

@@ -1,0 +1,171 @@
+// mdh_host.h -- the owners of what the host side of mdh_api.hip holds on the device: buffers, events, and the two
+// orderings it keeps between its streams.  Host only: no device code, nothing of the MDH_* error plumbing; every
+// function returns the runtime's own hipError_t and the caller wraps it (HIP_TRY).
+//
+// An owner that holds nothing makes no runtime call, neither when it is released nor when it is destroyed: a renderer
+// that never reached a device is deleted without one (mdh_create).  Owners are members, never copied.
+#pragma once
+#include <hip/hip_runtime_api.h>
+
+#include <cstddef>
+
+constexpr int HOST_NSTREAMS = 5; // the streams of a renderer that launch kernels (stream_index, mdh_api.hip)
+
+// Memory and its capacity in elements: on the device, or (Pinned) page-locked on the host.
+template <class T = unsigned char, bool Pinned = false>
+struct DevBuf {
+   T *ptr = nullptr;
+   size_t cap = 0;
+   DevBuf() = default;
+   DevBuf(const DevBuf &) = delete;
+   DevBuf &operator=(const DevBuf &) = delete;
+   ~DevBuf() { (void)release(); }
+   hipError_t release()
+   {
+      T *q = ptr;
+      ptr = nullptr; cap = 0; // (first: whatever the free says, nobody frees q again)
+      if (!q) return hipSuccess;
+      return Pinned ? hipHostFree(q) : hipFree(q);
+   }
+   // Room for n elements.  The contents do not survive a growth, and whoever may still use the old memory has to be
+   // drained first: that is the caller's.  After a failed allocation the buffer is empty.
+   hipError_t grow(size_t n)
+   {
+      if (n <= cap) return hipSuccess;
+      hipError_t e = release();
+      if (e != hipSuccess) return e;
+      void *q = nullptr;
+      e = Pinned ? hipHostMalloc(&q, n * sizeof(T), hipHostMallocDefault) : hipMalloc(&q, n * sizeof(T));
+      if (e != hipSuccess) return e;
+      ptr = (T *)q; cap = n;
+      return hipSuccess;
+   }
+   // as a member of create_all: the buffer with n elements
+   struct Sized {
+      DevBuf &b;
+      size_t n;
+      hipError_t create() { return b.grow(n); }
+      void release() { (void)b.release(); }
+   };
+   Sized sized(size_t n) { return {*this, n}; }
+};
+template <class T>
+using PinnedBuf = DevBuf<T, true>;
+
+// An event that orders streams (no timing).
+struct Event {
+   hipEvent_t ev = nullptr;
+   Event() = default;
+   Event(const Event &) = delete;
+   Event &operator=(const Event &) = delete;
+   ~Event() { release(); }
+   hipError_t create()
+   {
+      if (ev) return hipSuccess;
+      hipEvent_t e = nullptr;
+      const hipError_t rc = hipEventCreateWithFlags(&e, hipEventDisableTiming);
+      if (rc == hipSuccess) ev = e;
+      return rc;
+   }
+   void release()
+   {
+      if (ev) (void)hipEventDestroy(ev);
+      ev = nullptr;
+   }
+};
+
+// Resources that are looked for as one ("is it there?" asks any of them): all created, in order, or, when one creation
+// fails, all empty again and that error returned.  Members have create() and release(): Event, Fence, RingUse, DevBuf::sized.
+template <class... M>
+hipError_t create_all(M &&...m)
+{
+   hipError_t e = hipSuccess;
+   ((e = e == hipSuccess ? m.create() : e), ...);
+   if (e != hipSuccess) (m.release(), ...);
+   return e;
+}
+
+// "Has this stream seen the latest write?"  The writer signals behind its write; a reader waits before its read, which
+// costs a runtime call only on a stream that has not been ordered behind the latest signal yet.
+struct Fence {
+   Event ev;
+   hipStream_t by = nullptr; // the stream of the last signal
+   unsigned long long version = 0, seen[HOST_NSTREAMS] = {0};
+   hipError_t create() { return ev.create(); }
+   void release() { ev.release(); }
+   hipError_t signal(hipStream_t st, int si)
+   {
+      const hipError_t e = hipEventRecord(ev.ev, st);
+      if (e != hipSuccess) return e;
+      by = st;
+      seen[si] = ++version;
+      return hipSuccess;
+   }
+   hipError_t wait(hipStream_t st, int si)
+   {
+      if (version == 0 || seen[si] == version) return hipSuccess;
+      if (st != by) {
+         const hipError_t e = hipStreamWaitEvent(st, ev.ev, 0);
+         if (e != hipSuccess) return e;
+      }
+      seen[si] = version;
+      return hipSuccess;
+   }
+   void mark_all_seen() // (the caller has waited on the host for everything signalled so far)
+   {
+      for (unsigned long long &s : seen) s = version;
+   }
+};
+
+// "Who still reads this slot?" of a ring of N buffers: every stream that uses a slot marks it behind the use; before the
+// slot is rewritten its readers are retired, by a wait on the host or on the stream that rewrites it.
+template <int N>
+struct RingUse {
+   Event done[N][HOST_NSTREAMS];
+   bool used[N][HOST_NSTREAMS] = {{false}};
+   hipError_t create()
+   {
+      for (auto &slot : done)
+         for (Event &e : slot) {
+            const hipError_t rc = e.create();
+            if (rc != hipSuccess) { release(); return rc; }
+         }
+      return hipSuccess;
+   }
+   void release()
+   {
+      for (auto &slot : done)
+         for (Event &e : slot) e.release();
+      forget();
+   }
+   hipError_t mark(int slot, hipStream_t st, int si)
+   {
+      const hipError_t e = hipEventRecord(done[slot][si].ev, st);
+      if (e == hipSuccess) used[slot][si] = true;
+      return e;
+   }
+   template <class F>
+   hipError_t retire(int slot, F wait_for) // wait_for (stream index, its event) for every stream that marked the slot
+   {
+      for (int si = 0; si < HOST_NSTREAMS; ++si)
+         if (used[slot][si]) {
+            const hipError_t e = wait_for(si, done[slot][si].ev);
+            if (e != hipSuccess) return e;
+            used[slot][si] = false;
+         }
+      return hipSuccess;
+   }
+   hipError_t retire_on_host(int slot)
+   {
+      return retire(slot, [](int, hipEvent_t e) { return hipEventSynchronize(e); });
+   }
+   hipError_t retire_on_stream(int slot, hipStream_t st, int si_st) // (st's own uses are ordered by the stream itself)
+   {
+      return retire(slot, [&](int si, hipEvent_t e) { return si == si_st ? hipSuccess : hipStreamWaitEvent(st, e, 0); });
+   }
+   void forget() // (every stream was drained: nothing reads any slot)
+   {
+      for (auto &slot : used)
+         for (bool &u : slot) u = false;
+   }
+};
