@@ -138,6 +138,9 @@ package Madarch_HIP is
    --  Opt_Screen_Replay: 1 = the screen pass's hits and cage visibility are replayed from per-pixel
    --  records while camera and geometry stand still (the same bits), 0 (default) = marched every pass.
    Opt_Screen_Replay : constant int := 22;
+   --  Opt_Probe_Settle: 1 (default) = a frame's radiance and irradiance passes are not launched once
+   --  the probe atlases have stopped changing, the same bits; any edit launches them again; 0 = every frame
+   Opt_Probe_Settle : constant int := 23;
 
    function Set_Option (R : Handle; Option, Value : int) return Status
      with Import, Convention => C, External_Name => "mdh_set_option";

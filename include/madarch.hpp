@@ -360,6 +360,7 @@ class Renderer {
       return p;
    }
    void Set_Option(int32_t Option, int32_t Value) const { Check(mdh_set_option(h_.get(), Option, Value)); }
+   static constexpr int32_t Opt_Probe_Settle = MDH_OPT_PROBE_SETTLE; // Set_Option (.., 0): probe passes launched in every frame (default 1: left out once the atlases have stopped changing, the same bits; any edit launches them again)
    static constexpr int32_t Opt_Screen_Replay = MDH_OPT_SCREEN_REPLAY; // Set_Option (.., 1): the screen pass's marches replayed while camera and geometry stand still, the same bits (default 0)
    static constexpr int32_t Opt_Radiance_Replay = MDH_OPT_RADIANCE_REPLAY; // Set_Option (.., 0): probe rays marched in every pass (default 1: replayed while the geometry stands still, the same bits)
    static constexpr int32_t Opt_Triangle_BVH = MDH_OPT_TRIANGLE_BVH; // Set_Option (.., 1): triangles walked through a BVH, the same bits (scenes without partition or user-defined kinds)

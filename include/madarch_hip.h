@@ -305,7 +305,22 @@ enum {
     * without a space partition, user-defined kinds or global residency replays; everything
     * else keeps marching ("Exact work elimination", item 12).  0 drops the records.
     * mdh_screen_replay_stats counts the passes. */
-   MDH_OPT_SCREEN_REPLAY = 22
+   MDH_OPT_SCREEN_REPLAY = 22,
+   /* 1 (default) = a frame's radiance and irradiance passes are not launched once the probe atlases have stopped changing
+    * -- no effect on any texel or pixel; 0 = launched in every frame.  Both passes are deterministic in the bits they read:
+    * when a pass has stored the irradiance bits it was given and nothing else it reads has changed, every later pass
+    * stores them again.  Every tracked irradiance pass counts the texels it stores with other bits than the set it read
+    * and hands the count to the host through pinned memory; mdh_frame_begin reads what has arrived and never waits.  After
+    * MDH_SETTLE_PASSES = 16 consecutive unchanged passes (all atlas sets then hold the same bits) frames rotate through
+    * the sets, record their events and run every other pass as before, without the probe passes.  Every entry point counts
+    * as an edit that ends this -- the next frame launches its passes -- except mdh_render and the mdh_frame_* calls,
+    * mdh_finish, read-backs and getters, pass times and statistics, the camera setters, mdh_swap_buffers and the options
+    * TIMING, SCREEN_ORDER, SCREEN_SPLIT, SCREEN_REPLAY, GBUFFER, WINDOW, AO_STEPS, INDIRECT_SPECULAR and this one (a light
+    * set to the value it has is an edit too).  Single rank and MDH_OPT_SCREEN_MODE 0 only: a renderer with a communicator,
+    * a peer exchange or MDH_OPT_WORLD > 1 launches every pass.  With MDH_OPT_TIMING a settled pass is still counted; its
+    * time is the few microseconds between its two events.  0 forgets the run.  mdh_probe_settle_stats counts (DESIGN.md
+    * section 4, "Exact work elimination", item 13). */
+   MDH_OPT_PROBE_SETTLE = 23
 };
 
 /* passes of Renderers.Render (madarch-renderers.adb:302-321) */
@@ -514,6 +529,11 @@ int32_t mdh_pass_time(mdh_renderer *r, int32_t pass, double *total_ms, int64_t *
 /* MDH_OPT_RADIANCE_REPLAY: the radiance passes launched since mdh_create that marched their rays (`plain`), marched them
  * and wrote the rays' records (`recording`), and read the records instead of marching (`replaying`).  Any pointer may be null. */
 int32_t mdh_radiance_replay_stats(mdh_renderer *r, int64_t *plain, int64_t *recording, int64_t *replaying);
+/* MDH_OPT_PROBE_SETTLE: the length of the run of consecutive irradiance passes of frames that changed no texel, under the
+ * inputs that hold now (0 after any edit); the probe passes of frames that were not launched since mdh_create; the
+ * texels the newest observed pass changed.  Reads what the device has reported so far and waits for nothing.  Any pointer
+ * may be null. */
+int32_t mdh_probe_settle_stats(mdh_renderer *r, int64_t *run, int64_t *skipped, int64_t *last_changed_texels);
 /* MDH_OPT_SCREEN_REPLAY: the same count of the screen passes.  Any pointer may be null. */
 int32_t mdh_screen_replay_stats(mdh_renderer *r, int64_t *plain, int64_t *recording, int64_t *replaying);
 /* ... and the bytes of one pixel's record (32) */

@@ -25,6 +25,7 @@ OPT_INDIRECT_SPECULAR, OPT_HYSTERESIS_PERMILLE, OPT_RADIANCE_ORDER, OPT_SCREEN_O
 OPT_TABLE_RESIDENCY = 19  # read: 0 = the scene table in LDS, 1 = geometry in device memory (large scenes); write 1: force it
 OPT_TRIANGLE_BVH = 20  # 1: the triangles are walked through a bounding-volume hierarchy (the same bits; HIP library only)
 OPT_RADIANCE_REPLAY = 21  # 1 (default): probe rays' hits and cage visibility are replayed while the geometry stands still (the same bits; HIP library only)
+OPT_PROBE_SETTLE = 23  # 1 (default): a frame's probe passes are not launched once the atlases have stopped changing (the same bits; any edit launches them again; HIP library only)
 OPT_SCREEN_REPLAY = 22  # 1: the screen pass's hits and cage visibility are replayed while camera and geometry stand still (the same bits; HIP library only; default 0)
 
 PASS_RADIANCE, PASS_IRRADIANCE, PASS_VISIBILITY, PASS_SCATTERING, PASS_SCREEN, PASS_EXCHANGE = range(6)
@@ -151,6 +152,8 @@ HIP_ONLY_ABI = {
     "triangle_bvh_info": (_I, [_P, _PI, _PI, _PI, _PI]),
     # OPT_RADIANCE_REPLAY: radiance passes that marched, recorded, replayed
     "radiance_replay_stats": (_I, [_P, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+    # OPT_PROBE_SETTLE: the run of unchanged irradiance passes, probe passes not launched, texels the newest observed pass changed
+    "probe_settle_stats": (_I, [_P, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     # OPT_SCREEN_REPLAY: screen passes that marched, recorded, replayed; the bytes of a pixel's record
     "screen_replay_stats": (_I, [_P, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     "screen_record_bytes": (_I, []),

@@ -505,7 +505,22 @@ struct mdh_renderer {
    DevBuf<double> d_comm_scratch; // barrier / max reductions
    struct PeerState *peer = nullptr; // the peer exchange (mdh_peer_init): the same sharded frame, its exchange as copies
    bool irr_lds_granted = false; // k_irradiance may use up to 160 KiB of dynamic LDS on this renderer's device
+   // MDH_OPT_PROBE_SETTLE (mdh_host.h: SettleTracker): the frames' irradiance passes report whether they changed a texel; once
+   // MDH_SETTLE_PASSES of them in a row did not, under inputs that still hold, frames leave their probe passes out.
+   // (the slots and the counters are one group, created by the first tracked pass: settle_args)
+   SettleTracker settle;
+   PinnedBuf<SettleSlot> h_settle; // its slots
+   DevBuf<unsigned long long> d_settle; // k_irradiance's counter: workgroups done | texels changed << 32
+   bool settle_no_memory = false;  // their allocation failed: passes run untracked
+   int opt_settle = 1;
+   int frame_probe_seq = 0;        // the open frame's probe passes so far: 0 none, 1 one radiance pass, 2 radiance then irradiance, -1 anything else
+   long long settle_skipped = 0;   // probe passes of frames that were not launched
 };
+// Something a probe pass reads or writes may have changed: every entry point calls this except the few that provably touch
+// none of it ("Exact work elimination", item 13 lists them).  The next frame runs its probe passes.
+static void settle_bump(mdh_renderer *r) { if (r) r->settle.bump(); }
+// a frame of a single rank in screen mode 0: the only kind whose probe passes may be left out (collectives stay matched across ranks)
+static bool settle_eligible(const mdh_renderer *r) { return MDH_PROBE_SETTLE && r->opt_mode == 0 && !r->comm && !r->peer && r->opt_world == 1; }
 
 // Order `stream` after everything pipelined frames put on the alternate screen stream (which
 // itself waited for the probe stream): called before any operation outside a pipelined frame.
@@ -1174,6 +1189,11 @@ extern "C" int32_t mdh_create(int32_t width, int32_t height, const mdh_scene_des
 extern "C" int32_t mdh_set_option(mdh_renderer *r, int32_t option, int32_t value)
 {
    if (!r) return seterr(MDH_E_INVALID, "null renderer");
+   switch (option) { // (the options no probe pass reads: everything else, known or not, counts as an edit)
+   case MDH_OPT_TIMING: case MDH_OPT_SCREEN_ORDER: case MDH_OPT_SCREEN_SPLIT: case MDH_OPT_SCREEN_REPLAY: case MDH_OPT_GBUFFER:
+   case MDH_OPT_WINDOW: case MDH_OPT_AO_STEPS: case MDH_OPT_INDIRECT_SPECULAR: case MDH_OPT_PROBE_SETTLE: break;
+   default: settle_bump(r);
+   }
    // what an open frame has latched (its atlas set, slice, streams and screen mode) cannot change under it
    if (r->in_frame && (option == MDH_OPT_ATLAS_FORMAT || option == MDH_OPT_RANK || option == MDH_OPT_WORLD || option == MDH_OPT_FRAME_OVERLAP ||
                        option == MDH_OPT_SCREEN_MODE))
@@ -1271,6 +1291,7 @@ extern "C" int32_t mdh_set_option(mdh_renderer *r, int32_t option, int32_t value
          }
       }
       break;
+   case MDH_OPT_PROBE_SETTLE: r->opt_settle = value ? 1 : 0; r->settle.set_enabled(r->opt_settle != 0); break; // (0 forgets the run)
    default: return seterr(MDH_E_INVALID, "unknown option");
    }
    return MDH_OK;
@@ -1301,6 +1322,7 @@ extern "C" int32_t mdh_get_option(mdh_renderer *r, int32_t option, int32_t *valu
    case MDH_OPT_NUMERICS: *value = MDH_FAST_NUMERICS ? 1 : (MDH_HYBRID_NUMERICS ? 2 : 0); break; // 0 exact (shipped), 1 / 2 the labelled experiments
    case MDH_OPT_RADIANCE_MIPS: *value = r->opt_mips; break;
    case MDH_OPT_TRIANGLE_BVH: *value = r->opt_tri_bvh; break;
+   case MDH_OPT_PROBE_SETTLE: *value = r->opt_settle; break;
    case MDH_OPT_TABLE_RESIDENCY: { // of the committed scene: edits since the last commit are committed first
       if (r->table_dirty && !r->in_frame) {
          HIP_TRY(hipSetDevice(r->device));
@@ -1318,6 +1340,7 @@ extern "C" int32_t mdh_get_option(mdh_renderer *r, int32_t option, int32_t *valu
 // Set_Material (renderers.adb:349-367)
 extern "C" int32_t mdh_set_material(mdh_renderer *r, int32_t id0, const float albedo[3], float metallic, float roughness)
 {
+   settle_bump(r);
    if (!r || !albedo) return seterr(MDH_E_INVALID, "bad argument");
    if (id0 < 0 || id0 >= MAX_MATERIALS) return seterr(MDH_E_INDEX, "material index out of range");
    uint8_t *p = r->materials_ubo + 16 + 32 * id0;
@@ -1339,6 +1362,7 @@ extern "C" int32_t mdh_set_material(mdh_renderer *r, int32_t id0, const float al
 // Add_Material (renderers.adb:369-377)
 extern "C" int32_t mdh_add_material(mdh_renderer *r, const float albedo[3], float metallic, float roughness, int32_t *out_id0)
 {
+   settle_bump(r);
    if (!r) return seterr(MDH_E_INVALID, "null renderer");
    int id = r->last_material_index;
    int rc = mdh_set_material(r, id, albedo, metallic, roughness);
@@ -1357,6 +1381,7 @@ static int write_entity(mdh_renderer *r, const Kind &k, int index1, const void *
 // Set_Primitive (renderers.adb:379-398)
 extern "C" int32_t mdh_set_primitive(mdh_renderer *r, int32_t kind_ix, int32_t index1, const void *blob, int32_t nbytes)
 {
+   settle_bump(r);
    if (!r || kind_ix < 0 || kind_ix >= r->npk) return seterr(MDH_E_INVALID, "bad kind index");
    if (index1 < 1 || index1 > r->host_count[kind_ix]) return seterr(MDH_E_INDEX, "index past the primitives added");
    ++r->geometry_edits;
@@ -1365,6 +1390,7 @@ extern "C" int32_t mdh_set_primitive(mdh_renderer *r, int32_t kind_ix, int32_t i
 // Add_Primitive (renderers.adb:435-456)
 extern "C" int32_t mdh_add_primitive(mdh_renderer *r, int32_t kind_ix, const void *blob, int32_t nbytes, int32_t *out_count)
 {
+   settle_bump(r);
    if (!r || kind_ix < 0 || kind_ix >= r->npk) return seterr(MDH_E_INVALID, "bad kind index");
    int count = r->host_count[kind_ix] + 1;
    ++r->geometry_edits;
@@ -1379,6 +1405,7 @@ extern "C" int32_t mdh_add_primitive(mdh_renderer *r, int32_t kind_ix, const voi
 // Set_Light (renderers.adb:458-483)
 extern "C" int32_t mdh_set_light(mdh_renderer *r, int32_t index1, int32_t light_kind_ix, const void *blob, int32_t nbytes)
 {
+   settle_bump(r);
    if (!r || light_kind_ix < 0 || light_kind_ix >= r->nlk) return seterr(MDH_E_INVALID, "bad light kind index");
    int rc = write_entity(r, r->lk[light_kind_ix], index1, blob, nbytes);
    if (rc != MDH_OK) return rc;
@@ -1783,6 +1810,7 @@ static const void *table_kernel(const mdh_renderer *r, int family)
 // Update_Partitioning (renderers.adb:757-775): all three methods build the table on the device
 extern "C" int32_t mdh_update_partitioning(mdh_renderer *r, int32_t method)
 {
+   settle_bump(r);
    if (!r) return seterr(MDH_E_INVALID, "null renderer");
    if (!r->part.enable) return MDH_OK; // renderers.adb:763-765
    if (method < 0 || method > 2) return seterr(MDH_E_INVALID, "bad method");
@@ -2069,7 +2097,7 @@ static int pass_begin(PassRun &p)
    if (p.k.jit) { // a scene hiprtc cannot build falls back to the interpreter for good (the reason stays in mdh_last_error, MDH_OPT_JIT reads 0 afterwards)
       const std::string name = kernel_name(p.k);
       if (JitModule *jm = jit_module(r, {name})) p.fn = jm->fn[name];
-      else { r->opt_jit = 0; p.k = pick_kernel(r, p.pass, p.dst); }
+      else { r->opt_jit = 0; settle_bump(r); p.k = pick_kernel(r, p.pass, p.dst); }
    }
    if (!p.k.jit && p.pass != MDH_PASS_IRRADIANCE && !(p.kernel = kernel_ptr(p.k))) return seterr(MDH_E_INVALID, "no kernel built for this pass's variant"); // (before anything is acquired)
    if (p.pass != MDH_PASS_IRRADIANCE) { // (the irradiance pass does not stage the scene table)
@@ -2179,6 +2207,30 @@ static int pass_radiance(PassRun &p)
    return MDH_OK;
 }
 
+// MDH_OPT_PROBE_SETTLE: the irradiance pass of an open frame is numbered, and tracked when it is the frame's one irradiance
+// pass behind its one radiance pass (any other pattern breaks the run: SettleTracker::enqueue)
+static int settle_args(PassRun &p, int n, SettleArgs &sa)
+{
+   mdh_renderer *r = p.r;
+   const bool regular = r->frame_probe_seq == 1 && n > 0;
+   r->frame_probe_seq = regular ? 2 : -1;
+   bool trackable = regular && r->opt_settle && settle_eligible(r) && !r->settle_no_memory;
+   if (trackable && !r->d_settle.ptr) { // (zeroed once per renderer, here: every pass that finishes clears its own counter)
+      if (create_all(r->h_settle.sized(SettleTracker::RING), r->d_settle.sized(1)) != hipSuccess) {
+         (void)hipGetLastError();
+         r->settle_no_memory = true; // (the feature is an optimisation: without its few bytes every pass runs)
+         trackable = false;
+      } else {
+         memset(r->h_settle.ptr, 0, SettleTracker::RING * sizeof(SettleSlot));
+         r->settle.slots = r->h_settle.ptr;
+         HIP_TRY(hipMemsetAsync(r->d_settle.ptr, 0, sizeof(unsigned long long), p.st));
+      }
+   }
+   SettleSlot *slot = nullptr;
+   sa.seq = r->settle.enqueue(trackable, r->frame_pipelined ? 1 : 0, &slot);
+   if (sa.seq) { sa.ctr = r->d_settle.ptr; sa.slot = (unsigned long long *)(void *)slot; }
+   return MDH_OK;
+}
 static int pass_irradiance(PassRun &p)
 {
    mdh_renderer *r = p.r;
@@ -2208,8 +2260,10 @@ static int pass_irradiance(PassRun &p)
          r->irr_lds_granted = true;
       }
    }
+   SettleArgs sa = {nullptr, nullptr, 0u};
+   if (r->in_frame) { int src = settle_args(p, n, sa); if (src != MDH_OK) return src; }
    // (hysteresis: the previous frame's irradiance is set `src` -- the same set when the pass runs in place)
-   if (n > 0) hipLaunchKernelGGL(k_irradiance, dim3(n), dim3(MDH_IRR_BLOCK), lds, p.st, pr, (const void *)r->d_irr2[p.src].ptr, (float)r->opt_hyst / 1000.0f, tap_planes);
+   if (n > 0) hipLaunchKernelGGL(k_irradiance, dim3(n), dim3(MDH_IRR_BLOCK), lds, p.st, pr, (const void *)r->d_irr2[p.src].ptr, (float)r->opt_hyst / 1000.0f, tap_planes, sa);
    return MDH_OK;
 }
 
@@ -2426,6 +2480,7 @@ static int run_pass(mdh_renderer *r, int pass, hipStream_t st, int src, int dst,
 
 extern "C" int32_t mdh_render_pass(mdh_renderer *r, int32_t pass)
 {
+   settle_bump(r);
    if (!r) return seterr(MDH_E_INVALID, "null renderer");
    if (r->in_frame) return seterr(MDH_E_STATE, "a frame is open: use mdh_frame_probe_pass / mdh_frame_end");
    if (r->opt_rank >= r->opt_world) return seterr(MDH_E_STATE, "MDH_OPT_RANK is not below MDH_OPT_WORLD");
@@ -2489,6 +2544,10 @@ extern "C" int32_t mdh_frame_begin(mdh_renderer *r)
       r->frame_cur = cur;
    }
    r->in_frame = true;
+   // MDH_OPT_PROBE_SETTLE: the slots that have arrived are read (no wait), and the frame's probe passes are left out when the
+   // atlases have stopped changing -- the sets rotate, the events are recorded and every other pass runs as ever
+   r->frame_probe_seq = 0;
+   (void)r->settle.frame_begin(settle_eligible(r), r->frame_pipelined ? 1 : 0);
    return MDH_OK;
 }
 // a pass of an open frame failed: close the frame and make the next one re-join every stream (the work already
@@ -2497,6 +2556,7 @@ static int abandon_frame(mdh_renderer *r, int rc)
 {
    r->in_frame = false;
    r->main_dirty = true;
+   r->settle.reset();
    if (r->probe_stream) (void)hipStreamSynchronize(r->probe_stream);
    if (r->vol_stream) (void)hipStreamSynchronize(r->vol_stream);
    return rc;
@@ -2507,6 +2567,22 @@ extern "C" int32_t mdh_frame_probe_pass(mdh_renderer *r, int32_t pass)
    if (!r->in_frame) return seterr(MDH_E_STATE, "no open frame");
    if (pass != MDH_PASS_RADIANCE && pass != MDH_PASS_IRRADIANCE) return seterr(MDH_E_INVALID, "not a probe pass");
    if (r->opt_mode != 0) return MDH_OK; // modes 1 and 2 draw without probes (renderers.adb:302-321 runs them anyway; nothing reads them)
+   if (r->settle.skip_pass()) { // the pass would store the bits its set already holds (all sets hold them): not launched
+      ++r->settle_skipped;
+      if (r->opt_timing) { // (mdh_pass_time counts the passes of frames, run or settled: this one's time is what lies between its two events)
+         HIP_TRY(hipSetDevice(r->device));
+         hipEvent_t e0 = get_event(r), e1 = get_event(r);
+         if (!e0 || !e1) return seterr(MDH_E_DEVICE, "hipEventCreate failed");
+         HIP_TRY(hipEventRecord(e0, frame_probe_stream(r)));
+         HIP_TRY(hipEventRecord(e1, frame_probe_stream(r)));
+         r->pending.push_back({pass, e0, e1});
+      }
+      return MDH_OK;
+   }
+   if (pass == MDH_PASS_RADIANCE) {
+      if (r->frame_probe_seq == 0) r->frame_probe_seq = 1;
+      else { r->frame_probe_seq = -1; r->settle.untracked_pass(); }
+   }
    return run_pass(r, pass, frame_probe_stream(r), r->last, r->frame_cur);
 }
 static int frame_end_passes(mdh_renderer *r);
@@ -2742,6 +2818,7 @@ static int peer_check(mdh_renderer *r)
 }
 extern "C" int32_t mdh_peer_export(mdh_renderer *r, uint8_t blob_out[MDH_PEER_BLOB_BYTES])
 {
+   settle_bump(r);
    if (!r || !blob_out) return seterr(MDH_E_INVALID, "bad argument");
    if (r->in_frame) return seterr(MDH_E_STATE, "a frame is open");
    if (r->comm || peer_active(r)) return seterr(MDH_E_STATE, "the renderer has a communicator");
@@ -2771,6 +2848,7 @@ extern "C" int32_t mdh_peer_export(mdh_renderer *r, uint8_t blob_out[MDH_PEER_BL
 }
 extern "C" int32_t mdh_peer_init(mdh_renderer *r, const uint8_t *blobs, int32_t rank, int32_t world)
 {
+   settle_bump(r);
    if (!r || !blobs) return seterr(MDH_E_INVALID, "bad argument");
    if (world < 1 || rank < 0 || rank >= world) return seterr(MDH_E_INVALID, "rank is not below world");
    if (r->in_frame) return seterr(MDH_E_STATE, "a frame is open");
@@ -2856,6 +2934,7 @@ extern "C" int32_t mdh_comm_unique_id(uint8_t id_out[MDH_COMM_ID_BYTES])
 }
 extern "C" int32_t mdh_comm_init(mdh_renderer *r, const uint8_t id_in[MDH_COMM_ID_BYTES], int32_t rank, int32_t world)
 {
+   settle_bump(r);
    if (!r || !id_in) return seterr(MDH_E_INVALID, "bad argument");
    if (world < 1 || rank < 0 || rank >= world) return seterr(MDH_E_INVALID, "rank is not below world");
    if (r->in_frame) return seterr(MDH_E_STATE, "a frame is open");
@@ -2881,6 +2960,7 @@ extern "C" int32_t mdh_comm_init(mdh_renderer *r, const uint8_t id_in[MDH_COMM_I
 // the renderer is rank 0 of 1 again (the handle itself is the caller's business)
 static void comm_forget(mdh_renderer *r)
 {
+   settle_bump(r);
    r->comm = nullptr;
    r->comm_aborted = false;
    r->opt_rank = 0;
@@ -2912,6 +2992,7 @@ struct CommBusy { // the owning thread is inside RCCL with r->comm
 };
 extern "C" int32_t mdh_comm_destroy(mdh_renderer *r)
 {
+   settle_bump(r);
    if (!r) return seterr(MDH_E_INVALID, "null renderer");
    if (r->in_frame) return seterr(MDH_E_STATE, "a frame is open");
    HIP_TRY(hipSetDevice(r->device));
@@ -3007,6 +3088,7 @@ extern "C" int32_t mdh_frame_exchange(mdh_renderer *r, int32_t tex)
 }
 extern "C" int32_t mdh_comm_barrier(mdh_renderer *r)
 {
+   settle_bump(r);
    if (!r) return seterr(MDH_E_INVALID, "null renderer");
    if (r->in_frame) return seterr(MDH_E_STATE, "a frame is open");
    int rc = mdh_finish(r);
@@ -3021,6 +3103,7 @@ extern "C" int32_t mdh_comm_barrier(mdh_renderer *r)
 }
 extern "C" int32_t mdh_comm_max_f64(mdh_renderer *r, double *value)
 {
+   settle_bump(r);
    if (!r || !value) return seterr(MDH_E_INVALID, "bad argument");
    if (r->in_frame) return seterr(MDH_E_STATE, "a frame is open");
    if (peer_active(r)) return seterr(MDH_E_STATE, "the peer exchange has no collectives");
@@ -3037,6 +3120,7 @@ extern "C" int32_t mdh_comm_max_f64(mdh_renderer *r, double *value)
 }
 extern "C" int32_t mdh_comm_reduce_framebuffer(mdh_renderer *r, int32_t root)
 {
+   settle_bump(r);
    if (!r) return seterr(MDH_E_INVALID, "null renderer");
    if (r->in_frame) return seterr(MDH_E_STATE, "a frame is open");
    if (peer_active(r)) return seterr(MDH_E_STATE, "the peer exchange has no collectives: read every rank's framebuffer and add them");
@@ -3290,6 +3374,7 @@ extern "C" int32_t mdh_read_texture(mdh_renderer *r, int32_t tex, float *out, in
 }
 extern "C" int32_t mdh_write_texture(mdh_renderer *r, int32_t tex, const float *in, int32_t w, int32_t h, int32_t c)
 {
+   settle_bump(r);
    if (!r || tex < 0 || tex > 3 || !in) return seterr(MDH_E_INVALID, "bad argument");
    HIP_TRY(hipSetDevice(r->device));
    { int jr = join_main(r); if (jr != MDH_OK) return jr; }
@@ -3331,6 +3416,7 @@ extern "C" int32_t mdh_read_atlas_slice(mdh_renderer *r, int32_t tex, int32_t pr
 }
 extern "C" int32_t mdh_write_atlas_slice(mdh_renderer *r, int32_t tex, int32_t probe_begin, int32_t n_probes, const float *in)
 {
+   settle_bump(r);
    if (!r || (tex != MDH_TEX_RADIANCE && tex != MDH_TEX_IRRADIANCE) || !in) return seterr(MDH_E_INVALID, "bad argument");
    if (probe_begin < 0 || n_probes < 0 || probe_begin + n_probes > probe_total(r)) return seterr(MDH_E_INDEX, "probe range");
    HIP_TRY(hipSetDevice(r->device));
@@ -3339,6 +3425,7 @@ extern "C" int32_t mdh_write_atlas_slice(mdh_renderer *r, int32_t tex, int32_t p
 }
 extern "C" int32_t mdh_atlas_device_ptr(mdh_renderer *r, int32_t tex, void **dptr, int64_t *total_bytes, int64_t *own_offset, int64_t *own_bytes)
 {
+   settle_bump(r);
    if (!r || (tex != MDH_TEX_RADIANCE && tex != MDH_TEX_IRRADIANCE)) return seterr(MDH_E_INVALID, "bad argument");
    if (r->opt_rank >= r->opt_world) return seterr(MDH_E_STATE, "MDH_OPT_RANK is not below MDH_OPT_WORLD");
    int res = tex == MDH_TEX_RADIANCE ? r->probes.radiance_resolution : r->probes.irradiance_resolution;
@@ -3365,6 +3452,7 @@ extern "C" int32_t mdh_stream(mdh_renderer *r, void **stream)
 }
 extern "C" int32_t mdh_set_stream(mdh_renderer *r, void *stream)
 {
+   settle_bump(r);
    if (!r) return seterr(MDH_E_INVALID, "null renderer");
    HIP_TRY(hipSetDevice(r->device));
    { int jr = join_main(r); if (jr != MDH_OK) return jr; }
@@ -3384,6 +3472,7 @@ extern "C" int32_t mdh_set_stream(mdh_renderer *r, void *stream)
 extern "C" int32_t mdh_eval_distance_to(mdh_renderer *r, int32_t n, const float *pts, const int32_t *kind_ixs, int32_t n_kinds,
                                         float *normals_out, float *dist_out)
 {
+   settle_bump(r);
    if (!r || !pts || !kind_ixs || !dist_out || n < 0 || n_kinds < 0 || n_kinds > MDH_MAX_KINDS) return seterr(MDH_E_INVALID, "bad argument");
    for (int i = 0; i < n_kinds; ++i)
       if (kind_ixs[i] < 0 || kind_ixs[i] >= r->npk) return seterr(MDH_E_INVALID, "bad kind index");
@@ -3455,6 +3544,17 @@ extern "C" int32_t mdh_screen_replay_stats(mdh_renderer *r, int64_t *plain, int6
 }
 // the size of a pixel's record (tests/test_screen_replay_host.py holds DESIGN.md's figure against it)
 extern "C" int32_t mdh_screen_record_bytes(void) { return (int32_t)sizeof(PixelRecord); }
+// MDH_OPT_PROBE_SETTLE: the run of unchanged irradiance passes under the inputs that hold now, probe passes not launched
+// since creation, texels the newest observed pass changed.  Reads the slots that have arrived; waits for nothing.
+extern "C" int32_t mdh_probe_settle_stats(mdh_renderer *r, int64_t *run, int64_t *skipped, int64_t *last_changed_texels)
+{
+   if (!r) return seterr(MDH_E_INVALID, "null renderer");
+   if (r->settle.slots) r->settle.poll();
+   if (run) *run = r->settle.current_run();
+   if (skipped) *skipped = r->settle_skipped;
+   if (last_changed_texels) *last_changed_texels = r->settle.last_changed;
+   return MDH_OK;
+}
 // MDH_OPT_RADIANCE_REPLAY: radiance passes launched since creation that marched, marched and recorded, replayed
 extern "C" int32_t mdh_radiance_replay_stats(mdh_renderer *r, int64_t *plain, int64_t *recording, int64_t *replaying)
 {

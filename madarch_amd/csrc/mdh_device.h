@@ -1634,17 +1634,24 @@ template <bool P2 = false> MDH_DEV f3 atlas_texel(const void *base, int fmt, uns
    const f4v t = ((GlobalF4)base)[idx];
    return F3(t.x, t.y, t.z);
 }
+// The words an atlas texel is stored as -- the one place that says so: atlas_store stores them, MDH_OPT_PROBE_SETTLE compares
+// them (mdh_kernels.h).  RGBA8: x, y, z, 255 from the low byte up; float32: the three values with NaN as 0, then 1.
+MDH_DEV uchar4 atlas_word_rgba8(f3 v)
+{
+   uchar4 t;
+   t.x = (unsigned char)unorm8(v.x); t.y = (unsigned char)unorm8(v.y); t.z = (unsigned char)unorm8(v.z); t.w = 255;
+   return t;
+}
+MDH_DEV float4 atlas_word_f32(f3 v)
+{
+   float4 t;
+   t.x = (v.x != v.x) ? 0.0f : v.x; t.y = (v.y != v.y) ? 0.0f : v.y; t.z = (v.z != v.z) ? 0.0f : v.z; t.w = 1.0f;
+   return t;
+}
 MDH_DEV void atlas_store(void *base, int fmt, unsigned idx, f3 v)
 {
-   if (fmt == 0) {
-      uchar4 t;
-      t.x = (unsigned char)unorm8(v.x); t.y = (unsigned char)unorm8(v.y); t.z = (unsigned char)unorm8(v.z); t.w = 255;
-      ((uchar4 *)base)[idx] = t;
-   } else {
-      float4 t;
-      t.x = (v.x != v.x) ? 0.0f : v.x; t.y = (v.y != v.y) ? 0.0f : v.y; t.z = (v.z != v.z) ? 0.0f : v.z; t.w = 1.0f;
-      ((float4 *)base)[idx] = t;
-   }
+   if (fmt == 0) ((uchar4 *)base)[idx] = atlas_word_rgba8(v);
+   else ((float4 *)base)[idx] = atlas_word_f32(v);
 }
 // GL_LINEAR on the atlas image of pcx*res x pcy*res texels (render_passes.adb:113-114); Wf, Hf = (float)(pcx * res), (float)(pcy * res)
 template <bool P2 = false>

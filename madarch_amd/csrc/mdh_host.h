@@ -169,3 +169,80 @@ struct RingUse {
          for (bool &u : slot) u = false;
    }
 };
+
+// "Have the probe atlases stopped changing?" (MDH_OPT_PROBE_SETTLE; DESIGN.md section 4, "Exact work elimination", item 13).
+// Every tracked irradiance pass of a frame reports, through one slot of a small ring in memory the device can write, how many
+// texels it stored with other bits than the set it read held.  The tracker numbers the passes, remembers under which version of
+// the probe passes' inputs and under which schedule each was enqueued, reads the slots that have arrived -- it never waits --
+// and keeps the length of the run of consecutive unchanged passes.  A frame's probe passes may be left out once that run is
+// MDH_SETTLE_PASSES long, all of it enqueued under the version and the schedule that still hold.
+// No runtime call in here: the slots' memory is the caller's (pinned host memory in the renderer, plain memory in
+// tests/settle_check.cpp).
+#ifndef MDH_SETTLE_PASSES
+#define MDH_SETTLE_PASSES 16 // exactness needs MDH_ATLAS_SETS (every set then holds the same bits); the rest is margin that costs nothing in steady state
+#endif
+struct alignas(8) SettleSlot { unsigned changed, seq; }; // the device writes both as ONE 64-bit store: changed in the low word, seq in the high one
+struct SettleTracker {
+   static constexpr int RING = 64; // tracked passes in flight stay below it: a slot is never rewritten before it was read
+   SettleSlot *slots = nullptr;    // [RING], zeroed by the caller
+   struct Meta { unsigned long long pass, version; int schedule; };
+   Meta meta[RING] = {};
+   unsigned long long version = 1;                  // of everything a probe pass reads besides the irradiance atlas: bump ()
+   unsigned long long issued = 0;                   // irradiance passes of frames enqueued so far, tracked or not: a pass's number
+   unsigned long long seq_issued = 0, seq_seen = 0; // tracked passes enqueued / whose slot was read
+   unsigned long long floor = 0;                    // passes up to this number count for no run (reset)
+   unsigned long long last_pass = 0, run_version = 0;
+   int run_schedule = -1;
+   long long run = 0;
+   unsigned last_changed = 0;                       // texels the newest observed pass changed
+   bool enabled = true;
+   // the open frame: what frame_begin decided, and the version it decided under
+   bool frame_skip = false;
+   unsigned long long frame_version = 0;
+
+   static unsigned long long next_seq(unsigned long long s) { return (unsigned)(s + 1) == 0u ? s + 2 : s + 1; } // (a slot's 0 means "nothing yet")
+   void bump() { ++version; }
+   void reset() { run = 0; floor = issued; }
+   void set_enabled(bool on) { if (!on) { reset(); frame_skip = false; } enabled = on; } // (off inside an open frame: its passes run)
+   long long current_run() const { return run_version == version ? run : 0; }
+   // read the slots that have arrived, oldest first
+   void poll()
+   {
+      while (seq_seen != seq_issued) {
+         const unsigned long long s = next_seq(seq_seen);
+         const SettleSlot *sl = slots + s % RING;
+         static_assert(sizeof(SettleSlot) == sizeof(unsigned long long), "a slot is one 64-bit word");
+         const unsigned long long word = __atomic_load_n((const unsigned long long *)(const void *)sl, __ATOMIC_ACQUIRE); // (both halves of one store)
+         if ((unsigned)(word >> 32) != (unsigned)s) break;
+         const unsigned changed = (unsigned)word;
+         const Meta m = meta[s % RING];
+         seq_seen = s;
+         if (changed || m.pass != last_pass + 1 || m.pass <= floor || m.version != run_version || m.schedule != run_schedule) run = 0;
+         run_version = m.version; run_schedule = m.schedule; last_pass = m.pass; last_changed = changed;
+         if (!changed && m.pass > floor && run < (1ll << 62)) ++run;
+      }
+   }
+   // A frame opens: may its probe passes be left out?  `eligible`: screen mode 0 and a single rank (no communicator, no peer
+   // exchange, world 1 -- collectives stay matched across ranks).
+   bool frame_begin(bool eligible, int schedule)
+   {
+      if (slots) poll();
+      frame_version = version;
+      frame_skip = enabled && eligible && slots && run >= MDH_SETTLE_PASSES && run_version == version && run_schedule == schedule;
+      return frame_skip;
+   }
+   // asked for every probe pass of the open frame (an edit between frame_begin and the pass makes it run)
+   bool skip_pass() const { return frame_skip && version == frame_version; }
+   // An irradiance pass of the open frame is about to be launched.  Returns the slot's word for the kernel and *slot, or 0:
+   // the pass runs untracked (the feature is off, the frame is not eligible or irregular, the ring is full), which ends the run.
+   unsigned enqueue(bool trackable, int schedule, SettleSlot **slot)
+   {
+      ++issued;
+      if (!enabled || !trackable || !slots || seq_issued - seq_seen >= RING - 2) return 0u; // (- 2: next_seq may pass over a number)
+      seq_issued = next_seq(seq_issued);
+      meta[seq_issued % RING] = {issued, frame_version, schedule};
+      *slot = slots + seq_issued % RING;
+      return (unsigned)seq_issued;
+   }
+   void untracked_pass() { ++issued; } // a probe pass outside the frame's one-radiance-then-one-irradiance pattern: the chain breaks
+};

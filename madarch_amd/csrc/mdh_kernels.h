@@ -629,6 +629,62 @@ __global__ __launch_bounds__(256) void k_order_floor(unsigned char *keys, int n,
 #define MDH_IRR_CHANNELS_LDS ((size_t)2 * 64 * (MDH_IRR_CCHUNK + 4) * sizeof(float))
 #define MDH_IRR_CHANNELS_PLANE(n) ((size_t)(((n) + 63) / 64 * 64))
 typedef float pk2 __attribute__((ext_vector_type(2))); // two fp32 per VALU instruction (v_pk_mul_f32 / v_pk_add_f32: IEEE per component)
+// MDH_OPT_PROBE_SETTLE (mdh_host.h: SettleTracker; DESIGN.md section 4, "Exact work elimination", item 13): a tracked pass
+// (seq != 0) counts the texels it stores with other bits than `prev` -- the irradiance set the radiance pass read, this pass's
+// own set when it runs in place -- holds at the same index, and the workgroup that finishes last hands the count to the host.
+// Compiled out of the builds that count or time the work of passes.
+#ifndef MDH_PROBE_SETTLE
+#if defined(MDH_DIAG) || defined(MDH_PHASES)
+#define MDH_PROBE_SETTLE 0
+#else
+#define MDH_PROBE_SETTLE 1
+#endif
+#endif
+struct SettleArgs {
+   unsigned long long *ctr;  // of the pass under way: workgroups done in the low word, texels changed in the high one; zero between passes
+   unsigned long long *slot; // {changed, seq} in pinned host memory (SettleSlot), one 64-bit word
+   unsigned seq;             // 0: an untracked pass, nothing of this runs
+};
+struct AtlasBits { unsigned x, y, z, w; }; // a texel as stored: the RGBA8 word in x (format 0), the four floats' bits (format 1)
+MDH_DEV AtlasBits atlas_bits(const void *base, int fmt, unsigned idx)
+{
+   AtlasBits b = {0u, 0u, 0u, 0u};
+   if (fmt == 0) b.x = atlas_rgba8(base, idx);
+   else {
+      const f4v t = ((GlobalF4)base)[idx];
+      b.x = __float_as_uint(t.x); b.y = __float_as_uint(t.y); b.z = __float_as_uint(t.z); b.w = __float_as_uint(t.w);
+   }
+   return b;
+}
+// atlas_store, and whether the words stored differ from `old` (compared as integers: a NaN equals itself).  The words are
+// atlas_word_*'s, stored here as atlas_store stores them: what is compared is what is stored.
+MDH_DEV bool atlas_store_changed(void *base, int fmt, unsigned idx, f3 v, const AtlasBits &old)
+{
+   if (fmt == 0) {
+      const uchar4 t = atlas_word_rgba8(v);
+      ((uchar4 *)base)[idx] = t;
+      return ((unsigned)t.x | (unsigned)t.y << 8 | (unsigned)t.z << 16 | (unsigned)t.w << 24) != old.x;
+   }
+   const float4 t = atlas_word_f32(v);
+   ((float4 *)base)[idx] = t;
+   return __float_as_uint(t.x) != old.x || __float_as_uint(t.y) != old.y || __float_as_uint(t.z) != old.z || __float_as_uint(t.w) != old.w;
+}
+// One lane per workgroup, behind the workgroup's stores.  ONE atomic carries both counters -- the workgroup's changed texels
+// into the high word, one more workgroup done into the low one -- so the workgroup that finds itself last has the pass's total
+// in the value the atomic returns, and nothing has to be ordered against anything: no fence.  (measured: the first form, two
+// counters with __threadfence between them, made the pass 0.031 -> 0.039 ms alone and 0.072 -> 0.096 ms in flight at config
+// 3, profiles/r11_probe_settle_ab.log -- a device-scope release on this chip writes the L2's dirty lines back, the
+// workgroups' 12 MB of tap planes among them, once per workgroup.)  The last workgroup hands {changed, seq} to the host as
+// one 64-bit store -- the host reads both or neither -- and puts the counter back to zero for the next pass (passes follow
+// one another on their stream).
+MDH_DEV void settle_report(const SettleArgs &sa, unsigned nchanged, unsigned nblocks)
+{
+   const unsigned long long before = atomicAdd(sa.ctr, ((unsigned long long)nchanged << 32) | 1ull);
+   if ((unsigned)before + 1u != nblocks) return;
+   const unsigned total = (unsigned)(before >> 32) + nchanged;
+   __hip_atomic_store(sa.ctr, 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+   __hip_atomic_store(sa.slot, (unsigned long long)total | (unsigned long long)sa.seq << 32, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+}
 // `prev`, `hyst`: MDH_OPT_HYSTERESIS_PERMILLE (not in the reference; 0 = off): the texel is stored as
 // mix (fresh, what the previous frame's atlas holds, hyst)
 MDH_DEV f3 irradiance_blend(const KProbes &pr, const void *prev, float hyst, unsigned idx, f3 fresh)
@@ -682,8 +738,9 @@ template <bool RAD, int NB> MDH_DEV float irr_fold(const float *rv, const float4
 #undef MDH_IRR_F4
    return acc;
 }
-__global__ __launch_bounds__(MDH_IRR_BLOCK) void k_irradiance(KProbes pr, const void *prev, float hyst, float *tap_planes)
+__global__ __launch_bounds__(MDH_IRR_BLOCK) void k_irradiance(KProbes pr, const void *prev, float hyst, float *tap_planes, SettleArgs sa)
 {
+   const bool settle = MDH_PROBE_SETTLE && sa.seq != 0u; // (uniform)
    extern __shared__ float4 s_taps[]; // [2 * rres * rres]: {rad.xyz, 1} {dir.xyz, -}
    const int probe = pr.probe_begin + blockIdx.x;
    if (probe >= pr.probe_end) return;
@@ -725,12 +782,18 @@ __global__ __launch_bounds__(MDH_IRR_BLOCK) void k_irradiance(KProbes pr, const 
       float4 *part = s_taps + 2 * ntaps;
       part[wv * 64 + lane] = acc;
       __syncthreads();
-      if (wv == 0 && lane < pr.ires * pr.ires) {
-         const float4 a = part[lane], b = part[64 + lane], c = part[128 + lane], d = part[192 + lane];
-         const f3 sum = F3((a.x + b.x) + (c.x + d.x), (a.y + b.y) + (c.y + d.y), (a.z + b.z) + (c.z + d.z));
-         const f3 irradiance = sum / ((a.w + b.w) + (c.w + d.w));
-         const unsigned idx = atlas_index(pr.pcx, pr.ires, pr.ishift, i, j);
-         atlas_store(pr.irr, pr.fmt, idx, irradiance_blend(pr, prev, hyst, idx, irradiance));
+      if (wv == 0) {
+         bool changed = false;
+         if (lane < pr.ires * pr.ires) {
+            const float4 a = part[lane], b = part[64 + lane], c = part[128 + lane], d = part[192 + lane];
+            const f3 sum = F3((a.x + b.x) + (c.x + d.x), (a.y + b.y) + (c.y + d.y), (a.z + b.z) + (c.z + d.z));
+            const f3 irradiance = sum / ((a.w + b.w) + (c.w + d.w));
+            const unsigned idx = atlas_index(pr.pcx, pr.ires, pr.ishift, i, j);
+            const f3 v = irradiance_blend(pr, prev, hyst, idx, irradiance);
+            if (settle) changed = atlas_store_changed(pr.irr, pr.fmt, idx, v, atlas_bits(prev, pr.fmt, idx));
+            else atlas_store(pr.irr, pr.fmt, idx, v);
+         }
+         if (settle) { const unsigned n = (unsigned)__popcll(__ballot(changed)); if (lane == 0) settle_report(sa, n, gridDim.x); }
       }
       return;
    }
@@ -765,6 +828,13 @@ __global__ __launch_bounds__(MDH_IRR_BLOCK) void k_irradiance(KProbes pr, const 
       const int i = tx * pr.ires + x, j = ty * pr.ires + y;
       const f2 nc = F2((centre(i, pr.pcx * pr.ires) + 1.0f) * 0.5f, (centre(j, pr.pcy * pr.ires) + 1.0f) * 0.5f);
       const f3 irr_dir = ray_id_to_ray_dir(F2(fract_(nc.x * pcx), fract_(nc.y * pcy)));
+      // MDH_OPT_PROBE_SETTLE: the RGBA8 word the texel held, asked for here, a whole fold ahead of its use (the lane owns the
+      // texel: when the pass runs in place nothing else writes it before this lane's store).  One register; the four of a
+      // float32 texel are read behind the fold instead (held through it they cost the kernel a workgroup per CU: 96 -> 98
+      // vector registers, measured).
+      const unsigned out_idx = atlas_index(pr.pcx, pr.ires, pr.ishift, i, j);
+      unsigned out_old8 = 0u;
+      if (settle && pr.fmt == 0 && wv == 0 && lane < ntex) out_old8 = atlas_rgba8(prev, out_idx);
 #ifdef MDH_PHASES
       const unsigned long long ph_k0 = __builtin_amdgcn_s_memtime();
 #endif
@@ -886,10 +956,19 @@ __global__ __launch_bounds__(MDH_IRR_BLOCK) void k_irradiance(KProbes pr, const 
       // the four sums of a texel back to one lane (through the weight rows: the loop's last barrier is behind every read of them)
       if (wv > 0) s_w[(wv - 1) * 64 + lane] = acc;
       __syncthreads();
-      if (wv == 0 && lane < ntex) {
-         const f3 irradiance = F3(acc, s_w[lane], s_w[64 + lane]) / s_w[128 + lane];
-         const unsigned idx = atlas_index(pr.pcx, pr.ires, pr.ishift, i, j);
-         atlas_store(pr.irr, pr.fmt, idx, irradiance_blend(pr, prev, hyst, idx, irradiance));
+      if (wv == 0) {
+         bool changed = false;
+         if (lane < ntex) {
+            const f3 irradiance = F3(acc, s_w[lane], s_w[64 + lane]) / s_w[128 + lane];
+            const f3 v = irradiance_blend(pr, prev, hyst, out_idx, irradiance);
+            if (settle) {
+               AtlasBits out_old = {out_old8, 0u, 0u, 0u};
+               if (pr.fmt != 0) out_old = atlas_bits(prev, pr.fmt, out_idx);
+               changed = atlas_store_changed(pr.irr, pr.fmt, out_idx, v, out_old);
+            } else atlas_store(pr.irr, pr.fmt, out_idx, v);
+         }
+         // (behind the store: the fold's last wavefront has nothing left to do but this)
+         if (settle) { const unsigned n = (unsigned)__popcll(__ballot(changed)); if (lane == 0) settle_report(sa, n, gridDim.x); }
       }
       return;
    }
@@ -954,16 +1033,23 @@ __global__ __launch_bounds__(MDH_IRR_BLOCK) void k_irradiance(KProbes pr, const 
          }
          __syncthreads();
       }
-      if (wv == 0 && lane < pr.ires * pr.ires) {
-         const f3 irradiance = F3(acc_xy.x, acc_xy.y, acc_zw.x) / acc_zw.y;
-         const unsigned idx = atlas_index(pr.pcx, pr.ires, pr.ishift, i, j);
-         atlas_store(pr.irr, pr.fmt, idx, irradiance_blend(pr, prev, hyst, idx, irradiance));
+      if (wv == 0) {
+         bool changed = false;
+         if (lane < pr.ires * pr.ires) {
+            const f3 irradiance = F3(acc_xy.x, acc_xy.y, acc_zw.x) / acc_zw.y;
+            const unsigned idx = atlas_index(pr.pcx, pr.ires, pr.ishift, i, j);
+            const f3 v = irradiance_blend(pr, prev, hyst, idx, irradiance);
+            if (settle) changed = atlas_store_changed(pr.irr, pr.fmt, idx, v, atlas_bits(prev, pr.fmt, idx));
+            else atlas_store(pr.irr, pr.fmt, idx, v);
+         }
+         if (settle) { const unsigned n = (unsigned)__popcll(__ballot(changed)); if (lane == 0) settle_report(sa, n, gridDim.x); }
       }
       return;
    }
    for (int tap = threadIdx.x; tap < ntaps; tap += MDH_IRR_BLOCK) MDH_IRR_STAGE(tap, tap);
 #undef MDH_IRR_STAGE
    __syncthreads();
+   unsigned n_changed = 0u; // (this lane's texels)
    for (int rem = threadIdx.x; rem < pr.ires * pr.ires; rem += MDH_IRR_BLOCK) {
       const int y = rem / pr.ires, x = rem - y * pr.ires;
       const int i = tx * pr.ires + x, j = ty * pr.ires + y;
@@ -987,7 +1073,21 @@ __global__ __launch_bounds__(MDH_IRR_BLOCK) void k_irradiance(KProbes pr, const 
       total_weight = acc_zw.y;
       irradiance = irradiance / total_weight;
       const unsigned idx = atlas_index(pr.pcx, pr.ires, pr.ishift, i, j);
-      atlas_store(pr.irr, pr.fmt, idx, irradiance_blend(pr, prev, hyst, idx, irradiance));
+      const f3 v = irradiance_blend(pr, prev, hyst, idx, irradiance);
+      if (settle) n_changed += atlas_store_changed(pr.irr, pr.fmt, idx, v, atlas_bits(prev, pr.fmt, idx)) ? 1u : 0u;
+      else atlas_store(pr.irr, pr.fmt, idx, v);
+   }
+   if (settle) { // the wavefronts' counts through LDS (behind the last read of the taps), then one lane of the workgroup reports
+      for (int off = 32; off > 0; off >>= 1) n_changed += (unsigned)__shfl_xor((int)n_changed, off);
+      unsigned *s_cnt = (unsigned *)s_taps;
+      __syncthreads();
+      if ((threadIdx.x & 63) == 0) s_cnt[threadIdx.x >> 6] = n_changed;
+      __syncthreads();
+      if (threadIdx.x == 0) {
+         unsigned n = 0u;
+         for (int w = 0; w < MDH_IRR_BLOCK / 64; ++w) n += s_cnt[w];
+         settle_report(sa, n, gridDim.x);
+      }
    }
 }
 

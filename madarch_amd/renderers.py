@@ -260,6 +260,13 @@ class Renderer:
         self._b.check(self._b.radiance_replay_stats(self._h, *[C.byref(x) for x in v]))
         return tuple(x.value for x in v)
 
+    def Probe_Settle_Stats(self):
+        """OPT_PROBE_SETTLE: (run of unchanged irradiance passes under the present inputs, probe passes not launched
+        since creation, texels the newest observed pass changed)."""
+        v = [C.c_int64(0) for _ in range(3)]
+        self._b.check(self._b.probe_settle_stats(self._h, *[C.byref(x) for x in v]))
+        return tuple(int(x.value) for x in v)
+
     def Screen_Replay_Stats(self):
         """OPT_SCREEN_REPLAY: screen passes since creation that (marched, marched and recorded, replayed)."""
         v = [C.c_int64(0) for _ in range(3)]
