@@ -161,6 +161,24 @@ package Madarch_HIP is
       N_Kinds : int; Normals_Out, Dist_Out : System.Address) return Status
      with Import, Convention => C, External_Name => "mdh_eval_distance_to";
 
+   --  Ray queries (madarch_hip.h): the shaders' raycast, raycast_visibility and softshadows for
+   --  N rays of the host's, on the device beside the frames in flight.  Org and Dir: 3 N floats,
+   --  directions as given; every output of Raycast but Hit_Out may be Null_Address.  Scenes of
+   --  built-in kinds only (Status 7 otherwise); they edit nothing.
+   function Raycast
+     (R : Handle; N : int; Org, Dir : System.Address;
+      Hit_Out, Index_Out, T_Out, Steps_Out, Pos_Out, Normal_Out : System.Address) return Status
+     with Import, Convention => C, External_Name => "mdh_raycast";
+
+   function Raycast_Visibility
+     (R : Handle; N : int; Org, Dir, T_Max, Vis_Out : System.Address) return Status
+     with Import, Convention => C, External_Name => "mdh_raycast_visibility";
+
+   function Softshadows
+     (R : Handle; N : int; Org, Dir : System.Address; T_Min : C_float;
+      T_Max : System.Address; K : C_float; Shadow_Out : System.Address) return Status
+     with Import, Convention => C, External_Name => "mdh_softshadows";
+
    --  One frame on the N GPUs of a node, one process per GPU (madarch_hip.h, mdh_comm_*):
    --  every process creates its Renderer on its own device, rank 0 makes a 128-byte id and
    --  hands it to the others (a file, an environment variable), all call Comm_Init, and

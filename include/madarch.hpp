@@ -342,6 +342,38 @@ class Renderer {
       Check(mdh_eval_distance_to(h_.get(), 1, Position.data(), kinds.data(), (int32_t)kinds.size(), Normal.data(), &d));
       return d;
    }
+   // ---- ray queries (raymarching.glsl:4-56), batched on the device beside the frames in flight; they edit nothing.
+   // Origins and Directions hold 3 floats a ray (directions as given, not normalised); scenes of built-in kinds only
+   static size_t Ray_Count(const std::vector<float> &Origins, const std::vector<float> &Directions)
+   {
+      if (Origins.size() % 3 != 0 || Directions.size() != Origins.size()) throw Constraint_Error("origins and directions hold 3 floats a ray");
+      return Origins.size() / 3;
+   }
+   struct Ray_Hits { std::vector<int32_t> Hit, Index, Steps; std::vector<float> T, Position, Normal; }; // Index as in the geometry buffer, -1 = miss
+   Ray_Hits Raycast(const std::vector<float> &Origins, const std::vector<float> &Directions) const
+   {
+      const size_t n = Ray_Count(Origins, Directions);
+      Ray_Hits o;
+      o.Hit.resize(n); o.Index.resize(n); o.Steps.resize(n); o.T.resize(n); o.Position.resize(3 * n); o.Normal.resize(3 * n);
+      Check(mdh_raycast(h_.get(), (int32_t)n, Origins.data(), Directions.data(), o.Hit.data(), o.Index.data(), o.T.data(), o.Steps.data(), o.Position.data(), o.Normal.data()));
+      return o;
+   }
+   std::vector<float> Raycast_Visibility(const std::vector<float> &Origins, const std::vector<float> &Directions, const std::vector<float> &Max_Dists) const
+   {
+      const size_t n = Ray_Count(Origins, Directions);
+      if (Max_Dists.size() != n) throw Constraint_Error("one length per ray");
+      std::vector<float> vis(n);
+      Check(mdh_raycast_visibility(h_.get(), (int32_t)n, Origins.data(), Directions.data(), Max_Dists.data(), vis.data()));
+      return vis;
+   }
+   std::vector<float> Softshadows(const std::vector<float> &Origins, const std::vector<float> &Directions, Single Min_Dist, const std::vector<float> &Max_Dists, Single K) const
+   {
+      const size_t n = Ray_Count(Origins, Directions);
+      if (Max_Dists.size() != n) throw Constraint_Error("one length per ray");
+      std::vector<float> out(n);
+      Check(mdh_softshadows(h_.get(), (int32_t)n, Origins.data(), Directions.data(), Min_Dist, Max_Dists.data(), K, out.data()));
+      return out;
+   }
    void Update_Partitioning(Partitioning_Update_Method Method = GPU_Fast) const { Check(mdh_update_partitioning(h_.get(), (int32_t)Method)); } // renderers.adb:757-775
    // ---- headless additions
    std::vector<float> Read_Framebuffer() const // replaces Swap_Buffers: H*W*3 floats, row 0 = top

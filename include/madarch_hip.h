@@ -524,6 +524,38 @@ int32_t mdh_eval_distance_to(mdh_renderer *r, int32_t n, const float *points_xyz
                              const int32_t *kind_ixs, int32_t n_kinds, float *normals_xyz_out,
                              float *dist_out);
 
+/* Ray queries: the shaders' raycast, raycast_visibility and softshadows (glsl/raymarching.glsl:4-56) for n rays of the
+ * host's -- what a ray hits, whether two points see each other, how much of a light reaches a point.  All arrays are host
+ * memory; origins and directions are 3 n floats, and a direction is used as given (not normalised), as in the shaders.
+ * Like mdh_eval_distance_to the calls run on the query stream beside the frames in flight, see pending Set_Primitive /
+ * Add_Primitive / Update_Partitioning, and return when their results are on the host.  They go through the space
+ * partition (or the triangle BVH) where the scene has one, as every pass does.  They edit nothing: the probe-settle run
+ * and the radiance and screen replays go on across them.  n = 0 is MDH_OK.
+ *   MDH_E_INVALID  a null renderer or required array, n < 0, a non-finite origin, direction, tmax, tmin or k, a tmax
+ *                  above the scene's max_dist, tmin < 0 -- checked on the host before anything is launched
+ *   MDH_E_STATE    the scene declares a user-defined primitive or light kind: neither the kernels' interpreter nor the
+ *                  hiprtc build of such scenes answers ray queries (built-in kinds only)
+ * The shaders' marches have no step cap; here a step that no longer moves the ray (total + dist == total in fp32: a far
+ * point along a grazing ray, where the shader would never return) ends the march -- raycast reports a miss, visibility
+ * 1, soft shadows the value reached.
+ *
+ * mdh_raycast: raycast up to the scene's max_dist.  hit 0 / 1; index in the numbering of mdh_read_gbuffer, -1 for a
+ * miss; t the distance marched, 0 for a miss; steps the SDF evaluations, on a miss too; pos = org + dir * t as the march
+ * computed it; normal = primitive_info's normal of primitive `index` at pos; pos and normal 0 for a miss.  Every output
+ * except hit_out may be NULL. */
+int32_t mdh_raycast(mdh_renderer *r, int32_t n, const float *org_xyz, const float *dir_xyz, int32_t *hit_out,
+                    int32_t *index_out, float *t_out, int32_t *steps_out, float *pos_xyz_out, float *normal_xyz_out);
+/* raycast_visibility: 1.0 when ray i reaches tmax[i] (<= max_dist) without a hit, 0.0 otherwise */
+int32_t mdh_raycast_visibility(mdh_renderer *r, int32_t n, const float *org_xyz, const float *dir_xyz, const float *tmax,
+                               float *vis_out);
+/* softshadows with the shader's min_dist (tmin >= 0), max_dist (tmax[i] <= max_dist) and k: 0 behind an occluder, else
+ * the smallest k * d / max (0, t - y) along the ray, at most 1 */
+int32_t mdh_softshadows(mdh_renderer *r, int32_t n, const float *org_xyz, const float *dir_xyz, float tmin, const float *tmax,
+                        float k, float *out);
+/* under MDH_OPT_TIMING: the time of the last ray query's kernel in milliseconds, between two events on the query stream
+ * (without the copies to and from the device); 0 before the first timed query */
+int32_t mdh_ray_query_time(mdh_renderer *r, double *kernel_ms);
+
 /* accumulated HIP-event time and launch count of one pass (MDH_OPT_TIMING) */
 int32_t mdh_pass_time(mdh_renderer *r, int32_t pass, double *total_ms, int64_t *launches);
 /* MDH_OPT_RADIANCE_REPLAY: the radiance passes launched since mdh_create that marched their rays (`plain`), marched them

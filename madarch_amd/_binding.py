@@ -157,6 +157,11 @@ HIP_ONLY_ABI = {
     # OPT_SCREEN_REPLAY: screen passes that marched, recorded, replayed; the bytes of a pixel's record
     "screen_replay_stats": (_I, [_P, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     "screen_record_bytes": (_I, []),
+    # ray queries on the device (raymarching.glsl:4-56): raycast, raycast_visibility, softshadows for n rays of the host's
+    "raycast": (_I, [_P, _I, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "raycast_visibility": (_I, [_P, _I, _P, _P, _P, _P]),
+    "softshadows": (_I, [_P, _I, _P, _P, _F, _P, _F, _P]),
+    "ray_query_time": (_I, [_P, C.POINTER(C.c_double)]),  # OPT_TIMING: the last ray query's kernel, milliseconds
 }
 
 

@@ -337,6 +337,10 @@ struct mdh_renderer {
    hipStream_t query_stream = nullptr; // Eval_Distance_To: beside the frames in flight, not behind them
    hipStream_t vol_stream = nullptr;   // the camera-only volumetric passes of pipelined frames, beside their probe passes
    DevBuf<float> d_query; // Eval_Distance_To: points, normals, distances of the largest batch so far (7 floats a query)
+   DevBuf<float> d_rays;  // the ray queries (mdh_raycast, ..): rays and results of the largest batch so far (MDH_RAY_WORDS words a ray)
+   hipEvent_t rq_e0 = nullptr, rq_e1 = nullptr; // MDH_OPT_TIMING: around a ray query's kernel (taken from free_events once, handed back by mdh_destroy)
+   bool rq_timed = false; // (the query in flight recorded them)
+   double rq_ms = 0.0;    // ... and the time of the last one timed (mdh_ray_query_time)
    // Two sets of probe atlases.  `last` is the set the most recent frame wrote: every read, write and
    // single pass works on it in place.  A pipelined mdh_render (frame overlap, see mdh_render) writes the
    // other set while the previous frame's screen pass still reads this one, then flips.
@@ -1061,6 +1065,8 @@ extern "C" int32_t mdh_destroy(mdh_renderer *r)
    if (r->comm) { ncclComm_t c = r->comm; r->comm = nullptr; (void)rccl_api_destroy(c); }
    peer_drop(r);
    for (auto &p : r->pending) { (void)hipEventDestroy(p.e0); (void)hipEventDestroy(p.e1); }
+   if (r->rq_e0) r->free_events.push_back(r->rq_e0);
+   if (r->rq_e1) r->free_events.push_back(r->rq_e1);
    for (auto e : r->free_events) (void)hipEventDestroy(e);
    // the members release what they own; the streams go last, behind every event that was recorded on one
    const hipStream_t streams[] = {r->query_stream, r->vol_stream, r->copy_stream, r->probe_stream, r->alt_stream, r->own_stream};
@@ -1771,7 +1777,7 @@ template <typename Args> static int jit_launch(hipFunction_t f, int blocks, int 
 // frames in flight share their CUs' instruction caches (measured: the same kernels at other addresses, each as fast by itself,
 // the headline with frames in flight 0.5 % slower).  The kernels of global residency (MDH_PF_GTAB, mdh_device.h: Geo) come
 // last there: behind everything else they move nothing.
-enum { GK_k_visibility, GK_k_scat_march, GK_k_scattering, GK_k_radiance, GK_k_screen, GK_k_partition_build, GK_k_eval_distance, GK_k_diag_segments };
+enum { GK_k_visibility, GK_k_scat_march, GK_k_scattering, GK_k_radiance, GK_k_screen, GK_k_partition_build, GK_k_eval_distance, GK_k_diag_segments, GK_k_ray_query };
 // WHICH KERNEL A PASS RUNS ("One place that picks a pass's kernel"): every template argument of the
 // pass's kernel, computed once by pick_kernel; kernel_name and kernel_ptr turn the same description into the name hiprtc
 // instantiates and into the kernel of this library.
@@ -1782,6 +1788,7 @@ struct PassKernel {
    bool gbuf = false, alt = false; // ... the geometry buffer, the variant of the optional specular bodies
    bool small = false;             // k_radiance: SMALL
    int rec = 0;                    // k_radiance, k_screen: REC (0 marches, 1 marches and records, 2 replays the records: rad_replay_pick, scr_replay_pick)
+   int what = 0;                   // k_ray_query: WHAT (MDH_RQ_*)
    bool ada_div = false;           // k_eval_distance: MDH_OPT_ADA_DIVISION
    bool jit = false; // a function of the scene's hiprtc module (user-defined kinds under MDH_OPT_JIT), not a kernel of this library
    int pfk = 0;      // the variant by the scene's census, before the pass's own choices, and the power-of-two addressing
@@ -1796,7 +1803,7 @@ template <typename... A> static int launch_kernel_ptr(const void *kernel, dim3 g
    return MDH_OK;
 }
 // the kernels outside the passes that stage the scene table (the partition's builder, the distance query), by its residency
-static const void *table_kernel(const mdh_renderer *r, int family)
+static const void *table_kernel(const mdh_renderer *r, int family, int what = 0)
 {
    PassKernel k;
    k.family = family;
@@ -1804,6 +1811,13 @@ static const void *table_kernel(const mdh_renderer *r, int family)
    k.ada_div = r->opt_ada_div != 0;
    // the distance query walks the triangle BVH too -- unless it divides as Madarch.Values."/" does (L + R: no distance, no bound)
    if (family == GK_k_eval_distance && r->bvh_active && !k.ada_div) k.pf |= MDH_PF_BVH;
+   // the ray queries march as the passes do: through the space partition (its border as a variant of its own) or the triangle
+   // BVH where the scene has one -- the general variants, whose bits the census variants share (pick_kernel)
+   if (family == GK_k_ray_query) {
+      k.what = what;
+      if (r->part.enable) k.pf |= MDH_PF_PART | (r->part.border_behavior != 0 ? MDH_PF_FALLBACK : 0);
+      if (r->bvh_active) k.pf |= MDH_PF_BVH;
+   }
    return kernel_ptr(k);
 }
 
@@ -3505,6 +3519,126 @@ extern "C" int32_t mdh_eval_distance_to(mdh_renderer *r, int32_t n, const float 
    return MDH_OK;
 }
 
+// ------------------------------------------------------------------ ray queries
+// raycast, raycast_visibility and softshadows (raymarching.glsl:4-56) for n rays of the host's, on the query stream beside the
+// frames in flight (k_ray_query, mdh_kernels.h).  They read the committed scene and edit nothing: no settle_bump, no counter
+// of the replays' keys moves -- the probe-settle run, the radiance replay and the screen replay go on across them (pending
+// edits are committed first, and have made their own marks).
+#define MDH_RAY_WORDS 17 // origin, direction, tmax | hit, index, t (or the visibility / shadow value), steps, position, normal
+static bool all_finite(const float *v, size_t n)
+{
+   bool ok = true;
+   for (size_t i = 0; i < n; ++i) ok = ok && std::isfinite(v[i]);
+   return ok;
+}
+// the checks all three share, before anything is launched; tmax is null for mdh_raycast
+static int ray_query_check(const mdh_renderer *r, int32_t n, const float *org, const float *dir, const float *tmax)
+{
+   if (!r) return seterr(MDH_E_INVALID, "null renderer");
+   if (!org || !dir || n < 0) return seterr(MDH_E_INVALID, "bad argument");
+   if (has_custom_kinds(r)) return seterr(MDH_E_STATE, "ray queries answer scenes of built-in kinds only");
+   if (!all_finite(org, 3 * (size_t)n) || !all_finite(dir, 3 * (size_t)n)) return seterr(MDH_E_INVALID, "a ray is not finite");
+   if (tmax) {
+      bool ok = true;
+      for (int32_t i = 0; i < n; ++i) ok = ok && std::isfinite(tmax[i]) && tmax[i] <= r->max_dist;
+      if (!ok) return seterr(MDH_E_INVALID, "a ray's length is not finite or exceeds the scene's max_dist");
+   }
+   return MDH_OK;
+}
+// uploads the rays, launches k_ray_query<.., what> and leaves the query stream's results in d_rays (a: their places)
+static int ray_query_run(mdh_renderer *r, int what, int32_t n, const float *org, const float *dir, const float *tmax, float tmin, float k, bool normals, RayQueryArgs &a)
+{
+   HIP_TRY(hipSetDevice(r->device));
+   if (!r->query_stream) HIP_TRY(hipStreamCreateWithFlags(&r->query_stream, hipStreamNonBlocking));
+   hipStream_t qs = r->query_stream;
+   int rc = ensure_committed(r, qs);
+   if (rc != MDH_OK) return rc;
+   const size_t want = ((size_t)n < 256 ? 256 : (size_t)n) * MDH_RAY_WORDS;
+   if (want > r->d_rays.cap) {
+      if (r->d_rays.ptr) HIP_TRY(hipStreamSynchronize(qs));
+      HIP_TRY(r->d_rays.grow(want));
+   }
+   const size_t cap = r->d_rays.cap / MDH_RAY_WORDS;
+   float *base = r->d_rays.ptr;
+   float *d_org = base, *d_dir = base + 3 * cap, *d_tmax = base + 6 * cap;
+   a.n = n; a.tmin = tmin; a.k = k;
+   a.org = d_org; a.dir = d_dir; a.tmax = d_tmax;
+   a.hit = (int *)(base + 7 * cap); a.index = (int *)(base + 8 * cap); a.t = base + 9 * cap; a.steps = (int *)(base + 10 * cap);
+   a.pos = base + 11 * cap; a.normal = normals ? base + 14 * cap : nullptr; // (no normal asked for: the kernel leaves primitive_info out)
+   a.out = a.t;
+   HIP_TRY(hipMemcpyAsync(d_org, org, (size_t)n * 12, hipMemcpyHostToDevice, qs));
+   HIP_TRY(hipMemcpyAsync(d_dir, dir, (size_t)n * 12, hipMemcpyHostToDevice, qs));
+   if (tmax) HIP_TRY(hipMemcpyAsync(d_tmax, tmax, (size_t)n * 4, hipMemcpyHostToDevice, qs));
+   if ((rc = table_acquire(r, qs)) != MDH_OK) return rc;
+   const unsigned blocks = (unsigned)(((size_t)n + MDH_BLOCK - 1) / MDH_BLOCK);
+   const bool timed = r->opt_timing && (r->rq_e0 || (r->rq_e0 = get_event(r))) && (r->rq_e1 || (r->rq_e1 = get_event(r)));
+   if (timed) HIP_TRY(hipEventRecord(r->rq_e0, qs));
+   if ((rc = launch_kernel_ptr(table_kernel(r, GK_k_ray_query, what), dim3(blocks), dim3(MDH_BLOCK), lds_bytes(r), qs, r->ks, a)) != MDH_OK) return rc;
+   HIP_TRY(hipGetLastError());
+   if (timed) HIP_TRY(hipEventRecord(r->rq_e1, qs));
+   r->rq_timed = timed;
+   return table_release(r, qs);
+}
+// the host's wait for a query's results; under MDH_OPT_TIMING the kernel's own time is read off its two events
+static int ray_query_wait(mdh_renderer *r)
+{
+   HIP_TRY(hipStreamSynchronize(r->query_stream));
+   if (r->rq_timed) {
+      float ms = 0.0f;
+      HIP_TRY(hipEventElapsedTime(&ms, r->rq_e0, r->rq_e1));
+      r->rq_ms = ms;
+      r->rq_timed = false;
+   }
+   return MDH_OK;
+}
+extern "C" int32_t mdh_ray_query_time(mdh_renderer *r, double *kernel_ms)
+{
+   if (!r || !kernel_ms) return seterr(MDH_E_INVALID, "bad argument");
+   *kernel_ms = r->rq_ms;
+   return MDH_OK;
+}
+extern "C" int32_t mdh_raycast(mdh_renderer *r, int32_t n, const float *org, const float *dir, int32_t *hit_out, int32_t *index_out,
+                               float *t_out, int32_t *steps_out, float *pos_out, float *normal_out)
+{
+   int rc = ray_query_check(r, n, org, dir, nullptr);
+   if (rc != MDH_OK) return rc;
+   if (!hit_out) return seterr(MDH_E_INVALID, "bad argument");
+   if (n == 0) return MDH_OK;
+   RayQueryArgs a;
+   if ((rc = ray_query_run(r, MDH_RQ_RAYCAST, n, org, dir, nullptr, 0.0f, 0.0f, normal_out != nullptr, a)) != MDH_OK) return rc;
+   hipStream_t qs = r->query_stream;
+   HIP_TRY(hipMemcpyAsync(hit_out, a.hit, (size_t)n * 4, hipMemcpyDeviceToHost, qs));
+   if (index_out) HIP_TRY(hipMemcpyAsync(index_out, a.index, (size_t)n * 4, hipMemcpyDeviceToHost, qs));
+   if (t_out) HIP_TRY(hipMemcpyAsync(t_out, a.t, (size_t)n * 4, hipMemcpyDeviceToHost, qs));
+   if (steps_out) HIP_TRY(hipMemcpyAsync(steps_out, a.steps, (size_t)n * 4, hipMemcpyDeviceToHost, qs));
+   if (pos_out) HIP_TRY(hipMemcpyAsync(pos_out, a.pos, (size_t)n * 12, hipMemcpyDeviceToHost, qs));
+   if (normal_out) HIP_TRY(hipMemcpyAsync(normal_out, a.normal, (size_t)n * 12, hipMemcpyDeviceToHost, qs));
+   return ray_query_wait(r);
+}
+extern "C" int32_t mdh_raycast_visibility(mdh_renderer *r, int32_t n, const float *org, const float *dir, const float *tmax, float *vis_out)
+{
+   if (r && (!tmax || !vis_out)) return seterr(MDH_E_INVALID, "bad argument");
+   int rc = ray_query_check(r, n, org, dir, tmax);
+   if (rc != MDH_OK) return rc;
+   if (n == 0) return MDH_OK;
+   RayQueryArgs a;
+   if ((rc = ray_query_run(r, MDH_RQ_VISIBILITY, n, org, dir, tmax, 0.0f, 0.0f, false, a)) != MDH_OK) return rc;
+   HIP_TRY(hipMemcpyAsync(vis_out, a.out, (size_t)n * 4, hipMemcpyDeviceToHost, r->query_stream));
+   return ray_query_wait(r);
+}
+extern "C" int32_t mdh_softshadows(mdh_renderer *r, int32_t n, const float *org, const float *dir, float tmin, const float *tmax, float k, float *out)
+{
+   if (r && (!tmax || !out)) return seterr(MDH_E_INVALID, "bad argument");
+   if (r && (!std::isfinite(tmin) || !std::isfinite(k) || tmin < 0.0f)) return seterr(MDH_E_INVALID, "min_dist is negative, or min_dist or k is not finite");
+   int rc = ray_query_check(r, n, org, dir, tmax);
+   if (rc != MDH_OK) return rc;
+   if (n == 0) return MDH_OK;
+   RayQueryArgs a;
+   if ((rc = ray_query_run(r, MDH_RQ_SOFTSHADOW, n, org, dir, tmax, tmin, k, false, a)) != MDH_OK) return rc;
+   HIP_TRY(hipMemcpyAsync(out, a.out, (size_t)n * 4, hipMemcpyDeviceToHost, r->query_stream));
+   return ray_query_wait(r);
+}
+
 // the hierarchy of the committed scene (pending edits are committed first): its nodes, leaves, depth and the length of the
 // always-evaluated list; all 0 while MDH_OPT_TRIANGLE_BVH is off or the scene declares no triangles
 extern "C" int32_t mdh_triangle_bvh_info(mdh_renderer *r, int32_t *nodes, int32_t *leaves, int32_t *depth, int32_t *always)
@@ -3764,6 +3898,7 @@ static const void *kernel_ptr(const PassKernel &k)
 #define MDH_SCAT(PF) MDH_K(k_scattering, PF, k_scattering<PF>)
 #endif
 #define MDH_SCR(PF, MODE, ALT) if (k.family == GK_k_screen && k.pf == (PF) && k.mode == MODE && k.alt == ALT && k.rec == 0) return k.gbuf ? (const void *)k_screen<PF, MODE, true, ALT> : (const void *)k_screen<PF, MODE, false, ALT>;
+#define MDH_RQ(PF) if (k.family == GK_k_ray_query && k.pf == (PF)) return k.what == MDH_RQ_RAYCAST ? (const void *)k_ray_query<PF, MDH_RQ_RAYCAST> : k.what == MDH_RQ_VISIBILITY ? (const void *)k_ray_query<PF, MDH_RQ_VISIBILITY> : (const void *)k_ray_query<PF, MDH_RQ_SOFTSHADOW>;
 #define MDH_GTAB(PF) MDH_VIS(PF) MDH_SCAT(PF) MDH_RAD(PF) MDH_SCR(PF, 0, true) MDH_SCR(PF, 0, false) MDH_SCR(PF, 1, false) MDH_SCR(PF, 2, false)
    MDH_RAD(13) MDH_RAD(37) MDH_RAD(5) MDH_RAD(20) MDH_RAD(4) MDH_RAD(16) MDH_RAD(33) MDH_RAD(0) MDH_RAD(1) MDH_RAD(2) MDH_RAD(9) MDH_RAD(3)
    MDH_VIS(0) MDH_VIS(16) MDH_VIS(33) MDH_VIS(1) MDH_VIS(2) MDH_VIS(9) MDH_VIS(3)
@@ -3790,6 +3925,9 @@ static const void *kernel_ptr(const PassKernel &k)
 #if MDH_SCR_REPLAY_BUILT
    MDH_SCR_REC(20) MDH_SCR_REC(16) MDH_SCR_REC(4) MDH_SCR_REC(0)
 #endif
+   // the ray queries (mdh_raycast, ..): the newest last, behind everything older.  The scan, the partition with either border,
+   // global residency alone, with the partition, with the triangle BVH
+   MDH_RQ(0) MDH_RQ(1) MDH_RQ(9) MDH_RQ(64) MDH_RQ(65) MDH_RQ(73) MDH_RQ(192)
    return nullptr;
 #undef MDH_K
 #undef MDH_RAD
@@ -3799,4 +3937,5 @@ static const void *kernel_ptr(const PassKernel &k)
 #undef MDH_SCAT
 #undef MDH_SCR
 #undef MDH_GTAB
+#undef MDH_RQ
 }

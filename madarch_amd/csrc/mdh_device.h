@@ -1373,8 +1373,16 @@ template <int PART> MDH_DEV bool segment_clear(const KScene &sc, f3 A, f3 vd, fl
 }
 
 // ------------------------------------------------------------------------- raymarching
+// THE STALL GUARD (GUARD: the ray queries of mdh_kernels.h, k_ray_query, and nothing else -- the passes march their own rays,
+// which the scenes bound, and keep GUARD = false: the same code as before there was a choice).  The shaders' march loops have no
+// step cap, and a query's ray comes from outside.  A step with fl(total + dist) == total leaves the loop's whole state where it
+// was: dist >= MDH_EPS > 0 here (a smaller one has returned, a NaN makes total NaN and ends the loop at its test), so total is
+// finite and unchanged, the next evaluation is at the same point fl(from + fl(dir * total)) and gives the same dist, and the exit
+// tests -- `total < max`, `dist < MDH_EPS` -- read nothing else (softshadows' res and prev change, neither is tested).  The
+// shader, and the oracle, never return from such a ray: no bit they define is changed by returning.  It takes a far point and a
+// grazing ray: half an ulp of total above MDH_EPS is total >= 2^14.
 // glsl/raymarching.glsl:25-37
-template <int PART> MDH_DEV bool raycast(const KScene &sc, f3 from, f3 dir, int &index, f3 &coll, float &t_out, int &steps)
+template <int PART, bool GUARD = false> MDH_DEV bool raycast(const KScene &sc, f3 from, f3 dir, int &index, f3 &coll, float &t_out, int &steps)
 {
    int n = 0;
    MDH_WORK(0);
@@ -1388,22 +1396,43 @@ template <int PART> MDH_DEV bool raycast(const KScene &sc, f3 from, f3 dir, int 
          steps = n;
          return true;
       }
+      if (GUARD && total + dist == total) break; // stalled: a miss
       total += dist;
    }
    steps = n;
    return false;
 }
 // glsl/raymarching.glsl:39-56: raycast_visibility = 1 - float(hit)
-template <int PART> MDH_DEV float raycast_visibility(const KScene &sc, f3 from, f3 dir, float max_dist)
+template <int PART, bool GUARD = false> MDH_DEV float raycast_visibility(const KScene &sc, f3 from, f3 dir, float max_dist)
 {
    MDH_WORK(0);
    for (float total = 0.0f; total < max_dist;) {
       MDH_WORK(1);
       float dist = sdf<PART>(sc, from + dir * total);
       if (dist < MDH_EPS) return 0.0f;
+      if (GUARD && total + dist == total) break; // stalled: nothing was hit
       total += dist;
    }
    return 1.0f;
+}
+// glsl/raymarching.glsl:4-23, operation for operation the inline loop of shade_structured (mdh_march.h) with the shader's
+// min_dist, max_dist and k as arguments: k * d / 0 = +inf (or NaN for d = 0) leaves res as it is (v_min_f32: minNum)
+template <int PART, bool GUARD = false> MDH_DEV float softshadows(const KScene &sc, f3 from, f3 dir, float min_dist, float max_dist, float k)
+{
+   float res = 1.0f, prev = 1e20f;
+   MDH_WORK(0);
+   for (float total = min_dist; total < max_dist;) {
+      MDH_WORK(1);
+      float dist = sdf<PART>(sc, from + dir * total);
+      if (dist < MDH_EPS) return 0.0f;
+      float y = dist * dist / (2.0f * prev);
+      float d = sqrt_(dist * dist - y * y);
+      res = min_raw(res, k * d / max_(0.0f, total - y));
+      prev = dist;
+      if (GUARD && total + dist == total) break; // stalled: res as it stands
+      total += dist;
+   }
+   return res;
 }
 
 // ------------------------------------------------------------------------------ lights

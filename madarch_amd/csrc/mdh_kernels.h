@@ -1553,6 +1553,55 @@ template <bool ADA_DIV> __global__ __launch_bounds__(64) void k_eval_distance(KS
 template <bool ADA_DIV> __global__ __launch_bounds__(64) void k_eval_distance_gtab(KScene sc, EvalArgs a) { eval_distance<ADA_DIV, true>(sc, a); } // global residency of the scene table
 template <int = 0> __global__ __launch_bounds__(64) void k_eval_distance_bvh(KScene sc, EvalArgs a) { eval_distance<false, true, true>(sc, a); } // ... with the triangle BVH (the Ada division of MDH_OPT_ADA_EVAL_DIV is no distance: such queries scan)
 
+// ------------------------------------------------------------------------ ray queries
+// mdh_raycast, mdh_raycast_visibility, mdh_softshadows (mdh_api.hip): the shaders' raycast, raycast_visibility and softshadows
+// (raymarching.glsl:4-56) for rays that come from the host.  One ray per lane, 64 consecutive rays per wavefront; PART is the
+// scene's variant without its census (the census variants compute the general kernels' bits).  Built-in kinds only.  The
+// marches carry the stall guard (mdh_device.h, above raycast): they end for every finite ray.
+#define MDH_RQ_RAYCAST 0
+#define MDH_RQ_VISIBILITY 1
+#define MDH_RQ_SOFTSHADOW 2
+struct RayQueryArgs {
+   int n;
+   float tmin, k;      // soft shadow: the shader's min_dist and k
+   const float *org;   // 3 n
+   const float *dir;   // 3 n, used as given
+   const float *tmax;  // n (visibility, soft shadow)
+   int *hit, *index, *steps; // raycast: n each; all but hit may be null
+   float *t, *pos, *normal;  // ... n, 3 n, 3 n
+   float *out;               // visibility, soft shadow: n
+};
+template <int PART, int WHAT> __global__ __launch_bounds__(MDH_BLOCK) void k_ray_query(KScene sc, RayQueryArgs a)
+{
+   static_assert(!(PART & (MDH_PF_CUSTOM | MDH_PF_POW2 | MDH_PF_ROOM | MDH_PF_PSMALL)), "ray queries: the general variants of built-in kinds");
+   stage_table(sc); // (the kernel's only barrier: lanes past n leave behind it)
+   const long lin = (long)blockIdx.x * MDH_BLOCK + threadIdx.x;
+   if (lin >= (long)a.n) return;
+   const size_t q = (size_t)lin;
+   const f3 from = F3(a.org[3 * q], a.org[3 * q + 1], a.org[3 * q + 2]);
+   const f3 dir = F3(a.dir[3 * q], a.dir[3 * q + 1], a.dir[3 * q + 2]);
+   if (WHAT == MDH_RQ_VISIBILITY) { a.out[q] = raycast_visibility<PART, true>(sc, from, dir, a.tmax[q]); return; }
+   if (WHAT == MDH_RQ_SOFTSHADOW) { a.out[q] = softshadows<PART, true>(sc, from, dir, a.tmin, a.tmax[q], a.k); return; }
+   int index = -1, steps = 0;
+   float t = 0.0f;
+   f3 P = F3(0.0f, 0.0f, 0.0f), N = F3(0.0f, 0.0f, 0.0f);
+   const bool h = raycast<PART, true>(sc, from, dir, index, P, t, steps);
+   if (h) {
+      int material;
+      if (a.normal) primitive_info<false, (PART & MDH_PF_GTAB) != 0>(sc, index, P, N, material);
+   } else {
+      index = -1; // (the arg-min of the last step is no hit)
+      t = 0.0f;
+      P = F3(0.0f, 0.0f, 0.0f);
+   }
+   a.hit[q] = h ? 1 : 0;
+   if (a.index) a.index[q] = index;
+   if (a.t) a.t[q] = t;
+   if (a.steps) a.steps[q] = steps;
+   if (a.pos) { a.pos[3 * q] = P.x; a.pos[3 * q + 1] = P.y; a.pos[3 * q + 2] = P.z; }
+   if (a.normal) { a.normal[3 * q] = N.x; a.normal[3 * q + 1] = N.y; a.normal[3 * q + 2] = N.z; }
+}
+
 // ---------------------------------------------------------------------- the window's pixels
 // What Swap_Buffers (renderers.adb:320) puts on screen: the screen pass writes float colours and
 // the default framebuffer of the reference's window is RGBA8 without sRGB encoding, so each

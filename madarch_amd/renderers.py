@@ -114,6 +114,53 @@ class Renderer:
                                                _fp(nrm), _fp(dist)))
         return dist, nrm
 
+    # ---- ray queries (raymarching.glsl:4-56), batched on the device beside the frames in flight; they edit nothing
+    @staticmethod
+    def _rays(Origins, Directions, Max_Dists=None):
+        """(n, 3) origins and directions, and a length per ray (a scalar is broadcast): ValueError before any library call"""
+        org = np.ascontiguousarray(Origins, dtype=np.float32)
+        drs = np.ascontiguousarray(Directions, dtype=np.float32)
+        if org.ndim != 2 or org.shape[1] != 3 or drs.shape != org.shape:
+            raise ValueError("origins and directions are (n, 3) arrays of one shape, not %s and %s" % (org.shape, drs.shape))
+        if Max_Dists is None:
+            return org, drs, None
+        tmax = np.asarray(Max_Dists, dtype=np.float32)
+        if tmax.ndim == 0:
+            tmax = np.full(len(org), tmax, dtype=np.float32)
+        if tmax.shape != (len(org),):
+            raise ValueError("one length per ray: %s for %d rays" % (tmax.shape, len(org)))
+        return org, drs, np.ascontiguousarray(tmax)
+
+    def Raycast(self, Origins, Directions):
+        """raycast up to the scene's max_dist: {hit, index, t, steps, position, normal} (index as in Read_Gbuffer, -1 = miss)"""
+        org, drs, _ = self._rays(Origins, Directions)
+        n = len(org)
+        out = {"hit": np.zeros(n, np.int32), "index": np.zeros(n, np.int32), "t": np.zeros(n, np.float32),
+               "steps": np.zeros(n, np.int32), "position": np.zeros((n, 3), np.float32), "normal": np.zeros((n, 3), np.float32)}
+        self._b.check(self._b.raycast(self._h, n, _fp(org), _fp(drs), _fp(out["hit"]), _fp(out["index"]), _fp(out["t"]),
+                                      _fp(out["steps"]), _fp(out["position"]), _fp(out["normal"])))
+        return out
+
+    def Raycast_Visibility(self, Origins, Directions, Max_Dists):
+        """raycast_visibility: 1.0 where the ray reaches its Max_Dists (a scalar is broadcast) without a hit, else 0.0"""
+        org, drs, tmax = self._rays(Origins, Directions, Max_Dists)
+        vis = np.zeros(len(org), np.float32)
+        self._b.check(self._b.raycast_visibility(self._h, len(org), _fp(org), _fp(drs), _fp(tmax), _fp(vis)))
+        return vis
+
+    def Softshadows(self, Origins, Directions, Min_Dist, Max_Dists, K):
+        """softshadows with the shader's min_dist, max_dist (per ray; a scalar is broadcast) and k"""
+        org, drs, tmax = self._rays(Origins, Directions, Max_Dists)
+        out = np.zeros(len(org), np.float32)
+        self._b.check(self._b.softshadows(self._h, len(org), _fp(org), _fp(drs), float(Min_Dist), _fp(tmax), float(K), _fp(out)))
+        return out
+
+    def Ray_Query_Time(self):
+        """OPT_TIMING: the kernel time of the last ray query in milliseconds (HIP events on the query stream)"""
+        ms = C.c_double(0.0)
+        self._b.check(self._b.ray_query_time(self._h, C.byref(ms)))
+        return ms.value
+
     def Render_Pass(self, Pass):
         self._b.check(self._b.render_pass(self._h, int(Pass)))
 
