@@ -1511,6 +1511,53 @@ MDH_DEV void cook_torrance(f3 N, f3 V, f3 L, float NdotL, f3 albedo, float metal
    kD = F3(1.0f - F.x, 1.0f - F.y, 1.0f - F.z) * (1.0f - metallic);
    kS = min3s(sdiv3(numerator, dm), 1.0f);
 }
+// null_light (MDH_SKIP_NULL_BRDF) -- proves, before the BRDF is paid for, that a light adds exactly nothing to Lo in the light
+// loop of compute_direct_lighting (shade_structured, mdh_march.h), which computes
+//    B = sdiv3 (kD * albedo, PI) + kS;  contrib = (B * radiance) * NdotL;  shadows = 0, or softshadows if NdotL > EPS and
+//    contrib != 0 (MDH_SKIP_NULL_RAYS);  Lo = Lo + contrib * shadows.
+// Lo starts as +0 and a sum is -0 only when both terms are, so Lo is never -0 and Lo + (+-0) has Lo's bits (a NaN stays the
+// quiet NaN it is).  contrib * shadows is +-0 when B is finite and either
+//   (1) radiance is +-0 in all three components and NdotL is finite (NdotL <= 2: it is max_ (., 0), never NaN): (B * +-0) * NdotL
+//       = +-0, the loop's `lit` is false, shadows stays 0; or
+//   (2) NdotL > EPS is false and |radiance| <= 1e38 in all three components: |B| < 1.33 (below), so B * radiance does not
+//       overflow, contrib is finite, shadows stays 0 and contrib * 0 = +-0.  (A larger finite radiance can overflow in B * radiance,
+//       and inf * NdotL is NaN for NdotL = 0: such a light is shaded as before.)
+// B is finite under three conditions, all of them comparisons that are false for NaN:
+//   (a) albedo.xyz, metallic and roughness lie in [0, 1];
+//   (b) dot2 (V) <= 1.0015 -- V is the negated ray direction, a rotated unit vector or its reflection about a unit normal;
+//   (c) s = dot2 (V + L) lies in [1e-30, 3e38], so length (V + L) is finite and at least 1e-15, and every component of
+//       H = (V + L) / length (V + L) is finite, at most 1 + 2^-22 in magnitude.  (Without (c), V + L = (1e-23, 0, 0) has s = 0 and
+//       H.x = +inf; without (b) dot (H, V) is unbounded.  Either drives p5 to -inf and B to an infinity or NaN.)
+// cook_torrance then goes as follows, for ANY N and L (NaN and infinities included), in the exact build:
+//   - every dot product goes through max_ (., 0) -- maxNum: NaN becomes 0 -- so NdotV, NdotH and dot (H, V) lie in [0, +inf];
+//   - dot (H, V) <= |H| |V| + rounding < 1.001 by (b) and (c), so 1.001 - max_ (dot (H, V), 0) lies in (0, 1.001] and
+//     p5 in [0, 1.006);  F0 = 0.04 (1 - m) + albedo m lies in [0, 1 + 2^-23] by (a), so F = F0 + (1 - F0) p5 lies in [0, 1.01]
+//     (at F0 = 1 + 2^-23 the second term is above -2^-22);  kD = (1 - F) (1 - metallic) and kD * albedo / PI are finite, at most 0.32;
+//   - kk = (r + 1)^2 / 8 lies in [1/8, 1/2] by (a), so both ggx denominators NdotX (1 - kk) + kk are at least kk > 0 (or NaN or
+//     +inf with NdotX): ggx1 and ggx2 are >= 0 or NaN, G as well.  (Roughness above 2 sqrt 2 - 1 makes 1 - kk negative and
+//     the denominator can change sign: hence the range test.);
+//   - denom = (PI d) d is >= 0, +inf or NaN, a2 >= 0, so NDF is >= 0, +inf or NaN;  numerator = F (NDF G) with F >= 0 is
+//     >= 0, +inf or NaN, never negative;
+//   - dm = max_ (4 NdotV NdotL, 0.001) >= 0.001 or +inf;  numerator / dm is >= 0, +inf or NaN, and min_ (., 1) -- minNum -- puts
+//     kS into [0, 1].  Setting kS to 0 (cfg.direct_specular off) keeps it there.
+// Hence |B| <= 0.32 + 1.  tests/test_null_brdf_claim.py restates all of this in numpy float32 and holds it on random inputs
+// and on a grid of edge values.  The hybrid and fast builds replace the divisions and the normalisation by rcp / rsq forms with
+// other edge behaviour and contract products into fma: the skip is compiled out there.
+#ifndef MDH_SKIP_NULL_BRDF
+#define MDH_SKIP_NULL_BRDF 1
+#endif
+#define MDH_NULL_BRDF (MDH_SKIP_NULL_BRDF && !MDH_FAST_NUMERICS && !MDH_HYBRID_NUMERICS)
+// (& and | on purpose: two dozen compares in a straight line, where && and || make a branch of every one)
+MDH_DEV bool unit_range_(float x) { return (x >= 0.0f) & (x <= 1.0f); }
+MDH_DEV bool null_light(f3 V, f3 L, float NdotL, f3 radiance, const Material &m)
+{
+   const bool mat = unit_range_(m.albedo.x) & unit_range_(m.albedo.y) & unit_range_(m.albedo.z) & unit_range_(m.metallic) & unit_range_(m.roughness);
+   const float s = dot2(V + L); // (cook_torrance's own first operations)
+   const bool brdf_finite = mat & (dot2(V) <= 1.0015f) & (s >= 1e-30f) & (s <= 3e38f);
+   const bool dark = (radiance.x == 0.0f) & (radiance.y == 0.0f) & (radiance.z == 0.0f) & (NdotL <= 2.0f);
+   const bool away = !(NdotL > MDH_EPS) & (__builtin_fabsf(radiance.x) <= 1e38f) & (__builtin_fabsf(radiance.y) <= 1e38f) & (__builtin_fabsf(radiance.z) <= 1e38f);
+   return brdf_finite & (dark | away);
+}
 // glsl/lighting.glsl:42-49
 MDH_DEV f3 compute_indirect_lighting(f3 irradiance, f3 radiance, f3 V, f3 N, f3 L, f3 albedo, float metallic, float roughness)
 {

@@ -470,7 +470,16 @@ MDH_DEV unsigned pixel_record_word2(bool hit, bool traced, int index, int vis_bi
 // REC with SPEC = 1 (the screen pass of the reference's fixed mode, brute-force scan or room census): the same for both
 // shaded points -- 1 parks what a PixelRecord holds, 2 takes `rec` and `rec2` instead of both marches, both arg-min scans,
 // both first steps, every visibility march of both corner loops and the occlusion steps
-template <int PART, int MODE, int SPEC, bool QVIS, int REC = 0>
+// NULLB: null_light in front of the BRDF (MDH_SKIP_NULL_BRDF); false where the caller's kernel has no register to spare for it.
+// The predicate's lane masks live in SGPRs beside the light loop.  Which instantiations leave it out, and shade every light with
+// the code they had before (resource_usage.sh and bench.py, before against after):
+//   every space-partition variant (PART & MDH_PF_PART, decided in shade_structured): they run at 104 - 106 SGPRs; two of them
+//       gained 16 bytes of scratch per lane, and simple_scene, whose point light leaves few wavefronts wholly null, lost 0.5 %;
+//   k_screen <POW2, 0, GBUF>                 brute-force scan, power-of-two atlases, geometry buffer: scratch 32 -> 48 bytes per lane;
+//   k_radiance <0 | POW2, SMALL, REC = 1>    the brute-force scan's recording kernel, small form: 101 SGPRs, 8 -> 7 wavefronts per SIMD.
+constexpr bool null_brdf_screen(int PART, int MODE, bool GBUF, bool ALT, int REC) { return !(GBUF && PART == MDH_PF_POW2 && MODE == 0 && !ALT && REC == 0); }
+constexpr bool null_brdf_radiance(int PART, bool SMALL, int REC) { return !((PART & ~MDH_PF_POW2) == 0 && SMALL && REC == 1); }
+template <int PART, int MODE, int SPEC, bool QVIS, int REC = 0, bool NULLB = true>
 MDH_DEV f3 shade_structured(const KScene &sc, const KProbes &pr, const MachineCfg cfg, bool lane_valid, f3 from, f3 dir_in,
                             PrimaryHit &ph, bool &hit, f3 &pos_out, const RayRecord rec = RayRecord{0u, 0u, -1, 0u},
                             const RayRecord rec2 = RayRecord{0u, 0u, -1, 0u})
@@ -479,6 +488,7 @@ MDH_DEV f3 shade_structured(const KScene &sc, const KProbes &pr, const MachineCf
                  "records are of the radiance pass's rays or of the screen pass's fixed mode without a space partition");
    constexpr bool SREC = REC != 0 && SPEC == 1; // the screen pass's records
    constexpr bool P2 = (PART & MDH_PF_POW2) != 0;
+   constexpr bool NULL_BRDF = MDH_NULL_BRDF != 0 && NULLB && !(PART & MDH_PF_PART); // item 14 of "Exact work elimination": null_light in front of the BRDF
    constexpr bool REFLECT = SPEC != 0 && MODE == 0; // (modes 1 and 2 never shade a second point: no loop, and nothing kept for one)
    // The cage-corner loop unrolled where the registers allow it (the brute-force screen kernel of the reference's fixed mode:
    // 96 VGPRs with and without; the partition variants and the one for the optional specular modes would spill 80 - 200 bytes
@@ -585,10 +595,16 @@ MDH_DEV f3 shade_structured(const KScene &sc, const KProbes &pr, const MachineCf
                   float L_dist;
                   f3 radiance = sample_light<(PART & MDH_PF_CUSTOM) != 0>(sc, li, P, N, L, L_dist);
                   float NdotL = max_(dot(N, L), 0.0f);
-                  f3 kD, kS;
-                  cook_torrance(N, -rd, L, NdotL, m.albedo, m.metallic, m.roughness, kD, kS);
-                  if (ctx == 0 && !cfg.direct_specular) kS = F3(0.0f, 0.0f, 0.0f);
-                  const f3 contrib = ((sdiv3(kD * m.albedo, MDH_PI) + kS) * radiance) * NdotL;
+                  // a light that is dark here (outside a spot's cone) or behind the surface adds exactly nothing whatever the BRDF
+                  // says, as long as the BRDF is finite (null_light, mdh_device.h): no BRDF, no shadow ray, and +0 in contrib's
+                  // place -- Lo + (+0) * 0 has Lo's bits
+                  f3 contrib = F3(0.0f, 0.0f, 0.0f);
+                  if (!(NULL_BRDF && null_light(-rd, L, NdotL, radiance, m))) {
+                     f3 kD, kS;
+                     cook_torrance(N, -rd, L, NdotL, m.albedo, m.metallic, m.roughness, kD, kS);
+                     if (ctx == 0 && !cfg.direct_specular) kS = F3(0.0f, 0.0f, 0.0f);
+                     contrib = ((sdiv3(kD * m.albedo, MDH_PI) + kS) * radiance) * NdotL;
+                  }
                   float shadows = 0.0f;
                   PH_ADD(pt, 2);
                   // a light that contributes exactly nothing here (outside a spot's cone, black BRDF)
