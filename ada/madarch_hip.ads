@@ -141,6 +141,11 @@ package Madarch_HIP is
    --  Opt_Probe_Settle: 1 (default) = a frame's radiance and irradiance passes are not launched once
    --  the probe atlases have stopped changing, the same bits; any edit launches them again; 0 = every frame
    Opt_Probe_Settle : constant int := 23;
+   --  Opt_Ray_Stream_Refill: the device-array ray queries' wavefronts take new rays once this many of
+   --  their 64 lanes are idle (1 .. 64; 64 = lock step; the same bits).  Opt_Ray_Stream_Groups: the
+   --  workgroups such a query may launch, 0 (default) = as many as the device holds at once.
+   Opt_Ray_Stream_Refill : constant int := 24;
+   Opt_Ray_Stream_Groups : constant int := 25;
 
    function Set_Option (R : Handle; Option, Value : int) return Status
      with Import, Convention => C, External_Name => "mdh_set_option";
@@ -178,6 +183,32 @@ package Madarch_HIP is
      (R : Handle; N : int; Org, Dir : System.Address; T_Min : C_float;
       T_Max : System.Address; K : C_float; Shadow_Out : System.Address) return Status
      with Import, Convention => C, External_Name => "mdh_softshadows";
+
+   --  The same three queries for arrays in memory the device addresses, asynchronous and ordered
+   --  with Stream (a hipStream_t; Null_Address = the default stream): the kernel starts behind what
+   --  Stream holds at the call, work given to Stream afterwards sees the answers, and the call does
+   --  not wait.  A ray that is not finite (or whose T_Max exceeds the scene's max_dist) is not
+   --  marched: Raycast answers Hit = -1, the other two NaN.  An array the device cannot address: Status 1.
+   function Raycast_Device
+     (R : Handle; N : int; Org, Dir : System.Address;
+      Hit_Out, Index_Out, T_Out, Steps_Out, Pos_Out, Normal_Out : System.Address;
+      Stream : System.Address) return Status
+     with Import, Convention => C, External_Name => "mdh_raycast_device";
+
+   function Raycast_Visibility_Device
+     (R : Handle; N : int; Org, Dir, T_Max, Vis_Out : System.Address;
+      Stream : System.Address) return Status
+     with Import, Convention => C, External_Name => "mdh_raycast_visibility_device";
+
+   function Softshadows_Device
+     (R : Handle; N : int; Org, Dir : System.Address; T_Min : C_float;
+      T_Max : System.Address; K : C_float; Shadow_Out : System.Address;
+      Stream : System.Address) return Status
+     with Import, Convention => C, External_Name => "mdh_softshadows_device";
+
+   --  blocks until every device query enqueued so far has ended
+   function Ray_Query_Wait (R : Handle) return Status
+     with Import, Convention => C, External_Name => "mdh_ray_query_wait";
 
    --  One frame on the N GPUs of a node, one process per GPU (madarch_hip.h, mdh_comm_*):
    --  every process creates its Renderer on its own device, rank 0 makes a 128-byte id and

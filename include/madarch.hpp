@@ -374,6 +374,23 @@ class Renderer {
       Check(mdh_softshadows(h_.get(), (int32_t)n, Origins.data(), Directions.data(), Min_Dist, Max_Dists.data(), K, out.data()));
       return out;
    }
+   // ... and for arrays in memory the device addresses (N rays; every output of Raycast_Device but Hit may be null): asynchronous,
+   // behind what Stream (a hipStream_t, null = the default stream) holds at the call; work given to Stream afterwards sees the
+   // answers.  A ray that is not finite is not marched: Hit = -1 / NaN.  Ray_Query_Wait: the host's wait for all of them
+   void Raycast_Device(int32_t N, const float *Origins, const float *Directions, int32_t *Hit, int32_t *Index = nullptr, float *T = nullptr, int32_t *Steps = nullptr,
+                       float *Position = nullptr, float *Normal = nullptr, void *Stream = nullptr) const
+   {
+      Check(mdh_raycast_device(h_.get(), N, Origins, Directions, Hit, Index, T, Steps, Position, Normal, Stream));
+   }
+   void Raycast_Visibility_Device(int32_t N, const float *Origins, const float *Directions, const float *Max_Dists, float *Visibility, void *Stream = nullptr) const
+   {
+      Check(mdh_raycast_visibility_device(h_.get(), N, Origins, Directions, Max_Dists, Visibility, Stream));
+   }
+   void Softshadows_Device(int32_t N, const float *Origins, const float *Directions, Single Min_Dist, const float *Max_Dists, Single K, float *Out, void *Stream = nullptr) const
+   {
+      Check(mdh_softshadows_device(h_.get(), N, Origins, Directions, Min_Dist, Max_Dists, K, Out, Stream));
+   }
+   void Ray_Query_Wait() const { Check(mdh_ray_query_wait(h_.get())); }
    void Update_Partitioning(Partitioning_Update_Method Method = GPU_Fast) const { Check(mdh_update_partitioning(h_.get(), (int32_t)Method)); } // renderers.adb:757-775
    // ---- headless additions
    std::vector<float> Read_Framebuffer() const // replaces Swap_Buffers: H*W*3 floats, row 0 = top
@@ -393,6 +410,8 @@ class Renderer {
    }
    void Set_Option(int32_t Option, int32_t Value) const { Check(mdh_set_option(h_.get(), Option, Value)); }
    static constexpr int32_t Opt_Probe_Settle = MDH_OPT_PROBE_SETTLE; // Set_Option (.., 0): probe passes launched in every frame (default 1: left out once the atlases have stopped changing, the same bits; any edit launches them again)
+   static constexpr int32_t Opt_Ray_Stream_Refill = MDH_OPT_RAY_STREAM_REFILL; // Set_Option (.., 1 .. 64): the idle lanes at which a device-array ray query's wavefront takes new rays (64: lock step; the same bits)
+   static constexpr int32_t Opt_Ray_Stream_Groups = MDH_OPT_RAY_STREAM_GROUPS; // Set_Option (.., k): at most k workgroups for such a query (0, default: as many as the device holds at once)
    static constexpr int32_t Opt_Screen_Replay = MDH_OPT_SCREEN_REPLAY; // Set_Option (.., 1): the screen pass's marches replayed while camera and geometry stand still, the same bits (default 0)
    static constexpr int32_t Opt_Radiance_Replay = MDH_OPT_RADIANCE_REPLAY; // Set_Option (.., 0): probe rays marched in every pass (default 1: replayed while the geometry stands still, the same bits)
    static constexpr int32_t Opt_Triangle_BVH = MDH_OPT_TRIANGLE_BVH; // Set_Option (.., 1): triangles walked through a BVH, the same bits (scenes without partition or user-defined kinds)

@@ -320,7 +320,17 @@ enum {
     * a peer exchange or MDH_OPT_WORLD > 1 launches every pass.  With MDH_OPT_TIMING a settled pass is still counted; its
     * time is the few microseconds between its two events.  0 forgets the run.  mdh_probe_settle_stats counts (DESIGN.md
     * section 4, "Exact work elimination", item 13). */
-   MDH_OPT_PROBE_SETTLE = 23
+   MDH_OPT_PROBE_SETTLE = 23,
+   /* the device-array ray queries (mdh_raycast_device, ..): a wavefront takes new rays from the launch's counter when at
+    * least this many of its 64 lanes are idle (or none is busy).  1 .. 64, anything else MDH_E_INVALID; 64 = lock step, rounds of
+    * 64 consecutive rays, the schedule of the host-array queries.  Whatever the value, every ray has the same bits.  The
+    * default is the measured one ("Ray queries").  No pass reads it: setting it ends no replay and
+    * no settle run. */
+   MDH_OPT_RAY_STREAM_REFILL = 24,
+   /* ... and the workgroups of 256 threads such a query may launch: 0 (default) = as many as the device holds at once (or
+    * fewer, for a small batch), k > 0 = at most k -- room for the frames in flight beside a large batch.  Any number
+    * serves every ray.  Negative: MDH_E_INVALID.  No pass reads it either. */
+   MDH_OPT_RAY_STREAM_GROUPS = 25
 };
 
 /* passes of Renderers.Render (madarch-renderers.adb:302-321) */
@@ -555,6 +565,34 @@ int32_t mdh_softshadows(mdh_renderer *r, int32_t n, const float *org_xyz, const 
 /* under MDH_OPT_TIMING: the time of the last ray query's kernel in milliseconds, between two events on the query stream
  * (without the copies to and from the device); 0 before the first timed query */
 int32_t mdh_ray_query_time(mdh_renderer *r, double *kernel_ms);
+
+/* The same three queries for rays that live on the device: every array is memory the renderer's device can address
+ * (its own memory, page-locked host memory, managed memory), with the meaning, the layout and the optional outputs of
+ * the calls above.  `stream` is a hipStream_t (NULL: the default stream, which is PyTorch's).  The calls are asynchronous
+ * and ordered with that stream: the kernel starts after everything enqueued on `stream` before the call, whatever is
+ * enqueued on `stream` after the call sees the answers, and the call returns without waiting for the device.  The arrays
+ * stay the caller's and must live until the query has ended.  The scene is the one committed at the call, pending edits
+ * included; the calls edit nothing, as above.  n = 0 is MDH_OK without a launch.
+ *   MDH_E_INVALID  a null renderer or required array, n < 0, tmin < 0, a non-finite tmin or k, and an array that is not
+ *                  memory the device addresses (hipPointerGetAttributes: pageable host memory, another device's) or
+ *                  that ends outside its allocation -- checked before anything is launched; HIP's error state is cleared
+ *   MDH_E_STATE    a scene with a user-defined kind
+ * The host cannot look at the rays, so the device does: a ray with a non-finite component, or with a tmax that is not
+ * finite or exceeds the scene's max_dist -- what the calls above refuse the whole batch for -- is not marched.
+ * mdh_raycast_device answers it with hit = -1, index = -1, t = 0, steps = 0, pos = normal = 0; the other two with the
+ * quiet NaN 0x7fc00000.  Every other ray has the bits the calls above give it, whatever MDH_OPT_RAY_STREAM_REFILL and
+ * MDH_OPT_RAY_STREAM_GROUPS say: lanes take the next ray from a counter when their own has ended (k_ray_stream). */
+int32_t mdh_raycast_device(mdh_renderer *r, int32_t n, const float *org_xyz, const float *dir_xyz, int32_t *hit_out,
+                           int32_t *index_out, float *t_out, int32_t *steps_out, float *pos_xyz_out, float *normal_xyz_out,
+                           void *stream);
+int32_t mdh_raycast_visibility_device(mdh_renderer *r, int32_t n, const float *org_xyz, const float *dir_xyz,
+                                      const float *tmax, float *vis_out, void *stream);
+int32_t mdh_softshadows_device(mdh_renderer *r, int32_t n, const float *org_xyz, const float *dir_xyz, float tmin,
+                               const float *tmax, float k, float *out, void *stream);
+/* blocks until every device query enqueued so far has ended (for callers that read the answers from the host; work on
+ * the query's own stream needs no wait).  Under MDH_OPT_TIMING mdh_ray_query_time then reads the last one's kernel; called
+ * by itself it waits for that query's end event first. */
+int32_t mdh_ray_query_wait(mdh_renderer *r);
 
 /* accumulated HIP-event time and launch count of one pass (MDH_OPT_TIMING) */
 int32_t mdh_pass_time(mdh_renderer *r, int32_t pass, double *total_ms, int64_t *launches);

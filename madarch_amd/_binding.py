@@ -27,6 +27,8 @@ OPT_TRIANGLE_BVH = 20  # 1: the triangles are walked through a bounding-volume h
 OPT_RADIANCE_REPLAY = 21  # 1 (default): probe rays' hits and cage visibility are replayed while the geometry stands still (the same bits; HIP library only)
 OPT_PROBE_SETTLE = 23  # 1 (default): a frame's probe passes are not launched once the atlases have stopped changing (the same bits; any edit launches them again; HIP library only)
 OPT_SCREEN_REPLAY = 22  # 1: the screen pass's hits and cage visibility are replayed while camera and geometry stand still (the same bits; HIP library only; default 0)
+OPT_RAY_STREAM_REFILL = 24  # the device-array ray queries: a wavefront takes new rays once this many of its 64 lanes are idle (1 .. 64; 64 = lock step; the same bits; HIP library only)
+OPT_RAY_STREAM_GROUPS = 25  # ... and the workgroups such a query may launch (0, default: as many as the device holds at once)
 
 PASS_RADIANCE, PASS_IRRADIANCE, PASS_VISIBILITY, PASS_SCATTERING, PASS_SCREEN, PASS_EXCHANGE = range(6)
 PASS_NAMES = ("radiance", "irradiance", "visibility", "scattering", "screen", "exchange")
@@ -162,6 +164,11 @@ HIP_ONLY_ABI = {
     "raycast_visibility": (_I, [_P, _I, _P, _P, _P, _P]),
     "softshadows": (_I, [_P, _I, _P, _P, _F, _P, _F, _P]),
     "ray_query_time": (_I, [_P, C.POINTER(C.c_double)]),  # OPT_TIMING: the last ray query's kernel, milliseconds
+    # ... for arrays on the device, asynchronous and ordered with the stream given last (0: the default stream)
+    "raycast_device": (_I, [_P, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "raycast_visibility_device": (_I, [_P, _I, _P, _P, _P, _P, _P]),
+    "softshadows_device": (_I, [_P, _I, _P, _P, _F, _P, _F, _P, _P]),
+    "ray_query_wait": (_I, [_P]),  # blocks until every device query enqueued so far has ended
 }
 
 

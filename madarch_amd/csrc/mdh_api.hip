@@ -341,6 +341,12 @@ struct mdh_renderer {
    hipEvent_t rq_e0 = nullptr, rq_e1 = nullptr; // MDH_OPT_TIMING: around a ray query's kernel (taken from free_events once, handed back by mdh_destroy)
    bool rq_timed = false; // (the query in flight recorded them)
    double rq_ms = 0.0;    // ... and the time of the last one timed (mdh_ray_query_time)
+   // the device-array ray queries (mdh_raycast_device, ..): the counter k_ray_stream's wavefronts take their rays from (one:
+   // the launches follow one another on the query stream), and the two events between the caller's stream and the query stream
+   DevBuf<unsigned> d_rq_next;
+   Event ev_rq_in, ev_rq_out;
+   int opt_rq_refill = MDH_RAY_STREAM_REFILL_DEFAULT; // MDH_OPT_RAY_STREAM_REFILL
+   int opt_rq_groups = 0;                             // MDH_OPT_RAY_STREAM_GROUPS (0: as many workgroups as are resident)
    // Two sets of probe atlases.  `last` is the set the most recent frame wrote: every read, write and
    // single pass works on it in place.  A pipelined mdh_render (frame overlap, see mdh_render) writes the
    // other set while the previous frame's screen pass still reads this one, then flips.
@@ -1198,6 +1204,7 @@ extern "C" int32_t mdh_set_option(mdh_renderer *r, int32_t option, int32_t value
    switch (option) { // (the options no probe pass reads: everything else, known or not, counts as an edit)
    case MDH_OPT_TIMING: case MDH_OPT_SCREEN_ORDER: case MDH_OPT_SCREEN_SPLIT: case MDH_OPT_SCREEN_REPLAY: case MDH_OPT_GBUFFER:
    case MDH_OPT_WINDOW: case MDH_OPT_AO_STEPS: case MDH_OPT_INDIRECT_SPECULAR: case MDH_OPT_PROBE_SETTLE: break;
+   case MDH_OPT_RAY_STREAM_REFILL: case MDH_OPT_RAY_STREAM_GROUPS: break; // (the device-array ray queries' schedule: no pass reads it)
    default: settle_bump(r);
    }
    // what an open frame has latched (its atlas set, slice, streams and screen mode) cannot change under it
@@ -1298,6 +1305,11 @@ extern "C" int32_t mdh_set_option(mdh_renderer *r, int32_t option, int32_t value
       }
       break;
    case MDH_OPT_PROBE_SETTLE: r->opt_settle = value ? 1 : 0; r->settle.set_enabled(r->opt_settle != 0); break; // (0 forgets the run)
+   case MDH_OPT_RAY_STREAM_REFILL:
+      if (value < MDH_RS_REFILL_MIN || value > MDH_RS_REFILL_MAX) return seterr(MDH_E_INVALID, "MDH_OPT_RAY_STREAM_REFILL: 1 .. 64 idle lanes");
+      r->opt_rq_refill = value;
+      break;
+   case MDH_OPT_RAY_STREAM_GROUPS: if (value < 0) return seterr(MDH_E_INVALID, "MDH_OPT_RAY_STREAM_GROUPS: a number of workgroups, 0 = as many as are resident"); r->opt_rq_groups = value; break;
    default: return seterr(MDH_E_INVALID, "unknown option");
    }
    return MDH_OK;
@@ -1329,6 +1341,8 @@ extern "C" int32_t mdh_get_option(mdh_renderer *r, int32_t option, int32_t *valu
    case MDH_OPT_RADIANCE_MIPS: *value = r->opt_mips; break;
    case MDH_OPT_TRIANGLE_BVH: *value = r->opt_tri_bvh; break;
    case MDH_OPT_PROBE_SETTLE: *value = r->opt_settle; break;
+   case MDH_OPT_RAY_STREAM_REFILL: *value = r->opt_rq_refill; break;
+   case MDH_OPT_RAY_STREAM_GROUPS: *value = r->opt_rq_groups; break;
    case MDH_OPT_TABLE_RESIDENCY: { // of the committed scene: edits since the last commit are committed first
       if (r->table_dirty && !r->in_frame) {
          HIP_TRY(hipSetDevice(r->device));
@@ -1777,7 +1791,7 @@ template <typename Args> static int jit_launch(hipFunction_t f, int blocks, int 
 // frames in flight share their CUs' instruction caches (measured: the same kernels at other addresses, each as fast by itself,
 // the headline with frames in flight 0.5 % slower).  The kernels of global residency (MDH_PF_GTAB, mdh_device.h: Geo) come
 // last there: behind everything else they move nothing.
-enum { GK_k_visibility, GK_k_scat_march, GK_k_scattering, GK_k_radiance, GK_k_screen, GK_k_partition_build, GK_k_eval_distance, GK_k_diag_segments, GK_k_ray_query };
+enum { GK_k_visibility, GK_k_scat_march, GK_k_scattering, GK_k_radiance, GK_k_screen, GK_k_partition_build, GK_k_eval_distance, GK_k_diag_segments, GK_k_ray_query, GK_k_ray_stream };
 // WHICH KERNEL A PASS RUNS ("One place that picks a pass's kernel"): every template argument of the
 // pass's kernel, computed once by pick_kernel; kernel_name and kernel_ptr turn the same description into the name hiprtc
 // instantiates and into the kernel of this library.
@@ -1788,7 +1802,7 @@ struct PassKernel {
    bool gbuf = false, alt = false; // ... the geometry buffer, the variant of the optional specular bodies
    bool small = false;             // k_radiance: SMALL
    int rec = 0;                    // k_radiance, k_screen: REC (0 marches, 1 marches and records, 2 replays the records: rad_replay_pick, scr_replay_pick)
-   int what = 0;                   // k_ray_query: WHAT (MDH_RQ_*)
+   int what = 0;                   // k_ray_query, k_ray_stream: WHAT (MDH_RQ_*)
    bool ada_div = false;           // k_eval_distance: MDH_OPT_ADA_DIVISION
    bool jit = false; // a function of the scene's hiprtc module (user-defined kinds under MDH_OPT_JIT), not a kernel of this library
    int pfk = 0;      // the variant by the scene's census, before the pass's own choices, and the power-of-two addressing
@@ -1813,7 +1827,7 @@ static const void *table_kernel(const mdh_renderer *r, int family, int what = 0)
    if (family == GK_k_eval_distance && r->bvh_active && !k.ada_div) k.pf |= MDH_PF_BVH;
    // the ray queries march as the passes do: through the space partition (its border as a variant of its own) or the triangle
    // BVH where the scene has one -- the general variants, whose bits the census variants share (pick_kernel)
-   if (family == GK_k_ray_query) {
+   if (family == GK_k_ray_query || family == GK_k_ray_stream) {
       k.what = what;
       if (r->part.enable) k.pf |= MDH_PF_PART | (r->part.border_behavior != 0 ? MDH_PF_FALLBACK : 0);
       if (r->bvh_active) k.pf |= MDH_PF_BVH;
@@ -3528,7 +3542,7 @@ extern "C" int32_t mdh_eval_distance_to(mdh_renderer *r, int32_t n, const float 
 static bool all_finite(const float *v, size_t n)
 {
    bool ok = true;
-   for (size_t i = 0; i < n; ++i) ok = ok && std::isfinite(v[i]);
+   for (size_t i = 0; i < n; ++i) ok = ok && rs_finite(v[i]); // (mdh_ray_stream.h: the predicate the device-array queries apply per lane)
    return ok;
 }
 // the checks all three share, before anything is launched; tmax is null for mdh_raycast
@@ -3540,7 +3554,7 @@ static int ray_query_check(const mdh_renderer *r, int32_t n, const float *org, c
    if (!all_finite(org, 3 * (size_t)n) || !all_finite(dir, 3 * (size_t)n)) return seterr(MDH_E_INVALID, "a ray is not finite");
    if (tmax) {
       bool ok = true;
-      for (int32_t i = 0; i < n; ++i) ok = ok && std::isfinite(tmax[i]) && tmax[i] <= r->max_dist;
+      for (int32_t i = 0; i < n; ++i) ok = ok && rs_tmax_valid(tmax[i], r->max_dist);
       if (!ok) return seterr(MDH_E_INVALID, "a ray's length is not finite or exceeds the scene's max_dist");
    }
    return MDH_OK;
@@ -3594,6 +3608,14 @@ static int ray_query_wait(mdh_renderer *r)
 extern "C" int32_t mdh_ray_query_time(mdh_renderer *r, double *kernel_ms)
 {
    if (!r || !kernel_ms) return seterr(MDH_E_INVALID, "bad argument");
+   if (r->rq_timed) { // a device query nobody has waited for yet: for its end event, not for the stream
+      float ms = 0.0f;
+      HIP_TRY(hipSetDevice(r->device));
+      HIP_TRY(hipEventSynchronize(r->rq_e1));
+      HIP_TRY(hipEventElapsedTime(&ms, r->rq_e0, r->rq_e1));
+      r->rq_ms = ms;
+      r->rq_timed = false;
+   }
    *kernel_ms = r->rq_ms;
    return MDH_OK;
 }
@@ -3636,6 +3658,151 @@ extern "C" int32_t mdh_softshadows(mdh_renderer *r, int32_t n, const float *org,
    RayQueryArgs a;
    if ((rc = ray_query_run(r, MDH_RQ_SOFTSHADOW, n, org, dir, tmax, tmin, k, false, a)) != MDH_OK) return rc;
    HIP_TRY(hipMemcpyAsync(out, a.out, (size_t)n * 4, hipMemcpyDeviceToHost, r->query_stream));
+   return ray_query_wait(r);
+}
+
+// ------------------------------------------------------------------ ray queries on device arrays
+// mdh_raycast_device, mdh_raycast_visibility_device, mdh_softshadows_device: the same three queries for arrays the device
+// addresses, asynchronous and ordered with a stream of the caller's.  The kernel (k_ray_stream, mdh_kernels.h) still runs
+// on the query stream, so that the scene's commit and the table's fences are used as they are; two events bridge: the query
+// stream waits for what the caller's stream holds at the call, the caller's stream waits for the kernel.  Nothing is
+// copied and the host waits for nothing.  The rays are validated by the lanes that take them; what the host can check --
+// and must, a pointer the device cannot address is a fault inside the kernel -- is where the arrays live.
+struct RayArray { const void *p; size_t bytes; const char *what; };
+// is [p, p + bytes) memory this renderer's device addresses?  Memory of the device itself, page-locked host memory or
+// managed memory, as hipPointerGetAttributes knows it; pageable host memory is unregistered (or, to older runtimes, an
+// invalid value: the sticky error is cleared).  Where the runtime names the allocation's range, the array has to end inside it.
+static int ray_array_check(const mdh_renderer *r, const RayArray &a)
+{
+   if (!a.p) return MDH_OK; // (an optional output that was not asked for; required ones were looked at before)
+   hipPointerAttribute_t at;
+   memset(&at, 0, sizeof at);
+   const hipError_t e = hipPointerGetAttributes(&at, a.p);
+   if (e != hipSuccess) {
+      (void)hipGetLastError();
+      snprintf(g_err, sizeof g_err, "%s: not memory the device can address (%s)", a.what, hipGetErrorString(e));
+      return MDH_E_INVALID;
+   }
+   const bool ok = (at.type == hipMemoryTypeDevice && at.device == r->device) || at.type == hipMemoryTypeHost || at.type == hipMemoryTypeManaged;
+   if (!ok) {
+      snprintf(g_err, sizeof g_err, "%s: not memory the device can address (%s)", a.what, at.type == hipMemoryTypeDevice ? "another device's" : "pageable host memory");
+      return MDH_E_INVALID;
+   }
+   if (at.type == hipMemoryTypeDevice) {
+      hipDeviceptr_t base = nullptr;
+      size_t size = 0;
+      if (hipMemGetAddressRange(&base, &size, (hipDeviceptr_t)a.p) != hipSuccess) (void)hipGetLastError(); // (no range known: the caller's word)
+      else if ((const char *)a.p < (const char *)base || (size_t)((const char *)a.p - (const char *)base) + a.bytes > size) {
+         snprintf(g_err, sizeof g_err, "%s: %zu bytes from this address end outside its allocation", a.what, a.bytes);
+         return MDH_E_INVALID;
+      }
+   }
+   return MDH_OK;
+}
+// the workgroups of `kernel` with `lds` bytes of dynamic LDS the device holds at once (0: the runtime does not say)
+static long resident_groups(mdh_renderer *r, const void *kernel, size_t lds)
+{
+   auto it = r->resident.find({kernel, lds});
+   if (it == r->resident.end()) {
+      int per_cu = 0;
+      if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, MDH_BLOCK, lds) != hipSuccess) { (void)hipGetLastError(); per_cu = 0; }
+      it = r->resident.insert({{kernel, lds}, per_cu}).first;
+   }
+   return (long)it->second * r->n_cus;
+}
+// checks everything, then enqueues k_ray_stream<.., what> between the two events; `arrays`: every array of the call
+static int ray_stream_run(mdh_renderer *r, int what, int32_t n, const RayArray *arrays, int n_arrays, RayQueryArgs &a, hipStream_t stream)
+{
+   if (has_custom_kinds(r)) return seterr(MDH_E_STATE, "ray queries answer scenes of built-in kinds only");
+   HIP_TRY(hipSetDevice(r->device));
+   for (int i = 0; i < n_arrays; ++i) {
+      const int rc = ray_array_check(r, arrays[i]);
+      if (rc != MDH_OK) return rc;
+   }
+   if (n == 0) return MDH_OK;
+   if (!r->query_stream) HIP_TRY(hipStreamCreateWithFlags(&r->query_stream, hipStreamNonBlocking));
+   hipStream_t qs = r->query_stream;
+   HIP_TRY(create_all(r->d_rq_next.sized(1), r->ev_rq_in, r->ev_rq_out)); // (one group, created by the first device query)
+   int rc = ensure_committed(r, qs);
+   if (rc != MDH_OK) return rc;
+   const void *kernel = table_kernel(r, GK_k_ray_stream, what);
+   const size_t lds = lds_bytes(r);
+   long groups = ((long)n + MDH_BLOCK - 1) / MDH_BLOCK;
+   if (kernel) { // (none: launch_kernel_ptr says so)
+      const long resident = resident_groups(r, kernel, lds);
+      if (resident > 0 && groups > resident) groups = resident;
+   }
+   if (r->opt_rq_groups > 0 && groups > r->opt_rq_groups) groups = r->opt_rq_groups;
+   RayStreamArgs sa;
+   sa.q = a;
+   sa.next = r->d_rq_next.ptr;
+   sa.refill = r->opt_rq_refill;
+   if (stream != qs) { // the rays are what the caller's stream has made of them at this call
+      HIP_TRY(hipEventRecord(r->ev_rq_in.ev, stream));
+      HIP_TRY(hipStreamWaitEvent(qs, r->ev_rq_in.ev, 0));
+   }
+   HIP_TRY(hipMemsetAsync(r->d_rq_next.ptr, 0, sizeof(unsigned), qs));
+   if ((rc = table_acquire(r, qs)) != MDH_OK) return rc;
+   const bool timed = r->opt_timing && (r->rq_e0 || (r->rq_e0 = get_event(r))) && (r->rq_e1 || (r->rq_e1 = get_event(r)));
+   if (timed) HIP_TRY(hipEventRecord(r->rq_e0, qs));
+   if ((rc = launch_kernel_ptr(kernel, dim3((unsigned)groups), dim3(MDH_BLOCK), lds, qs, r->ks, sa)) != MDH_OK) return rc;
+   HIP_TRY(hipGetLastError());
+   if (timed) HIP_TRY(hipEventRecord(r->rq_e1, qs));
+   r->rq_timed = timed; // (pending: mdh_ray_query_wait or mdh_ray_query_time reads the pair)
+   if ((rc = table_release(r, qs)) != MDH_OK) return rc;
+   if (stream != qs) { // ... and the answers are there for whatever the caller's stream is given next
+      HIP_TRY(hipEventRecord(r->ev_rq_out.ev, qs));
+      HIP_TRY(hipStreamWaitEvent(stream, r->ev_rq_out.ev, 0));
+   }
+   return MDH_OK;
+}
+extern "C" int32_t mdh_raycast_device(mdh_renderer *r, int32_t n, const float *org, const float *dir, int32_t *hit_out, int32_t *index_out,
+                                      float *t_out, int32_t *steps_out, float *pos_out, float *normal_out, void *stream)
+{
+   if (!r) return seterr(MDH_E_INVALID, "null renderer");
+   if (!org || !dir || !hit_out || n < 0) return seterr(MDH_E_INVALID, "bad argument");
+   const size_t w = (size_t)n * 4;
+   const RayArray arrays[] = {{org, 3 * w, "origins"}, {dir, 3 * w, "directions"}, {hit_out, w, "hit"}, {index_out, w, "index"}, {t_out, w, "t"},
+                              {steps_out, w, "steps"}, {pos_out, 3 * w, "positions"}, {normal_out, 3 * w, "normals"}};
+   RayQueryArgs a;
+   a.n = n; a.tmin = 0.0f; a.k = 0.0f;
+   a.org = org; a.dir = dir; a.tmax = nullptr;
+   a.hit = hit_out; a.index = index_out; a.steps = steps_out;
+   a.t = t_out; a.pos = pos_out; a.normal = normal_out;
+   a.out = nullptr;
+   return ray_stream_run(r, MDH_RQ_RAYCAST, n, arrays, 8, a, (hipStream_t)stream);
+}
+static int32_t ray_stream_scalar(mdh_renderer *r, int what, int32_t n, const float *org, const float *dir, float tmin, const float *tmax, float k, float *out, void *stream)
+{
+   const size_t w = (size_t)n * 4;
+   const RayArray arrays[] = {{org, 3 * w, "origins"}, {dir, 3 * w, "directions"}, {tmax, w, "tmax"}, {out, w, "results"}};
+   RayQueryArgs a;
+   a.n = n; a.tmin = tmin; a.k = k;
+   a.org = org; a.dir = dir; a.tmax = tmax;
+   a.hit = a.index = a.steps = nullptr;
+   a.t = a.pos = a.normal = nullptr;
+   a.out = out;
+   return ray_stream_run(r, what, n, arrays, 4, a, (hipStream_t)stream);
+}
+extern "C" int32_t mdh_raycast_visibility_device(mdh_renderer *r, int32_t n, const float *org, const float *dir, const float *tmax, float *vis_out, void *stream)
+{
+   if (!r) return seterr(MDH_E_INVALID, "null renderer");
+   if (!org || !dir || !tmax || !vis_out || n < 0) return seterr(MDH_E_INVALID, "bad argument");
+   return ray_stream_scalar(r, MDH_RQ_VISIBILITY, n, org, dir, 0.0f, tmax, 0.0f, vis_out, stream);
+}
+extern "C" int32_t mdh_softshadows_device(mdh_renderer *r, int32_t n, const float *org, const float *dir, float tmin, const float *tmax, float k, float *out, void *stream)
+{
+   if (!r) return seterr(MDH_E_INVALID, "null renderer");
+   if (!org || !dir || !tmax || !out || n < 0) return seterr(MDH_E_INVALID, "bad argument");
+   if (!std::isfinite(tmin) || !std::isfinite(k) || tmin < 0.0f) return seterr(MDH_E_INVALID, "min_dist is negative, or min_dist or k is not finite");
+   return ray_stream_scalar(r, MDH_RQ_SOFTSHADOW, n, org, dir, tmin, tmax, k, out, stream);
+}
+// the host's wait for every device query enqueued so far (callers that order their own stream need none)
+extern "C" int32_t mdh_ray_query_wait(mdh_renderer *r)
+{
+   if (!r) return seterr(MDH_E_INVALID, "null renderer");
+   if (!r->query_stream) return MDH_OK; // (no query yet)
+   HIP_TRY(hipSetDevice(r->device));
    return ray_query_wait(r);
 }
 
@@ -3899,6 +4066,7 @@ static const void *kernel_ptr(const PassKernel &k)
 #endif
 #define MDH_SCR(PF, MODE, ALT) if (k.family == GK_k_screen && k.pf == (PF) && k.mode == MODE && k.alt == ALT && k.rec == 0) return k.gbuf ? (const void *)k_screen<PF, MODE, true, ALT> : (const void *)k_screen<PF, MODE, false, ALT>;
 #define MDH_RQ(PF) if (k.family == GK_k_ray_query && k.pf == (PF)) return k.what == MDH_RQ_RAYCAST ? (const void *)k_ray_query<PF, MDH_RQ_RAYCAST> : k.what == MDH_RQ_VISIBILITY ? (const void *)k_ray_query<PF, MDH_RQ_VISIBILITY> : (const void *)k_ray_query<PF, MDH_RQ_SOFTSHADOW>;
+#define MDH_RS(PF) if (k.family == GK_k_ray_stream && k.pf == (PF)) return k.what == MDH_RQ_RAYCAST ? (const void *)k_ray_stream<PF, MDH_RQ_RAYCAST> : k.what == MDH_RQ_VISIBILITY ? (const void *)k_ray_stream<PF, MDH_RQ_VISIBILITY> : (const void *)k_ray_stream<PF, MDH_RQ_SOFTSHADOW>;
 #define MDH_GTAB(PF) MDH_VIS(PF) MDH_SCAT(PF) MDH_RAD(PF) MDH_SCR(PF, 0, true) MDH_SCR(PF, 0, false) MDH_SCR(PF, 1, false) MDH_SCR(PF, 2, false)
    MDH_RAD(13) MDH_RAD(37) MDH_RAD(5) MDH_RAD(20) MDH_RAD(4) MDH_RAD(16) MDH_RAD(33) MDH_RAD(0) MDH_RAD(1) MDH_RAD(2) MDH_RAD(9) MDH_RAD(3)
    MDH_VIS(0) MDH_VIS(16) MDH_VIS(33) MDH_VIS(1) MDH_VIS(2) MDH_VIS(9) MDH_VIS(3)
@@ -3928,6 +4096,8 @@ static const void *kernel_ptr(const PassKernel &k)
    // the ray queries (mdh_raycast, ..): the newest last, behind everything older.  The scan, the partition with either border,
    // global residency alone, with the partition, with the triangle BVH
    MDH_RQ(0) MDH_RQ(1) MDH_RQ(9) MDH_RQ(64) MDH_RQ(65) MDH_RQ(73) MDH_RQ(192)
+   // ... and the same queries for device arrays, whose lanes take the next ray when theirs has ended (mdh_raycast_device, ..): behind them
+   MDH_RS(0) MDH_RS(1) MDH_RS(9) MDH_RS(64) MDH_RS(65) MDH_RS(73) MDH_RS(192)
    return nullptr;
 #undef MDH_K
 #undef MDH_RAD
@@ -3938,4 +4108,5 @@ static const void *kernel_ptr(const PassKernel &k)
 #undef MDH_SCR
 #undef MDH_GTAB
 #undef MDH_RQ
+#undef MDH_RS
 }

@@ -1435,6 +1435,63 @@ template <int PART, bool GUARD = false> MDH_DEV float softshadows(const KScene &
    return res;
 }
 
+// THE THREE MARCHES IN STEP FORM (k_ray_stream, mdh_kernels.h: a lane that has ended its ray takes the next one while its
+// neighbours march on).  A lane's ray is a RayMarch; *_begin is the loop's initialisation and its first test, *_step one
+// iteration and the test before the next.  Operation for operation raycast<PART, true>, raycast_visibility<PART, true> and
+// softshadows<PART, true> above, stall guard included: a ray's answer has the bits the loops give it.  The loops stay as they
+// are -- every pass marches with them.  The caller keeps a lane without a ray out of *_step, so that the wave ballots of the
+// culled scan see lanes with rays only, as they do in the loops once lanes have returned.
+#define MDH_RS_GO 0   // the loop goes on: another step
+#define MDH_RS_HIT 1  // dist < MDH_EPS at from + dir * total
+#define MDH_RS_OUT 2  // the loop has ended without one (its test failed, or the ray stalled)
+struct RayMarch {
+   f3 from, dir;
+   float total, max_dist; // the loop's variable and its bound (raycast: the scene's max_dist)
+   float res, prev;       // softshadows
+   int n, index;          // raycast: evaluations so far, the arg-min of the last one
+};
+MDH_DEV int march_begin(RayMarch &m, f3 from, f3 dir, float min_dist, float max_dist)
+{
+   m.from = from; m.dir = dir;
+   m.total = min_dist; m.max_dist = max_dist;
+   m.res = 1.0f; m.prev = 1e20f;
+   m.n = 0; m.index = -1;
+   MDH_WORK(0);
+   return m.total < m.max_dist ? MDH_RS_GO : MDH_RS_OUT;
+}
+template <int PART> MDH_DEV int raycast_step(const KScene &sc, RayMarch &m)
+{
+   MDH_WORK(1);
+   float dist = sdf_info<PART>(sc, m.from + m.dir * m.total, m.index);
+   ++m.n;
+   if (dist < MDH_EPS) return MDH_RS_HIT; // (coll = from + dir * total, t = total: the caller's)
+   if (m.total + dist == m.total) return MDH_RS_OUT; // stalled: a miss
+   m.total += dist;
+   return m.total < m.max_dist ? MDH_RS_GO : MDH_RS_OUT;
+}
+template <int PART> MDH_DEV int visibility_step(const KScene &sc, RayMarch &m)
+{
+   MDH_WORK(1);
+   float dist = sdf<PART>(sc, m.from + m.dir * m.total);
+   if (dist < MDH_EPS) return MDH_RS_HIT; // 0.0
+   if (m.total + dist == m.total) return MDH_RS_OUT; // stalled: nothing was hit
+   m.total += dist;
+   return m.total < m.max_dist ? MDH_RS_GO : MDH_RS_OUT; // 1.0
+}
+template <int PART> MDH_DEV int softshadows_step(const KScene &sc, RayMarch &m, float k)
+{
+   MDH_WORK(1);
+   float dist = sdf<PART>(sc, m.from + m.dir * m.total);
+   if (dist < MDH_EPS) return MDH_RS_HIT; // 0.0
+   float y = dist * dist / (2.0f * m.prev);
+   float d = sqrt_(dist * dist - y * y);
+   m.res = min_raw(m.res, k * d / max_(0.0f, m.total - y));
+   m.prev = dist;
+   if (m.total + dist == m.total) return MDH_RS_OUT; // stalled: res as it stands
+   m.total += dist;
+   return m.total < m.max_dist ? MDH_RS_GO : MDH_RS_OUT; // res
+}
+
 // ------------------------------------------------------------------------------ lights
 // sample_<Light> (scenes.adb:497-549) dispatched by cumulative RUNTIME counts (scenes.adb:731-764)
 template <bool CUSTOM> MDH_DEV f3 sample_light(const KScene &sc, int index, f3 pos, f3 normal, f3 &dir, float &dist)

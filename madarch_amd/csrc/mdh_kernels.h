@@ -1603,6 +1603,110 @@ template <int PART, int WHAT> __global__ __launch_bounds__(MDH_BLOCK) void k_ray
    if (a.normal) { a.normal[3 * q] = N.x; a.normal[3 * q + 1] = N.y; a.normal[3 * q + 2] = N.z; }
 }
 
+// mdh_raycast_device, mdh_raycast_visibility_device, mdh_softshadows_device (mdh_api.hip): the same three queries for rays
+// that live in device memory, with the marches in step form (mdh_device.h: RayMarch) so that A LANE TAKES THE NEXT RAY WHEN
+// ITS OWN HAS ENDED.  The grid is at most what the device holds at once; its wavefronts share the launch's counter `next`
+// (zeroed before the launch) and take rays from it as mdh_ray_stream.h says: a wavefront with at least `refill` idle lanes,
+// or none busy, has lane 0 add the number of its idle lanes to the counter -- one vector atomic -- and its j-th idle lane
+// takes ray base + j while that is below n.  A wavefront whose hand-out reached n asks no more and ends when its lanes have;
+// nothing waits for another wavefront, so every grid size serves every ray exactly once.  refill = 64: rounds of 64
+// consecutive rays, k_ray_query's schedule.  A lane stores its answers at its ray's index as soon as the ray ends.
+// The host cannot look at these rays, so a lane tests its ray before marching it (rs_ray_valid, rs_tmax_valid: the host
+// path's predicate) and answers one that fails without a march: raycast with a miss of 0 steps, the other two with NaN.
+// stage_table's barrier is the only one: every thread of the workgroup reaches it, and none leaves the loop through a
+// barrier.  Not part of the hiprtc build (built-in kinds only).
+#ifndef MDH_JIT
+#include "mdh_ray_stream.h"
+struct RayStreamArgs {
+   RayQueryArgs q;
+   unsigned *next; // the launch's counter of rays handed out
+   int refill;     // 1 .. 64
+};
+template <int PART, int WHAT> MDH_DEV void ray_stream_store(const KScene &sc, const RayQueryArgs &a, size_t q, const RayMarch &m, int status)
+{
+   if (WHAT == MDH_RQ_VISIBILITY) { a.out[q] = status == MDH_RS_HIT ? 0.0f : 1.0f; return; }
+   if (WHAT == MDH_RQ_SOFTSHADOW) { a.out[q] = status == MDH_RS_HIT ? 0.0f : m.res; return; }
+   const bool h = status == MDH_RS_HIT;
+   int index = -1; // (a miss: the arg-min of the last step is no hit)
+   float t = 0.0f;
+   f3 P = F3(0.0f, 0.0f, 0.0f), N = F3(0.0f, 0.0f, 0.0f);
+   if (h) {
+      index = m.index;
+      P = m.from + m.dir * m.total;
+      t = m.total;
+      int material;
+      if (a.normal) primitive_info<false, (PART & MDH_PF_GTAB) != 0>(sc, index, P, N, material);
+   }
+   a.hit[q] = h ? 1 : 0;
+   if (a.index) a.index[q] = index;
+   if (a.t) a.t[q] = t;
+   if (a.steps) a.steps[q] = m.n;
+   if (a.pos) { a.pos[3 * q] = P.x; a.pos[3 * q + 1] = P.y; a.pos[3 * q + 2] = P.z; }
+   if (a.normal) { a.normal[3 * q] = N.x; a.normal[3 * q + 1] = N.y; a.normal[3 * q + 2] = N.z; }
+}
+// a ray that is not marched
+template <int WHAT> MDH_DEV void ray_stream_refuse(const RayQueryArgs &a, size_t q)
+{
+   if (WHAT != MDH_RQ_RAYCAST) { a.out[q] = __uint_as_float(MDH_RS_BAD_BITS); return; }
+   a.hit[q] = -1;
+   if (a.index) a.index[q] = -1;
+   if (a.t) a.t[q] = 0.0f;
+   if (a.steps) a.steps[q] = 0;
+   if (a.pos) { a.pos[3 * q] = 0.0f; a.pos[3 * q + 1] = 0.0f; a.pos[3 * q + 2] = 0.0f; }
+   if (a.normal) { a.normal[3 * q] = 0.0f; a.normal[3 * q + 1] = 0.0f; a.normal[3 * q + 2] = 0.0f; }
+}
+template <int PART, int WHAT> __global__ __launch_bounds__(MDH_BLOCK) void k_ray_stream(KScene sc, RayStreamArgs sa)
+{
+   static_assert(!(PART & (MDH_PF_CUSTOM | MDH_PF_POW2 | MDH_PF_ROOM | MDH_PF_PSMALL)), "ray queries: the general variants of built-in kinds");
+   static_assert(MDH_BLOCK % MDH_RS_WAVE == 0, "whole wavefronts");
+   stage_table(sc); // (the kernel's only barrier; every thread is still here)
+   const RayQueryArgs &a = sa.q;
+   const int lane = threadIdx.x & 63;
+   const unsigned n = (unsigned)a.n;
+   const int refill = sa.refill;
+   RayMarch m;
+   long long ray = -1; // the lane's ray; -1: idle
+   int status = MDH_RS_OUT;
+   bool drained = false; // (wave-uniform) the counter has passed n: this wavefront takes no more rays
+   for (;;) {
+      const unsigned long long idle = __ballot(ray < 0);
+      const int n_idle = __popcll(idle);
+      if (!drained && rs_refills(n_idle, refill)) { // (wave-uniform: every lane of the wavefront is in this loop)
+         unsigned base = 0;
+         if (lane == 0) base = atomicAdd(sa.next, (unsigned)n_idle);
+         base = (unsigned)__builtin_amdgcn_readfirstlane((int)base);
+         if (ray < 0) {
+            ray = rs_ray_of(base, idle, lane, n);
+            if (ray >= 0) {
+               const size_t q = (size_t)ray;
+               const float ox = a.org[3 * q], oy = a.org[3 * q + 1], oz = a.org[3 * q + 2];
+               const float dx = a.dir[3 * q], dy = a.dir[3 * q + 1], dz = a.dir[3 * q + 2];
+               const float tmax = WHAT == MDH_RQ_RAYCAST ? sc.max_dist : a.tmax[q];
+               if (!rs_ray_valid(ox, oy, oz, dx, dy, dz) || (WHAT != MDH_RQ_RAYCAST && !rs_tmax_valid(tmax, sc.max_dist))) {
+                  ray_stream_refuse<WHAT>(a, q);
+                  ray = -1; // (idle again: the next hand-out serves the lane)
+               } else
+                  status = march_begin(m, F3(ox, oy, oz), F3(dx, dy, dz), WHAT == MDH_RQ_SOFTSHADOW ? a.tmin : 0.0f, tmax);
+            }
+         }
+         drained = rs_drained(base, n_idle, n);
+      }
+      if (__ballot(ray >= 0) == 0ull) {
+         if (drained) break;
+         continue; // (every ray of the hand-out was refused: the next one)
+      }
+      if (ray >= 0) {
+         if (status == MDH_RS_GO)
+            status = WHAT == MDH_RQ_RAYCAST ? raycast_step<PART>(sc, m) : WHAT == MDH_RQ_VISIBILITY ? visibility_step<PART>(sc, m) : softshadows_step<PART>(sc, m, a.k);
+         if (status != MDH_RS_GO) {
+            ray_stream_store<PART, WHAT>(sc, a, (size_t)ray, m, status);
+            ray = -1;
+         }
+      }
+   }
+}
+#endif
+
 // ---------------------------------------------------------------------- the window's pixels
 // What Swap_Buffers (renderers.adb:320) puts on screen: the screen pass writes float colours and
 // the default framebuffer of the reference's window is RGBA8 without sRGB encoding, so each

@@ -1,0 +1,56 @@
+// mdh_ray_stream.h -- what the device-array ray queries (k_ray_stream, mdh_kernels.h; mdh_raycast_device, .., mdh_api.hip)
+// decide without a device: which rays are marched at all, and how a wavefront hands the next rays to its idle lanes.
+// Plain inline functions, no HIP runtime in them: the kernels include this header, the host's checks call the same
+// predicate (ray_query_check), and tests/ray_stream_check.cpp drives the hand-out on the CPU under the sanitizers.
+//
+// THE HAND-OUT.  A launch owns one 32-bit counter `next`, zero at its start.  A wavefront that refills counts its idle
+// lanes (k = the set bits of `idle`), one lane adds k to the counter and broadcasts the value it found there (`base`), and
+// the j-th idle lane in lane order takes ray base + j -- if that is below n; otherwise the lane has no ray, and since the
+// counter only grows, neither has any lane of this wavefront ever again: the wavefront is drained (rs_drained) and asks no
+// more.  A wavefront therefore adds to the counter at most once beyond n, and at most 64 then: the counter cannot wrap
+// for n < 2^31 and fewer than 2^25 wavefronts.  No wavefront reads what another one wrote except through the counter.
+#pragma once
+
+#if defined(__HIPCC__) || defined(__CUDACC__)
+#define MDH_RS_FN __host__ __device__ inline
+#else
+#define MDH_RS_FN inline
+#endif
+
+#define MDH_RS_WAVE 64
+#define MDH_RS_REFILL_MIN 1
+#define MDH_RS_REFILL_MAX 64 // lock step: rounds of 64 consecutive rays, k_ray_query's schedule
+#ifndef MDH_RAY_STREAM_REFILL_DEFAULT
+#define MDH_RAY_STREAM_REFILL_DEFAULT 64 // MDH_OPT_RAY_STREAM_REFILL as a renderer starts ("Ray queries": the measurement that sets it)
+#endif
+#define MDH_RS_BAD_BITS 0x7fc00000u // what visibility and soft shadow answer a ray that was not marched with: the quiet NaN
+
+// ---------------------------------------------------------------------- which rays are marched
+MDH_RS_FN bool rs_finite(float x)
+{
+   unsigned u;
+   __builtin_memcpy(&u, &x, 4);
+   return (u & 0x7f800000u) != 0x7f800000u; // (neither an infinity nor a NaN; denormals are finite)
+}
+// the six components of a ray
+MDH_RS_FN bool rs_ray_valid(float ox, float oy, float oz, float dx, float dy, float dz)
+{
+   return rs_finite(ox) && rs_finite(oy) && rs_finite(oz) && rs_finite(dx) && rs_finite(dy) && rs_finite(dz);
+}
+// the length of a visibility or soft-shadow ray: finite and within the scene's max_dist (any finite value below it, negative ones too)
+MDH_RS_FN bool rs_tmax_valid(float tmax, float max_dist) { return rs_finite(tmax) && tmax <= max_dist; }
+
+// ---------------------------------------------------------------------- the hand-out
+MDH_RS_FN int rs_popcount(unsigned long long m) { return __builtin_popcountll(m); }
+// does a wavefront with n_idle idle lanes take new rays?
+MDH_RS_FN bool rs_refills(int n_idle, int refill) { return n_idle >= refill || n_idle == MDH_RS_WAVE; }
+// the place of `lane` among the idle lanes (bit l of `idle`: lane l is idle)
+MDH_RS_FN int rs_idle_rank(unsigned long long idle, int lane) { return rs_popcount(idle & ((1ull << lane) - 1ull)); }
+// the ray an idle lane takes from a hand-out that found `base` in the counter, or -1: none, now and for good
+MDH_RS_FN long long rs_ray_of(unsigned base, unsigned long long idle, int lane, unsigned n)
+{
+   const unsigned long long q = (unsigned long long)base + (unsigned)rs_idle_rank(idle, lane);
+   return q < (unsigned long long)n ? (long long)q : -1;
+}
+// after a hand-out of k rays from `base`: has the counter passed n (no later hand-out can yield a ray)?
+MDH_RS_FN bool rs_drained(unsigned base, int k, unsigned n) { return (unsigned long long)base + (unsigned)k >= (unsigned long long)n; }

@@ -161,6 +161,71 @@ class Renderer:
         self._b.check(self._b.ray_query_time(self._h, C.byref(ms)))
         return ms.value
 
+    # ---- the same queries for arrays on the device: asynchronous, ordered with a stream of the caller's.  An array is an
+    # integer address or any object with data_ptr () -- a torch tensor, which this package never imports
+    @staticmethod
+    def _device_array(Array, What, Values, Kind, Optional=False):
+        """the address of at least `Values` float32 ("float32") or int32 ("int32") values on the device; what the object tells
+        about itself (is_cuda, is_contiguous, numel, dtype) is checked: ValueError before any library call"""
+        if Array is None:
+            if Optional:
+                return None
+            raise ValueError("%s: an array is required" % What)
+        if isinstance(Array, (int, np.integer)):
+            return C.c_void_p(int(Array))
+        if not hasattr(Array, "data_ptr"):
+            raise ValueError("%s: an integer address or an object with data_ptr (), not %s" % (What, type(Array).__name__))
+        if hasattr(Array, "is_cuda") and not Array.is_cuda:
+            raise ValueError("%s: not on the device" % What)
+        if hasattr(Array, "is_contiguous") and not Array.is_contiguous():
+            raise ValueError("%s: not contiguous" % What)
+        if hasattr(Array, "dtype") and str(Array.dtype).rsplit(".", 1)[-1] != Kind:
+            raise ValueError("%s: %s, not %s" % (What, Array.dtype, Kind))
+        if hasattr(Array, "numel") and Array.numel() < Values:
+            raise ValueError("%s: %d values, %d needed" % (What, Array.numel(), Values))
+        return C.c_void_p(int(Array.data_ptr()))
+
+    @staticmethod
+    def _ray_count(Origins, N):
+        if N is None:
+            if not hasattr(Origins, "numel"):
+                raise ValueError("N: the number of rays is required with plain addresses")
+            N = Origins.numel() // 3
+        if int(N) < 0:
+            raise ValueError("N: %d rays" % N)
+        return int(N)
+
+    def Raycast_Device(self, Origins, Directions, Hit, Index=None, T=None, Steps=None, Position=None, Normal=None, Stream=0, N=None):
+        """Raycast for N rays (default: what Origins holds) in device memory, enqueued behind what `Stream` (an integer
+        hipStream_t, 0 = the default stream) holds; work given to Stream afterwards sees the answers.  Every output but Hit
+        may be None.  A ray that is not finite is not marched: hit = -1, index = -1, the rest 0."""
+        n = self._ray_count(Origins, N)
+        dev = self._device_array
+        args = [dev(Origins, "Origins", 3 * n, "float32"), dev(Directions, "Directions", 3 * n, "float32"), dev(Hit, "Hit", n, "int32"),
+                dev(Index, "Index", n, "int32", True), dev(T, "T", n, "float32", True), dev(Steps, "Steps", n, "int32", True),
+                dev(Position, "Position", 3 * n, "float32", True), dev(Normal, "Normal", 3 * n, "float32", True)]
+        self._b.check(self._b.raycast_device(self._h, n, *args, C.c_void_p(int(Stream))))
+
+    def Raycast_Visibility_Device(self, Origins, Directions, Max_Dists, Visibility, Stream=0, N=None):
+        """Raycast_Visibility likewise, one length per ray; NaN for a ray that is not finite or longer than max_dist"""
+        n = self._ray_count(Origins, N)
+        dev = self._device_array
+        args = [dev(Origins, "Origins", 3 * n, "float32"), dev(Directions, "Directions", 3 * n, "float32"),
+                dev(Max_Dists, "Max_Dists", n, "float32"), dev(Visibility, "Visibility", n, "float32")]
+        self._b.check(self._b.raycast_visibility_device(self._h, n, *args, C.c_void_p(int(Stream))))
+
+    def Softshadows_Device(self, Origins, Directions, Min_Dist, Max_Dists, K, Out, Stream=0, N=None):
+        """Softshadows likewise"""
+        n = self._ray_count(Origins, N)
+        dev = self._device_array
+        org, drs = dev(Origins, "Origins", 3 * n, "float32"), dev(Directions, "Directions", 3 * n, "float32")
+        tmax, out = dev(Max_Dists, "Max_Dists", n, "float32"), dev(Out, "Out", n, "float32")
+        self._b.check(self._b.softshadows_device(self._h, n, org, drs, float(Min_Dist), tmax, float(K), out, C.c_void_p(int(Stream))))
+
+    def Ray_Query_Wait(self):
+        """blocks until every device query enqueued so far has ended"""
+        self._b.check(self._b.ray_query_wait(self._h))
+
     def Render_Pass(self, Pass):
         self._b.check(self._b.render_pass(self._h, int(Pass)))
 
