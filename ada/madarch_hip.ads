@@ -210,6 +210,34 @@ package Madarch_HIP is
    function Ray_Query_Wait (R : Handle) return Status
      with Import, Convention => C, External_Name => "mdh_ray_query_wait";
 
+   --  What a ray sees (madarch_hip.h): pixel_color_probes along N rays of the host's, through the
+   --  pixel program of the screen pass.  Mode 0 (the fixed mode) or 2 (direct light times occlusion);
+   --  Tone_Map 0 = the linear colour, 1 = the framebuffer's bits.  RGB_Out: 3 N floats, required;
+   --  the other outputs may be Null_Address and count as in Read_Gbuffer.  Never any fog.  A ray that
+   --  is not finite, starts beyond 1024 along an axis or has a direction component beyond 2 is not
+   --  shaded: Status 1 for the batch of host arrays, NaN and Hit = -1 for that ray of device arrays.
+   function Shade_Rays
+     (R : Handle; N : int; Org, Dir : System.Address; Mode, Tone_Map : int;
+      RGB_Out, Hit_Out, Index_Out, T_Out, Steps_Out : System.Address) return Status
+     with Import, Convention => C, External_Name => "mdh_shade_rays";
+
+   function Shade_Rays_Device
+     (R : Handle; N : int; Org, Dir : System.Address; Mode, Tone_Map : int;
+      RGB_Out, Hit_Out, Index_Out, T_Out, Steps_Out : System.Address;
+      Stream : System.Address) return Status
+     with Import, Convention => C, External_Name => "mdh_shade_rays_device";
+
+   --  The rays of a Width x Height frame of the current camera, rows top first, 3 floats a ray:
+   --  computed on the device by the screen pass's own functions, the frame's rays to the bit.
+   function Camera_Rays
+     (R : Handle; Width, Height : int; Org_Out, Dir_Out : System.Address) return Status
+     with Import, Convention => C, External_Name => "mdh_camera_rays";
+
+   function Camera_Rays_Device
+     (R : Handle; Width, Height : int; Org_Out, Dir_Out : System.Address;
+      Stream : System.Address) return Status
+     with Import, Convention => C, External_Name => "mdh_camera_rays_device";
+
    --  One frame on the N GPUs of a node, one process per GPU (madarch_hip.h, mdh_comm_*):
    --  every process creates its Renderer on its own device, rank 0 makes a 128-byte id and
    --  hands it to the others (a file, an environment variable), all call Comm_Init, and

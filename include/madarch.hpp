@@ -391,6 +391,36 @@ class Renderer {
       Check(mdh_softshadows_device(h_.get(), N, Origins, Directions, Min_Dist, Max_Dists, K, Out, Stream));
    }
    void Ray_Query_Wait() const { Check(mdh_ray_query_wait(h_.get())); }
+   // ---- what a ray sees: pixel_color_probes (render_probes.glsl:246-291) along rays of the host's, through the screen pass's
+   // pixel program.  Mode 0 (the fixed mode) or 2 (direct light times occlusion); linear colour, or with Tone_Map the
+   // framebuffer's bits; a miss is the sky along the ray; never any fog.  Index, T, Steps as in the geometry buffer
+   struct Ray_Colours { std::vector<float> Rgb, T; std::vector<int32_t> Hit, Index, Steps; };
+   Ray_Colours Shade_Rays(const std::vector<float> &Origins, const std::vector<float> &Directions, int32_t Mode = 0, bool Tone_Map = false) const
+   {
+      const size_t n = Ray_Count(Origins, Directions);
+      Ray_Colours o;
+      o.Rgb.resize(3 * n); o.T.resize(n); o.Hit.resize(n); o.Index.resize(n); o.Steps.resize(n);
+      Check(mdh_shade_rays(h_.get(), (int32_t)n, Origins.data(), Directions.data(), Mode, Tone_Map ? 1 : 0, o.Rgb.data(), o.Hit.data(), o.Index.data(), o.T.data(), o.Steps.data()));
+      return o;
+   }
+   // ... for arrays in memory the device addresses, asynchronous and ordered with Stream as Raycast_Device is (every output but Rgb
+   // may be null).  A ray that is not finite, starts beyond 1024 along an axis or has a direction component beyond 2: NaN, Hit = -1
+   void Shade_Rays_Device(int32_t N, const float *Origins, const float *Directions, float *Rgb, int32_t *Hit = nullptr, int32_t *Index = nullptr, float *T = nullptr,
+                          int32_t *Steps = nullptr, int32_t Mode = 0, bool Tone_Map = false, void *Stream = nullptr) const
+   {
+      Check(mdh_shade_rays_device(h_.get(), N, Origins, Directions, Mode, Tone_Map ? 1 : 0, Rgb, Hit, Index, T, Steps, Stream));
+   }
+   // the rays of a Width x Height frame of the current camera, rows top first, 3 floats a ray: the frame's rays to the bit
+   void Camera_Rays(int32_t Width, int32_t Height, std::vector<float> &Origins, std::vector<float> &Directions) const
+   {
+      if (Width <= 0 || Height <= 0) throw Constraint_Error("a frame has at least one pixel");
+      Origins.resize((size_t)Width * Height * 3); Directions.resize((size_t)Width * Height * 3);
+      Check(mdh_camera_rays(h_.get(), Width, Height, Origins.data(), Directions.data()));
+   }
+   void Camera_Rays_Device(int32_t Width, int32_t Height, float *Origins, float *Directions, void *Stream = nullptr) const
+   {
+      Check(mdh_camera_rays_device(h_.get(), Width, Height, Origins, Directions, Stream));
+   }
    void Update_Partitioning(Partitioning_Update_Method Method = GPU_Fast) const { Check(mdh_update_partitioning(h_.get(), (int32_t)Method)); } // renderers.adb:757-775
    // ---- headless additions
    std::vector<float> Read_Framebuffer() const // replaces Swap_Buffers: H*W*3 floats, row 0 = top

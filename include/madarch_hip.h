@@ -594,6 +594,50 @@ int32_t mdh_softshadows_device(mdh_renderer *r, int32_t n, const float *org_xyz,
  * by itself it waits for that query's end event first. */
 int32_t mdh_ray_query_wait(mdh_renderer *r);
 
+/* What a ray sees: pixel_color_probes (glsl/render_probes.glsl:246-291) -- direct light with soft shadows, the DDGI
+ * irradiance of the cage, the reflection's radiance tap, ambient occlusion -- along n rays of the host's, through the pixel
+ * program the screen pass runs.  Origins and directions are 3 n floats, directions used as given.
+ *   mode 0      the reference's fixed mode: pixel_color_probes with the renderer's current MDH_OPT_AO_STEPS and
+ *               MDH_OPT_INDIRECT_SPECULAR and with direct specular on, as renderers.adb:136-143 sets the screen shader
+ *   mode 2      this library's mode-2 screen pass: direct light times occlusion, no probes
+ *   tone_map 0  the linear colour pixel_color_probes returns; a miss is the sky of render_probes.glsl:287 along the ray
+ *   tone_map 1  draw_screen.glsl:29 applied to it: the bits the framebuffer would hold
+ * rgb_out (3 n floats) is required; hit_out (0 / 1), index_out, t_out and steps_out may be NULL and carry the meaning and
+ * the numbering of mdh_read_gbuffer.
+ * NO VOLUMETRICS: the fog of glsl/volumetrics.glsl:34-54 is looked up by the fragment's screen position, which a free ray
+ * does not have -- the query never composes fog, whatever the renderer's volumetric settings.
+ * The call reads the scene committed at the call, pending edits included, and the atlas set a
+ * mdh_render_pass (MDH_PASS_SCREEN) issued at the same moment would read: it runs behind the passes that write that set, and
+ * no later frame rewrites the set before the query's kernel has ended.  It edits nothing: the probe-settle run and the
+ * radiance and screen replays go on across it.  n = 0 is MDH_OK without a launch.
+ *   MDH_E_INVALID  a null renderer or required array, n < 0, a mode other than 0 or 2 (mode 1, the normal, is
+ *                  mdh_raycast's), and -- mdh_shade_rays, on the host, the whole batch -- a ray that is not shaded (below)
+ *   MDH_E_STATE    a scene with a user-defined kind; an open frame; MDH_OPT_INDIRECT_SPECULAR 1 or 3, or 2 over a mip
+ *                  chain in use (the screen pass's other variant: not built for rays); a scene outside the bound below
+ * The marches of the pixel program have no step cap and no stall guard, so termination is kept by a bound: a ray is
+ * shaded only if every component is finite, every origin component is at most 1024 and every direction component at most
+ * 2 in magnitude, and the call is refused when the scene's max_dist exceeds 1024 or a light's position or the probe
+ * grid's far corner has a component beyond 1024 in magnitude.  Every march parameter then stays below 2^14, where a step
+ * of at least epsilon still advances it ("Shading a host's rays"). */
+int32_t mdh_shade_rays(mdh_renderer *r, int32_t n, const float *org_xyz, const float *dir_xyz, int32_t mode, int32_t tone_map,
+                       float *rgb_out, int32_t *hit_out, int32_t *index_out, float *t_out, int32_t *steps_out);
+/* The same call for arrays the device addresses, under the contract of mdh_raycast_device: asynchronous and ordered with
+ * `stream` (a hipStream_t; NULL: the default stream), mdh_ray_query_wait is the host's wait, and where every array lives
+ * and ends is checked with hipPointerGetAttributes before anything is launched (MDH_E_INVALID).  The host cannot look at
+ * the rays, so the lane that takes a ray which is not shaded answers it without marching: the quiet NaN 0x7fc00000 in all
+ * three colours, hit = -1, index = -1, t = 0, steps = 0.  Every other ray has the bits mdh_shade_rays gives it. */
+int32_t mdh_shade_rays_device(mdh_renderer *r, int32_t n, const float *org_xyz, const float *dir_xyz, int32_t mode,
+                              int32_t tone_map, float *rgb_out, int32_t *hit_out, int32_t *index_out, float *t_out,
+                              int32_t *steps_out, void *stream);
+/* The rays of a width x height frame of the renderer's current camera (glsl/draw_screen.glsl:20-24), 3 width height floats
+ * each, rows top first like the framebuffer.  They are computed on the device by the screen pass's own functions and are
+ * the frame's rays to the bit: a host jitters, warps or subsamples them and hands them to the calls above.  The device
+ * variant is enqueued on `stream` itself.  MDH_E_INVALID: a null renderer or array, a width or height below 1, more than
+ * 2^28 pixels, an array the device cannot address. */
+int32_t mdh_camera_rays(mdh_renderer *r, int32_t width, int32_t height, float *org_xyz_out, float *dir_xyz_out);
+int32_t mdh_camera_rays_device(mdh_renderer *r, int32_t width, int32_t height, float *org_xyz_out, float *dir_xyz_out,
+                               void *stream);
+
 /* accumulated HIP-event time and launch count of one pass (MDH_OPT_TIMING) */
 int32_t mdh_pass_time(mdh_renderer *r, int32_t pass, double *total_ms, int64_t *launches);
 /* MDH_OPT_RADIANCE_REPLAY: the radiance passes launched since mdh_create that marched their rays (`plain`), marched them

@@ -169,6 +169,12 @@ HIP_ONLY_ABI = {
     "raycast_visibility_device": (_I, [_P, _I, _P, _P, _P, _P, _P]),
     "softshadows_device": (_I, [_P, _I, _P, _P, _F, _P, _F, _P, _P]),
     "ray_query_wait": (_I, [_P]),  # blocks until every device query enqueued so far has ended
+    # the frame's pixel program (render_probes.glsl:246-291) along n rays of the host's: (r, n, org, dir, mode, tone_map, rgb,
+    # hit, index, t, steps[, stream]); and the rays of a width x height frame of the current camera (draw_screen.glsl:20-24)
+    "shade_rays": (_I, [_P, _I, _P, _P, _I, _I, _P, _P, _P, _P, _P]),
+    "shade_rays_device": (_I, [_P, _I, _P, _P, _I, _I, _P, _P, _P, _P, _P, _P]),
+    "camera_rays": (_I, [_P, _I, _I, _P, _P]),
+    "camera_rays_device": (_I, [_P, _I, _I, _P, _P, _P]),
 }
 
 

@@ -345,6 +345,9 @@ struct mdh_renderer {
    // the launches follow one another on the query stream), and the two events between the caller's stream and the query stream
    DevBuf<unsigned> d_rq_next;
    Event ev_rq_in, ev_rq_out;
+   // mdh_shade_rays, mdh_shade_rays_device: the events between the main stream and the query stream on both sides of the kernel
+   // (the atlas set the query reads: shade_rays_run), and the one from the caller's stream (one group, created by the first call)
+   Event ev_sq_frame, ev_sq_caller, ev_sq_done;
    int opt_rq_refill = MDH_RAY_STREAM_REFILL_DEFAULT; // MDH_OPT_RAY_STREAM_REFILL
    int opt_rq_groups = 0;                             // MDH_OPT_RAY_STREAM_GROUPS (0: as many workgroups as are resident)
    // Two sets of probe atlases.  `last` is the set the most recent frame wrote: every read, write and
@@ -1459,12 +1462,14 @@ static size_t lds_bytes(const mdh_renderer *r) { return (size_t)(r->ks.table_f4 
 static size_t lds_bytes_march(const mdh_renderer *r) { return lds_bytes(r) + (size_t)MDH_PARK_DWORDS * MDH_BLOCK * sizeof(float); }
 // the screen pass runs without the visibility queue, whose entries, first steps and result words are the park
 // slots from 15 up: 3 KiB less per workgroup, room for one more workgroup of a neighbouring pass on the CU
-static size_t lds_bytes_screen(const mdh_renderer *r)
+// (`mode`: the screen mode of the launch -- the renderer's for its screen pass, the call's for mdh_shade_rays)
+static size_t lds_bytes_screen_mode(const mdh_renderer *r, int mode)
 {
    // (scenes with a space partition: three more rows, the second shaded point's normal across its visibility marches, MDH_PARK_VD_ROW)
-   const int rows = r->opt_mode == 2 ? MDH_DIRECT_PARK_ROWS : (r->part.enable ? std::max(MDH_SCR_PARK_ROWS, MDH_PARK_VD_ROW + 3) : MDH_SCR_PARK_ROWS);
+   const int rows = mode == 2 ? MDH_DIRECT_PARK_ROWS : (r->part.enable ? std::max(MDH_SCR_PARK_ROWS, MDH_PARK_VD_ROW + 3) : MDH_SCR_PARK_ROWS);
    return lds_bytes(r) + (size_t)rows * MDH_BLOCK * sizeof(float);
 }
+static size_t lds_bytes_screen(const mdh_renderer *r) { return lds_bytes_screen_mode(r, r->opt_mode); }
 
 // ------------------------------------------------------------------ hiprtc build of user-defined kinds
 // MDH_OPT_JIT: instead of interpreting the MDH_X programs, compile them.  Every program becomes a
@@ -1791,14 +1796,14 @@ template <typename Args> static int jit_launch(hipFunction_t f, int blocks, int 
 // frames in flight share their CUs' instruction caches (measured: the same kernels at other addresses, each as fast by itself,
 // the headline with frames in flight 0.5 % slower).  The kernels of global residency (MDH_PF_GTAB, mdh_device.h: Geo) come
 // last there: behind everything else they move nothing.
-enum { GK_k_visibility, GK_k_scat_march, GK_k_scattering, GK_k_radiance, GK_k_screen, GK_k_partition_build, GK_k_eval_distance, GK_k_diag_segments, GK_k_ray_query, GK_k_ray_stream };
+enum { GK_k_visibility, GK_k_scat_march, GK_k_scattering, GK_k_radiance, GK_k_screen, GK_k_partition_build, GK_k_eval_distance, GK_k_diag_segments, GK_k_ray_query, GK_k_ray_stream, GK_k_ray_shade, GK_k_camera_rays };
 // WHICH KERNEL A PASS RUNS ("One place that picks a pass's kernel"): every template argument of the
 // pass's kernel, computed once by pick_kernel; kernel_name and kernel_ptr turn the same description into the name hiprtc
 // instantiates and into the kernel of this library.
 struct PassKernel {
    int family = -1; // GK_*
    int pf = 0;      // the kernel's MDH_PF_* word
-   int mode = 0;    // k_screen: the screen mode, ...
+   int mode = 0;    // k_screen, k_ray_shade: the screen mode, ...
    bool gbuf = false, alt = false; // ... the geometry buffer, the variant of the optional specular bodies
    bool small = false;             // k_radiance: SMALL
    int rec = 0;                    // k_radiance, k_screen: REC (0 marches, 1 marches and records, 2 replays the records: rad_replay_pick, scr_replay_pick)
@@ -1827,8 +1832,9 @@ static const void *table_kernel(const mdh_renderer *r, int family, int what = 0)
    if (family == GK_k_eval_distance && r->bvh_active && !k.ada_div) k.pf |= MDH_PF_BVH;
    // the ray queries march as the passes do: through the space partition (its border as a variant of its own) or the triangle
    // BVH where the scene has one -- the general variants, whose bits the census variants share (pick_kernel)
-   if (family == GK_k_ray_query || family == GK_k_ray_stream) {
+   if (family == GK_k_ray_query || family == GK_k_ray_stream || family == GK_k_ray_shade) {
       k.what = what;
+      if (family == GK_k_ray_shade) { k.what = 0; k.mode = what; } // (mdh_shade_rays: `what` is the call's screen mode, 0 or 2)
       if (r->part.enable) k.pf |= MDH_PF_PART | (r->part.border_behavior != 0 ? MDH_PF_FALLBACK : 0);
       if (r->bvh_active) k.pf |= MDH_PF_BVH;
    }
@@ -3806,6 +3812,197 @@ extern "C" int32_t mdh_ray_query_wait(mdh_renderer *r)
    return ray_query_wait(r);
 }
 
+// ------------------------------------------------------------------ shading a host's rays
+// mdh_shade_rays, mdh_shade_rays_device: pixel_color_probes (render_probes.glsl:246-291) along n rays of the host's, through
+// the pixel program the screen pass runs (k_ray_shade, mdh_kernels.h).  The plumbing is the ray queries': the query stream,
+// ensure_committed, table_acquire / table_release, d_rays for host arrays, ray_array_check and two events to the caller's
+// stream for device arrays, rq_e0 / rq_e1 under MDH_OPT_TIMING.  No settle_bump: nothing is edited.
+// WHICH ATLASES, AND WHEN.  The query is a mdh_render_pass (MDH_PASS_SCREEN) that runs on the query stream: it reads set
+// `last`, and it is tied to the main stream as that pass is tied to it by running there -- join_main, then the query stream
+// waits for the main stream (which every screen pass of a frame up to `last`, hence every probe pass of those frames, is
+// ordered before), and behind the kernel the main stream waits for the query stream with main_dirty set, so that the next
+// frame orders its probe, volumetric and alternate streams behind the query before any of them rewrites a set.
+// (the three events: one group, created by the first call)
+static int shade_scene_check(const mdh_renderer *r)
+{
+   // (the scene's half of the bound that stands in for a stall guard, mdh_ray_stream.h: rs_shade_ray_valid has the ray's)
+   if (!rs_shade_extent_valid(r->max_dist)) return seterr(MDH_E_STATE, "shaded rays need a max_dist of at most 1024");
+   for (int k = 0; k < r->nlk; ++k) {
+      const Kind &kd = r->lk[k];
+      int n = rd_i(r, kd.count_off);
+      if (n > kd.max_count) n = kd.max_count;
+      for (int i = 0; i < n; ++i)
+         for (int c = 0; c < 3; ++c)
+            if (!rs_shade_extent_valid(rd_f(r, kd.array_off + kd.stride * i + kd.f_a + 4 * c))) return seterr(MDH_E_STATE, "shaded rays need every light within 1024 of the origin along every axis");
+   }
+   for (int c = 0; c < 3; ++c)
+      if (!rs_shade_extent_valid((float)(r->probes.grid_dimensions[c] - 1) * r->probes.grid_spacing[c])) return seterr(MDH_E_STATE, "shaded rays need the probe grid's far corner within 1024 of the origin along every axis");
+   return MDH_OK;
+}
+// everything both calls refuse before they look at their arrays
+static int shade_rays_check(const mdh_renderer *r, int32_t n, const float *org, const float *dir, int32_t mode, const float *rgb)
+{
+   if (!r) return seterr(MDH_E_INVALID, "null renderer");
+   if (!org || !dir || !rgb || n < 0) return seterr(MDH_E_INVALID, "bad argument");
+   if (mode != 0 && mode != 2) return seterr(MDH_E_INVALID, "rays are shaded in mode 0 or 2 (mode 1, the normal, is mdh_raycast's)");
+   if (has_custom_kinds(r)) return seterr(MDH_E_STATE, "ray queries answer scenes of built-in kinds only");
+   if (r->in_frame) return seterr(MDH_E_STATE, "a frame is open");
+   // (the ALT variant of the screen pass, pick_kernel: not built for rays)
+   if (r->opt_spec == 1 || r->opt_spec == 3 || (r->opt_spec == 2 && r->opt_mips && r->d_rad_mips[r->last].ptr))
+      return seterr(MDH_E_STATE, "rays are shaded with MDH_OPT_INDIRECT_SPECULAR 0 or 2, the latter without MDH_OPT_RADIANCE_MIPS");
+   return shade_scene_check(r);
+}
+// the query stream and the events, the committed scene, the kernel; then the launch between the fences.  `caller`: the stream
+// device arrays are ordered with, or the query stream itself (host arrays: the copies around the launch are the caller's)
+static int shade_rays_run(mdh_renderer *r, int32_t mode, const RayShadeArgs &a, hipStream_t qs, hipStream_t caller)
+{
+   int rc;
+   const void *kernel = table_kernel(r, GK_k_ray_shade, mode);
+   if (!kernel) return seterr(MDH_E_INVALID, "no kernel built for this variant");
+   if ((rc = join_main(r)) != MDH_OK) return rc;
+   r->main_dirty = true;
+   HIP_TRY(hipEventRecord(r->ev_sq_frame.ev, r->stream));
+   HIP_TRY(hipStreamWaitEvent(qs, r->ev_sq_frame.ev, 0));
+   if (caller != qs) { // the rays are what the caller's stream has made of them at this call
+      HIP_TRY(hipEventRecord(r->ev_sq_caller.ev, caller));
+      HIP_TRY(hipStreamWaitEvent(qs, r->ev_sq_caller.ev, 0));
+   }
+   if ((rc = table_acquire(r, qs)) != MDH_OK) return rc;
+   const KProbes pr = make_probes(r); // (set `last`)
+   const unsigned blocks = (unsigned)(((size_t)a.n + MDH_BLOCK - 1) / MDH_BLOCK);
+   const bool timed = r->opt_timing && (r->rq_e0 || (r->rq_e0 = get_event(r))) && (r->rq_e1 || (r->rq_e1 = get_event(r)));
+   if (timed) HIP_TRY(hipEventRecord(r->rq_e0, qs));
+   if ((rc = launch_kernel_ptr(kernel, dim3(blocks), dim3(MDH_BLOCK), lds_bytes_screen_mode(r, mode), qs, r->ks, pr, a)) != MDH_OK) return rc;
+   HIP_TRY(hipGetLastError());
+   if (timed) HIP_TRY(hipEventRecord(r->rq_e1, qs));
+   r->rq_timed = timed;
+   if ((rc = table_release(r, qs)) != MDH_OK) return rc;
+   HIP_TRY(hipEventRecord(r->ev_sq_done.ev, qs)); // no later frame rewrites the set before this point ...
+   HIP_TRY(hipStreamWaitEvent(r->stream, r->ev_sq_done.ev, 0));
+   if (caller != qs) HIP_TRY(hipStreamWaitEvent(caller, r->ev_sq_done.ev, 0)); // ... and the answers are there for the caller's stream
+   return MDH_OK;
+}
+static int shade_rays_begin(mdh_renderer *r, hipStream_t *qs)
+{
+   HIP_TRY(hipSetDevice(r->device));
+   if (!r->query_stream) HIP_TRY(hipStreamCreateWithFlags(&r->query_stream, hipStreamNonBlocking));
+   HIP_TRY(create_all(r->ev_sq_frame, r->ev_sq_caller, r->ev_sq_done));
+   *qs = r->query_stream;
+   return ensure_committed(r, *qs);
+}
+// room in d_rays for n rays (MDH_RAY_WORDS words each); the places are the ray queries'
+static int rays_buffer(mdh_renderer *r, size_t n, hipStream_t qs, float **base, size_t *cap)
+{
+   const size_t want = (n < 256 ? 256 : n) * MDH_RAY_WORDS;
+   if (want > r->d_rays.cap) {
+      if (r->d_rays.ptr) HIP_TRY(hipStreamSynchronize(qs));
+      HIP_TRY(r->d_rays.grow(want));
+   }
+   *cap = r->d_rays.cap / MDH_RAY_WORDS;
+   *base = r->d_rays.ptr;
+   return MDH_OK;
+}
+extern "C" int32_t mdh_shade_rays(mdh_renderer *r, int32_t n, const float *org, const float *dir, int32_t mode, int32_t tone_map, float *rgb_out,
+                                  int32_t *hit_out, int32_t *index_out, float *t_out, int32_t *steps_out)
+{
+   int rc = shade_rays_check(r, n, org, dir, mode, rgb_out);
+   if (rc != MDH_OK) return rc;
+   {
+      bool ok = true;
+      for (size_t i = 0; i < (size_t)n; ++i) ok = ok && rs_shade_ray_valid(org[3 * i], org[3 * i + 1], org[3 * i + 2], dir[3 * i], dir[3 * i + 1], dir[3 * i + 2]); // (the lanes' predicate)
+      if (!ok) return seterr(MDH_E_INVALID, "a ray is not finite, starts beyond 1024 or has a direction component beyond 2");
+   }
+   if (n == 0) return MDH_OK;
+   hipStream_t qs = nullptr;
+   if ((rc = shade_rays_begin(r, &qs)) != MDH_OK) return rc;
+   float *base = nullptr;
+   size_t cap = 0;
+   if ((rc = rays_buffer(r, (size_t)n, qs, &base, &cap)) != MDH_OK) return rc;
+   RayShadeArgs a;
+   a.n = n; a.tone_map = tone_map ? 1 : 0; a.ao_steps = r->opt_ao; a.spec_mode = r->opt_spec;
+   a.org = base; a.dir = base + 3 * cap;
+   a.hit = (int *)(base + 7 * cap); a.index = (int *)(base + 8 * cap); a.t = base + 9 * cap; a.steps = (int *)(base + 10 * cap);
+   a.rgb = base + 11 * cap;
+   HIP_TRY(hipMemcpyAsync(base, org, (size_t)n * 12, hipMemcpyHostToDevice, qs));
+   HIP_TRY(hipMemcpyAsync(base + 3 * cap, dir, (size_t)n * 12, hipMemcpyHostToDevice, qs));
+   if ((rc = shade_rays_run(r, mode, a, qs, qs)) != MDH_OK) return rc;
+   HIP_TRY(hipMemcpyAsync(rgb_out, a.rgb, (size_t)n * 12, hipMemcpyDeviceToHost, qs));
+   if (hit_out) HIP_TRY(hipMemcpyAsync(hit_out, a.hit, (size_t)n * 4, hipMemcpyDeviceToHost, qs));
+   if (index_out) HIP_TRY(hipMemcpyAsync(index_out, a.index, (size_t)n * 4, hipMemcpyDeviceToHost, qs));
+   if (t_out) HIP_TRY(hipMemcpyAsync(t_out, a.t, (size_t)n * 4, hipMemcpyDeviceToHost, qs));
+   if (steps_out) HIP_TRY(hipMemcpyAsync(steps_out, a.steps, (size_t)n * 4, hipMemcpyDeviceToHost, qs));
+   return ray_query_wait(r);
+}
+extern "C" int32_t mdh_shade_rays_device(mdh_renderer *r, int32_t n, const float *org, const float *dir, int32_t mode, int32_t tone_map, float *rgb_out,
+                                         int32_t *hit_out, int32_t *index_out, float *t_out, int32_t *steps_out, void *stream)
+{
+   int rc = shade_rays_check(r, n, org, dir, mode, rgb_out);
+   if (rc != MDH_OK) return rc;
+   HIP_TRY(hipSetDevice(r->device));
+   const size_t w = (size_t)n * 4;
+   const RayArray arrays[] = {{org, 3 * w, "origins"}, {dir, 3 * w, "directions"}, {rgb_out, 3 * w, "colours"}, {hit_out, w, "hit"},
+                              {index_out, w, "index"}, {t_out, w, "t"}, {steps_out, w, "steps"}};
+   for (const RayArray &ra : arrays)
+      if ((rc = ray_array_check(r, ra)) != MDH_OK) return rc;
+   if (n == 0) return MDH_OK;
+   hipStream_t qs = nullptr;
+   if ((rc = shade_rays_begin(r, &qs)) != MDH_OK) return rc;
+   RayShadeArgs a;
+   a.n = n; a.tone_map = tone_map ? 1 : 0; a.ao_steps = r->opt_ao; a.spec_mode = r->opt_spec;
+   a.org = org; a.dir = dir; a.rgb = rgb_out;
+   a.hit = hit_out; a.index = index_out; a.t = t_out; a.steps = steps_out;
+   return shade_rays_run(r, mode, a, qs, (hipStream_t)stream);
+}
+
+// mdh_camera_rays, mdh_camera_rays_device: the rays of a width x height frame of the current camera (draw_screen.glsl:20-24),
+// computed on the device by the screen kernel's own functions (k_camera_rays, mdh_kernels.h).  They read the camera, by value,
+// and nothing else of the renderer.
+static int camera_rays_check(const mdh_renderer *r, int32_t width, int32_t height, const float *org, const float *dir)
+{
+   if (!r) return seterr(MDH_E_INVALID, "null renderer");
+   if (!org || !dir || width <= 0 || height <= 0 || (long long)width * height > (1ll << 28)) return seterr(MDH_E_INVALID, "bad argument");
+   return MDH_OK;
+}
+static int camera_rays_launch(mdh_renderer *r, int32_t width, int32_t height, float *d_org, float *d_dir, hipStream_t st)
+{
+   PassKernel k;
+   k.family = GK_k_camera_rays;
+   CameraRayArgs a = {width, height, d_org, d_dir};
+   const long n = (long)width * height;
+   const int rc = launch_kernel_ptr(kernel_ptr(k), dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, make_camera(r), a);
+   if (rc != MDH_OK) return rc;
+   HIP_TRY(hipGetLastError());
+   return MDH_OK;
+}
+extern "C" int32_t mdh_camera_rays(mdh_renderer *r, int32_t width, int32_t height, float *org_out, float *dir_out)
+{
+   int rc = camera_rays_check(r, width, height, org_out, dir_out);
+   if (rc != MDH_OK) return rc;
+   HIP_TRY(hipSetDevice(r->device));
+   if (!r->query_stream) HIP_TRY(hipStreamCreateWithFlags(&r->query_stream, hipStreamNonBlocking));
+   hipStream_t qs = r->query_stream;
+   const size_t n = (size_t)width * height;
+   float *base = nullptr;
+   size_t cap = 0;
+   if ((rc = rays_buffer(r, n, qs, &base, &cap)) != MDH_OK) return rc;
+   if ((rc = camera_rays_launch(r, width, height, base, base + 3 * cap, qs)) != MDH_OK) return rc;
+   HIP_TRY(hipMemcpyAsync(org_out, base, n * 12, hipMemcpyDeviceToHost, qs));
+   HIP_TRY(hipMemcpyAsync(dir_out, base + 3 * cap, n * 12, hipMemcpyDeviceToHost, qs));
+   HIP_TRY(hipStreamSynchronize(qs));
+   return MDH_OK;
+}
+extern "C" int32_t mdh_camera_rays_device(mdh_renderer *r, int32_t width, int32_t height, float *org_out, float *dir_out, void *stream)
+{
+   int rc = camera_rays_check(r, width, height, org_out, dir_out);
+   if (rc != MDH_OK) return rc;
+   HIP_TRY(hipSetDevice(r->device));
+   const size_t bytes = (size_t)width * height * 12;
+   const RayArray arrays[] = {{org_out, bytes, "origins"}, {dir_out, bytes, "directions"}};
+   for (const RayArray &ra : arrays)
+      if ((rc = ray_array_check(r, ra)) != MDH_OK) return rc;
+   return camera_rays_launch(r, width, height, org_out, dir_out, (hipStream_t)stream); // (on the caller's stream itself: ordered with it by being there)
+}
+
 // the hierarchy of the committed scene (pending edits are committed first): its nodes, leaves, depth and the length of the
 // always-evaluated list; all 0 while MDH_OPT_TRIANGLE_BVH is off or the scene declares no triangles
 extern "C" int32_t mdh_triangle_bvh_info(mdh_renderer *r, int32_t *nodes, int32_t *leaves, int32_t *depth, int32_t *always)
@@ -4067,6 +4264,7 @@ static const void *kernel_ptr(const PassKernel &k)
 #define MDH_SCR(PF, MODE, ALT) if (k.family == GK_k_screen && k.pf == (PF) && k.mode == MODE && k.alt == ALT && k.rec == 0) return k.gbuf ? (const void *)k_screen<PF, MODE, true, ALT> : (const void *)k_screen<PF, MODE, false, ALT>;
 #define MDH_RQ(PF) if (k.family == GK_k_ray_query && k.pf == (PF)) return k.what == MDH_RQ_RAYCAST ? (const void *)k_ray_query<PF, MDH_RQ_RAYCAST> : k.what == MDH_RQ_VISIBILITY ? (const void *)k_ray_query<PF, MDH_RQ_VISIBILITY> : (const void *)k_ray_query<PF, MDH_RQ_SOFTSHADOW>;
 #define MDH_RS(PF) if (k.family == GK_k_ray_stream && k.pf == (PF)) return k.what == MDH_RQ_RAYCAST ? (const void *)k_ray_stream<PF, MDH_RQ_RAYCAST> : k.what == MDH_RQ_VISIBILITY ? (const void *)k_ray_stream<PF, MDH_RQ_VISIBILITY> : (const void *)k_ray_stream<PF, MDH_RQ_SOFTSHADOW>;
+#define MDH_SH(PF) if (k.family == GK_k_ray_shade && k.pf == (PF) && (k.mode == 0 || k.mode == 2)) return k.mode == 0 ? (const void *)k_ray_shade<PF, 0> : (const void *)k_ray_shade<PF, 2>;
 #define MDH_GTAB(PF) MDH_VIS(PF) MDH_SCAT(PF) MDH_RAD(PF) MDH_SCR(PF, 0, true) MDH_SCR(PF, 0, false) MDH_SCR(PF, 1, false) MDH_SCR(PF, 2, false)
    MDH_RAD(13) MDH_RAD(37) MDH_RAD(5) MDH_RAD(20) MDH_RAD(4) MDH_RAD(16) MDH_RAD(33) MDH_RAD(0) MDH_RAD(1) MDH_RAD(2) MDH_RAD(9) MDH_RAD(3)
    MDH_VIS(0) MDH_VIS(16) MDH_VIS(33) MDH_VIS(1) MDH_VIS(2) MDH_VIS(9) MDH_VIS(3)
@@ -4098,6 +4296,10 @@ static const void *kernel_ptr(const PassKernel &k)
    MDH_RQ(0) MDH_RQ(1) MDH_RQ(9) MDH_RQ(64) MDH_RQ(65) MDH_RQ(73) MDH_RQ(192)
    // ... and the same queries for device arrays, whose lanes take the next ray when theirs has ended (mdh_raycast_device, ..): behind them
    MDH_RS(0) MDH_RS(1) MDH_RS(9) MDH_RS(64) MDH_RS(65) MDH_RS(73) MDH_RS(192)
+   // ... and the pixel program for a host's rays (mdh_shade_rays, mdh_shade_rays_device; mode 0 or 2) with the kernel that hands
+   // out the camera's rays (mdh_camera_rays): the newest last
+   MDH_SH(0) MDH_SH(1) MDH_SH(9) MDH_SH(64) MDH_SH(65) MDH_SH(73) MDH_SH(192)
+   MDH_K(k_camera_rays, 0, k_camera_rays<>)
    return nullptr;
 #undef MDH_K
 #undef MDH_RAD
@@ -4109,4 +4311,5 @@ static const void *kernel_ptr(const PassKernel &k)
 #undef MDH_GTAB
 #undef MDH_RQ
 #undef MDH_RS
+#undef MDH_SH
 }

@@ -1705,6 +1705,119 @@ template <int PART, int WHAT> __global__ __launch_bounds__(MDH_BLOCK) void k_ray
       }
    }
 }
+
+// mdh_shade_rays, mdh_shade_rays_device (mdh_api.hip): the frame's pixel program -- pixel_color_probes,
+// render_probes.glsl:246-291 -- for rays that come from the host, where k_screen feeds it the camera's.  One ray per lane, 64
+// consecutive rays per wavefront; PART is the scene's general variant, as in k_ray_query, MODE the screen mode (0 or 2).
+// shade_structured works with wave-wide ballots and the park rows of its wavefront, so every lane of a wavefront that has a ray
+// goes through it: lanes past n, and lanes whose ray is not shaded, as lane_valid = false.  The marches in there carry no stall
+// guard: a lane tests its ray first (rs_shade_ray_valid, mdh_ray_stream.h: the host-array call's predicate) and the host has
+// tested the scene, which together keep every march parameter below 2^14.  A ray that fails is answered with the quiet NaN in
+// all three colours, hit = -1, index = -1, t = 0, steps = 0.  No volumetrics: a free ray has no screen position to look the
+// fog up by.  stage_table's barrier is the only one.  As in k_screen nothing of the prologue stays live across the pixel
+// program: the ray's index and the arguments the stores need are derived again behind it.
+struct RayShadeArgs {
+   int n;
+   int tone_map;  // 0: the linear colour; 1: draw_screen.glsl:29 on it, as k_screen stores it
+   int ao_steps;  // MDH_OPT_AO_STEPS
+   int spec_mode; // MDH_OPT_INDIRECT_SPECULAR (0 or 2: the bodies of SPEC = 1)
+   const float *org, *dir; // 3 n each
+   float *rgb;             // 3 n
+   int *hit, *index, *steps; // n each, or null
+   float *t;                 // n, or null
+};
+MDH_DEV bool ray_shade_load(const RayShadeArgs &a, long lin, f3 &from, f3 &dir)
+{
+   from = F3(0.0f, 0.0f, 0.0f); dir = F3(0.0f, 0.0f, 0.0f);
+   if (lin >= (long)a.n) return false;
+   const size_t q = (size_t)lin;
+   const float ox = a.org[3 * q], oy = a.org[3 * q + 1], oz = a.org[3 * q + 2];
+   const float dx = a.dir[3 * q], dy = a.dir[3 * q + 1], dz = a.dir[3 * q + 2];
+   if (!rs_shade_ray_valid(ox, oy, oz, dx, dy, dz)) return false;
+   from = F3(ox, oy, oz); dir = F3(dx, dy, dz);
+   return true;
+}
+template <int PART, int MODE> __global__ __launch_bounds__(MDH_BLOCK, MDH_OCC(PART, MODE)) void k_ray_shade(KScene sc, KProbes pr, RayShadeArgs a)
+{
+   static_assert(!(PART & (MDH_PF_CUSTOM | MDH_PF_POW2 | MDH_PF_ROOM | MDH_PF_PSMALL)), "ray queries: the general variants of built-in kinds");
+   static_assert(MODE == 0 || MODE == 2, "the fixed mode, or direct light times occlusion");
+   stage_table(sc); // (the kernel's only barrier)
+   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
+   if (((long)blockIdx.x * (MDH_BLOCK / 64) + wave) * 64 >= (long)a.n) return; // wave-uniform: no ray in this wavefront
+   PH_KERNEL_BEGIN();
+   f3 c;
+   PrimaryHit ph;
+   bool hit;
+   f3 pos;
+   {
+      f3 from, dir;
+      const bool valid = ray_shade_load(a, ((long)blockIdx.x * (MDH_BLOCK / 64) + wave) * 64 + lane, from, dir);
+      MachineCfg cfg; // renderers.adb:136-143
+      cfg.direct_specular = true;
+      cfg.spec_mode = a.spec_mode;
+      cfg.ao_steps = a.ao_steps;
+      c = MDH_SHADE<PART, MODE, 1, false>(sc, pr, cfg, valid, from, dir, ph, hit, pos);
+   }
+   struct KArgs { KScene sc; KProbes pr; RayShadeArgs a; };
+   static_assert(alignof(KScene) == 8 && alignof(KProbes) == 8 && alignof(RayShadeArgs) == 8, "kernel argument alignments");
+   static_assert(__builtin_offsetof(KArgs, pr) == sizeof(KScene) && __builtin_offsetof(KArgs, a) == sizeof(KScene) + sizeof(KProbes), "KArgs is the kernel argument segment of k_ray_shade");
+   typedef const KArgs __attribute__((address_space(4))) *KArgsPtr; // constant address space: scalar loads
+   KArgsPtr ka = (KArgsPtr)__builtin_amdgcn_kernarg_segment_ptr();
+   asm volatile("" : "+s"(ka));
+   RayShadeArgs a2;
+   {
+      typedef const int __attribute__((address_space(4))) *IntPtr;
+      IntPtr pa = (IntPtr)&ka->a;
+      int *da = (int *)&a2;
+#pragma unroll
+      for (int q = 0; q < (int)(sizeof(RayShadeArgs) / 4); ++q) da[q] = pa[q];
+   }
+   // the ray again (the same loads and the same predicate: the same answer)
+   int wave2 = wave;
+   asm volatile("" : "+s"(wave2));
+   const long lin = ((long)blockIdx.x * (MDH_BLOCK / 64) + wave2) * 64 + lane_index_fresh();
+   if (lin >= (long)a2.n) { PH_KERNEL_END(); return; }
+   const size_t q = (size_t)lin;
+   f3 from2, dir2;
+   if (!ray_shade_load(a2, lin, from2, dir2)) { // not shaded
+      const float bad = __uint_as_float(MDH_RS_BAD_BITS);
+      a2.rgb[3 * q] = bad; a2.rgb[3 * q + 1] = bad; a2.rgb[3 * q + 2] = bad;
+      if (a2.hit) a2.hit[q] = -1;
+      if (a2.index) a2.index[q] = -1;
+      if (a2.t) a2.t[q] = 0.0f;
+      if (a2.steps) a2.steps[q] = 0;
+      PH_KERNEL_END();
+      return;
+   }
+   if (a2.tone_map) // draw_screen.glsl:29
+      c = F3(spow(sdiv(c.x, c.x + 1.0f), 0.4545f), spow(sdiv(c.y, c.y + 1.0f), 0.4545f), spow(sdiv(c.z, c.z + 1.0f), 0.4545f));
+   a2.rgb[3 * q] = c.x; a2.rgb[3 * q + 1] = c.y; a2.rgb[3 * q + 2] = c.z;
+   if (a2.hit) a2.hit[q] = hit ? 1 : 0;
+   if (a2.index) a2.index[q] = ph.index;
+   if (a2.t) a2.t[q] = ph.t;
+   if (a2.steps) a2.steps[q] = ph.steps;
+   PH_KERNEL_END();
+}
+
+// mdh_camera_rays, mdh_camera_rays_device: the rays k_screen gives the pixels of a W x H frame (tile_pixel's centre, camera_ray:
+// draw_screen.glsl:20-24), rows top first -- the same operations on the same values, so the frame's rays to the bit
+struct CameraRayArgs {
+   int W, H;
+   float *org, *dir; // 3 W H each
+};
+template <int = 0> __global__ __launch_bounds__(256) void k_camera_rays(KCamera cam, CameraRayArgs a) // (a template: built where it is first named, mdh_api.hip: kernel_ptr)
+{
+   const long lin = (long)blockIdx.x * 256 + threadIdx.x;
+   if (lin >= (long)a.W * a.H) return;
+   const int j = (int)(lin / a.W), i = (int)(lin - (long)j * a.W);
+   const float u = centre(i, a.W);
+   const float v = -centre(j, a.H); // row 0 = top
+   f3 origin, dir;
+   camera_ray(cam, u, v, origin, dir);
+   const size_t q = (size_t)lin;
+   a.org[3 * q] = origin.x; a.org[3 * q + 1] = origin.y; a.org[3 * q + 2] = origin.z;
+   a.dir[3 * q] = dir.x; a.dir[3 * q + 1] = dir.y; a.dir[3 * q + 2] = dir.z;
+}
 #endif
 
 // ---------------------------------------------------------------------- the window's pixels

@@ -1,5 +1,6 @@
 // mdh_ray_stream.h -- what the device-array ray queries (k_ray_stream, mdh_kernels.h; mdh_raycast_device, .., mdh_api.hip)
-// decide without a device: which rays are marched at all, and how a wavefront hands the next rays to its idle lanes.
+// decide without a device: which rays are marched at all, and how a wavefront hands the next rays to its idle lanes -- and
+// which rays mdh_shade_rays and mdh_shade_rays_device shade (k_ray_shade; tests/shade_rays_check.cpp drives that predicate).
 // Plain inline functions, no HIP runtime in them: the kernels include this header, the host's checks call the same
 // predicate (ray_query_check), and tests/ray_stream_check.cpp drives the hand-out on the CPU under the sanitizers.
 //
@@ -39,6 +40,23 @@ MDH_RS_FN bool rs_ray_valid(float ox, float oy, float oz, float dx, float dy, fl
 }
 // the length of a visibility or soft-shadow ray: finite and within the scene's max_dist (any finite value below it, negative ones too)
 MDH_RS_FN bool rs_tmax_valid(float tmax, float max_dist) { return rs_finite(tmax) && tmax <= max_dist; }
+
+// ---------------------------------------------------------------------- which rays are shaded
+// mdh_shade_rays, mdh_shade_rays_device (k_ray_shade, mdh_kernels.h): the marches of the pixel program -- primary, reflection,
+// shadow, cage visibility -- carry no stall guard, so a shaded ray has to keep every march parameter below 2^14, where a step of
+// at least epsilon still moves it ("Shading a host's rays": the derivation).  The ray's half of the bound:
+// every component finite, an origin within MDH_RS_SHADE_EXTENT of 0 along every axis, a direction within MDH_RS_SHADE_DIR.
+// The scene's half (rs_shade_extent_valid of max_dist, of every light's position and of the probe grid's far corner) is the
+// host's check at the call.
+#define MDH_RS_SHADE_EXTENT 1024.0f
+#define MDH_RS_SHADE_DIR 2.0f
+MDH_RS_FN bool rs_within(float x, float bound) { return rs_finite(x) && x >= -bound && x <= bound; } // (a NaN compares false twice; denormals and both zeros are within)
+MDH_RS_FN bool rs_shade_extent_valid(float x) { return rs_within(x, MDH_RS_SHADE_EXTENT); }
+MDH_RS_FN bool rs_shade_ray_valid(float ox, float oy, float oz, float dx, float dy, float dz)
+{
+   return rs_within(ox, MDH_RS_SHADE_EXTENT) && rs_within(oy, MDH_RS_SHADE_EXTENT) && rs_within(oz, MDH_RS_SHADE_EXTENT) &&
+          rs_within(dx, MDH_RS_SHADE_DIR) && rs_within(dy, MDH_RS_SHADE_DIR) && rs_within(dz, MDH_RS_SHADE_DIR);
+}
 
 // ---------------------------------------------------------------------- the hand-out
 MDH_RS_FN int rs_popcount(unsigned long long m) { return __builtin_popcountll(m); }

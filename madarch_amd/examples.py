@@ -218,5 +218,32 @@ def ball_game(Width=1000, Height=1000, Probes=None, Binding=None, Device=0):
     return Ball_Game(Width, Height, Probes, Binding, Device)
 
 
+def fisheye_view(R, Width, Height, Fov=np.pi, Mode=0, Tone_Map=True):
+    """A fisheye view (equidistant projection, `Fov` radians across the inscribed circle) of whatever R renders, through
+    Renderer.Camera_Rays warped on the host and Renderer.Shade_Rays: the pinhole camera of draw_screen.glsl:20-24 cannot
+    see half a sphere, its rays can be bent to.  Frames come first -- the rays see the probes as the last one left them.
+    -> (Height, Width, 3) colours, black outside the circle."""
+    org, _ = R.Camera_Rays(Width, Height)
+    o = org.reshape(Height, Width, 3).astype(np.float64)
+
+    def unit(v):
+        return v / np.linalg.norm(v)
+    # the camera's frame from its own rays: their origins span the image plane, u to the right and v up, both in [-1, 1]
+    centre = o.mean(axis=(0, 1))
+    right = unit(o[:, -1].mean(axis=0) - o[:, 0].mean(axis=0)) if Width > 1 else np.array([1.0, 0.0, 0.0])
+    up = unit(o[0].mean(axis=0) - o[-1].mean(axis=0)) if Height > 1 else np.array([0.0, 1.0, 0.0])
+    forward = np.cross(right, up)
+    u, v = (o - centre) @ right, (o - centre) @ up
+    r = np.hypot(u, v)
+    theta = r * (0.5 * Fov)
+    s = np.sin(theta) / np.maximum(r, 1e-12)
+    drs = (s * u)[..., None] * right + (s * v)[..., None] * up + np.cos(theta)[..., None] * forward
+    eye = np.broadcast_to(centre, drs.shape)
+    out = R.Shade_Rays(eye.reshape(-1, 3).astype(np.float32), drs.reshape(-1, 3).astype(np.float32), Mode=Mode, Tone_Map=Tone_Map)
+    image = out["rgb"].reshape(Height, Width, 3)
+    image[r > 1.0] = 0.0
+    return image
+
+
 SCENES = {"simple_scene": simple_scene, "global_illumination": global_illumination,
           "light_shafts": light_shafts, "obj_mesh": obj_mesh}

@@ -226,6 +226,61 @@ class Renderer:
         """blocks until every device query enqueued so far has ended"""
         self._b.check(self._b.ray_query_wait(self._h))
 
+    # ---- what a ray sees: the frame's pixel program (pixel_color_probes, render_probes.glsl:246-291) along rays of the host's
+    @staticmethod
+    def _shade_mode(Mode):
+        if int(Mode) not in (0, 2):
+            raise ValueError("Mode: rays are shaded in mode 0 or 2, not %s (the normal of mode 1 is Raycast's)" % (Mode,))
+        return int(Mode)
+
+    def Shade_Rays(self, Origins, Directions, Mode=0, Tone_Map=False):
+        """the colour along every ray: {rgb, hit, index, t, steps}.  Mode 0 is the renderer's fixed mode (direct light, the
+        probes' irradiance, the reflection's radiance tap, occlusion; OPT_AO_STEPS and OPT_INDIRECT_SPECULAR as they are set),
+        mode 2 direct light times occlusion.  Linear colour, or with Tone_Map the bits the framebuffer would hold; a miss is
+        the sky along the ray.  No fog, whatever the volumetric settings.  index, t, steps as in Read_Gbuffer."""
+        mode = self._shade_mode(Mode)
+        org, drs, _ = self._rays(Origins, Directions)
+        n = len(org)
+        out = {"rgb": np.zeros((n, 3), np.float32), "hit": np.zeros(n, np.int32), "index": np.zeros(n, np.int32),
+               "t": np.zeros(n, np.float32), "steps": np.zeros(n, np.int32)}
+        self._b.check(self._b.shade_rays(self._h, n, _fp(org), _fp(drs), mode, 1 if Tone_Map else 0, _fp(out["rgb"]), _fp(out["hit"]),
+                                         _fp(out["index"]), _fp(out["t"]), _fp(out["steps"])))
+        return out
+
+    def Shade_Rays_Device(self, Origins, Directions, Rgb, Hit=None, Index=None, T=None, Steps=None, Mode=0, Tone_Map=False, Stream=0, N=None):
+        """Shade_Rays for N rays (default: what Origins holds) in device memory, asynchronous and ordered with `Stream` as
+        Raycast_Device is.  Every output but Rgb may be None.  A ray that is not finite, starts beyond 1024 along an axis or has a
+        direction component beyond 2 is not shaded: NaN in all three colours, hit = -1, index = -1, t = 0, steps = 0."""
+        mode = self._shade_mode(Mode)
+        n = self._ray_count(Origins, N)
+        dev = self._device_array
+        args = [dev(Origins, "Origins", 3 * n, "float32"), dev(Directions, "Directions", 3 * n, "float32")]
+        outs = [dev(Rgb, "Rgb", 3 * n, "float32"), dev(Hit, "Hit", n, "int32", True), dev(Index, "Index", n, "int32", True),
+                dev(T, "T", n, "float32", True), dev(Steps, "Steps", n, "int32", True)]
+        self._b.check(self._b.shade_rays_device(self._h, n, *args, mode, 1 if Tone_Map else 0, *outs, C.c_void_p(int(Stream))))
+
+    @staticmethod
+    def _frame_size(Width, Height):
+        if int(Width) <= 0 or int(Height) <= 0:
+            raise ValueError("a frame of %s x %s pixels" % (Width, Height))
+        return int(Width), int(Height)
+
+    def Camera_Rays(self, Width, Height):
+        """(origins, directions), each (Width * Height, 3): the rays of a Width x Height frame of the current camera, rows top
+        first, computed on the device by the screen pass's own functions -- the frame's rays to the bit"""
+        w, h = self._frame_size(Width, Height)
+        org = np.zeros((w * h, 3), np.float32)
+        drs = np.zeros((w * h, 3), np.float32)
+        self._b.check(self._b.camera_rays(self._h, w, h, _fp(org), _fp(drs)))
+        return org, drs
+
+    def Camera_Rays_Device(self, Width, Height, Origins, Directions, Stream=0):
+        """Camera_Rays into device memory, enqueued on `Stream`"""
+        w, h = self._frame_size(Width, Height)
+        dev = self._device_array
+        org, drs = dev(Origins, "Origins", 3 * w * h, "float32"), dev(Directions, "Directions", 3 * w * h, "float32")
+        self._b.check(self._b.camera_rays_device(self._h, w, h, org, drs, C.c_void_p(int(Stream))))
+
     def Render_Pass(self, Pass):
         self._b.check(self._b.render_pass(self._h, int(Pass)))
 
