@@ -238,6 +238,31 @@ package Madarch_HIP is
       Stream : System.Address) return Status
      with Import, Convention => C, External_Name => "mdh_camera_rays_device";
 
+   --  What light arrives at a point the host owns (madarch_hip.h): pixel_color_probes from the hit on at
+   --  N points that need not lie on a primitive.  Pos, Normal, View_Dir: 3 N floats each (View_Dir is the
+   --  direction the point is seen along); Material_Ids: N ids as Add_Material returns them.  Mode 0,
+   --  2, or 3 (Point_Irradiance: sample_irradiance alone; View_Dir and Material_Ids may be
+   --  Null_Address, Tone_Map 0).  RGB_Out: 3 N floats.  A point that is not finite, lies beyond 1024,
+   --  has a normal or view component beyond 1 or names no material is not shaded: Status 1 for the
+   --  batch of host arrays, NaN for that point of device arrays.
+   Point_Irradiance : constant int := 3;
+
+   function Shade_Points
+     (R : Handle; N : int; Pos, Normal, View_Dir, Material_Ids : System.Address;
+      Mode, Tone_Map : int; RGB_Out : System.Address) return Status
+     with Import, Convention => C, External_Name => "mdh_shade_points";
+
+   function Shade_Points_Device
+     (R : Handle; N : int; Pos, Normal, View_Dir, Material_Ids : System.Address;
+      Mode, Tone_Map : int; RGB_Out : System.Address; Stream : System.Address) return Status
+     with Import, Convention => C, External_Name => "mdh_shade_points_device";
+
+   --  The material id of N primitive indices (the numbering of Read_Gbuffer and Raycast), -1 for -1
+   --  and for an index no primitive has: a lookup on the host.
+   function Primitive_Material
+     (R : Handle; N : int; Index, Material_Out : System.Address) return Status
+     with Import, Convention => C, External_Name => "mdh_primitive_material";
+
    --  One frame on the N GPUs of a node, one process per GPU (madarch_hip.h, mdh_comm_*):
    --  every process creates its Renderer on its own device, rank 0 makes a 128-byte id and
    --  hands it to the others (a file, an environment variable), all call Comm_Init, and

@@ -421,6 +421,34 @@ class Renderer {
    {
       Check(mdh_camera_rays_device(h_.get(), Width, Height, Origins, Directions, Stream));
    }
+   // ---- what light arrives at a point the host owns: pixel_color_probes from the hit on (render_probes.glsl:253-285) at points that
+   // need not lie on a primitive.  View_Dirs: the direction each point is seen ALONG; Material_Ids: what Add_Material returned.
+   // Mode 0 (the fixed mode), 2 (direct light times occlusion) or 3 (MDH_POINT_IRRADIANCE: sample_irradiance alone -- View_Dirs and
+   // Material_Ids may be empty, no tone map).  3 floats a point; never any fog
+   std::vector<float> Shade_Points(const std::vector<float> &Positions, const std::vector<float> &Normals, const std::vector<float> &View_Dirs,
+                                   const std::vector<int32_t> &Material_Ids, int32_t Mode = 0, bool Tone_Map = false) const
+   {
+      const size_t n = Ray_Count(Positions, Normals);
+      if (Mode != MDH_POINT_IRRADIANCE && (View_Dirs.size() != 3 * n || Material_Ids.size() != n)) throw Constraint_Error("one view direction and one material id per point");
+      std::vector<float> Rgb(3 * n);
+      Check(mdh_shade_points(h_.get(), (int32_t)n, Positions.data(), Normals.data(), Mode == MDH_POINT_IRRADIANCE ? nullptr : View_Dirs.data(),
+                             Mode == MDH_POINT_IRRADIANCE ? nullptr : Material_Ids.data(), Mode, Tone_Map ? 1 : 0, Rgb.data()));
+      return Rgb;
+   }
+   // ... for arrays in memory the device addresses, asynchronous and ordered with Stream as Shade_Rays_Device is.  A point that is not
+   // finite, lies beyond 1024, has a normal or view component beyond 1 or names no material: NaN in all three colours
+   void Shade_Points_Device(int32_t N, const float *Positions, const float *Normals, const float *View_Dirs, const int32_t *Material_Ids, float *Rgb,
+                            int32_t Mode = 0, bool Tone_Map = false, void *Stream = nullptr) const
+   {
+      Check(mdh_shade_points_device(h_.get(), N, Positions, Normals, View_Dirs, Material_Ids, Mode, Tone_Map ? 1 : 0, Rgb, Stream));
+   }
+   // the material id of every primitive index (the numbering of Read_Gbuffer and Raycast; -1 for -1): Raycast's hits for Shade_Points
+   std::vector<int32_t> Primitive_Material(const std::vector<int32_t> &Index) const
+   {
+      std::vector<int32_t> Material(Index.size());
+      Check(mdh_primitive_material(h_.get(), (int32_t)Index.size(), Index.data(), Material.data()));
+      return Material;
+   }
    void Update_Partitioning(Partitioning_Update_Method Method = GPU_Fast) const { Check(mdh_update_partitioning(h_.get(), (int32_t)Method)); } // renderers.adb:757-775
    // ---- headless additions
    std::vector<float> Read_Framebuffer() const // replaces Swap_Buffers: H*W*3 floats, row 0 = top

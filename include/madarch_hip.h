@@ -638,6 +638,51 @@ int32_t mdh_camera_rays(mdh_renderer *r, int32_t width, int32_t height, float *o
 int32_t mdh_camera_rays_device(mdh_renderer *r, int32_t width, int32_t height, float *org_xyz_out, float *dir_xyz_out,
                                void *stream);
 
+/* What light arrives at a point the host owns: the lighting of pixel_color_probes (glsl/render_probes.glsl:253-285) from the
+ * hit on, for n points that need not lie on any primitive of the scene -- a host's own rasterised meshes, particles, a light
+ * meter, a lightmap baker.  pos_xyz and normal_xyz (3 n floats each) are the shaded point and its normal, used as given
+ * (not normalised) as the shaders use them; view_dir_xyz (3 n floats) is the shader's `dir`, the direction the point is seen
+ * ALONG, from the eye to the point; material_ids (n) are ids of the renderer's material table, 0-based as mdh_add_material
+ * returns them (a host registers its own materials with the calls it has).
+ *   mode 0      (compute_direct_lighting + compute_indirect_lighting (sample_irradiance, specular_col)) * ambient occlusion,
+ *               with the renderer's MDH_OPT_AO_STEPS and MDH_OPT_INDIRECT_SPECULAR (0 or 2; for 2 the reflection's radiance
+ *               tap, sample_radiance_no_specular, from pos, normal and reflect (view_dir, normal)) and direct specular on
+ *   mode 2      direct light times occlusion, no probes
+ *   mode 3      MDH_POINT_IRRADIANCE: rgb_out = sample_irradiance (pos, normal) (render_probes.glsl:6-69) and nothing else;
+ *               view_dir_xyz and material_ids may be NULL and are not read; tone_map must be 0
+ *   tone_map 1  (modes 0 and 2) draw_screen.glsl:29 applied, as mdh_shade_rays does
+ * NO VOLUMETRICS: never any fog.  A point mdh_raycast found -- its position and normal, the ray's direction, the material
+ * mdh_primitive_material names -- gets the bits mdh_shade_rays gives that ray and the frame gives that pixel.
+ * The contract is mdh_shade_rays': the call runs on the query stream beside the frames in flight, reads the scene committed
+ * at the call, pending edits included, and the atlas set a mdh_render_pass (MDH_PASS_SCREEN) issued at that moment would
+ * read, and edits nothing: the probe-settle run and both replays go on across it.  It marches through the space partition
+ * or the triangle BVH where the scene has one.  n = 0 is MDH_OK without a launch.
+ *   MDH_E_INVALID  a null renderer or required array, n < 0, a mode other than 0, 2 or 3, a tone map in mode 3, and --
+ *                  mdh_shade_points, on the host, the whole batch -- a point that is not shaded (below)
+ *   MDH_E_STATE    a scene with a user-defined kind; an open frame; in modes 0 and 2 MDH_OPT_INDIRECT_SPECULAR 1 or 3, or 2
+ *                  over a mip chain in use; a scene outside the bound of mdh_shade_rays (max_dist, lights, probe grid)
+ * The marches have no step cap and no stall guard, so a point is shaded only inside a bound: every component finite, every
+ * position component at most 1024 in magnitude, every normal and view-direction component at most 1, the material id
+ * inside the table (0 .. 19).  The bound on normals and view directions is TIGHTER than the 2 of a shaded ray's direction:
+ * the reflected direction view - 2 dot (normal, view) normal is as long as |view| (1 + 2 |normal|^2), 7 sqrt 3 for
+ * components of 1 and 50 sqrt 3 for components of 2, and only the former keeps the reflection's hit -- and the shadow and
+ * visibility rays that start there -- below 2^14 ("Lighting a host's points"). */
+#define MDH_POINT_IRRADIANCE 3
+int32_t mdh_shade_points(mdh_renderer *r, int32_t n, const float *pos_xyz, const float *normal_xyz, const float *view_dir_xyz,
+                         const int32_t *material_ids, int32_t mode, int32_t tone_map, float *rgb_out);
+/* The same call for arrays the device addresses, under the contract of mdh_shade_rays_device: asynchronous and ordered with
+ * `stream` (a hipStream_t; NULL: the default stream), mdh_ray_query_wait is the host's wait and mdh_ray_query_time times
+ * the kernel, and where every array lives and ends is checked with hipPointerGetAttributes before anything is launched
+ * (MDH_E_INVALID).  The host cannot look at the points, so the lane that takes a point which is not shaded answers it
+ * without marching: the quiet NaN 0x7fc00000 in all three colours.  Every other point has the bits mdh_shade_points gives. */
+int32_t mdh_shade_points_device(mdh_renderer *r, int32_t n, const float *pos_xyz, const float *normal_xyz,
+                                const float *view_dir_xyz, const int32_t *material_ids, int32_t mode, int32_t tone_map,
+                                float *rgb_out, void *stream);
+/* The material id of primitive index[q] -- the numbering of mdh_read_gbuffer and mdh_raycast -- in the scene as it stands,
+ * pending edits included: a lookup on the host, no launch.  -1 for -1 and for an index no primitive has.  It feeds
+ * mdh_raycast's hits to mdh_shade_points.  MDH_E_STATE: a scene with a user-defined kind (its material is a program). */
+int32_t mdh_primitive_material(mdh_renderer *r, int32_t n, const int32_t *index, int32_t *material_out);
+
 /* accumulated HIP-event time and launch count of one pass (MDH_OPT_TIMING) */
 int32_t mdh_pass_time(mdh_renderer *r, int32_t pass, double *total_ms, int64_t *launches);
 /* MDH_OPT_RADIANCE_REPLAY: the radiance passes launched since mdh_create that marched their rays (`plain`), marched them

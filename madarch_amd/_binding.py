@@ -175,6 +175,11 @@ HIP_ONLY_ABI = {
     "shade_rays_device": (_I, [_P, _I, _P, _P, _I, _I, _P, _P, _P, _P, _P, _P]),
     "camera_rays": (_I, [_P, _I, _I, _P, _P]),
     "camera_rays_device": (_I, [_P, _I, _I, _P, _P, _P]),
+    # the light at n points of the host's (render_probes.glsl:253-285 from the hit on; mode 3: sample_irradiance alone):
+    # (r, n, pos, normal, view_dir, material_ids, mode, tone_map, rgb[, stream]); and the material id of primitive indices
+    "shade_points": (_I, [_P, _I, _P, _P, _P, _P, _I, _I, _P]),
+    "shade_points_device": (_I, [_P, _I, _P, _P, _P, _P, _I, _I, _P, _P]),
+    "primitive_material": (_I, [_P, _I, _P, _P]),
 }
 
 

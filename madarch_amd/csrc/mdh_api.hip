@@ -1796,14 +1796,14 @@ template <typename Args> static int jit_launch(hipFunction_t f, int blocks, int 
 // frames in flight share their CUs' instruction caches (measured: the same kernels at other addresses, each as fast by itself,
 // the headline with frames in flight 0.5 % slower).  The kernels of global residency (MDH_PF_GTAB, mdh_device.h: Geo) come
 // last there: behind everything else they move nothing.
-enum { GK_k_visibility, GK_k_scat_march, GK_k_scattering, GK_k_radiance, GK_k_screen, GK_k_partition_build, GK_k_eval_distance, GK_k_diag_segments, GK_k_ray_query, GK_k_ray_stream, GK_k_ray_shade, GK_k_camera_rays };
+enum { GK_k_visibility, GK_k_scat_march, GK_k_scattering, GK_k_radiance, GK_k_screen, GK_k_partition_build, GK_k_eval_distance, GK_k_diag_segments, GK_k_ray_query, GK_k_ray_stream, GK_k_ray_shade, GK_k_camera_rays, GK_k_point_shade };
 // WHICH KERNEL A PASS RUNS ("One place that picks a pass's kernel"): every template argument of the
 // pass's kernel, computed once by pick_kernel; kernel_name and kernel_ptr turn the same description into the name hiprtc
 // instantiates and into the kernel of this library.
 struct PassKernel {
    int family = -1; // GK_*
    int pf = 0;      // the kernel's MDH_PF_* word
-   int mode = 0;    // k_screen, k_ray_shade: the screen mode, ...
+   int mode = 0;    // k_screen, k_ray_shade: the screen mode (k_point_shade: 0, 2, or 3 for the irradiance alone), ...
    bool gbuf = false, alt = false; // ... the geometry buffer, the variant of the optional specular bodies
    bool small = false;             // k_radiance: SMALL
    int rec = 0;                    // k_radiance, k_screen: REC (0 marches, 1 marches and records, 2 replays the records: rad_replay_pick, scr_replay_pick)
@@ -1832,9 +1832,9 @@ static const void *table_kernel(const mdh_renderer *r, int family, int what = 0)
    if (family == GK_k_eval_distance && r->bvh_active && !k.ada_div) k.pf |= MDH_PF_BVH;
    // the ray queries march as the passes do: through the space partition (its border as a variant of its own) or the triangle
    // BVH where the scene has one -- the general variants, whose bits the census variants share (pick_kernel)
-   if (family == GK_k_ray_query || family == GK_k_ray_stream || family == GK_k_ray_shade) {
+   if (family == GK_k_ray_query || family == GK_k_ray_stream || family == GK_k_ray_shade || family == GK_k_point_shade) {
       k.what = what;
-      if (family == GK_k_ray_shade) { k.what = 0; k.mode = what; } // (mdh_shade_rays: `what` is the call's screen mode, 0 or 2)
+      if (family == GK_k_ray_shade || family == GK_k_point_shade) { k.what = 0; k.mode = what; } // (mdh_shade_rays, mdh_shade_points: `what` is the call's mode)
       if (r->part.enable) k.pf |= MDH_PF_PART | (r->part.border_behavior != 0 ? MDH_PF_FALLBACK : 0);
       if (r->bvh_active) k.pf |= MDH_PF_BVH;
    }
@@ -3854,10 +3854,10 @@ static int shade_rays_check(const mdh_renderer *r, int32_t n, const float *org, 
 }
 // the query stream and the events, the committed scene, the kernel; then the launch between the fences.  `caller`: the stream
 // device arrays are ordered with, or the query stream itself (host arrays: the copies around the launch are the caller's)
-static int shade_rays_run(mdh_renderer *r, int32_t mode, const RayShadeArgs &a, hipStream_t qs, hipStream_t caller)
+// (`kernel`, `lds`: k_ray_shade with the screen pass's rows, or k_point_shade -- mdh_shade_points below -- with its own)
+template <typename Args> static int shade_query_run(mdh_renderer *r, const void *kernel, size_t lds, const Args &a, hipStream_t qs, hipStream_t caller)
 {
    int rc;
-   const void *kernel = table_kernel(r, GK_k_ray_shade, mode);
    if (!kernel) return seterr(MDH_E_INVALID, "no kernel built for this variant");
    if ((rc = join_main(r)) != MDH_OK) return rc;
    r->main_dirty = true;
@@ -3872,7 +3872,7 @@ static int shade_rays_run(mdh_renderer *r, int32_t mode, const RayShadeArgs &a, 
    const unsigned blocks = (unsigned)(((size_t)a.n + MDH_BLOCK - 1) / MDH_BLOCK);
    const bool timed = r->opt_timing && (r->rq_e0 || (r->rq_e0 = get_event(r))) && (r->rq_e1 || (r->rq_e1 = get_event(r)));
    if (timed) HIP_TRY(hipEventRecord(r->rq_e0, qs));
-   if ((rc = launch_kernel_ptr(kernel, dim3(blocks), dim3(MDH_BLOCK), lds_bytes_screen_mode(r, mode), qs, r->ks, pr, a)) != MDH_OK) return rc;
+   if ((rc = launch_kernel_ptr(kernel, dim3(blocks), dim3(MDH_BLOCK), lds, qs, r->ks, pr, a)) != MDH_OK) return rc;
    HIP_TRY(hipGetLastError());
    if (timed) HIP_TRY(hipEventRecord(r->rq_e1, qs));
    r->rq_timed = timed;
@@ -3881,6 +3881,10 @@ static int shade_rays_run(mdh_renderer *r, int32_t mode, const RayShadeArgs &a, 
    HIP_TRY(hipStreamWaitEvent(r->stream, r->ev_sq_done.ev, 0));
    if (caller != qs) HIP_TRY(hipStreamWaitEvent(caller, r->ev_sq_done.ev, 0)); // ... and the answers are there for the caller's stream
    return MDH_OK;
+}
+static int shade_rays_run(mdh_renderer *r, int32_t mode, const RayShadeArgs &a, hipStream_t qs, hipStream_t caller)
+{
+   return shade_query_run(r, table_kernel(r, GK_k_ray_shade, mode), lds_bytes_screen_mode(r, mode), a, qs, caller);
 }
 static int shade_rays_begin(mdh_renderer *r, hipStream_t *qs)
 {
@@ -3952,6 +3956,110 @@ extern "C" int32_t mdh_shade_rays_device(mdh_renderer *r, int32_t n, const float
    a.org = org; a.dir = dir; a.rgb = rgb_out;
    a.hit = hit_out; a.index = index_out; a.t = t_out; a.steps = steps_out;
    return shade_rays_run(r, mode, a, qs, (hipStream_t)stream);
+}
+
+// ------------------------------------------------------------------ lighting a host's points
+// mdh_shade_points, mdh_shade_points_device: the light that arrives at n points of the host's -- pixel_color_probes from the
+// hit on (mode 0), direct light times occlusion (mode 2), or sample_irradiance alone (mode 3) -- through k_point_shade
+// (mdh_kernels.h).  Everything but the kernel and its arrays is mdh_shade_rays': shade_rays_begin, shade_query_run with its
+// fences and its timing, shade_scene_check, ray_array_check, d_rays for host arrays.  Nothing is edited.
+static int shade_points_check(const mdh_renderer *r, int32_t n, const float *pos, const float *normal, const float *view, const int32_t *material,
+                              int32_t mode, int32_t tone_map, const float *rgb)
+{
+   if (!r) return seterr(MDH_E_INVALID, "null renderer");
+   if (!pos || !normal || !rgb || n < 0) return seterr(MDH_E_INVALID, "bad argument");
+   if (mode != 0 && mode != 2 && mode != MDH_POINT_IRRADIANCE) return seterr(MDH_E_INVALID, "points are shaded in mode 0, 2 or 3 (the irradiance alone)");
+   if (mode == MDH_POINT_IRRADIANCE && tone_map != 0) return seterr(MDH_E_INVALID, "the irradiance of mode 3 is not tone-mapped");
+   if (mode != MDH_POINT_IRRADIANCE && (!view || !material)) return seterr(MDH_E_INVALID, "modes 0 and 2 need a view direction and a material id per point");
+   if (has_custom_kinds(r)) return seterr(MDH_E_STATE, "point queries answer scenes of built-in kinds only");
+   if (r->in_frame) return seterr(MDH_E_STATE, "a frame is open");
+   // (the ALT variant of the screen pass, pick_kernel: not built for points either; mode 3 has no reflection)
+   if (mode != MDH_POINT_IRRADIANCE && (r->opt_spec == 1 || r->opt_spec == 3 || (r->opt_spec == 2 && r->opt_mips && r->d_rad_mips[r->last].ptr)))
+      return seterr(MDH_E_STATE, "points are shaded with MDH_OPT_INDIRECT_SPECULAR 0 or 2, the latter without MDH_OPT_RADIANCE_MIPS");
+   return shade_scene_check(r);
+}
+static PointShadeArgs shade_points_args(const mdh_renderer *r, int32_t n, int32_t tone_map)
+{
+   PointShadeArgs a;
+   a.n = n; a.tone_map = tone_map ? 1 : 0; a.ao_steps = r->opt_ao; a.spec_mode = r->opt_spec; a.n_materials = MAX_MATERIALS; a.pad_ = 0;
+   a.pos = a.normal = a.view = nullptr; a.material = nullptr; a.rgb = nullptr;
+   return a;
+}
+static size_t shade_points_lds(const mdh_renderer *r, int32_t mode) { return mode == MDH_POINT_IRRADIANCE ? lds_bytes(r) : lds_bytes_screen_mode(r, mode); } // (mode 3 parks nothing)
+extern "C" int32_t mdh_shade_points(mdh_renderer *r, int32_t n, const float *pos, const float *normal, const float *view, const int32_t *material,
+                                    int32_t mode, int32_t tone_map, float *rgb_out)
+{
+   int rc = shade_points_check(r, n, pos, normal, view, material, mode, tone_map, rgb_out);
+   if (rc != MDH_OK) return rc;
+   {
+      const bool full = mode != MDH_POINT_IRRADIANCE;
+      bool ok = true;
+      for (size_t i = 0; i < (size_t)n; ++i) // (the lanes' predicate)
+         ok = ok && rs_shade_point_valid(pos[3 * i], pos[3 * i + 1], pos[3 * i + 2], normal[3 * i], normal[3 * i + 1], normal[3 * i + 2], full ? view[3 * i] : 0.0f,
+                                         full ? view[3 * i + 1] : 0.0f, full ? view[3 * i + 2] : 0.0f, full ? material[i] : 0, full ? MAX_MATERIALS : 1);
+      if (!ok) return seterr(MDH_E_INVALID, "a point is not finite, lies beyond 1024, has a normal or view component beyond 1, or names no material");
+   }
+   if (n == 0) return MDH_OK;
+   hipStream_t qs = nullptr;
+   if ((rc = shade_rays_begin(r, &qs)) != MDH_OK) return rc;
+   float *base = nullptr;
+   size_t cap = 0;
+   if ((rc = rays_buffer(r, (size_t)n, qs, &base, &cap)) != MDH_OK) return rc;
+   PointShadeArgs a = shade_points_args(r, n, tone_map);
+   a.pos = base; a.normal = base + 3 * cap; a.view = base + 6 * cap; a.material = (const int *)(base + 9 * cap); a.rgb = base + 11 * cap;
+   HIP_TRY(hipMemcpyAsync(base, pos, (size_t)n * 12, hipMemcpyHostToDevice, qs));
+   HIP_TRY(hipMemcpyAsync(base + 3 * cap, normal, (size_t)n * 12, hipMemcpyHostToDevice, qs));
+   if (mode != MDH_POINT_IRRADIANCE) {
+      HIP_TRY(hipMemcpyAsync(base + 6 * cap, view, (size_t)n * 12, hipMemcpyHostToDevice, qs));
+      HIP_TRY(hipMemcpyAsync(base + 9 * cap, material, (size_t)n * 4, hipMemcpyHostToDevice, qs));
+   }
+   if ((rc = shade_query_run(r, table_kernel(r, GK_k_point_shade, mode), shade_points_lds(r, mode), a, qs, qs)) != MDH_OK) return rc;
+   HIP_TRY(hipMemcpyAsync(rgb_out, a.rgb, (size_t)n * 12, hipMemcpyDeviceToHost, qs));
+   return ray_query_wait(r);
+}
+extern "C" int32_t mdh_shade_points_device(mdh_renderer *r, int32_t n, const float *pos, const float *normal, const float *view, const int32_t *material,
+                                           int32_t mode, int32_t tone_map, float *rgb_out, void *stream)
+{
+   int rc = shade_points_check(r, n, pos, normal, view, material, mode, tone_map, rgb_out);
+   if (rc != MDH_OK) return rc;
+   HIP_TRY(hipSetDevice(r->device));
+   const size_t w = (size_t)n * 4;
+   const bool full = mode != MDH_POINT_IRRADIANCE; // (mode 3 reads neither view directions nor material ids: not looked at)
+   const RayArray arrays[] = {{pos, 3 * w, "positions"}, {normal, 3 * w, "normals"}, {full ? view : nullptr, 3 * w, "view directions"},
+                              {full ? material : nullptr, w, "material ids"}, {rgb_out, 3 * w, "colours"}};
+   for (const RayArray &ra : arrays)
+      if ((rc = ray_array_check(r, ra)) != MDH_OK) return rc;
+   if (n == 0) return MDH_OK;
+   hipStream_t qs = nullptr;
+   if ((rc = shade_rays_begin(r, &qs)) != MDH_OK) return rc;
+   PointShadeArgs a = shade_points_args(r, n, tone_map);
+   a.pos = pos; a.normal = normal; a.view = full ? view : nullptr; a.material = full ? (const int *)material : nullptr; a.rgb = rgb_out;
+   return shade_query_run(r, table_kernel(r, GK_k_point_shade, mode), shade_points_lds(r, mode), a, qs, (hipStream_t)stream);
+}
+// the material id of primitive `index` (the numbering of mdh_read_gbuffer and mdh_raycast: the kinds in their declared order,
+// each with its declared count) as the scene's table holds it now, pending edits included; -1 for -1 and for an index no
+// primitive has.  A lookup on the host: what primitive_info (mdh_device.h) reads, without a launch.
+extern "C" int32_t mdh_primitive_material(mdh_renderer *r, int32_t n, const int32_t *index, int32_t *material_out)
+{
+   if (!r) return seterr(MDH_E_INVALID, "null renderer");
+   if (n < 0 || (n > 0 && (!index || !material_out))) return seterr(MDH_E_INVALID, "bad argument");
+   if (has_custom_kinds(r)) return seterr(MDH_E_STATE, "a user-defined kind's material is a program's result: built-in kinds only");
+   for (int32_t q = 0; q < n; ++q) {
+      int32_t m = -1;
+      long rest = index[q];
+      for (int k = 0; k < r->npk && rest >= 0; ++k) {
+         const Kind &kd = r->pk[k];
+         if (rest < kd.max_count) {
+            int count = rd_i(r, kd.count_off);
+            if (count > kd.max_count) count = kd.max_count;
+            if (rest < count) m = rd_i(r, kd.array_off + kd.stride * (int)rest + kd.f_d);
+            break;
+         }
+         rest -= kd.max_count;
+      }
+      material_out[q] = m;
+   }
+   return MDH_OK;
 }
 
 // mdh_camera_rays, mdh_camera_rays_device: the rays of a width x height frame of the current camera (draw_screen.glsl:20-24),
@@ -4265,6 +4373,7 @@ static const void *kernel_ptr(const PassKernel &k)
 #define MDH_RQ(PF) if (k.family == GK_k_ray_query && k.pf == (PF)) return k.what == MDH_RQ_RAYCAST ? (const void *)k_ray_query<PF, MDH_RQ_RAYCAST> : k.what == MDH_RQ_VISIBILITY ? (const void *)k_ray_query<PF, MDH_RQ_VISIBILITY> : (const void *)k_ray_query<PF, MDH_RQ_SOFTSHADOW>;
 #define MDH_RS(PF) if (k.family == GK_k_ray_stream && k.pf == (PF)) return k.what == MDH_RQ_RAYCAST ? (const void *)k_ray_stream<PF, MDH_RQ_RAYCAST> : k.what == MDH_RQ_VISIBILITY ? (const void *)k_ray_stream<PF, MDH_RQ_VISIBILITY> : (const void *)k_ray_stream<PF, MDH_RQ_SOFTSHADOW>;
 #define MDH_SH(PF) if (k.family == GK_k_ray_shade && k.pf == (PF) && (k.mode == 0 || k.mode == 2)) return k.mode == 0 ? (const void *)k_ray_shade<PF, 0> : (const void *)k_ray_shade<PF, 2>;
+#define MDH_PT(PF) if (k.family == GK_k_point_shade && k.pf == (PF) && (k.mode == 0 || k.mode == 2 || k.mode == 3)) return k.mode == 0 ? (const void *)k_point_shade<PF, 0> : k.mode == 2 ? (const void *)k_point_shade<PF, 2> : (const void *)k_point_shade<PF, 3>;
 #define MDH_GTAB(PF) MDH_VIS(PF) MDH_SCAT(PF) MDH_RAD(PF) MDH_SCR(PF, 0, true) MDH_SCR(PF, 0, false) MDH_SCR(PF, 1, false) MDH_SCR(PF, 2, false)
    MDH_RAD(13) MDH_RAD(37) MDH_RAD(5) MDH_RAD(20) MDH_RAD(4) MDH_RAD(16) MDH_RAD(33) MDH_RAD(0) MDH_RAD(1) MDH_RAD(2) MDH_RAD(9) MDH_RAD(3)
    MDH_VIS(0) MDH_VIS(16) MDH_VIS(33) MDH_VIS(1) MDH_VIS(2) MDH_VIS(9) MDH_VIS(3)
@@ -4300,6 +4409,8 @@ static const void *kernel_ptr(const PassKernel &k)
    // out the camera's rays (mdh_camera_rays): the newest last
    MDH_SH(0) MDH_SH(1) MDH_SH(9) MDH_SH(64) MDH_SH(65) MDH_SH(73) MDH_SH(192)
    MDH_K(k_camera_rays, 0, k_camera_rays<>)
+   // ... and the light at a host's own points (mdh_shade_points, mdh_shade_points_device; mode 0, 2 or 3): behind everything older
+   MDH_PT(0) MDH_PT(1) MDH_PT(9) MDH_PT(64) MDH_PT(65) MDH_PT(73) MDH_PT(192)
    return nullptr;
 #undef MDH_K
 #undef MDH_RAD
@@ -4312,4 +4423,5 @@ static const void *kernel_ptr(const PassKernel &k)
 #undef MDH_RQ
 #undef MDH_RS
 #undef MDH_SH
+#undef MDH_PT
 }

@@ -1818,6 +1818,161 @@ template <int = 0> __global__ __launch_bounds__(256) void k_camera_rays(KCamera 
    a.org[3 * q] = origin.x; a.org[3 * q + 1] = origin.y; a.org[3 * q + 2] = origin.z;
    a.dir[3 * q] = dir.x; a.dir[3 * q + 1] = dir.y; a.dir[3 * q + 2] = dir.z;
 }
+
+// mdh_shade_points, mdh_shade_points_device (mdh_api.hip): the light that arrives at points the host owns.  One point per lane,
+// 64 consecutive points per wavefront, k_ray_shade's structure: stage_table's barrier is the only one, every lane of a
+// wavefront that has a point goes through the program (lanes past n and lanes whose point is not shaded as lane_valid =
+// false), nothing of the prologue stays live across the shading, and the stores take their arguments from the kernel argument
+// segment again.  PART is the scene's general variant.  MODE:
+//   0, 2  pixel_color_probes from the hit on (render_probes.glsl:253-285): shade_structured entered at the caller's point
+//         (POINT, mdh_march.h) -- position, normal and material id as given, view_dir the shader's `dir` -- so a point that
+//         mdh_raycast found gets the bits the frame gives its pixel;
+//   3     sample_irradiance (render_probes.glsl:6-69) alone: point_irradiance below, no material, no light, no park rows.
+// A lane tests its point first (rs_shade_point_valid, mdh_ray_stream.h: the host-array call's predicate); a point that fails
+// is answered with the quiet NaN in all three colours and marches nothing.  Never any fog.
+struct PointShadeArgs {
+   int n;
+   int tone_map;    // 0: the linear colour; 1: draw_screen.glsl:29 on it (modes 0 and 2)
+   int ao_steps;    // MDH_OPT_AO_STEPS
+   int spec_mode;   // MDH_OPT_INDIRECT_SPECULAR (0 or 2)
+   int n_materials; // the material table's entries
+   int pad_;
+   const float *pos, *normal; // 3 n each
+   const float *view;         // 3 n (modes 0 and 2)
+   const int *material;       // n (modes 0 and 2)
+   float *rgb;                // 3 n
+};
+// sample_irradiance (render_probes.glsl:6-69) in the oracle's operation order, one cage corner after the other: the weight
+// from the angle, the visibility march from pos + normal * 0.05 * 5 over probe_distance - 0.25, the crush below 0.2, the
+// trilinear factor, the bilinear tap of the irradiance atlas (either format), the square root of the texel; then the division
+// by the total weight and the square, 0 when that weight is 0.  Nothing folded, shared or proved clear: the pixel program's
+// eliminations are exact, so this literal form has their bits, and a host's points are few beside a frame's.
+template <int PART> MDH_DEV f3 point_irradiance(const KScene &sc, const KProbes &pr, f3 pos, f3 normal)
+{
+   const int u8_tab = sc.u8_slot * 4;
+   const i3 gp = world_to_grid(pr, pos);
+   f3 irradiance = F3(0.0f, 0.0f, 0.0f);
+   float total_weight = 0.0f;
+   const f3 alpha = pos / F3(pr.sx, pr.sy, pr.sz) - F3((float)gp.x, (float)gp.y, (float)gp.z);
+   const f3 from_off = pos + (normal * MDH_MIN_STEP) * 5.0f;
+   f2 rid = ray_dir_to_ray_id(normal);
+   rid = F2(clamp_(rid.x, pr.irr_lo, pr.irr_hi), clamp_(rid.y, pr.irr_lo, pr.irr_hi));
+#pragma unroll 1
+   for (int i = 0; i < 8; ++i) {
+      const i3 q = cage_probe(pr, gp, i);
+      const f3 hit_to_probe = grid_to_world(pr, q) - pos;
+      const float probe_distance = length(hit_to_probe);
+      const f3 dir_to_probe = sdiv3(hit_to_probe, probe_distance);
+      const float angle = (dot(dir_to_probe, normal) + 1.0f) * 0.5f;
+      float weight = angle * angle + 0.2f;
+      // raycast_visibility, raymarching.glsl:39-56
+      float vis = 1.0f;
+      {
+         const float vmax = probe_distance - MDH_MIN_STEP * 5.0f;
+         float total = 0.0f;
+         while (total < vmax) {
+            const float sd = sdf<PART>(sc, from_off + dir_to_probe * total);
+            if (sd < MDH_EPS) { vis = 0.0f; break; }
+            total += sd;
+         }
+      }
+      weight *= vis;
+      const float crush = 0.2f;
+      if (weight < crush) weight *= weight * weight * (1.0f / (crush * crush));
+      const f3 tri = F3(mix_(1.0f - alpha.x, alpha.x, (float)(i & 1)), mix_(1.0f - alpha.y, alpha.y, (float)((i >> 1) & 1)),
+                        mix_(1.0f - alpha.z, alpha.z, (float)((i >> 2) & 1)));
+      weight *= tri.x * tri.y * tri.z;
+      const f2 base = probe_id_to_coord(pr, grid_to_probe_id(pr, q));
+      const f3 tx = atlas_sample(pr.irr, pr.fmt, pr.pcx, pr.pcy, pr.ires, pr.ishift, pr.irr_w, pr.irr_h, base.x + div_pcx(pr, rid.x), base.y + div_pcy(pr, rid.y), u8_tab, pr.m_ires);
+      irradiance = irradiance + ssqrt3(tx) * weight;
+      total_weight += weight;
+   }
+   if (total_weight == 0.0f) return F3(0.0f, 0.0f, 0.0f); // (render_probes.glsl:65: 0 / 0 fixed as 0)
+   irradiance = sdiv3(irradiance, total_weight);
+   return irradiance * irradiance;
+}
+template <int MODE> MDH_DEV bool point_shade_load(const PointShadeArgs &a, long lin, f3 &pos, f3 &normal, f3 &view, int &material)
+{
+   pos = F3(0.0f, 0.0f, 0.0f); normal = F3(0.0f, 0.0f, 0.0f); view = F3(0.0f, 0.0f, 0.0f);
+   material = 0;
+   if (lin >= (long)a.n) return false;
+   const size_t q = (size_t)lin;
+   const float px = a.pos[3 * q], py = a.pos[3 * q + 1], pz = a.pos[3 * q + 2];
+   const float nx = a.normal[3 * q], ny = a.normal[3 * q + 1], nz = a.normal[3 * q + 2];
+   float vx = 0.0f, vy = 0.0f, vz = 0.0f;
+   int m = 0;
+   if (MODE != 3) {
+      vx = a.view[3 * q]; vy = a.view[3 * q + 1]; vz = a.view[3 * q + 2];
+      m = a.material[q];
+   }
+   if (!rs_shade_point_valid(px, py, pz, nx, ny, nz, vx, vy, vz, m, MODE != 3 ? a.n_materials : 1)) return false;
+   pos = F3(px, py, pz); normal = F3(nx, ny, nz); view = F3(vx, vy, vz);
+   material = m;
+   return true;
+}
+template <int PART, int MODE> __global__ __launch_bounds__(MDH_BLOCK, MDH_OCC(PART, MODE == 3 ? 2 : MODE)) void k_point_shade(KScene sc, KProbes pr, PointShadeArgs a)
+{
+   static_assert(!(PART & (MDH_PF_CUSTOM | MDH_PF_POW2 | MDH_PF_ROOM | MDH_PF_PSMALL)), "point queries: the general variants of built-in kinds");
+   static_assert(MODE == 0 || MODE == 2 || MODE == 3, "the fixed mode, direct light times occlusion, or the irradiance alone");
+   stage_table(sc); // (the kernel's only barrier)
+   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
+   if (((long)blockIdx.x * (MDH_BLOCK / 64) + wave) * 64 >= (long)a.n) return; // wave-uniform: no point in this wavefront
+   f3 c;
+   if constexpr (MODE == 3) {
+      f3 pos, normal, view;
+      int material;
+      c = F3(0.0f, 0.0f, 0.0f);
+      if (point_shade_load<MODE>(a, ((long)blockIdx.x * (MDH_BLOCK / 64) + wave) * 64 + lane, pos, normal, view, material)) c = point_irradiance<PART>(sc, pr, pos, normal);
+   } else {
+      PH_KERNEL_BEGIN();
+      PrimaryHit ph;
+      bool hit;
+      f3 pos_out;
+      {
+         f3 pos, normal, view;
+         int material;
+         const bool valid = point_shade_load<MODE>(a, ((long)blockIdx.x * (MDH_BLOCK / 64) + wave) * 64 + lane, pos, normal, view, material);
+         MachineCfg cfg; // renderers.adb:136-143
+         cfg.direct_specular = true;
+         cfg.spec_mode = a.spec_mode;
+         cfg.ao_steps = a.ao_steps;
+         c = MDH_SHADE<PART, MODE, 1, false, 0, true, true>(sc, pr, cfg, valid, pos, view, ph, hit, pos_out, RayRecord{0u, 0u, -1, 0u}, RayRecord{0u, 0u, -1, 0u}, normal, material);
+      }
+      PH_KERNEL_END();
+   }
+   struct KArgs { KScene sc; KProbes pr; PointShadeArgs a; };
+   static_assert(alignof(KScene) == 8 && alignof(KProbes) == 8 && alignof(PointShadeArgs) == 8, "kernel argument alignments");
+   static_assert(__builtin_offsetof(KArgs, pr) == sizeof(KScene) && __builtin_offsetof(KArgs, a) == sizeof(KScene) + sizeof(KProbes), "KArgs is the kernel argument segment of k_point_shade");
+   typedef const KArgs __attribute__((address_space(4))) *KArgsPtr; // constant address space: scalar loads
+   KArgsPtr ka = (KArgsPtr)__builtin_amdgcn_kernarg_segment_ptr();
+   asm volatile("" : "+s"(ka));
+   PointShadeArgs a2;
+   {
+      typedef const int __attribute__((address_space(4))) *IntPtr;
+      IntPtr pa = (IntPtr)&ka->a;
+      int *da = (int *)&a2;
+#pragma unroll
+      for (int q = 0; q < (int)(sizeof(PointShadeArgs) / 4); ++q) da[q] = pa[q];
+   }
+   // the point again (the same loads and the same predicate: the same answer)
+   int wave2 = wave;
+   asm volatile("" : "+s"(wave2));
+   const long lin = ((long)blockIdx.x * (MDH_BLOCK / 64) + wave2) * 64 + lane_index_fresh();
+   if (lin >= (long)a2.n) return;
+   const size_t q = (size_t)lin;
+   {
+      f3 pos2, normal2, view2;
+      int material2;
+      if (!point_shade_load<MODE>(a2, lin, pos2, normal2, view2, material2)) { // not shaded
+         const float bad = __uint_as_float(MDH_RS_BAD_BITS);
+         a2.rgb[3 * q] = bad; a2.rgb[3 * q + 1] = bad; a2.rgb[3 * q + 2] = bad;
+         return;
+      }
+   }
+   if (MODE != 3 && a2.tone_map) // draw_screen.glsl:29
+      c = F3(spow(sdiv(c.x, c.x + 1.0f), 0.4545f), spow(sdiv(c.y, c.y + 1.0f), 0.4545f), spow(sdiv(c.z, c.z + 1.0f), 0.4545f));
+   a2.rgb[3 * q] = c.x; a2.rgb[3 * q + 1] = c.y; a2.rgb[3 * q + 2] = c.z;
+}
 #endif
 
 // ---------------------------------------------------------------------- the window's pixels

@@ -479,11 +479,16 @@ MDH_DEV unsigned pixel_record_word2(bool hit, bool traced, int index, int vis_bi
 //   k_radiance <0 | POW2, SMALL, REC = 1>    the brute-force scan's recording kernel, small form: 101 SGPRs, 8 -> 7 wavefronts per SIMD.
 constexpr bool null_brdf_screen(int PART, int MODE, bool GBUF, bool ALT, int REC) { return !(GBUF && PART == MDH_PF_POW2 && MODE == 0 && !ALT && REC == 0); }
 constexpr bool null_brdf_radiance(int PART, bool SMALL, int REC) { return !((PART & ~MDH_PF_POW2) == 0 && SMALL && REC == 1); }
-template <int PART, int MODE, int SPEC, bool QVIS, int REC = 0, bool NULLB = true>
+// POINT (k_point_shade, mdh_kernels.h: mdh_shade_points): the first shaded point is the caller's -- `from` is the point itself,
+// `dir_in` the direction it is seen along, `pt_normal` and `pt_material` what primitive_info would have said -- and context 0
+// runs no primary march, no arg-min scan and no primitive_info: every valid lane "hits" at its point with index -1, t 0 and
+// no steps, and everything from the offset origin on is the code of a marched hit.  false (every other kernel): nothing changes.
+template <int PART, int MODE, int SPEC, bool QVIS, int REC = 0, bool NULLB = true, bool POINT = false>
 MDH_DEV f3 shade_structured(const KScene &sc, const KProbes &pr, const MachineCfg cfg, bool lane_valid, f3 from, f3 dir_in,
                             PrimaryHit &ph, bool &hit, f3 &pos_out, const RayRecord rec = RayRecord{0u, 0u, -1, 0u},
-                            const RayRecord rec2 = RayRecord{0u, 0u, -1, 0u})
+                            const RayRecord rec2 = RayRecord{0u, 0u, -1, 0u}, const f3 pt_normal = F3(0.0f, 0.0f, 0.0f), const int pt_material = 0)
 {
+   static_assert(!POINT || (REC == 0 && SPEC == 1 && !QVIS && MODE != 1), "a caller's point goes through the screen pass's program, mode 0 or 2, without records");
    static_assert(REC == 0 || (SPEC == 0 && QVIS && MODE == 0) || (SPEC == 1 && !QVIS && MODE == 0 && !(PART & MDH_PF_PART) && MDH_SHARE_FIRST_STEP),
                  "records are of the radiance pass's rays or of the screen pass's fixed mode without a space partition");
    constexpr bool SREC = REC != 0 && SPEC == 1; // the screen pass's records
@@ -535,6 +540,10 @@ MDH_DEV f3 shade_structured(const KScene &sc, const KProbes &pr, const MachineCf
             h = (q.word >> 31) != 0u;
             t = __int_as_float((int)q.t);
             steps = (int)(q.word & MDH_REC_STEPS_MASK); // (the second point's are read by nobody)
+         } else if (POINT && ctx == 0) { // the caller's point: nothing to march
+            h = true;
+            t = 0.0f;
+            steps = 0;
          } else
          h = march_plain<PART>(sc, ro, rd, sc.max_dist, t, steps);
          if (REC == 1 && !(SREC && ctx)) park_store1<MDH_PARK_REC + 4>(pk, wb, __int_as_float(steps)); // (hit or miss: the sort key needs them)
@@ -550,15 +559,18 @@ MDH_DEV f3 shade_structured(const KScene &sc, const KProbes &pr, const MachineCf
             if (h) park_store3<MDH_PARK_SPEC>(pk, wb, radiance_with_specular<PART>(sc, pr, pk, wb, ro + rd * t, u8_tab));
          } else
          if (h) {
-            f3 P = ro + rd * t;
+            f3 P = (POINT && ctx == 0) ? ro : ro + rd * t; // (the caller's point as given: its bits, a negative zero included)
             int index = -1;
             f3 N;
             int pm;
             MDH_WORK(3);
+            if (POINT && ctx == 0) { N = pt_normal; pm = pt_material; } // (as given too; ph.index stays -1)
+            else {
             if (REC == 2) index = (SREC && ctx) ? (int)(rec2.word & MDH_REC2_INDEX_MASK) - 1 : rec.index;
             else
             (void)sdf_info<PART>(sc, P, index);
             primitive_info<(PART & MDH_PF_CUSTOM) != 0, (PART & MDH_PF_GTAB) != 0>(sc, index, P, N, pm);
+            }
             if (ctx == 0) {
                park_store1<PARK_MAT>(pk, wb, __int_as_float(pm));
                ph.index = index; ph.t = t;

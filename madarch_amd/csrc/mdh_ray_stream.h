@@ -58,6 +58,25 @@ MDH_RS_FN bool rs_shade_ray_valid(float ox, float oy, float oz, float dx, float 
           rs_within(dx, MDH_RS_SHADE_DIR) && rs_within(dy, MDH_RS_SHADE_DIR) && rs_within(dz, MDH_RS_SHADE_DIR);
 }
 
+// ---------------------------------------------------------------------- which points are shaded
+// mdh_shade_points, mdh_shade_points_device (k_point_shade, mdh_kernels.h; tests/shade_points_check.cpp drives this predicate):
+// the same program from a point of the host's on, so the same requirement -- every march parameter below 2^14 -- with the
+// point's normal and view direction now the host's too ("Lighting a host's points": the derivation).
+// Every component finite, the position within MDH_RS_SHADE_EXTENT of 0 along every axis, the normal and the view direction
+// within MDH_RS_POINT_DIR, the material id inside the table of n_materials entries.  The direction bound is 1, NOT the 2 of a
+// shaded ray: reflect (view, normal) = view - 2 dot (normal, view) normal is as long as |view| (1 + 2 |normal|^2), the
+// reflection's hit lies up to max_dist times that from the point, and with components of 2 that is 86 x 1024 -- with
+// components of 1 it is 7 sqrt 3 x 1024 < 12 416, and the shadow and visibility rays of that hit stay below 15 966 < 2^14.
+// Mode 3 (the irradiance alone) has neither a view direction nor a material: its caller passes zeros.
+#define MDH_RS_POINT_DIR 1.0f
+MDH_RS_FN bool rs_shade_point_valid(float px, float py, float pz, float nx, float ny, float nz, float vx, float vy, float vz, int material, int n_materials)
+{
+   return rs_within(px, MDH_RS_SHADE_EXTENT) && rs_within(py, MDH_RS_SHADE_EXTENT) && rs_within(pz, MDH_RS_SHADE_EXTENT) &&
+          rs_within(nx, MDH_RS_POINT_DIR) && rs_within(ny, MDH_RS_POINT_DIR) && rs_within(nz, MDH_RS_POINT_DIR) &&
+          rs_within(vx, MDH_RS_POINT_DIR) && rs_within(vy, MDH_RS_POINT_DIR) && rs_within(vz, MDH_RS_POINT_DIR) &&
+          material >= 0 && material < n_materials;
+}
+
 // ---------------------------------------------------------------------- the hand-out
 MDH_RS_FN int rs_popcount(unsigned long long m) { return __builtin_popcountll(m); }
 // does a wavefront with n_idle idle lanes take new rays?

@@ -245,5 +245,28 @@ def fisheye_view(R, Width, Height, Fov=np.pi, Mode=0, Tone_Map=True):
     return image
 
 
+def lit_points(R=None, Count=64, Frames=4, Radius=1.6, Binding=None):
+    """A ring of `Count` points the host owns -- no primitive of the scene -- round the sphere of the global_illumination
+    room, normals pointing away from it, seen from the camera, each with a material of the host's own: what light arrives at
+    them after `Frames` frames, through Renderer.Shade_Points in mode 0.  The probes light what the scene never heard of.
+    -> (positions, normals, colours), each (Count, 3); the colours are linear."""
+    own = R is None
+    if own:
+        R = global_illumination(64, 64, Binding=Binding)
+    chalk = R.Add_Material(materials.Create((0.8, 0.8, 0.8), 0.0, 0.9))  # (the host registers its materials with the calls it has)
+    for _ in range(Frames):
+        R.Render()
+    a = np.arange(Count) * (2.0 * np.pi / Count)
+    out = np.stack([np.cos(a), np.zeros(Count), np.sin(a)], axis=1)
+    pos = (np.array([3.0, 4.0, 3.0]) + Radius * out).astype(np.float32)
+    nrm = out.astype(np.float32)
+    view = pos - np.array([2.0, 2.0, 0.0], dtype=np.float32)  # from the eye to the point
+    view = (view / np.linalg.norm(view, axis=1, keepdims=True)).astype(np.float32)
+    rgb = R.Shade_Points(pos, nrm, view, np.full(Count, chalk, np.int32), Mode=0)
+    if own:
+        R.Destroy()
+    return pos, nrm, rgb
+
+
 SCENES = {"simple_scene": simple_scene, "global_illumination": global_illumination,
           "light_shafts": light_shafts, "obj_mesh": obj_mesh}

@@ -281,6 +281,65 @@ class Renderer:
         org, drs = dev(Origins, "Origins", 3 * w * h, "float32"), dev(Directions, "Directions", 3 * w * h, "float32")
         self._b.check(self._b.camera_rays_device(self._h, w, h, org, drs, C.c_void_p(int(Stream))))
 
+    # ---- what light arrives at a point the host owns: pixel_color_probes from the hit on (render_probes.glsl:253-285)
+    POINT_IRRADIANCE = 3
+
+    @staticmethod
+    def _point_mode(Mode, Tone_Map):
+        if int(Mode) not in (0, 2, 3):
+            raise ValueError("Mode: points are shaded in mode 0, 2 or 3 (the irradiance alone), not %s" % (Mode,))
+        if int(Mode) == 3 and Tone_Map:
+            raise ValueError("Tone_Map: the irradiance of mode 3 is not tone-mapped")
+        return int(Mode)
+
+    def Shade_Points(self, Positions, Normals, View_Dirs=None, Material_Ids=None, Mode=0, Tone_Map=False):
+        """(n, 3) colours: the light at every point.  Positions and Normals are used as given; View_Dirs is the direction each
+        point is seen ALONG (from the eye to the point), Material_Ids the ids Add_Material returned.  Mode 0 is the renderer's
+        fixed mode from the hit on (direct light, the probes' irradiance, the reflection's radiance tap, occlusion), mode 2
+        direct light times occlusion, mode 3 sample_irradiance alone (View_Dirs and Material_Ids may be None, no tone map).
+        No fog.  Points beyond 1024, normals or view directions with a component beyond 1 and unknown materials are refused."""
+        mode = self._point_mode(Mode, Tone_Map)
+        pos = np.ascontiguousarray(Positions, dtype=np.float32)
+        nrm = np.ascontiguousarray(Normals, dtype=np.float32)
+        if pos.ndim != 2 or pos.shape[1] != 3 or nrm.shape != pos.shape:
+            raise ValueError("positions and normals are (n, 3) arrays of one shape, not %s and %s" % (pos.shape, nrm.shape))
+        n = len(pos)
+        view = mat = None
+        if mode != 3:
+            if View_Dirs is None or Material_Ids is None:
+                raise ValueError("modes 0 and 2 need View_Dirs and Material_Ids")
+            view = np.ascontiguousarray(View_Dirs, dtype=np.float32)
+            mat = np.ascontiguousarray(Material_Ids, dtype=np.int32)
+            if view.shape != pos.shape or mat.shape != (n,):
+                raise ValueError("one view direction and one material id per point: %s and %s for %d points" % (view.shape, mat.shape, n))
+        rgb = np.zeros((n, 3), np.float32)
+        self._b.check(self._b.shade_points(self._h, n, _fp(pos), _fp(nrm), _fp(view) if view is not None else None,
+                                           _fp(mat) if mat is not None else None, mode, 1 if Tone_Map else 0, _fp(rgb)))
+        return rgb
+
+    def Shade_Points_Device(self, Positions, Normals, View_Dirs, Material_Ids, Rgb, Mode=0, Tone_Map=False, Stream=0, N=None):
+        """Shade_Points for N points (default: what Positions holds) in device memory, asynchronous and ordered with `Stream`
+        as Shade_Rays_Device is.  View_Dirs and Material_Ids may be None in mode 3.  A point that is not shaded (see
+        Shade_Points) is answered with NaN in all three colours."""
+        mode = self._point_mode(Mode, Tone_Map)
+        n = self._ray_count(Positions, N)
+        dev = self._device_array
+        args = [dev(Positions, "Positions", 3 * n, "float32"), dev(Normals, "Normals", 3 * n, "float32"),
+                dev(View_Dirs, "View_Dirs", 3 * n, "float32", mode == 3), dev(Material_Ids, "Material_Ids", n, "int32", mode == 3)]
+        rgb = dev(Rgb, "Rgb", 3 * n, "float32")
+        self._b.check(self._b.shade_points_device(self._h, n, *args, mode, 1 if Tone_Map else 0, rgb, C.c_void_p(int(Stream))))
+
+    def Primitive_Material(self, Index):
+        """the material id of every primitive index (the numbering of Read_Gbuffer and Raycast), -1 for -1 and for an index no
+        primitive has: a lookup on the host, which feeds Raycast's hits to Shade_Points"""
+        idx = np.ascontiguousarray(Index, dtype=np.int32)
+        out = np.full(idx.shape, -1, np.int32)
+        flat = np.ascontiguousarray(idx.reshape(-1))
+        res = np.zeros(len(flat), np.int32)
+        self._b.check(self._b.primitive_material(self._h, len(flat), _fp(flat), _fp(res)))
+        out.reshape(-1)[:] = res
+        return out
+
     def Render_Pass(self, Pass):
         self._b.check(self._b.render_pass(self._h, int(Pass)))
 
