@@ -4328,6 +4328,17 @@ extern "C" int32_t mdh_diag_read(unsigned long long *out16)
    if (hipMemcpyToSymbol(HIP_SYMBOL(g_diag), z, sizeof z) != hipSuccess) return MDH_E_DEVICE;
    return MDH_OK;
 }
+// read and reset the count of wavefront-points that fetched their eight irradiance taps once (MDH_SHARE_TAPS, mdh_march.h),
+// over every launch since the last call; waits for the device
+extern "C" int32_t mdh_diag_shared_taps(unsigned long long *out1)
+{
+   if (!out1) return MDH_E_INVALID;
+   if (hipDeviceSynchronize() != hipSuccess) return MDH_E_DEVICE;
+   if (hipMemcpyFromSymbol(out1, HIP_SYMBOL(g_shared_taps), sizeof(unsigned long long)) != hipSuccess) return MDH_E_DEVICE;
+   const unsigned long long z = 0;
+   if (hipMemcpyToSymbol(HIP_SYMBOL(g_shared_taps), &z, sizeof z) != hipSuccess) return MDH_E_DEVICE;
+   return MDH_OK;
+}
 #endif
 #ifdef MDH_PHASES
 extern "C" int32_t mdh_diag_phases(unsigned long long *out16)

@@ -184,9 +184,17 @@ __device__ unsigned long long g_work[4];
       unsigned long long m_ = __ballot(1);                                                  \
       if ((threadIdx.x & 63) == __ffsll((long long)m_) - 1) atomicAdd(&g_work[slot], (unsigned long long)__popcll(m_)); \
    } while (0)
+// wavefront-points whose eight irradiance taps were fetched once for the wavefront (MDH_SHARE_TAPS, mdh_march.h); a count of
+// its own, summed over launches until mdh_diag_shared_taps takes it: g_work keeps its slots and values
+__device__ unsigned long long g_shared_taps;
+#define MDH_COUNT_SHARED_TAPS()                                                             \
+   do {                                                                                     \
+      if ((threadIdx.x & 63) == __ffsll((long long)__ballot(1)) - 1) atomicAdd(&g_shared_taps, 1ull); \
+   } while (0)
 #else
 #define MDH_DIAG_STEP(type) do { } while (0)
 #define MDH_WORK(slot) do { } while (0)
+#define MDH_COUNT_SHARED_TAPS() do { } while (0)
 #endif
 // ------------------------------------------------------------------------------ vec math
 struct f3 { float x, y, z; };

@@ -191,15 +191,16 @@ __global__ __launch_bounds__(MDH_BLOCK, MDH_OCC(PART, MODE)) void k_screen(KScen
       cfg.spec_mode = a.spec_mode;
       cfg.ao_steps = a.ao_steps;
       constexpr bool NULLB = null_brdf_screen(PART, MODE, GBUF, ALT, REC); // (mdh_march.h: which instantiations shade every light)
+      constexpr bool SHARET = share_taps_screen(PART, GBUF, REC); // (mdh_march.h: which instantiations fetch every lane's taps)
       if (REC == 2) {
          RayRecord rec = {0u, 0u, -1, 0u}, rec2 = {0u, 0u, -1, 0u};
          if (valid) {
             const PixelRecord *q = a.rec + screen_record_index(own, i, j);
             rec = q->first; rec2 = q->second;
          }
-         c = MDH_SHADE<PART, MODE, ALT ? 2 : 1, false, REC, NULLB>(sc, pr, cfg, valid, origin, dir, ph, hit, pos, rec, rec2);
+         c = MDH_SHADE<PART, MODE, ALT ? 2 : 1, false, REC, SHARET, NULLB>(sc, pr, cfg, valid, origin, dir, ph, hit, pos, rec, rec2);
       } else
-      c = MDH_SHADE<PART, MODE, ALT ? 2 : 1, false, REC, NULLB>(sc, pr, cfg, valid, origin, dir, ph, hit, pos);
+      c = MDH_SHADE<PART, MODE, ALT ? 2 : 1, false, REC, SHARET, NULLB>(sc, pr, cfg, valid, origin, dir, ph, hit, pos);
    }
    struct KArgs { KScene sc; KProbes pr; KVolumetrics vol; KCamera cam; ScreenArgs a; };
    // (the kernel argument segment lays the by-value arguments out like this struct: each at its natural alignment, all of
@@ -403,7 +404,7 @@ template <int PART, bool SMALL = false, int REC = 0> __global__ __launch_bounds_
          if (valid) rec = ro.rec[(size_t)(probe_raw - pr.probe_begin) * (pr.rres * pr.rres) + y * pr.rres + x];
          c = MDH_SHADE<PART, 0, 0, true, 2>(sc, pr, cfg, valid, world, ray_dir, ph, hit, pos, rec);
       } else
-      c = MDH_SHADE<PART, 0, 0, MDH_RAD_QVIS != 0, REC, null_brdf_radiance(PART, SMALL, REC)>(sc, pr, cfg, valid, world, ray_dir, ph, hit, pos);
+      c = MDH_SHADE<PART, 0, 0, MDH_RAD_QVIS != 0, REC, true, null_brdf_radiance(PART, SMALL, REC)>(sc, pr, cfg, valid, world, ray_dir, ph, hit, pos);
       if (REC == 1) ph.index = hit ? 1 : 0; // (the one bit of the record that must stay live: in the register of the arg-min, which the pass does not use)
    }
    // The texel again: nothing of the prologue stays live across the pixel program (its coordinates, the order's entry and
@@ -1936,7 +1937,7 @@ template <int PART, int MODE> __global__ __launch_bounds__(MDH_BLOCK, MDH_OCC(PA
          cfg.direct_specular = true;
          cfg.spec_mode = a.spec_mode;
          cfg.ao_steps = a.ao_steps;
-         c = MDH_SHADE<PART, MODE, 1, false, 0, true, true>(sc, pr, cfg, valid, pos, view, ph, hit, pos_out, RayRecord{0u, 0u, -1, 0u}, RayRecord{0u, 0u, -1, 0u}, normal, material);
+         c = MDH_SHADE<PART, MODE, 1, false, 0, true, true, true>(sc, pr, cfg, valid, pos, view, ph, hit, pos_out, RayRecord{0u, 0u, -1, 0u}, RayRecord{0u, 0u, -1, 0u}, normal, material);
       }
       PH_KERNEL_END();
    }

@@ -25,6 +25,9 @@
 #ifndef MDH_TWIN_PREV
 #define MDH_TWIN_PREV 1
 #endif
+#ifndef MDH_SHARE_TAPS
+#define MDH_SHARE_TAPS 1 // a wavefront whose points share cage cell and normal fetches its eight irradiance taps once (shade_structured)
+#endif
 
 struct MachineCfg {
    bool direct_specular;   // M_COMPUTE_DIRECT_SPECULAR
@@ -152,6 +155,11 @@ template <int PART> MDH_DEV bool march_plain(const KScene &sc, f3 o, f3 d, float
 // texel of N
 #define MDH_PARK_ALPHA 12
 #define MDH_PARK_RIDN 15
+// ... and row 17, the one row of the reflection's colour that alpha and the texel leave free (12-14 and 15-16 are theirs), holds
+// what a wavefront shares across its lanes there (MDH_SHARE_TAPS): sqrt(irradiance tap) of the eight cage probes, [corner][3]
+// in the wavefront's first 24 columns.  Every lane reads every column: plain LDS accesses, ordered like queued_visibility's rows.
+#define MDH_PARK_TAPS 17
+typedef __attribute__((address_space(3))) float *ParkLds; // (row r, column c of a wavefront: park_wave_base + (r * MDH_BLOCK + c) * 4)
 #define MDH_SCR_PARK_ROWS MDH_PARK_DWORDS
 MDH_DEV float *park_base(const KScene &sc) { return (float *)(s_tab + sc.table_f4 + sc.part_bits_f4); }
 // A thread's own column of the park rows is addressed WITHOUT an address register: ds_write_addtid_b32 /
@@ -479,11 +487,25 @@ MDH_DEV unsigned pixel_record_word2(bool hit, bool traced, int index, int vis_bi
 //   k_radiance <0 | POW2, SMALL, REC = 1>    the brute-force scan's recording kernel, small form: 101 SGPRs, 8 -> 7 wavefronts per SIMD.
 constexpr bool null_brdf_screen(int PART, int MODE, bool GBUF, bool ALT, int REC) { return !(GBUF && PART == MDH_PF_POW2 && MODE == 0 && !ALT && REC == 0); }
 constexpr bool null_brdf_radiance(int PART, bool SMALL, int REC) { return !((PART & ~MDH_PF_POW2) == 0 && SMALL && REC == 1); }
+// SHARET: a wavefront's eight irradiance taps fetched once where its lanes share them (MDH_SHARE_TAPS, at the first point's corner
+// loop); false where the caller's kernel would pay for it with scratch memory.  Every screen kernel that takes it keeps its
+// wavefronts per SIMD; the eight below gained 16 bytes of scratch per lane and keep the code they had (resource_usage.sh, before
+// against after):
+//   k_screen <0, 0, no GBUF, REC 0>              brute-force scan, marching:                      16 -> 32
+//   k_screen <ROOM, 0, GBUF and no GBUF, REC 2>  the rooms' census, replaying:                    64 -> 80, 48 -> 80
+//   k_screen <ROOM | POW2, 0, no GBUF, REC 1>    ... with power-of-two atlases, recording:        32 -> 48
+//   k_screen <ROOM | POW2, 0, GBUF, REC 0 and 1> ... with the geometry buffer:                    48 -> 64, 64 -> 80
+//   k_screen <POW2, 0, GBUF, REC 0 and 1>        brute-force scan, power-of-two atlases, GBUF:    32 -> 48
+constexpr bool share_taps_screen(int PART, bool GBUF, int REC)
+{
+   return !((PART == 0 && !GBUF && REC == 0) || (PART == MDH_PF_ROOM && REC == 2) || (PART == (MDH_PF_ROOM | MDH_PF_POW2) && !GBUF && REC == 1) ||
+            (PART == (MDH_PF_ROOM | MDH_PF_POW2) && GBUF && REC != 2) || (PART == MDH_PF_POW2 && GBUF && REC != 2));
+}
 // POINT (k_point_shade, mdh_kernels.h: mdh_shade_points): the first shaded point is the caller's -- `from` is the point itself,
 // `dir_in` the direction it is seen along, `pt_normal` and `pt_material` what primitive_info would have said -- and context 0
 // runs no primary march, no arg-min scan and no primitive_info: every valid lane "hits" at its point with index -1, t 0 and
 // no steps, and everything from the offset origin on is the code of a marched hit.  false (every other kernel): nothing changes.
-template <int PART, int MODE, int SPEC, bool QVIS, int REC = 0, bool NULLB = true, bool POINT = false>
+template <int PART, int MODE, int SPEC, bool QVIS, int REC = 0, bool SHARET = true, bool NULLB = true, bool POINT = false>
 MDH_DEV f3 shade_structured(const KScene &sc, const KProbes &pr, const MachineCfg cfg, bool lane_valid, f3 from, f3 dir_in,
                             PrimaryHit &ph, bool &hit, f3 &pos_out, const RayRecord rec = RayRecord{0u, 0u, -1, 0u},
                             const RayRecord rec2 = RayRecord{0u, 0u, -1, 0u}, const f3 pt_normal = F3(0.0f, 0.0f, 0.0f), const int pt_material = 0)
@@ -506,6 +528,10 @@ MDH_DEV f3 shade_structured(const KScene &sc, const KProbes &pr, const MachineCf
    // the x-twin's probe term kept for the corner behind it (item 6 of "Exact work elimination") -- not in the space-partition
    // variants, where its four registers across the visibility march are scratch memory
    constexpr bool TWIN_PREV = MDH_TWIN_PREV != 0 && !(PART & MDH_PF_PART);
+   // the first point's eight irradiance taps fetched once per wavefront where its lanes share them (item 15 of "Exact work
+   // elimination", at the corner loop below): the screen family's fixed mode over the built-in scans only -- every other
+   // instantiation is the code it was
+   constexpr bool SHARE_TAPS = MDH_SHARE_TAPS != 0 && SHARET && SPEC == 1 && !QVIS && MODE == 0 && TAP_EARLY && (PART & ~(MDH_PF_ROOM | MDH_PF_POW2)) == 0;
    // the space-partition variants of the screen pass: the shaded point and its normal come back from park rows behind every
    // corner's visibility march (the second point's wait in the rows of its colour and in three rows of their own) and the probe's grid position is derived again there:
    // the lookups of that march need the registers -- kept live across it, these values went to scratch memory eight times per
@@ -702,6 +728,46 @@ MDH_DEV f3 shade_structured(const KScene &sc, const KProbes &pr, const MachineCf
                         park_store1<MDH_PARK_RIDN + 1>(pk, wb, rid_n.y);
                      }
                   }
+                  // The irradiance tap of corner i reads the atlas at a place that the probe -- cage_probe (pq, gp, i) -- and the
+                  // clamped texel of N decide, and nothing else of the point does.  An 8x8 tile on a wall, the floor or a box
+                  // face has one N, bit for bit, and mostly one cage cell: its 64 lanes would compute the same eight taps.  Where
+                  // every lane here holds the first one's gp and the first one's bits of N (-0 is not +0; a NaN is itself), the
+                  // wavefront computes them in ONE pass, the lane of rank r among the active ones taking corner r & 7, and every
+                  // corner reads its triple from the wavefront's row.  No bit changes: every input of corner i's tap is equal in
+                  // all lanes by that test, rid_n included (a function of N and the probe parameters); the statements are the
+                  // loop's own, in its order, nothing contracted; a value does not depend on the lane that computes it; and the
+                  // sum acc + s_term * weight keeps its order i = 0 .. 7 and its per-lane weights.  A corner folded onto an
+                  // earlier one names that one's probe (the clamp of cage_probe), so its slot holds that probe's value.
+                  bool shared = false;
+                  if (SHARE_TAPS && ctx == 0) {
+                     const unsigned long long act = __ballot(true);
+                     const int nx = __float_as_int(N.x), ny = __float_as_int(N.y), nz = __float_as_int(N.z);
+                     const bool same = gp.x == __builtin_amdgcn_readfirstlane(gp.x) && gp.y == __builtin_amdgcn_readfirstlane(gp.y) &&
+                                       gp.z == __builtin_amdgcn_readfirstlane(gp.z) && nx == __builtin_amdgcn_readfirstlane(nx) &&
+                                       ny == __builtin_amdgcn_readfirstlane(ny) && nz == __builtin_amdgcn_readfirstlane(nz);
+                     shared = __popcll(act) >= 8 && __ballot(same) == act;
+                     if (shared) {
+                        MDH_COUNT_SHARED_TAPS();
+                        const int rank = (int)__builtin_amdgcn_mbcnt_hi((unsigned)(act >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)act, 0u));
+                        const int c = rank & 7;
+                        const KProbes pq = probes_fresh(pr);
+                        const i3 q = cage_probe(pq, gp, c);
+                        const f2 base = probe_id_to_coord<P2>(pq, grid_to_probe_id<P2>(pq, q));
+                        const AtlasTap tap = atlas_tap_issue<P2>(pq.irr, pq.fmt, pq.pcx, pq.pcy, pq.ires, pq.ishift, pq.irr_w, pq.irr_h, base.x + div_pcx<P2>(pq, rid_n.x), base.y + div_pcy<P2>(pq, rid_n.y), pq.m_ires);
+                        const f3 tx = atlas_tap_resolve(pq.irr, pq.fmt, tap, u8_tab);
+                        f3 s;
+                        if (pq.fmt == 0 && !MDH_HYBRID_NUMERICS) s = F3(sqrt_unscaled_(tx.x), sqrt_unscaled_(tx.y), sqrt_unscaled_(tx.z));
+                        else
+                        s = ssqrt3(tx);
+                        if (rank < 8) {
+                           const ParkLds slot = (ParkLds)(unsigned)(wb + (MDH_PARK_TAPS * MDH_BLOCK + 3 * c) * 4);
+                           slot[0] = s.x; slot[1] = s.y; slot[2] = s.z;
+                        }
+                        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+                        __builtin_amdgcn_wave_barrier();
+                        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+                     }
+                  }
                   // A corner folded onto its twin along x follows it directly (i - 1): the twin's probe term -- direction,
                   // visibility, weight before the trilinear factor, irradiance tap -- is this corner's, value for value,
                   // and is still in registers.  (Twins along y and z are two and four corners back: a ring of terms in LDS for
@@ -730,7 +796,7 @@ MDH_DEV f3 shade_structured(const KScene &sc, const KProbes &pr, const MachineCf
                      // the irradiance tap of this corner (render_probes.glsl:44-58) depends on the probe and
                      // N only: its texel loads go out now and land while the visibility ray is marched
                      AtlasTap tap;
-                     if (TAP_EARLY && irrp) {
+                     if (TAP_EARLY && irrp && !(SHARE_TAPS && shared)) { // (a sharing wavefront holds no tap across the march)
                         const f2 rid = parked ? park_load2<MDH_PARK_RIDN>(pk, wb) : rid_n;
                         const f2 base = probe_id_to_coord<P2>(pq, grid_to_probe_id<P2>(pq, q));
                         tap = atlas_tap_issue<P2>(pq.irr, pq.fmt, pq.pcx, pq.pcy, pq.ires, pq.ishift, pq.irr_w, pq.irr_h, base.x + div_pcx<P2>(pq, rid.x), base.y + div_pcy<P2>(pq, rid.y), pq.m_ires);
@@ -794,6 +860,10 @@ MDH_DEV f3 shade_structured(const KScene &sc, const KProbes &pr, const MachineCf
                         const float crush = 0.2f;
                         if (weight < crush) weight *= weight * weight * (1.0f / (crush * crush));
                         wpre = weight;
+                        if (SHARE_TAPS && shared) { // the wavefront's value of corner i: one address for all lanes, a broadcast read
+                           const ParkLds slot = (ParkLds)(unsigned)(wb + (MDH_PARK_TAPS * MDH_BLOCK + 3 * i) * 4); // (from the scalar that is live anyway)
+                           s_term = F3(slot[0], slot[1], slot[2]);
+                        } else {
                         f3 tx;
                         if (TAP_EARLY) tx = atlas_tap_resolve(pq.irr, pq.fmt, tap, u8_tab);
                         else { // (the space-partition variants: the tap's eight registers do not live across the visibility march)
@@ -808,6 +878,7 @@ MDH_DEV f3 shade_structured(const KScene &sc, const KProbes &pr, const MachineCf
                         if (pq.fmt == 0 && !MDH_HYBRID_NUMERICS) s_term = F3(sqrt_unscaled_(tx.x), sqrt_unscaled_(tx.y), sqrt_unscaled_(tx.z));
                         else
                         s_term = ssqrt3(tx);
+                        }
                      } else { // render_probes.glsl:170-183; probe_to_spec = -vd
                         float weight = dot(-vd, -N);
                         weight *= vis;
