@@ -1,4 +1,5 @@
-"""The cases of test_ref64_oracle.py (the oracle) and test_gpu_ref64.py (the HIP library): each is one plain scene
+"""The cases of test_ref64_oracle.py and test_ref64_partition_oracle.py (the oracle) and of test_gpu_ref64.py,
+test_gpu_ref64_passes.py and test_gpu_ref64_partition.py (the HIP library): each is one plain scene
 description, built once as a renderer over the binding under test and once as ref64's float64 scene, and held by
 ref64.hold.  The float64 results are cached per process, so the two files never compute a case twice in one run."""
 import numpy as np
@@ -87,8 +88,12 @@ def describe(scene, camera="identity", ao=3, spec=2, **kw):
 def make_renderer(desc, W, H, binding, mode=0, atlas=1):
     """the description through the host API; nothing here is shared with ref64"""
     assert desc["max_dist"] == 20.0  # scenes.ads:51, the default every case keeps
+    pt = desc.get("partition")
+    partitioning = scenes.Partitioning_Settings(Enable=False) if pt is None else scenes.Partitioning_Settings(
+        Enable=True, Index_Count=pt["index_count"], Border_Behavior={"Clamp": scenes.Clamp, "Fallback": scenes.Fallback}[pt["border"]],
+        Grid_Dimensions=pt["dims"], Grid_Spacing=pt["spacing"], Grid_Offset=pt["offset"])
     scene = scenes.Compile([(KINDS[k][0], n) for k, n in desc["kinds"]], [(LIGHTS[k][0], n) for k, n in desc["light_kinds"]],
-                           Partitioning=scenes.Partitioning_Settings(Enable=False))
+                           Partitioning=partitioning)
     volumetrics = desc["vol"]["settings"] if desc.get("vol") else renderers.No_Volumetrics
     R = renderers.Create(windows.Open(W, H, "ref64"), scene, Probes=desc["probes"]["settings"], Volumetrics=volumetrics, Binding=binding)
     for i, (a, m, r) in enumerate(desc["materials"]):
@@ -521,3 +526,301 @@ def run_distance(binding, name, kinds, count=None, seed=SEED % 1000 + 11, prepar
     R.Destroy()
     assert len(dist) == len(pts)
     return hold_distances(name, desc, kinds, pts, dist, nrm)
+
+
+# ---------------------------------------------------------------------------------------- the space partition
+SIMPLE_SPHERES = [(x, y, z) for y, z, xs in ((3.5, 2.0, (0.5, 1.5, 2.5, 3.5, 4.5, 5.5)), (0.5, 2.0, (0.5, 1.5, 2.5, 3.5, 4.5, 5.5)),
+                                             (3.5, 5.0, (0.5, 1.5, 2.5, 3.5, 4.5, 5.5)), (0.5, 5.0, (0.5, 1.5))) for x in xs]
+MORE_SPHERES = [(x, 0.5, 5.0) for x in (2.5, 3.5, 4.5, 5.5)] + [(x, 2.0, 3.5) for x in (0.5, 1.5, 2.5, 3.5, 4.5, 5.5)] + [
+    (x, 5.5, 3.5) for x in (0.5, 1.5, 2.5, 3.5)]
+SIMPLE_BOXES = [((3.0, 1.0, 2.0), (0.5, 0.5, 0.5)), ((0.0, 1.0, 2.0), (0.3, 0.3, 0.5)), ((3.0, 1.0, 4.0), (0.5, 0.5, 0.5)),
+                ((4.0, 2.0, 2.0), (0.5, 0.5, 0.5)), ((2.0, 2.0, 2.0), (0.5, 0.5, 0.5)), ((1.0, 1.0, 6.0), (0.5, 0.5, 0.5)),
+                ((3.0, 1.0, 6.0), (0.5, 0.5, 0.5))]
+SMALL_TRIANGLES = [((2.8, 2.6, 3.0), (3.2, 2.6, 3.1), (3.0, 3.0, 3.05)), ((1.0, 2.2, 3.5), (1.4, 2.2, 3.6), (1.2, 2.6, 3.5))]
+
+
+def rows(variant="plain", probes=SMALL_PROBES):
+    """The simple_scene example's room (examples/simple_scene/main.adb): its planes, its 20 spheres in rows and the first seven
+    of its boxes, under its point light, seen by a rotated camera.  Variants: "34 spheres" of 40 declared (more than 32 of a
+    kind, 70 declared primitives: three mask words in the library's bit form), "triangles" (two small ones, declared and
+    added), "two radii" (the spheres alternate between 0.5 and 0.2)."""
+    assert variant in ("plain", "34 spheres", "triangles", "two radii")
+    kinds = [("Sphere", 40 if variant == "34 spheres" else 20), ("Plane", 10), ("Box", 20)]
+    centres = SIMPLE_SPHERES + (MORE_SPHERES if variant == "34 spheres" else [])
+    prims = [("Plane", n, o, m) for n, o, m in ROOM_PLANES]
+    prims += [("Sphere", c, 0.2 if variant == "two radii" and i % 2 else 0.5, 3) for i, c in enumerate(centres)]
+    prims += [("Box", c, s, 2) for c, s in SIMPLE_BOXES]
+    if variant == "triangles":
+        kinds.append(("Triangle", 2))
+        prims += [("Triangle", a, b, c, 1) for a, b, c in SMALL_TRIANGLES]
+    return {"kinds": kinds, "prims": prims, "light_kinds": [("point", 4)], "lights": [("point", (0.0, 3.0, 0.0), (0.9, 0.9, 0.9))],
+            "materials": [((0.0, 0.0, 0.0), 0.0, 0.6), ((1.0, 0.0, 0.0), 0.0, 0.6), ((0.0, 0.0, 1.0), 0.0, 0.6), ((0.1, 0.1, 0.1), 0.9, 0.1)],
+            "max_dist": 20.0, "cam_pos": (3.0, 2.5, -0.5), "cam_m": rotation(), "ao_steps": 3, "spec_mode": 2, "probes": probes_of(probes)}
+
+
+# dims, spacing, offset.  A: inside the room, no power of two anywhere.  B: power-of-two spacing (the library's small form).
+# C: odd dims (GPU_Fast visits 6 x 4 x 8 of its cells and writes their records with those sizes).  D: A with more than six
+# digits, so that the lookup (six-digit text) and the CPU builders (binary32) read different numbers.  E: simple_scene's own.
+# The offsets of A .. D keep the cell centres off the scene's half-integer lattice: over E as it stands, several per cent
+# of the cells have a primitive within rounding of the builder's threshold.  F, with the scene "ties", is ON a lattice on purpose:
+# its diagonal is 1.5 exactly, every centre and distance is computed without rounding, and in the cells (0, 0, z) the wall's
+# distance, 2, EQUALS the floor's 0.5 + the diagonal: `dist < threshold` must leave the wall out.
+GRIDS = {"A": ((6, 5, 7), (0.7, 0.6, 0.9), (0.37, 0.21, 0.53)), "B": ((8, 6, 12), (0.5, 0.5, 0.5), (0.37, 0.21, 0.53)),
+         "C": ((7, 5, 9), (0.7, 0.6, 0.9), (0.37, 0.21, 0.53)), "D": ((6, 5, 7), (0.7071068, 0.6180340, 0.9), (0.3700004, 0.21, 0.53)),
+         "E": ((10, 10, 20), (1.0, 1.0, 1.0), (-1.5, -1.5, -10.0)), "F": ((4, 2, 2), (0.5, 1.0, 1.0), (0.0, 0.0, 0.0))}
+METHODS = {"CPU_Best": renderers.CPU_Best, "CPU_Fast": renderers.CPU_Fast, "GPU_Fast": renderers.GPU_Fast}
+AMBIGUOUS_CAP = 0.05
+
+
+def partition_scene(scene, grid, border="Clamp", index_count=20):
+    """`scene`: "room" (the radiance pass's, both lights) or a variant of rows"""
+    if scene == "room":
+        desc = room(lights=(("point", (1.5, 5.5, 4.5), (0.6, 0.5, 0.4)), SPOT), clear_of_probes=True)
+    elif scene == "ties":
+        desc = rows("plain")
+        desc["prims"] = [("Plane", (0.0, 1.0, 0.0), 0.0, 0), ("Plane", (1.0, 0.0, 0.0), 1.75, 1), ("Sphere", (10.0, 10.0, 10.0), 0.5, 3)]
+    else:
+        desc = rows(scene)
+    dims, spacing, offset = GRIDS[grid]
+    desc["partition"] = {"dims": dims, "spacing": spacing, "offset": offset, "index_count": index_count, "border": border}
+    return desc
+
+
+def check_table(R, name, key, desc, method, overflow=False, ties=False):
+    """the table of renderer R against ref64.partition_build: every unambiguous record exactly, and the warnings"""
+    build = cached(("table",) + key, lambda: ref64.partition_build(desc, method))
+    got = R.Read_Partitioning()
+    share = float(build.ambiguous.mean())
+    print("%s: %d records, ambiguous share %.4f (%d), %d overflow, %d warnings" % (
+        name, len(got), share, int(build.ambiguous.sum()), int(build.overflow.sum()), build.warnings))
+    assert share <= AMBIGUOUS_CAP, "%s: %.4f of the records are ambiguous in float64 alone" % (name, share)
+    if overflow:
+        assert (build.overflow & ~build.ambiguous).any(), "%s: no unambiguous record overflows" % name
+    if ties:
+        assert build.ties > 0 and not build.ambiguous.any(), "%s: %d exact ties" % (name, build.ties)
+    assert got.shape == build.table.shape
+    bad = (got != build.table).any(axis=1) & ~build.ambiguous
+    assert not bad.any(), "%s: %d records differ, first %d: got %s, float64 %s" % (
+        name, bad.sum(), np.argwhere(bad)[0][0], got[bad][0].tolist(), build.table[bad][0].tolist())
+    assert R.Partition_Warnings() == build.warnings, "%s: %d warnings, float64 %d" % (name, R.Partition_Warnings(), build.warnings)
+    return got
+
+
+def run_partition_table(binding, name, scene, grid, method, border="Clamp", index_count=20, overflow=False, prepare=None, ties=False):
+    """Update_Partitioning (method) through the binding, the table read back and held by check_table.  `overflow`: the case
+    is meant to cut lists (some unambiguous record must).  `ties`: the case is meant to have distances EQUAL to the threshold."""
+    desc = partition_scene(scene, grid, border, index_count)
+    R = make_renderer(desc, 8, 8, binding)
+    if prepare is not None:
+        prepare(R)
+    R.Update_Partitioning(Method=METHODS[method])
+    check_table(R, name, (scene, grid, method, index_count), desc, method, overflow, ties)
+    R.Destroy()
+
+
+def differs(a, b, rtol, atol):
+    """per pixel: two float64 frames differ by more than the frame test would let pass"""
+    return (a["hit"] != b["hit"]) | (a["index"] != b["index"]) | (np.abs(a["t"] - b["t"]) > ref64.T_ATOL) | ~(
+        np.abs(a["colour"] - b["colour"]) <= atol + rtol * np.abs(b["colour"])).all(axis=-1)
+
+
+def run_partition_screen(binding, name, scene, grid, method, mode, prepare=None, border="Clamp", W=36, H=24, negative=False, variant=None):
+    """One screen pass marched through a table (modes 1 and 2: one Render; mode 0: Render_Pass (PASS_SCREEN) over written
+    atlases, as run_screen).  First the table the binding builds is held by check_table.  Then the float64 frames are
+    computed over the table READ BACK from the binding: the frame test so holds the lookup and the march on every record,
+    also where the builders' decision was ambiguous and check_table had to let the record pass.
+    Two conditions on the float64 side alone come first: the table must change the frame (more than 10 % of the pixels differ
+    from the same frame without the partition -- a grid that covers the scene proves nothing about the lookup), and with
+    `negative` some soft-shadow step must have a negative radicand.  (A frame of fewer than 100 pixels cannot show a share of
+    10 %; the one-pixel case prints its figure and asserts the rest.)
+    `variant` (the literal build only): called with the renderer after the frame, to read which kernel ran."""
+    desc = partition_scene(scene, grid, border)
+    irr, rad = atlases(desc, SEED % 1000 + 3) if mode == 0 else (None, None)
+    R = make_renderer(desc, W, H, binding, mode=mode)
+    if prepare is not None:
+        prepare(R)
+    R.Update_Partitioning(Method=METHODS[method])
+    table = check_table(R, name, (scene, grid, method, 20), desc, method)
+    with_table = dict(desc, partition=dict(desc["partition"], table=table))
+    without = {k: v for k, v in desc.items() if k != "partition"}
+    key = ("partition screen", scene, grid, border, W, H, mode, table.tobytes())
+    runs = cached(key, lambda: ref64.three_runs(lambda seed: ref64.screen(with_table, W, H, mode, irr, rad, seed=seed)))
+    plain = cached(("partition screen", scene, W, H, mode), lambda: ref64.screen(without, W, H, mode, irr, rad))
+    tols = (0.0, 1e-4) if mode == 1 else (ref64.COLOUR_RTOL, ref64.COLOUR_ATOL)
+    changed = float(differs(runs[0], plain, *tols).mean())
+    steps = int(runs[0]["negative"].sum())
+    print("%s: the table changes %.3f of the pixels; %d pixels with a negative shadow radicand" % (name, changed, steps))
+    if W * H >= 100:
+        assert changed > 0.10, "%s: the table changes only %.3f of the pixels" % (name, changed)
+    if negative:
+        assert steps > 0, "%s: no soft-shadow step has a negative radicand" % name
+    if mode == 0:
+        R.Write_Texture(B.TEX_IRRADIANCE, irr)
+        R.Write_Texture(B.TEX_RADIANCE, rad)
+        R.Render_Pass(B.PASS_SCREEN)
+    else:
+        R.Render()
+    fb = R.Read_Framebuffer()
+    index, t, _ = R.Read_Gbuffer()
+    if variant is not None:
+        variant(R)
+    R.Destroy()
+    if mode == 1:  # (run_screen's bound: the hit displaced by the march tolerance turns a sphere's normal by dt / r)
+        radii = [float(p[2]) for p in desc["prims"] if p[0] == "Sphere"]
+        return ref64.hold(name, runs, fb, index, t, rtol=0.0, atol=0.5 * ref64.T_ATOL / min(radii) + 4.0 * 2.0 ** -24, table=True)
+    return ref64.hold(name, runs, ref64.undo_tone_map(fb), index, t, table=True)
+
+
+def run_partition_radiance(binding, name, grid, method="CPU_Fast", prepare=None, variant=None):
+    """one Render_Pass (PASS_RADIANCE) over written atlases through a table, in the radiance pass's room with both lights:
+    run_radiance's rules, the table held and read back as in run_partition_screen, and the same first condition"""
+    desc = partition_scene("room", grid)
+    irr, rad = atlases(desc, SEED % 1000 + 5)
+    R = make_renderer(desc, 8, 8, binding, atlas=1)
+    if prepare is not None:
+        prepare(R)
+    R.Update_Partitioning(Method=METHODS[method])
+    table = check_table(R, name, ("room", grid, method, 20), desc, method)
+    with_table = dict(desc, partition=dict(desc["partition"], table=table))
+    without = {k: v for k, v in desc.items() if k != "partition"}
+    runs = cached(("partition radiance", grid, table.tobytes()), lambda: ref64.three_runs(lambda seed: ref64.radiance_texels(with_table, irr, rad, seed=seed)))
+    plain = cached(("radiance", SMALL_PROBES.Probe_Count, 1), lambda: ref64.three_runs(lambda seed: ref64.radiance_texels(without, irr, rad, seed=seed)))[0]
+    changed = float(differs(runs[0], plain, ref64.COLOUR_RTOL, ref64.COLOUR_ATOL).mean())
+    print("%s: the table changes %.3f of the texels" % (name, changed))
+    assert changed > 0.10, "%s: the table changes only %.3f of the texels" % (name, changed)
+    R.Write_Texture(B.TEX_IRRADIANCE, irr)
+    R.Write_Texture(B.TEX_RADIANCE, rad)
+    R.Render_Pass(B.PASS_RADIANCE)
+    got = R.Read_Texture(B.TEX_RADIANCE)
+    if variant is not None:
+        variant(R)
+    R.Destroy()
+    return ref64.hold(name, runs, got, table=True)
+
+
+# The frames of tests/test_gpu_ref64_partition.py, each named for the kernel variant it is meant to run: `pfk` is what the
+# diagnostic build's mdh_diag_variant reports for its pass (MDH_PF_PART 1, _FALLBACK 8, _PSMALL 32, _GTAB 64).  pfk is the
+# family pick_kernel chose; for mode 1 it still reads PART | PSMALL on grid B, though the census is dropped there and the
+# general partition kernel runs.
+PART, FALLBACK, PSMALL, GTAB = 1, 8, 32, 64
+PARTITION_FRAMES = {
+    "B Clamp mode 0": dict(grid="B", mode=0, pfk=PART | PSMALL),
+    "B Clamp mode 2": dict(grid="B", mode=2, pfk=PART | PSMALL),
+    "B Clamp mode 1": dict(grid="B", mode=1, pfk=PART | PSMALL),
+    "A Clamp mode 2": dict(grid="A", mode=2, pfk=PART),                                  # division by the spacing
+    "A Fallback mode 0": dict(grid="A", border="Fallback", mode=0, pfk=PART | FALLBACK),
+    "A Fallback mode 2": dict(grid="A", border="Fallback", mode=2, pfk=PART | FALLBACK, negative=True),
+    "A Clamp resident": dict(grid="A", mode=2, resident=True, pfk=PART | GTAB),
+    "A Fallback resident": dict(grid="A", border="Fallback", mode=2, resident=True, pfk=PART | FALLBACK | GTAB, negative=True),
+    "34 spheres": dict(scene="34 spheres", grid="B", mode=2, pfk=PART),                  # the general bits form, three mask words
+    # (built on the device: the host builders evaluate a triangle through Madarch.Values, whose "/" on floats adds -- a quirk of
+    #  the reference that ref64 does not restate, see test_values_division_bug_is_reproduced)
+    "triangles": dict(scene="triangles", grid="B", method="GPU_Fast", mode=2, pfk=PART),
+    "two radii": dict(scene="two radii", grid="B", mode=2, pfk=PART | PSMALL),
+    "C GPU_Fast": dict(grid="C", method="GPU_Fast", mode=2, pfk=PART),
+    "D six digits": dict(grid="D", mode=2, pfk=PART),
+    "A Fallback 1x1": dict(grid="A", border="Fallback", mode=2, size=(1, 1), pfk=PART | FALLBACK),
+    "A Fallback 61x37": dict(grid="A", border="Fallback", mode=2, size=(61, 37), pfk=PART | FALLBACK, negative=True),
+}
+PARTITION_RADIANCE = {"A": PART, "B": PART | PSMALL}
+
+
+def force_residency(R):
+    """the scene's table read from device memory (as tests/test_gpu_large_scenes.py forces it)"""
+    R.Set_Option(B.OPT_TABLE_RESIDENCY, 1)
+    assert R.Get_Option(B.OPT_TABLE_RESIDENCY) == 1
+
+
+def run_partition_frame(binding, case, variant=None):
+    c = PARTITION_FRAMES[case]
+    W, H = c.get("size", (36, 24))
+    return run_partition_screen(binding, "partition " + case, c.get("scene", "plain"), c["grid"], c.get("method", "CPU_Fast"), c["mode"],
+                                prepare=force_residency if c.get("resident") else None, border=c.get("border", "Clamp"), W=W, H=H,
+                                negative=c.get("negative", False), variant=variant)
+
+
+def render_partition_frame(binding, case):
+    """the case's renderer after its one frame, nothing held (for the variant check)"""
+    c = PARTITION_FRAMES[case]
+    W, H = c.get("size", (36, 24))
+    desc = partition_scene(c.get("scene", "plain"), c["grid"], c.get("border", "Clamp"))
+    R = make_renderer(desc, W, H, binding, mode=c["mode"])
+    if c.get("resident"):
+        force_residency(R)
+    R.Update_Partitioning(Method=METHODS[c.get("method", "CPU_Fast")])
+    if c["mode"] == 0:
+        irr, rad = atlases(desc, SEED % 1000 + 3)
+        R.Write_Texture(B.TEX_IRRADIANCE, irr)
+        R.Write_Texture(B.TEX_RADIANCE, rad)
+        R.Render_Pass(B.PASS_SCREEN)
+    else:
+        R.Render()
+    return R
+
+
+def render_partition_radiance(binding, grid):
+    desc = partition_scene("room", grid)
+    irr, rad = atlases(desc, SEED % 1000 + 5)
+    R = make_renderer(desc, 8, 8, binding, atlas=1)
+    R.Update_Partitioning(Method=METHODS["CPU_Fast"])
+    R.Write_Texture(B.TEX_IRRADIANCE, irr)
+    R.Write_Texture(B.TEX_RADIANCE, rad)
+    R.Render_Pass(B.PASS_RADIANCE)
+    return R
+
+
+def run_partition_lookups(binding, name, border, n=4000):
+    """partitioning_closest_info at seeded points in a box that overhangs grid A by more than a cell on every side,
+    through the oracle's orc_probe_closest, against Scene.lookup over the table read back: the distance to 8 ulp32 of the
+    largest number that enters it (hold_distances' bound), the index exactly.  Left out: points within the margin of a cell
+    face (ref64.hold, cell_face_margin); the index where the two closest candidates are within the distance's bound of
+    each other.  The sample must reach the lookup's three border quirks."""
+    import ctypes as C
+    desc = partition_scene("plain", "A", border)
+    R = make_renderer(desc, 8, 8, binding)
+    R.Update_Partitioning(Method=METHODS["CPU_Fast"])
+    table = R.Read_Partitioning()
+    dims, spacing, offset = (np.array(v) for v in GRIDS["A"])
+    lo, hi = offset - 1.7 * spacing, offset + (dims + 1.7) * spacing
+    rng = np.random.RandomState(SEED % 1000 + 29)
+    pts = rng.uniform(lo, hi, size=(n, 3))
+    on = n // 20  # the first twentieth ON a face: one coordinate at offset + j * spacing, which binary32 may put on either side
+    axis, j = rng.randint(0, 3, size=on), rng.randint(-1, 9, size=on)
+    pts[np.arange(on), axis] = (offset + j[:, None] * spacing)[np.arange(on), axis]
+    pts = pts.astype(np.float32)
+    dist, index = np.zeros(n, np.float32), np.zeros(n, np.int32)
+    binding.lib.orc_probe_closest(R._h, n, pts.ctypes.data_as(C.c_void_p), 1, dist.ctypes.data_as(C.c_void_p), index.ctypes.data_as(C.c_void_p))
+    R.Destroy()
+    sc = ref64.Scene(dict(desc, partition=dict(desc["partition"], table=table)))
+    P = pts.astype(np.float64)
+    want_d, arg = sc.lookup(P)
+    want_i = np.where(arg >= 0, sc.number[np.maximum(arg, 0)], -1)
+    fx = np.floor((P - sc.poff6) / sc.psp6)
+    inside = ((fx >= 0) & (fx <= dims)).all(axis=1)
+    cell = fx[:, 0] * dims[1] * dims[2] + fx[:, 1] * dims[2] + fx[:, 2]
+    back = ~inside if border == "Fallback" else np.zeros(n, dtype=bool)
+    reach = inside if border == "Fallback" else np.ones(n, dtype=bool)
+    cfx = np.clip(fx, 0, dims)
+    ccell = cfx[:, 0] * dims[1] * dims[2] + cfx[:, 1] * dims[2] + cfx[:, 2]
+    past, aliased = reach & (ccell >= dims.prod()), reach & (cfx[:, 2] == dims[2]) & (ccell < dims.prod())
+    print("%s: %d points, %d outside the grid, %d past the table, %d aliased through fx.z == dims.z, %d fall back, %d near a face" % (
+        name, n, int((~((fx >= 0) & (fx < dims)).all(axis=1)).sum()), int(past.sum()), int(aliased.sum()), int(back.sum()), int(sc.face.sum())))
+    assert past.sum() > 20 and aliased.sum() > 20 and (border != "Fallback" or back.sum() > 20)
+    assert sc.face[:on].all() and sc.face.sum() < on + 5
+    assert (want_d[past] == sc.max_dist).all() and (want_i[past] == -1).all()
+    held = ~sc.face
+    tol = 8.0 * ulp32(np.maximum(np.abs(P).max(axis=1), np.abs(want_d)))
+    err = np.abs(dist.astype(np.float64) - want_d)
+    print("%s: largest distance error %.2f of its tolerance" % (name, (err / tol)[held].max()))
+    bad = held & (err > tol)
+    assert not bad.any(), "%s: %d distances off, first at %s: got %r, float64 %r" % (name, bad.sum(), pts[bad][0], dist[bad][0], want_d[bad][0])
+    # the arg-min is sure where the runner-up -- the cell's next candidate, or max_dist itself -- is farther off than twice the bound
+    D = np.stack([sc.prim_distance(k, P) for k in range(len(sc.prims))], axis=1)
+    ranks = np.where(back[:, None], 0, sc.rank[np.where(reach & (ccell < dims.prod()), ccell, dims.prod()).astype(int)])
+    D = np.where(ranks < sc.never, D, np.inf)
+    D[np.arange(n)[arg >= 0], arg[arg >= 0]] = np.inf
+    sure = held & (np.minimum(D.min(axis=1), sc.max_dist) - np.where(arg >= 0, want_d, sc.max_dist) > 2.0 * tol) | (held & (arg < 0) & (D.min(axis=1) - sc.max_dist > 2.0 * tol))
+    bad = sure & (index != want_i)
+    print("%s: %d indices held" % (name, int(sure.sum())))
+    assert sure.sum() > 0.9 * n
+    assert not bad.any(), "%s: %d indices differ, first at %s: got %d, float64 %d" % (name, bad.sum(), pts[bad][0], index[bad][0], want_i[bad][0])

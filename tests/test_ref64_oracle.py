@@ -13,7 +13,8 @@ froxel texture under two lights (one a spot light), the scattering texture over 
 frame, and the volumetric composition of a pixel.  The shapes are those of tests/test_gpu_ref64_passes.py, where the
 kernels change form; here they prove ref64's new code and show that the fragile caps hold for the reference alone.
 
-Not covered: the space partition, user-defined kinds, indirect-specular modes 1 and 3 (restated in
+The space partition -- its builders, its lookup and frames marched through a table -- is held in
+test_ref64_partition_oracle.py.  Not covered: user-defined kinds, indirect-specular modes 1 and 3 (restated in
 test_oracle_pins64.py)."""
 import pytest
 
