@@ -103,7 +103,30 @@ typedef struct {
  * rounded through Single'Image like every literal of the generated GLSL
  * (madarch-exprs.adb:330-336); E ** n with a literal integer n = 2..16 is repeated
  * multiplication, squaring from the most significant bit of n ((x^2)^2 x for n = 5).  Arithmetic is IEEE fp32, one operation per
- * instruction, division and square root correctly rounded. */
+ * instruction, division and square root correctly rounded.
+ *
+ * At the IEEE edges (tests/mdhx_cases.py holds every evaluator to these, bit for bit):
+ *   - ADD SUB MUL DIV DIVF SQRT FLOOR are the IEEE 754 operations, round to nearest even, with
+ *     gradual underflow, overflow to infinity and the signed zeros of the standard (sqrt (-0) = -0,
+ *     x - x = +0, floor (-0) = -0).  A NaN result's sign and payload are UNSPECIFIED (0/0 is
+ *     0xFFC00000 on x86 and 0x7FC00000 on gfx950): only its being a NaN is defined.  Every other
+ *     result is defined on all its 32 bits.
+ *   - MIN / MAX are minNum / maxNum: a NaN operand is ignored, two NaNs give a NaN; -0 is ordered
+ *     below +0 in either operand order (min (+0, -0) = min (-0, +0) = -0, max = +0), as
+ *     v_min_f32 / v_max_f32 do.
+ *   - LT GT LE GE are 0 when an operand is a NaN; -0 equals +0.
+ *   - SEL takes b when a != 0: a NaN condition takes b, -0 (and +0) take c.
+ *   - SIGN of a NaN and of either zero is +0.  NEG and ABS act on the sign bit alone.
+ *   - ITOF reads the register's bits as int32 and rounds once, to nearest even (2^24 + 1 -> 2^24,
+ *     INT_MAX -> 2^31).
+ *   - POW (x, y): NaN for x < 0 or a NaN x; 0 for x = +-0 whatever y is (pow (0, 0) = 0,
+ *     pow (0, -1) = 0); NaN for a NaN y otherwise; for x = +inf: inf, 1 or 0 as y > 0, = 0, < 0;
+ *     1 for x = 1 (also with y = +-inf); else 2^z with z = y log2 (x) in fp32: +inf for z >= 128,
+ *     0 for z < -126 (results below the normal range are flushed), and within
+ *     1.2e-6 max (1, |z|) relative of the exact power in between.
+ *   - SIN COS TAN of +-inf and of a NaN are NaN; ATAN (+-inf) = +-pi/2, of a NaN NaN.  Beyond
+ *     |x| ~ 1e4 the reduction of SIN COS TAN loses accuracy, from |x| >= 1e9 pi/2 on there is none.
+ *     ACOS and ASIN are NaN for |x| > 1 and for a NaN. */
 enum {
    MDH_X_LIT = 0,    /* R[dst] = the next word (raw bits)                          */
    MDH_X_MOV = 1,    /* R[dst] = R[a]                                              */

@@ -229,7 +229,9 @@ MDH_DEV float min0_raw(float a) { float r; asm("v_min_f32 %0, 0, %1" : "=v"(r) :
 // The core of that expansion by itself: v_sqrt_f32, its two neighbours, two fma residuals, two selects -- the
 // compiler's own nine instructions, hence its result, for every input that it does not rescale: 0, anything from
 // 2^-96 up, infinities and NaN (for 0 both residual tests fail and the 0 of v_sqrt_f32 stands).  For callers that
-// KNOW their operand is no positive number below 2^-96.
+// KNOW their operand is no nonzero number below 2^-96 in magnitude: v_sqrt_f32 takes a subnormal operand for a zero of
+// its sign, so a NEGATIVE subnormal would give -0 here where the root is NaN (tests/test_gpu_mdhx_ops.py) -- the guards
+// of sqrt_ and sqrt_wave_ below send those to the full expansion too.
 // MDH_FAST_NUMERICS: the LABELLED EXPERIMENT build (`make -C madarch_amd/csrc fast`, never the shipped library): what the
 // path would cost under BASELINE.json's tolerance (1e-4 relative per channel) instead of this build's own contract (the
 // oracle's bits) -- the hardware's v_sqrt_f32 / v_rcp_f32 / v_log_f32 / v_exp_f32 as GLSL on any GPU uses them, fused
@@ -257,17 +259,17 @@ MDH_DEV float sqrt_(float x)
 #if MDH_FAST_NUMERICS
    return __builtin_amdgcn_sqrtf(x);
 #endif
-   if (__ballot(x < 0x1p-96f && x > 0.0f) != 0ull) return __builtin_sqrtf(x);
+   if (__ballot(__builtin_fabsf(x) < 0x1p-96f && x != 0.0f) != 0ull) return __builtin_sqrtf(x);
    return sqrt_unscaled_(x);
 }
 // the correctly rounded root of a wavefront's operands through the nine-instruction core when none of them is a positive
-// number below 2^-96 (the only inputs hipcc's expansion rescales: sqrt_unscaled_ above), through the full expansion otherwise
+// or negative number below 2^-96 in magnitude (the inputs hipcc's expansion must rescale: sqrt_unscaled_ above), through the full expansion otherwise
 MDH_DEV float sqrt_wave_(float x)
 {
 #if MDH_FAST_NUMERICS
    return __builtin_amdgcn_sqrtf(x);
 #endif
-   if (__ballot(x < 0x1p-96f && x > 0.0f) != 0ull) return sqrt_(x);
+   if (__ballot(__builtin_fabsf(x) < 0x1p-96f && x != 0.0f) != 0ull) return sqrt_(x);
    return sqrt_unscaled_(x);
 }
 // MDH_HYBRID_NUMERICS: the second LABELLED EXPERIMENT (`make -C madarch_amd/csrc hybrid`; never the shipped
@@ -408,6 +410,7 @@ MDH_DEV float exp2_(float z)
    p = p * u + 0.5f;
    p = p * u + 1.0f;
    p = p * u + 1.0f;
+   if (n > 127.0f) return (p * 0x1p127f) * 2.0f; // z in (127.5, 128]: 2^128 is no binary32, and p may be below 1
    return p * __int_as_float(((int)n + 127) << 23);
 }
 MDH_DEV float log2_(float x)
@@ -439,8 +442,10 @@ MDH_DEV float pow_(float x, float y)
 #endif
    if (x != x || x < 0.0f) return __builtin_nanf("");
    if (x == 0.0f) return 0.0f;
-   if (x > 3.40282347e+38f) return x;
-   return exp2_(y * log2_(x));
+   if (x > 3.40282347e+38f) return y != y ? y : (y > 0.0f ? x : (y < 0.0f ? 0.0f : 1.0f));
+   const float z = y * log2_(x);
+   if (z != z) return y != y ? y : 1.0f; // (0 * inf: 1^(+-inf) is 1)
+   return exp2_(z);
 }
 #if MDH_HYBRID_NUMERICS
 MDH_DEV float sexp(float x) { return __builtin_amdgcn_exp2f(x * 1.44269502162933349609375f); }

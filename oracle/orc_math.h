@@ -32,11 +32,16 @@ ORC_INLINE v3 V3(float x, float y, float z) { v3 r = {x, y, z}; return r; }
 ORC_INLINE v3 v3s(float s) { return V3(s, s, s); }
 ORC_INLINE v2 V2(float x, float y) { v2 r = {x, y}; return r; }
 
+ORC_INLINE float f_of_bits(uint32_t u) { union { uint32_t u; float f; } c; c.u = u; return c.f; }
+ORC_INLINE uint32_t bits_of_f(float f) { union { uint32_t u; float f; } c; c.f = f; return c.u; }
+
 /* GLSL min/max (GLSL 4.30 8.3: y < x ? y : x, undefined for NaN).  The oracle
  * fixes the NaN case as IEEE 754-2008 minNum/maxNum -- a NaN operand is
- * ignored -- which is what the gfx950 v_min_f32/v_max_f32 the kernels use do. */
-ORC_INLINE float fmin_(float a, float b) { return (a != a) ? b : (b != b) ? a : (b < a) ? b : a; }
-ORC_INLINE float fmax_(float a, float b) { return (a != a) ? b : (b != b) ? a : (a < b) ? b : a; }
+ * ignored -- which is what the gfx950 v_min_f32/v_max_f32 the kernels use do.
+ * Those order -0 below +0 whichever operand comes first: of two equal numbers
+ * (equal bits, but for the two zeros) min keeps a set sign bit, max a clear one. */
+ORC_INLINE float fmin_(float a, float b) { return (a != a) ? b : (b != b) ? a : (b < a) ? b : (a < b) ? a : f_of_bits(bits_of_f(a) | bits_of_f(b)); }
+ORC_INLINE float fmax_(float a, float b) { return (a != a) ? b : (b != b) ? a : (a < b) ? b : (b < a) ? a : f_of_bits(bits_of_f(a) & bits_of_f(b)); }
 ORC_INLINE float clamp_(float x, float lo, float hi) { return fmin_(fmax_(x, lo), hi); }
 ORC_INLINE int imin_(int a, int b) { return b < a ? b : a; }
 ORC_INLINE int imax_(int a, int b) { return a < b ? b : a; }
@@ -75,9 +80,6 @@ ORC_INLINE v3 cross(v3 a, v3 b)
 }
 /* reflect(I,N) = I - 2 dot(N,I) N (GLSL 4.30 8.5) */
 ORC_INLINE v3 reflect(v3 i, v3 n) { return sub(i, scale(n, 2.0f * dot(n, i))); }
-
-ORC_INLINE float f_of_bits(uint32_t u) { union { uint32_t u; float f; } c; c.u = u; return c.f; }
-ORC_INLINE uint32_t bits_of_f(float f) { union { uint32_t u; float f; } c; c.f = f; return c.u; }
 
 /* Transcendentals.  GLSL gives acos / exp / pow implementation-defined precision and the
  * hardware approximations of the GPU (v_exp_f32, v_log_f32) have no bit-identical CPU
@@ -172,6 +174,7 @@ ORC_INLINE float exp2_(float z)
    p = p * u + 0.5f;
    p = p * u + 1.0f;
    p = p * u + 1.0f;
+   if (n > 127.0f) return (p * 0x1p127f) * 2.0f; /* z in (127.5, 128]: 2^128 is no binary32, and p may be below 1 */
    return p * f_of_bits((uint32_t)((int32_t)n + 127) << 23);
 }
 /* log2(x), x > 0: x = m 2^e with m in [sqrt(1/2), sqrt(2)); ln m = 2 atanh(s), s = (m-1)/(m+1),
@@ -195,13 +198,16 @@ ORC_INLINE float log2_(float x)
 }
 ORC_INLINE float exp_(float x) { return exp2_(x * 1.44269502162933349609375f); }
 /* pow(x, y) for the tonemap (y = 0.4545, draw_screen.glsl:29): 2^(y log2 x); x < 0 is NaN as in
- * GLSL, 0 gives 0 */
+ * GLSL, 0 gives 0 whatever y is; +inf gives inf, 1 or 0 by the sign of y; a NaN y gives NaN, and
+ * 1^(+-inf) is 1 (the exponent 0 * inf is no NaN of the result) */
 ORC_INLINE float pow_(float x, float y)
 {
    if (x != x || x < 0.0f) return NAN;
    if (x == 0.0f) return 0.0f;
-   if (x > 3.40282347e+38f) return x;
-   return exp2_(y * log2_(x));
+   if (x > 3.40282347e+38f) return y != y ? y : (y > 0.0f ? x : (y < 0.0f ? 0.0f : 1.0f));
+   float z = y * log2_(x);
+   if (z != z) return y != y ? y : 1.0f;
+   return exp2_(z);
 }
 /* pow(x, 5.0) of fresnel_schlick (cook_torrance_brdf.glsl:2) */
 ORC_INLINE float pow5_(float x) { float x2 = x * x; return (x2 * x2) * x; }
