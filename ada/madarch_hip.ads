@@ -263,6 +263,26 @@ package Madarch_HIP is
      (R : Handle; N : int; Index, Material_Out : System.Address) return Status
      with Import, Convention => C, External_Name => "mdh_primitive_material";
 
+   --  Ground truth for the probes: a path tracer along N rays of the host's (madarch_hip.h,
+   --  mdh_path_trace).  RGB_Accum holds sums, in and out; ray I has id Id_First + I; Bounces 0 .. 6.
+   function Path_Trace
+     (R : Handle; N : int; Org, Dir : System.Address; Seed, Id_First : Interfaces.Unsigned_32;
+      Sample_First, Sample_Count, Bounces : int;
+      RGB_Accum, Hit_Out, Index_Out, T_Out : System.Address) return Status
+     with Import, Convention => C, External_Name => "mdh_path_trace";
+
+   function Path_Trace_Device
+     (R : Handle; N : int; Org, Dir : System.Address; Seed, Id_First : Interfaces.Unsigned_32;
+      Sample_First, Sample_Count, Bounces : int;
+      RGB_Accum, Hit_Out, Index_Out, T_Out : System.Address; Stream : System.Address) return Status
+     with Import, Convention => C, External_Name => "mdh_path_trace_device";
+
+   --  The sampler by itself, on the host: no launch and no renderer.
+   function Path_Scatter
+     (N : int; Dir, Normal, Roughness : System.Address; Seed, Id_First : Interfaces.Unsigned_32;
+      Sample, Bounce : int; Dir_Out : System.Address) return Status
+     with Import, Convention => C, External_Name => "mdh_path_scatter";
+
    --  One frame on the N GPUs of a node, one process per GPU (madarch_hip.h, mdh_comm_*):
    --  every process creates its Renderer on its own device, rank 0 makes a 128-byte id and
    --  hands it to the others (a file, an environment variable), all call Comm_Init, and

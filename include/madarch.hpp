@@ -449,6 +449,40 @@ class Renderer {
       Check(mdh_primitive_material(h_.get(), (int32_t)Index.size(), Index.data(), Material.data()));
       return Material;
    }
+   // ---- ground truth for the probes: a path tracer along rays of the host's (the reference's render_path.glsl made to run).  Rgb holds
+   // SUMS: samples Sample_First .. Sample_First + Sample_Count - 1 are added to Rgb_Accum (empty: zeros) in that order, the host divides by
+   // the count; ray i has id Id_First + i and its random numbers depend on (Seed, id, sample, bounce) alone.  Hit, Index, T: the primary
+   // segment.  Bounces 0 .. 6; never any fog, no atlas, no occlusion
+   struct Path_Colours { std::vector<float> Rgb, T; std::vector<int32_t> Hit, Index; };
+   Path_Colours Path_Trace(const std::vector<float> &Origins, const std::vector<float> &Directions, uint32_t Seed = 0, uint32_t Id_First = 0, int32_t Sample_First = 0,
+                           int32_t Sample_Count = 1, int32_t Bounces = 3, const std::vector<float> &Rgb_Accum = std::vector<float>()) const
+   {
+      const size_t n = Ray_Count(Origins, Directions);
+      if (!Rgb_Accum.empty() && Rgb_Accum.size() != 3 * n) throw Constraint_Error("one colour sum per ray");
+      Path_Colours o;
+      o.Rgb = Rgb_Accum.empty() ? std::vector<float>(3 * n, 0.0f) : Rgb_Accum;
+      o.T.resize(n); o.Hit.resize(n); o.Index.resize(n);
+      Check(mdh_path_trace(h_.get(), (int32_t)n, Origins.data(), Directions.data(), Seed, Id_First, Sample_First, Sample_Count, Bounces, o.Rgb.data(), o.Hit.data(),
+                           o.Index.data(), o.T.data()));
+      return o;
+   }
+   // ... for arrays in memory the device addresses, asynchronous and ordered with Stream as Shade_Rays_Device is; the sums stay on the device
+   // from call to call.  A ray that is not finite, starts beyond 1024 or has a direction component beyond 2: NaN, Hit = -1
+   void Path_Trace_Device(int32_t N, const float *Origins, const float *Directions, float *Rgb_Accum, int32_t *Hit = nullptr, int32_t *Index = nullptr, float *T = nullptr,
+                          uint32_t Seed = 0, uint32_t Id_First = 0, int32_t Sample_First = 0, int32_t Sample_Count = 1, int32_t Bounces = 3, void *Stream = nullptr) const
+   {
+      Check(mdh_path_trace_device(h_.get(), N, Origins, Directions, Seed, Id_First, Sample_First, Sample_Count, Bounces, Rgb_Accum, Hit, Index, T, Stream));
+   }
+   // the sampler by itself, on the host, the lanes' bits: no launch and no renderer.  3 floats a direction, one roughness each
+   static std::vector<float> Path_Scatter(const std::vector<float> &Directions, const std::vector<float> &Normals, const std::vector<float> &Roughness, uint32_t Seed = 0,
+                                          uint32_t Id_First = 0, int32_t Sample = 0, int32_t Bounce = 0)
+   {
+      const size_t n = Roughness.size();
+      if (Directions.size() != 3 * n || Normals.size() != 3 * n) throw Constraint_Error("one direction, one normal and one roughness per path");
+      std::vector<float> Out(3 * n);
+      Check(mdh_path_scatter((int32_t)n, Directions.data(), Normals.data(), Roughness.data(), Seed, Id_First, Sample, Bounce, Out.data()));
+      return Out;
+   }
    void Update_Partitioning(Partitioning_Update_Method Method = GPU_Fast) const { Check(mdh_update_partitioning(h_.get(), (int32_t)Method)); } // renderers.adb:757-775
    // ---- headless additions
    std::vector<float> Read_Framebuffer() const // replaces Swap_Buffers: H*W*3 floats, row 0 = top

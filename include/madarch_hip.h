@@ -706,6 +706,50 @@ int32_t mdh_shade_points_device(mdh_renderer *r, int32_t n, const float *pos_xyz
  * mdh_raycast's hits to mdh_shade_points.  MDH_E_STATE: a scene with a user-defined kind (its material is a program). */
 int32_t mdh_primitive_material(mdh_renderer *r, int32_t n, const int32_t *index, int32_t *material_out);
 
+/* Ground truth for the probes: a path tracer along n rays of the host's.  For every ray and sample: mask = 1, rgb = 0, then up
+ * to bounces + 1 segments, each the shaders' raycast to max_dist.  A miss adds mask * sky (the expression of
+ * glsl/render_probes.glsl:287 along the segment) and ends the path.  A hit adds mask * compute_direct_lighting
+ * (glsl/lighting.glsl:1-40, direct specular on), multiplies the mask by the hit's albedo and goes on from
+ * P + normal * 0.05 * 5 along the sampler's direction (mdh_path_scatter below).  It restates the reference's
+ * glsl/render_path.glsl, which the reference never includes, with three deviations: the sky is masked, it is added once, and
+ * the next origin is offset from the surface.  Ray i has id id_first + i; the random numbers of a path depend on (seed, id,
+ * sample, bounce) and on nothing else -- not on the batch or its order.
+ * rgb_accum (3 n floats, linear, IN AND OUT) holds sums: the call adds samples sample_first .. sample_first + sample_count - 1
+ * to what the array holds, in that order, so a run of samples split over several calls has the bits of one call; the host
+ * divides by the count.  hit_out (0 / 1), index_out and t_out may be NULL and describe the primary segment, as mdh_shade_rays'.
+ * NO VOLUMETRICS: the query never composes fog.  It reads no atlas, and MDH_OPT_AO_STEPS and MDH_OPT_INDIRECT_SPECULAR do
+ * not enter it.  Otherwise the contract is mdh_shade_rays': the call runs on the query stream behind the same fences, reads
+ * the scene committed at the call, pending edits included, and edits nothing: the probe-settle run and both replays go on
+ * across it.  n = 0 or sample_count = 0 is MDH_OK without a launch.  Every refusal happens before a launch:
+ *   MDH_E_INVALID  a null renderer or required array, n < 0, sample_first < 0, sample_count < 0, a sum of the two beyond
+ *                  2^31 - 1, bounces outside 0 .. 6, and -- mdh_path_trace, on the host, the whole batch -- a ray outside
+ *                  the bound of mdh_shade_rays (finite, origin within 1024, direction within 2 per component) or with a
+ *                  direction of zero
+ *   MDH_E_STATE    a scene with a user-defined kind; an open frame; a max_dist above 1024 or a light beyond 1024
+ * The marches have no stall guard.  Behind the first segment every direction is a unit vector, so a bounce moves the shaded
+ * point by less than max_dist + 0.25: six bounces keep every march parameter below 13 246 < 2^14 (DESIGN.md section 4,
+ * "Path tracing a host's rays"). */
+int32_t mdh_path_trace(mdh_renderer *r, int32_t n, const float *org_xyz, const float *dir_xyz, uint32_t seed, uint32_t id_first,
+                       int32_t sample_first, int32_t sample_count, int32_t bounces, float *rgb_accum, int32_t *hit_out,
+                       int32_t *index_out, float *t_out);
+/* The same call for arrays the device addresses, under the contract of mdh_shade_rays_device: asynchronous and ordered with
+ * `stream`, mdh_ray_query_wait is the host's wait and mdh_ray_query_time times the kernel, and where every array lives and
+ * ends is checked with hipPointerGetAttributes before anything is launched (MDH_E_INVALID).  The lane that takes a ray
+ * outside the bound, or with a zero direction, answers it without marching: the quiet NaN 0x7fc00000 in all three colours, hit = -1, index = -1, t = 0.
+ * Every other ray has the bits mdh_path_trace gives it.  The sums stay on the device from call to call. */
+int32_t mdh_path_trace_device(mdh_renderer *r, int32_t n, const float *org_xyz, const float *dir_xyz, uint32_t seed,
+                              uint32_t id_first, int32_t sample_first, int32_t sample_count, int32_t bounces, float *rgb_accum,
+                              int32_t *hit_out, int32_t *index_out, float *t_out, void *stream);
+/* The sampler by itself, on the host: no launch and no renderer.  dir_out[i] is the direction the path of ray id_first + i
+ * takes behind bounce `bounce` of sample `sample`, having arrived along dir_xyz[i] at a surface with normal normal_xyz[i]
+ * (any length but 0) and roughness[i]: cosine-weighted about the normal with probability `roughness`, else the mirror
+ * direction widened by the roughness; always normalised.  The functions are the ones the lanes of mdh_path_trace call
+ * (csrc/mdh_path.h): the same bits, so a host can continue paths its own way or compose the whole estimator from mdh_raycast,
+ * mdh_primitive_material and mdh_shade_points.  A component that is not finite (a zero normal, a mirror direction that
+ * cancels) ends the path in mdh_path_trace.  MDH_E_INVALID: n, sample or bounce below 0, a null array with n > 0. */
+int32_t mdh_path_scatter(int32_t n, const float *dir_xyz, const float *normal_xyz, const float *roughness, uint32_t seed,
+                         uint32_t id_first, int32_t sample, int32_t bounce, float *dir_out);
+
 /* accumulated HIP-event time and launch count of one pass (MDH_OPT_TIMING) */
 int32_t mdh_pass_time(mdh_renderer *r, int32_t pass, double *total_ms, int64_t *launches);
 /* MDH_OPT_RADIANCE_REPLAY: the radiance passes launched since mdh_create that marched their rays (`plain`), marched them

@@ -180,6 +180,12 @@ HIP_ONLY_ABI = {
     "shade_points": (_I, [_P, _I, _P, _P, _P, _P, _I, _I, _P]),
     "shade_points_device": (_I, [_P, _I, _P, _P, _P, _P, _I, _I, _P, _P]),
     "primitive_material": (_I, [_P, _I, _P, _P]),
+    # the path tracer along n rays of the host's: (r, n, org, dir, seed, id_first, sample_first, sample_count, bounces,
+    # rgb_accum (in and out), hit, index, t[, stream]); and its sampler on the host, no renderer: (n, dir, normal, roughness,
+    # seed, id_first, sample, bounce, dir_out)
+    "path_trace": (_I, [_P, _I, _P, _P, C.c_uint32, C.c_uint32, _I, _I, _I, _P, _P, _P, _P]),
+    "path_trace_device": (_I, [_P, _I, _P, _P, C.c_uint32, C.c_uint32, _I, _I, _I, _P, _P, _P, _P, _P]),
+    "path_scatter": (_I, [_I, _P, _P, _P, C.c_uint32, C.c_uint32, _I, _I, _P]),
 }
 
 

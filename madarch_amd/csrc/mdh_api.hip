@@ -1796,7 +1796,7 @@ template <typename Args> static int jit_launch(hipFunction_t f, int blocks, int 
 // frames in flight share their CUs' instruction caches (measured: the same kernels at other addresses, each as fast by itself,
 // the headline with frames in flight 0.5 % slower).  The kernels of global residency (MDH_PF_GTAB, mdh_device.h: Geo) come
 // last there: behind everything else they move nothing.
-enum { GK_k_visibility, GK_k_scat_march, GK_k_scattering, GK_k_radiance, GK_k_screen, GK_k_partition_build, GK_k_eval_distance, GK_k_diag_segments, GK_k_ray_query, GK_k_ray_stream, GK_k_ray_shade, GK_k_camera_rays, GK_k_point_shade };
+enum { GK_k_visibility, GK_k_scat_march, GK_k_scattering, GK_k_radiance, GK_k_screen, GK_k_partition_build, GK_k_eval_distance, GK_k_diag_segments, GK_k_ray_query, GK_k_ray_stream, GK_k_ray_shade, GK_k_camera_rays, GK_k_point_shade, GK_k_path_trace };
 // WHICH KERNEL A PASS RUNS ("One place that picks a pass's kernel"): every template argument of the
 // pass's kernel, computed once by pick_kernel; kernel_name and kernel_ptr turn the same description into the name hiprtc
 // instantiates and into the kernel of this library.
@@ -1832,7 +1832,7 @@ static const void *table_kernel(const mdh_renderer *r, int family, int what = 0)
    if (family == GK_k_eval_distance && r->bvh_active && !k.ada_div) k.pf |= MDH_PF_BVH;
    // the ray queries march as the passes do: through the space partition (its border as a variant of its own) or the triangle
    // BVH where the scene has one -- the general variants, whose bits the census variants share (pick_kernel)
-   if (family == GK_k_ray_query || family == GK_k_ray_stream || family == GK_k_ray_shade || family == GK_k_point_shade) {
+   if (family == GK_k_ray_query || family == GK_k_ray_stream || family == GK_k_ray_shade || family == GK_k_point_shade || family == GK_k_path_trace) {
       k.what = what;
       if (family == GK_k_ray_shade || family == GK_k_point_shade) { k.what = 0; k.mode = what; } // (mdh_shade_rays, mdh_shade_points: `what` is the call's mode)
       if (r->part.enable) k.pf |= MDH_PF_PART | (r->part.border_behavior != 0 ? MDH_PF_FALLBACK : 0);
@@ -3958,6 +3958,124 @@ extern "C" int32_t mdh_shade_rays_device(mdh_renderer *r, int32_t n, const float
    return shade_rays_run(r, mode, a, qs, (hipStream_t)stream);
 }
 
+// ------------------------------------------------------------------ path tracing a host's rays
+// mdh_path_trace, mdh_path_trace_device: the estimator of k_path_trace (mdh_kernels.h) along n rays of the host's, samples
+// sample_first .. sample_first + sample_count - 1 added to rgb_accum.  The plumbing is mdh_shade_rays': shade_rays_begin,
+// the fences of shade_query_run (no atlas is read, but the query keeps that call's place among the frames), d_rays for host
+// arrays, ray_array_check for device arrays, rq_e0 / rq_e1 under MDH_OPT_TIMING.  No settle_bump: nothing is edited.
+// MDH_OPT_AO_STEPS and MDH_OPT_INDIRECT_SPECULAR do not enter.  Every refusal happens before a launch.
+// the scene's half of the bound (mdh_path.h): shade_scene_check without the probe grid, which no path reads
+static int path_scene_check(const mdh_renderer *r)
+{
+   if (!rs_shade_extent_valid(r->max_dist)) return seterr(MDH_E_STATE, "traced paths need a max_dist of at most 1024");
+   for (int k = 0; k < r->nlk; ++k) {
+      const Kind &kd = r->lk[k];
+      int n = rd_i(r, kd.count_off);
+      if (n > kd.max_count) n = kd.max_count;
+      for (int i = 0; i < n; ++i)
+         for (int c = 0; c < 3; ++c)
+            if (!rs_shade_extent_valid(rd_f(r, kd.array_off + kd.stride * i + kd.f_a + 4 * c))) return seterr(MDH_E_STATE, "traced paths need every light within 1024 of the origin along every axis");
+   }
+   return MDH_OK;
+}
+// everything both calls refuse before they look at their arrays
+static int path_trace_check(const mdh_renderer *r, int32_t n, const float *org, const float *dir, int32_t sample_first, int32_t sample_count, int32_t bounces, const float *rgb)
+{
+   if (!r) return seterr(MDH_E_INVALID, "null renderer");
+   if (!org || !dir || !rgb || n < 0) return seterr(MDH_E_INVALID, "bad argument");
+   if (sample_first < 0 || sample_count < 0 || sample_count > INT32_MAX - sample_first) return seterr(MDH_E_INVALID, "the samples are sample_first .. sample_first + sample_count - 1, both at least 0 and their sum below 2^31");
+   if (!path_bounces_valid(bounces)) return seterr(MDH_E_INVALID, "paths take 0 to 6 bounces");
+   if (has_custom_kinds(r)) return seterr(MDH_E_STATE, "ray queries answer scenes of built-in kinds only");
+   if (r->in_frame) return seterr(MDH_E_STATE, "a frame is open");
+   return path_scene_check(r);
+}
+static int path_trace_run(mdh_renderer *r, const PathTraceArgs &a, hipStream_t qs, hipStream_t caller)
+{
+   int rc;
+   const void *kernel = table_kernel(r, GK_k_path_trace);
+   if (!kernel) return seterr(MDH_E_INVALID, "no kernel built for this variant");
+   if ((rc = join_main(r)) != MDH_OK) return rc;
+   r->main_dirty = true;
+   HIP_TRY(hipEventRecord(r->ev_sq_frame.ev, r->stream));
+   HIP_TRY(hipStreamWaitEvent(qs, r->ev_sq_frame.ev, 0));
+   if (caller != qs) { // the rays and the sums are what the caller's stream has made of them at this call
+      HIP_TRY(hipEventRecord(r->ev_sq_caller.ev, caller));
+      HIP_TRY(hipStreamWaitEvent(qs, r->ev_sq_caller.ev, 0));
+   }
+   if ((rc = table_acquire(r, qs)) != MDH_OK) return rc;
+   const unsigned blocks = (unsigned)(((size_t)a.n + MDH_BLOCK - 1) / MDH_BLOCK);
+   const bool timed = r->opt_timing && (r->rq_e0 || (r->rq_e0 = get_event(r))) && (r->rq_e1 || (r->rq_e1 = get_event(r)));
+   if (timed) HIP_TRY(hipEventRecord(r->rq_e0, qs));
+   if ((rc = launch_kernel_ptr(kernel, dim3(blocks), dim3(MDH_BLOCK), lds_bytes(r), qs, r->ks, a)) != MDH_OK) return rc; // (no park rows)
+   HIP_TRY(hipGetLastError());
+   if (timed) HIP_TRY(hipEventRecord(r->rq_e1, qs));
+   r->rq_timed = timed;
+   if ((rc = table_release(r, qs)) != MDH_OK) return rc;
+   HIP_TRY(hipEventRecord(r->ev_sq_done.ev, qs));
+   HIP_TRY(hipStreamWaitEvent(r->stream, r->ev_sq_done.ev, 0));
+   if (caller != qs) HIP_TRY(hipStreamWaitEvent(caller, r->ev_sq_done.ev, 0)); // the sums are there for the caller's stream
+   return MDH_OK;
+}
+extern "C" int32_t mdh_path_trace(mdh_renderer *r, int32_t n, const float *org, const float *dir, uint32_t seed, uint32_t id_first, int32_t sample_first,
+                                  int32_t sample_count, int32_t bounces, float *rgb_accum, int32_t *hit_out, int32_t *index_out, float *t_out)
+{
+   int rc = path_trace_check(r, n, org, dir, sample_first, sample_count, bounces, rgb_accum);
+   if (rc != MDH_OK) return rc;
+   {
+      bool ok = true;
+      for (size_t i = 0; i < (size_t)n; ++i) ok = ok && path_ray_valid(org[3 * i], org[3 * i + 1], org[3 * i + 2], dir[3 * i], dir[3 * i + 1], dir[3 * i + 2]); // (the lanes' predicate)
+      if (!ok) return seterr(MDH_E_INVALID, "a ray is not finite, starts beyond 1024, has a direction component beyond 2 or a direction of zero");
+   }
+   if (n == 0 || sample_count == 0) return MDH_OK;
+   hipStream_t qs = nullptr;
+   if ((rc = shade_rays_begin(r, &qs)) != MDH_OK) return rc;
+   float *base = nullptr;
+   size_t cap = 0;
+   if ((rc = rays_buffer(r, (size_t)n, qs, &base, &cap)) != MDH_OK) return rc;
+   PathTraceArgs a;
+   a.n = n; a.bounces = bounces; a.seed = seed; a.id_first = id_first; a.sample_first = sample_first; a.sample_count = sample_count;
+   a.org = base; a.dir = base + 3 * cap;
+   a.hit = (int *)(base + 7 * cap); a.index = (int *)(base + 8 * cap); a.t = base + 9 * cap;
+   a.rgb = base + 11 * cap;
+   HIP_TRY(hipMemcpyAsync(base, org, (size_t)n * 12, hipMemcpyHostToDevice, qs));
+   HIP_TRY(hipMemcpyAsync(base + 3 * cap, dir, (size_t)n * 12, hipMemcpyHostToDevice, qs));
+   HIP_TRY(hipMemcpyAsync(a.rgb, rgb_accum, (size_t)n * 12, hipMemcpyHostToDevice, qs)); // (the sums so far)
+   if ((rc = path_trace_run(r, a, qs, qs)) != MDH_OK) return rc;
+   HIP_TRY(hipMemcpyAsync(rgb_accum, a.rgb, (size_t)n * 12, hipMemcpyDeviceToHost, qs));
+   if (hit_out) HIP_TRY(hipMemcpyAsync(hit_out, a.hit, (size_t)n * 4, hipMemcpyDeviceToHost, qs));
+   if (index_out) HIP_TRY(hipMemcpyAsync(index_out, a.index, (size_t)n * 4, hipMemcpyDeviceToHost, qs));
+   if (t_out) HIP_TRY(hipMemcpyAsync(t_out, a.t, (size_t)n * 4, hipMemcpyDeviceToHost, qs));
+   return ray_query_wait(r);
+}
+extern "C" int32_t mdh_path_trace_device(mdh_renderer *r, int32_t n, const float *org, const float *dir, uint32_t seed, uint32_t id_first, int32_t sample_first,
+                                         int32_t sample_count, int32_t bounces, float *rgb_accum, int32_t *hit_out, int32_t *index_out, float *t_out, void *stream)
+{
+   int rc = path_trace_check(r, n, org, dir, sample_first, sample_count, bounces, rgb_accum);
+   if (rc != MDH_OK) return rc;
+   HIP_TRY(hipSetDevice(r->device));
+   const size_t w = (size_t)n * 4;
+   const RayArray arrays[] = {{org, 3 * w, "origins"}, {dir, 3 * w, "directions"}, {rgb_accum, 3 * w, "colour sums"}, {hit_out, w, "hit"},
+                              {index_out, w, "index"}, {t_out, w, "t"}};
+   for (const RayArray &ra : arrays)
+      if ((rc = ray_array_check(r, ra)) != MDH_OK) return rc;
+   if (n == 0 || sample_count == 0) return MDH_OK;
+   hipStream_t qs = nullptr;
+   if ((rc = shade_rays_begin(r, &qs)) != MDH_OK) return rc;
+   PathTraceArgs a;
+   a.n = n; a.bounces = bounces; a.seed = seed; a.id_first = id_first; a.sample_first = sample_first; a.sample_count = sample_count;
+   a.org = org; a.dir = dir; a.rgb = rgb_accum;
+   a.hit = hit_out; a.index = index_out; a.t = t_out;
+   return path_trace_run(r, a, qs, (hipStream_t)stream);
+}
+// the sampler by itself, on the host over the functions the lanes call (mdh_path.h): no launch, no renderer
+extern "C" int32_t mdh_path_scatter(int32_t n, const float *dir, const float *normal, const float *roughness, uint32_t seed, uint32_t id_first, int32_t sample,
+                                    int32_t bounce, float *dir_out)
+{
+   if (n < 0 || sample < 0 || bounce < 0 || (n > 0 && (!dir || !normal || !roughness || !dir_out))) return seterr(MDH_E_INVALID, "bad argument");
+   for (size_t i = 0; i < (size_t)n; ++i)
+      path_scatter_at(dir + 3 * i, normal + 3 * i, roughness[i], seed, id_first + (uint32_t)i, (uint32_t)sample, (uint32_t)bounce, dir_out + 3 * i);
+   return MDH_OK;
+}
 // ------------------------------------------------------------------ lighting a host's points
 // mdh_shade_points, mdh_shade_points_device: the light that arrives at n points of the host's -- pixel_color_probes from the
 // hit on (mode 0), direct light times occlusion (mode 2), or sample_irradiance alone (mode 3) -- through k_point_shade
@@ -4364,8 +4482,10 @@ extern "C" int32_t mdh_diag_waves(unsigned long long *out, int32_t n_waves)
 // order the code object holds them; a description that names none of them is an error of the caller, never another kernel.
 // (k_screen<16, 2>, <6, 0> and <7, 0> are built and never picked: the census of the rooms has no mode-2 variant of its own and
 //  scenes with user-defined kinds get the power-of-two addressing from hiprtc only -- pick_kernel)
+static const void *kernel_ptr_path(const PassKernel &k);
 static const void *kernel_ptr(const PassKernel &k)
 {
+   if (k.family == GK_k_path_trace) return kernel_ptr_path(k); // (the newest family, named behind this function)
 #define MDH_K(FAMILY, PF, ...) if (k.family == GK_##FAMILY && k.pf == (PF)) return (const void *)(__VA_ARGS__);
 #define MDH_RAD(PF) if (k.family == GK_k_radiance && k.pf == (PF) && k.rec == 0) return (const void *)(k.small ? k_radiance<PF, true> : k_radiance<PF, false>);
 // (MDH_OPT_RADIANCE_REPLAY: the recording and the replaying kernel of a variant, behind everything older)
@@ -4435,4 +4555,14 @@ static const void *kernel_ptr(const PassKernel &k)
 #undef MDH_RS
 #undef MDH_SH
 #undef MDH_PT
+}
+// ... and the path tracer along a host's rays (mdh_path_trace, mdh_path_trace_device), the newest family: kernel_ptr hands its
+// descriptions on to this function, which is defined behind it, so that k_path_trace is first named behind every other kernel
+// and the code object keeps the order of everything older
+static const void *kernel_ptr_path(const PassKernel &k)
+{
+#define MDH_PATH(PF) if (k.pf == (PF)) return (const void *)k_path_trace<PF>;
+   MDH_PATH(0) MDH_PATH(1) MDH_PATH(9) MDH_PATH(64) MDH_PATH(65) MDH_PATH(73) MDH_PATH(192)
+   return nullptr;
+#undef MDH_PATH
 }

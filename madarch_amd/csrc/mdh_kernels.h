@@ -1974,6 +1974,163 @@ template <int PART, int MODE> __global__ __launch_bounds__(MDH_BLOCK, MDH_OCC(PA
       c = F3(spow(sdiv(c.x, c.x + 1.0f), 0.4545f), spow(sdiv(c.y, c.y + 1.0f), 0.4545f), spow(sdiv(c.z, c.z + 1.0f), 0.4545f));
    a2.rgb[3 * q] = c.x; a2.rgb[3 * q + 1] = c.y; a2.rgb[3 * q + 2] = c.z;
 }
+
+// mdh_path_trace, mdh_path_trace_device (mdh_api.hip): a path tracer along rays of the host's, the ground truth the probes are
+// an approximation of.  One ray per lane, 64 consecutive rays per wavefront; PART is the scene's general variant, as in
+// k_ray_query.  The estimator for one sample of one ray -- the reference's glsl/render_path.glsl, which it never includes:
+//    mask = 1, rgb = 0;  up to bounces + 1 segments, each march_plain to max_dist;
+//    a miss adds mask * sky (dir) (render_probes.glsl:287) and ends the path;
+//    a hit runs sdf_info / primitive_info as the pixel program does, adds mask * compute_direct_lighting (lighting.glsl:1-40,
+//    direct specular on: path_direct below), multiplies the mask by the albedo, and goes on from P + (N * MDH_MIN_STEP) * 5
+//    -- where the shadow rays start -- along path_scatter's direction (mdh_path.h); a direction that is not finite ends the path.
+// THREE DEVIATIONS from render_path.glsl, which cannot run as written: the sky is MASKED (the file adds it unmasked), it is
+// added ONCE (the file adds it again for every bounce that is left), and the next ray's origin is OFFSET (the file starts it on
+// the surface it just hit, where the first step is below epsilon).  The random numbers are path_u01's, not fract (sin ..).
+// A lane adds its samples sample_first .. sample_first + sample_count - 1 to rgb[ray] in that order, starting from what the
+// array holds: a run of samples split over two calls has the bits of one call.
+// THE LOOP IS FLAT: it runs over segments, not over samples x bounces.  In one iteration every lane does the next segment of
+// its own path, whichever sample and bounce that is; a lane whose path has ended begins its next sample while its neighbours
+// take their next bounce, and the wavefront ends when all lanes have used up their samples.  No atomics, no shared counter, and
+// a lane runs the sequence of operations it would run alone: no bit depends on its neighbours.  (MDH_PATH_LOCKSTEP, a
+// switch of scripts/bench_path_trace.py's build only: the wavefront waits for its slowest path before the next sample.)
+// No stall guard: a lane tests its ray first (path_ray_valid) and the host has tested the scene and the bounces; a ray that
+// fails is answered with the quiet NaN in all three colours, hit = -1, index = -1, t = 0.  The optional outputs describe the
+// primary segment.  No atlas is read, NO VOLUMETRICS, no occlusion term, no indirect specular.  stage_table's barrier is the only one.
+#include "mdh_path.h"
+#ifndef MDH_PATH_LOCKSTEP
+#define MDH_PATH_LOCKSTEP 0
+#endif
+struct PathTraceArgs {
+   int n;
+   int bounces;              // 0 .. MDH_PATH_MAX_BOUNCES
+   unsigned seed, id_first;  // ray i has id id_first + i
+   int sample_first, sample_count;
+   const float *org, *dir;   // 3 n each
+   float *rgb;               // 3 n, in and out: the sums
+   int *hit, *index;         // n each, or null
+   float *t;                 // n, or null
+};
+// compute_direct_lighting (lighting.glsl:1-40) at P with normal N, seen along rd: the light loop of shade_structured
+// (mdh_march.h) for its first point with direct specular on -- the shared first step, null_light in front of the BRDF, the
+// shadow march with min_raw, sdiv3 -- as a lane's own function: no park rows, no wave-wide ballots
+template <int PART> MDH_DEV f3 path_direct(const KScene &sc, f3 P, f3 N, f3 from_off, f3 rd, const Material &m)
+{
+   const float sd0 = MDH_SHARE_FIRST_STEP ? sdf<PART>(sc, from_off) : 0.0f;
+   f3 Lo = F3(0.0f, 0.0f, 0.0f);
+#pragma unroll 1
+   for (int li = 0; li < sc.total_lights; ++li) {
+      f3 L;
+      float L_dist;
+      const f3 radiance = sample_light<false>(sc, li, P, N, L, L_dist);
+      const float NdotL = max_(dot(N, L), 0.0f);
+      f3 contrib = F3(0.0f, 0.0f, 0.0f); // (a light that is dark here or behind the surface: +0, null_light)
+      if (!(MDH_NULL_BRDF && null_light(-rd, L, NdotL, radiance, m))) {
+         f3 kD, kS;
+         cook_torrance(N, -rd, L, NdotL, m.albedo, m.metallic, m.roughness, kD, kS);
+         contrib = ((sdiv3(kD * m.albedo, MDH_PI) + kS) * radiance) * NdotL;
+      }
+      float shadows = 0.0f;
+      const bool lit = MDH_SKIP_NULL_RAYS ? (contrib.x != 0.0f || contrib.y != 0.0f || contrib.z != 0.0f) : true;
+      if (NdotL > MDH_EPS && lit) { // softshadows, raymarching.glsl:4-23
+         float res = 1.0f, prev = 1e20f, total = 0.0f;
+         bool blocked = false;
+         bool first = MDH_SHARE_FIRST_STEP != 0;
+         while (total < L_dist) {
+            const float dist = first ? sd0 : sdf<PART>(sc, from_off + L * total);
+            first = false;
+            if (dist < MDH_EPS) { blocked = true; break; }
+            const float y = dist * dist / (2.0f * prev);
+            const float d = sqrt_(dist * dist - y * y);
+            res = min_raw(res, 64.0f * d / max_(0.0f, total - y));
+            prev = dist;
+            total += dist;
+         }
+         shadows = blocked ? 0.0f : res;
+      }
+      Lo = Lo + contrib * shadows;
+   }
+   return Lo;
+}
+template <int PART> __global__ __launch_bounds__(MDH_BLOCK) void k_path_trace(KScene sc, PathTraceArgs a)
+{
+   static_assert(!(PART & (MDH_PF_CUSTOM | MDH_PF_POW2 | MDH_PF_ROOM | MDH_PF_PSMALL)), "ray queries: the general variants of built-in kinds");
+   stage_table(sc); // (the kernel's only barrier: lanes past n leave behind it)
+   const long lin = (long)blockIdx.x * MDH_BLOCK + threadIdx.x;
+   if (lin >= (long)a.n) return;
+   const size_t q = (size_t)lin;
+   const f3 org = F3(a.org[3 * q], a.org[3 * q + 1], a.org[3 * q + 2]);
+   const f3 dir = F3(a.dir[3 * q], a.dir[3 * q + 1], a.dir[3 * q + 2]);
+   if (!path_ray_valid(org.x, org.y, org.z, dir.x, dir.y, dir.z)) { // not traced
+      const float bad = __uint_as_float(MDH_RS_BAD_BITS);
+      a.rgb[3 * q] = bad; a.rgb[3 * q + 1] = bad; a.rgb[3 * q + 2] = bad;
+      if (a.hit) a.hit[q] = -1;
+      if (a.index) a.index[q] = -1;
+      if (a.t) a.t[q] = 0.0f;
+      return;
+   }
+   const unsigned id = a.id_first + (unsigned)q;
+   f3 acc = F3(a.rgb[3 * q], a.rgb[3 * q + 1], a.rgb[3 * q + 2]);
+   int p_hit = 0, p_index = -1; // the primary segment (the same in every sample)
+   float p_t = 0.0f;
+   // the lane's path: its sample, the bounce of its next segment, the ray of that segment, what it has gathered
+   int sample = a.sample_first, bounce = 0;
+   const int sample_end = a.sample_first + a.sample_count;
+   f3 ro = org, rd = dir, mask = F3(1.0f, 1.0f, 1.0f), rgb = F3(0.0f, 0.0f, 0.0f);
+#if MDH_PATH_LOCKSTEP
+   bool waiting = false; // the lane's sample has ended and a neighbour's has not
+#endif
+#pragma unroll 1
+   while (sample < sample_end) { // one segment per iteration
+#if MDH_PATH_LOCKSTEP
+      if (__ballot(!waiting) == 0ull) waiting = false; // (every lane has ended its sample: the next one, together)
+      if (waiting) continue;
+#endif
+      float t;
+      int steps;
+      const bool h = march_plain<PART>(sc, ro, rd, sc.max_dist, t, steps);
+      bool ended = true;
+      if (!h) { // render_probes.glsl:287
+         const float s = rd.y * 0.7f;
+         rgb = rgb + mask * F3(0.30f - s, 0.36f - s, 0.60f - s);
+      } else {
+         const f3 P = ro + rd * t;
+         int index = -1, pm;
+         f3 N;
+         (void)sdf_info<PART>(sc, P, index);
+         primitive_info<false, (PART & MDH_PF_GTAB) != 0>(sc, index, P, N, pm);
+         if (bounce == 0) { p_hit = 1; p_index = index; p_t = t; }
+         const Material m = get_material(sc, pm);
+         const f3 from_off = P + (N * MDH_MIN_STEP) * 5.0f;
+         rgb = rgb + mask * path_direct<PART>(sc, P, N, from_off, rd, m);
+         mask = mask * m.albedo;
+         if (bounce < a.bounces) {
+            const float dv[3] = {rd.x, rd.y, rd.z}, nv[3] = {N.x, N.y, N.z};
+            float out[3];
+            path_scatter_at(dv, nv, m.roughness, a.seed, id, (unsigned)sample, (unsigned)bounce, out);
+            if (path_dir_finite(out[0], out[1], out[2])) {
+               ro = from_off;
+               rd = F3(out[0], out[1], out[2]);
+               ++bounce;
+               ended = false;
+            }
+         }
+      }
+      if (ended) { // the sample is complete: the next one starts at the primary ray
+         acc = acc + rgb;
+         ++sample;
+         bounce = 0;
+         ro = org; rd = dir;
+         mask = F3(1.0f, 1.0f, 1.0f); rgb = F3(0.0f, 0.0f, 0.0f);
+#if MDH_PATH_LOCKSTEP
+         waiting = true;
+#endif
+      }
+   }
+   a.rgb[3 * q] = acc.x; a.rgb[3 * q + 1] = acc.y; a.rgb[3 * q + 2] = acc.z;
+   if (a.hit) a.hit[q] = p_hit;
+   if (a.index) a.index[q] = p_index;
+   if (a.t) a.t[q] = p_t;
+}
 #endif
 
 // ---------------------------------------------------------------------- the window's pixels

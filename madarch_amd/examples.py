@@ -268,5 +268,26 @@ def lit_points(R=None, Count=64, Frames=4, Radius=1.6, Binding=None):
     return pos, nrm, rgb
 
 
+def path_traced_view(R, Width, Height, Samples=64, Bounces=3, Seed=1, Slice=16):
+    """What renderer R's camera sees, twice over the same rays (Camera_Rays): path traced -- Renderer.Path_Trace in slices of
+    `Slice` samples, the sums handed back in, divided by the count -- and as the frame itself shows it in mode 0 (the pixel
+    program along the frame's rays: direct light, the probes' irradiance, the reflection's tap, occlusion).  Both go through
+    draw_screen.glsl:29 on the host.  The first is the ground truth the probes approximate; render some frames before the call
+    so that they have settled.  -> (path traced, frame), each (Height, Width, 3), and the two linear images likewise."""
+    org, drs = R.Camera_Rays(Width, Height)
+    sums, first = None, 0
+    while first < Samples:
+        count = min(int(Slice), Samples - first)
+        sums = R.Path_Trace(org, drs, Seed=Seed, Sample_First=first, Sample_Count=count, Bounces=Bounces, Rgb_Accum=sums)["rgb"]
+        first += count
+    traced = (sums if sums is not None else np.zeros_like(org)).astype(np.float64) / max(int(Samples), 1)
+    frame = R.Shade_Rays(org, drs, Mode=0, Tone_Map=False)["rgb"].astype(np.float64)
+
+    def tone(x):  # draw_screen.glsl:29
+        with np.errstate(invalid="ignore"):
+            return ((x / (x + 1.0)) ** float(np.float32(0.4545))).astype(np.float32).reshape(Height, Width, 3)
+    return tone(traced), tone(frame), traced.reshape(Height, Width, 3), frame.reshape(Height, Width, 3)
+
+
 SCENES = {"simple_scene": simple_scene, "global_illumination": global_illumination,
           "light_shafts": light_shafts, "obj_mesh": obj_mesh}

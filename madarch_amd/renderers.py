@@ -340,6 +340,81 @@ class Renderer:
         out.reshape(-1)[:] = res
         return out
 
+    # ---- ground truth for the probes: a path tracer along rays of the host's (the reference's render_path.glsl made to run)
+    MAX_BOUNCES = 6
+
+    @staticmethod
+    def _path_args(Seed, Id_First, Sample_First, Sample_Count, Bounces):
+        """ValueError before any library call"""
+        if not 0 <= int(Bounces) <= Renderer.MAX_BOUNCES:
+            raise ValueError("Bounces: paths take 0 to %d bounces, not %s" % (Renderer.MAX_BOUNCES, Bounces))
+        if int(Sample_First) < 0 or int(Sample_Count) < 0 or int(Sample_First) + int(Sample_Count) > 2 ** 31 - 1:
+            raise ValueError("samples %s .. + %s: both at least 0, their sum below 2^31" % (Sample_First, Sample_Count))
+        for what, v in (("Seed", Seed), ("Id_First", Id_First)):
+            if not 0 <= int(v) < 2 ** 32:
+                raise ValueError("%s: a 32-bit unsigned word, not %s" % (what, v))
+        return int(Seed), int(Id_First), int(Sample_First), int(Sample_Count), int(Bounces)
+
+    def Path_Trace(self, Origins, Directions, Seed=0, Id_First=0, Sample_First=0, Sample_Count=1, Bounces=3, Rgb_Accum=None):
+        """{rgb, hit, index, t}: rgb is Rgb_Accum (zeros when None; never modified) plus the sum of samples Sample_First ..
+        Sample_First + Sample_Count - 1 of the path tracer along every ray -- direct light at every hit, the masked sky at a
+        miss, up to Bounces bounces; linear, to be divided by the number of samples.  Ray i has id Id_First + i and its random
+        numbers depend on (Seed, id, sample, bounce) alone; a run of samples split over calls has the bits of one call.  hit,
+        index and t describe the primary segment.  No fog, no atlas, no occlusion."""
+        seed, id0, s0, sc, nb = self._path_args(Seed, Id_First, Sample_First, Sample_Count, Bounces)
+        org, drs, _ = self._rays(Origins, Directions)
+        n = len(org)
+        if Rgb_Accum is None:
+            rgb = np.zeros((n, 3), np.float32)
+        else:
+            rgb = np.array(Rgb_Accum, dtype=np.float32, order="C")
+            if rgb.shape != (n, 3):
+                raise ValueError("Rgb_Accum: one colour per ray, not %s for %d rays" % (rgb.shape, n))
+        out = {"rgb": rgb, "hit": np.zeros(n, np.int32), "index": np.full(n, -1, np.int32), "t": np.zeros(n, np.float32)}
+        self._b.check(self._b.path_trace(self._h, n, _fp(org), _fp(drs), seed, id0, s0, sc, nb, _fp(rgb), _fp(out["hit"]),
+                                         _fp(out["index"]), _fp(out["t"])))
+        return out
+
+    def Path_Trace_Device(self, Origins, Directions, Rgb_Accum, Hit=None, Index=None, T=None, Seed=0, Id_First=0, Sample_First=0,
+                          Sample_Count=1, Bounces=3, Stream=0, N=None):
+        """Path_Trace for N rays (default: what Origins holds) in device memory, asynchronous and ordered with `Stream` as
+        Shade_Rays_Device is; the samples are added to Rgb_Accum in place, which stays on the device from call to call.  A ray
+        that is not finite, starts beyond 1024 or has a direction component beyond 2 is not traced: NaN in all three colours,
+        hit = -1, index = -1, t = 0."""
+        seed, id0, s0, sc, nb = self._path_args(Seed, Id_First, Sample_First, Sample_Count, Bounces)
+        n = self._ray_count(Origins, N)
+        dev = self._device_array
+        args = [dev(Origins, "Origins", 3 * n, "float32"), dev(Directions, "Directions", 3 * n, "float32")]
+        outs = [dev(Rgb_Accum, "Rgb_Accum", 3 * n, "float32"), dev(Hit, "Hit", n, "int32", True), dev(Index, "Index", n, "int32", True),
+                dev(T, "T", n, "float32", True)]
+        self._b.check(self._b.path_trace_device(self._h, n, *args, seed, id0, s0, sc, nb, *outs, C.c_void_p(int(Stream))))
+
+    @staticmethod
+    def Path_Scatter(Directions, Normals, Roughness, Seed=0, Id_First=0, Sample=0, Bounce=0, Binding=None):
+        """(n, 3) directions: where the path of ray Id_First + i goes behind bounce `Bounce` of sample `Sample`, having arrived
+        along Directions[i] at a surface with Normals[i] (any length but 0) and Roughness[i] (a scalar is broadcast).  The
+        sampler of Path_Trace by itself, on the host, the same bits: no launch and no renderer."""
+        b = Binding or B.hip_binding()
+        drs = np.ascontiguousarray(Directions, dtype=np.float32)
+        nrm = np.ascontiguousarray(Normals, dtype=np.float32)
+        if drs.ndim != 2 or drs.shape[1] != 3 or nrm.shape != drs.shape:
+            raise ValueError("directions and normals are (n, 3) arrays of one shape, not %s and %s" % (drs.shape, nrm.shape))
+        n = len(drs)
+        rough = np.asarray(Roughness, dtype=np.float32)
+        if rough.ndim == 0:
+            rough = np.full(n, rough, dtype=np.float32)
+        if rough.shape != (n,):
+            raise ValueError("one roughness per direction: %s for %d" % (rough.shape, n))
+        rough = np.ascontiguousarray(rough)
+        if int(Sample) < 0 or int(Bounce) < 0:
+            raise ValueError("sample %s, bounce %s: both at least 0" % (Sample, Bounce))
+        for what, v in (("Seed", Seed), ("Id_First", Id_First)):
+            if not 0 <= int(v) < 2 ** 32:
+                raise ValueError("%s: a 32-bit unsigned word, not %s" % (what, v))
+        out = np.zeros((n, 3), np.float32)
+        b.check(b.path_scatter(n, _fp(drs), _fp(nrm), _fp(rough), int(Seed), int(Id_First), int(Sample), int(Bounce), _fp(out)))
+        return out
+
     def Render_Pass(self, Pass):
         self._b.check(self._b.render_pass(self._h, int(Pass)))
 
