@@ -28,6 +28,9 @@
 #ifndef MDH_SHARE_TAPS
 #define MDH_SHARE_TAPS 1 // a wavefront whose points share cage cell and normal fetches its eight irradiance taps once (shade_structured)
 #endif
+#ifndef MDH_TWIN_FOLDED
+#define MDH_TWIN_FOLDED 1 // ... and a corner of it folded along y or z takes its twin's weight and visibility bit instead of computing them again
+#endif
 
 struct MachineCfg {
    bool direct_specular;   // M_COMPUTE_DIRECT_SPECULAR
@@ -487,7 +490,7 @@ MDH_DEV unsigned pixel_record_word2(bool hit, bool traced, int index, int vis_bi
 //   k_radiance <0 | POW2, SMALL, REC = 1>    the brute-force scan's recording kernel, small form: 101 SGPRs, 8 -> 7 wavefronts per SIMD.
 constexpr bool null_brdf_screen(int PART, int MODE, bool GBUF, bool ALT, int REC) { return !(GBUF && PART == MDH_PF_POW2 && MODE == 0 && !ALT && REC == 0); }
 constexpr bool null_brdf_radiance(int PART, bool SMALL, int REC) { return !((PART & ~MDH_PF_POW2) == 0 && SMALL && REC == 1); }
-// SHARET: a wavefront's eight irradiance taps fetched once where its lanes share them (MDH_SHARE_TAPS, at the first point's corner
+// SHARET (0, 1; 2 below): a wavefront's eight irradiance taps fetched once where its lanes share them (MDH_SHARE_TAPS, at the first point's corner
 // loop); false where the caller's kernel would pay for it with scratch memory.  Every screen kernel that takes it keeps its
 // wavefronts per SIMD; the eight below gained 16 bytes of scratch per lane and keep the code they had (resource_usage.sh, before
 // against after):
@@ -501,11 +504,29 @@ constexpr bool share_taps_screen(int PART, bool GBUF, int REC)
    return !((PART == 0 && !GBUF && REC == 0) || (PART == MDH_PF_ROOM && REC == 2) || (PART == (MDH_PF_ROOM | MDH_PF_POW2) && !GBUF && REC == 1) ||
             (PART == (MDH_PF_ROOM | MDH_PF_POW2) && GBUF && REC != 2) || (PART == MDH_PF_POW2 && GBUF && REC != 2));
 }
+// SHARET = 2: a sharing wavefront's corner folded along y or z takes its twin's weight and visibility bit (MDH_TWIN_FOLDED; DESIGN.md
+// section 4 item 16).  The screen kernels that share taps take it and keep their scratch memory and their wavefronts per SIMD to
+// the digit -- the benchmark's k_screen <ROOM | POW2, 0, no GBUF, REC 0> 32 bytes and six; two gain one VGPR below their limit --
+// but for seven, which keep the code they had.  Four paid with scratch memory (resource_usage.sh, before against after):
+//   k_screen <0, 0, GBUF, REC 2>                 brute-force scan with the geometry buffer, replaying:  16 -> 32
+//   k_screen <POW2, 0, no GBUF, REC 0>           ... with power-of-two atlases, marching:               16 -> 32
+//   k_screen <POW2, 0, GBUF, REC 2>              ... with the geometry buffer, replaying:               16 -> 32
+//   k_screen <ROOM | POW2, 0, no GBUF, REC 2>    the rooms' census, power-of-two atlases, replaying:    64 -> 96
+// and three paid in a build that held this beside two parts since removed, and were not built with it alone:
+//   k_screen <0, 0, GBUF, REC 0>, k_screen <ROOM, 0, no GBUF, REC 1>, k_screen <ROOM | POW2, 0, GBUF, REC 2>
+// k_ray_shade <0, 0> and k_point_shade <0, 0> share taps too and are left as they are (shade_structured's default): their
+// wavefronts are a caller's rays and points, not tiles of a surface.
+constexpr bool folded_twins_screen(int PART, bool GBUF, int REC)
+{
+   return share_taps_screen(PART, GBUF, REC) &&
+          !((PART == 0 && GBUF && REC != 1) || (PART == MDH_PF_POW2 && !GBUF && REC == 0) || (PART == MDH_PF_POW2 && GBUF && REC == 2) ||
+            (PART == (MDH_PF_ROOM | MDH_PF_POW2) && REC == 2) || (PART == MDH_PF_ROOM && !GBUF && REC == 1));
+}
 // POINT (k_point_shade, mdh_kernels.h: mdh_shade_points): the first shaded point is the caller's -- `from` is the point itself,
 // `dir_in` the direction it is seen along, `pt_normal` and `pt_material` what primitive_info would have said -- and context 0
 // runs no primary march, no arg-min scan and no primitive_info: every valid lane "hits" at its point with index -1, t 0 and
 // no steps, and everything from the offset origin on is the code of a marched hit.  false (every other kernel): nothing changes.
-template <int PART, int MODE, int SPEC, bool QVIS, int REC = 0, bool SHARET = true, bool NULLB = true, bool POINT = false>
+template <int PART, int MODE, int SPEC, bool QVIS, int REC = 0, int SHARET = 1, bool NULLB = true, bool POINT = false>
 MDH_DEV f3 shade_structured(const KScene &sc, const KProbes &pr, const MachineCfg cfg, bool lane_valid, f3 from, f3 dir_in,
                             PrimaryHit &ph, bool &hit, f3 &pos_out, const RayRecord rec = RayRecord{0u, 0u, -1, 0u},
                             const RayRecord rec2 = RayRecord{0u, 0u, -1, 0u}, const f3 pt_normal = F3(0.0f, 0.0f, 0.0f), const int pt_material = 0)
@@ -532,6 +553,9 @@ MDH_DEV f3 shade_structured(const KScene &sc, const KProbes &pr, const MachineCf
    // elimination", at the corner loop below): the screen family's fixed mode over the built-in scans only -- every other
    // instantiation is the code it was
    constexpr bool SHARE_TAPS = MDH_SHARE_TAPS != 0 && SHARET && SPEC == 1 && !QVIS && MODE == 0 && TAP_EARLY && (PART & ~(MDH_PF_ROOM | MDH_PF_POW2)) == 0;
+   // ... and in such a wavefront (item 16) a corner folded along y or z takes the weight and the visibility bit of the corner it
+   // folds onto, kept in four registers
+   constexpr bool TWIN_FOLDED = MDH_TWIN_FOLDED != 0 && SHARET == 2 && SHARE_TAPS && CORNER_UNROLL == 8;
    // the space-partition variants of the screen pass: the shaded point and its normal come back from park rows behind every
    // corner's visibility march (the second point's wait in the rows of its colour and in three rows of their own) and the probe's grid position is derived again there:
    // the lookups of that march need the registers -- kept live across it, these values went to scratch memory eight times per
@@ -770,10 +794,18 @@ MDH_DEV f3 shade_structured(const KScene &sc, const KProbes &pr, const MachineCf
                   }
                   // A corner folded onto its twin along x follows it directly (i - 1): the twin's probe term -- direction,
                   // visibility, weight before the trilinear factor, irradiance tap -- is this corner's, value for value,
-                  // and is still in registers.  (Twins along y and z are two and four corners back: a ring of terms in LDS for
-                  // y was measured at +0.4 %, DESIGN.md.)
+                  // and is still in registers.  (Twins along y and z are two and four corners back: below.)
                   f3 s_keep = F3(0.0f, 0.0f, 0.0f);
                   float w_keep = 0.0f;
+                  // A corner folded onto its twin along y or z (two and four corners back) in a SHARING wavefront: the irradiance
+                  // tap is in the wavefront's row whichever corner asks, so the twin's term is one float -- its weight before the
+                  // trilinear factor -- and its visibility bit.  Corner i keeps its weight in w_fold[i & 3]; the twin b = i & ~folds
+                  // of a later corner is found in w_fold[b & 3] (a corner between them with the same index modulo 4 is b | 4: a twin
+                  // of b itself, with b's weight).  The cell is the wavefront's, so its folds are one scalar: no lane diverges.
+                  // Folds along two or three axes take the same path: b clears every folded bit of y and z, and a corner that
+                  // also folds along x holds what the x-twin in front of it left (twin_prev), which is b's value again.
+                  float w_fold[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+                  const int folds = (TWIN_FOLDED && shared) ? (__builtin_amdgcn_readfirstlane(folded) & 6) : 0;
 #pragma unroll CORNER_UNROLL
                   for (int i = 0; i < 8; ++i) {
                      // best probe: a folded corner has the weight of its twin, which is not strictly larger
@@ -783,6 +815,13 @@ MDH_DEV f3 shade_structured(const KScene &sc, const KProbes &pr, const MachineCf
                      float wpre = 0.0f;                // its weight before the trilinear factor
                      const i3 q = cage_probe(pq, gp, i);
                      const bool twin_prev = TWIN_PREV && irrp && (i & 1) && (folded & 1);
+                     if (TWIN_FOLDED && (i & folds)) {
+                        const ParkLds slot = (ParkLds)(unsigned)(wb + (MDH_PARK_TAPS * MDH_BLOCK + 3 * i) * 4); // (the twin's probe: the same triple)
+                        s_term = F3(slot[0], slot[1], slot[2]);
+                        wpre = (folds & 2) ? w_fold[i & 1] : w_fold[i & 3];
+                        vis_bits |= ((vis_bits >> (i & ~folds)) & 1) << i;
+                        if (!twin_prev) MDH_WORK(0); // (the folded corner's ray, which never took a step, counted as before; an x-twin's never was)
+                     } else
                      if (twin_prev) {
                         s_term = s_keep;
                         wpre = w_keep;
@@ -894,6 +933,7 @@ MDH_DEV f3 shade_structured(const KScene &sc, const KProbes &pr, const MachineCf
                         acc = acc + s_term * weight;
                         accw += weight;
                         if (TWIN_PREV) { s_keep = s_term; w_keep = wpre; }
+                        if (TWIN_FOLDED) w_fold[i & 3] = wpre;
                      }
                      PH_ADD(pt, 6);
                   }
