@@ -283,6 +283,33 @@ package Madarch_HIP is
       Sample, Bounce : int; Dir_Out : System.Address) return Status
      with Import, Convention => C, External_Name => "mdh_path_scatter";
 
+   --  The lights' fog at N points and along N rays of the host's (madarch_hip.h,
+   --  mdh_inscatter_points, mdh_inscatter_rays): the integrand of the visibility pass evaluated
+   --  anywhere, and the scattering pass's serial sum along any ray.  F, Len_Out and Steps_Out may
+   --  be Null_Address; March 0 or 1; at most Inscatter_Max_Steps steps of Step within max_dist.
+   --  A point or ray that is not finite, or a T_Max outside 0 .. max_dist: Status 1 for the batch
+   --  of host arrays, NaN and Steps = -1 for that one of device arrays.
+   Inscatter_Max_Steps : constant int := 4096;
+
+   function Inscatter_Points
+     (R : Handle; N : int; Pos, Dir, F, RGB_Out : System.Address) return Status
+     with Import, Convention => C, External_Name => "mdh_inscatter_points";
+
+   function Inscatter_Points_Device
+     (R : Handle; N : int; Pos, Dir, F, RGB_Out : System.Address;
+      Stream : System.Address) return Status
+     with Import, Convention => C, External_Name => "mdh_inscatter_points_device";
+
+   function Inscatter_Rays
+     (R : Handle; N : int; Org, Dir, T_Max : System.Address; March : int; Step : C_float;
+      RGB_Out, Len_Out, Steps_Out : System.Address) return Status
+     with Import, Convention => C, External_Name => "mdh_inscatter_rays";
+
+   function Inscatter_Rays_Device
+     (R : Handle; N : int; Org, Dir, T_Max : System.Address; March : int; Step : C_float;
+      RGB_Out, Len_Out, Steps_Out : System.Address; Stream : System.Address) return Status
+     with Import, Convention => C, External_Name => "mdh_inscatter_rays_device";
+
    --  One frame on the N GPUs of a node, one process per GPU (madarch_hip.h, mdh_comm_*):
    --  every process creates its Renderer on its own device, rank 0 makes a 128-byte id and
    --  hands it to the others (a file, an environment variable), all call Comm_Init, and

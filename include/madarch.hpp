@@ -483,6 +483,39 @@ class Renderer {
       Check(mdh_path_scatter((int32_t)n, Directions.data(), Normals.data(), Roughness.data(), Seed, Id_First, Sample, Bounce, Out.data()));
       return Out;
    }
+   // ---- the lights' fog at points and along rays of the host's (compute_frustrum_visibility.glsl:8-19, accumulate_scattering.glsl:17-28),
+   // without the froxel grid or the camera it is bound to.  Points: sample_lights (position, direction), times exp (-F tau) where F
+   // (one distance per point) is not empty.  Rays: L = 0; for (f = 0; f < len; f += Step) L = L + inscatter ((dir * f) + org, dir) * exp (-f tau);
+   // Rgb = L * Step; Len is Max_Dists, or with March the distance to what the ray hits where that is shorter; Steps the loop's turns
+   std::vector<float> Inscatter_Points(const std::vector<float> &Positions, const std::vector<float> &Directions, const std::vector<float> &F = std::vector<float>()) const
+   {
+      const size_t n = Ray_Count(Positions, Directions);
+      if (!F.empty() && F.size() != n) throw Constraint_Error("one distance per point");
+      std::vector<float> Rgb(3 * n);
+      Check(mdh_inscatter_points(h_.get(), (int32_t)n, Positions.data(), Directions.data(), F.empty() ? nullptr : F.data(), Rgb.data()));
+      return Rgb;
+   }
+   struct Inscattered { std::vector<float> Rgb, Len; std::vector<int32_t> Steps; };
+   Inscattered Inscatter_Rays(const std::vector<float> &Origins, const std::vector<float> &Directions, const std::vector<float> &Max_Dists, float Step, bool March = false) const
+   {
+      const size_t n = Ray_Count(Origins, Directions);
+      if (Max_Dists.size() != n) throw Constraint_Error("one length per ray");
+      Inscattered o;
+      o.Rgb.resize(3 * n); o.Len.resize(n); o.Steps.resize(n);
+      Check(mdh_inscatter_rays(h_.get(), (int32_t)n, Origins.data(), Directions.data(), Max_Dists.data(), March ? 1 : 0, Step, o.Rgb.data(), o.Len.data(), o.Steps.data()));
+      return o;
+   }
+   // ... for arrays in memory the device addresses, asynchronous and ordered with Stream as Raycast_Device is.  F, Len and Steps may be null.
+   // A point or ray that is not finite, or a length outside 0 .. max_dist: NaN in Rgb and Len, Steps = -1
+   void Inscatter_Points_Device(int32_t N, const float *Positions, const float *Directions, float *Rgb, const float *F = nullptr, void *Stream = nullptr) const
+   {
+      Check(mdh_inscatter_points_device(h_.get(), N, Positions, Directions, F, Rgb, Stream));
+   }
+   void Inscatter_Rays_Device(int32_t N, const float *Origins, const float *Directions, const float *Max_Dists, float Step, float *Rgb, float *Len = nullptr,
+                              int32_t *Steps = nullptr, bool March = false, void *Stream = nullptr) const
+   {
+      Check(mdh_inscatter_rays_device(h_.get(), N, Origins, Directions, Max_Dists, March ? 1 : 0, Step, Rgb, Len, Steps, Stream));
+   }
    void Update_Partitioning(Partitioning_Update_Method Method = GPU_Fast) const { Check(mdh_update_partitioning(h_.get(), (int32_t)Method)); } // renderers.adb:757-775
    // ---- headless additions
    std::vector<float> Read_Framebuffer() const // replaces Swap_Buffers: H*W*3 floats, row 0 = top

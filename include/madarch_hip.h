@@ -628,7 +628,8 @@ int32_t mdh_ray_query_wait(mdh_renderer *r);
  * rgb_out (3 n floats) is required; hit_out (0 / 1), index_out, t_out and steps_out may be NULL and carry the meaning and
  * the numbering of mdh_read_gbuffer.
  * NO VOLUMETRICS: the fog of glsl/volumetrics.glsl:34-54 is looked up by the fragment's screen position, which a free ray
- * does not have -- the query never composes fog, whatever the renderer's volumetric settings.
+ * does not have -- the query never composes fog, whatever the renderer's volumetric settings.  (The fog along a free ray
+ * is a call of its own: mdh_inscatter_rays below, which a host composes with this call's linear colour.)
  * The call reads the scene committed at the call, pending edits included, and the atlas set a
  * mdh_render_pass (MDH_PASS_SCREEN) issued at the same moment would read: it runs behind the passes that write that set, and
  * no later frame rewrites the set before the query's kernel has ended.  It edits nothing: the probe-settle run and the
@@ -717,7 +718,7 @@ int32_t mdh_primitive_material(mdh_renderer *r, int32_t n, const int32_t *index,
  * rgb_accum (3 n floats, linear, IN AND OUT) holds sums: the call adds samples sample_first .. sample_first + sample_count - 1
  * to what the array holds, in that order, so a run of samples split over several calls has the bits of one call; the host
  * divides by the count.  hit_out (0 / 1), index_out and t_out may be NULL and describe the primary segment, as mdh_shade_rays'.
- * NO VOLUMETRICS: the query never composes fog.  It reads no atlas, and MDH_OPT_AO_STEPS and MDH_OPT_INDIRECT_SPECULAR do
+ * NO VOLUMETRICS: the query never composes fog (mdh_inscatter_rays below gathers it along a ray).  It reads no atlas, and MDH_OPT_AO_STEPS and MDH_OPT_INDIRECT_SPECULAR do
  * not enter it.  Otherwise the contract is mdh_shade_rays': the call runs on the query stream behind the same fences, reads
  * the scene committed at the call, pending edits included, and edits nothing: the probe-settle run and both replays go on
  * across it.  n = 0 or sample_count = 0 is MDH_OK without a launch.  Every refusal happens before a launch:
@@ -749,6 +750,53 @@ int32_t mdh_path_trace_device(mdh_renderer *r, int32_t n, const float *org_xyz, 
  * cancels) ends the path in mdh_path_trace.  MDH_E_INVALID: n, sample or bounce below 0, a null array with n > 0. */
 int32_t mdh_path_scatter(int32_t n, const float *dir_xyz, const float *normal_xyz, const float *roughness, uint32_t seed,
                          uint32_t id_first, int32_t sample, int32_t bounce, float *dir_out);
+
+/* The lights' fog for points and rays of the host's: the participating medium of glsl/volumetrics.glsl without the froxel
+ * grid, the screen-space scattering texture or the pinhole camera they are bound to.  All arrays are host memory; positions,
+ * origins and directions are 3 n floats and a direction is used as given (not normalised), as in the shaders.
+ *
+ * mdh_inscatter_points: rgb_out[i] = sample_lights (pos_i, dir_i) of glsl/compute_frustrum_visibility.glsl:8-19 -- over all
+ * lights in the light loop's order, result += ((radiance * (exp (-L_dist tau) * visibility)) * tau) *
+ * henvey_greenstein_phase (L, dir), with sample_light's normal (1, 0, 0) and tau = 0.1: operation for operation what the
+ * visibility pass stores for a froxel, so a froxel's own sample point and direction give the froxel texture's bits.  With f
+ * given (n floats; may be NULL) the result is multiplied by exp (-f_i tau), one multiplication per channel: the product
+ * the scattering pass forms per step, with the library's exp, so that a host can rebuild a ray's sum.
+ *
+ * mdh_inscatter_rays: the serial loop of glsl/accumulate_scattering.glsl:17-28 with the integrand evaluated, not tapped:
+ *     len_i = march ? min (length (to - org), tmax_i) : tmax_i
+ *             (to = org + dir * tmax_i; the shaders' raycast to the scene's max_dist, on a hit to = org + dir * t)
+ *     L = 0;  for (f = 0; f < len_i; f += step)  L = L + inscatter ((dir * f) + org, dir) * exp (-f tau)
+ *     rgb_out[i] = L * step;  len_out[i] = len_i;  steps_out[i] = the loop's turns
+ * in fp32 and in this order: f runs through the values of repeated addition, not through k * step, and the sample point is
+ * formed as (dir * f) + org per component.  len_out and steps_out may be NULL.  The answer does not depend on the froxel or
+ * scattering settings and needs no volumetrics in the renderer.  A scene without lights answers zeros.
+ *
+ * The contract is the ray queries' (mdh_raycast above): the calls run on the query stream beside the frames in flight, see
+ * pending edits, go through the space partition or the triangle BVH where the scene has one, read no atlas and edit
+ * nothing: the probe-settle run and both replays go on across them.  mdh_ray_query_time times their kernel under
+ * MDH_OPT_TIMING.  The visibility rays and the length's march carry the ray queries' stall guard; a ray's work is bounded by
+ * tmax <= max_dist and max_dist / step <= MDH_INSCATTER_MAX_STEPS.  n = 0 is MDH_OK without a launch.  Every refusal
+ * happens before anything is launched:
+ *   MDH_E_INVALID  a null renderer or required array, n < 0, march other than 0 or 1, a step that is not finite or not
+ *                  above 0, max_dist / step above MDH_INSCATTER_MAX_STEPS; a non-finite position, origin, direction or
+ *                  f; a tmax that is not finite, is negative or exceeds the scene's max_dist
+ *   MDH_E_STATE    a scene with a user-defined kind */
+#define MDH_INSCATTER_MAX_STEPS 4096
+int32_t mdh_inscatter_points(mdh_renderer *r, int32_t n, const float *pos_xyz, const float *dir_xyz, const float *f,
+                             float *rgb_out);
+int32_t mdh_inscatter_rays(mdh_renderer *r, int32_t n, const float *org_xyz, const float *dir_xyz, const float *tmax,
+                           int32_t march, float step, float *rgb_out, float *len_out, int32_t *steps_out);
+/* The same calls for arrays the device addresses, under the contract of mdh_raycast_device: asynchronous and ordered with
+ * `stream` (a hipStream_t; NULL: the default stream), mdh_ray_query_wait is the host's wait, and where every array lives
+ * and ends is checked with hipPointerGetAttributes before anything is launched (MDH_E_INVALID; HIP's error state is
+ * cleared).  The host cannot look at the values, so the device does: a point or ray the calls above would refuse the batch
+ * for is not marched -- its rgb and len are the quiet NaN 0x7fc00000 and its steps -1.  Every other one has the bits the
+ * calls above give it. */
+int32_t mdh_inscatter_points_device(mdh_renderer *r, int32_t n, const float *pos_xyz, const float *dir_xyz, const float *f,
+                                    float *rgb_out, void *stream);
+int32_t mdh_inscatter_rays_device(mdh_renderer *r, int32_t n, const float *org_xyz, const float *dir_xyz, const float *tmax,
+                                  int32_t march, float step, float *rgb_out, float *len_out, int32_t *steps_out,
+                                  void *stream);
 
 /* accumulated HIP-event time and launch count of one pass (MDH_OPT_TIMING) */
 int32_t mdh_pass_time(mdh_renderer *r, int32_t pass, double *total_ms, int64_t *launches);

@@ -186,6 +186,12 @@ HIP_ONLY_ABI = {
     "path_trace": (_I, [_P, _I, _P, _P, C.c_uint32, C.c_uint32, _I, _I, _I, _P, _P, _P, _P]),
     "path_trace_device": (_I, [_P, _I, _P, _P, C.c_uint32, C.c_uint32, _I, _I, _I, _P, _P, _P, _P, _P]),
     "path_scatter": (_I, [_I, _P, _P, _P, C.c_uint32, C.c_uint32, _I, _I, _P]),
+    # the lights' fog at n points and along n rays of the host's: (r, n, pos, dir, f or null, rgb[, stream]) and
+    # (r, n, org, dir, tmax, march, step, rgb, len, steps[, stream])
+    "inscatter_points": (_I, [_P, _I, _P, _P, _P, _P]),
+    "inscatter_points_device": (_I, [_P, _I, _P, _P, _P, _P, _P]),
+    "inscatter_rays": (_I, [_P, _I, _P, _P, _P, _I, _F, _P, _P, _P]),
+    "inscatter_rays_device": (_I, [_P, _I, _P, _P, _P, _I, _F, _P, _P, _P, _P]),
 }
 
 

@@ -1796,7 +1796,7 @@ template <typename Args> static int jit_launch(hipFunction_t f, int blocks, int 
 // frames in flight share their CUs' instruction caches (measured: the same kernels at other addresses, each as fast by itself,
 // the headline with frames in flight 0.5 % slower).  The kernels of global residency (MDH_PF_GTAB, mdh_device.h: Geo) come
 // last there: behind everything else they move nothing.
-enum { GK_k_visibility, GK_k_scat_march, GK_k_scattering, GK_k_radiance, GK_k_screen, GK_k_partition_build, GK_k_eval_distance, GK_k_diag_segments, GK_k_ray_query, GK_k_ray_stream, GK_k_ray_shade, GK_k_camera_rays, GK_k_point_shade, GK_k_path_trace };
+enum { GK_k_visibility, GK_k_scat_march, GK_k_scattering, GK_k_radiance, GK_k_screen, GK_k_partition_build, GK_k_eval_distance, GK_k_diag_segments, GK_k_ray_query, GK_k_ray_stream, GK_k_ray_shade, GK_k_camera_rays, GK_k_point_shade, GK_k_path_trace, GK_k_point_inscatter, GK_k_ray_inscatter };
 // WHICH KERNEL A PASS RUNS ("One place that picks a pass's kernel"): every template argument of the
 // pass's kernel, computed once by pick_kernel; kernel_name and kernel_ptr turn the same description into the name hiprtc
 // instantiates and into the kernel of this library.
@@ -1832,7 +1832,8 @@ static const void *table_kernel(const mdh_renderer *r, int family, int what = 0)
    if (family == GK_k_eval_distance && r->bvh_active && !k.ada_div) k.pf |= MDH_PF_BVH;
    // the ray queries march as the passes do: through the space partition (its border as a variant of its own) or the triangle
    // BVH where the scene has one -- the general variants, whose bits the census variants share (pick_kernel)
-   if (family == GK_k_ray_query || family == GK_k_ray_stream || family == GK_k_ray_shade || family == GK_k_point_shade || family == GK_k_path_trace) {
+   if (family == GK_k_ray_query || family == GK_k_ray_stream || family == GK_k_ray_shade || family == GK_k_point_shade || family == GK_k_path_trace ||
+       family == GK_k_point_inscatter || family == GK_k_ray_inscatter) {
       k.what = what;
       if (family == GK_k_ray_shade || family == GK_k_point_shade) { k.what = 0; k.mode = what; } // (mdh_shade_rays, mdh_shade_points: `what` is the call's mode)
       if (r->part.enable) k.pf |= MDH_PF_PART | (r->part.border_behavior != 0 ? MDH_PF_FALLBACK : 0);
@@ -4076,6 +4077,153 @@ extern "C" int32_t mdh_path_scatter(int32_t n, const float *dir, const float *no
       path_scatter_at(dir + 3 * i, normal + 3 * i, roughness[i], seed, id_first + (uint32_t)i, (uint32_t)sample, (uint32_t)bounce, dir_out + 3 * i);
    return MDH_OK;
 }
+// ------------------------------------------------------------------ in-scattering along a host's rays and at its points
+// mdh_inscatter_points, mdh_inscatter_rays and their _device forms: the lights' fog at n points and along n rays of the host's
+// (k_point_inscatter, k_ray_inscatter, mdh_kernels.h).  The plumbing is the RAY QUERIES', not the shade queries': nothing here
+// reads an atlas, so there is no ordering against the frame's passes -- the query stream, ensure_committed (pending edits are
+// seen), table_acquire / table_release, d_rays for host arrays, ray_array_check and the two caller-stream events of
+// ray_stream_run for device arrays, rq_e0 / rq_e1 under MDH_OPT_TIMING.  No settle_bump: nothing is edited.  Every refusal
+// happens before a launch.
+// what both forms of both calls refuse before they look at their arrays (the points' calls have neither march nor step)
+static int inscatter_check(const mdh_renderer *r, int32_t n, bool arrays, bool rays, int32_t march, float step)
+{
+   if (!r) return seterr(MDH_E_INVALID, "null renderer");
+   if (!arrays || n < 0) return seterr(MDH_E_INVALID, "bad argument");
+   if (rays && march != 0 && march != 1) return seterr(MDH_E_INVALID, "march is 0 or 1");
+   if (rays && !rs_inscatter_step_valid(step, r->max_dist)) return seterr(MDH_E_INVALID, "the step is not finite, not above 0, or more than 4096 of it fit into the scene's max_dist");
+   if (has_custom_kinds(r)) return seterr(MDH_E_STATE, "ray queries answer scenes of built-in kinds only");
+   return MDH_OK;
+}
+static int inscatter_begin(mdh_renderer *r, hipStream_t *qs)
+{
+   HIP_TRY(hipSetDevice(r->device));
+   if (!r->query_stream) HIP_TRY(hipStreamCreateWithFlags(&r->query_stream, hipStreamNonBlocking));
+   *qs = r->query_stream;
+   return ensure_committed(r, *qs);
+}
+// enqueues the kernel on the query stream, between the caller's stream's events where the arrays are the caller's
+template <typename Args> static int inscatter_run(mdh_renderer *r, int family, unsigned blocks, const Args &a, hipStream_t qs, hipStream_t caller)
+{
+   int rc;
+   const void *kernel = table_kernel(r, family);
+   if (!kernel) return seterr(MDH_E_INVALID, "no kernel built for this variant");
+   if (caller != qs) { // the arrays are what the caller's stream has made of them at this call
+      HIP_TRY(create_all(r->d_rq_next.sized(1), r->ev_rq_in, r->ev_rq_out)); // (the device queries' group)
+      HIP_TRY(hipEventRecord(r->ev_rq_in.ev, caller));
+      HIP_TRY(hipStreamWaitEvent(qs, r->ev_rq_in.ev, 0));
+   }
+   if ((rc = table_acquire(r, qs)) != MDH_OK) return rc;
+   const bool timed = r->opt_timing && (r->rq_e0 || (r->rq_e0 = get_event(r))) && (r->rq_e1 || (r->rq_e1 = get_event(r)));
+   if (timed) HIP_TRY(hipEventRecord(r->rq_e0, qs));
+   if ((rc = launch_kernel_ptr(kernel, dim3(blocks), dim3(MDH_BLOCK), lds_bytes(r), qs, r->ks, a)) != MDH_OK) return rc;
+   HIP_TRY(hipGetLastError());
+   if (timed) HIP_TRY(hipEventRecord(r->rq_e1, qs));
+   r->rq_timed = timed;
+   if ((rc = table_release(r, qs)) != MDH_OK) return rc;
+   if (caller != qs) { // ... and the answers are there for whatever the caller's stream is given next
+      HIP_TRY(hipEventRecord(r->ev_rq_out.ev, qs));
+      HIP_TRY(hipStreamWaitEvent(caller, r->ev_rq_out.ev, 0));
+   }
+   return MDH_OK;
+}
+static unsigned inscatter_point_blocks(int32_t n) { return (unsigned)(((size_t)n + MDH_BLOCK - 1) / MDH_BLOCK); }
+static unsigned inscatter_ray_blocks(int32_t n) { return (unsigned)(((size_t)n + MDH_BLOCK / MDH_RS_WAVE - 1) / (MDH_BLOCK / MDH_RS_WAVE)); } // (a wavefront per ray)
+extern "C" int32_t mdh_inscatter_points(mdh_renderer *r, int32_t n, const float *pos, const float *dir, const float *f, float *rgb_out)
+{
+   int rc = inscatter_check(r, n, pos && dir && rgb_out, false, 0, 0.0f);
+   if (rc != MDH_OK) return rc;
+   if (!all_finite(pos, 3 * (size_t)n) || !all_finite(dir, 3 * (size_t)n)) return seterr(MDH_E_INVALID, "a point or direction is not finite");
+   if (f) {
+      bool ok = true;
+      for (int32_t i = 0; i < n; ++i) ok = ok && rs_inscatter_f_valid(f[i]); // (the lanes' predicate)
+      if (!ok) return seterr(MDH_E_INVALID, "a distance along the ray is not finite");
+   }
+   if (n == 0) return MDH_OK;
+   hipStream_t qs = nullptr;
+   if ((rc = inscatter_begin(r, &qs)) != MDH_OK) return rc;
+   float *base = nullptr;
+   size_t cap = 0;
+   if ((rc = rays_buffer(r, (size_t)n, qs, &base, &cap)) != MDH_OK) return rc;
+   InscatterPointArgs a;
+   a.n = n;
+   a.pos = base; a.dir = base + 3 * cap; a.f = f ? base + 6 * cap : nullptr;
+   a.rgb = base + 11 * cap;
+   HIP_TRY(hipMemcpyAsync(base, pos, (size_t)n * 12, hipMemcpyHostToDevice, qs));
+   HIP_TRY(hipMemcpyAsync(base + 3 * cap, dir, (size_t)n * 12, hipMemcpyHostToDevice, qs));
+   if (f) HIP_TRY(hipMemcpyAsync(base + 6 * cap, f, (size_t)n * 4, hipMemcpyHostToDevice, qs));
+   if ((rc = inscatter_run(r, GK_k_point_inscatter, inscatter_point_blocks(n), a, qs, qs)) != MDH_OK) return rc;
+   HIP_TRY(hipMemcpyAsync(rgb_out, a.rgb, (size_t)n * 12, hipMemcpyDeviceToHost, qs));
+   return ray_query_wait(r);
+}
+extern "C" int32_t mdh_inscatter_points_device(mdh_renderer *r, int32_t n, const float *pos, const float *dir, const float *f, float *rgb_out, void *stream)
+{
+   int rc = inscatter_check(r, n, pos && dir && rgb_out, false, 0, 0.0f);
+   if (rc != MDH_OK) return rc;
+   HIP_TRY(hipSetDevice(r->device));
+   const size_t w = (size_t)n * 4;
+   const RayArray arrays[] = {{pos, 3 * w, "positions"}, {dir, 3 * w, "directions"}, {f, w, "distances"}, {rgb_out, 3 * w, "colours"}};
+   for (const RayArray &ra : arrays)
+      if ((rc = ray_array_check(r, ra)) != MDH_OK) return rc;
+   if (n == 0) return MDH_OK;
+   hipStream_t qs = nullptr;
+   if ((rc = inscatter_begin(r, &qs)) != MDH_OK) return rc;
+   InscatterPointArgs a;
+   a.n = n;
+   a.pos = pos; a.dir = dir; a.f = f;
+   a.rgb = rgb_out;
+   return inscatter_run(r, GK_k_point_inscatter, inscatter_point_blocks(n), a, qs, (hipStream_t)stream);
+}
+extern "C" int32_t mdh_inscatter_rays(mdh_renderer *r, int32_t n, const float *org, const float *dir, const float *tmax, int32_t march, float step,
+                                      float *rgb_out, float *len_out, int32_t *steps_out)
+{
+   int rc = inscatter_check(r, n, org && dir && tmax && rgb_out, true, march, step);
+   if (rc != MDH_OK) return rc;
+   if (!all_finite(org, 3 * (size_t)n) || !all_finite(dir, 3 * (size_t)n)) return seterr(MDH_E_INVALID, "a ray is not finite");
+   {
+      bool ok = true;
+      for (int32_t i = 0; i < n; ++i) ok = ok && rs_inscatter_tmax_valid(tmax[i], r->max_dist); // (the wavefronts' predicate)
+      if (!ok) return seterr(MDH_E_INVALID, "a ray's length is not finite, is negative or exceeds the scene's max_dist");
+   }
+   if (n == 0) return MDH_OK;
+   hipStream_t qs = nullptr;
+   if ((rc = inscatter_begin(r, &qs)) != MDH_OK) return rc;
+   float *base = nullptr;
+   size_t cap = 0;
+   if ((rc = rays_buffer(r, (size_t)n, qs, &base, &cap)) != MDH_OK) return rc;
+   InscatterRayArgs a;
+   a.n = n; a.march = march; a.step = step;
+   a.org = base; a.dir = base + 3 * cap; a.tmax = base + 6 * cap;
+   a.len = base + 9 * cap; a.steps = (int *)(base + 10 * cap); a.rgb = base + 11 * cap;
+   HIP_TRY(hipMemcpyAsync(base, org, (size_t)n * 12, hipMemcpyHostToDevice, qs));
+   HIP_TRY(hipMemcpyAsync(base + 3 * cap, dir, (size_t)n * 12, hipMemcpyHostToDevice, qs));
+   HIP_TRY(hipMemcpyAsync(base + 6 * cap, tmax, (size_t)n * 4, hipMemcpyHostToDevice, qs));
+   if ((rc = inscatter_run(r, GK_k_ray_inscatter, inscatter_ray_blocks(n), a, qs, qs)) != MDH_OK) return rc;
+   HIP_TRY(hipMemcpyAsync(rgb_out, a.rgb, (size_t)n * 12, hipMemcpyDeviceToHost, qs));
+   if (len_out) HIP_TRY(hipMemcpyAsync(len_out, a.len, (size_t)n * 4, hipMemcpyDeviceToHost, qs));
+   if (steps_out) HIP_TRY(hipMemcpyAsync(steps_out, a.steps, (size_t)n * 4, hipMemcpyDeviceToHost, qs));
+   return ray_query_wait(r);
+}
+extern "C" int32_t mdh_inscatter_rays_device(mdh_renderer *r, int32_t n, const float *org, const float *dir, const float *tmax, int32_t march, float step,
+                                             float *rgb_out, float *len_out, int32_t *steps_out, void *stream)
+{
+   int rc = inscatter_check(r, n, org && dir && tmax && rgb_out, true, march, step);
+   if (rc != MDH_OK) return rc;
+   HIP_TRY(hipSetDevice(r->device));
+   const size_t w = (size_t)n * 4;
+   const RayArray arrays[] = {{org, 3 * w, "origins"}, {dir, 3 * w, "directions"}, {tmax, w, "tmax"}, {rgb_out, 3 * w, "colours"},
+                              {len_out, w, "lengths"}, {steps_out, w, "steps"}};
+   for (const RayArray &ra : arrays)
+      if ((rc = ray_array_check(r, ra)) != MDH_OK) return rc;
+   if (n == 0) return MDH_OK;
+   hipStream_t qs = nullptr;
+   if ((rc = inscatter_begin(r, &qs)) != MDH_OK) return rc;
+   InscatterRayArgs a;
+   a.n = n; a.march = march; a.step = step;
+   a.org = org; a.dir = dir; a.tmax = tmax;
+   a.rgb = rgb_out; a.len = len_out; a.steps = steps_out;
+   return inscatter_run(r, GK_k_ray_inscatter, inscatter_ray_blocks(n), a, qs, (hipStream_t)stream);
+}
+
 // ------------------------------------------------------------------ lighting a host's points
 // mdh_shade_points, mdh_shade_points_device: the light that arrives at n points of the host's -- pixel_color_probes from the
 // hit on (mode 0), direct light times occlusion (mode 2), or sample_irradiance alone (mode 3) -- through k_point_shade
@@ -4483,9 +4631,11 @@ extern "C" int32_t mdh_diag_waves(unsigned long long *out, int32_t n_waves)
 // (k_screen<16, 2>, <6, 0> and <7, 0> are built and never picked: the census of the rooms has no mode-2 variant of its own and
 //  scenes with user-defined kinds get the power-of-two addressing from hiprtc only -- pick_kernel)
 static const void *kernel_ptr_path(const PassKernel &k);
+static const void *kernel_ptr_inscatter(const PassKernel &k);
 static const void *kernel_ptr(const PassKernel &k)
 {
-   if (k.family == GK_k_path_trace) return kernel_ptr_path(k); // (the newest family, named behind this function)
+   if (k.family == GK_k_path_trace) return kernel_ptr_path(k); // (the newer families, named behind this function)
+   if (k.family == GK_k_point_inscatter || k.family == GK_k_ray_inscatter) return kernel_ptr_inscatter(k);
 #define MDH_K(FAMILY, PF, ...) if (k.family == GK_##FAMILY && k.pf == (PF)) return (const void *)(__VA_ARGS__);
 #define MDH_RAD(PF) if (k.family == GK_k_radiance && k.pf == (PF) && k.rec == 0) return (const void *)(k.small ? k_radiance<PF, true> : k_radiance<PF, false>);
 // (MDH_OPT_RADIANCE_REPLAY: the recording and the replaying kernel of a variant, behind everything older)
@@ -4565,4 +4715,13 @@ static const void *kernel_ptr_path(const PassKernel &k)
    MDH_PATH(0) MDH_PATH(1) MDH_PATH(9) MDH_PATH(64) MDH_PATH(65) MDH_PATH(73) MDH_PATH(192)
    return nullptr;
 #undef MDH_PATH
+}
+// ... and behind it the lights' fog at a host's points and along its rays (mdh_inscatter_points, mdh_inscatter_rays and their
+// _device forms), in the same way: the newest kernels last, nothing older moves
+static const void *kernel_ptr_inscatter(const PassKernel &k)
+{
+#define MDH_INS(PF) if (k.pf == (PF)) return k.family == GK_k_point_inscatter ? (const void *)k_point_inscatter<PF> : (const void *)k_ray_inscatter<PF>;
+   MDH_INS(0) MDH_INS(1) MDH_INS(9) MDH_INS(64) MDH_INS(65) MDH_INS(73) MDH_INS(192)
+   return nullptr;
+#undef MDH_INS
 }

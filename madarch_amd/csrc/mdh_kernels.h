@@ -2132,6 +2132,146 @@ template <int PART> __global__ __launch_bounds__(MDH_BLOCK) void k_path_trace(KS
    if (a.index) a.index[q] = p_index;
    if (a.t) a.t[q] = p_t;
 }
+
+// mdh_inscatter_points, mdh_inscatter_rays and their _device forms (mdh_api.hip): the participating medium for points and rays
+// of the host's -- the integrand of k_visibility evaluated anywhere, and the sum of accumulate_scattering.glsl:17-28 along any
+// ray with the integrand EVALUATED at every step where k_scat_fold taps the froxels.  PART is the scene's general variant, as
+// in k_ray_query; nothing of KVolumetrics enters: the answers do not depend on the froxel or scattering settings.
+//    inscatter (pos, dir) = sample_lights of compute_frustrum_visibility.glsl:8-19, operation for operation the light loop of
+//    k_visibility above (sample_light with the normal (1, 0, 0), MDH_TAU), which keeps its own copy: the visibility rays here
+//    carry the stall guard (raycast_visibility<PART, true>: the same bits wherever the passes' march ends), because the points
+//    come from outside;
+//    a ray:  len = march ? min_ (length (to - org), tmax) : tmax, to = org + dir * tmax or, on a hit of the guarded march_plain
+//            to max_dist, org + dir * t (scattering_length with max_depth := tmax);
+//            L = 0; for (f = 0; f < len; f += step) L = L + inscatter ((dir * f) + org, dir) * sexp (-f * MDH_TAU);
+//            rgb = L * step -- fp32, this order, f by repeated addition, THE SAMPLE POINT AS (dir * f) + org.
+// A point or ray the host-array call refuses its batch for (rs_ray_valid, rs_inscatter_tmax_valid, rs_inscatter_f_valid:
+// mdh_ray_stream.h) is not marched: the quiet NaN in rgb and len, -1 steps.  stage_table's barrier is the only one.
+template <int PART> MDH_DEV f3 inscatter(const KScene &sc, f3 pos, f3 dir)
+{
+   f3 result = F3(0.0f, 0.0f, 0.0f);
+#pragma unroll 1
+   for (int l = 0; l < sc.total_lights; ++l) { // sample_lights :8-19
+      f3 L;
+      float L_dist;
+      f3 radiance = sample_light<false>(sc, l, pos, F3(1.0f, 0.0f, 0.0f), L, L_dist);
+      float visibility = raycast_visibility<PART, true>(sc, pos, L, L_dist);
+      f3 L_in = radiance * (sexp(-L_dist * MDH_TAU) * visibility);
+      result = result + (L_in * MDH_TAU) * henvey_greenstein_phase(L, dir);
+   }
+   return result;
+}
+struct InscatterPointArgs {
+   int n;
+   const float *pos, *dir; // 3 n each
+   const float *f;         // n, or null: no factor
+   float *rgb;             // 3 n
+};
+// one point per lane, 64 consecutive points per wavefront
+template <int PART> __global__ __launch_bounds__(MDH_BLOCK) void k_point_inscatter(KScene sc, InscatterPointArgs a)
+{
+   static_assert(!(PART & (MDH_PF_CUSTOM | MDH_PF_POW2 | MDH_PF_ROOM | MDH_PF_PSMALL)), "ray queries: the general variants of built-in kinds");
+   stage_table(sc); // (the kernel's only barrier: lanes past n leave behind it)
+   const long lin = (long)blockIdx.x * MDH_BLOCK + threadIdx.x;
+   if (lin >= (long)a.n) return;
+   const size_t q = (size_t)lin;
+   const f3 pos = F3(a.pos[3 * q], a.pos[3 * q + 1], a.pos[3 * q + 2]);
+   const f3 dir = F3(a.dir[3 * q], a.dir[3 * q + 1], a.dir[3 * q + 2]);
+   const float f = a.f ? a.f[q] : 0.0f;
+   f3 rgb;
+   if (!rs_ray_valid(pos.x, pos.y, pos.z, dir.x, dir.y, dir.z) || !rs_inscatter_f_valid(f)) {
+      const float bad = __uint_as_float(MDH_RS_BAD_BITS);
+      rgb = F3(bad, bad, bad);
+   } else {
+      rgb = inscatter<PART>(sc, pos, dir);
+      if (a.f) rgb = rgb * sexp(-f * MDH_TAU); // (the product k_scat_fold forms)
+   }
+   a.rgb[3 * q] = rgb.x; a.rgb[3 * q + 1] = rgb.y; a.rgb[3 * q + 2] = rgb.z;
+}
+struct InscatterRayArgs {
+   int n;
+   int march;   // 1: the ray ends where it hits the scene
+   float step;
+   const float *org, *dir; // 3 n each
+   const float *tmax;      // n
+   float *rgb;             // 3 n
+   float *len;             // n, or null
+   int *steps;             // n, or null
+};
+// ONE WAVEFRONT PER RAY, four rays per workgroup, the ray's steps spread over the lanes in chunks of 64: lane k of chunk c
+// evaluates step 64 c + k.  A chunk's sample points are neighbours along one line, so their visibility rays to a light pass
+// the same geometry and end together -- the argument of the froxels' 4 x 4 x 4 blocks.  The wavefront keeps f at the chunk's
+// base; a lane reaches its own f by its k additions of `step`, and the next base is the last lane's f + step: the serial
+// loop's values to the bit.  Each lane forms its three products, and the wavefront adds them to its accumulator IN STEP
+// ORDER, one lane's value broadcast at a time (v_readlane): 64 dependent additions per channel and chunk beside 64 x lights
+// visibility marches, and exactly the serial sum.  The lanes with a step are a prefix of the chunk (f grows with the lane);
+// the fold stops at their count, so that a lane past the ray's length adds nothing -- not even +0 into a -0.
+// Everything per ray -- validity, the length's march -- is wave-uniform and done once.  No wavefront reads what another one
+// wrote, no buffer in device memory beside the caller's arrays, one kernel.
+template <int PART> __global__ __launch_bounds__(MDH_BLOCK) void k_ray_inscatter(KScene sc, InscatterRayArgs a)
+{
+   static_assert(!(PART & (MDH_PF_CUSTOM | MDH_PF_POW2 | MDH_PF_ROOM | MDH_PF_PSMALL)), "ray queries: the general variants of built-in kinds");
+   static_assert(MDH_BLOCK % MDH_RS_WAVE == 0, "whole wavefronts");
+   stage_table(sc); // (the kernel's only barrier: wavefronts past n leave behind it)
+   const int lane = threadIdx.x & 63;
+   const long ray = (long)blockIdx.x * (MDH_BLOCK / MDH_RS_WAVE) + (threadIdx.x >> 6);
+   if (ray >= (long)a.n) return; // (wave-uniform)
+   const size_t q = (size_t)ray;
+   const f3 org = F3(a.org[3 * q], a.org[3 * q + 1], a.org[3 * q + 2]);
+   const f3 dir = F3(a.dir[3 * q], a.dir[3 * q + 1], a.dir[3 * q + 2]);
+   const float tmax = a.tmax[q];
+   if (!rs_ray_valid(org.x, org.y, org.z, dir.x, dir.y, dir.z) || !rs_inscatter_tmax_valid(tmax, sc.max_dist)) { // not marched
+      if (lane == 0) {
+         const float bad = __uint_as_float(MDH_RS_BAD_BITS);
+         a.rgb[3 * q] = bad; a.rgb[3 * q + 1] = bad; a.rgb[3 * q + 2] = bad;
+         if (a.len) a.len[q] = bad;
+         if (a.steps) a.steps[q] = -1;
+      }
+      return;
+   }
+   float len = tmax;
+   if (a.march) { // scattering_length with max_depth := tmax; march_plain (mdh_march.h) with the stall guard of the ray queries
+      f3 to = org + dir * tmax;
+      const SdfRegs regs = sdf_regs<(PART & MDH_PF_GTAB) != 0>(sc);
+      float total = 0.0f;
+      bool h = false;
+      while (total < sc.max_dist) {
+         const float dist = sdf<PART>(sc, org + dir * total, regs);
+         if (dist < MDH_EPS) { h = true; break; }
+         if (total + dist == total) break; // stalled: a miss
+         total += dist;
+      }
+      if (h) to = org + dir * total;
+      len = min_(length(to - org), tmax);
+   }
+   len = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(len))); // (every lane holds the same bits: said to the compiler)
+   f3 acc = F3(0.0f, 0.0f, 0.0f);
+   float base = 0.0f; // f of the chunk's first step
+   int count = 0;
+#pragma unroll 1
+   while (base < len) { // (wave-uniform)
+      float f = base;
+      for (int k = 0; k < lane; ++k) f += a.step;
+      const bool live = f < len;
+      f3 pr = F3(0.0f, 0.0f, 0.0f);
+      if (live) pr = inscatter<PART>(sc, dir * f + org, dir) * sexp(-f * MDH_TAU);
+      const int m = __popcll(__ballot(live)); // the chunk's steps: lanes 0 .. m - 1
+      for (int k = 0; k < m; ++k) { // L = L + product, step by step
+         acc.x = acc.x + __int_as_float(__builtin_amdgcn_readlane(__float_as_int(pr.x), k));
+         acc.y = acc.y + __int_as_float(__builtin_amdgcn_readlane(__float_as_int(pr.y), k));
+         acc.z = acc.z + __int_as_float(__builtin_amdgcn_readlane(__float_as_int(pr.z), k));
+      }
+      count += m;
+      if (m < MDH_RS_WAVE) break; // the ray's last step lay in this chunk
+      base = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(f), MDH_RS_WAVE - 1)) + a.step;
+   }
+   if (lane == 0) {
+      acc = acc * a.step;
+      a.rgb[3 * q] = acc.x; a.rgb[3 * q + 1] = acc.y; a.rgb[3 * q + 2] = acc.z;
+      if (a.len) a.len[q] = len;
+      if (a.steps) a.steps[q] = count;
+   }
+}
 #endif
 
 // ---------------------------------------------------------------------- the window's pixels

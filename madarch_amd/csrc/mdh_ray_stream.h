@@ -77,6 +77,23 @@ MDH_RS_FN bool rs_shade_point_valid(float px, float py, float pz, float nx, floa
           material >= 0 && material < n_materials;
 }
 
+// ---------------------------------------------------------------------- which rays and points gather in-scattered light
+// mdh_inscatter_points, mdh_inscatter_rays and their _device forms (k_point_inscatter, k_ray_inscatter, mdh_kernels.h).  Their
+// marches carry the stall guard, so finite inputs are all a point needs; a ray's work is bounded by its length over the
+// step, and that by the call: tmax within [0, max_dist] per ray, max_dist / step at most MDH_INSCATTER_MAX_STEPS per call.
+#ifndef MDH_INSCATTER_MAX_STEPS
+#define MDH_INSCATTER_MAX_STEPS 4096 // (madarch_hip.h names the same value)
+#endif
+// a ray's length: finite, not negative (-0 is 0) and within the scene's max_dist
+MDH_RS_FN bool rs_inscatter_tmax_valid(float tmax, float max_dist) { return rs_finite(tmax) && tmax >= 0.0f && tmax <= max_dist; }
+// the call's step: finite, above 0, and at most MDH_INSCATTER_MAX_STEPS of it within max_dist (a NaN on either side fails)
+MDH_RS_FN bool rs_inscatter_step_valid(float step, float max_dist)
+{
+   return rs_finite(step) && step > 0.0f && max_dist / step <= (float)MDH_INSCATTER_MAX_STEPS;
+}
+// a point's distance along its ray, where the caller gives one
+MDH_RS_FN bool rs_inscatter_f_valid(float f) { return rs_finite(f); }
+
 // ---------------------------------------------------------------------- the hand-out
 MDH_RS_FN int rs_popcount(unsigned long long m) { return __builtin_popcountll(m); }
 // does a wavefront with n_idle idle lanes take new rays?

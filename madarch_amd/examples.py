@@ -245,6 +245,44 @@ def fisheye_view(R, Width, Height, Fov=np.pi, Mode=0, Tone_Map=True):
     return image
 
 
+def foggy_fisheye_view(R, Width, Height, Fov=np.pi, Step=0.1, Rays=None):
+    """fisheye_view with the lights' fog: the same rays (fisheye_view's construction), Renderer.Shade_Rays for the linear
+    colour, t and hit, Renderer.Inscatter_Rays along every ray up to its hit (max_dist on a miss) in steps of `Step`, composed
+    as render_volumetrics composes them -- colour * exp (-len tau) + L -- and tone-mapped (draw_screen.glsl:29) on the host.
+    The shafts of the light_shafts scene through a lens the froxel grid cannot serve.  `Rays` ((origins, directions), each
+    (Width * Height, 3)) replaces the lens: the pinhole's own Camera_Rays give what the frame approximates with froxels.
+    -> (Height, Width, 3) colours, black outside the circle."""
+    r = np.zeros((Height, Width))
+    if Rays is None:
+        org, _ = R.Camera_Rays(Width, Height)
+        o = org.reshape(Height, Width, 3).astype(np.float64)
+
+        def unit(v):
+            return v / np.linalg.norm(v)
+        centre = o.mean(axis=(0, 1))
+        right = unit(o[:, -1].mean(axis=0) - o[:, 0].mean(axis=0)) if Width > 1 else np.array([1.0, 0.0, 0.0])
+        up = unit(o[0].mean(axis=0) - o[-1].mean(axis=0)) if Height > 1 else np.array([0.0, 1.0, 0.0])
+        forward = np.cross(right, up)
+        u, v = (o - centre) @ right, (o - centre) @ up
+        r = np.hypot(u, v)
+        theta = r * (0.5 * Fov)
+        s = np.sin(theta) / np.maximum(r, 1e-12)
+        drs = (s * u)[..., None] * right + (s * v)[..., None] * up + np.cos(theta)[..., None] * forward
+        org, drs = np.broadcast_to(centre, drs.shape).reshape(-1, 3).astype(np.float32), drs.reshape(-1, 3).astype(np.float32)
+    else:
+        org, drs = (np.ascontiguousarray(a, dtype=np.float32).reshape(-1, 3) for a in Rays)
+    seen = R.Shade_Rays(org, drs, Mode=0, Tone_Map=False)
+    max_dist = np.float32(R.Scene.Max_Dist)
+    tmax = np.where(seen["hit"] != 0, np.minimum(seen["t"], max_dist), max_dist).astype(np.float32)
+    fog = R.Inscatter_Rays(org, drs, tmax, Step)
+    tau = 0.1  # volumetrics.glsl:12
+    x = seen["rgb"].astype(np.float64) * np.exp(-fog["len"].astype(np.float64) * tau)[:, None] + fog["rgb"].astype(np.float64)
+    with np.errstate(invalid="ignore"):
+        image = ((x / (x + 1.0)) ** float(np.float32(0.4545))).astype(np.float32).reshape(Height, Width, 3)
+    image[r > 1.0] = 0.0
+    return image
+
+
 def lit_points(R=None, Count=64, Frames=4, Radius=1.6, Binding=None):
     """A ring of `Count` points the host owns -- no primitive of the scene -- round the sphere of the global_illumination
     room, normals pointing away from it, seen from the camera, each with a material of the host's own: what light arrives at

@@ -415,6 +415,66 @@ class Renderer:
         b.check(b.path_scatter(n, _fp(drs), _fp(nrm), _fp(rough), int(Seed), int(Id_First), int(Sample), int(Bounce), _fp(out)))
         return out
 
+    # ---- the lights' fog at points and along rays of the host's (compute_frustrum_visibility.glsl:8-19,
+    # accumulate_scattering.glsl:17-28), without the froxel grid or the camera it is bound to; ray-query plumbing, nothing edited
+    INSCATTER_MAX_STEPS = 4096
+
+    @staticmethod
+    def _inscatter_step(March, Step):
+        """ValueError before any library call (max_dist / Step <= INSCATTER_MAX_STEPS is the library's check: it knows max_dist)"""
+        if isinstance(March, (bool, np.bool_)):
+            March = int(March)
+        if not isinstance(March, (int, np.integer)) or int(March) not in (0, 1):
+            raise ValueError("March: 0 or 1, not %r" % (March,))
+        step = float(Step)
+        if not np.isfinite(step) or not step > 0.0:
+            raise ValueError("Step: finite and above 0, not %r" % (Step,))
+        return int(March), step
+
+    def Inscatter_Points(self, Positions, Directions, F=None):
+        """(n, 3) colours: sample_lights (position, direction) of the visibility pass -- what reaches each point from every
+        light through the fog, times tau and the phase function towards `direction`, used as given.  With F (one distance
+        per point; a scalar is broadcast) each colour is multiplied by exp (-F tau): the scattering pass's product."""
+        pos, drs, f = self._rays(Positions, Directions, F)
+        rgb = np.zeros((len(pos), 3), np.float32)
+        self._b.check(self._b.inscatter_points(self._h, len(pos), _fp(pos), _fp(drs), _fp(f) if f is not None else None, _fp(rgb)))
+        return rgb
+
+    def Inscatter_Rays(self, Origins, Directions, Max_Dists, Step, March=False):
+        """{rgb, len, steps}: the in-scattered light along every ray -- L = 0; for (f = 0; f < len; f += Step) L = L +
+        inscatter ((dir * f) + org, dir) * exp (-f tau); rgb = L * Step, in fp32 and in this order.  len is Max_Dists (per ray;
+        a scalar is broadcast; within 0 .. max_dist), or with March the distance to what the ray hits where that is shorter.
+        steps counts the loop's turns.  Independent of the renderer's volumetric settings."""
+        march, step = self._inscatter_step(March, Step)
+        org, drs, tmax = self._rays(Origins, Directions, Max_Dists)
+        if tmax is None:
+            raise ValueError("Max_Dists: a length per ray is required")
+        n = len(org)
+        out = {"rgb": np.zeros((n, 3), np.float32), "len": np.zeros(n, np.float32), "steps": np.zeros(n, np.int32)}
+        self._b.check(self._b.inscatter_rays(self._h, n, _fp(org), _fp(drs), _fp(tmax), march, step, _fp(out["rgb"]), _fp(out["len"]),
+                                             _fp(out["steps"])))
+        return out
+
+    def Inscatter_Points_Device(self, Positions, Directions, Rgb, F=None, Stream=0, N=None):
+        """Inscatter_Points for N points (default: what Positions holds) in device memory, asynchronous and ordered with
+        `Stream` as Raycast_Device is.  F may be None.  A point with a component that is not finite gets NaN in all three colours."""
+        n = self._ray_count(Positions, N)
+        dev = self._device_array
+        args = [dev(Positions, "Positions", 3 * n, "float32"), dev(Directions, "Directions", 3 * n, "float32"),
+                dev(F, "F", n, "float32", True), dev(Rgb, "Rgb", 3 * n, "float32")]
+        self._b.check(self._b.inscatter_points_device(self._h, n, *args, C.c_void_p(int(Stream))))
+
+    def Inscatter_Rays_Device(self, Origins, Directions, Max_Dists, Step, Rgb, Len=None, Steps=None, March=False, Stream=0, N=None):
+        """Inscatter_Rays likewise, one length per ray in device memory; Len and Steps may be None.  A ray that is not finite, or
+        whose length is not finite, negative or beyond max_dist, is not marched: NaN in rgb and len, -1 steps."""
+        march, step = self._inscatter_step(March, Step)
+        n = self._ray_count(Origins, N)
+        dev = self._device_array
+        args = [dev(Origins, "Origins", 3 * n, "float32"), dev(Directions, "Directions", 3 * n, "float32"),
+                dev(Max_Dists, "Max_Dists", n, "float32")]
+        outs = [dev(Rgb, "Rgb", 3 * n, "float32"), dev(Len, "Len", n, "float32", True), dev(Steps, "Steps", n, "int32", True)]
+        self._b.check(self._b.inscatter_rays_device(self._h, n, *args, march, step, *outs, C.c_void_p(int(Stream))))
+
     def Render_Pass(self, Pass):
         self._b.check(self._b.render_pass(self._h, int(Pass)))
 
