@@ -310,6 +310,30 @@ package Madarch_HIP is
       RGB_Out, Len_Out, Steps_Out : System.Address; Stream : System.Address) return Status
      with Import, Convention => C, External_Name => "mdh_inscatter_rays_device";
 
+   --  Swept spheres and contacts for a host that owns moving bodies (madarch_hip.h,
+   --  mdh_spherecast): Radius and T_Max may be Null_Address (0, the scene's max_dist);
+   --  N_Kinds = 0 is the whole scene, otherwise Kind_Ixs lists the kinds to collide with
+   function Spherecast
+     (R : Handle; N : int; Org, Dir, Radius, T_Max, Kind_Ixs : System.Address; N_Kinds : int;
+      Hit_Out, Index_Out, T_Out, Steps_Out, Pos_Out, Normal_Out : System.Address) return Status
+     with Import, Convention => C, External_Name => "mdh_spherecast";
+
+   function Spherecast_Device
+     (R : Handle; N : int; Org, Dir, Radius, T_Max, Kind_Ixs : System.Address; N_Kinds : int;
+      Hit_Out, Index_Out, T_Out, Steps_Out, Pos_Out, Normal_Out : System.Address;
+      Stream : System.Address) return Status
+     with Import, Convention => C, External_Name => "mdh_spherecast_device";
+
+   function Contacts
+     (R : Handle; N : int; Centre, Radius, Kind_Ixs : System.Address; N_Kinds : int;
+      Dist_Out, Index_Out, Normal_Out : System.Address) return Status
+     with Import, Convention => C, External_Name => "mdh_contacts";
+
+   function Contacts_Device
+     (R : Handle; N : int; Centre, Radius, Kind_Ixs : System.Address; N_Kinds : int;
+      Dist_Out, Index_Out, Normal_Out : System.Address; Stream : System.Address) return Status
+     with Import, Convention => C, External_Name => "mdh_contacts_device";
+
    --  One frame on the N GPUs of a node, one process per GPU (madarch_hip.h, mdh_comm_*):
    --  every process creates its Renderer on its own device, rank 0 makes a 128-byte id and
    --  hands it to the others (a file, an environment variable), all call Comm_Init, and

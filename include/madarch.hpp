@@ -516,6 +516,31 @@ class Renderer {
    {
       Check(mdh_inscatter_rays_device(h_.get(), N, Origins, Directions, Max_Dists, March ? 1 : 0, Step, Rgb, Len, Steps, Stream));
    }
+   // ---- swept spheres and contacts, for a host that owns moving bodies (madarch_hip.h: mdh_spherecast, mdh_contacts).  Kinds
+   // empty: the scene as every pass sees it; kind indices in scene order otherwise: the exact minimum over those kinds' instances.
+   // Radii and Max_Dists may be null (0, the scene's max_dist); every output but Hit and Dist may be null
+   void Spherecast(int32_t N, const float *Origins, const float *Directions, const float *Radii, const float *Max_Dists, const std::vector<int32_t> &Kinds,
+                   int32_t *Hit, int32_t *Index = nullptr, float *T = nullptr, int32_t *Steps = nullptr, float *Position = nullptr, float *Normal = nullptr) const
+   {
+      Check(mdh_spherecast(h_.get(), N, Origins, Directions, Radii, Max_Dists, Kinds.empty() ? nullptr : Kinds.data(), (int32_t)Kinds.size(), Hit, Index, T, Steps, Position, Normal));
+   }
+   void Contacts(int32_t N, const float *Centres, const float *Radii, const std::vector<int32_t> &Kinds, float *Dist, int32_t *Index = nullptr, float *Normal = nullptr) const
+   {
+      Check(mdh_contacts(h_.get(), N, Centres, Radii, Kinds.empty() ? nullptr : Kinds.data(), (int32_t)Kinds.size(), Dist, Index, Normal));
+   }
+   // ... for arrays the device addresses, ordered with Stream (Raycast_Device's contract; Ray_Query_Wait is the host's wait)
+   void Spherecast_Device(int32_t N, const float *Origins, const float *Directions, const float *Radii, const float *Max_Dists, const std::vector<int32_t> &Kinds,
+                          int32_t *Hit, int32_t *Index = nullptr, float *T = nullptr, int32_t *Steps = nullptr, float *Position = nullptr, float *Normal = nullptr,
+                          void *Stream = nullptr) const
+   {
+      Check(mdh_spherecast_device(h_.get(), N, Origins, Directions, Radii, Max_Dists, Kinds.empty() ? nullptr : Kinds.data(), (int32_t)Kinds.size(), Hit, Index, T, Steps,
+                                  Position, Normal, Stream));
+   }
+   void Contacts_Device(int32_t N, const float *Centres, const float *Radii, const std::vector<int32_t> &Kinds, float *Dist, int32_t *Index = nullptr, float *Normal = nullptr,
+                        void *Stream = nullptr) const
+   {
+      Check(mdh_contacts_device(h_.get(), N, Centres, Radii, Kinds.empty() ? nullptr : Kinds.data(), (int32_t)Kinds.size(), Dist, Index, Normal, Stream));
+   }
    void Update_Partitioning(Partitioning_Update_Method Method = GPU_Fast) const { Check(mdh_update_partitioning(h_.get(), (int32_t)Method)); } // renderers.adb:757-775
    // ---- headless additions
    std::vector<float> Read_Framebuffer() const // replaces Swap_Buffers: H*W*3 floats, row 0 = top

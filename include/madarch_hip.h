@@ -798,6 +798,55 @@ int32_t mdh_inscatter_rays_device(mdh_renderer *r, int32_t n, const float *org_x
                                   int32_t march, float step, float *rgb_out, float *len_out, int32_t *steps_out,
                                   void *stream);
 
+/* SWEPT SPHERES AND CONTACTS, for a host that owns moving bodies (the reference's examples/ball_game asks
+ * Eval_Distance_To for each ball's new centre: a point test, which a long step carries through a thin obstacle).
+ *
+ * mdh_spherecast sweeps a sphere of radius radius[i] (NULL: 0) with its centre along ray i up to tmax[i] (NULL: the scene's
+ * max_dist) and reports the first contact.  The march is raycast's (glsl/raymarching.glsl:25-37) with the distance
+ * fl (D (org + dir * total) - radius) and the bound tmax:
+ *    for (total = 0; total < tmax;) { dist = D (p) - radius; ++steps; if (dist < epsilon) hit at t = total;
+ *                                     [total + dist == total: a miss]  total += dist }
+ * so radius = 0 up to max_dist over the whole scene is mdh_raycast bit for bit, and a sphere that overlaps something at
+ * its origin hits at t = 0 with one step.  pos is the CENTRE at contact, org + dir * t as the march computed it; normal is
+ * the normal of primitive `index` at that centre, as Eval_Distance_To gives it at a ball's centre (the touching point is
+ * pos - normal * radius).  On a miss index = -1 and t, pos and normal are 0.  All outputs but hit_out may be NULL.
+ *
+ * mdh_contacts evaluates once at each centre: dist = fl (D (centre) - radius), negative where the sphere penetrates, index
+ * the closest primitive and normal its normal at the centre; where no instance exists dist = 1.0e10 - radius, index = -1
+ * and normal = 0.  index_out and normal_out may be NULL.
+ *
+ * D: n_kinds = 0 -- the scene as every pass and mdh_raycast see it, through the space partition (its borders and Index_Count
+ * included) or the triangle BVH where the scene has one.  n_kinds > 0 -- the exact minimum over the committed instances of
+ * the listed kinds in the order listed, as mdh_eval_distance_to scans them (the lowest index wins a tie, no partition is
+ * consulted), always with the shaders' division: MDH_OPT_ADA_EVAL_DIV is ignored, a march needs a distance.  A ball that
+ * is itself a sphere of the scene lists the kinds it collides with, as the reference's query does.  index is in
+ * mdh_read_gbuffer's numbering either way.
+ *
+ * The contract is the ray queries' (mdh_raycast above): the query stream beside the frames in flight, pending edits seen,
+ * nothing edited -- the probe-settle run and both replays go on across the calls, unlike across mdh_eval_distance_to --,
+ * the stall guard in the march, mdh_ray_query_time under MDH_OPT_TIMING.  n = 0 is MDH_OK without a launch.  Every refusal
+ * happens before anything is launched:
+ *   MDH_E_INVALID  a null renderer or required array, n < 0, n_kinds outside 0 .. MDH_MAX_KINDS or a kind index outside the
+ *                  scene's kinds; a non-finite origin, direction, centre, radius or tmax; a radius or a tmax below 0 or above
+ *                  the scene's max_dist
+ *   MDH_E_STATE    a scene with a user-defined kind */
+int32_t mdh_spherecast(mdh_renderer *r, int32_t n, const float *org_xyz, const float *dir_xyz, const float *radius,
+                       const float *tmax, const int32_t *kind_ixs, int32_t n_kinds, int32_t *hit_out, int32_t *index_out,
+                       float *t_out, int32_t *steps_out, float *pos_xyz_out, float *normal_xyz_out);
+int32_t mdh_contacts(mdh_renderer *r, int32_t n, const float *centre_xyz, const float *radius, const int32_t *kind_ixs,
+                     int32_t n_kinds, float *dist_out, int32_t *index_out, float *normal_xyz_out);
+/* The same calls for arrays the device addresses (kind_ixs stays the host's), under the contract of mdh_raycast_device:
+ * asynchronous and ordered with `stream`, mdh_ray_query_wait is the host's wait, where every array lives and ends is checked
+ * before anything is launched, and MDH_OPT_RAY_STREAM_REFILL / _GROUPS shape the whole-scene sweep's launch.  A ray the calls
+ * above would refuse the batch for is answered without a march as mdh_raycast_device answers it (hit = -1, index = -1, the
+ * rest 0); such a centre with dist = the quiet NaN 0x7fc00000, index = -1 and normal = 0. */
+int32_t mdh_spherecast_device(mdh_renderer *r, int32_t n, const float *org_xyz, const float *dir_xyz, const float *radius,
+                              const float *tmax, const int32_t *kind_ixs, int32_t n_kinds, int32_t *hit_out,
+                              int32_t *index_out, float *t_out, int32_t *steps_out, float *pos_xyz_out,
+                              float *normal_xyz_out, void *stream);
+int32_t mdh_contacts_device(mdh_renderer *r, int32_t n, const float *centre_xyz, const float *radius, const int32_t *kind_ixs,
+                            int32_t n_kinds, float *dist_out, int32_t *index_out, float *normal_xyz_out, void *stream);
+
 /* accumulated HIP-event time and launch count of one pass (MDH_OPT_TIMING) */
 int32_t mdh_pass_time(mdh_renderer *r, int32_t pass, double *total_ms, int64_t *launches);
 /* MDH_OPT_RADIANCE_REPLAY: the radiance passes launched since mdh_create that marched their rays (`plain`), marched them

@@ -192,6 +192,12 @@ HIP_ONLY_ABI = {
     "inscatter_points_device": (_I, [_P, _I, _P, _P, _P, _P, _P]),
     "inscatter_rays": (_I, [_P, _I, _P, _P, _P, _I, _F, _P, _P, _P]),
     "inscatter_rays_device": (_I, [_P, _I, _P, _P, _P, _I, _F, _P, _P, _P, _P]),
+    # swept spheres and contacts: (r, n, org, dir, radius or null, tmax or null, kind_ixs, n_kinds (0: the whole scene), hit,
+    # index, t, steps, pos, normal[, stream]) and (r, n, centre, radius or null, kind_ixs, n_kinds, dist, index, normal[, stream])
+    "spherecast": (_I, [_P, _I, _P, _P, _P, _P, _P, _I, _P, _P, _P, _P, _P, _P]),
+    "spherecast_device": (_I, [_P, _I, _P, _P, _P, _P, _P, _I, _P, _P, _P, _P, _P, _P, _P]),
+    "contacts": (_I, [_P, _I, _P, _P, _P, _I, _P, _P, _P]),
+    "contacts_device": (_I, [_P, _I, _P, _P, _P, _I, _P, _P, _P, _P]),
 }
 
 

@@ -1796,7 +1796,7 @@ template <typename Args> static int jit_launch(hipFunction_t f, int blocks, int 
 // frames in flight share their CUs' instruction caches (measured: the same kernels at other addresses, each as fast by itself,
 // the headline with frames in flight 0.5 % slower).  The kernels of global residency (MDH_PF_GTAB, mdh_device.h: Geo) come
 // last there: behind everything else they move nothing.
-enum { GK_k_visibility, GK_k_scat_march, GK_k_scattering, GK_k_radiance, GK_k_screen, GK_k_partition_build, GK_k_eval_distance, GK_k_diag_segments, GK_k_ray_query, GK_k_ray_stream, GK_k_ray_shade, GK_k_camera_rays, GK_k_point_shade, GK_k_path_trace, GK_k_point_inscatter, GK_k_ray_inscatter };
+enum { GK_k_visibility, GK_k_scat_march, GK_k_scattering, GK_k_radiance, GK_k_screen, GK_k_partition_build, GK_k_eval_distance, GK_k_diag_segments, GK_k_ray_query, GK_k_ray_stream, GK_k_ray_shade, GK_k_camera_rays, GK_k_point_shade, GK_k_path_trace, GK_k_point_inscatter, GK_k_ray_inscatter, GK_k_listed };
 // WHICH KERNEL A PASS RUNS ("One place that picks a pass's kernel"): every template argument of the
 // pass's kernel, computed once by pick_kernel; kernel_name and kernel_ptr turn the same description into the name hiprtc
 // instantiates and into the kernel of this library.
@@ -1807,7 +1807,7 @@ struct PassKernel {
    bool gbuf = false, alt = false; // ... the geometry buffer, the variant of the optional specular bodies
    bool small = false;             // k_radiance: SMALL
    int rec = 0;                    // k_radiance, k_screen: REC (0 marches, 1 marches and records, 2 replays the records: rad_replay_pick, scr_replay_pick)
-   int what = 0;                   // k_ray_query, k_ray_stream: WHAT (MDH_RQ_*)
+   int what = 0;                   // k_ray_query, k_ray_stream, k_listed: WHAT (MDH_RQ_*)
    bool ada_div = false;           // k_eval_distance: MDH_OPT_ADA_DIVISION
    bool jit = false; // a function of the scene's hiprtc module (user-defined kinds under MDH_OPT_JIT), not a kernel of this library
    int pfk = 0;      // the variant by the scene's census, before the pass's own choices, and the power-of-two addressing
@@ -1839,6 +1839,7 @@ static const void *table_kernel(const mdh_renderer *r, int family, int what = 0)
       if (r->part.enable) k.pf |= MDH_PF_PART | (r->part.border_behavior != 0 ? MDH_PF_FALLBACK : 0);
       if (r->bvh_active) k.pf |= MDH_PF_BVH;
    }
+   if (family == GK_k_listed) k.what = what; // (the exact scan of listed kinds: the table's residency alone)
    return kernel_ptr(k);
 }
 
@@ -3545,7 +3546,7 @@ extern "C" int32_t mdh_eval_distance_to(mdh_renderer *r, int32_t n, const float 
 // frames in flight (k_ray_query, mdh_kernels.h).  They read the committed scene and edit nothing: no settle_bump, no counter
 // of the replays' keys moves -- the probe-settle run, the radiance replay and the screen replay go on across them (pending
 // edits are committed first, and have made their own marks).
-#define MDH_RAY_WORDS 17 // origin, direction, tmax | hit, index, t (or the visibility / shadow value), steps, position, normal
+#define MDH_RAY_WORDS 18 // origin, direction, tmax | hit, index, t (or the visibility / shadow value), steps, position, normal | a swept sphere's radius
 static bool all_finite(const float *v, size_t n)
 {
    bool ok = true;
@@ -3586,7 +3587,7 @@ static int ray_query_run(mdh_renderer *r, int what, int32_t n, const float *org,
    a.org = d_org; a.dir = d_dir; a.tmax = d_tmax;
    a.hit = (int *)(base + 7 * cap); a.index = (int *)(base + 8 * cap); a.t = base + 9 * cap; a.steps = (int *)(base + 10 * cap);
    a.pos = base + 11 * cap; a.normal = normals ? base + 14 * cap : nullptr; // (no normal asked for: the kernel leaves primitive_info out)
-   a.out = a.t;
+   a.out = a.t; a.radius = nullptr;
    HIP_TRY(hipMemcpyAsync(d_org, org, (size_t)n * 12, hipMemcpyHostToDevice, qs));
    HIP_TRY(hipMemcpyAsync(d_dir, dir, (size_t)n * 12, hipMemcpyHostToDevice, qs));
    if (tmax) HIP_TRY(hipMemcpyAsync(d_tmax, tmax, (size_t)n * 4, hipMemcpyHostToDevice, qs));
@@ -3776,7 +3777,7 @@ extern "C" int32_t mdh_raycast_device(mdh_renderer *r, int32_t n, const float *o
    a.org = org; a.dir = dir; a.tmax = nullptr;
    a.hit = hit_out; a.index = index_out; a.steps = steps_out;
    a.t = t_out; a.pos = pos_out; a.normal = normal_out;
-   a.out = nullptr;
+   a.out = nullptr; a.radius = nullptr;
    return ray_stream_run(r, MDH_RQ_RAYCAST, n, arrays, 8, a, (hipStream_t)stream);
 }
 static int32_t ray_stream_scalar(mdh_renderer *r, int what, int32_t n, const float *org, const float *dir, float tmin, const float *tmax, float k, float *out, void *stream)
@@ -3788,7 +3789,7 @@ static int32_t ray_stream_scalar(mdh_renderer *r, int what, int32_t n, const flo
    a.org = org; a.dir = dir; a.tmax = tmax;
    a.hit = a.index = a.steps = nullptr;
    a.t = a.pos = a.normal = nullptr;
-   a.out = out;
+   a.out = out; a.radius = nullptr;
    return ray_stream_run(r, what, n, arrays, 4, a, (hipStream_t)stream);
 }
 extern "C" int32_t mdh_raycast_visibility_device(mdh_renderer *r, int32_t n, const float *org, const float *dir, const float *tmax, float *vis_out, void *stream)
@@ -3811,6 +3812,196 @@ extern "C" int32_t mdh_ray_query_wait(mdh_renderer *r)
    if (!r->query_stream) return MDH_OK; // (no query yet)
    HIP_TRY(hipSetDevice(r->device));
    return ray_query_wait(r);
+}
+
+// ------------------------------------------------------------------ sweeping a host's spheres
+// mdh_spherecast, mdh_contacts and their _device forms: a sphere swept along each ray to its first contact, and one evaluation
+// at each centre, against the scene as every pass sees it (n_kinds = 0: k_ray_query / k_ray_stream with MDH_RQ_SPHERECAST,
+// k_ray_query with MDH_RQ_CONTACT) or against the exact minimum over the kinds listed (k_listed, mdh_kernels.h).  The contract
+// is the ray queries': the query stream, pending edits seen, nothing edited and no settle_bump, d_rays for host arrays,
+// ray_array_check and the two events for device arrays.  MDH_OPT_ADA_EVAL_DIV is not consulted: a march needs a distance.
+static int sweep_kinds_check(const mdh_renderer *r, const int32_t *kind_ixs, int32_t n_kinds)
+{
+   if (n_kinds < 0 || n_kinds > MDH_MAX_KINDS || (n_kinds > 0 && !kind_ixs)) return seterr(MDH_E_INVALID, "bad argument");
+   for (int i = 0; i < n_kinds; ++i)
+      if (kind_ixs[i] < 0 || kind_ixs[i] >= r->npk) return seterr(MDH_E_INVALID, "bad kind index");
+   return MDH_OK;
+}
+// what the host can say of host arrays before anything is launched (dir and tmax: null for contacts)
+static int sweep_host_check(const mdh_renderer *r, int32_t n, const float *org, const float *dir, const float *radius, const float *tmax)
+{
+   if (!all_finite(org, 3 * (size_t)n) || (dir && !all_finite(dir, 3 * (size_t)n))) return seterr(MDH_E_INVALID, dir ? "a ray is not finite" : "a centre is not finite");
+   bool ok = true;
+   if (radius) for (int32_t i = 0; i < n; ++i) ok = ok && rs_sweep_radius_valid(radius[i], r->max_dist);
+   if (!ok) return seterr(MDH_E_INVALID, "a radius is not finite, negative or exceeds the scene's max_dist");
+   if (tmax) for (int32_t i = 0; i < n; ++i) ok = ok && rs_sweep_tmax_valid(tmax[i], r->max_dist);
+   if (!ok) return seterr(MDH_E_INVALID, "a ray's length is not finite, negative or exceeds the scene's max_dist");
+   return MDH_OK;
+}
+// enqueues the call's kernel on the query stream between the timing events: k_ray_query<.., what> (host arrays, and contacts
+// wherever they live), k_ray_stream<.., MDH_RQ_SPHERECAST> (device arrays: `streamed`) or k_listed<.., what> (n_kinds > 0)
+static int sweep_launch(mdh_renderer *r, int what, const RayQueryArgs &a, const int32_t *kind_ixs, int32_t n_kinds, bool streamed, hipStream_t qs)
+{
+   int rc = table_acquire(r, qs);
+   if (rc != MDH_OK) return rc;
+   const bool timed = r->opt_timing && (r->rq_e0 || (r->rq_e0 = get_event(r))) && (r->rq_e1 || (r->rq_e1 = get_event(r)));
+   const size_t lds = lds_bytes(r);
+   long groups = ((long)a.n + MDH_BLOCK - 1) / MDH_BLOCK;
+   if (n_kinds > 0) {
+      ListedArgs la;
+      la.q = a; la.n_kinds = n_kinds;
+      for (int i = 0; i < MDH_MAX_KINDS; ++i) { la.kinds[i] = i < n_kinds ? kind_ixs[i] : 0; la.host_count[i] = r->host_count[i]; }
+      if (timed) HIP_TRY(hipEventRecord(r->rq_e0, qs));
+      if ((rc = launch_kernel_ptr(table_kernel(r, GK_k_listed, what), dim3((unsigned)groups), dim3(MDH_BLOCK), lds, qs, r->ks, la)) != MDH_OK) return rc;
+   } else if (streamed) {
+      const void *kernel = table_kernel(r, GK_k_ray_stream, what);
+      if (kernel) { // (none: launch_kernel_ptr says so)
+         const long resident = resident_groups(r, kernel, lds);
+         if (resident > 0 && groups > resident) groups = resident;
+      }
+      if (r->opt_rq_groups > 0 && groups > r->opt_rq_groups) groups = r->opt_rq_groups;
+      RayStreamArgs sa;
+      sa.q = a; sa.next = r->d_rq_next.ptr; sa.refill = r->opt_rq_refill;
+      HIP_TRY(hipMemsetAsync(r->d_rq_next.ptr, 0, sizeof(unsigned), qs));
+      if (timed) HIP_TRY(hipEventRecord(r->rq_e0, qs));
+      if ((rc = launch_kernel_ptr(kernel, dim3((unsigned)groups), dim3(MDH_BLOCK), lds, qs, r->ks, sa)) != MDH_OK) return rc;
+   } else {
+      if (timed) HIP_TRY(hipEventRecord(r->rq_e0, qs));
+      if ((rc = launch_kernel_ptr(table_kernel(r, GK_k_ray_query, what), dim3((unsigned)groups), dim3(MDH_BLOCK), lds, qs, r->ks, a)) != MDH_OK) return rc;
+   }
+   HIP_TRY(hipGetLastError());
+   if (timed) HIP_TRY(hipEventRecord(r->rq_e1, qs));
+   r->rq_timed = timed; // (pending for a device query: mdh_ray_query_wait or mdh_ray_query_time reads the pair)
+   return table_release(r, qs);
+}
+// host arrays: uploads what the call brings into d_rays, launches, and leaves the results there (a: their places)
+static int sweep_host_run(mdh_renderer *r, int what, int32_t n, const float *org, const float *dir, const float *radius, const float *tmax,
+                          const int32_t *kind_ixs, int32_t n_kinds, bool normals, RayQueryArgs &a)
+{
+   HIP_TRY(hipSetDevice(r->device));
+   if (!r->query_stream) HIP_TRY(hipStreamCreateWithFlags(&r->query_stream, hipStreamNonBlocking));
+   hipStream_t qs = r->query_stream;
+   int rc = ensure_committed(r, qs);
+   if (rc != MDH_OK) return rc;
+   const size_t want = ((size_t)n < 256 ? 256 : (size_t)n) * MDH_RAY_WORDS;
+   if (want > r->d_rays.cap) {
+      if (r->d_rays.ptr) HIP_TRY(hipStreamSynchronize(qs));
+      HIP_TRY(r->d_rays.grow(want));
+   }
+   const size_t cap = r->d_rays.cap / MDH_RAY_WORDS;
+   float *base = r->d_rays.ptr;
+   float *d_org = base, *d_dir = base + 3 * cap, *d_tmax = base + 6 * cap, *d_radius = base + 17 * cap;
+   a.n = n; a.tmin = 0.0f; a.k = 0.0f;
+   a.org = d_org; a.dir = dir ? d_dir : nullptr; a.tmax = tmax ? d_tmax : nullptr; a.radius = radius ? d_radius : nullptr;
+   a.hit = (int *)(base + 7 * cap); a.index = (int *)(base + 8 * cap); a.t = base + 9 * cap; a.steps = (int *)(base + 10 * cap);
+   a.pos = base + 11 * cap; a.normal = normals ? base + 14 * cap : nullptr; // (no normal asked for: the kernel leaves primitive_info out)
+   a.out = nullptr;
+   HIP_TRY(hipMemcpyAsync(d_org, org, (size_t)n * 12, hipMemcpyHostToDevice, qs));
+   if (dir) HIP_TRY(hipMemcpyAsync(d_dir, dir, (size_t)n * 12, hipMemcpyHostToDevice, qs));
+   if (tmax) HIP_TRY(hipMemcpyAsync(d_tmax, tmax, (size_t)n * 4, hipMemcpyHostToDevice, qs));
+   if (radius) HIP_TRY(hipMemcpyAsync(d_radius, radius, (size_t)n * 4, hipMemcpyHostToDevice, qs));
+   return sweep_launch(r, what, a, kind_ixs, n_kinds, false, qs);
+}
+// device arrays: checks where they live, then enqueues the kernel between the two events that order it with `stream`
+static int sweep_device_run(mdh_renderer *r, int what, const RayArray *arrays, int n_arrays, const RayQueryArgs &a, const int32_t *kind_ixs, int32_t n_kinds, hipStream_t stream)
+{
+   HIP_TRY(hipSetDevice(r->device));
+   for (int i = 0; i < n_arrays; ++i) {
+      const int rc = ray_array_check(r, arrays[i]);
+      if (rc != MDH_OK) return rc;
+   }
+   if (a.n == 0) return MDH_OK;
+   if (!r->query_stream) HIP_TRY(hipStreamCreateWithFlags(&r->query_stream, hipStreamNonBlocking));
+   hipStream_t qs = r->query_stream;
+   HIP_TRY(create_all(r->d_rq_next.sized(1), r->ev_rq_in, r->ev_rq_out)); // (one group, created by the first device query)
+   int rc = ensure_committed(r, qs);
+   if (rc != MDH_OK) return rc;
+   if (stream != qs) { // the arrays are what the caller's stream has made of them at this call
+      HIP_TRY(hipEventRecord(r->ev_rq_in.ev, stream));
+      HIP_TRY(hipStreamWaitEvent(qs, r->ev_rq_in.ev, 0));
+   }
+   if ((rc = sweep_launch(r, what, a, kind_ixs, n_kinds, what == MDH_RQ_SPHERECAST, qs)) != MDH_OK) return rc;
+   if (stream != qs) { // ... and the answers are there for whatever the caller's stream is given next
+      HIP_TRY(hipEventRecord(r->ev_rq_out.ev, qs));
+      HIP_TRY(hipStreamWaitEvent(stream, r->ev_rq_out.ev, 0));
+   }
+   return MDH_OK;
+}
+extern "C" int32_t mdh_spherecast(mdh_renderer *r, int32_t n, const float *org, const float *dir, const float *radius, const float *tmax,
+                                  const int32_t *kind_ixs, int32_t n_kinds, int32_t *hit_out, int32_t *index_out, float *t_out, int32_t *steps_out,
+                                  float *pos_out, float *normal_out)
+{
+   if (!r) return seterr(MDH_E_INVALID, "null renderer");
+   if (!org || !dir || !hit_out || n < 0) return seterr(MDH_E_INVALID, "bad argument");
+   if (has_custom_kinds(r)) return seterr(MDH_E_STATE, "ray queries answer scenes of built-in kinds only");
+   int rc = sweep_kinds_check(r, kind_ixs, n_kinds);
+   if (rc != MDH_OK || (rc = sweep_host_check(r, n, org, dir, radius, tmax)) != MDH_OK) return rc;
+   if (n == 0) return MDH_OK;
+   RayQueryArgs a;
+   if ((rc = sweep_host_run(r, MDH_RQ_SPHERECAST, n, org, dir, radius, tmax, kind_ixs, n_kinds, normal_out != nullptr, a)) != MDH_OK) return rc;
+   hipStream_t qs = r->query_stream;
+   HIP_TRY(hipMemcpyAsync(hit_out, a.hit, (size_t)n * 4, hipMemcpyDeviceToHost, qs));
+   if (index_out) HIP_TRY(hipMemcpyAsync(index_out, a.index, (size_t)n * 4, hipMemcpyDeviceToHost, qs));
+   if (t_out) HIP_TRY(hipMemcpyAsync(t_out, a.t, (size_t)n * 4, hipMemcpyDeviceToHost, qs));
+   if (steps_out) HIP_TRY(hipMemcpyAsync(steps_out, a.steps, (size_t)n * 4, hipMemcpyDeviceToHost, qs));
+   if (pos_out) HIP_TRY(hipMemcpyAsync(pos_out, a.pos, (size_t)n * 12, hipMemcpyDeviceToHost, qs));
+   if (normal_out) HIP_TRY(hipMemcpyAsync(normal_out, a.normal, (size_t)n * 12, hipMemcpyDeviceToHost, qs));
+   return ray_query_wait(r);
+}
+extern "C" int32_t mdh_spherecast_device(mdh_renderer *r, int32_t n, const float *org, const float *dir, const float *radius, const float *tmax,
+                                         const int32_t *kind_ixs, int32_t n_kinds, int32_t *hit_out, int32_t *index_out, float *t_out, int32_t *steps_out,
+                                         float *pos_out, float *normal_out, void *stream)
+{
+   if (!r) return seterr(MDH_E_INVALID, "null renderer");
+   if (!org || !dir || !hit_out || n < 0) return seterr(MDH_E_INVALID, "bad argument");
+   if (has_custom_kinds(r)) return seterr(MDH_E_STATE, "ray queries answer scenes of built-in kinds only");
+   const int rc = sweep_kinds_check(r, kind_ixs, n_kinds); // (the kind list is the host's)
+   if (rc != MDH_OK) return rc;
+   const size_t w = (size_t)n * 4;
+   const RayArray arrays[] = {{org, 3 * w, "origins"}, {dir, 3 * w, "directions"}, {radius, w, "radii"}, {tmax, w, "tmax"}, {hit_out, w, "hit"}, {index_out, w, "index"},
+                              {t_out, w, "t"}, {steps_out, w, "steps"}, {pos_out, 3 * w, "positions"}, {normal_out, 3 * w, "normals"}};
+   RayQueryArgs a;
+   a.n = n; a.tmin = 0.0f; a.k = 0.0f;
+   a.org = org; a.dir = dir; a.tmax = tmax; a.radius = radius;
+   a.hit = hit_out; a.index = index_out; a.steps = steps_out;
+   a.t = t_out; a.pos = pos_out; a.normal = normal_out;
+   a.out = nullptr;
+   return sweep_device_run(r, MDH_RQ_SPHERECAST, arrays, 10, a, kind_ixs, n_kinds, (hipStream_t)stream);
+}
+extern "C" int32_t mdh_contacts(mdh_renderer *r, int32_t n, const float *centre, const float *radius, const int32_t *kind_ixs, int32_t n_kinds,
+                                float *dist_out, int32_t *index_out, float *normal_out)
+{
+   if (!r) return seterr(MDH_E_INVALID, "null renderer");
+   if (!centre || !dist_out || n < 0) return seterr(MDH_E_INVALID, "bad argument");
+   if (has_custom_kinds(r)) return seterr(MDH_E_STATE, "ray queries answer scenes of built-in kinds only");
+   int rc = sweep_kinds_check(r, kind_ixs, n_kinds);
+   if (rc != MDH_OK || (rc = sweep_host_check(r, n, centre, nullptr, radius, nullptr)) != MDH_OK) return rc;
+   if (n == 0) return MDH_OK;
+   RayQueryArgs a;
+   if ((rc = sweep_host_run(r, MDH_RQ_CONTACT, n, centre, nullptr, radius, nullptr, kind_ixs, n_kinds, normal_out != nullptr, a)) != MDH_OK) return rc;
+   hipStream_t qs = r->query_stream;
+   HIP_TRY(hipMemcpyAsync(dist_out, a.t, (size_t)n * 4, hipMemcpyDeviceToHost, qs));
+   if (index_out) HIP_TRY(hipMemcpyAsync(index_out, a.index, (size_t)n * 4, hipMemcpyDeviceToHost, qs));
+   if (normal_out) HIP_TRY(hipMemcpyAsync(normal_out, a.normal, (size_t)n * 12, hipMemcpyDeviceToHost, qs));
+   return ray_query_wait(r);
+}
+extern "C" int32_t mdh_contacts_device(mdh_renderer *r, int32_t n, const float *centre, const float *radius, const int32_t *kind_ixs, int32_t n_kinds,
+                                       float *dist_out, int32_t *index_out, float *normal_out, void *stream)
+{
+   if (!r) return seterr(MDH_E_INVALID, "null renderer");
+   if (!centre || !dist_out || n < 0) return seterr(MDH_E_INVALID, "bad argument");
+   if (has_custom_kinds(r)) return seterr(MDH_E_STATE, "ray queries answer scenes of built-in kinds only");
+   const int rc = sweep_kinds_check(r, kind_ixs, n_kinds);
+   if (rc != MDH_OK) return rc;
+   const size_t w = (size_t)n * 4;
+   const RayArray arrays[] = {{centre, 3 * w, "centres"}, {radius, w, "radii"}, {dist_out, w, "distances"}, {index_out, w, "index"}, {normal_out, 3 * w, "normals"}};
+   RayQueryArgs a;
+   a.n = n; a.tmin = 0.0f; a.k = 0.0f;
+   a.org = centre; a.dir = nullptr; a.tmax = nullptr; a.radius = radius;
+   a.hit = nullptr; a.index = index_out; a.steps = nullptr;
+   a.t = dist_out; a.pos = nullptr; a.normal = normal_out;
+   a.out = nullptr;
+   return sweep_device_run(r, MDH_RQ_CONTACT, arrays, 5, a, kind_ixs, n_kinds, (hipStream_t)stream);
 }
 
 // ------------------------------------------------------------------ shading a host's rays
@@ -4632,8 +4823,10 @@ extern "C" int32_t mdh_diag_waves(unsigned long long *out, int32_t n_waves)
 //  scenes with user-defined kinds get the power-of-two addressing from hiprtc only -- pick_kernel)
 static const void *kernel_ptr_path(const PassKernel &k);
 static const void *kernel_ptr_inscatter(const PassKernel &k);
+static const void *kernel_ptr_sweep(const PassKernel &k);
 static const void *kernel_ptr(const PassKernel &k)
 {
+   if (k.family == GK_k_listed || ((k.family == GK_k_ray_query || k.family == GK_k_ray_stream) && k.what >= MDH_RQ_SPHERECAST)) return kernel_ptr_sweep(k);
    if (k.family == GK_k_path_trace) return kernel_ptr_path(k); // (the newer families, named behind this function)
    if (k.family == GK_k_point_inscatter || k.family == GK_k_ray_inscatter) return kernel_ptr_inscatter(k);
 #define MDH_K(FAMILY, PF, ...) if (k.family == GK_##FAMILY && k.pf == (PF)) return (const void *)(__VA_ARGS__);
@@ -4724,4 +4917,19 @@ static const void *kernel_ptr_inscatter(const PassKernel &k)
    MDH_INS(0) MDH_INS(1) MDH_INS(9) MDH_INS(64) MDH_INS(65) MDH_INS(73) MDH_INS(192)
    return nullptr;
 #undef MDH_INS
+}
+// ... and behind that the swept spheres and contacts (mdh_spherecast, mdh_contacts and their _device forms): the new WHAT
+// values of k_ray_query and k_ray_stream and the scan of listed kinds, first named here, behind every older kernel
+static const void *kernel_ptr_sweep(const PassKernel &k)
+{
+#define MDH_SW(PF) if (k.pf == (PF)) { \
+      if (k.family == GK_k_ray_query) return k.what == MDH_RQ_SPHERECAST ? (const void *)k_ray_query<PF, MDH_RQ_SPHERECAST> : k.what == MDH_RQ_CONTACT ? (const void *)k_ray_query<PF, MDH_RQ_CONTACT> : nullptr; \
+      if (k.family == GK_k_ray_stream) return k.what == MDH_RQ_SPHERECAST ? (const void *)k_ray_stream<PF, MDH_RQ_SPHERECAST> : nullptr; }
+   MDH_SW(0) MDH_SW(1) MDH_SW(9) MDH_SW(64) MDH_SW(65) MDH_SW(73) MDH_SW(192)
+#undef MDH_SW
+   if (k.family == GK_k_listed && (k.what == MDH_RQ_SPHERECAST || k.what == MDH_RQ_CONTACT)) {
+      if (k.pf == 0) return k.what == MDH_RQ_SPHERECAST ? (const void *)k_listed<false, MDH_RQ_SPHERECAST> : (const void *)k_listed<false, MDH_RQ_CONTACT>;
+      if (k.pf == MDH_PF_GTAB) return k.what == MDH_RQ_SPHERECAST ? (const void *)k_listed<true, MDH_RQ_SPHERECAST> : (const void *)k_listed<true, MDH_RQ_CONTACT>;
+   }
+   return nullptr;
 }

@@ -1505,6 +1505,54 @@ template <int PART> MDH_DEV int softshadows_step(const KScene &sc, RayMarch &m, 
    return m.total < m.max_dist ? MDH_RS_GO : MDH_RS_OUT; // res
 }
 
+// THE SWEPT SPHERE (mdh_spherecast, mdh_kernels.h: k_ray_query, k_ray_stream): raycast's loop with the distance
+// fl (sdf (p) - rho) and the bound the ray brings -- a sphere of radius rho whose centre runs along the ray touches the scene
+// where that falls below epsilon.  x - 0.0f is x to the bit, so rho = 0 up to the scene's max_dist is raycast's march.  The
+// march carries NO arg-min: it evaluates sdf<PART>, which has sdf_info<PART>'s distance bits, and the caller asks sdf_info once,
+// at the hit (sweep_index).  The stall guard's argument holds as it stands: a march that goes on has dist >= MDH_EPS.
+#ifndef MDH_JIT
+template <int PART> MDH_DEV bool spherecast(const KScene &sc, f3 from, f3 dir, float rho, float max_dist, f3 &coll, float &t_out, int &steps)
+{
+   int n = 0;
+   MDH_WORK(0);
+   for (float total = 0.0f; total < max_dist;) {
+      MDH_WORK(1);
+      float dist = sdf<PART>(sc, from + dir * total) - rho;
+      ++n;
+      if (dist < MDH_EPS) {
+         coll = from + dir * total;
+         t_out = total;
+         steps = n;
+         return true;
+      }
+      if (total + dist == total) break; // stalled: a miss
+      total += dist;
+   }
+   steps = n;
+   return false;
+}
+// ... in step form (m.n: the evaluations so far; m.index stays -1)
+template <int PART> MDH_DEV int spherecast_step(const KScene &sc, RayMarch &m, float rho)
+{
+   MDH_WORK(1);
+   float dist = sdf<PART>(sc, m.from + m.dir * m.total) - rho;
+   ++m.n;
+   if (dist < MDH_EPS) return MDH_RS_HIT;
+   if (m.total + dist == m.total) return MDH_RS_OUT; // stalled: a miss
+   m.total += dist;
+   return m.total < m.max_dist ? MDH_RS_GO : MDH_RS_OUT;
+}
+// the primitive a sweep touches: the arg-min at the centre of contact, and that primitive's normal there
+template <int PART> MDH_DEV int sweep_index(const KScene &sc, f3 P, bool want_normal, f3 &N)
+{
+   int index = -1, material;
+   (void)sdf_info<PART>(sc, P, index);
+   N = F3(0.0f, 0.0f, 0.0f);
+   if (want_normal && index >= 0) primitive_info<false, (PART & MDH_PF_GTAB) != 0>(sc, index, P, N, material);
+   return index;
+}
+#endif
+
 // ------------------------------------------------------------------------------ lights
 // sample_<Light> (scenes.adb:497-549) dispatched by cumulative RUNTIME counts (scenes.adb:731-764)
 template <bool CUSTOM> MDH_DEV f3 sample_light(const KScene &sc, int index, f3 pos, f3 normal, f3 &dir, float &dist)

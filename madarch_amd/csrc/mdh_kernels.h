@@ -1561,9 +1561,13 @@ template <int = 0> __global__ __launch_bounds__(64) void k_eval_distance_bvh(KSc
 // (raymarching.glsl:4-56) for rays that come from the host.  One ray per lane, 64 consecutive rays per wavefront; PART is the
 // scene's variant without its census (the census variants compute the general kernels' bits).  Built-in kinds only.  The
 // marches carry the stall guard (mdh_device.h, above raycast): they end for every finite ray.
+// Two more WHAT values serve mdh_spherecast and mdh_contacts over the whole scene (sweep_query below; DESIGN.md section 4,
+// "Sweeping a host's spheres"); k_listed, behind the newest kernels of this file, serves them over the kinds a host lists.
 #define MDH_RQ_RAYCAST 0
 #define MDH_RQ_VISIBILITY 1
 #define MDH_RQ_SOFTSHADOW 2
+#define MDH_RQ_SPHERECAST 3 // mdh_spherecast: a sphere swept along the ray (spherecast, mdh_device.h)
+#define MDH_RQ_CONTACT 4    // mdh_contacts: one evaluation at a sphere's centre
 struct RayQueryArgs {
    int n;
    float tmin, k;      // soft shadow: the shader's min_dist and k
@@ -1573,7 +1577,60 @@ struct RayQueryArgs {
    int *hit, *index, *steps; // raycast: n each; all but hit may be null
    float *t, *pos, *normal;  // ... n, 3 n, 3 n
    float *out;               // visibility, soft shadow: n
+   const float *radius;      // swept spheres and contacts: n, or null: 0 (there tmax may be null too: the scene's max_dist)
 };
+#ifndef MDH_JIT
+#include "mdh_ray_stream.h"
+// A swept sphere's or a contact's answers, and the answers of one that fails the lanes' test (sweep_valid, contact_valid:
+// the host path's predicate, which the lanes apply whoever holds the arrays).  A contact's distance goes to a.t.
+MDH_DEV bool sweep_valid(const KScene &sc, f3 from, f3 dir, float rho, float tmax)
+{
+   return rs_ray_valid(from.x, from.y, from.z, dir.x, dir.y, dir.z) && rs_sweep_radius_valid(rho, sc.max_dist) && rs_sweep_tmax_valid(tmax, sc.max_dist);
+}
+MDH_DEV bool contact_valid(const KScene &sc, f3 c, float rho) { return rs_centre_valid(c.x, c.y, c.z) && rs_sweep_radius_valid(rho, sc.max_dist); }
+MDH_DEV void sweep_store(const RayQueryArgs &a, size_t q, int hit, int index, float t, int steps, f3 P, f3 N)
+{
+   a.hit[q] = hit;
+   if (a.index) a.index[q] = index;
+   if (a.t) a.t[q] = t;
+   if (a.steps) a.steps[q] = steps;
+   if (a.pos) { a.pos[3 * q] = P.x; a.pos[3 * q + 1] = P.y; a.pos[3 * q + 2] = P.z; }
+   if (a.normal) { a.normal[3 * q] = N.x; a.normal[3 * q + 1] = N.y; a.normal[3 * q + 2] = N.z; }
+}
+MDH_DEV void contact_store(const RayQueryArgs &a, size_t q, float dist, int index, f3 N)
+{
+   a.t[q] = dist;
+   if (a.index) a.index[q] = index;
+   if (a.normal) { a.normal[3 * q] = N.x; a.normal[3 * q + 1] = N.y; a.normal[3 * q + 2] = N.z; }
+}
+// the whole scene as every pass sees it: the march without an arg-min, one sdf_info at the hit
+template <int PART, int WHAT> MDH_DEV void sweep_query(const KScene &sc, const RayQueryArgs &a, size_t q)
+{
+   const f3 zero = F3(0.0f, 0.0f, 0.0f);
+   const f3 from = F3(a.org[3 * q], a.org[3 * q + 1], a.org[3 * q + 2]);
+   const float rho = a.radius ? a.radius[q] : 0.0f;
+   if (WHAT == MDH_RQ_CONTACT) {
+      if (!contact_valid(sc, from, rho)) { contact_store(a, q, __uint_as_float(MDH_RS_BAD_BITS), -1, zero); return; }
+      int index = -1, material;
+      const float dist = sdf_info<PART>(sc, from, index) - rho;
+      f3 N = zero;
+      if (a.normal && index >= 0) primitive_info<false, (PART & MDH_PF_GTAB) != 0>(sc, index, from, N, material);
+      contact_store(a, q, dist, index, N);
+      return;
+   }
+   const f3 dir = F3(a.dir[3 * q], a.dir[3 * q + 1], a.dir[3 * q + 2]);
+   const float tmax = a.tmax ? a.tmax[q] : sc.max_dist;
+   if (!sweep_valid(sc, from, dir, rho, tmax)) { sweep_store(a, q, -1, -1, 0.0f, 0, zero, zero); return; }
+   int steps = 0;
+   float t = 0.0f;
+   f3 P = zero, N = zero;
+   if (spherecast<PART>(sc, from, dir, rho, tmax, P, t, steps)) {
+      const int index = sweep_index<PART>(sc, P, a.normal != nullptr, N);
+      sweep_store(a, q, 1, index, t, steps, P, N);
+   } else
+      sweep_store(a, q, 0, -1, 0.0f, steps, zero, zero);
+}
+#endif
 template <int PART, int WHAT> __global__ __launch_bounds__(MDH_BLOCK) void k_ray_query(KScene sc, RayQueryArgs a)
 {
    static_assert(!(PART & (MDH_PF_CUSTOM | MDH_PF_POW2 | MDH_PF_ROOM | MDH_PF_PSMALL)), "ray queries: the general variants of built-in kinds");
@@ -1581,6 +1638,9 @@ template <int PART, int WHAT> __global__ __launch_bounds__(MDH_BLOCK) void k_ray
    const long lin = (long)blockIdx.x * MDH_BLOCK + threadIdx.x;
    if (lin >= (long)a.n) return;
    const size_t q = (size_t)lin;
+#ifndef MDH_JIT
+   if (WHAT == MDH_RQ_SPHERECAST || WHAT == MDH_RQ_CONTACT) { sweep_query<PART, WHAT>(sc, a, q); return; }
+#endif
    const f3 from = F3(a.org[3 * q], a.org[3 * q + 1], a.org[3 * q + 2]);
    const f3 dir = F3(a.dir[3 * q], a.dir[3 * q + 1], a.dir[3 * q + 2]);
    if (WHAT == MDH_RQ_VISIBILITY) { a.out[q] = raycast_visibility<PART, true>(sc, from, dir, a.tmax[q]); return; }
@@ -1617,6 +1677,8 @@ template <int PART, int WHAT> __global__ __launch_bounds__(MDH_BLOCK) void k_ray
 // path's predicate) and answers one that fails without a march: raycast with a miss of 0 steps, the other two with NaN.
 // stage_table's barrier is the only one: every thread of the workgroup reaches it, and none leaves the loop through a
 // barrier.  Not part of the hiprtc build (built-in kinds only).
+// MDH_RQ_SPHERECAST is the fourth march (spherecast_step, with the lane's radius beside its RayMarch): its lanes test radius and
+// length too (sweep_valid) and ask for the hit's arg-min when they store (sweep_index), among the lanes that hit alone.
 #ifndef MDH_JIT
 #include "mdh_ray_stream.h"
 struct RayStreamArgs {
@@ -1628,6 +1690,17 @@ template <int PART, int WHAT> MDH_DEV void ray_stream_store(const KScene &sc, co
 {
    if (WHAT == MDH_RQ_VISIBILITY) { a.out[q] = status == MDH_RS_HIT ? 0.0f : 1.0f; return; }
    if (WHAT == MDH_RQ_SOFTSHADOW) { a.out[q] = status == MDH_RS_HIT ? 0.0f : m.res; return; }
+   if (WHAT == MDH_RQ_SPHERECAST) { // the arg-min the march did not carry, asked once at the centre of contact
+      const f3 zero = F3(0.0f, 0.0f, 0.0f);
+      if (status == MDH_RS_HIT) {
+         const f3 C = m.from + m.dir * m.total;
+         f3 Nc;
+         const int index = sweep_index<PART>(sc, C, a.normal != nullptr, Nc);
+         sweep_store(a, q, 1, index, m.total, m.n, C, Nc);
+      } else
+         sweep_store(a, q, 0, -1, 0.0f, m.n, zero, zero);
+      return;
+   }
    const bool h = status == MDH_RS_HIT;
    int index = -1; // (a miss: the arg-min of the last step is no hit)
    float t = 0.0f;
@@ -1649,7 +1722,7 @@ template <int PART, int WHAT> MDH_DEV void ray_stream_store(const KScene &sc, co
 // a ray that is not marched
 template <int WHAT> MDH_DEV void ray_stream_refuse(const RayQueryArgs &a, size_t q)
 {
-   if (WHAT != MDH_RQ_RAYCAST) { a.out[q] = __uint_as_float(MDH_RS_BAD_BITS); return; }
+   if (WHAT == MDH_RQ_VISIBILITY || WHAT == MDH_RQ_SOFTSHADOW) { a.out[q] = __uint_as_float(MDH_RS_BAD_BITS); return; }
    a.hit[q] = -1;
    if (a.index) a.index[q] = -1;
    if (a.t) a.t[q] = 0.0f;
@@ -1667,6 +1740,7 @@ template <int PART, int WHAT> __global__ __launch_bounds__(MDH_BLOCK) void k_ray
    const unsigned n = (unsigned)a.n;
    const int refill = sa.refill;
    RayMarch m;
+   float rho = 0.0f;   // a swept sphere's radius
    long long ray = -1; // the lane's ray; -1: idle
    int status = MDH_RS_OUT;
    bool drained = false; // (wave-uniform) the counter has passed n: this wavefront takes no more rays
@@ -1683,8 +1757,10 @@ template <int PART, int WHAT> __global__ __launch_bounds__(MDH_BLOCK) void k_ray
                const size_t q = (size_t)ray;
                const float ox = a.org[3 * q], oy = a.org[3 * q + 1], oz = a.org[3 * q + 2];
                const float dx = a.dir[3 * q], dy = a.dir[3 * q + 1], dz = a.dir[3 * q + 2];
-               const float tmax = WHAT == MDH_RQ_RAYCAST ? sc.max_dist : a.tmax[q];
-               if (!rs_ray_valid(ox, oy, oz, dx, dy, dz) || (WHAT != MDH_RQ_RAYCAST && !rs_tmax_valid(tmax, sc.max_dist))) {
+               const float tmax = WHAT == MDH_RQ_RAYCAST || (WHAT == MDH_RQ_SPHERECAST && !a.tmax) ? sc.max_dist : a.tmax[q];
+               if (WHAT == MDH_RQ_SPHERECAST) rho = a.radius ? a.radius[q] : 0.0f;
+               if (WHAT == MDH_RQ_SPHERECAST ? !sweep_valid(sc, F3(ox, oy, oz), F3(dx, dy, dz), rho, tmax)
+                                             : !rs_ray_valid(ox, oy, oz, dx, dy, dz) || (WHAT != MDH_RQ_RAYCAST && !rs_tmax_valid(tmax, sc.max_dist))) {
                   ray_stream_refuse<WHAT>(a, q);
                   ray = -1; // (idle again: the next hand-out serves the lane)
                } else
@@ -1699,7 +1775,7 @@ template <int PART, int WHAT> __global__ __launch_bounds__(MDH_BLOCK) void k_ray
       }
       if (ray >= 0) {
          if (status == MDH_RS_GO)
-            status = WHAT == MDH_RQ_RAYCAST ? raycast_step<PART>(sc, m) : WHAT == MDH_RQ_VISIBILITY ? visibility_step<PART>(sc, m) : softshadows_step<PART>(sc, m, a.k);
+            status = WHAT == MDH_RQ_SPHERECAST ? spherecast_step<PART>(sc, m, rho) : WHAT == MDH_RQ_RAYCAST ? raycast_step<PART>(sc, m) : WHAT == MDH_RQ_VISIBILITY ? visibility_step<PART>(sc, m) : softshadows_step<PART>(sc, m, a.k);
          if (status != MDH_RS_GO) {
             ray_stream_store<PART, WHAT>(sc, a, (size_t)ray, m, status);
             ray = -1;
@@ -2271,6 +2347,72 @@ template <int PART> __global__ __launch_bounds__(MDH_BLOCK) void k_ray_inscatter
       if (a.len) a.len[q] = len;
       if (a.steps) a.steps[q] = count;
    }
+}
+
+// ------------------------------------------------------------------------ swept spheres against listed kinds
+// mdh_spherecast, mdh_contacts and their _device forms with a list of kinds (mdh_api.hip): the scene is the exact minimum
+// over the listed kinds' committed instances in the order listed -- eval_distance's scan above (initial closest 1.0e10f, strict
+// <: the lowest index wins a tie; no partition, no hierarchy) with the shaders' division always, since a march needs a
+// distance.  The arg-min costs the scan one select, so the march carries it; `index` is the flat index every pass uses (the
+// kind's base plus the instance), and the normal is primitive_info's of that index, computed once, for the winner -- what
+// eval_distance computes at every improvement.  One ray or centre per lane, 64 consecutive ones per wavefront; the lanes apply
+// the host path's predicate whoever holds the arrays.  WHAT: MDH_RQ_SPHERECAST or MDH_RQ_CONTACT.
+struct ListedArgs {
+   RayQueryArgs q;
+   int n_kinds;
+   int kinds[MDH_MAX_KINDS];
+   int host_count[MDH_MAX_KINDS];
+};
+template <bool GTAB> MDH_DEV float listed_closest(const KScene &sc, const ListedArgs &la, f3 p, int &index)
+{
+   float closest = 1.0e10f;
+   index = -1;
+   for (int kk = 0; kk < la.n_kinds; ++kk) {
+      const int k = la.kinds[kk], base = hdr(H_KBASE + k), count = la.host_count[k];
+      for (int i = 0; i < count; ++i) {
+         const float d = part_dist<false, GTAB, GTAB>(sc, k, i, p);
+         if (d < closest) { closest = d; index = base + i; }
+      }
+   }
+   return closest;
+}
+template <bool GTAB, int WHAT> __global__ __launch_bounds__(MDH_BLOCK) void k_listed(KScene sc, ListedArgs la)
+{
+   static_assert(WHAT == MDH_RQ_SPHERECAST || WHAT == MDH_RQ_CONTACT, "swept spheres and contacts");
+   stage_table(sc); // (the kernel's only barrier: lanes past n leave behind it)
+   const RayQueryArgs &a = la.q;
+   const long lin = (long)blockIdx.x * MDH_BLOCK + threadIdx.x;
+   if (lin >= (long)a.n) return;
+   const size_t q = (size_t)lin;
+   const f3 zero = F3(0.0f, 0.0f, 0.0f);
+   const f3 from = F3(a.org[3 * q], a.org[3 * q + 1], a.org[3 * q + 2]);
+   const float rho = a.radius ? a.radius[q] : 0.0f;
+   int index = -1, material;
+   f3 N = zero;
+   if (WHAT == MDH_RQ_CONTACT) {
+      if (!contact_valid(sc, from, rho)) { contact_store(a, q, __uint_as_float(MDH_RS_BAD_BITS), -1, zero); return; }
+      const float dist = listed_closest<GTAB>(sc, la, from, index) - rho;
+      if (a.normal && index >= 0) primitive_info<false, GTAB>(sc, index, from, N, material);
+      contact_store(a, q, dist, index, N);
+      return;
+   }
+   const f3 dir = F3(a.dir[3 * q], a.dir[3 * q + 1], a.dir[3 * q + 2]);
+   const float tmax = a.tmax ? a.tmax[q] : sc.max_dist;
+   if (!sweep_valid(sc, from, dir, rho, tmax)) { sweep_store(a, q, -1, -1, 0.0f, 0, zero, zero); return; }
+   int steps = 0;
+   bool h = false;
+   float total = 0.0f;
+   while (total < tmax) {
+      const float dist = listed_closest<GTAB>(sc, la, from + dir * total, index) - rho;
+      ++steps;
+      if (dist < MDH_EPS) { h = true; break; }
+      if (total + dist == total) break; // stalled: a miss
+      total += dist;
+   }
+   if (!h) { sweep_store(a, q, 0, -1, 0.0f, steps, zero, zero); return; }
+   const f3 P = from + dir * total;
+   if (a.normal && index >= 0) primitive_info<false, GTAB>(sc, index, P, N, material);
+   sweep_store(a, q, 1, index, total, steps, P, N);
 }
 #endif
 

@@ -94,6 +94,13 @@ MDH_RS_FN bool rs_inscatter_step_valid(float step, float max_dist)
 // a point's distance along its ray, where the caller gives one
 MDH_RS_FN bool rs_inscatter_f_valid(float f) { return rs_finite(f); }
 
+// ---------------------------------------------------------------------- which spheres are swept or tested
+// mdh_spherecast, mdh_contacts and their _device forms (mdh_kernels.h).  The marches carry the stall guard, so a finite ray is
+// all the march needs; the radius and the length are finite and within [0, max_dist] (-0 is 0).
+MDH_RS_FN bool rs_sweep_radius_valid(float radius, float max_dist) { return rs_finite(radius) && radius >= 0.0f && radius <= max_dist; }
+MDH_RS_FN bool rs_sweep_tmax_valid(float tmax, float max_dist) { return rs_finite(tmax) && tmax >= 0.0f && tmax <= max_dist; }
+MDH_RS_FN bool rs_centre_valid(float x, float y, float z) { return rs_finite(x) && rs_finite(y) && rs_finite(z); }
+
 // ---------------------------------------------------------------------- the hand-out
 MDH_RS_FN int rs_popcount(unsigned long long m) { return __builtin_popcountll(m); }
 // does a wavefront with n_idle idle lanes take new rays?

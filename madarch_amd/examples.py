@@ -156,12 +156,15 @@ class Ball_Game:
     thrown from the camera that bounce off planes and boxes.  The physics step is the reference's: per
     ball one Eval_Distance_To against (Plane, Box) -- the CPU expression evaluator there, the batched device
     query here -- then Set_Primitive; every frame rebuilds the partition (Update_Partitioning) and renders.
-    The interactive parts (keys, mouse) are the methods Throw_Ball / Move_Camera."""
+    The interactive parts (keys, mouse) are the methods Throw_Ball / Move_Camera.
+    Swept = True replaces the point test, which a ball whose step is longer than an obstacle is thick passes through, by ONE
+    Spherecast for all balls: the first contact of each moving sphere with the planes and boxes."""
 
     Ball_Radius = np.float32(0.2)
     Gravity = np.array([0.0, -9.81, 0.0], dtype=np.float32)
 
-    def __init__(self, Width=1000, Height=1000, Probes=None, Binding=None, Device=0):
+    def __init__(self, Width=1000, Height=1000, Probes=None, Binding=None, Device=0, Swept=False):
+        self.Swept = bool(Swept)
         self.Scene = scenes.Compile(  # main.adb:30-35: the default partitioning settings (enabled)
             All_Primitives=[(spheres.Sphere, 20), (planes.Plane, 10), (boxes.Box, 10)],
             All_Lights=[(spot_lights.Spot_Light, 4)])
@@ -198,6 +201,8 @@ class Ball_Game:
         Dt = np.float32(Dt)
         new_vel = [(b[2] + self.Gravity * Dt).astype(np.float32) for b in self.Ball_Bodies]
         new_pos = [(b[1] + v * Dt).astype(np.float32) for b, v in zip(self.Ball_Bodies, new_vel)]
+        if self.Swept:
+            return self._step_swept(Dt, new_vel, new_pos)
         dists, normals = self.R.Eval_Distances_To(np.stack(new_pos), (planes.Plane, boxes.Box))
         for body, vel, pos, dist, normal in zip(self.Ball_Bodies, new_vel, new_pos, dists, normals):
             if np.float32(dist) <= self.Ball_Radius:
@@ -208,14 +213,32 @@ class Ball_Game:
             self.R.Set_Primitive(spheres.Sphere, body[0], spheres.Create(pos, self.Ball_Radius, self.Box_Mat))
             body[1], body[2] = pos, vel
 
+    def _step_swept(self, Dt, new_vel, new_pos):
+        """the balls' spheres swept from their old centres along their new velocities over the step's length: a ball that
+        touches a plane or a box on the way is reflected about the contact's normal and placed at the contact's centre (a ball
+        that rests on a surface and moves away from it touches at t = 0 and is let go)"""
+        speed = [np.sqrt(np.float32((v[0] * v[0] + v[1] * v[1]) + v[2] * v[2])) for v in new_vel]
+        drs = np.stack([v / s if s > 0.0 else np.zeros(3, np.float32) for v, s in zip(new_vel, speed)]).astype(np.float32)
+        tmax = np.minimum(np.asarray(speed, np.float32) * Dt, np.float32(self.Scene.Max_Dist))
+        cast = self.R.Spherecast(np.stack([b[1] for b in self.Ball_Bodies]), drs, self.Ball_Radius, tmax, (planes.Plane, boxes.Box))
+        for k, (body, vel, pos) in enumerate(zip(self.Ball_Bodies, new_vel, new_pos)):
+            if cast["hit"][k] == 1:
+                normal = cast["normal"][k]
+                d = np.float32((vel[0] * normal[0] + vel[1] * normal[1]) + vel[2] * normal[2])
+                if d < 0.0 or cast["t"][k] > 0.0:
+                    vel = (vel - np.float32(2.0) * d * normal).astype(np.float32)  # Math_Utils.Reflect, math_utils.adb:38-42
+                    pos = cast["position"][k].copy()
+            self.R.Set_Primitive(spheres.Sphere, body[0], spheres.Create(pos, self.Ball_Radius, self.Box_Mat))
+            body[1], body[2] = pos, vel
+
     def Frame(self, Dt=0.01):  # the loop body, main.adb:244-252
         self.Step_Physics(Dt)
         self.R.Update_Partitioning()
         self.R.Render()
 
 
-def ball_game(Width=1000, Height=1000, Probes=None, Binding=None, Device=0):
-    return Ball_Game(Width, Height, Probes, Binding, Device)
+def ball_game(Width=1000, Height=1000, Probes=None, Binding=None, Device=0, Swept=False):
+    return Ball_Game(Width, Height, Probes, Binding, Device, Swept)
 
 
 def fisheye_view(R, Width, Height, Fov=np.pi, Mode=0, Tone_Map=True):

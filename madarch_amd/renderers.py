@@ -226,6 +226,80 @@ class Renderer:
         """blocks until every device query enqueued so far has ended"""
         self._b.check(self._b.ray_query_wait(self._h))
 
+    # ---- swept spheres and contacts, for a host that owns moving bodies.  Prims = None: the scene as every pass sees it;
+    # a tuple of kinds: the exact minimum over those kinds' instances, in the order given (always the shaders' division)
+    def _kinds(self, Prims):
+        if Prims is None:
+            return None, 0
+        kinds = np.asarray([self.Scene.prim_kind_index(p) for p in Prims], dtype=np.int32)
+        if len(kinds) == 0:
+            raise ValueError("Prims: None for the whole scene, or at least one kind")
+        return kinds, len(kinds)
+
+    @staticmethod
+    def _per_item(Values, n, What):
+        """None, or one float32 per ray or centre (a scalar is broadcast): ValueError before any library call"""
+        if Values is None:
+            return None
+        v = np.asarray(Values, dtype=np.float32)
+        if v.ndim == 0:
+            v = np.full(n, v, dtype=np.float32)
+        if v.shape != (n,):
+            raise ValueError("%s: one value per ray or centre: %s for %d" % (What, v.shape, n))
+        return np.ascontiguousarray(v)
+
+    def Spherecast(self, Origins, Directions, Radii=None, Max_Dists=None, Prims=None):
+        """a sphere of radius Radii (None: 0) swept with its centre along every ray up to Max_Dists (None: the scene's
+        max_dist): {hit, index, t, steps, position, normal} -- position is the centre at contact, normal the touched
+        primitive's normal at that centre"""
+        org, drs, tmax = self._rays(Origins, Directions, Max_Dists)
+        n = len(org)
+        rad = self._per_item(Radii, n, "Radii")
+        kinds, nk = self._kinds(Prims)
+        out = {"hit": np.zeros(n, np.int32), "index": np.zeros(n, np.int32), "t": np.zeros(n, np.float32),
+               "steps": np.zeros(n, np.int32), "position": np.zeros((n, 3), np.float32), "normal": np.zeros((n, 3), np.float32)}
+        self._b.check(self._b.spherecast(self._h, n, _fp(org), _fp(drs), None if rad is None else _fp(rad), None if tmax is None else _fp(tmax),
+                                         None if kinds is None else _fp(kinds), nk, _fp(out["hit"]), _fp(out["index"]), _fp(out["t"]),
+                                         _fp(out["steps"]), _fp(out["position"]), _fp(out["normal"])))
+        return out
+
+    def Contacts(self, Centres, Radii=None, Prims=None):
+        """one evaluation at every centre: {dist, index, normal}, dist = the scene's distance minus the radius (negative
+        where the sphere penetrates), index the closest primitive (-1: none exists), normal its normal at the centre"""
+        pts = np.ascontiguousarray(Centres, dtype=np.float32)
+        if pts.ndim != 2 or pts.shape[1] != 3:
+            raise ValueError("centres are an (n, 3) array, not %s" % (pts.shape,))
+        n = len(pts)
+        rad = self._per_item(Radii, n, "Radii")
+        kinds, nk = self._kinds(Prims)
+        out = {"dist": np.zeros(n, np.float32), "index": np.zeros(n, np.int32), "normal": np.zeros((n, 3), np.float32)}
+        self._b.check(self._b.contacts(self._h, n, _fp(pts), None if rad is None else _fp(rad), None if kinds is None else _fp(kinds), nk,
+                                       _fp(out["dist"]), _fp(out["index"]), _fp(out["normal"])))
+        return out
+
+    def Spherecast_Device(self, Origins, Directions, Hit, Radii=None, Max_Dists=None, Prims=None, Index=None, T=None, Steps=None,
+                          Position=None, Normal=None, Stream=0, N=None):
+        """Spherecast for N rays in device memory under Raycast_Device's contract; Radii and Max_Dists are device arrays or
+        None.  A ray, radius or length the host-array call would refuse is not marched: hit = -1, index = -1, the rest 0."""
+        n = self._ray_count(Origins, N)
+        dev = self._device_array
+        kinds, nk = self._kinds(Prims)
+        args = [dev(Origins, "Origins", 3 * n, "float32"), dev(Directions, "Directions", 3 * n, "float32"),
+                dev(Radii, "Radii", n, "float32", True), dev(Max_Dists, "Max_Dists", n, "float32", True),
+                None if kinds is None else _fp(kinds), nk, dev(Hit, "Hit", n, "int32"),
+                dev(Index, "Index", n, "int32", True), dev(T, "T", n, "float32", True), dev(Steps, "Steps", n, "int32", True),
+                dev(Position, "Position", 3 * n, "float32", True), dev(Normal, "Normal", 3 * n, "float32", True)]
+        self._b.check(self._b.spherecast_device(self._h, n, *args, C.c_void_p(int(Stream))))
+
+    def Contacts_Device(self, Centres, Dist, Radii=None, Prims=None, Index=None, Normal=None, Stream=0, N=None):
+        """Contacts likewise; a centre or radius the host-array call would refuse is answered with dist = NaN, index = -1"""
+        n = self._ray_count(Centres, N)
+        dev = self._device_array
+        kinds, nk = self._kinds(Prims)
+        args = [dev(Centres, "Centres", 3 * n, "float32"), dev(Radii, "Radii", n, "float32", True), None if kinds is None else _fp(kinds), nk,
+                dev(Dist, "Dist", n, "float32"), dev(Index, "Index", n, "int32", True), dev(Normal, "Normal", 3 * n, "float32", True)]
+        self._b.check(self._b.contacts_device(self._h, n, *args, C.c_void_p(int(Stream))))
+
     # ---- what a ray sees: the frame's pixel program (pixel_color_probes, render_probes.glsl:246-291) along rays of the host's
     @staticmethod
     def _shade_mode(Mode):
