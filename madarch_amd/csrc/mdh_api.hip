@@ -4596,6 +4596,19 @@ extern "C" int32_t mdh_diag_bvh(unsigned long long *out2)
 }
 #endif
 
+#ifdef MDH_BEST_STATS
+// the counter build: the best-first probe search's wave-rounds, winning lanes, fallback wavefronts and fallback lanes since the last call
+extern "C" int32_t mdh_diag_best_first(unsigned long long *out4)
+{
+   if (!out4) return MDH_E_INVALID;
+   if (hipDeviceSynchronize() != hipSuccess) return MDH_E_DEVICE;
+   if (hipMemcpyFromSymbol(out4, HIP_SYMBOL(g_best_stats), sizeof(unsigned long long) * 4) != hipSuccess) return MDH_E_DEVICE;
+   unsigned long long z[4] = {0, 0, 0, 0};
+   if (hipMemcpyToSymbol(HIP_SYMBOL(g_best_stats), z, sizeof z) != hipSuccess) return MDH_E_DEVICE;
+   return MDH_OK;
+}
+#endif
+
 // MDH_OPT_SCREEN_REPLAY: screen passes launched since creation that marched, marched and recorded, replayed
 extern "C" int32_t mdh_screen_replay_stats(mdh_renderer *r, int64_t *plain, int64_t *recording, int64_t *replaying)
 {

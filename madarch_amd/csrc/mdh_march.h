@@ -32,6 +32,20 @@
 #define MDH_TWIN_FOLDED 1 // ... and a corner of it folded along y or z takes its twin's weight and visibility bit instead of computing them again
 #endif
 
+#ifndef MDH_BEST_FIRST
+#ifdef MDH_DIAG
+#define MDH_BEST_FIRST 0 // (the diagnostic builds count the in-order loop's rays: their work counters are pinned)
+#else
+#define MDH_BEST_FIRST 1 // the second point's cage probes visited by decreasing dot(probe_to_spec, -N): the first visible one is the loop's (shade_structured)
+#endif
+#endif
+#ifdef MDH_BEST_STATS // the counter build (make beststats), summed over launches until mdh_diag_best_first takes them:
+__device__ unsigned long long g_best_stats[4]; // wave-rounds of the fast path, lanes that won there, wavefronts in the fallback, lanes in it
+#define MDH_BEST_STAT(slot, n) do { const unsigned long long n_ = (n); if ((threadIdx.x & 63) == __ffsll((long long)__ballot(1)) - 1) atomicAdd(&g_best_stats[slot], n_); } while (0)
+#else
+#define MDH_BEST_STAT(slot, n) do { } while (0)
+#endif
+
 struct MachineCfg {
    bool direct_specular;   // M_COMPUTE_DIRECT_SPECULAR
    int spec_mode;          // M_COMPUTE_INDIRECT_SPECULAR: 0 none, 1 .. 3 the three bodies of render_probes.glsl:264-272
@@ -522,6 +536,19 @@ constexpr bool folded_twins_screen(int PART, bool GBUF, int REC)
           !((PART == 0 && GBUF && REC != 1) || (PART == MDH_PF_POW2 && !GBUF && REC == 0) || (PART == MDH_PF_POW2 && GBUF && REC == 2) ||
             (PART == (MDH_PF_ROOM | MDH_PF_POW2) && REC == 2) || (PART == MDH_PF_ROOM && !GBUF && REC == 1));
 }
+// SHARET | 4: the second point's best cage probe searched best first (MDH_BEST_FIRST, in front of the corner loop; DESIGN.md section 4
+// item 17) -- a bit of its own beside the two of the sharing level, which is SHARET & 3.  The screen kernels of the fixed mode over the built-in scans, marching and recording, take it and keep their registers,
+// their scratch memory and their wavefronts per SIMD to the digit (the scan over the corners is a rolled loop: unrolled it cost
+// every one of them 16 bytes of scratch per lane) -- but for three, which paid 16 bytes and keep the code they had
+// (resource_usage.sh, before against after):
+//   k_screen <0, 0, GBUF, REC 0>            brute-force scan with the geometry buffer, marching:      32 -> 48
+//   k_screen <POW2, 0, GBUF, REC 1>         ... with power-of-two atlases, recording:                 32 -> 48
+//   k_screen <ROOM, 0, GBUF, REC 1>         the rooms' census with the geometry buffer, recording:    64 -> 80
+// k_ray_shade and k_point_shade are left as they are (shade_structured's default).
+constexpr bool best_first_screen(int PART, bool GBUF, int REC)
+{
+   return REC != 2 && !(GBUF && ((PART == 0 && REC == 0) || (PART == MDH_PF_POW2 && REC == 1) || (PART == MDH_PF_ROOM && REC == 1)));
+}
 // POINT (k_point_shade, mdh_kernels.h: mdh_shade_points): the first shaded point is the caller's -- `from` is the point itself,
 // `dir_in` the direction it is seen along, `pt_normal` and `pt_material` what primitive_info would have said -- and context 0
 // runs no primary march, no arg-min scan and no primitive_info: every valid lane "hits" at its point with index -1, t 0 and
@@ -552,10 +579,15 @@ MDH_DEV f3 shade_structured(const KScene &sc, const KProbes &pr, const MachineCf
    // the first point's eight irradiance taps fetched once per wavefront where its lanes share them (item 15 of "Exact work
    // elimination", at the corner loop below): the screen family's fixed mode over the built-in scans only -- every other
    // instantiation is the code it was
-   constexpr bool SHARE_TAPS = MDH_SHARE_TAPS != 0 && SHARET && SPEC == 1 && !QVIS && MODE == 0 && TAP_EARLY && (PART & ~(MDH_PF_ROOM | MDH_PF_POW2)) == 0;
+   constexpr bool SHARE_TAPS = MDH_SHARE_TAPS != 0 && (SHARET & 3) && SPEC == 1 && !QVIS && MODE == 0 && TAP_EARLY && (PART & ~(MDH_PF_ROOM | MDH_PF_POW2)) == 0;
    // ... and in such a wavefront (item 16) a corner folded along y or z takes the weight and the visibility bit of the corner it
    // folds onto, kept in four registers
-   constexpr bool TWIN_FOLDED = MDH_TWIN_FOLDED != 0 && SHARET == 2 && SHARE_TAPS && CORNER_UNROLL == 8;
+   constexpr bool TWIN_FOLDED = MDH_TWIN_FOLDED != 0 && (SHARET & 3) == 2 && SHARE_TAPS && CORNER_UNROLL == 8;
+   // the second point's best cage probe searched by decreasing d = dot(probe_to_spec, -N) instead of corner by corner (item 17 of
+   // "Exact work elimination", in front of the corner loop below): the screen family's fixed mode over the built-in scans,
+   // marching and recording -- every other instantiation is the code it was
+   constexpr bool BEST_FIRST = MDH_BEST_FIRST != 0 && (SHARET & 4) != 0 && MDH_SHARE_FIRST_STEP != 0 && MDH_REUSE_FOLDED != 0 && SPEC == 1 && !QVIS && MODE == 0 &&
+                               (PART & ~(MDH_PF_ROOM | MDH_PF_POW2)) == 0 && REC != 2;
    // the space-partition variants of the screen pass: the shaded point and its normal come back from park rows behind every
    // corner's visibility march (the second point's wait in the rows of its colour and in three rows of their own) and the probe's grid position is derived again there:
    // the lookups of that march need the registers -- kept live across it, these values went to scratch memory eight times per
@@ -806,6 +838,79 @@ MDH_DEV f3 shade_structured(const KScene &sc, const KProbes &pr, const MachineCf
                   // also folds along x holds what the x-twin in front of it left (twin_prev), which is b's value again.
                   float w_fold[4] = {0.0f, 0.0f, 0.0f, 0.0f};
                   const int folds = (TWIN_FOLDED && shared) ? (__builtin_amdgcn_readfirstlane(folded) & 6) : 0;
+                  // The second point's loop names ONE probe: the first corner in index order that attains the maximum of W_i, where
+                  // W_i = d_i = dot(probe_to_spec_i, -N) if corner i is visible and d_i * 0 otherwise (MDH_SKIP_NULL_RAYS rests on
+                  // the same reading).  In index order a wavefront runs a corner's clearance test while ANY of its lanes can still
+                  // win there.  Here every lane takes its untried corner of largest d > 0 (the lowest index among equals) per round
+                  // -- a scan with the loop's own statements in the loop's order, nothing contracted, no test and no march -- and
+                  // sends that one ray through the immediate outcomes, segment_clear and the march.  A visible candidate c is the
+                  // loop's probe: every corner of larger d was tried before it and is blocked, W = +0 < d_c; every corner of equal d
+                  // and lower index likewise; every other W_j <= d_j <= d_c, and an equal one has a higher index, so it is not
+                  // strictly larger; a NaN wins in neither form.  Only best_q and acc leave the loop, and they are c's: the same
+                  // operations on the same values.  A lane that runs out of candidates of positive d without a visible one (all
+                  // blocked, none in front, a NaN) takes the in-order loop below from corner 0 as it is; the lanes that hold a
+                  // winner sit it out.  The record (REC 1) of a winner: 1 for the winner and for every untried corner (a skipped
+                  // corner's value), 0 for a tried and blocked one.  The replaying kernel's in-order loop over these bits sees
+                  // W'_c = d_c, +0 at the tried corners, and d_j at the untried ones, which are <= d_c and above index c where equal
+                  // (or not positive, or NaN): it names c.  A fallback lane's record is the loop's own.
+                  bool in_order = true;
+                  if (BEST_FIRST && ctx == 1) {
+                     int tried = 0; // bit i: corner i was a candidate and is blocked
+                     bool searching = true;
+                     in_order = false;
+                     // the candidate of the round; a winner's stays as it is (a lane that is not searching scans nothing)
+                     float bvmax = 0.0f;
+                     f3 bvd = F3(0.0f, 0.0f, 0.0f);
+                     int bi = -1, bq = 0;
+#pragma unroll 1
+                     for (;;) {
+                        if (searching) {
+                           float bd = 0.0f;
+                           bi = -1;
+#pragma unroll 1
+                           for (int i = 0; i < 8; ++i) {
+                              if ((i & folded) || ((tried >> i) & 1)) continue;
+                              const KProbes pq = probes_fresh(pr);
+                              const i3 q = cage_probe(pq, gp, i);
+                              const f3 pw = grid_to_world(pq, q);
+                              const f3 hvec = P - pw;
+                              const float dist = length(hvec);
+                              f3 vd = sdiv3(hvec, dist);
+                              vd = -vd;
+                              const float d = dot(-vd, -N);
+                              if (d > bd) { bd = d; bi = i; bvd = vd; bvmax = dist - MDH_MIN_STEP * 5.0f; bq = q.x | (q.y << 10) | (q.z << 20); }
+                           }
+                           if (bi < 0) { in_order = true; searching = false; }
+                        }
+                        if (!__ballot(searching)) break;
+                        MDH_BEST_STAT(0, 1);
+                        // raycast_visibility of the candidate, as the loop runs it (a lane that is not searching has no ray: vmax 0)
+                        float vis = 1.0f, total = 0.0f;
+                        float vmax = searching ? bvmax : 0.0f;
+                        if (0.0f < vmax && !(sd0 < MDH_EPS) && sd0 < vmax)
+                           if (segment_clear<PART>(sc, from_off, bvd, vmax)) vmax = 0.0f;
+                        bool first = true;
+                        while (total < vmax) {
+                           float sd = first ? sd0 : sdf<PART>(sc, from_off + bvd * total);
+                           first = false;
+                           if (sd < MDH_EPS) { vis = 0.0f; break; }
+                           total += sd;
+                        }
+                        if (searching) {
+                           if (vis != 0.0f) searching = false;
+                           else tried |= 1 << bi;
+                        }
+                     }
+                     MDH_BEST_STAT(1, __popcll(__ballot(!in_order)));
+                     if (!in_order) { best_q = bq; acc = -bvd; } // (accw, the winner's d, is read by nobody behind the loop)
+                     if (SREC && REC == 1 && !in_order) {
+#pragma unroll
+                        for (int i = 0; i < 8; ++i)
+                           if (!(i & folded) && !((tried >> i) & 1)) vis_bits |= 1 << i;
+                     }
+                     if (__ballot(in_order)) { MDH_BEST_STAT(2, 1); MDH_BEST_STAT(3, __popcll(__ballot(in_order))); }
+                  }
+                  if (in_order)
 #pragma unroll CORNER_UNROLL
                   for (int i = 0; i < 8; ++i) {
                      // best probe: a folded corner has the weight of its twin, which is not strictly larger
