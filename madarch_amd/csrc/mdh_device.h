@@ -914,8 +914,22 @@ template <bool CUSTOM, bool ROOM = false, bool GTAB = false, bool BVH = false> M
    return closest;
 }
 // closest_primitive_info (scenes.adb:631-674): kinds in SCENE order (the arg-min keeps the
-// first of equal distances).  Only evaluated at hit points, so compact rather than fast.
-template <bool CUSTOM, bool GTAB = false, bool BVH = false> MDH_DEV float closest_primitive_info(const KScene &sc, f3 x, int &index)
+// first of equal distances).  Evaluated at hit points only -- twice per pixel of the screen pass.
+//
+// MDH_INFO_CULL (CULL): the typed arg-min skips a sphere or a box behind closest_primitive's two
+// wave-ballot culls, the same inequalities and margins against the running `closest` the planes left.  A skipped candidate has
+// d > closest STRICTLY in every lane (the margins' argument at closest_primitive), so under MDH_CAND's rule -- closer, or as
+// close with a lower flat index -- it can neither win nor tie: `closest` and `best` keep their bits.  NaN: `closest` is never NaN
+// (MDH_CAND takes no NaN distance, and max_dist is the scene's).  The sphere's test is written so that a NaN d2 leaves `need`
+// true.  The box's m = max_ (q.x, max_ (q.y, q.z)) is maxNum and DROPS a NaN component of q, so a lane with a NaN coordinate can
+// still cull the box: sd_box drops the same component through the same max_ calls, its d >= m (1 - 2^-23) > closest holds over
+// the components that are left, and where all three are NaN m is NaN and `need` stays true -- and a NaN d would not be taken anyway.  A
+// tile that lies on a wall culls both and takes no root.  ROOM (the census known when the kernel is built, as in
+// closest_primitive): one sphere, one box, no triangles -- no loops, no count or base read beyond the two it needs.
+#ifndef MDH_INFO_CULL
+#define MDH_INFO_CULL 1
+#endif
+template <bool CUSTOM, bool GTAB = false, bool BVH = false, bool ROOM = false, bool CULL = false> MDH_DEV float closest_primitive_info(const KScene &sc, f3 x, int &index)
 {
    const typename Geo<GTAB>::F4 s_tab = Geo<GTAB>::f4(sc); // (shadows the LDS table, as in closest_primitive)
    float closest = sc.max_dist;
@@ -930,7 +944,7 @@ template <bool CUSTOM, bool GTAB = false, bool BVH = false> MDH_DEV float closes
          const int i_ = (idx_);                                                                    \
          if (d_ < closest || (d_ == closest && best >= 0 && i_ < best)) { closest = d_; best = i_; } \
       } while (0)
-      if (sc.n_axis > 0) {
+      if (ROOM || sc.n_axis > 0) {
          const float c[6] = {x.x, -x.x, x.y, -x.y, x.z, -x.z};
 #pragma unroll
          for (int g = 0; g < 6; ++g) {
@@ -938,23 +952,59 @@ template <bool CUSTOM, bool GTAB = false, bool BVH = false> MDH_DEV float closes
             if (pi >= 0) MDH_CAND(c[g] + sc.axis_off[g], pi);
          }
       }
-      {
-         const int n = sc.tcount[PK_SPHERE], s0 = sc.tslot[PK_SPHERE], base = hdr(H_TBASE + PK_SPHERE);
+      // closest_primitive's culls (its MDH_SPHERE_STEP and MDH_BOX_STEP): false when no lane of the wavefront can take the candidate
+#define MDH_SPHERE_NEEDED(a_, need_)                                                               \
+      do {                                                                                         \
+         const float tsum_ = closest + (a_).w;                                                     \
+         const float d2_ = dot2(xyz(a_) - x);                                                      \
+         need_ = __ballot(!(tsum_ < 0.0f) && !(d2_ > (tsum_ * tsum_) * 1.000001f)) != 0ull;        \
+      } while (0)
+#define MDH_BOX_NEEDED(c_, e_, need_)                                                              \
+      do {                                                                                         \
+         const f3 q_ = abs3(xyz(c_) - x) - xyz(e_);                                                \
+         const float thr_ = closest > 0.0f ? closest * 1.000001f : closest;                        \
+         need_ = __ballot(!(max_(q_.x, max_(q_.y, q_.z)) > thr_)) != 0ull;                         \
+      } while (0)
+      if (ROOM) { // one sphere, one box, no triangles
+         const float4 a = s_tab[sc.tslot[PK_SPHERE]];
+         const float4 c = s_tab[sc.tslot[PK_BOX]], e = s_tab[sc.tslot[PK_BOX] + 1];
+         bool need = true;
+         if (CULL) MDH_SPHERE_NEEDED(a, need);
+         if (need) MDH_CAND(sd_sphere(a, x), hdr(H_TBASE + PK_SPHERE));
+         need = true;
+         if (CULL) MDH_BOX_NEEDED(c, e, need);
+         if (need) MDH_CAND(sd_box(c, e, x), hdr(H_TBASE + PK_BOX));
+      } else {
+         {
+            const int n = sc.tcount[PK_SPHERE], s0 = sc.tslot[PK_SPHERE], base = hdr(H_TBASE + PK_SPHERE);
 #pragma unroll 1
-         for (int i = 0; i < n; ++i) MDH_CAND(sd_sphere(s_tab[uni<GTAB>(s0 + i)], x), base + i);
-      }
-      {
-         const int n = sc.tcount[PK_BOX], s0 = sc.tslot[PK_BOX], base = hdr(H_TBASE + PK_BOX);
+            for (int i = 0; i < n; ++i) {
+               const float4 a = s_tab[uni<GTAB>(s0 + i)];
+               bool need = true;
+               if (CULL) MDH_SPHERE_NEEDED(a, need);
+               if (need) MDH_CAND(sd_sphere(a, x), base + i);
+            }
+         }
+         {
+            const int n = sc.tcount[PK_BOX], s0 = sc.tslot[PK_BOX], base = hdr(H_TBASE + PK_BOX);
 #pragma unroll 1
-         for (int i = 0; i < n; ++i) MDH_CAND(sd_box(s_tab[uni<GTAB>(s0 + 2 * i)], s_tab[uni<GTAB>(s0 + 2 * i + 1)], x), base + i);
-      }
-      if (BVH) bvh_triangles<true>(sc, x, closest, best, hdr(H_TBASE + PK_TRIANGLE)); // (MDH_CAND's rule: the arg-min does not depend on the order of the visits)
-      else {
-         const int n = sc.tcount[PK_TRIANGLE], s0 = sc.tslot[PK_TRIANGLE], base = hdr(H_TBASE + PK_TRIANGLE);
+            for (int i = 0; i < n; ++i) {
+               const float4 c = s_tab[uni<GTAB>(s0 + 2 * i)], e = s_tab[uni<GTAB>(s0 + 2 * i + 1)];
+               bool need = true;
+               if (CULL) MDH_BOX_NEEDED(c, e, need);
+               if (need) MDH_CAND(sd_box(c, e, x), base + i);
+            }
+         }
+         if (BVH) bvh_triangles<true>(sc, x, closest, best, hdr(H_TBASE + PK_TRIANGLE)); // (MDH_CAND's rule: the arg-min does not depend on the order of the visits)
+         else {
+            const int n = sc.tcount[PK_TRIANGLE], s0 = sc.tslot[PK_TRIANGLE], base = hdr(H_TBASE + PK_TRIANGLE);
 #pragma unroll 1
-         for (int i = 0; i < n; ++i)
-            MDH_CAND(sd_triangle<false>(xyz(s_tab[uni<GTAB>(s0 + 3 * i)]), xyz(s_tab[uni<GTAB>(s0 + 3 * i + 1)]), xyz(s_tab[uni<GTAB>(s0 + 3 * i + 2)]), x), base + i);
+            for (int i = 0; i < n; ++i)
+               MDH_CAND(sd_triangle<false>(xyz(s_tab[uni<GTAB>(s0 + 3 * i)]), xyz(s_tab[uni<GTAB>(s0 + 3 * i + 1)]), xyz(s_tab[uni<GTAB>(s0 + 3 * i + 2)]), x), base + i);
+         }
       }
+#undef MDH_SPHERE_NEEDED
+#undef MDH_BOX_NEEDED
 #undef MDH_CAND
       if (best >= 0) index = best;
       return closest;
@@ -1298,7 +1348,8 @@ template <int PART> MDH_DEV float sdf_info(const KScene &sc, f3 x, int &index)
 {
    MDH_WORK(2);
    if (PART & MDH_PF_PART) return partitioning_lookup<true, (PART & MDH_PF_CUSTOM) != 0, MDH_PF_HAS_FALLBACK(PART), (PART & MDH_PF_PSMALL) != 0, (PART & MDH_PF_GTAB) != 0>(sc, x, index);
-   return closest_primitive_info<(PART & MDH_PF_CUSTOM) != 0, (PART & MDH_PF_GTAB) != 0, (PART & MDH_PF_BVH) != 0>(sc, x, index);
+   constexpr bool INFO_CULL = MDH_INFO_CULL != 0; // (closest_primitive's culls in the typed arg-min; no kernel paid for them in scratch memory or wavefronts: resource_usage.sh)
+   return closest_primitive_info<(PART & MDH_PF_CUSTOM) != 0, (PART & MDH_PF_GTAB) != 0, (PART & MDH_PF_BVH) != 0, INFO_CULL && (PART & MDH_PF_ROOM) != 0, INFO_CULL>(sc, x, index);
 }
 
 // ------------------------------------------------------------- probe-visibility clearance
@@ -1374,6 +1425,8 @@ template <int PART> MDH_DEV bool segment_clear_bound(const KScene &sc, f3 A, f3 
                           __builtin_fabsf(m.y * hv.z - m.z * hv.y) > e.y * ah.z + e.z * ah.y ||
                           __builtin_fabsf(m.z * hv.x - m.x * hv.z) > e.z * ah.x + e.x * ah.z ||
                           __builtin_fabsf(m.x * hv.y - m.y * hv.x) > e.x * ah.y + e.y * ah.x;
+         // (measured and dropped, round 23: the three cross axes behind a ballot of the lanes the face axes leave -- DESIGN.md
+         //  section 4 "What was tried and dropped")
          ok = ok && sep;
       }
    }
