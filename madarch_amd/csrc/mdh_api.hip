@@ -342,12 +342,9 @@ struct mdh_renderer {
    bool rq_timed = false; // (the query in flight recorded them)
    double rq_ms = 0.0;    // ... and the time of the last one timed (mdh_ray_query_time)
    // the device-array ray queries (mdh_raycast_device, ..): the counter k_ray_stream's wavefronts take their rays from (one:
-   // the launches follow one another on the query stream), and the two events between the caller's stream and the query stream
+   // the launches follow one another on the query stream)
    DevBuf<unsigned> d_rq_next;
-   Event ev_rq_in, ev_rq_out;
-   // mdh_shade_rays, mdh_shade_rays_device: the events between the main stream and the query stream on both sides of the kernel
-   // (the atlas set the query reads: shade_rays_run), and the one from the caller's stream (one group, created by the first call)
-   Event ev_sq_frame, ev_sq_caller, ev_sq_done;
+   QueryBridge bridge; // every query's events to the caller's stream and to the frames (query_enqueue; created by the first that needs one)
    int opt_rq_refill = MDH_RAY_STREAM_REFILL_DEFAULT; // MDH_OPT_RAY_STREAM_REFILL
    int opt_rq_groups = 0;                             // MDH_OPT_RAY_STREAM_GROUPS (0: as many workgroups as are resident)
    // Two sets of probe atlases.  `last` is the set the most recent frame wrote: every read, write and
@@ -3504,6 +3501,14 @@ extern "C" int32_t mdh_set_stream(mdh_renderer *r, void *stream)
    return MDH_OK;
 }
 
+// the query stream, created by the first call that needs it (device_set: the caller has made the device current)
+static int query_stream_get(mdh_renderer *r, hipStream_t *qs, bool device_set = false)
+{
+   if (!device_set) HIP_TRY(hipSetDevice(r->device));
+   if (!r->query_stream) HIP_TRY(hipStreamCreateWithFlags(&r->query_stream, hipStreamNonBlocking));
+   *qs = r->query_stream;
+   return MDH_OK;
+}
 // Eval_Distance_To (renderers.adb:499-526), batched on the device
 extern "C" int32_t mdh_eval_distance_to(mdh_renderer *r, int32_t n, const float *pts, const int32_t *kind_ixs, int32_t n_kinds,
                                         float *normals_out, float *dist_out)
@@ -3514,11 +3519,9 @@ extern "C" int32_t mdh_eval_distance_to(mdh_renderer *r, int32_t n, const float 
       if (kind_ixs[i] < 0 || kind_ixs[i] >= r->npk) return seterr(MDH_E_INVALID, "bad kind index");
    if (n == 0) return MDH_OK;
    // on a stream of its own: the query waits for the table it reads, not for the frames in flight
-   HIP_TRY(hipSetDevice(r->device));
-   if (!r->query_stream) HIP_TRY(hipStreamCreateWithFlags(&r->query_stream, hipStreamNonBlocking));
-   hipStream_t qs = r->query_stream;
-   int rc = ensure_committed(r, qs);
-   if (rc != MDH_OK) return rc;
+   hipStream_t qs = nullptr;
+   int rc = query_stream_get(r, &qs);
+   if (rc != MDH_OK || (rc = ensure_committed(r, qs)) != MDH_OK) return rc;
    const size_t want = ((size_t)n < 256 ? 256 : (size_t)n) * 7; // 7 floats per query: point, normal, distance
    if (want > r->d_query.cap) {
       if (r->d_query.ptr) HIP_TRY(hipStreamSynchronize(qs));
@@ -3541,141 +3544,73 @@ extern "C" int32_t mdh_eval_distance_to(mdh_renderer *r, int32_t n, const float 
    return MDH_OK;
 }
 
-// ------------------------------------------------------------------ ray queries
-// raycast, raycast_visibility and softshadows (raymarching.glsl:4-56) for n rays of the host's, on the query stream beside the
-// frames in flight (k_ray_query, mdh_kernels.h).  They read the committed scene and edit nothing: no settle_bump, no counter
-// of the replays' keys moves -- the probe-settle run, the radiance replay and the screen replay go on across them (pending
-// edits are committed first, and have made their own marks).
-#define MDH_RAY_WORDS 18 // origin, direction, tmax | hit, index, t (or the visibility / shadow value), steps, position, normal | a swept sphere's radius
-static bool all_finite(const float *v, size_t n)
-{
-   bool ok = true;
-   for (size_t i = 0; i < n; ++i) ok = ok && rs_finite(v[i]); // (mdh_ray_stream.h: the predicate the device-array queries apply per lane)
-   return ok;
-}
-// the checks all three share, before anything is launched; tmax is null for mdh_raycast
-static int ray_query_check(const mdh_renderer *r, int32_t n, const float *org, const float *dir, const float *tmax)
-{
-   if (!r) return seterr(MDH_E_INVALID, "null renderer");
-   if (!org || !dir || n < 0) return seterr(MDH_E_INVALID, "bad argument");
-   if (has_custom_kinds(r)) return seterr(MDH_E_STATE, "ray queries answer scenes of built-in kinds only");
-   if (!all_finite(org, 3 * (size_t)n) || !all_finite(dir, 3 * (size_t)n)) return seterr(MDH_E_INVALID, "a ray is not finite");
-   if (tmax) {
-      bool ok = true;
-      for (int32_t i = 0; i < n; ++i) ok = ok && rs_tmax_valid(tmax[i], r->max_dist);
-      if (!ok) return seterr(MDH_E_INVALID, "a ray's length is not finite or exceeds the scene's max_dist");
+// ------------------------------------------------------------------ the query path
+// What every query of the host's own rays and points shares ("The query path"): the query stream, the staging of
+// host arrays in d_rays, the check of device arrays, and query_enqueue -- the one order in which a query's kernel is tied
+// to the frames, to the caller's stream, to the scene's table and to the timing pair.  A family below is its checks, its
+// args struct's filler and its kernel.
+// d_rays: MDH_RAY_WORDS words a ray, each array at its slot's offset times the buffer's capacity in rays
+#define MDH_RAY_WORDS 18
+constexpr int RAY_SLOT_WORDS[] = {3, 3, 1, 1, 1, 1, 1, 3, 3, 1};
+constexpr int ray_slot(int i) { int at = 0; for (int k = 0; k < i; ++k) at += RAY_SLOT_WORDS[k]; return at; }
+enum RaySlot : int {
+   SLOT_ORG = ray_slot(0), SLOT_DIR = ray_slot(1), SLOT_TMAX = ray_slot(2),                                   // what a ray brings
+   SLOT_HIT = ray_slot(3), SLOT_INDEX = ray_slot(4), SLOT_T = ray_slot(5), SLOT_STEPS = ray_slot(6),          // its answers: t, or the visibility / shadow value
+   SLOT_POS = ray_slot(7), SLOT_NORMAL = ray_slot(8), SLOT_RADIUS = ray_slot(9),                              // ... and a swept sphere's radius
+   SLOT_VIEW = SLOT_TMAX, SLOT_MATERIAL = SLOT_T, // a point's view direction (3 words, over tmax, hit and index: a point has none) and material id
+   SLOT_F = SLOT_TMAX, SLOT_LEN = SLOT_T,         // in-scattering: a point's distance along its ray, a ray's length
+   SLOT_RGB = SLOT_POS,                           // a shaded or traced ray's, a point's colour
+};
+static_assert(SLOT_ORG == 0 && SLOT_DIR == 3 && SLOT_TMAX == 6 && SLOT_HIT == 7 && SLOT_INDEX == 8 && SLOT_T == 9 && SLOT_STEPS == 10 && SLOT_POS == 11 &&
+              SLOT_NORMAL == 14 && SLOT_RADIUS == 17, "the places the kernels' arrays have always had");
+static_assert(ray_slot(sizeof RAY_SLOT_WORDS / sizeof *RAY_SLOT_WORDS) == MDH_RAY_WORDS, "the slots fill a ray's words");
+// n rays' room in d_rays on the query stream.  up and down copy `words` words a ray between a host array and a slot, skip a
+// null array, and yield the slot's place; the first copy that fails is kept in err, and nothing is enqueued behind it.
+struct RayStage {
+   float *base = nullptr;
+   size_t cap = 0, n = 0;
+   hipStream_t qs = nullptr;
+   hipError_t err = hipSuccess;
+   template <class T = float> T *at(int slot) const { return (T *)(base + (size_t)slot * cap); }
+   template <class T> T *up(int slot, const T *host, int words)
+   {
+      if (host && err == hipSuccess) err = hipMemcpyAsync(at(slot), host, n * words * 4, hipMemcpyHostToDevice, qs);
+      return at<T>(slot);
    }
-   return MDH_OK;
-}
-// uploads the rays, launches k_ray_query<.., what> and leaves the query stream's results in d_rays (a: their places)
-static int ray_query_run(mdh_renderer *r, int what, int32_t n, const float *org, const float *dir, const float *tmax, float tmin, float k, bool normals, RayQueryArgs &a)
+   template <class T> T *down(T *host, int slot, int words)
+   {
+      if (host && err == hipSuccess) err = hipMemcpyAsync(host, at(slot), n * words * 4, hipMemcpyDeviceToHost, qs);
+      return at<T>(slot);
+   }
+};
+// the only place that grows d_rays: at least 256 rays; whatever the query stream still does with the old memory is drained
+static int rays_stage(mdh_renderer *r, size_t n, hipStream_t qs, RayStage &st)
 {
-   HIP_TRY(hipSetDevice(r->device));
-   if (!r->query_stream) HIP_TRY(hipStreamCreateWithFlags(&r->query_stream, hipStreamNonBlocking));
-   hipStream_t qs = r->query_stream;
-   int rc = ensure_committed(r, qs);
-   if (rc != MDH_OK) return rc;
-   const size_t want = ((size_t)n < 256 ? 256 : (size_t)n) * MDH_RAY_WORDS;
+   const size_t want = (n < 256 ? 256 : n) * MDH_RAY_WORDS;
    if (want > r->d_rays.cap) {
       if (r->d_rays.ptr) HIP_TRY(hipStreamSynchronize(qs));
       HIP_TRY(r->d_rays.grow(want));
    }
-   const size_t cap = r->d_rays.cap / MDH_RAY_WORDS;
-   float *base = r->d_rays.ptr;
-   float *d_org = base, *d_dir = base + 3 * cap, *d_tmax = base + 6 * cap;
-   a.n = n; a.tmin = tmin; a.k = k;
-   a.org = d_org; a.dir = d_dir; a.tmax = d_tmax;
-   a.hit = (int *)(base + 7 * cap); a.index = (int *)(base + 8 * cap); a.t = base + 9 * cap; a.steps = (int *)(base + 10 * cap);
-   a.pos = base + 11 * cap; a.normal = normals ? base + 14 * cap : nullptr; // (no normal asked for: the kernel leaves primitive_info out)
-   a.out = a.t; a.radius = nullptr;
-   HIP_TRY(hipMemcpyAsync(d_org, org, (size_t)n * 12, hipMemcpyHostToDevice, qs));
-   HIP_TRY(hipMemcpyAsync(d_dir, dir, (size_t)n * 12, hipMemcpyHostToDevice, qs));
-   if (tmax) HIP_TRY(hipMemcpyAsync(d_tmax, tmax, (size_t)n * 4, hipMemcpyHostToDevice, qs));
-   if ((rc = table_acquire(r, qs)) != MDH_OK) return rc;
-   const unsigned blocks = (unsigned)(((size_t)n + MDH_BLOCK - 1) / MDH_BLOCK);
-   const bool timed = r->opt_timing && (r->rq_e0 || (r->rq_e0 = get_event(r))) && (r->rq_e1 || (r->rq_e1 = get_event(r)));
-   if (timed) HIP_TRY(hipEventRecord(r->rq_e0, qs));
-   if ((rc = launch_kernel_ptr(table_kernel(r, GK_k_ray_query, what), dim3(blocks), dim3(MDH_BLOCK), lds_bytes(r), qs, r->ks, a)) != MDH_OK) return rc;
-   HIP_TRY(hipGetLastError());
-   if (timed) HIP_TRY(hipEventRecord(r->rq_e1, qs));
-   r->rq_timed = timed;
-   return table_release(r, qs);
-}
-// the host's wait for a query's results; under MDH_OPT_TIMING the kernel's own time is read off its two events
-static int ray_query_wait(mdh_renderer *r)
-{
-   HIP_TRY(hipStreamSynchronize(r->query_stream));
-   if (r->rq_timed) {
-      float ms = 0.0f;
-      HIP_TRY(hipEventElapsedTime(&ms, r->rq_e0, r->rq_e1));
-      r->rq_ms = ms;
-      r->rq_timed = false;
-   }
+   st.base = r->d_rays.ptr; st.cap = r->d_rays.cap / MDH_RAY_WORDS; st.n = n; st.qs = qs;
    return MDH_OK;
 }
-extern "C" int32_t mdh_ray_query_time(mdh_renderer *r, double *kernel_ms)
+// a host form's first steps behind its last refusal: the query stream, the committed scene, room for its n rays
+static int host_query_begin(mdh_renderer *r, int32_t n, RayStage &st)
 {
-   if (!r || !kernel_ms) return seterr(MDH_E_INVALID, "bad argument");
-   if (r->rq_timed) { // a device query nobody has waited for yet: for its end event, not for the stream
-      float ms = 0.0f;
-      HIP_TRY(hipSetDevice(r->device));
-      HIP_TRY(hipEventSynchronize(r->rq_e1));
-      HIP_TRY(hipEventElapsedTime(&ms, r->rq_e0, r->rq_e1));
-      r->rq_ms = ms;
-      r->rq_timed = false;
-   }
-   *kernel_ms = r->rq_ms;
-   return MDH_OK;
+   hipStream_t qs = nullptr;
+   int rc = query_stream_get(r, &qs);
+   if (rc != MDH_OK || (rc = ensure_committed(r, qs)) != MDH_OK) return rc;
+   return rays_stage(r, (size_t)n, qs, st);
 }
-extern "C" int32_t mdh_raycast(mdh_renderer *r, int32_t n, const float *org, const float *dir, int32_t *hit_out, int32_t *index_out,
-                               float *t_out, int32_t *steps_out, float *pos_out, float *normal_out)
+// a device form's, behind ray_arrays_check
+static int device_query_begin(mdh_renderer *r, hipStream_t *qs)
 {
-   int rc = ray_query_check(r, n, org, dir, nullptr);
-   if (rc != MDH_OK) return rc;
-   if (!hit_out) return seterr(MDH_E_INVALID, "bad argument");
-   if (n == 0) return MDH_OK;
-   RayQueryArgs a;
-   if ((rc = ray_query_run(r, MDH_RQ_RAYCAST, n, org, dir, nullptr, 0.0f, 0.0f, normal_out != nullptr, a)) != MDH_OK) return rc;
-   hipStream_t qs = r->query_stream;
-   HIP_TRY(hipMemcpyAsync(hit_out, a.hit, (size_t)n * 4, hipMemcpyDeviceToHost, qs));
-   if (index_out) HIP_TRY(hipMemcpyAsync(index_out, a.index, (size_t)n * 4, hipMemcpyDeviceToHost, qs));
-   if (t_out) HIP_TRY(hipMemcpyAsync(t_out, a.t, (size_t)n * 4, hipMemcpyDeviceToHost, qs));
-   if (steps_out) HIP_TRY(hipMemcpyAsync(steps_out, a.steps, (size_t)n * 4, hipMemcpyDeviceToHost, qs));
-   if (pos_out) HIP_TRY(hipMemcpyAsync(pos_out, a.pos, (size_t)n * 12, hipMemcpyDeviceToHost, qs));
-   if (normal_out) HIP_TRY(hipMemcpyAsync(normal_out, a.normal, (size_t)n * 12, hipMemcpyDeviceToHost, qs));
-   return ray_query_wait(r);
-}
-extern "C" int32_t mdh_raycast_visibility(mdh_renderer *r, int32_t n, const float *org, const float *dir, const float *tmax, float *vis_out)
-{
-   if (r && (!tmax || !vis_out)) return seterr(MDH_E_INVALID, "bad argument");
-   int rc = ray_query_check(r, n, org, dir, tmax);
-   if (rc != MDH_OK) return rc;
-   if (n == 0) return MDH_OK;
-   RayQueryArgs a;
-   if ((rc = ray_query_run(r, MDH_RQ_VISIBILITY, n, org, dir, tmax, 0.0f, 0.0f, false, a)) != MDH_OK) return rc;
-   HIP_TRY(hipMemcpyAsync(vis_out, a.out, (size_t)n * 4, hipMemcpyDeviceToHost, r->query_stream));
-   return ray_query_wait(r);
-}
-extern "C" int32_t mdh_softshadows(mdh_renderer *r, int32_t n, const float *org, const float *dir, float tmin, const float *tmax, float k, float *out)
-{
-   if (r && (!tmax || !out)) return seterr(MDH_E_INVALID, "bad argument");
-   if (r && (!std::isfinite(tmin) || !std::isfinite(k) || tmin < 0.0f)) return seterr(MDH_E_INVALID, "min_dist is negative, or min_dist or k is not finite");
-   int rc = ray_query_check(r, n, org, dir, tmax);
-   if (rc != MDH_OK) return rc;
-   if (n == 0) return MDH_OK;
-   RayQueryArgs a;
-   if ((rc = ray_query_run(r, MDH_RQ_SOFTSHADOW, n, org, dir, tmax, tmin, k, false, a)) != MDH_OK) return rc;
-   HIP_TRY(hipMemcpyAsync(out, a.out, (size_t)n * 4, hipMemcpyDeviceToHost, r->query_stream));
-   return ray_query_wait(r);
+   const int rc = query_stream_get(r, qs, true);
+   return rc != MDH_OK ? rc : ensure_committed(r, *qs);
 }
 
-// ------------------------------------------------------------------ ray queries on device arrays
-// mdh_raycast_device, mdh_raycast_visibility_device, mdh_softshadows_device: the same three queries for arrays the device
-// addresses, asynchronous and ordered with a stream of the caller's.  The kernel (k_ray_stream, mdh_kernels.h) still runs
-// on the query stream, so that the scene's commit and the table's fences are used as they are; two events bridge: the query
-// stream waits for what the caller's stream holds at the call, the caller's stream waits for the kernel.  Nothing is
-// copied and the host waits for nothing.  The rays are validated by the lanes that take them; what the host can check --
-// and must, a pointer the device cannot address is a fault inside the kernel -- is where the arrays live.
+// Arrays the device addresses: nothing is copied, and the rays are validated by the lanes that take them.  What the host can
+// check -- and must, a pointer the device cannot address is a fault inside the kernel -- is where the arrays live.
 struct RayArray { const void *p; size_t bytes; const char *what; };
 // is [p, p + bytes) memory this renderer's device addresses?  Memory of the device itself, page-locked host memory or
 // managed memory, as hipPointerGetAttributes knows it; pageable host memory is unregistered (or, to older runtimes, an
@@ -3718,79 +3653,274 @@ static long resident_groups(mdh_renderer *r, const void *kernel, size_t lds)
    }
    return (long)it->second * r->n_cus;
 }
-// checks everything, then enqueues k_ray_stream<.., what> between the two events; `arrays`: every array of the call
-static int ray_stream_run(mdh_renderer *r, int what, int32_t n, const RayArray *arrays, int n_arrays, RayQueryArgs &a, hipStream_t stream)
+// every array of a device form (the device is made current for the look)
+template <size_t N> static int ray_arrays_check(const mdh_renderer *r, const RayArray (&arrays)[N])
 {
-   if (has_custom_kinds(r)) return seterr(MDH_E_STATE, "ray queries answer scenes of built-in kinds only");
    HIP_TRY(hipSetDevice(r->device));
-   for (int i = 0; i < n_arrays; ++i) {
-      const int rc = ray_array_check(r, arrays[i]);
+   for (const RayArray &ra : arrays) {
+      const int rc = ray_array_check(r, ra);
       if (rc != MDH_OK) return rc;
    }
-   if (n == 0) return MDH_OK;
-   if (!r->query_stream) HIP_TRY(hipStreamCreateWithFlags(&r->query_stream, hipStreamNonBlocking));
-   hipStream_t qs = r->query_stream;
-   HIP_TRY(create_all(r->d_rq_next.sized(1), r->ev_rq_in, r->ev_rq_out)); // (one group, created by the first device query)
-   int rc = ensure_committed(r, qs);
-   if (rc != MDH_OK) return rc;
-   const void *kernel = table_kernel(r, GK_k_ray_stream, what);
-   const size_t lds = lds_bytes(r);
+   return MDH_OK;
+}
+// the workgroups of a streamed query of n rays: no more than are resident, or than MDH_OPT_RAY_STREAM_GROUPS allows
+static unsigned stream_groups(mdh_renderer *r, const void *kernel, size_t lds, int32_t n)
+{
    long groups = ((long)n + MDH_BLOCK - 1) / MDH_BLOCK;
    if (kernel) { // (none: launch_kernel_ptr says so)
       const long resident = resident_groups(r, kernel, lds);
       if (resident > 0 && groups > resident) groups = resident;
    }
    if (r->opt_rq_groups > 0 && groups > r->opt_rq_groups) groups = r->opt_rq_groups;
-   RayStreamArgs sa;
-   sa.q = a;
-   sa.next = r->d_rq_next.ptr;
-   sa.refill = r->opt_rq_refill;
-   if (stream != qs) { // the rays are what the caller's stream has made of them at this call
-      HIP_TRY(hipEventRecord(r->ev_rq_in.ev, stream));
-      HIP_TRY(hipStreamWaitEvent(qs, r->ev_rq_in.ev, 0));
+   return (unsigned)groups;
+}
+// One query on the query stream qs.  `framed`: it reads what the frames write (an atlas set) or keeps a place among them, so
+// it is tied to the main stream as a screen pass is by running there -- join_main, qs behind the main stream, and behind the
+// kernel the main stream behind qs with main_dirty set, so that the next frame orders its probe, volumetric and alternate
+// streams behind the query before any of them rewrites a set.  `caller`: the stream device arrays are ordered with, or qs
+// itself (host arrays: the copies around this call are on qs).  `launch` enqueues the kernel, and nothing else: under
+// MDH_OPT_TIMING the pair rq_e0 / rq_e1 around it is what mdh_ray_query_time reports.
+template <typename Launch> static int query_enqueue(mdh_renderer *r, hipStream_t qs, hipStream_t caller, bool framed, Launch launch)
+{
+   int rc;
+   if (framed) {
+      if ((rc = join_main(r)) != MDH_OK) return rc;
+      r->main_dirty = true;
    }
-   HIP_TRY(hipMemsetAsync(r->d_rq_next.ptr, 0, sizeof(unsigned), qs));
+   const hipStream_t *main = framed ? &r->stream : nullptr;
+   if (main || caller != qs) HIP_TRY(r->bridge.create());
+   HIP_TRY(r->bridge.enter(qs, caller, main));
    if ((rc = table_acquire(r, qs)) != MDH_OK) return rc;
    const bool timed = r->opt_timing && (r->rq_e0 || (r->rq_e0 = get_event(r))) && (r->rq_e1 || (r->rq_e1 = get_event(r)));
    if (timed) HIP_TRY(hipEventRecord(r->rq_e0, qs));
-   if ((rc = launch_kernel_ptr(kernel, dim3((unsigned)groups), dim3(MDH_BLOCK), lds, qs, r->ks, sa)) != MDH_OK) return rc;
+   if ((rc = launch()) != MDH_OK) return rc;
    HIP_TRY(hipGetLastError());
    if (timed) HIP_TRY(hipEventRecord(r->rq_e1, qs));
-   r->rq_timed = timed; // (pending: mdh_ray_query_wait or mdh_ray_query_time reads the pair)
+   r->rq_timed = timed; // (pending for a device form: mdh_ray_query_wait or mdh_ray_query_time reads the pair)
    if ((rc = table_release(r, qs)) != MDH_OK) return rc;
-   if (stream != qs) { // ... and the answers are there for whatever the caller's stream is given next
-      HIP_TRY(hipEventRecord(r->ev_rq_out.ev, qs));
-      HIP_TRY(hipStreamWaitEvent(stream, r->ev_rq_out.ev, 0));
+   HIP_TRY(r->bridge.leave(qs, caller, main));
+   return MDH_OK;
+}
+// ... of a kernel that takes the scene and `a`, a lane per ray; a variant nobody built is refused before anything is enqueued
+template <typename... A> static int query_kernel(mdh_renderer *r, const void *kernel, unsigned blocks, size_t lds, hipStream_t qs, hipStream_t caller, bool framed, A... a)
+{
+   if (!kernel) return seterr(MDH_E_INVALID, "no kernel built for this variant");
+   return query_enqueue(r, qs, caller, framed, [&] { return launch_kernel_ptr(kernel, dim3(blocks), dim3(MDH_BLOCK), lds, qs, r->ks, a...); });
+}
+static unsigned lane_blocks(int32_t n) { return (unsigned)(((size_t)n + MDH_BLOCK - 1) / MDH_BLOCK); }
+// the scene's half of the bound that stands in for a stall guard (mdh_ray_stream.h: rs_shade_ray_valid has the ray's), for
+// `who` ("shaded rays", "traced paths"); `probes`: the query reads the probe grid
+static int scene_extent_check(const mdh_renderer *r, const char *who, bool probes)
+{
+   const char *what = nullptr;
+   if (!rs_shade_extent_valid(r->max_dist)) what = "a max_dist of at most 1024";
+   for (int k = 0; k < r->nlk && !what; ++k) {
+      const Kind &kd = r->lk[k];
+      int n = rd_i(r, kd.count_off);
+      if (n > kd.max_count) n = kd.max_count;
+      for (int i = 0; i < n; ++i)
+         for (int c = 0; c < 3; ++c)
+            if (!rs_shade_extent_valid(rd_f(r, kd.array_off + kd.stride * i + kd.f_a + 4 * c))) what = "every light within 1024 of the origin along every axis";
+   }
+   for (int c = 0; c < 3 && probes && !what; ++c)
+      if (!rs_shade_extent_valid((float)(r->probes.grid_dimensions[c] - 1) * r->probes.grid_spacing[c])) what = "the probe grid's far corner within 1024 of the origin along every axis";
+   if (!what) return MDH_OK;
+   snprintf(g_err, sizeof g_err, "%s need %s", who, what);
+   return MDH_E_STATE;
+}
+static int shade_scene_check(const mdh_renderer *r) { return scene_extent_check(r, "shaded rays", true); } // (rays and points alike)
+
+// the host's wait for a query's results; under MDH_OPT_TIMING the kernel's own time is read off its two events
+static int ray_query_wait(mdh_renderer *r)
+{
+   HIP_TRY(hipStreamSynchronize(r->query_stream));
+   if (r->rq_timed) {
+      float ms = 0.0f;
+      HIP_TRY(hipEventElapsedTime(&ms, r->rq_e0, r->rq_e1));
+      r->rq_ms = ms;
+      r->rq_timed = false;
    }
    return MDH_OK;
+}
+extern "C" int32_t mdh_ray_query_time(mdh_renderer *r, double *kernel_ms)
+{
+   if (!r || !kernel_ms) return seterr(MDH_E_INVALID, "bad argument");
+   if (r->rq_timed) { // a device query nobody has waited for yet: for its end event, not for the stream
+      float ms = 0.0f;
+      HIP_TRY(hipSetDevice(r->device));
+      HIP_TRY(hipEventSynchronize(r->rq_e1));
+      HIP_TRY(hipEventElapsedTime(&ms, r->rq_e0, r->rq_e1));
+      r->rq_ms = ms;
+      r->rq_timed = false;
+   }
+   *kernel_ms = r->rq_ms;
+   return MDH_OK;
+}
+// the host's wait for every device query enqueued so far (callers that order their own stream need none)
+extern "C" int32_t mdh_ray_query_wait(mdh_renderer *r)
+{
+   if (!r) return seterr(MDH_E_INVALID, "null renderer");
+   if (!r->query_stream) return MDH_OK; // (no query yet)
+   HIP_TRY(hipSetDevice(r->device));
+   return ray_query_wait(r);
+}
+
+// ------------------------------------------------------------------ ray queries
+// raycast, raycast_visibility and softshadows (raymarching.glsl:4-56) for n rays of the host's, on the query stream beside the
+// frames in flight (k_ray_query, mdh_kernels.h).  They read the committed scene and edit nothing: no settle_bump, no counter
+// of the replays' keys moves -- the probe-settle run, the radiance replay and the screen replay go on across them (pending
+// edits are committed first, and have made their own marks).
+static bool all_finite(const float *v, size_t n)
+{
+   bool ok = true;
+   for (size_t i = 0; i < n; ++i) ok = ok && rs_finite(v[i]); // (mdh_ray_stream.h: the predicate the device-array queries apply per lane)
+   return ok;
+}
+// the checks all three share, before anything is launched; tmax is null for mdh_raycast
+static int ray_query_check(const mdh_renderer *r, int32_t n, const float *org, const float *dir, const float *tmax)
+{
+   if (!r) return seterr(MDH_E_INVALID, "null renderer");
+   if (!org || !dir || n < 0) return seterr(MDH_E_INVALID, "bad argument");
+   if (has_custom_kinds(r)) return seterr(MDH_E_STATE, "ray queries answer scenes of built-in kinds only");
+   if (!all_finite(org, 3 * (size_t)n) || !all_finite(dir, 3 * (size_t)n)) return seterr(MDH_E_INVALID, "a ray is not finite");
+   if (tmax) {
+      bool ok = true;
+      for (int32_t i = 0; i < n; ++i) ok = ok && rs_tmax_valid(tmax[i], r->max_dist);
+      if (!ok) return seterr(MDH_E_INVALID, "a ray's length is not finite or exceeds the scene's max_dist");
+   }
+   return MDH_OK;
+}
+// the family's args: the queries here, the device-array forms and the sweeps below all fill them in this one place
+static RayQueryArgs ray_query_args(int32_t n, float tmin, float k, const float *org, const float *dir, const float *tmax, const float *radius, int *hit, int *index,
+                                   float *t, int *steps, float *pos, float *normal, float *out)
+{
+   RayQueryArgs a;
+   a.n = n; a.tmin = tmin; a.k = k;
+   a.org = org; a.dir = dir; a.tmax = tmax; a.radius = radius;
+   a.hit = hit; a.index = index; a.steps = steps;
+   a.t = t; a.pos = pos; a.normal = normal;
+   a.out = out;
+   return a;
+}
+// ... with the answers' places in d_rays (no normal asked for: the kernel leaves primitive_info out)
+static RayQueryArgs ray_query_staged(const RayStage &st, float tmin, float k, const float *org, const float *dir, const float *tmax, const float *radius, bool normals, float *out)
+{
+   return ray_query_args((int32_t)st.n, tmin, k, org, dir, tmax, radius, st.at<int>(SLOT_HIT), st.at<int>(SLOT_INDEX), st.at(SLOT_T), st.at<int>(SLOT_STEPS),
+                         st.at(SLOT_POS), normals ? st.at(SLOT_NORMAL) : nullptr, out);
+}
+// a raycast's or a sweep's answers, from d_rays to the arrays the host asked for
+static void ray_query_down(RayStage &st, int32_t *hit_out, int32_t *index_out, float *t_out, int32_t *steps_out, float *pos_out, float *normal_out)
+{
+   st.down(hit_out, SLOT_HIT, 1); st.down(index_out, SLOT_INDEX, 1); st.down(t_out, SLOT_T, 1); st.down(steps_out, SLOT_STEPS, 1);
+   st.down(pos_out, SLOT_POS, 3); st.down(normal_out, SLOT_NORMAL, 3);
+}
+// enqueues the family's kernel for `a`: k_listed<.., what> (n_kinds > 0: the exact minimum over the kinds listed), k_ray_stream
+// <.., what> (`streamed`: device arrays, lanes refilled as rays end) or k_ray_query<.., what>
+static int ray_query_enqueue(mdh_renderer *r, int what, const RayQueryArgs &a, const int32_t *kind_ixs, int32_t n_kinds, bool streamed, hipStream_t qs, hipStream_t caller)
+{
+   const size_t lds = lds_bytes(r);
+   const dim3 block(MDH_BLOCK);
+   if (n_kinds > 0) {
+      ListedArgs la;
+      la.q = a; la.n_kinds = n_kinds;
+      for (int i = 0; i < MDH_MAX_KINDS; ++i) { la.kinds[i] = i < n_kinds ? kind_ixs[i] : 0; la.host_count[i] = r->host_count[i]; }
+      const void *kernel = table_kernel(r, GK_k_listed, what);
+      return query_enqueue(r, qs, caller, false, [&] { return launch_kernel_ptr(kernel, dim3(lane_blocks(a.n)), block, lds, qs, r->ks, la); });
+   }
+   if (streamed) {
+      const void *kernel = table_kernel(r, GK_k_ray_stream, what);
+      const unsigned groups = stream_groups(r, kernel, lds, a.n);
+      HIP_TRY(r->d_rq_next.grow(1)); // (created by the first streamed query)
+      RayStreamArgs sa;
+      sa.q = a; sa.next = r->d_rq_next.ptr; sa.refill = r->opt_rq_refill;
+      HIP_TRY(hipMemsetAsync(r->d_rq_next.ptr, 0, sizeof(unsigned), qs));
+      return query_enqueue(r, qs, caller, false, [&] { return launch_kernel_ptr(kernel, dim3(groups), block, lds, qs, r->ks, sa); });
+   }
+   const void *kernel = table_kernel(r, GK_k_ray_query, what);
+   return query_enqueue(r, qs, caller, false, [&] { return launch_kernel_ptr(kernel, dim3(lane_blocks(a.n)), block, lds, qs, r->ks, a); });
+}
+// host arrays: uploads the rays, launches k_ray_query<.., what> and leaves the results in d_rays (a.out: beside t)
+static int ray_query_run(mdh_renderer *r, int what, int32_t n, const float *org, const float *dir, const float *tmax, float tmin, float k, bool normals, RayStage &st)
+{
+   const int rc = host_query_begin(r, n, st);
+   if (rc != MDH_OK) return rc;
+   const float *d_org = st.up(SLOT_ORG, org, 3), *d_dir = st.up(SLOT_DIR, dir, 3), *d_tmax = st.up(SLOT_TMAX, tmax, 1);
+   HIP_TRY(st.err);
+   return ray_query_enqueue(r, what, ray_query_staged(st, tmin, k, d_org, d_dir, d_tmax, nullptr, normals, st.at(SLOT_T)), nullptr, 0, false, st.qs, st.qs);
+}
+// a scalar per ray (the visibility, the shadow value) back to the host
+static int32_t ray_query_scalar(mdh_renderer *r, int what, int32_t n, const float *org, const float *dir, const float *tmax, float tmin, float k, float *out)
+{
+   RayStage st;
+   const int rc = ray_query_run(r, what, n, org, dir, tmax, tmin, k, false, st);
+   if (rc != MDH_OK) return rc;
+   st.down(out, SLOT_T, 1);
+   HIP_TRY(st.err);
+   return ray_query_wait(r);
+}
+extern "C" int32_t mdh_raycast(mdh_renderer *r, int32_t n, const float *org, const float *dir, int32_t *hit_out, int32_t *index_out,
+                               float *t_out, int32_t *steps_out, float *pos_out, float *normal_out)
+{
+   int rc = ray_query_check(r, n, org, dir, nullptr);
+   if (rc != MDH_OK) return rc;
+   if (!hit_out) return seterr(MDH_E_INVALID, "bad argument");
+   if (n == 0) return MDH_OK;
+   RayStage st;
+   if ((rc = ray_query_run(r, MDH_RQ_RAYCAST, n, org, dir, nullptr, 0.0f, 0.0f, normal_out != nullptr, st)) != MDH_OK) return rc;
+   ray_query_down(st, hit_out, index_out, t_out, steps_out, pos_out, normal_out);
+   HIP_TRY(st.err);
+   return ray_query_wait(r);
+}
+extern "C" int32_t mdh_raycast_visibility(mdh_renderer *r, int32_t n, const float *org, const float *dir, const float *tmax, float *vis_out)
+{
+   if (r && (!tmax || !vis_out)) return seterr(MDH_E_INVALID, "bad argument");
+   const int rc = ray_query_check(r, n, org, dir, tmax);
+   if (rc != MDH_OK || n == 0) return rc;
+   return ray_query_scalar(r, MDH_RQ_VISIBILITY, n, org, dir, tmax, 0.0f, 0.0f, vis_out);
+}
+extern "C" int32_t mdh_softshadows(mdh_renderer *r, int32_t n, const float *org, const float *dir, float tmin, const float *tmax, float k, float *out)
+{
+   if (r && (!tmax || !out)) return seterr(MDH_E_INVALID, "bad argument");
+   if (r && (!std::isfinite(tmin) || !std::isfinite(k) || tmin < 0.0f)) return seterr(MDH_E_INVALID, "min_dist is negative, or min_dist or k is not finite");
+   const int rc = ray_query_check(r, n, org, dir, tmax);
+   if (rc != MDH_OK || n == 0) return rc;
+   return ray_query_scalar(r, MDH_RQ_SOFTSHADOW, n, org, dir, tmax, tmin, k, out);
+}
+
+// ------------------------------------------------------------------ ray queries on device arrays
+// mdh_raycast_device, mdh_raycast_visibility_device, mdh_softshadows_device: the same three queries for arrays the device
+// addresses, asynchronous and ordered with a stream of the caller's.  The kernel (k_ray_stream, mdh_kernels.h) still runs
+// on the query stream, so that the scene's commit and the table's fences are used as they are; the bridge's events order it
+// with the caller's stream (query_enqueue).  Nothing is copied and the host waits for nothing.
+// where the arrays live, then the family's kernel between the caller's stream's events; `arrays`: every array of the call
+template <size_t N>
+static int ray_query_device(mdh_renderer *r, int what, const RayArray (&arrays)[N], const RayQueryArgs &a, const int32_t *kind_ixs, int32_t n_kinds, bool streamed, void *stream)
+{
+   int rc = ray_arrays_check(r, arrays);
+   if (rc != MDH_OK || a.n == 0) return rc;
+   hipStream_t qs = nullptr;
+   if ((rc = device_query_begin(r, &qs)) != MDH_OK) return rc;
+   return ray_query_enqueue(r, what, a, kind_ixs, n_kinds, streamed, qs, (hipStream_t)stream);
 }
 extern "C" int32_t mdh_raycast_device(mdh_renderer *r, int32_t n, const float *org, const float *dir, int32_t *hit_out, int32_t *index_out,
                                       float *t_out, int32_t *steps_out, float *pos_out, float *normal_out, void *stream)
 {
    if (!r) return seterr(MDH_E_INVALID, "null renderer");
    if (!org || !dir || !hit_out || n < 0) return seterr(MDH_E_INVALID, "bad argument");
+   if (has_custom_kinds(r)) return seterr(MDH_E_STATE, "ray queries answer scenes of built-in kinds only");
    const size_t w = (size_t)n * 4;
    const RayArray arrays[] = {{org, 3 * w, "origins"}, {dir, 3 * w, "directions"}, {hit_out, w, "hit"}, {index_out, w, "index"}, {t_out, w, "t"},
                               {steps_out, w, "steps"}, {pos_out, 3 * w, "positions"}, {normal_out, 3 * w, "normals"}};
-   RayQueryArgs a;
-   a.n = n; a.tmin = 0.0f; a.k = 0.0f;
-   a.org = org; a.dir = dir; a.tmax = nullptr;
-   a.hit = hit_out; a.index = index_out; a.steps = steps_out;
-   a.t = t_out; a.pos = pos_out; a.normal = normal_out;
-   a.out = nullptr; a.radius = nullptr;
-   return ray_stream_run(r, MDH_RQ_RAYCAST, n, arrays, 8, a, (hipStream_t)stream);
+   const RayQueryArgs a = ray_query_args(n, 0.0f, 0.0f, org, dir, nullptr, nullptr, hit_out, index_out, t_out, steps_out, pos_out, normal_out, nullptr);
+   return ray_query_device(r, MDH_RQ_RAYCAST, arrays, a, nullptr, 0, true, stream);
 }
 static int32_t ray_stream_scalar(mdh_renderer *r, int what, int32_t n, const float *org, const float *dir, float tmin, const float *tmax, float k, float *out, void *stream)
 {
+   if (has_custom_kinds(r)) return seterr(MDH_E_STATE, "ray queries answer scenes of built-in kinds only");
    const size_t w = (size_t)n * 4;
    const RayArray arrays[] = {{org, 3 * w, "origins"}, {dir, 3 * w, "directions"}, {tmax, w, "tmax"}, {out, w, "results"}};
-   RayQueryArgs a;
-   a.n = n; a.tmin = tmin; a.k = k;
-   a.org = org; a.dir = dir; a.tmax = tmax;
-   a.hit = a.index = a.steps = nullptr;
-   a.t = a.pos = a.normal = nullptr;
-   a.out = out; a.radius = nullptr;
-   return ray_stream_run(r, what, n, arrays, 4, a, (hipStream_t)stream);
+   const RayQueryArgs a = ray_query_args(n, tmin, k, org, dir, tmax, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, out);
+   return ray_query_device(r, what, arrays, a, nullptr, 0, true, stream);
 }
 extern "C" int32_t mdh_raycast_visibility_device(mdh_renderer *r, int32_t n, const float *org, const float *dir, const float *tmax, float *vis_out, void *stream)
 {
@@ -3805,21 +3935,13 @@ extern "C" int32_t mdh_softshadows_device(mdh_renderer *r, int32_t n, const floa
    if (!std::isfinite(tmin) || !std::isfinite(k) || tmin < 0.0f) return seterr(MDH_E_INVALID, "min_dist is negative, or min_dist or k is not finite");
    return ray_stream_scalar(r, MDH_RQ_SOFTSHADOW, n, org, dir, tmin, tmax, k, out, stream);
 }
-// the host's wait for every device query enqueued so far (callers that order their own stream need none)
-extern "C" int32_t mdh_ray_query_wait(mdh_renderer *r)
-{
-   if (!r) return seterr(MDH_E_INVALID, "null renderer");
-   if (!r->query_stream) return MDH_OK; // (no query yet)
-   HIP_TRY(hipSetDevice(r->device));
-   return ray_query_wait(r);
-}
 
 // ------------------------------------------------------------------ sweeping a host's spheres
 // mdh_spherecast, mdh_contacts and their _device forms: a sphere swept along each ray to its first contact, and one evaluation
 // at each centre, against the scene as every pass sees it (n_kinds = 0: k_ray_query / k_ray_stream with MDH_RQ_SPHERECAST,
 // k_ray_query with MDH_RQ_CONTACT) or against the exact minimum over the kinds listed (k_listed, mdh_kernels.h).  The contract
-// is the ray queries': the query stream, pending edits seen, nothing edited and no settle_bump, d_rays for host arrays,
-// ray_array_check and the two events for device arrays.  MDH_OPT_ADA_EVAL_DIV is not consulted: a march needs a distance.
+// is the ray queries', through the query path: pending edits seen, nothing edited and no settle_bump.  MDH_OPT_ADA_EVAL_DIV
+// is not consulted: a march needs a distance.
 static int sweep_kinds_check(const mdh_renderer *r, const int32_t *kind_ixs, int32_t n_kinds)
 {
    if (n_kinds < 0 || n_kinds > MDH_MAX_KINDS || (n_kinds > 0 && !kind_ixs)) return seterr(MDH_E_INVALID, "bad argument");
@@ -3838,199 +3960,79 @@ static int sweep_host_check(const mdh_renderer *r, int32_t n, const float *org, 
    if (!ok) return seterr(MDH_E_INVALID, "a ray's length is not finite, negative or exceeds the scene's max_dist");
    return MDH_OK;
 }
-// enqueues the call's kernel on the query stream between the timing events: k_ray_query<.., what> (host arrays, and contacts
-// wherever they live), k_ray_stream<.., MDH_RQ_SPHERECAST> (device arrays: `streamed`) or k_listed<.., what> (n_kinds > 0)
-static int sweep_launch(mdh_renderer *r, int what, const RayQueryArgs &a, const int32_t *kind_ixs, int32_t n_kinds, bool streamed, hipStream_t qs)
-{
-   int rc = table_acquire(r, qs);
-   if (rc != MDH_OK) return rc;
-   const bool timed = r->opt_timing && (r->rq_e0 || (r->rq_e0 = get_event(r))) && (r->rq_e1 || (r->rq_e1 = get_event(r)));
-   const size_t lds = lds_bytes(r);
-   long groups = ((long)a.n + MDH_BLOCK - 1) / MDH_BLOCK;
-   if (n_kinds > 0) {
-      ListedArgs la;
-      la.q = a; la.n_kinds = n_kinds;
-      for (int i = 0; i < MDH_MAX_KINDS; ++i) { la.kinds[i] = i < n_kinds ? kind_ixs[i] : 0; la.host_count[i] = r->host_count[i]; }
-      if (timed) HIP_TRY(hipEventRecord(r->rq_e0, qs));
-      if ((rc = launch_kernel_ptr(table_kernel(r, GK_k_listed, what), dim3((unsigned)groups), dim3(MDH_BLOCK), lds, qs, r->ks, la)) != MDH_OK) return rc;
-   } else if (streamed) {
-      const void *kernel = table_kernel(r, GK_k_ray_stream, what);
-      if (kernel) { // (none: launch_kernel_ptr says so)
-         const long resident = resident_groups(r, kernel, lds);
-         if (resident > 0 && groups > resident) groups = resident;
-      }
-      if (r->opt_rq_groups > 0 && groups > r->opt_rq_groups) groups = r->opt_rq_groups;
-      RayStreamArgs sa;
-      sa.q = a; sa.next = r->d_rq_next.ptr; sa.refill = r->opt_rq_refill;
-      HIP_TRY(hipMemsetAsync(r->d_rq_next.ptr, 0, sizeof(unsigned), qs));
-      if (timed) HIP_TRY(hipEventRecord(r->rq_e0, qs));
-      if ((rc = launch_kernel_ptr(kernel, dim3((unsigned)groups), dim3(MDH_BLOCK), lds, qs, r->ks, sa)) != MDH_OK) return rc;
-   } else {
-      if (timed) HIP_TRY(hipEventRecord(r->rq_e0, qs));
-      if ((rc = launch_kernel_ptr(table_kernel(r, GK_k_ray_query, what), dim3((unsigned)groups), dim3(MDH_BLOCK), lds, qs, r->ks, a)) != MDH_OK) return rc;
-   }
-   HIP_TRY(hipGetLastError());
-   if (timed) HIP_TRY(hipEventRecord(r->rq_e1, qs));
-   r->rq_timed = timed; // (pending for a device query: mdh_ray_query_wait or mdh_ray_query_time reads the pair)
-   return table_release(r, qs);
-}
-// host arrays: uploads what the call brings into d_rays, launches, and leaves the results there (a: their places)
+// host arrays: uploads what the call brings into d_rays (dir and tmax: null for contacts), launches, and leaves the results there
 static int sweep_host_run(mdh_renderer *r, int what, int32_t n, const float *org, const float *dir, const float *radius, const float *tmax,
-                          const int32_t *kind_ixs, int32_t n_kinds, bool normals, RayQueryArgs &a)
+                          const int32_t *kind_ixs, int32_t n_kinds, bool normals, RayStage &st)
 {
-   HIP_TRY(hipSetDevice(r->device));
-   if (!r->query_stream) HIP_TRY(hipStreamCreateWithFlags(&r->query_stream, hipStreamNonBlocking));
-   hipStream_t qs = r->query_stream;
-   int rc = ensure_committed(r, qs);
+   const int rc = host_query_begin(r, n, st);
    if (rc != MDH_OK) return rc;
-   const size_t want = ((size_t)n < 256 ? 256 : (size_t)n) * MDH_RAY_WORDS;
-   if (want > r->d_rays.cap) {
-      if (r->d_rays.ptr) HIP_TRY(hipStreamSynchronize(qs));
-      HIP_TRY(r->d_rays.grow(want));
-   }
-   const size_t cap = r->d_rays.cap / MDH_RAY_WORDS;
-   float *base = r->d_rays.ptr;
-   float *d_org = base, *d_dir = base + 3 * cap, *d_tmax = base + 6 * cap, *d_radius = base + 17 * cap;
-   a.n = n; a.tmin = 0.0f; a.k = 0.0f;
-   a.org = d_org; a.dir = dir ? d_dir : nullptr; a.tmax = tmax ? d_tmax : nullptr; a.radius = radius ? d_radius : nullptr;
-   a.hit = (int *)(base + 7 * cap); a.index = (int *)(base + 8 * cap); a.t = base + 9 * cap; a.steps = (int *)(base + 10 * cap);
-   a.pos = base + 11 * cap; a.normal = normals ? base + 14 * cap : nullptr; // (no normal asked for: the kernel leaves primitive_info out)
-   a.out = nullptr;
-   HIP_TRY(hipMemcpyAsync(d_org, org, (size_t)n * 12, hipMemcpyHostToDevice, qs));
-   if (dir) HIP_TRY(hipMemcpyAsync(d_dir, dir, (size_t)n * 12, hipMemcpyHostToDevice, qs));
-   if (tmax) HIP_TRY(hipMemcpyAsync(d_tmax, tmax, (size_t)n * 4, hipMemcpyHostToDevice, qs));
-   if (radius) HIP_TRY(hipMemcpyAsync(d_radius, radius, (size_t)n * 4, hipMemcpyHostToDevice, qs));
-   return sweep_launch(r, what, a, kind_ixs, n_kinds, false, qs);
+   const float *d_org = st.up(SLOT_ORG, org, 3), *d_dir = st.up(SLOT_DIR, dir, 3), *d_tmax = st.up(SLOT_TMAX, tmax, 1), *d_radius = st.up(SLOT_RADIUS, radius, 1);
+   HIP_TRY(st.err);
+   const RayQueryArgs a = ray_query_staged(st, 0.0f, 0.0f, d_org, dir ? d_dir : nullptr, tmax ? d_tmax : nullptr, radius ? d_radius : nullptr, normals, nullptr);
+   return ray_query_enqueue(r, what, a, kind_ixs, n_kinds, false, st.qs, st.qs);
 }
-// device arrays: checks where they live, then enqueues the kernel between the two events that order it with `stream`
-static int sweep_device_run(mdh_renderer *r, int what, const RayArray *arrays, int n_arrays, const RayQueryArgs &a, const int32_t *kind_ixs, int32_t n_kinds, hipStream_t stream)
+// what all four refuse before they look at their arrays
+static int sweep_check(const mdh_renderer *r, int32_t n, bool arrays, const int32_t *kind_ixs, int32_t n_kinds)
 {
-   HIP_TRY(hipSetDevice(r->device));
-   for (int i = 0; i < n_arrays; ++i) {
-      const int rc = ray_array_check(r, arrays[i]);
-      if (rc != MDH_OK) return rc;
-   }
-   if (a.n == 0) return MDH_OK;
-   if (!r->query_stream) HIP_TRY(hipStreamCreateWithFlags(&r->query_stream, hipStreamNonBlocking));
-   hipStream_t qs = r->query_stream;
-   HIP_TRY(create_all(r->d_rq_next.sized(1), r->ev_rq_in, r->ev_rq_out)); // (one group, created by the first device query)
-   int rc = ensure_committed(r, qs);
-   if (rc != MDH_OK) return rc;
-   if (stream != qs) { // the arrays are what the caller's stream has made of them at this call
-      HIP_TRY(hipEventRecord(r->ev_rq_in.ev, stream));
-      HIP_TRY(hipStreamWaitEvent(qs, r->ev_rq_in.ev, 0));
-   }
-   if ((rc = sweep_launch(r, what, a, kind_ixs, n_kinds, what == MDH_RQ_SPHERECAST, qs)) != MDH_OK) return rc;
-   if (stream != qs) { // ... and the answers are there for whatever the caller's stream is given next
-      HIP_TRY(hipEventRecord(r->ev_rq_out.ev, qs));
-      HIP_TRY(hipStreamWaitEvent(stream, r->ev_rq_out.ev, 0));
-   }
-   return MDH_OK;
+   if (!r) return seterr(MDH_E_INVALID, "null renderer");
+   if (!arrays || n < 0) return seterr(MDH_E_INVALID, "bad argument");
+   if (has_custom_kinds(r)) return seterr(MDH_E_STATE, "ray queries answer scenes of built-in kinds only");
+   return sweep_kinds_check(r, kind_ixs, n_kinds); // (the kind list is the host's, wherever the arrays live)
 }
 extern "C" int32_t mdh_spherecast(mdh_renderer *r, int32_t n, const float *org, const float *dir, const float *radius, const float *tmax,
                                   const int32_t *kind_ixs, int32_t n_kinds, int32_t *hit_out, int32_t *index_out, float *t_out, int32_t *steps_out,
                                   float *pos_out, float *normal_out)
 {
-   if (!r) return seterr(MDH_E_INVALID, "null renderer");
-   if (!org || !dir || !hit_out || n < 0) return seterr(MDH_E_INVALID, "bad argument");
-   if (has_custom_kinds(r)) return seterr(MDH_E_STATE, "ray queries answer scenes of built-in kinds only");
-   int rc = sweep_kinds_check(r, kind_ixs, n_kinds);
+   int rc = sweep_check(r, n, org && dir && hit_out, kind_ixs, n_kinds);
    if (rc != MDH_OK || (rc = sweep_host_check(r, n, org, dir, radius, tmax)) != MDH_OK) return rc;
    if (n == 0) return MDH_OK;
-   RayQueryArgs a;
-   if ((rc = sweep_host_run(r, MDH_RQ_SPHERECAST, n, org, dir, radius, tmax, kind_ixs, n_kinds, normal_out != nullptr, a)) != MDH_OK) return rc;
-   hipStream_t qs = r->query_stream;
-   HIP_TRY(hipMemcpyAsync(hit_out, a.hit, (size_t)n * 4, hipMemcpyDeviceToHost, qs));
-   if (index_out) HIP_TRY(hipMemcpyAsync(index_out, a.index, (size_t)n * 4, hipMemcpyDeviceToHost, qs));
-   if (t_out) HIP_TRY(hipMemcpyAsync(t_out, a.t, (size_t)n * 4, hipMemcpyDeviceToHost, qs));
-   if (steps_out) HIP_TRY(hipMemcpyAsync(steps_out, a.steps, (size_t)n * 4, hipMemcpyDeviceToHost, qs));
-   if (pos_out) HIP_TRY(hipMemcpyAsync(pos_out, a.pos, (size_t)n * 12, hipMemcpyDeviceToHost, qs));
-   if (normal_out) HIP_TRY(hipMemcpyAsync(normal_out, a.normal, (size_t)n * 12, hipMemcpyDeviceToHost, qs));
+   RayStage st;
+   if ((rc = sweep_host_run(r, MDH_RQ_SPHERECAST, n, org, dir, radius, tmax, kind_ixs, n_kinds, normal_out != nullptr, st)) != MDH_OK) return rc;
+   ray_query_down(st, hit_out, index_out, t_out, steps_out, pos_out, normal_out);
+   HIP_TRY(st.err);
    return ray_query_wait(r);
 }
 extern "C" int32_t mdh_spherecast_device(mdh_renderer *r, int32_t n, const float *org, const float *dir, const float *radius, const float *tmax,
                                          const int32_t *kind_ixs, int32_t n_kinds, int32_t *hit_out, int32_t *index_out, float *t_out, int32_t *steps_out,
                                          float *pos_out, float *normal_out, void *stream)
 {
-   if (!r) return seterr(MDH_E_INVALID, "null renderer");
-   if (!org || !dir || !hit_out || n < 0) return seterr(MDH_E_INVALID, "bad argument");
-   if (has_custom_kinds(r)) return seterr(MDH_E_STATE, "ray queries answer scenes of built-in kinds only");
-   const int rc = sweep_kinds_check(r, kind_ixs, n_kinds); // (the kind list is the host's)
+   const int rc = sweep_check(r, n, org && dir && hit_out, kind_ixs, n_kinds);
    if (rc != MDH_OK) return rc;
    const size_t w = (size_t)n * 4;
    const RayArray arrays[] = {{org, 3 * w, "origins"}, {dir, 3 * w, "directions"}, {radius, w, "radii"}, {tmax, w, "tmax"}, {hit_out, w, "hit"}, {index_out, w, "index"},
                               {t_out, w, "t"}, {steps_out, w, "steps"}, {pos_out, 3 * w, "positions"}, {normal_out, 3 * w, "normals"}};
-   RayQueryArgs a;
-   a.n = n; a.tmin = 0.0f; a.k = 0.0f;
-   a.org = org; a.dir = dir; a.tmax = tmax; a.radius = radius;
-   a.hit = hit_out; a.index = index_out; a.steps = steps_out;
-   a.t = t_out; a.pos = pos_out; a.normal = normal_out;
-   a.out = nullptr;
-   return sweep_device_run(r, MDH_RQ_SPHERECAST, arrays, 10, a, kind_ixs, n_kinds, (hipStream_t)stream);
+   const RayQueryArgs a = ray_query_args(n, 0.0f, 0.0f, org, dir, tmax, radius, hit_out, index_out, t_out, steps_out, pos_out, normal_out, nullptr);
+   return ray_query_device(r, MDH_RQ_SPHERECAST, arrays, a, kind_ixs, n_kinds, true, stream);
 }
 extern "C" int32_t mdh_contacts(mdh_renderer *r, int32_t n, const float *centre, const float *radius, const int32_t *kind_ixs, int32_t n_kinds,
                                 float *dist_out, int32_t *index_out, float *normal_out)
 {
-   if (!r) return seterr(MDH_E_INVALID, "null renderer");
-   if (!centre || !dist_out || n < 0) return seterr(MDH_E_INVALID, "bad argument");
-   if (has_custom_kinds(r)) return seterr(MDH_E_STATE, "ray queries answer scenes of built-in kinds only");
-   int rc = sweep_kinds_check(r, kind_ixs, n_kinds);
+   int rc = sweep_check(r, n, centre && dist_out, kind_ixs, n_kinds);
    if (rc != MDH_OK || (rc = sweep_host_check(r, n, centre, nullptr, radius, nullptr)) != MDH_OK) return rc;
    if (n == 0) return MDH_OK;
-   RayQueryArgs a;
-   if ((rc = sweep_host_run(r, MDH_RQ_CONTACT, n, centre, nullptr, radius, nullptr, kind_ixs, n_kinds, normal_out != nullptr, a)) != MDH_OK) return rc;
-   hipStream_t qs = r->query_stream;
-   HIP_TRY(hipMemcpyAsync(dist_out, a.t, (size_t)n * 4, hipMemcpyDeviceToHost, qs));
-   if (index_out) HIP_TRY(hipMemcpyAsync(index_out, a.index, (size_t)n * 4, hipMemcpyDeviceToHost, qs));
-   if (normal_out) HIP_TRY(hipMemcpyAsync(normal_out, a.normal, (size_t)n * 12, hipMemcpyDeviceToHost, qs));
+   RayStage st;
+   if ((rc = sweep_host_run(r, MDH_RQ_CONTACT, n, centre, nullptr, radius, nullptr, kind_ixs, n_kinds, normal_out != nullptr, st)) != MDH_OK) return rc;
+   ray_query_down(st, nullptr, index_out, dist_out, nullptr, nullptr, normal_out); // (a contact's distance: where a ray's t is)
+   HIP_TRY(st.err);
    return ray_query_wait(r);
 }
 extern "C" int32_t mdh_contacts_device(mdh_renderer *r, int32_t n, const float *centre, const float *radius, const int32_t *kind_ixs, int32_t n_kinds,
                                        float *dist_out, int32_t *index_out, float *normal_out, void *stream)
 {
-   if (!r) return seterr(MDH_E_INVALID, "null renderer");
-   if (!centre || !dist_out || n < 0) return seterr(MDH_E_INVALID, "bad argument");
-   if (has_custom_kinds(r)) return seterr(MDH_E_STATE, "ray queries answer scenes of built-in kinds only");
-   const int rc = sweep_kinds_check(r, kind_ixs, n_kinds);
+   const int rc = sweep_check(r, n, centre && dist_out, kind_ixs, n_kinds);
    if (rc != MDH_OK) return rc;
    const size_t w = (size_t)n * 4;
    const RayArray arrays[] = {{centre, 3 * w, "centres"}, {radius, w, "radii"}, {dist_out, w, "distances"}, {index_out, w, "index"}, {normal_out, 3 * w, "normals"}};
-   RayQueryArgs a;
-   a.n = n; a.tmin = 0.0f; a.k = 0.0f;
-   a.org = centre; a.dir = nullptr; a.tmax = nullptr; a.radius = radius;
-   a.hit = nullptr; a.index = index_out; a.steps = nullptr;
-   a.t = dist_out; a.pos = nullptr; a.normal = normal_out;
-   a.out = nullptr;
-   return sweep_device_run(r, MDH_RQ_CONTACT, arrays, 5, a, kind_ixs, n_kinds, (hipStream_t)stream);
+   const RayQueryArgs a = ray_query_args(n, 0.0f, 0.0f, centre, nullptr, nullptr, radius, nullptr, index_out, dist_out, nullptr, nullptr, normal_out, nullptr);
+   return ray_query_device(r, MDH_RQ_CONTACT, arrays, a, kind_ixs, n_kinds, false, stream);
 }
 
 // ------------------------------------------------------------------ shading a host's rays
 // mdh_shade_rays, mdh_shade_rays_device: pixel_color_probes (render_probes.glsl:246-291) along n rays of the host's, through
-// the pixel program the screen pass runs (k_ray_shade, mdh_kernels.h).  The plumbing is the ray queries': the query stream,
-// ensure_committed, table_acquire / table_release, d_rays for host arrays, ray_array_check and two events to the caller's
-// stream for device arrays, rq_e0 / rq_e1 under MDH_OPT_TIMING.  No settle_bump: nothing is edited.
+// the pixel program the screen pass runs (k_ray_shade, mdh_kernels.h), by the query path.  No settle_bump: nothing is edited.
 // WHICH ATLASES, AND WHEN.  The query is a mdh_render_pass (MDH_PASS_SCREEN) that runs on the query stream: it reads set
-// `last`, and it is tied to the main stream as that pass is tied to it by running there -- join_main, then the query stream
-// waits for the main stream (which every screen pass of a frame up to `last`, hence every probe pass of those frames, is
-// ordered before), and behind the kernel the main stream waits for the query stream with main_dirty set, so that the next
-// frame orders its probe, volumetric and alternate streams behind the query before any of them rewrites a set.
-// (the three events: one group, created by the first call)
-static int shade_scene_check(const mdh_renderer *r)
-{
-   // (the scene's half of the bound that stands in for a stall guard, mdh_ray_stream.h: rs_shade_ray_valid has the ray's)
-   if (!rs_shade_extent_valid(r->max_dist)) return seterr(MDH_E_STATE, "shaded rays need a max_dist of at most 1024");
-   for (int k = 0; k < r->nlk; ++k) {
-      const Kind &kd = r->lk[k];
-      int n = rd_i(r, kd.count_off);
-      if (n > kd.max_count) n = kd.max_count;
-      for (int i = 0; i < n; ++i)
-         for (int c = 0; c < 3; ++c)
-            if (!rs_shade_extent_valid(rd_f(r, kd.array_off + kd.stride * i + kd.f_a + 4 * c))) return seterr(MDH_E_STATE, "shaded rays need every light within 1024 of the origin along every axis");
-   }
-   for (int c = 0; c < 3; ++c)
-      if (!rs_shade_extent_valid((float)(r->probes.grid_dimensions[c] - 1) * r->probes.grid_spacing[c])) return seterr(MDH_E_STATE, "shaded rays need the probe grid's far corner within 1024 of the origin along every axis");
-   return MDH_OK;
-}
+// `last` at its place among the frames (query_enqueue, `framed`): behind every screen pass of a frame up to `last`, hence
+// every probe pass of those frames, and in front of whatever a later frame rewrites.
 // everything both calls refuse before they look at their arrays
 static int shade_rays_check(const mdh_renderer *r, int32_t n, const float *org, const float *dir, int32_t mode, const float *rgb)
 {
@@ -4044,59 +4046,18 @@ static int shade_rays_check(const mdh_renderer *r, int32_t n, const float *org, 
       return seterr(MDH_E_STATE, "rays are shaded with MDH_OPT_INDIRECT_SPECULAR 0 or 2, the latter without MDH_OPT_RADIANCE_MIPS");
    return shade_scene_check(r);
 }
-// the query stream and the events, the committed scene, the kernel; then the launch between the fences.  `caller`: the stream
-// device arrays are ordered with, or the query stream itself (host arrays: the copies around the launch are the caller's)
-// (`kernel`, `lds`: k_ray_shade with the screen pass's rows, or k_point_shade -- mdh_shade_points below -- with its own)
-template <typename Args> static int shade_query_run(mdh_renderer *r, const void *kernel, size_t lds, const Args &a, hipStream_t qs, hipStream_t caller)
+static RayShadeArgs ray_shade_args(const mdh_renderer *r, int32_t n, int32_t tone_map, const float *org, const float *dir, float *rgb, int *hit, int *index, float *t, int *steps)
 {
-   int rc;
-   if (!kernel) return seterr(MDH_E_INVALID, "no kernel built for this variant");
-   if ((rc = join_main(r)) != MDH_OK) return rc;
-   r->main_dirty = true;
-   HIP_TRY(hipEventRecord(r->ev_sq_frame.ev, r->stream));
-   HIP_TRY(hipStreamWaitEvent(qs, r->ev_sq_frame.ev, 0));
-   if (caller != qs) { // the rays are what the caller's stream has made of them at this call
-      HIP_TRY(hipEventRecord(r->ev_sq_caller.ev, caller));
-      HIP_TRY(hipStreamWaitEvent(qs, r->ev_sq_caller.ev, 0));
-   }
-   if ((rc = table_acquire(r, qs)) != MDH_OK) return rc;
-   const KProbes pr = make_probes(r); // (set `last`)
-   const unsigned blocks = (unsigned)(((size_t)a.n + MDH_BLOCK - 1) / MDH_BLOCK);
-   const bool timed = r->opt_timing && (r->rq_e0 || (r->rq_e0 = get_event(r))) && (r->rq_e1 || (r->rq_e1 = get_event(r)));
-   if (timed) HIP_TRY(hipEventRecord(r->rq_e0, qs));
-   if ((rc = launch_kernel_ptr(kernel, dim3(blocks), dim3(MDH_BLOCK), lds, qs, r->ks, pr, a)) != MDH_OK) return rc;
-   HIP_TRY(hipGetLastError());
-   if (timed) HIP_TRY(hipEventRecord(r->rq_e1, qs));
-   r->rq_timed = timed;
-   if ((rc = table_release(r, qs)) != MDH_OK) return rc;
-   HIP_TRY(hipEventRecord(r->ev_sq_done.ev, qs)); // no later frame rewrites the set before this point ...
-   HIP_TRY(hipStreamWaitEvent(r->stream, r->ev_sq_done.ev, 0));
-   if (caller != qs) HIP_TRY(hipStreamWaitEvent(caller, r->ev_sq_done.ev, 0)); // ... and the answers are there for the caller's stream
-   return MDH_OK;
+   RayShadeArgs a;
+   a.n = n; a.tone_map = tone_map ? 1 : 0; a.ao_steps = r->opt_ao; a.spec_mode = r->opt_spec;
+   a.org = org; a.dir = dir; a.rgb = rgb;
+   a.hit = hit; a.index = index; a.t = t; a.steps = steps;
+   return a;
 }
+// k_ray_shade with the screen pass's rows and the probes of set `last`, at its place among the frames
 static int shade_rays_run(mdh_renderer *r, int32_t mode, const RayShadeArgs &a, hipStream_t qs, hipStream_t caller)
 {
-   return shade_query_run(r, table_kernel(r, GK_k_ray_shade, mode), lds_bytes_screen_mode(r, mode), a, qs, caller);
-}
-static int shade_rays_begin(mdh_renderer *r, hipStream_t *qs)
-{
-   HIP_TRY(hipSetDevice(r->device));
-   if (!r->query_stream) HIP_TRY(hipStreamCreateWithFlags(&r->query_stream, hipStreamNonBlocking));
-   HIP_TRY(create_all(r->ev_sq_frame, r->ev_sq_caller, r->ev_sq_done));
-   *qs = r->query_stream;
-   return ensure_committed(r, *qs);
-}
-// room in d_rays for n rays (MDH_RAY_WORDS words each); the places are the ray queries'
-static int rays_buffer(mdh_renderer *r, size_t n, hipStream_t qs, float **base, size_t *cap)
-{
-   const size_t want = (n < 256 ? 256 : n) * MDH_RAY_WORDS;
-   if (want > r->d_rays.cap) {
-      if (r->d_rays.ptr) HIP_TRY(hipStreamSynchronize(qs));
-      HIP_TRY(r->d_rays.grow(want));
-   }
-   *cap = r->d_rays.cap / MDH_RAY_WORDS;
-   *base = r->d_rays.ptr;
-   return MDH_OK;
+   return query_kernel(r, table_kernel(r, GK_k_ray_shade, mode), lane_blocks(a.n), lds_bytes_screen_mode(r, mode), qs, caller, true, make_probes(r), a);
 }
 extern "C" int32_t mdh_shade_rays(mdh_renderer *r, int32_t n, const float *org, const float *dir, int32_t mode, int32_t tone_map, float *rgb_out,
                                   int32_t *hit_out, int32_t *index_out, float *t_out, int32_t *steps_out)
@@ -4109,24 +4070,14 @@ extern "C" int32_t mdh_shade_rays(mdh_renderer *r, int32_t n, const float *org, 
       if (!ok) return seterr(MDH_E_INVALID, "a ray is not finite, starts beyond 1024 or has a direction component beyond 2");
    }
    if (n == 0) return MDH_OK;
-   hipStream_t qs = nullptr;
-   if ((rc = shade_rays_begin(r, &qs)) != MDH_OK) return rc;
-   float *base = nullptr;
-   size_t cap = 0;
-   if ((rc = rays_buffer(r, (size_t)n, qs, &base, &cap)) != MDH_OK) return rc;
-   RayShadeArgs a;
-   a.n = n; a.tone_map = tone_map ? 1 : 0; a.ao_steps = r->opt_ao; a.spec_mode = r->opt_spec;
-   a.org = base; a.dir = base + 3 * cap;
-   a.hit = (int *)(base + 7 * cap); a.index = (int *)(base + 8 * cap); a.t = base + 9 * cap; a.steps = (int *)(base + 10 * cap);
-   a.rgb = base + 11 * cap;
-   HIP_TRY(hipMemcpyAsync(base, org, (size_t)n * 12, hipMemcpyHostToDevice, qs));
-   HIP_TRY(hipMemcpyAsync(base + 3 * cap, dir, (size_t)n * 12, hipMemcpyHostToDevice, qs));
-   if ((rc = shade_rays_run(r, mode, a, qs, qs)) != MDH_OK) return rc;
-   HIP_TRY(hipMemcpyAsync(rgb_out, a.rgb, (size_t)n * 12, hipMemcpyDeviceToHost, qs));
-   if (hit_out) HIP_TRY(hipMemcpyAsync(hit_out, a.hit, (size_t)n * 4, hipMemcpyDeviceToHost, qs));
-   if (index_out) HIP_TRY(hipMemcpyAsync(index_out, a.index, (size_t)n * 4, hipMemcpyDeviceToHost, qs));
-   if (t_out) HIP_TRY(hipMemcpyAsync(t_out, a.t, (size_t)n * 4, hipMemcpyDeviceToHost, qs));
-   if (steps_out) HIP_TRY(hipMemcpyAsync(steps_out, a.steps, (size_t)n * 4, hipMemcpyDeviceToHost, qs));
+   RayStage st;
+   if ((rc = host_query_begin(r, n, st)) != MDH_OK) return rc;
+   const float *d_org = st.up(SLOT_ORG, org, 3), *d_dir = st.up(SLOT_DIR, dir, 3);
+   HIP_TRY(st.err);
+   const RayShadeArgs a = ray_shade_args(r, n, tone_map, d_org, d_dir, st.at(SLOT_RGB), st.at<int>(SLOT_HIT), st.at<int>(SLOT_INDEX), st.at(SLOT_T), st.at<int>(SLOT_STEPS));
+   if ((rc = shade_rays_run(r, mode, a, st.qs, st.qs)) != MDH_OK) return rc;
+   st.down(rgb_out, SLOT_RGB, 3); st.down(hit_out, SLOT_HIT, 1); st.down(index_out, SLOT_INDEX, 1); st.down(t_out, SLOT_T, 1); st.down(steps_out, SLOT_STEPS, 1);
+   HIP_TRY(st.err);
    return ray_query_wait(r);
 }
 extern "C" int32_t mdh_shade_rays_device(mdh_renderer *r, int32_t n, const float *org, const float *dir, int32_t mode, int32_t tone_map, float *rgb_out,
@@ -4134,42 +4085,20 @@ extern "C" int32_t mdh_shade_rays_device(mdh_renderer *r, int32_t n, const float
 {
    int rc = shade_rays_check(r, n, org, dir, mode, rgb_out);
    if (rc != MDH_OK) return rc;
-   HIP_TRY(hipSetDevice(r->device));
    const size_t w = (size_t)n * 4;
    const RayArray arrays[] = {{org, 3 * w, "origins"}, {dir, 3 * w, "directions"}, {rgb_out, 3 * w, "colours"}, {hit_out, w, "hit"},
                               {index_out, w, "index"}, {t_out, w, "t"}, {steps_out, w, "steps"}};
-   for (const RayArray &ra : arrays)
-      if ((rc = ray_array_check(r, ra)) != MDH_OK) return rc;
-   if (n == 0) return MDH_OK;
+   if ((rc = ray_arrays_check(r, arrays)) != MDH_OK || n == 0) return rc;
    hipStream_t qs = nullptr;
-   if ((rc = shade_rays_begin(r, &qs)) != MDH_OK) return rc;
-   RayShadeArgs a;
-   a.n = n; a.tone_map = tone_map ? 1 : 0; a.ao_steps = r->opt_ao; a.spec_mode = r->opt_spec;
-   a.org = org; a.dir = dir; a.rgb = rgb_out;
-   a.hit = hit_out; a.index = index_out; a.t = t_out; a.steps = steps_out;
-   return shade_rays_run(r, mode, a, qs, (hipStream_t)stream);
+   if ((rc = device_query_begin(r, &qs)) != MDH_OK) return rc;
+   return shade_rays_run(r, mode, ray_shade_args(r, n, tone_map, org, dir, rgb_out, hit_out, index_out, t_out, steps_out), qs, (hipStream_t)stream);
 }
 
 // ------------------------------------------------------------------ path tracing a host's rays
 // mdh_path_trace, mdh_path_trace_device: the estimator of k_path_trace (mdh_kernels.h) along n rays of the host's, samples
-// sample_first .. sample_first + sample_count - 1 added to rgb_accum.  The plumbing is mdh_shade_rays': shade_rays_begin,
-// the fences of shade_query_run (no atlas is read, but the query keeps that call's place among the frames), d_rays for host
-// arrays, ray_array_check for device arrays, rq_e0 / rq_e1 under MDH_OPT_TIMING.  No settle_bump: nothing is edited.
+// sample_first .. sample_first + sample_count - 1 added to rgb_accum, by the query path at a shaded ray's place among the
+// frames (no atlas is read, but the query keeps that call's place).  No settle_bump: nothing is edited.
 // MDH_OPT_AO_STEPS and MDH_OPT_INDIRECT_SPECULAR do not enter.  Every refusal happens before a launch.
-// the scene's half of the bound (mdh_path.h): shade_scene_check without the probe grid, which no path reads
-static int path_scene_check(const mdh_renderer *r)
-{
-   if (!rs_shade_extent_valid(r->max_dist)) return seterr(MDH_E_STATE, "traced paths need a max_dist of at most 1024");
-   for (int k = 0; k < r->nlk; ++k) {
-      const Kind &kd = r->lk[k];
-      int n = rd_i(r, kd.count_off);
-      if (n > kd.max_count) n = kd.max_count;
-      for (int i = 0; i < n; ++i)
-         for (int c = 0; c < 3; ++c)
-            if (!rs_shade_extent_valid(rd_f(r, kd.array_off + kd.stride * i + kd.f_a + 4 * c))) return seterr(MDH_E_STATE, "traced paths need every light within 1024 of the origin along every axis");
-   }
-   return MDH_OK;
-}
 // everything both calls refuse before they look at their arrays
 static int path_trace_check(const mdh_renderer *r, int32_t n, const float *org, const float *dir, int32_t sample_first, int32_t sample_count, int32_t bounces, const float *rgb)
 {
@@ -4179,34 +4108,21 @@ static int path_trace_check(const mdh_renderer *r, int32_t n, const float *org, 
    if (!path_bounces_valid(bounces)) return seterr(MDH_E_INVALID, "paths take 0 to 6 bounces");
    if (has_custom_kinds(r)) return seterr(MDH_E_STATE, "ray queries answer scenes of built-in kinds only");
    if (r->in_frame) return seterr(MDH_E_STATE, "a frame is open");
-   return path_scene_check(r);
+   return scene_extent_check(r, "traced paths", false); // (no path reads the probe grid)
 }
+static PathTraceArgs path_trace_args(int32_t n, uint32_t seed, uint32_t id_first, int32_t sample_first, int32_t sample_count, int32_t bounces, const float *org,
+                                     const float *dir, float *rgb, int *hit, int *index, float *t)
+{
+   PathTraceArgs a;
+   a.n = n; a.bounces = bounces; a.seed = seed; a.id_first = id_first; a.sample_first = sample_first; a.sample_count = sample_count;
+   a.org = org; a.dir = dir; a.rgb = rgb;
+   a.hit = hit; a.index = index; a.t = t;
+   return a;
+}
+// k_path_trace (no park rows) at the place among the frames a shaded ray's kernel has: no atlas is read, the place is kept
 static int path_trace_run(mdh_renderer *r, const PathTraceArgs &a, hipStream_t qs, hipStream_t caller)
 {
-   int rc;
-   const void *kernel = table_kernel(r, GK_k_path_trace);
-   if (!kernel) return seterr(MDH_E_INVALID, "no kernel built for this variant");
-   if ((rc = join_main(r)) != MDH_OK) return rc;
-   r->main_dirty = true;
-   HIP_TRY(hipEventRecord(r->ev_sq_frame.ev, r->stream));
-   HIP_TRY(hipStreamWaitEvent(qs, r->ev_sq_frame.ev, 0));
-   if (caller != qs) { // the rays and the sums are what the caller's stream has made of them at this call
-      HIP_TRY(hipEventRecord(r->ev_sq_caller.ev, caller));
-      HIP_TRY(hipStreamWaitEvent(qs, r->ev_sq_caller.ev, 0));
-   }
-   if ((rc = table_acquire(r, qs)) != MDH_OK) return rc;
-   const unsigned blocks = (unsigned)(((size_t)a.n + MDH_BLOCK - 1) / MDH_BLOCK);
-   const bool timed = r->opt_timing && (r->rq_e0 || (r->rq_e0 = get_event(r))) && (r->rq_e1 || (r->rq_e1 = get_event(r)));
-   if (timed) HIP_TRY(hipEventRecord(r->rq_e0, qs));
-   if ((rc = launch_kernel_ptr(kernel, dim3(blocks), dim3(MDH_BLOCK), lds_bytes(r), qs, r->ks, a)) != MDH_OK) return rc; // (no park rows)
-   HIP_TRY(hipGetLastError());
-   if (timed) HIP_TRY(hipEventRecord(r->rq_e1, qs));
-   r->rq_timed = timed;
-   if ((rc = table_release(r, qs)) != MDH_OK) return rc;
-   HIP_TRY(hipEventRecord(r->ev_sq_done.ev, qs));
-   HIP_TRY(hipStreamWaitEvent(r->stream, r->ev_sq_done.ev, 0));
-   if (caller != qs) HIP_TRY(hipStreamWaitEvent(caller, r->ev_sq_done.ev, 0)); // the sums are there for the caller's stream
-   return MDH_OK;
+   return query_kernel(r, table_kernel(r, GK_k_path_trace), lane_blocks(a.n), lds_bytes(r), qs, caller, true, a);
 }
 extern "C" int32_t mdh_path_trace(mdh_renderer *r, int32_t n, const float *org, const float *dir, uint32_t seed, uint32_t id_first, int32_t sample_first,
                                   int32_t sample_count, int32_t bounces, float *rgb_accum, int32_t *hit_out, int32_t *index_out, float *t_out)
@@ -4219,24 +4135,15 @@ extern "C" int32_t mdh_path_trace(mdh_renderer *r, int32_t n, const float *org, 
       if (!ok) return seterr(MDH_E_INVALID, "a ray is not finite, starts beyond 1024, has a direction component beyond 2 or a direction of zero");
    }
    if (n == 0 || sample_count == 0) return MDH_OK;
-   hipStream_t qs = nullptr;
-   if ((rc = shade_rays_begin(r, &qs)) != MDH_OK) return rc;
-   float *base = nullptr;
-   size_t cap = 0;
-   if ((rc = rays_buffer(r, (size_t)n, qs, &base, &cap)) != MDH_OK) return rc;
-   PathTraceArgs a;
-   a.n = n; a.bounces = bounces; a.seed = seed; a.id_first = id_first; a.sample_first = sample_first; a.sample_count = sample_count;
-   a.org = base; a.dir = base + 3 * cap;
-   a.hit = (int *)(base + 7 * cap); a.index = (int *)(base + 8 * cap); a.t = base + 9 * cap;
-   a.rgb = base + 11 * cap;
-   HIP_TRY(hipMemcpyAsync(base, org, (size_t)n * 12, hipMemcpyHostToDevice, qs));
-   HIP_TRY(hipMemcpyAsync(base + 3 * cap, dir, (size_t)n * 12, hipMemcpyHostToDevice, qs));
-   HIP_TRY(hipMemcpyAsync(a.rgb, rgb_accum, (size_t)n * 12, hipMemcpyHostToDevice, qs)); // (the sums so far)
-   if ((rc = path_trace_run(r, a, qs, qs)) != MDH_OK) return rc;
-   HIP_TRY(hipMemcpyAsync(rgb_accum, a.rgb, (size_t)n * 12, hipMemcpyDeviceToHost, qs));
-   if (hit_out) HIP_TRY(hipMemcpyAsync(hit_out, a.hit, (size_t)n * 4, hipMemcpyDeviceToHost, qs));
-   if (index_out) HIP_TRY(hipMemcpyAsync(index_out, a.index, (size_t)n * 4, hipMemcpyDeviceToHost, qs));
-   if (t_out) HIP_TRY(hipMemcpyAsync(t_out, a.t, (size_t)n * 4, hipMemcpyDeviceToHost, qs));
+   RayStage st;
+   if ((rc = host_query_begin(r, n, st)) != MDH_OK) return rc;
+   const float *d_org = st.up(SLOT_ORG, org, 3), *d_dir = st.up(SLOT_DIR, dir, 3);
+   float *d_rgb = st.up(SLOT_RGB, rgb_accum, 3); // (the sums so far)
+   HIP_TRY(st.err);
+   const PathTraceArgs a = path_trace_args(n, seed, id_first, sample_first, sample_count, bounces, d_org, d_dir, d_rgb, st.at<int>(SLOT_HIT), st.at<int>(SLOT_INDEX), st.at(SLOT_T));
+   if ((rc = path_trace_run(r, a, st.qs, st.qs)) != MDH_OK) return rc;
+   st.down(rgb_accum, SLOT_RGB, 3); st.down(hit_out, SLOT_HIT, 1); st.down(index_out, SLOT_INDEX, 1); st.down(t_out, SLOT_T, 1);
+   HIP_TRY(st.err);
    return ray_query_wait(r);
 }
 extern "C" int32_t mdh_path_trace_device(mdh_renderer *r, int32_t n, const float *org, const float *dir, uint32_t seed, uint32_t id_first, int32_t sample_first,
@@ -4244,20 +4151,13 @@ extern "C" int32_t mdh_path_trace_device(mdh_renderer *r, int32_t n, const float
 {
    int rc = path_trace_check(r, n, org, dir, sample_first, sample_count, bounces, rgb_accum);
    if (rc != MDH_OK) return rc;
-   HIP_TRY(hipSetDevice(r->device));
    const size_t w = (size_t)n * 4;
    const RayArray arrays[] = {{org, 3 * w, "origins"}, {dir, 3 * w, "directions"}, {rgb_accum, 3 * w, "colour sums"}, {hit_out, w, "hit"},
                               {index_out, w, "index"}, {t_out, w, "t"}};
-   for (const RayArray &ra : arrays)
-      if ((rc = ray_array_check(r, ra)) != MDH_OK) return rc;
-   if (n == 0 || sample_count == 0) return MDH_OK;
+   if ((rc = ray_arrays_check(r, arrays)) != MDH_OK || n == 0 || sample_count == 0) return rc;
    hipStream_t qs = nullptr;
-   if ((rc = shade_rays_begin(r, &qs)) != MDH_OK) return rc;
-   PathTraceArgs a;
-   a.n = n; a.bounces = bounces; a.seed = seed; a.id_first = id_first; a.sample_first = sample_first; a.sample_count = sample_count;
-   a.org = org; a.dir = dir; a.rgb = rgb_accum;
-   a.hit = hit_out; a.index = index_out; a.t = t_out;
-   return path_trace_run(r, a, qs, (hipStream_t)stream);
+   if ((rc = device_query_begin(r, &qs)) != MDH_OK) return rc;
+   return path_trace_run(r, path_trace_args(n, seed, id_first, sample_first, sample_count, bounces, org, dir, rgb_accum, hit_out, index_out, t_out), qs, (hipStream_t)stream);
 }
 // the sampler by itself, on the host over the functions the lanes call (mdh_path.h): no launch, no renderer
 extern "C" int32_t mdh_path_scatter(int32_t n, const float *dir, const float *normal, const float *roughness, uint32_t seed, uint32_t id_first, int32_t sample,
@@ -4270,11 +4170,9 @@ extern "C" int32_t mdh_path_scatter(int32_t n, const float *dir, const float *no
 }
 // ------------------------------------------------------------------ in-scattering along a host's rays and at its points
 // mdh_inscatter_points, mdh_inscatter_rays and their _device forms: the lights' fog at n points and along n rays of the host's
-// (k_point_inscatter, k_ray_inscatter, mdh_kernels.h).  The plumbing is the RAY QUERIES', not the shade queries': nothing here
-// reads an atlas, so there is no ordering against the frame's passes -- the query stream, ensure_committed (pending edits are
-// seen), table_acquire / table_release, d_rays for host arrays, ray_array_check and the two caller-stream events of
-// ray_stream_run for device arrays, rq_e0 / rq_e1 under MDH_OPT_TIMING.  No settle_bump: nothing is edited.  Every refusal
-// happens before a launch.
+// (k_point_inscatter, k_ray_inscatter, mdh_kernels.h), by the query path as the RAY QUERIES take it, not the shade queries:
+// nothing here reads an atlas, so there is no ordering against the frame's passes.  No settle_bump: nothing is edited.  Every
+// refusal happens before a launch.
 // what both forms of both calls refuse before they look at their arrays (the points' calls have neither march nor step)
 static int inscatter_check(const mdh_renderer *r, int32_t n, bool arrays, bool rays, int32_t march, float step)
 {
@@ -4285,40 +4183,32 @@ static int inscatter_check(const mdh_renderer *r, int32_t n, bool arrays, bool r
    if (has_custom_kinds(r)) return seterr(MDH_E_STATE, "ray queries answer scenes of built-in kinds only");
    return MDH_OK;
 }
-static int inscatter_begin(mdh_renderer *r, hipStream_t *qs)
+static InscatterPointArgs inscatter_point_args(int32_t n, const float *pos, const float *dir, const float *f, float *rgb)
 {
-   HIP_TRY(hipSetDevice(r->device));
-   if (!r->query_stream) HIP_TRY(hipStreamCreateWithFlags(&r->query_stream, hipStreamNonBlocking));
-   *qs = r->query_stream;
-   return ensure_committed(r, *qs);
+   InscatterPointArgs a;
+   a.n = n;
+   a.pos = pos; a.dir = dir; a.f = f;
+   a.rgb = rgb;
+   return a;
 }
-// enqueues the kernel on the query stream, between the caller's stream's events where the arrays are the caller's
-template <typename Args> static int inscatter_run(mdh_renderer *r, int family, unsigned blocks, const Args &a, hipStream_t qs, hipStream_t caller)
+static InscatterRayArgs inscatter_ray_args(int32_t n, int32_t march, float step, const float *org, const float *dir, const float *tmax, float *rgb, float *len, int *steps)
 {
-   int rc;
-   const void *kernel = table_kernel(r, family);
-   if (!kernel) return seterr(MDH_E_INVALID, "no kernel built for this variant");
-   if (caller != qs) { // the arrays are what the caller's stream has made of them at this call
-      HIP_TRY(create_all(r->d_rq_next.sized(1), r->ev_rq_in, r->ev_rq_out)); // (the device queries' group)
-      HIP_TRY(hipEventRecord(r->ev_rq_in.ev, caller));
-      HIP_TRY(hipStreamWaitEvent(qs, r->ev_rq_in.ev, 0));
-   }
-   if ((rc = table_acquire(r, qs)) != MDH_OK) return rc;
-   const bool timed = r->opt_timing && (r->rq_e0 || (r->rq_e0 = get_event(r))) && (r->rq_e1 || (r->rq_e1 = get_event(r)));
-   if (timed) HIP_TRY(hipEventRecord(r->rq_e0, qs));
-   if ((rc = launch_kernel_ptr(kernel, dim3(blocks), dim3(MDH_BLOCK), lds_bytes(r), qs, r->ks, a)) != MDH_OK) return rc;
-   HIP_TRY(hipGetLastError());
-   if (timed) HIP_TRY(hipEventRecord(r->rq_e1, qs));
-   r->rq_timed = timed;
-   if ((rc = table_release(r, qs)) != MDH_OK) return rc;
-   if (caller != qs) { // ... and the answers are there for whatever the caller's stream is given next
-      HIP_TRY(hipEventRecord(r->ev_rq_out.ev, qs));
-      HIP_TRY(hipStreamWaitEvent(caller, r->ev_rq_out.ev, 0));
-   }
-   return MDH_OK;
+   InscatterRayArgs a;
+   a.n = n; a.march = march; a.step = step;
+   a.org = org; a.dir = dir; a.tmax = tmax;
+   a.rgb = rgb; a.len = len; a.steps = steps;
+   return a;
 }
-static unsigned inscatter_point_blocks(int32_t n) { return (unsigned)(((size_t)n + MDH_BLOCK - 1) / MDH_BLOCK); }
-static unsigned inscatter_ray_blocks(int32_t n) { return (unsigned)(((size_t)n + MDH_BLOCK / MDH_RS_WAVE - 1) / (MDH_BLOCK / MDH_RS_WAVE)); } // (a wavefront per ray)
+// a lane per point; a wavefront per ray.  No atlas is read: neither kernel has a place among the frames
+static int inscatter_points_run(mdh_renderer *r, const InscatterPointArgs &a, hipStream_t qs, hipStream_t caller)
+{
+   return query_kernel(r, table_kernel(r, GK_k_point_inscatter), lane_blocks(a.n), lds_bytes(r), qs, caller, false, a);
+}
+static int inscatter_rays_run(mdh_renderer *r, const InscatterRayArgs &a, hipStream_t qs, hipStream_t caller)
+{
+   const unsigned blocks = (unsigned)(((size_t)a.n + MDH_BLOCK / MDH_RS_WAVE - 1) / (MDH_BLOCK / MDH_RS_WAVE));
+   return query_kernel(r, table_kernel(r, GK_k_ray_inscatter), blocks, lds_bytes(r), qs, caller, false, a);
+}
 extern "C" int32_t mdh_inscatter_points(mdh_renderer *r, int32_t n, const float *pos, const float *dir, const float *f, float *rgb_out)
 {
    int rc = inscatter_check(r, n, pos && dir && rgb_out, false, 0, 0.0f);
@@ -4330,39 +4220,25 @@ extern "C" int32_t mdh_inscatter_points(mdh_renderer *r, int32_t n, const float 
       if (!ok) return seterr(MDH_E_INVALID, "a distance along the ray is not finite");
    }
    if (n == 0) return MDH_OK;
-   hipStream_t qs = nullptr;
-   if ((rc = inscatter_begin(r, &qs)) != MDH_OK) return rc;
-   float *base = nullptr;
-   size_t cap = 0;
-   if ((rc = rays_buffer(r, (size_t)n, qs, &base, &cap)) != MDH_OK) return rc;
-   InscatterPointArgs a;
-   a.n = n;
-   a.pos = base; a.dir = base + 3 * cap; a.f = f ? base + 6 * cap : nullptr;
-   a.rgb = base + 11 * cap;
-   HIP_TRY(hipMemcpyAsync(base, pos, (size_t)n * 12, hipMemcpyHostToDevice, qs));
-   HIP_TRY(hipMemcpyAsync(base + 3 * cap, dir, (size_t)n * 12, hipMemcpyHostToDevice, qs));
-   if (f) HIP_TRY(hipMemcpyAsync(base + 6 * cap, f, (size_t)n * 4, hipMemcpyHostToDevice, qs));
-   if ((rc = inscatter_run(r, GK_k_point_inscatter, inscatter_point_blocks(n), a, qs, qs)) != MDH_OK) return rc;
-   HIP_TRY(hipMemcpyAsync(rgb_out, a.rgb, (size_t)n * 12, hipMemcpyDeviceToHost, qs));
+   RayStage st;
+   if ((rc = host_query_begin(r, n, st)) != MDH_OK) return rc;
+   const float *d_pos = st.up(SLOT_ORG, pos, 3), *d_dir = st.up(SLOT_DIR, dir, 3), *d_f = st.up(SLOT_F, f, 1);
+   HIP_TRY(st.err);
+   if ((rc = inscatter_points_run(r, inscatter_point_args(n, d_pos, d_dir, f ? d_f : nullptr, st.at(SLOT_RGB)), st.qs, st.qs)) != MDH_OK) return rc;
+   st.down(rgb_out, SLOT_RGB, 3);
+   HIP_TRY(st.err);
    return ray_query_wait(r);
 }
 extern "C" int32_t mdh_inscatter_points_device(mdh_renderer *r, int32_t n, const float *pos, const float *dir, const float *f, float *rgb_out, void *stream)
 {
    int rc = inscatter_check(r, n, pos && dir && rgb_out, false, 0, 0.0f);
    if (rc != MDH_OK) return rc;
-   HIP_TRY(hipSetDevice(r->device));
    const size_t w = (size_t)n * 4;
    const RayArray arrays[] = {{pos, 3 * w, "positions"}, {dir, 3 * w, "directions"}, {f, w, "distances"}, {rgb_out, 3 * w, "colours"}};
-   for (const RayArray &ra : arrays)
-      if ((rc = ray_array_check(r, ra)) != MDH_OK) return rc;
-   if (n == 0) return MDH_OK;
+   if ((rc = ray_arrays_check(r, arrays)) != MDH_OK || n == 0) return rc;
    hipStream_t qs = nullptr;
-   if ((rc = inscatter_begin(r, &qs)) != MDH_OK) return rc;
-   InscatterPointArgs a;
-   a.n = n;
-   a.pos = pos; a.dir = dir; a.f = f;
-   a.rgb = rgb_out;
-   return inscatter_run(r, GK_k_point_inscatter, inscatter_point_blocks(n), a, qs, (hipStream_t)stream);
+   if ((rc = device_query_begin(r, &qs)) != MDH_OK) return rc;
+   return inscatter_points_run(r, inscatter_point_args(n, pos, dir, f, rgb_out), qs, (hipStream_t)stream);
 }
 extern "C" int32_t mdh_inscatter_rays(mdh_renderer *r, int32_t n, const float *org, const float *dir, const float *tmax, int32_t march, float step,
                                       float *rgb_out, float *len_out, int32_t *steps_out)
@@ -4376,22 +4252,14 @@ extern "C" int32_t mdh_inscatter_rays(mdh_renderer *r, int32_t n, const float *o
       if (!ok) return seterr(MDH_E_INVALID, "a ray's length is not finite, is negative or exceeds the scene's max_dist");
    }
    if (n == 0) return MDH_OK;
-   hipStream_t qs = nullptr;
-   if ((rc = inscatter_begin(r, &qs)) != MDH_OK) return rc;
-   float *base = nullptr;
-   size_t cap = 0;
-   if ((rc = rays_buffer(r, (size_t)n, qs, &base, &cap)) != MDH_OK) return rc;
-   InscatterRayArgs a;
-   a.n = n; a.march = march; a.step = step;
-   a.org = base; a.dir = base + 3 * cap; a.tmax = base + 6 * cap;
-   a.len = base + 9 * cap; a.steps = (int *)(base + 10 * cap); a.rgb = base + 11 * cap;
-   HIP_TRY(hipMemcpyAsync(base, org, (size_t)n * 12, hipMemcpyHostToDevice, qs));
-   HIP_TRY(hipMemcpyAsync(base + 3 * cap, dir, (size_t)n * 12, hipMemcpyHostToDevice, qs));
-   HIP_TRY(hipMemcpyAsync(base + 6 * cap, tmax, (size_t)n * 4, hipMemcpyHostToDevice, qs));
-   if ((rc = inscatter_run(r, GK_k_ray_inscatter, inscatter_ray_blocks(n), a, qs, qs)) != MDH_OK) return rc;
-   HIP_TRY(hipMemcpyAsync(rgb_out, a.rgb, (size_t)n * 12, hipMemcpyDeviceToHost, qs));
-   if (len_out) HIP_TRY(hipMemcpyAsync(len_out, a.len, (size_t)n * 4, hipMemcpyDeviceToHost, qs));
-   if (steps_out) HIP_TRY(hipMemcpyAsync(steps_out, a.steps, (size_t)n * 4, hipMemcpyDeviceToHost, qs));
+   RayStage st;
+   if ((rc = host_query_begin(r, n, st)) != MDH_OK) return rc;
+   const float *d_org = st.up(SLOT_ORG, org, 3), *d_dir = st.up(SLOT_DIR, dir, 3), *d_tmax = st.up(SLOT_TMAX, tmax, 1);
+   HIP_TRY(st.err);
+   const InscatterRayArgs a = inscatter_ray_args(n, march, step, d_org, d_dir, d_tmax, st.at(SLOT_RGB), st.at(SLOT_LEN), st.at<int>(SLOT_STEPS));
+   if ((rc = inscatter_rays_run(r, a, st.qs, st.qs)) != MDH_OK) return rc;
+   st.down(rgb_out, SLOT_RGB, 3); st.down(len_out, SLOT_LEN, 1); st.down(steps_out, SLOT_STEPS, 1);
+   HIP_TRY(st.err);
    return ray_query_wait(r);
 }
 extern "C" int32_t mdh_inscatter_rays_device(mdh_renderer *r, int32_t n, const float *org, const float *dir, const float *tmax, int32_t march, float step,
@@ -4399,27 +4267,19 @@ extern "C" int32_t mdh_inscatter_rays_device(mdh_renderer *r, int32_t n, const f
 {
    int rc = inscatter_check(r, n, org && dir && tmax && rgb_out, true, march, step);
    if (rc != MDH_OK) return rc;
-   HIP_TRY(hipSetDevice(r->device));
    const size_t w = (size_t)n * 4;
    const RayArray arrays[] = {{org, 3 * w, "origins"}, {dir, 3 * w, "directions"}, {tmax, w, "tmax"}, {rgb_out, 3 * w, "colours"},
                               {len_out, w, "lengths"}, {steps_out, w, "steps"}};
-   for (const RayArray &ra : arrays)
-      if ((rc = ray_array_check(r, ra)) != MDH_OK) return rc;
-   if (n == 0) return MDH_OK;
+   if ((rc = ray_arrays_check(r, arrays)) != MDH_OK || n == 0) return rc;
    hipStream_t qs = nullptr;
-   if ((rc = inscatter_begin(r, &qs)) != MDH_OK) return rc;
-   InscatterRayArgs a;
-   a.n = n; a.march = march; a.step = step;
-   a.org = org; a.dir = dir; a.tmax = tmax;
-   a.rgb = rgb_out; a.len = len_out; a.steps = steps_out;
-   return inscatter_run(r, GK_k_ray_inscatter, inscatter_ray_blocks(n), a, qs, (hipStream_t)stream);
+   if ((rc = device_query_begin(r, &qs)) != MDH_OK) return rc;
+   return inscatter_rays_run(r, inscatter_ray_args(n, march, step, org, dir, tmax, rgb_out, len_out, steps_out), qs, (hipStream_t)stream);
 }
 
 // ------------------------------------------------------------------ lighting a host's points
 // mdh_shade_points, mdh_shade_points_device: the light that arrives at n points of the host's -- pixel_color_probes from the
 // hit on (mode 0), direct light times occlusion (mode 2), or sample_irradiance alone (mode 3) -- through k_point_shade
-// (mdh_kernels.h).  Everything but the kernel and its arrays is mdh_shade_rays': shade_rays_begin, shade_query_run with its
-// fences and its timing, shade_scene_check, ray_array_check, d_rays for host arrays.  Nothing is edited.
+// (mdh_kernels.h), by the query path at a shaded ray's place among the frames, under shade_scene_check.  Nothing is edited.
 static int shade_points_check(const mdh_renderer *r, int32_t n, const float *pos, const float *normal, const float *view, const int32_t *material,
                               int32_t mode, int32_t tone_map, const float *rgb)
 {
@@ -4435,21 +4295,26 @@ static int shade_points_check(const mdh_renderer *r, int32_t n, const float *pos
       return seterr(MDH_E_STATE, "points are shaded with MDH_OPT_INDIRECT_SPECULAR 0 or 2, the latter without MDH_OPT_RADIANCE_MIPS");
    return shade_scene_check(r);
 }
-static PointShadeArgs shade_points_args(const mdh_renderer *r, int32_t n, int32_t tone_map)
+static PointShadeArgs shade_points_args(const mdh_renderer *r, int32_t n, int32_t tone_map, const float *pos, const float *normal, const float *view, const int32_t *material, float *rgb)
 {
    PointShadeArgs a;
    a.n = n; a.tone_map = tone_map ? 1 : 0; a.ao_steps = r->opt_ao; a.spec_mode = r->opt_spec; a.n_materials = MAX_MATERIALS; a.pad_ = 0;
-   a.pos = a.normal = a.view = nullptr; a.material = nullptr; a.rgb = nullptr;
+   a.pos = pos; a.normal = normal; a.view = view; a.material = material; a.rgb = rgb;
    return a;
 }
-static size_t shade_points_lds(const mdh_renderer *r, int32_t mode) { return mode == MDH_POINT_IRRADIANCE ? lds_bytes(r) : lds_bytes_screen_mode(r, mode); } // (mode 3 parks nothing)
+// k_point_shade with its own rows (mode 3 parks nothing), at a shaded ray's place among the frames
+static int shade_points_run(mdh_renderer *r, int32_t mode, const PointShadeArgs &a, hipStream_t qs, hipStream_t caller)
+{
+   const size_t lds = mode == MDH_POINT_IRRADIANCE ? lds_bytes(r) : lds_bytes_screen_mode(r, mode);
+   return query_kernel(r, table_kernel(r, GK_k_point_shade, mode), lane_blocks(a.n), lds, qs, caller, true, make_probes(r), a);
+}
 extern "C" int32_t mdh_shade_points(mdh_renderer *r, int32_t n, const float *pos, const float *normal, const float *view, const int32_t *material,
                                     int32_t mode, int32_t tone_map, float *rgb_out)
 {
    int rc = shade_points_check(r, n, pos, normal, view, material, mode, tone_map, rgb_out);
    if (rc != MDH_OK) return rc;
+   const bool full = mode != MDH_POINT_IRRADIANCE; // (mode 3 reads neither view directions nor material ids: not looked at)
    {
-      const bool full = mode != MDH_POINT_IRRADIANCE;
       bool ok = true;
       for (size_t i = 0; i < (size_t)n; ++i) // (the lanes' predicate)
          ok = ok && rs_shade_point_valid(pos[3 * i], pos[3 * i + 1], pos[3 * i + 2], normal[3 * i], normal[3 * i + 1], normal[3 * i + 2], full ? view[3 * i] : 0.0f,
@@ -4457,21 +4322,14 @@ extern "C" int32_t mdh_shade_points(mdh_renderer *r, int32_t n, const float *pos
       if (!ok) return seterr(MDH_E_INVALID, "a point is not finite, lies beyond 1024, has a normal or view component beyond 1, or names no material");
    }
    if (n == 0) return MDH_OK;
-   hipStream_t qs = nullptr;
-   if ((rc = shade_rays_begin(r, &qs)) != MDH_OK) return rc;
-   float *base = nullptr;
-   size_t cap = 0;
-   if ((rc = rays_buffer(r, (size_t)n, qs, &base, &cap)) != MDH_OK) return rc;
-   PointShadeArgs a = shade_points_args(r, n, tone_map);
-   a.pos = base; a.normal = base + 3 * cap; a.view = base + 6 * cap; a.material = (const int *)(base + 9 * cap); a.rgb = base + 11 * cap;
-   HIP_TRY(hipMemcpyAsync(base, pos, (size_t)n * 12, hipMemcpyHostToDevice, qs));
-   HIP_TRY(hipMemcpyAsync(base + 3 * cap, normal, (size_t)n * 12, hipMemcpyHostToDevice, qs));
-   if (mode != MDH_POINT_IRRADIANCE) {
-      HIP_TRY(hipMemcpyAsync(base + 6 * cap, view, (size_t)n * 12, hipMemcpyHostToDevice, qs));
-      HIP_TRY(hipMemcpyAsync(base + 9 * cap, material, (size_t)n * 4, hipMemcpyHostToDevice, qs));
-   }
-   if ((rc = shade_query_run(r, table_kernel(r, GK_k_point_shade, mode), shade_points_lds(r, mode), a, qs, qs)) != MDH_OK) return rc;
-   HIP_TRY(hipMemcpyAsync(rgb_out, a.rgb, (size_t)n * 12, hipMemcpyDeviceToHost, qs));
+   RayStage st;
+   if ((rc = host_query_begin(r, n, st)) != MDH_OK) return rc;
+   const float *d_pos = st.up(SLOT_ORG, pos, 3), *d_normal = st.up(SLOT_DIR, normal, 3), *d_view = st.up(SLOT_VIEW, full ? view : nullptr, 3);
+   const int32_t *d_material = st.up(SLOT_MATERIAL, full ? material : nullptr, 1);
+   HIP_TRY(st.err);
+   if ((rc = shade_points_run(r, mode, shade_points_args(r, n, tone_map, d_pos, d_normal, d_view, d_material, st.at(SLOT_RGB)), st.qs, st.qs)) != MDH_OK) return rc;
+   st.down(rgb_out, SLOT_RGB, 3);
+   HIP_TRY(st.err);
    return ray_query_wait(r);
 }
 extern "C" int32_t mdh_shade_points_device(mdh_renderer *r, int32_t n, const float *pos, const float *normal, const float *view, const int32_t *material,
@@ -4479,19 +4337,13 @@ extern "C" int32_t mdh_shade_points_device(mdh_renderer *r, int32_t n, const flo
 {
    int rc = shade_points_check(r, n, pos, normal, view, material, mode, tone_map, rgb_out);
    if (rc != MDH_OK) return rc;
-   HIP_TRY(hipSetDevice(r->device));
    const size_t w = (size_t)n * 4;
-   const bool full = mode != MDH_POINT_IRRADIANCE; // (mode 3 reads neither view directions nor material ids: not looked at)
-   const RayArray arrays[] = {{pos, 3 * w, "positions"}, {normal, 3 * w, "normals"}, {full ? view : nullptr, 3 * w, "view directions"},
-                              {full ? material : nullptr, w, "material ids"}, {rgb_out, 3 * w, "colours"}};
-   for (const RayArray &ra : arrays)
-      if ((rc = ray_array_check(r, ra)) != MDH_OK) return rc;
-   if (n == 0) return MDH_OK;
+   if (mode == MDH_POINT_IRRADIANCE) { view = nullptr; material = nullptr; } // (mode 3 reads neither: not looked at, not passed on)
+   const RayArray arrays[] = {{pos, 3 * w, "positions"}, {normal, 3 * w, "normals"}, {view, 3 * w, "view directions"}, {material, w, "material ids"}, {rgb_out, 3 * w, "colours"}};
+   if ((rc = ray_arrays_check(r, arrays)) != MDH_OK || n == 0) return rc;
    hipStream_t qs = nullptr;
-   if ((rc = shade_rays_begin(r, &qs)) != MDH_OK) return rc;
-   PointShadeArgs a = shade_points_args(r, n, tone_map);
-   a.pos = pos; a.normal = normal; a.view = full ? view : nullptr; a.material = full ? (const int *)material : nullptr; a.rgb = rgb_out;
-   return shade_query_run(r, table_kernel(r, GK_k_point_shade, mode), shade_points_lds(r, mode), a, qs, (hipStream_t)stream);
+   if ((rc = device_query_begin(r, &qs)) != MDH_OK) return rc;
+   return shade_points_run(r, mode, shade_points_args(r, n, tone_map, pos, normal, view, material, rgb_out), qs, (hipStream_t)stream);
 }
 // the material id of primitive `index` (the numbering of mdh_read_gbuffer and mdh_raycast: the kinds in their declared order,
 // each with its declared count) as the scene's table holds it now, pending edits included; -1 for -1 and for an index no
@@ -4543,16 +4395,12 @@ extern "C" int32_t mdh_camera_rays(mdh_renderer *r, int32_t width, int32_t heigh
 {
    int rc = camera_rays_check(r, width, height, org_out, dir_out);
    if (rc != MDH_OK) return rc;
-   HIP_TRY(hipSetDevice(r->device));
-   if (!r->query_stream) HIP_TRY(hipStreamCreateWithFlags(&r->query_stream, hipStreamNonBlocking));
-   hipStream_t qs = r->query_stream;
-   const size_t n = (size_t)width * height;
-   float *base = nullptr;
-   size_t cap = 0;
-   if ((rc = rays_buffer(r, n, qs, &base, &cap)) != MDH_OK) return rc;
-   if ((rc = camera_rays_launch(r, width, height, base, base + 3 * cap, qs)) != MDH_OK) return rc;
-   HIP_TRY(hipMemcpyAsync(org_out, base, n * 12, hipMemcpyDeviceToHost, qs));
-   HIP_TRY(hipMemcpyAsync(dir_out, base + 3 * cap, n * 12, hipMemcpyDeviceToHost, qs));
+   hipStream_t qs = nullptr;
+   RayStage st;
+   if ((rc = query_stream_get(r, &qs)) != MDH_OK || (rc = rays_stage(r, (size_t)width * height, qs, st)) != MDH_OK) return rc;
+   if ((rc = camera_rays_launch(r, width, height, st.at(SLOT_ORG), st.at(SLOT_DIR), qs)) != MDH_OK) return rc;
+   st.down(org_out, SLOT_ORG, 3); st.down(dir_out, SLOT_DIR, 3);
+   HIP_TRY(st.err);
    HIP_TRY(hipStreamSynchronize(qs));
    return MDH_OK;
 }
@@ -4560,13 +4408,12 @@ extern "C" int32_t mdh_camera_rays_device(mdh_renderer *r, int32_t width, int32_
 {
    int rc = camera_rays_check(r, width, height, org_out, dir_out);
    if (rc != MDH_OK) return rc;
-   HIP_TRY(hipSetDevice(r->device));
    const size_t bytes = (size_t)width * height * 12;
    const RayArray arrays[] = {{org_out, bytes, "origins"}, {dir_out, bytes, "directions"}};
-   for (const RayArray &ra : arrays)
-      if ((rc = ray_array_check(r, ra)) != MDH_OK) return rc;
+   if ((rc = ray_arrays_check(r, arrays)) != MDH_OK) return rc;
    return camera_rays_launch(r, width, height, org_out, dir_out, (hipStream_t)stream); // (on the caller's stream itself: ordered with it by being there)
 }
+
 
 // the hierarchy of the committed scene (pending edits are committed first): its nodes, leaves, depth and the length of the
 // always-evaluated list; all 0 while MDH_OPT_TRIANGLE_BVH is off or the scene declares no triangles

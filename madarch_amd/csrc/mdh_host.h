@@ -75,7 +75,8 @@ struct Event {
 };
 
 // Resources that are looked for as one ("is it there?" asks any of them): all created, in order, or, when one creation
-// fails, all empty again and that error returned.  Members have create() and release(): Event, Fence, RingUse, DevBuf::sized.
+// fails, all empty again and that error returned.  Members have create() and release(): Event, Fence, RingUse, QueryBridge,
+// DevBuf::sized.
 template <class... M>
 hipError_t create_all(M &&...m)
 {
@@ -84,6 +85,38 @@ hipError_t create_all(M &&...m)
    if (e != hipSuccess) (m.release(), ...);
    return e;
 }
+
+// "What does a query run between?"  A query's kernel runs on the query stream qs, for a caller whose arrays another stream
+// may hold, and -- where it reads what the frames write -- at its place among the frames on the main stream.  enter orders qs
+// behind the main stream (frame) and behind the caller's stream (in); leave orders both behind the kernel (out).  Without a
+// main stream only the caller's half is enqueued, and a caller that is qs itself needs none: no runtime call at all.
+// One set of events serves every query: an event is recorded again only after the wait on it was enqueued, and a wait that
+// is enqueued keeps the record it saw -- what every repeated call of one family has always relied on.
+struct QueryBridge {
+   Event frame, in, out;
+   hipError_t create() { return create_all(frame, in, out); }
+   void release() { frame.release(); in.release(); out.release(); }
+   hipError_t enter(hipStream_t qs, hipStream_t caller, const hipStream_t *main)
+   {
+      hipError_t e = main ? order(frame, *main, qs) : hipSuccess;
+      if (e == hipSuccess && caller != qs) e = order(in, caller, qs);
+      return e;
+   }
+   hipError_t leave(hipStream_t qs, hipStream_t caller, const hipStream_t *main)
+   {
+      if (!main && caller == qs) return hipSuccess;
+      hipError_t e = hipEventRecord(out.ev, qs);
+      if (e == hipSuccess && main) e = hipStreamWaitEvent(*main, out.ev, 0);
+      if (e == hipSuccess && caller != qs) e = hipStreamWaitEvent(caller, out.ev, 0);
+      return e;
+   }
+private:
+   static hipError_t order(Event &ev, hipStream_t first, hipStream_t then)
+   {
+      const hipError_t e = hipEventRecord(ev.ev, first);
+      return e == hipSuccess ? hipStreamWaitEvent(then, ev.ev, 0) : e;
+   }
+};
 
 // "Has this stream seen the latest write?"  The writer signals behind its write; a reader waits before its read, which
 // costs a runtime call only on a stream that has not been ordered behind the latest signal yet.

@@ -245,6 +245,66 @@ static void check_groups()
    }
 }
 
+// the queries' bridge: the logs are ray_stream_run's (no main stream) and shade_query_run's (with it) as they stood before
+// the bridge, written out by hand with in / out / frame for ev_rq_in, ev_sq_caller / ev_rq_out, ev_sq_done / ev_sq_frame
+static void check_query_bridge()
+{
+   const hipStream_t main = S0, qs = S3, caller = S1;
+   for (int k = 1; k <= 3; ++k) { // whichever creation fails, all three events are empty again
+      QueryBridge b;
+      g_fail_in = k;
+      CHECK(b.create() == hipErrorOutOfMemory && g_fail_in == 0);
+      CHECK(!b.frame.ev && !b.in.ev && !b.out.ev && g_live_ev.empty() && g_ev_created == g_ev_destroyed);
+   }
+   const long created = g_ev_created, destroyed = g_ev_destroyed;
+   size_t m = mark();
+   {
+      QueryBridge b;
+      DevBuf<unsigned> next;
+      CHECK(create_all(next.sized(1), b) == hipSuccess && b.create() == hipSuccess); // (as a member of a group, and idempotent)
+      CHECK(since(m) == (Log{"malloc", "event_create", "event_create", "event_create"}));
+      const hipEvent_t frame = b.frame.ev, in = b.in.ev, out = b.out.ev;
+      CHECK(frame != in && in != out && frame != out);
+      for (int round = 0; round < 2; ++round) { // a second call records the same three events again
+         // host arrays, no place among the frames (mdh_raycast): nothing at all
+         m = mark();
+         CHECK(b.enter(qs, qs, nullptr) == hipSuccess && b.leave(qs, qs, nullptr) == hipSuccess);
+         CHECK(since(m).empty());
+         // device arrays, no place among the frames (ray_stream_run)
+         m = mark();
+         CHECK(b.enter(qs, caller, nullptr) == hipSuccess);
+         CHECK(since(m) == (Log{name("record", in, caller), name("wait", qs, in)}));
+         m = mark();
+         CHECK(b.leave(qs, caller, nullptr) == hipSuccess);
+         CHECK(since(m) == (Log{name("record", out, qs), name("wait", caller, out)}));
+         // host arrays at a place among the frames (shade_query_run, caller == qs)
+         m = mark();
+         CHECK(b.enter(qs, qs, &main) == hipSuccess);
+         CHECK(since(m) == (Log{name("record", frame, main), name("wait", qs, frame)}));
+         m = mark();
+         CHECK(b.leave(qs, qs, &main) == hipSuccess);
+         CHECK(since(m) == (Log{name("record", out, qs), name("wait", main, out)}));
+         // device arrays at a place among the frames (shade_query_run, caller != qs)
+         m = mark();
+         CHECK(b.enter(qs, caller, &main) == hipSuccess);
+         CHECK(since(m) == (Log{name("record", frame, main), name("wait", qs, frame), name("record", in, caller), name("wait", qs, in)}));
+         m = mark();
+         CHECK(b.leave(qs, caller, &main) == hipSuccess);
+         CHECK(since(m) == (Log{name("record", out, qs), name("wait", main, out), name("wait", caller, out)}));
+         CHECK(b.frame.ev == frame && b.in.ev == in && b.out.ev == out);
+      }
+      // the default stream as the caller's is a stream like any other, not "none"
+      m = mark();
+      CHECK(b.enter(qs, nullptr, nullptr) == hipSuccess && b.leave(qs, nullptr, nullptr) == hipSuccess);
+      CHECK(since(m) == (Log{name("record", in, nullptr), name("wait", qs, in), name("record", out, qs), name("wait", nullptr, out)}));
+      m = mark();
+      b.release(); b.release();
+      CHECK(since(m) == (Log{name("event_destroy", frame), name("event_destroy", in), name("event_destroy", out)}));
+      CHECK(b.create() == hipSuccess); // ... and the destructor's turn
+   }
+   CHECK(g_live_ev.empty() && g_ev_created - created == 6 && g_ev_destroyed - destroyed == 6); // every event destroyed once
+}
+
 static void check_empty_owners()
 {
    const size_t m = mark();
@@ -254,8 +314,9 @@ static void check_empty_owners()
       Event e;
       Fence f;
       RingUse<4> u;
+      QueryBridge q;
       CHECK(b.release() == hipSuccess && h.release() == hipSuccess);
-      e.release(); f.release(); u.release(); u.forget(); f.mark_all_seen();
+      e.release(); f.release(); u.release(); u.forget(); f.mark_all_seen(); q.release();
    }
    CHECK(since(m).empty());
 }
@@ -268,6 +329,7 @@ int main()
    check_buf<false>("malloc", "free");
    check_buf<true>("host_malloc", "host_free");
    check_groups();
+   check_query_bridge();
    CHECK(g_live_mem.empty() && g_live_ev.empty());
    CHECK(g_mallocs > 0 && g_mallocs == g_frees && g_ev_created > 0 && g_ev_created == g_ev_destroyed);
    printf("host_sync_check: ok (%ld allocations, %ld events, %zu runtime calls)\n", g_mallocs, g_ev_created, g_log.size());

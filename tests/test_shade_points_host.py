@@ -143,7 +143,7 @@ def test_the_kernel_and_the_host_call_the_checked_predicate():
     assert re.search(r"\brs_shade_point_valid\s*\(", header)
     assert re.search(r"\brs_shade_point_valid\s*\(", kernels) and re.search(r"\brs_shade_point_valid\s*\(", api)
     points = api[api.index("static int shade_points_check("):api.index('extern "C" int32_t mdh_primitive_material')]
-    assert "shade_scene_check(r)" in points and points.count("ray_array_check(") == 1 and "settle_bump" not in points
+    assert "shade_scene_check(r)" in points and points.count("ray_arrays_check(") == 1 and "settle_bump" not in points
     # the kernel is k_point_shade, in the seven general variants and three modes, named last: nothing older moves
     body = api[api.index("static const void *kernel_ptr(const PassKernel &k)\n{"):]
     assert re.search(r"MDH_PT\(0\) MDH_PT\(1\) MDH_PT\(9\) MDH_PT\(64\) MDH_PT\(65\) MDH_PT\(73\) MDH_PT\(192\)\s*return nullptr;", body)
