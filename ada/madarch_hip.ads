@@ -334,6 +334,28 @@ package Madarch_HIP is
       Dist_Out, Index_Out, Normal_Out : System.Address; Stream : System.Address) return Status
      with Import, Convention => C, External_Name => "mdh_contacts_device";
 
+   --  The scene's surface as a mesh: surface nets over a grid of Cells (3 ints) cubic cells of
+   --  Spacing from Origin (3 floats) at level Iso (madarch_hip.h, mdh_surface_mesh, has the
+   --  definition).  Every output but Counts_Out (2 ints: vertices and quads found) may be
+   --  Null_Address with its capacity 0; N_Kinds as for Contacts
+   Surface_Max_Corners : constant := 2 ** 24;
+
+   function Surface_Mesh
+     (R : Handle; Origin : System.Address; Spacing : C_float; Cells : System.Address;
+      Iso : C_float; Kind_Ixs : System.Address; N_Kinds : int;
+      Vertex_Capacity, Quad_Capacity : int;
+      Positions_Out, Normals_Out, Index_Out, Quads_Out, Field_Out, Counts_Out : System.Address)
+      return Status
+     with Import, Convention => C, External_Name => "mdh_surface_mesh";
+
+   function Surface_Mesh_Device
+     (R : Handle; Origin : System.Address; Spacing : C_float; Cells : System.Address;
+      Iso : C_float; Kind_Ixs : System.Address; N_Kinds : int;
+      Vertex_Capacity, Quad_Capacity : int;
+      Positions_Out, Normals_Out, Index_Out, Quads_Out, Field_Out, Counts_Out : System.Address;
+      Stream : System.Address) return Status
+     with Import, Convention => C, External_Name => "mdh_surface_mesh_device";
+
    --  One frame on the N GPUs of a node, one process per GPU (madarch_hip.h, mdh_comm_*):
    --  every process creates its Renderer on its own device, rank 0 makes a 128-byte id and
    --  hands it to the others (a file, an environment variable), all call Comm_Init, and

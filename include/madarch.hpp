@@ -541,6 +541,31 @@ class Renderer {
    {
       Check(mdh_contacts_device(h_.get(), N, Centres, Radii, Kinds.empty() ? nullptr : Kinds.data(), (int32_t)Kinds.size(), Dist, Index, Normal, Stream));
    }
+   // ---- the scene's surface as a mesh: surface nets over a grid (madarch_hip.h: mdh_surface_mesh has the definition).  Kinds as
+   // for Contacts.  Surface_Mesh counts, allocates and calls again; the _Device form takes arrays with their capacities, and
+   // Counts (2 int32 the device addresses) holds what was found, whatever the capacities
+   struct Mesh {
+      std::vector<float> Positions, Normals; // 3 a vertex
+      std::vector<int32_t> Index, Quads;     // one a vertex, 4 a quad
+   };
+   Mesh Surface_Mesh(const float (&Origin)[3], float Spacing, const int32_t (&Cells)[3], float Iso = 0.0f, const std::vector<int32_t> &Kinds = {}) const
+   {
+      const int32_t *kinds = Kinds.empty() ? nullptr : Kinds.data();
+      int32_t counts[2] = {0, 0};
+      Check(mdh_surface_mesh(h_.get(), Origin, Spacing, Cells, Iso, kinds, (int32_t)Kinds.size(), 0, 0, nullptr, nullptr, nullptr, nullptr, nullptr, counts));
+      Mesh m;
+      const int32_t nv = counts[0], nq = counts[1];
+      m.Positions.resize(3 * (size_t)nv); m.Normals.resize(3 * (size_t)nv); m.Index.resize((size_t)nv); m.Quads.resize(4 * (size_t)nq);
+      Check(mdh_surface_mesh(h_.get(), Origin, Spacing, Cells, Iso, kinds, (int32_t)Kinds.size(), nv, nq, nv ? m.Positions.data() : nullptr, nv ? m.Normals.data() : nullptr,
+                             nv ? m.Index.data() : nullptr, nq ? m.Quads.data() : nullptr, nullptr, counts));
+      return m;
+   }
+   void Surface_Mesh_Device(const float (&Origin)[3], float Spacing, const int32_t (&Cells)[3], float Iso, const std::vector<int32_t> &Kinds, int32_t Vertex_Capacity,
+                            int32_t Quad_Capacity, float *Positions, float *Normals, int32_t *Index, int32_t *Quads, float *Field, int32_t *Counts, void *Stream = nullptr) const
+   {
+      Check(mdh_surface_mesh_device(h_.get(), Origin, Spacing, Cells, Iso, Kinds.empty() ? nullptr : Kinds.data(), (int32_t)Kinds.size(), Vertex_Capacity, Quad_Capacity,
+                                    Positions, Normals, Index, Quads, Field, Counts, Stream));
+   }
    void Update_Partitioning(Partitioning_Update_Method Method = GPU_Fast) const { Check(mdh_update_partitioning(h_.get(), (int32_t)Method)); } // renderers.adb:757-775
    // ---- headless additions
    std::vector<float> Read_Framebuffer() const // replaces Swap_Buffers: H*W*3 floats, row 0 = top

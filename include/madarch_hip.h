@@ -847,6 +847,68 @@ int32_t mdh_spherecast_device(mdh_renderer *r, int32_t n, const float *org_xyz, 
 int32_t mdh_contacts_device(mdh_renderer *r, int32_t n, const float *centre_xyz, const float *radius, const int32_t *kind_ixs,
                             int32_t n_kinds, float *dist_out, int32_t *index_out, float *normal_xyz_out, void *stream);
 
+/* MESHING THE SCENE'S SURFACE, for a host's own rasteriser, physics, wireframe, OBJ export or baked distance volume: naive
+ * surface nets over a regular grid, deterministic in values and in order (no atomics on the device).
+ *
+ * The grid: origin[3], cubic cells of `spacing` h > 0, cells[3] = (cx, cy, cz) cells, each >= 1; iso is the level.
+ * D: n_kinds = 0 -- the whole scene as every pass sees it, through the space partition or the triangle BVH; n_kinds > 0 --
+ * the exact scan of the listed kinds with the shaders' division, exactly as mdh_contacts takes kind_ixs and n_kinds (a host
+ * lists Sphere and Box to mesh the objects without the room's walls).
+ *
+ * THE DEFINITION.  Every operation is one binary32 operation, unfused.
+ *  1. Corner (i, j, k), 0 <= i <= cx and so on, lies at p_x = origin_x + (float) i * h -- one product, then one sum --
+ *     likewise y and z.  Its value is v = fl (D (p) - iso): the bits mdh_contacts gives as dist at p with radius iso.  A
+ *     corner is INSIDE iff v < 0; zero and NaN are outside.
+ *  2. Cell (i, j, k), 0 <= i < cx and so on, has the corners c = 0 .. 7: bit 0 of c is the x offset, bit 1 the y offset,
+ *     bit 2 the z offset.  A cell is ACTIVE iff some of its corners are inside and some are outside.
+ *  3. The vertex of an active cell comes from its 12 edges in a fixed order: the outer loop over the axes a = x, y, z, the
+ *     inner loop over e = 0 .. 3, where the two other axes in ascending order take the offsets e & 1 and e >> 1.  An edge
+ *     CROSSES iff its endpoints v0 (offset 0 along a) and v1 differ in insideness; then t = v0 / (v0 - v1) and its local
+ *     point q has t on axis a and the edge's offsets 0 or 1 on the other two.  s = s + q in that order from 0 over the m
+ *     crossing edges, u = s / (float) m per component, and the world position is x = origin_x + ((float) i + u_x) * h: a
+ *     sum, a product, a sum.
+ *  4. Vertices are numbered by ascending cell id (k cy + j) cx + i.
+ *  5. A vertex carries `index` and `normal`: the closest primitive at the vertex and its normal there, the bits
+ *     mdh_contacts returns at that point for the same kind list.
+ *  6. The grid edge along axis a from corner (i, j, k) emits a quad iff its a-coordinate is < cells[a], both other
+ *     coordinates lie in 1 .. cells - 1 (all four cells round the edge exist) and its endpoints differ in insideness.
+ *  7. With b = (a + 1) mod 3 and c = (a + 2) mod 3 the quad's four vertex ids are those of the cells at (b, c) offsets
+ *     (-1, -1), (0, -1), (0, 0), (-1, 0) when the lower endpoint is inside -- the geometric normal then points along +a,
+ *     out of the solid -- and in the reverse order otherwise.
+ *  8. Quads are ordered by ascending key cornerid * 3 + a, cornerid = (k (cy + 1) + j) (cx + 1) + i.
+ *
+ * OUTPUTS, all optional but counts_out: positions_out and normals_out (3 floats a vertex), index_out (one int32 a vertex),
+ * quads_out (4 int32 a quad), field_out ((cx + 1) (cy + 1) (cz + 1) corner values, x fastest: a baked distance volume),
+ * counts_out[2] = the vertices and the quads FOUND, whatever the capacities.  The call writes the first min (found, capacity)
+ * entries of each array and nothing behind them, and returns MDH_OK; a quad names the vertices by the ids they were found
+ * with.  Capacity 0 with null arrays is a pure count.  With vertex_capacity > 0 at least one of the three vertex arrays is
+ * given, with quad_capacity > 0 quads_out is; with capacity 0 none of them is.
+ *
+ * The contract is the ray queries' (mdh_raycast above): the query stream beside the frames in flight, pending
+ * mdh_set_primitive, mdh_add_primitive and mdh_update_partitioning seen, nothing edited -- the probe-settle run and both
+ * replays go on --, mdh_ray_query_time under MDH_OPT_TIMING from the first launch to the last.  Every refusal happens before
+ * anything is launched:
+ *   MDH_E_INVALID  a null renderer, origin, cells or counts_out; a cell count < 1; a non-finite origin, spacing or iso, or
+ *                  spacing <= 0; |iso| above the scene's max_dist; a grid corner outside +-1024; a grid of more than
+ *                  MDH_SURFACE_MAX_CORNERS corners; a negative capacity; an array with capacity 0, or a capacity > 0
+ *                  without its array; n_kinds outside 0 .. MDH_MAX_KINDS or a kind index outside the scene's kinds
+ *   MDH_E_STATE    a scene with a user-defined kind */
+/* the grid's cap: 2^24 corners.  Every id the kernels form fits an int32 with room to spare (the largest, a quad's key
+ * cornerid * 3 + 2, stays below 2^26), and the renderer's scratch -- a float a corner, an int32 a cell, two int32 per 256
+ * corners -- stays below 129 MiB.  256^3 corners, a 255^3 grid of cells, is the largest cube. */
+#define MDH_SURFACE_MAX_CORNERS 16777216
+int32_t mdh_surface_mesh(mdh_renderer *r, const float *origin, float spacing, const int32_t *cells, float iso,
+                         const int32_t *kind_ixs, int32_t n_kinds, int32_t vertex_capacity, int32_t quad_capacity,
+                         float *positions_out, float *normals_out, int32_t *index_out, int32_t *quads_out, float *field_out,
+                         int32_t *counts_out);
+/* The same call for arrays the device addresses (origin, cells and kind_ixs stay the host's), under the contract of
+ * mdh_raycast_device: asynchronous and ordered with `stream`, mdh_ray_query_wait is the host's wait, and where every array
+ * lives and ends is checked before anything is launched (counts_out: 2 int32 the device addresses).  Nothing waits. */
+int32_t mdh_surface_mesh_device(mdh_renderer *r, const float *origin, float spacing, const int32_t *cells, float iso,
+                                const int32_t *kind_ixs, int32_t n_kinds, int32_t vertex_capacity, int32_t quad_capacity,
+                                float *positions_out, float *normals_out, int32_t *index_out, int32_t *quads_out,
+                                float *field_out, int32_t *counts_out, void *stream);
+
 /* accumulated HIP-event time and launch count of one pass (MDH_OPT_TIMING) */
 int32_t mdh_pass_time(mdh_renderer *r, int32_t pass, double *total_ms, int64_t *launches);
 /* MDH_OPT_RADIANCE_REPLAY: the radiance passes launched since mdh_create that marched their rays (`plain`), marched them

@@ -198,7 +198,12 @@ HIP_ONLY_ABI = {
     "spherecast_device": (_I, [_P, _I, _P, _P, _P, _P, _P, _I, _P, _P, _P, _P, _P, _P, _P]),
     "contacts": (_I, [_P, _I, _P, _P, _P, _I, _P, _P, _P]),
     "contacts_device": (_I, [_P, _I, _P, _P, _P, _I, _P, _P, _P, _P]),
+    # the scene's surface as a mesh, surface nets over a grid: (r, origin[3], spacing, cells[3], iso, kind_ixs, n_kinds (0: the
+    # whole scene), vertex_capacity, quad_capacity, positions, normals, index, quads, field, counts[2][, stream])
+    "surface_mesh": (_I, [_P, _P, _F, _P, _F, _P, _I, _I, _I, _P, _P, _P, _P, _P, _P]),
+    "surface_mesh_device": (_I, [_P, _P, _F, _P, _F, _P, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P]),
 }
+SURFACE_MAX_CORNERS = 1 << 24  # MDH_SURFACE_MAX_CORNERS
 
 
 class Binding:

@@ -344,6 +344,10 @@ struct mdh_renderer {
    // the device-array ray queries (mdh_raycast_device, ..): the counter k_ray_stream's wavefronts take their rays from (one:
    // the launches follow one another on the query stream)
    DevBuf<unsigned> d_rq_next;
+   // the surface mesher (mdh_surface_mesh, ..): the corners' values, the cells' vertices and the workgroups' counts of the
+   // largest grid so far, and the host form's results of the largest capacities so far; used on the query stream alone
+   DevBuf<float> d_surf_field;
+   DevBuf<int> d_surf_map, d_surf_wg, d_surf_out;
    QueryBridge bridge; // every query's events to the caller's stream and to the frames (query_enqueue; created by the first that needs one)
    int opt_rq_refill = MDH_RAY_STREAM_REFILL_DEFAULT; // MDH_OPT_RAY_STREAM_REFILL
    int opt_rq_groups = 0;                             // MDH_OPT_RAY_STREAM_GROUPS (0: as many workgroups as are resident)
@@ -1793,7 +1797,7 @@ template <typename Args> static int jit_launch(hipFunction_t f, int blocks, int 
 // frames in flight share their CUs' instruction caches (measured: the same kernels at other addresses, each as fast by itself,
 // the headline with frames in flight 0.5 % slower).  The kernels of global residency (MDH_PF_GTAB, mdh_device.h: Geo) come
 // last there: behind everything else they move nothing.
-enum { GK_k_visibility, GK_k_scat_march, GK_k_scattering, GK_k_radiance, GK_k_screen, GK_k_partition_build, GK_k_eval_distance, GK_k_diag_segments, GK_k_ray_query, GK_k_ray_stream, GK_k_ray_shade, GK_k_camera_rays, GK_k_point_shade, GK_k_path_trace, GK_k_point_inscatter, GK_k_ray_inscatter, GK_k_listed };
+enum { GK_k_visibility, GK_k_scat_march, GK_k_scattering, GK_k_radiance, GK_k_screen, GK_k_partition_build, GK_k_eval_distance, GK_k_diag_segments, GK_k_ray_query, GK_k_ray_stream, GK_k_ray_shade, GK_k_camera_rays, GK_k_point_shade, GK_k_path_trace, GK_k_point_inscatter, GK_k_ray_inscatter, GK_k_listed, GK_k_surface_field, GK_k_surface_vertices, GK_k_surface_field_listed, GK_k_surface_vertices_listed };
 // WHICH KERNEL A PASS RUNS ("One place that picks a pass's kernel"): every template argument of the
 // pass's kernel, computed once by pick_kernel; kernel_name and kernel_ptr turn the same description into the name hiprtc
 // instantiates and into the kernel of this library.
@@ -1830,7 +1834,7 @@ static const void *table_kernel(const mdh_renderer *r, int family, int what = 0)
    // the ray queries march as the passes do: through the space partition (its border as a variant of its own) or the triangle
    // BVH where the scene has one -- the general variants, whose bits the census variants share (pick_kernel)
    if (family == GK_k_ray_query || family == GK_k_ray_stream || family == GK_k_ray_shade || family == GK_k_point_shade || family == GK_k_path_trace ||
-       family == GK_k_point_inscatter || family == GK_k_ray_inscatter) {
+       family == GK_k_point_inscatter || family == GK_k_ray_inscatter || family == GK_k_surface_field || family == GK_k_surface_vertices) {
       k.what = what;
       if (family == GK_k_ray_shade || family == GK_k_point_shade) { k.what = 0; k.mode = what; } // (mdh_shade_rays, mdh_shade_points: `what` is the call's mode)
       if (r->part.enable) k.pf |= MDH_PF_PART | (r->part.border_behavior != 0 ? MDH_PF_FALLBACK : 0);
@@ -4027,6 +4031,139 @@ extern "C" int32_t mdh_contacts_device(mdh_renderer *r, int32_t n, const float *
    return ray_query_device(r, MDH_RQ_CONTACT, arrays, a, kind_ixs, n_kinds, false, stream);
 }
 
+// ------------------------------------------------------------------ meshing the scene's surface
+// mdh_surface_mesh, mdh_surface_mesh_device: surface nets over a regular grid of the scene's distance (mdh_surface.h has the
+// definition and the five kernels), by the query path -- the query stream, the committed scene, one bridge enter / leave and
+// one table acquire / release round all launches, whose first and last mdh_ray_query_time's events enclose.  No settle_bump:
+// nothing is edited.  The scratch is the renderer's and grows on demand; only the query stream uses it, and is drained
+// before a buffer is replaced.
+struct SurfaceGrid { int nc, ncell, nblocks; }; // corners, cells, workgroups of k_surface_count
+static int surface_check(const mdh_renderer *r, const float *origin, float h, const int32_t *cells, float iso, const int32_t *kind_ixs, int32_t n_kinds, int32_t vcap,
+                         int32_t qcap, const void *pos, const void *nrm, const void *idx, const void *quads, const void *counts, SurfaceGrid &g)
+{
+   if (!r) return seterr(MDH_E_INVALID, "null renderer");
+   if (!origin || !cells || !counts) return seterr(MDH_E_INVALID, "bad argument");
+   if (has_custom_kinds(r)) return seterr(MDH_E_STATE, "ray queries answer scenes of built-in kinds only");
+   int rc = sweep_kinds_check(r, kind_ixs, n_kinds);
+   if (rc != MDH_OK) return rc;
+   if (cells[0] < 1 || cells[1] < 1 || cells[2] < 1) return seterr(MDH_E_INVALID, "a grid has at least one cell along every axis");
+   if (!all_finite(origin, 3) || !rs_finite(h) || !rs_finite(iso) || !(h > 0.0f)) return seterr(MDH_E_INVALID, "the grid's origin, spacing or level is not finite, or the spacing is not positive");
+   if (std::fabs(iso) > r->max_dist) return seterr(MDH_E_INVALID, "the level exceeds the scene's max_dist");
+   long long nc = 1;
+   for (int c = 0; c < 3; ++c) {
+      if (cells[c] >= MDH_SURFACE_MAX_CORNERS) return seterr(MDH_E_INVALID, "the grid has more than MDH_SURFACE_MAX_CORNERS corners");
+      nc *= (long long)cells[c] + 1; // (below 2^72 / 2^48 / 2^24 in turn: no overflow)
+      if (nc > MDH_SURFACE_MAX_CORNERS) return seterr(MDH_E_INVALID, "the grid has more than MDH_SURFACE_MAX_CORNERS corners");
+      const float far = origin[c] + (float)cells[c] * h; // (the last corner as the lanes compute it; the corners between lie between)
+      if (!(std::fabs(origin[c]) <= 1024.0f) || !(std::fabs(far) <= 1024.0f)) return seterr(MDH_E_INVALID, "a grid corner lies outside +-1024");
+   }
+   if (vcap < 0 || qcap < 0) return seterr(MDH_E_INVALID, "a negative capacity");
+   if (vcap == 0 ? (pos || nrm || idx) : (!pos && !nrm && !idx)) return seterr(MDH_E_INVALID, "vertex arrays and vertex_capacity: both or neither");
+   if ((qcap == 0) != (quads == nullptr)) return seterr(MDH_E_INVALID, "quads_out and quad_capacity: both or neither");
+   g.nc = (int)nc;
+   g.ncell = cells[0] * cells[1] * cells[2];
+   g.nblocks = (g.nc + MDH_BLOCK - 1) / MDH_BLOCK;
+   return MDH_OK;
+}
+// room for n elements in a buffer only the query stream uses
+template <class T> static int surface_room(DevBuf<T> &b, size_t n, hipStream_t qs)
+{
+   if (n <= b.cap) return MDH_OK;
+   if (b.ptr) HIP_TRY(hipStreamSynchronize(qs));
+   HIP_TRY(b.grow(n));
+   return MDH_OK;
+}
+// the launches for outputs the device addresses (a: the grid, the capacities and the outputs are filled in)
+static int surface_enqueue(mdh_renderer *r, SurfaceArgs a, const SurfaceGrid &g, const int32_t *kind_ixs, int32_t n_kinds, hipStream_t qs, hipStream_t caller)
+{
+   int rc;
+   if ((rc = surface_room(r->d_surf_field, (size_t)g.nc, qs)) != MDH_OK || (rc = surface_room(r->d_surf_map, (size_t)g.ncell, qs)) != MDH_OK ||
+       (rc = surface_room(r->d_surf_wg, 2 * (size_t)g.nblocks, qs)) != MDH_OK)
+      return rc;
+   a.nblocks = g.nblocks;
+   a.field = r->d_surf_field.ptr; a.map = r->d_surf_map.ptr; a.wg = r->d_surf_wg.ptr;
+   ListedArgs la;
+   la.q = RayQueryArgs();
+   la.n_kinds = n_kinds;
+   for (int i = 0; i < MDH_MAX_KINDS; ++i) { la.kinds[i] = i < n_kinds ? kind_ixs[i] : 0; la.host_count[i] = r->host_count[i]; }
+   const bool listed = n_kinds > 0;
+   const void *field = table_kernel(r, listed ? GK_k_surface_field_listed : GK_k_surface_field);
+   const void *vertices = table_kernel(r, listed ? GK_k_surface_vertices_listed : GK_k_surface_vertices);
+   if (!field || !vertices) return seterr(MDH_E_INVALID, "no kernel built for this variant");
+   const size_t lds = lds_bytes(r);
+   const dim3 block(MDH_BLOCK);
+   const long waves = (long)((a.cx + 4) / 4) * ((a.cy + 4) / 4) * ((a.cz + 4) / 4); // 4 x 4 x 4 blocks of the cx + 1, .. corners
+   const unsigned field_groups = (unsigned)((waves + MDH_BLOCK / 64 - 1) / (MDH_BLOCK / 64)), cell_groups = (unsigned)((g.ncell + MDH_BLOCK - 1) / MDH_BLOCK);
+   return query_enqueue(r, qs, caller, false, [&] {
+      int rc = listed ? launch_kernel_ptr(field, dim3(field_groups), block, lds, qs, r->ks, a, la) : launch_kernel_ptr(field, dim3(field_groups), block, lds, qs, r->ks, a);
+      if (rc == MDH_OK) rc = launch_kernel_ptr((const void *)k_surface_count, dim3((unsigned)g.nblocks), block, 0, qs, a);
+      if (rc == MDH_OK) rc = launch_kernel_ptr((const void *)k_surface_scan, dim3(1), block, 0, qs, a);
+      if (rc == MDH_OK && (a.vcap > 0 || a.qcap > 0)) // (the quads read the cells' vertices)
+         rc = listed ? launch_kernel_ptr(vertices, dim3(cell_groups), block, lds, qs, r->ks, a, la) : launch_kernel_ptr(vertices, dim3(cell_groups), block, lds, qs, r->ks, a);
+      if (rc == MDH_OK && a.qcap > 0) rc = launch_kernel_ptr((const void *)k_surface_quads, dim3((unsigned)g.nblocks), block, 0, qs, a);
+      return rc;
+   });
+}
+static SurfaceArgs surface_args(const float *origin, float h, const int32_t *cells, float iso, int32_t vcap, int32_t qcap)
+{
+   SurfaceArgs a;
+   memset(&a, 0, sizeof a);
+   a.ox = origin[0]; a.oy = origin[1]; a.oz = origin[2]; a.h = h; a.iso = iso;
+   a.cx = cells[0]; a.cy = cells[1]; a.cz = cells[2];
+   a.vcap = vcap; a.qcap = qcap;
+   return a;
+}
+extern "C" int32_t mdh_surface_mesh(mdh_renderer *r, const float *origin, float spacing, const int32_t *cells, float iso, const int32_t *kind_ixs, int32_t n_kinds,
+                                    int32_t vcap, int32_t qcap, float *pos_out, float *normal_out, int32_t *index_out, int32_t *quads_out, float *field_out, int32_t *counts_out)
+{
+   SurfaceGrid g;
+   int rc = surface_check(r, origin, spacing, cells, iso, kind_ixs, n_kinds, vcap, qcap, pos_out, normal_out, index_out, quads_out, counts_out, g);
+   if (rc != MDH_OK) return rc;
+   hipStream_t qs = nullptr;
+   if ((rc = query_stream_get(r, &qs)) != MDH_OK || (rc = ensure_committed(r, qs)) != MDH_OK) return rc;
+   // the results' places in d_surf_out: the counts, then what was asked for
+   const size_t v = (size_t)vcap, q = (size_t)qcap;
+   const size_t at_pos = 2, at_nrm = at_pos + (pos_out ? 3 * v : 0), at_idx = at_nrm + (normal_out ? 3 * v : 0), at_quads = at_idx + (index_out ? v : 0), words = at_quads + 4 * q;
+   if ((rc = surface_room(r->d_surf_out, words, qs)) != MDH_OK) return rc;
+   int *out = r->d_surf_out.ptr;
+   SurfaceArgs a = surface_args(origin, spacing, cells, iso, vcap, qcap);
+   a.counts = out;
+   a.positions = pos_out ? (float *)(out + at_pos) : nullptr;
+   a.normals = normal_out ? (float *)(out + at_nrm) : nullptr;
+   a.index = index_out ? out + at_idx : nullptr;
+   a.quads = quads_out ? out + at_quads : nullptr;
+   if ((rc = surface_enqueue(r, a, g, kind_ixs, n_kinds, qs, qs)) != MDH_OK) return rc;
+   int32_t found[2] = {0, 0};
+   HIP_TRY(hipMemcpyAsync(found, out, sizeof found, hipMemcpyDeviceToHost, qs));
+   HIP_TRY(hipStreamSynchronize(qs));
+   const size_t nv = (size_t)std::min(found[0], vcap), nq = (size_t)std::min(found[1], qcap); // (nothing behind them is written)
+   if (pos_out && nv) HIP_TRY(hipMemcpyAsync(pos_out, a.positions, nv * 12, hipMemcpyDeviceToHost, qs));
+   if (normal_out && nv) HIP_TRY(hipMemcpyAsync(normal_out, a.normals, nv * 12, hipMemcpyDeviceToHost, qs));
+   if (index_out && nv) HIP_TRY(hipMemcpyAsync(index_out, a.index, nv * 4, hipMemcpyDeviceToHost, qs));
+   if (quads_out && nq) HIP_TRY(hipMemcpyAsync(quads_out, a.quads, nq * 16, hipMemcpyDeviceToHost, qs));
+   if (field_out) HIP_TRY(hipMemcpyAsync(field_out, r->d_surf_field.ptr, (size_t)g.nc * 4, hipMemcpyDeviceToHost, qs));
+   if ((rc = ray_query_wait(r)) != MDH_OK) return rc;
+   counts_out[0] = found[0]; counts_out[1] = found[1];
+   return MDH_OK;
+}
+extern "C" int32_t mdh_surface_mesh_device(mdh_renderer *r, const float *origin, float spacing, const int32_t *cells, float iso, const int32_t *kind_ixs, int32_t n_kinds,
+                                           int32_t vcap, int32_t qcap, float *pos_out, float *normal_out, int32_t *index_out, int32_t *quads_out, float *field_out,
+                                           int32_t *counts_out, void *stream)
+{
+   SurfaceGrid g;
+   int rc = surface_check(r, origin, spacing, cells, iso, kind_ixs, n_kinds, vcap, qcap, pos_out, normal_out, index_out, quads_out, counts_out, g);
+   if (rc != MDH_OK) return rc;
+   const size_t v = (size_t)vcap * 4, q = (size_t)qcap * 4;
+   const RayArray arrays[] = {{pos_out, 3 * v, "positions"}, {normal_out, 3 * v, "normals"}, {index_out, v, "index"}, {quads_out, 4 * q, "quads"},
+                              {field_out, (size_t)g.nc * 4, "field"}, {counts_out, 8, "counts"}};
+   if ((rc = ray_arrays_check(r, arrays)) != MDH_OK) return rc;
+   hipStream_t qs = nullptr;
+   if ((rc = device_query_begin(r, &qs)) != MDH_OK) return rc;
+   SurfaceArgs a = surface_args(origin, spacing, cells, iso, vcap, qcap);
+   a.positions = pos_out; a.normals = normal_out; a.index = index_out; a.quads = quads_out; a.field_out = field_out; a.counts = counts_out;
+   return surface_enqueue(r, a, g, kind_ixs, n_kinds, qs, (hipStream_t)stream);
+}
+
 // ------------------------------------------------------------------ shading a host's rays
 // mdh_shade_rays, mdh_shade_rays_device: pixel_color_probes (render_probes.glsl:246-291) along n rays of the host's, through
 // the pixel program the screen pass runs (k_ray_shade, mdh_kernels.h), by the query path.  No settle_bump: nothing is edited.
@@ -4684,8 +4821,10 @@ extern "C" int32_t mdh_diag_waves(unsigned long long *out, int32_t n_waves)
 static const void *kernel_ptr_path(const PassKernel &k);
 static const void *kernel_ptr_inscatter(const PassKernel &k);
 static const void *kernel_ptr_sweep(const PassKernel &k);
+static const void *kernel_ptr_surface(const PassKernel &k);
 static const void *kernel_ptr(const PassKernel &k)
 {
+   if (k.family >= GK_k_surface_field && k.family <= GK_k_surface_vertices_listed) return kernel_ptr_surface(k);
    if (k.family == GK_k_listed || ((k.family == GK_k_ray_query || k.family == GK_k_ray_stream) && k.what >= MDH_RQ_SPHERECAST)) return kernel_ptr_sweep(k);
    if (k.family == GK_k_path_trace) return kernel_ptr_path(k); // (the newer families, named behind this function)
    if (k.family == GK_k_point_inscatter || k.family == GK_k_ray_inscatter) return kernel_ptr_inscatter(k);
@@ -4791,5 +4930,18 @@ static const void *kernel_ptr_sweep(const PassKernel &k)
       if (k.pf == 0) return k.what == MDH_RQ_SPHERECAST ? (const void *)k_listed<false, MDH_RQ_SPHERECAST> : (const void *)k_listed<false, MDH_RQ_CONTACT>;
       if (k.pf == MDH_PF_GTAB) return k.what == MDH_RQ_SPHERECAST ? (const void *)k_listed<true, MDH_RQ_SPHERECAST> : (const void *)k_listed<true, MDH_RQ_CONTACT>;
    }
+   return nullptr;
+}
+// ... and behind that the surface mesher (mdh_surface_mesh, mdh_surface_mesh_device; mdh_surface.h): the field and the vertices
+// in the queries' variants and over listed kinds, first named here; its three kernels that read no scene have no variants
+static const void *kernel_ptr_surface(const PassKernel &k)
+{
+#define MDH_SF(PF) if (k.pf == (PF)) { \
+      if (k.family == GK_k_surface_field) return (const void *)k_surface_field<PF>; \
+      if (k.family == GK_k_surface_vertices) return (const void *)k_surface_vertices<PF>; }
+   MDH_SF(0) MDH_SF(1) MDH_SF(9) MDH_SF(64) MDH_SF(65) MDH_SF(73) MDH_SF(192)
+#undef MDH_SF
+   if (k.family == GK_k_surface_field_listed) return k.pf == 0 ? (const void *)k_surface_field_listed<false> : k.pf == MDH_PF_GTAB ? (const void *)k_surface_field_listed<true> : nullptr;
+   if (k.family == GK_k_surface_vertices_listed) return k.pf == 0 ? (const void *)k_surface_vertices_listed<false> : k.pf == MDH_PF_GTAB ? (const void *)k_surface_vertices_listed<true> : nullptr;
    return nullptr;
 }

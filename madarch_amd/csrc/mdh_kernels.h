@@ -2415,6 +2415,12 @@ template <bool GTAB, int WHAT> __global__ __launch_bounds__(MDH_BLOCK) void k_li
    if (a.normal && index >= 0) primitive_info<false, GTAB>(sc, index, P, N, material);
    sweep_store(a, q, 1, index, total, steps, P, N);
 }
+
+// ------------------------------------------------------------------------ meshing the scene's surface
+// mdh_surface_mesh, mdh_surface_mesh_device (mdh_api.hip): surface nets over a grid of the scene's distance -- the field,
+// the counts, their scan, the vertices and the quads, every slot a function of the grid alone.  The definition and the
+// kernels: mdh_surface.h.
+#include "mdh_surface.h"
 #endif
 
 // ---------------------------------------------------------------------- the window's pixels

@@ -350,5 +350,23 @@ def path_traced_view(R, Width, Height, Samples=64, Bounces=3, Seed=1, Slice=16):
     return tone(traced), tone(frame), traced.reshape(Height, Width, 3), frame.reshape(Height, Width, 3)
 
 
+def scene_mesh(Path=None, R=None, Spacing=0.1, Binding=None):
+    """The sphere and the box of the global_illumination room as a quad mesh, without the room's walls: Renderer.Surface_Mesh
+    over the kinds (Sphere, Box) on a grid of `Spacing` round the two bodies, written to `Path` as Wavefront OBJ where one is
+    given.  -> the mesh, {positions, quads, normals, index}"""
+    from . import meshes
+    own = R is None
+    if own:
+        R = global_illumination(64, 64, Binding=Binding)
+    lo, hi = np.array([1.0, -2.0, 1.5]), np.array([5.0, 5.5, 6.0])  # round the sphere ((3, 4, 3), 1) and the box ((3, 0, 4) +- 1.5)
+    cells = np.ceil((hi - lo) / Spacing).astype(np.int32)
+    mesh = R.Surface_Mesh(lo, Spacing, cells, 0.0, (spheres.Sphere, boxes.Box))
+    if Path is not None:
+        meshes.Write_Obj(Path, mesh["positions"], mesh["quads"], mesh["normals"])
+    if own:
+        R.Destroy()
+    return mesh
+
+
 SCENES = {"simple_scene": simple_scene, "global_illumination": global_illumination,
           "light_shafts": light_shafts, "obj_mesh": obj_mesh}

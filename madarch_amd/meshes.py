@@ -58,3 +58,17 @@ def degenerate(tris, eps=1e-12):
     t = np.asarray(tris, dtype=np.float64)
     n = np.cross(t[:, 1] - t[:, 0], t[:, 2] - t[:, 0])
     return np.nonzero(0.5 * np.sqrt((n * n).sum(axis=1)) <= eps)[0]
+
+
+def Write_Obj(path, positions, quads, normals=None):
+    """A quad mesh as Wavefront OBJ text: positions (V, 3), quads (Q, 4) of vertex ids counted from 0 -- what
+    Renderer.Surface_Mesh returns -- and optionally a normal per vertex.  %.9g round-trips a float32."""
+    with open(path, "w") as f:
+        for p in np.asarray(positions, dtype=np.float32):
+            f.write("v %.9g %.9g %.9g\n" % tuple(p))
+        if normals is not None:
+            for n in np.asarray(normals, dtype=np.float32):
+                f.write("vn %.9g %.9g %.9g\n" % tuple(n))
+        fmt = "f %d//%d %d//%d %d//%d %d//%d\n" if normals is not None else "f %d %d %d %d\n"
+        for q in np.asarray(quads, dtype=np.int64) + 1:
+            f.write(fmt % (tuple(np.repeat(q, 2)) if normals is not None else tuple(q)))

@@ -300,6 +300,56 @@ class Renderer:
                 dev(Dist, "Dist", n, "float32"), dev(Index, "Index", n, "int32", True), dev(Normal, "Normal", 3 * n, "float32", True)]
         self._b.check(self._b.contacts_device(self._h, n, *args, C.c_void_p(int(Stream))))
 
+    # ---- the scene's surface as a mesh: surface nets over a regular grid (madarch_hip.h: mdh_surface_mesh has the definition).
+    # Prims as for Contacts: None, the whole scene, or a tuple of kinds -- (Sphere, Box) meshes the objects without the walls
+    @staticmethod
+    def _grid(Origin, Spacing, Cells):
+        origin = np.ascontiguousarray(Origin, dtype=np.float32)
+        cells = np.ascontiguousarray(Cells, dtype=np.int32)
+        if origin.shape != (3,) or cells.shape != (3,):
+            raise ValueError("a grid has an origin of 3 floats and 3 cell counts, not %s and %s" % (origin.shape, cells.shape))
+        return origin, float(Spacing), cells
+
+    def Surface_Mesh(self, Origin, Spacing, Cells, Iso=0.0, Prims=None, Normals=True, Index=True, Field=False):
+        """the level set D = Iso over the grid of Cells cubic cells of side Spacing from Origin: {positions (V, 3), quads
+        (Q, 4) of vertex ids, normals (V, 3), index (V), field (cz + 1, cy + 1, cx + 1) corner values minus Iso} -- the last
+        three where asked for.  Counts first, allocates, and calls again."""
+        origin, h, cells = self._grid(Origin, Spacing, Cells)
+        kinds, nk = self._kinds(Prims)
+        grid = (_fp(origin), h, _fp(cells), float(Iso), None if kinds is None else _fp(kinds), nk)
+        counts = np.zeros(2, np.int32)
+        self._b.check(self._b.surface_mesh(self._h, *grid, 0, 0, None, None, None, None, None, _fp(counts)))
+        nv, nq = int(counts[0]), int(counts[1])
+        out = {"positions": np.zeros((nv, 3), np.float32), "quads": np.zeros((nq, 4), np.int32)}
+        if Normals:
+            out["normals"] = np.zeros((nv, 3), np.float32)
+        if Index:
+            out["index"] = np.zeros(nv, np.int32)
+        if Field:
+            out["field"] = np.zeros((int(cells[2]) + 1, int(cells[1]) + 1, int(cells[0]) + 1), np.float32)
+
+        def ptr(key, n):
+            return _fp(out[key]) if key in out and n > 0 else None
+        self._b.check(self._b.surface_mesh(self._h, *grid, nv, nq, ptr("positions", nv), ptr("normals", nv), ptr("index", nv), ptr("quads", nq),
+                                           ptr("field", 1), _fp(counts)))
+        if (int(counts[0]), int(counts[1])) != (nv, nq):
+            raise RuntimeError("the scene changed between the count and the fill")
+        return out
+
+    def Surface_Mesh_Device(self, Origin, Spacing, Cells, Counts, Iso=0.0, Prims=None, Vertex_Capacity=0, Quad_Capacity=0, Positions=None, Normals=None,
+                            Index=None, Quads=None, Field=None, Stream=0):
+        """the same mesh into device memory under Raycast_Device's contract: tensors or addresses with their capacities, Counts
+        (2 int32 on the device) = the vertices and quads found, whatever the capacities; nothing waits"""
+        origin, h, cells = self._grid(Origin, Spacing, Cells)
+        kinds, nk = self._kinds(Prims)
+        nv, nq = int(Vertex_Capacity), int(Quad_Capacity)
+        corners = int(np.prod(cells.astype(np.int64) + 1))
+        dev = self._device_array
+        args = [dev(Positions, "Positions", 3 * nv, "float32", True), dev(Normals, "Normals", 3 * nv, "float32", True), dev(Index, "Index", nv, "int32", True),
+                dev(Quads, "Quads", 4 * nq, "int32", True), dev(Field, "Field", corners, "float32", True), dev(Counts, "Counts", 2, "int32")]
+        self._b.check(self._b.surface_mesh_device(self._h, _fp(origin), h, _fp(cells), float(Iso), None if kinds is None else _fp(kinds), nk, nv, nq, *args,
+                                                  C.c_void_p(int(Stream))))
+
     # ---- what a ray sees: the frame's pixel program (pixel_color_probes, render_probes.glsl:246-291) along rays of the host's
     @staticmethod
     def _shade_mode(Mode):
