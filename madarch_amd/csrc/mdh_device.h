@@ -839,10 +839,24 @@ template <bool GTAB = false> MDH_DEV SdfRegs sdf_regs(const KScene &sc)
 // configs 3, 4, 5).  The same operations on the same operands; what goes is what a count known only at run time costs at every
 // march step -- the loops' scalar bookkeeping and branches around bodies that run once or never -- and the registers their
 // induction state holds: 96 -> 80 VGPRs in the screen kernel, six wavefronts per SIMD without a further spill.
-template <bool CUSTOM, bool ROOM = false, bool GTAB = false, bool BVH = false> MDH_DEV float closest_primitive(const KScene &sc, f3 x, const SdfRegs *regs = nullptr)
+// MDH_RAY_BOUNDS: two numbers per lane that a march computes once (ray_bounds below), hs below the
+// first sphere's distance and hb below the first box's at every position the march can evaluate.  Where hs > closest in every
+// live lane the sphere's block is skipped without its own test, and the box's likewise behind it; either block would have
+// computed min_raw(closest, d) with d >= closest.  A NaN or -inf bound compares false: the block runs as before, its own cull included.
+#ifndef MDH_RAY_BOUNDS
+#define MDH_RAY_BOUNDS 1
+#endif
+// (the parts, for the A/B runs of profiles/r26_ray_bounds_ab.log: 1 the sphere's bound, 2 the box's.  One register min(hs, hb) behind
+//  one ballot in front of both blocks was measured and dropped: DESIGN.md section 4 "What was tried and dropped")
+#ifndef MDH_RAY_BOUNDS_PARTS
+#define MDH_RAY_BOUNDS_PARTS 3
+#endif
+struct RayBounds { float hs, hb; };
+template <bool CUSTOM, bool ROOM = false, bool GTAB = false, bool BVH = false> MDH_DEV float closest_primitive(const KScene &sc, f3 x, const SdfRegs *regs = nullptr, const RayBounds *rb = nullptr)
 {
    const typename Geo<GTAB>::F4 s_tab = Geo<GTAB>::f4(sc); // (shadows the LDS table: global residency reads the image; every index below is wave-uniform)
    float closest = sc.max_dist;
+   const int RB = (ROOM && MDH_RAY_BOUNDS && rb) ? MDH_RAY_BOUNDS_PARTS : 0; // (rb comes with the ROOM census only: one sphere, one box)
    // the first sphere and the first box are on their way from LDS while the planes are evaluated: a wavefront that
    // has a SIMD to itself (the tail of every pass, and whole passes of a sharded frame) has nothing else to
    // hide that latency behind.
@@ -868,6 +882,9 @@ template <bool CUSTOM, bool ROOM = false, bool GTAB = false, bool BVH = false> M
          const bool need = !(tsum < 0.0f) && !(d2 > (tsum * tsum) * 1.000001f);              \
          if (__ballot(need) != 0ull) closest = min_raw(closest, sqrt_(d2) - a.w); \
       } while (0)
+      if (RB & 1) { // (the ray's bound in front of the block)
+         if (__ballot(!(rb->hs > closest)) != 0ull) MDH_SPHERE_STEP(pf_s);
+      } else
       if (n > 0) MDH_SPHERE_STEP(pf_s);
 #pragma unroll 1
       for (int i = 1; i < n; ++i) MDH_SPHERE_STEP(s_tab[uni<GTAB>(s0 + i)]);
@@ -883,6 +900,9 @@ template <bool CUSTOM, bool ROOM = false, bool GTAB = false, bool BVH = false> M
          if (__ballot(!(m > thr)) != 0ull)                                                   \
             closest = min_raw(closest, length(F3(max0_raw(q.x), max0_raw(q.y), max0_raw(q.z))) + min0_raw(m)); \
       } while (0)
+      if (RB & 2) { // (behind the sphere's block: `closest` is what that left, unchanged where it was skipped)
+         if (__ballot(!(rb->hb > closest)) != 0ull) MDH_BOX_STEP(pf_b0, pf_b1);
+      } else
       if (n > 0) MDH_BOX_STEP(pf_b0, pf_b1);
 #pragma unroll 1
       for (int i = 1; i < n; ++i) MDH_BOX_STEP(s_tab[uni<GTAB>(s0 + 2 * i)], s_tab[uni<GTAB>(s0 + 2 * i + 1)]);
@@ -912,6 +932,64 @@ template <bool CUSTOM, bool ROOM = false, bool GTAB = false, bool BVH = false> M
       }
    }
    return closest;
+}
+// ray_bounds (MDH_RAY_BOUNDS; ROOM census: regs holds THE sphere and THE box) -- the two ray constants of a march that evaluates
+// the SDF at fl(o + fl(d * total)), 0 <= total < tmax, and nowhere else.  With p* = o + d t*, t* = clamp(dot(c - o, d), 0, tmax),
+// the point of the segment S = o + d [0, tmax] closest to a centre c, and q = c - p*:
+//   sphere  every p of S has |c - p| >= |q|, so the sphere's distance is >= |q| - r;
+//   box     S is convex, so (c - p) . q >= |q|^2 for every p of S: along n = q / |q| the segment stays |q| from the centre, and the
+//           box reaches sum |n_a| e_a that way (its support function).  Outside the box the distance is at least the gap along
+//           n, g = |q| - sum |q_a| e_a / |q|; inside, the distance is m = max_a (|c - p|_a - e_a) < 0 and (c - p) . n <= sum (m + e_a) |n_a|
+//           gives m sum |n_a| >= g, hence m >= g (g < 0, sum |n_a| >= 1).
+// What the computed values owe the ideal ones, with L = lim + tmax (|o| <= lim per coordinate is required; every centre,
+// radius and half-size is below lim / 2, commit_scene):
+//   - |d|^2 is required within 2^-18 of 1 (camera_ray's normalisation and reflect about a unit normal leave a few 2^-23), else the
+//     bounds are off.  The computed t differs from t* -- the true minimiser divides by |d|^2 -- by at most |dot(c - o, d)| 2^-17.9
+//     plus the dot's rounding: < 3 lim 2^-17.8 (clamp is 1-Lipschitz), which moves p* along d by that much;
+//   - w = c - o, d * t and their difference round by < 2^-21 (3 lim + tmax) together; so the computed q is within
+//     eta < 2^-15.9 L of the true one;
+//   - |q| changes by at most eta, the unit vector n by at most 2 eta / |q|, the support sum by at most |e| |n - n'| <= 2 (e_x + e_y + e_z) eta / |q|;
+//   - dot2, v_sqrt_f32 and v_rsq_f32 (one ulp each), the products and sums behind them: a few 2^-23 of values below 3 lim + tmax, < 2^-20 L;
+//   - the march's positions lie within 2^-22 L of S (two roundings of magnitudes below lim + 2 tmax per coordinate) and the SDF is
+//     1-Lipschitz; the computed sqrt(d2) - r and length(max(q, 0)) + min(m, 0) round by < 2^-21 L.
+// The sum stays below 2^-15 L (1 + 2 (e_x + e_y + e_z) / |q|); the margin E = 2^-14 L, scaled by that factor for the box, is twice
+// it.  So hs > closest implies that the block's own float32 distance is > closest: min_raw(closest, d) returns closest, whether
+// the block's cull would have fired or its root been taken -- the box's threshold closest * 1.000001 never enters (hb > closest
+// does NOT imply m > thr: beside an edge m < d; the skipped block is one whose result is `closest` on either path, in both
+// signs of closest).  Off (all ones, a NaN, which compares false) where segment_clear is off for the scene (hdr(H_VCLEAR) <= 0: negative radii or
+// half-sizes, non-finite tables, triangles), where |o| exceeds lim in a coordinate, where d is not unit as above (zero, infinite and NaN
+// directions among them), and for a NaN or negative tmax; tmax = inf makes E inf and the bounds -inf.  q = 0: rq = inf, hb = NaN, which compares false.
+// tmax = max_dist may put the far end beyond lim: L carries tmax, and nothing above needs |o + d tmax| <= lim.
+MDH_DEV RayBounds ray_bounds(const SdfRegs &regs, f3 o, f3 d, float tmax)
+{
+   const float thr = __int_as_float(hdr(H_VCLEAR)), lim = __int_as_float(hdr(H_VCLEAR_LIM));
+   // (written so that nothing here waits in a register across the pixel program's loop over its two points, where the compiler
+   //  moves what does not change from ray to ray: inline constants and scalars only -- v_ldexp_f32 for the power of two,
+   //  v_med3_f32 for the clamp, whose scalar tmax then needs no quieted copy, and all ones (a NaN) for "off".  With -inf from a
+   //  register and the clamp as min(max()) the headline kernel paid 16 bytes of scratch memory per lane in its corner loop.)
+   bool ok = thr > 0.0f && tmax >= 0.0f;
+   ok = ok && __builtin_fabsf(o.x) <= lim && __builtin_fabsf(o.y) <= lim && __builtin_fabsf(o.z) <= lim;
+   ok = ok && __builtin_ldexpf(__builtin_fabsf(dot2(d) - 1.0f), 18) <= 1.0f;
+   const float E = __builtin_ldexpf(lim + tmax, -14);
+   RayBounds r;
+   {
+      const f3 w = xyz(regs.s) - o;
+      const f3 q = w - d * __builtin_amdgcn_fmed3f(dot(w, d), 0.0f, tmax);
+      r.hs = (__builtin_amdgcn_sqrtf(dot2(q)) - regs.s.w) - E;
+   }
+   {
+      const f3 w = xyz(regs.b0) - o;
+      const f3 q = w - d * __builtin_amdgcn_fmed3f(dot(w, d), 0.0f, tmax);
+      const float q2 = dot2(q), rq = __builtin_amdgcn_rsqf(q2);
+      const f3 e = xyz(regs.b1);
+      const float sup = ((__builtin_fabsf(q.x) * e.x + __builtin_fabsf(q.y) * e.y) + __builtin_fabsf(q.z) * e.z) * rq;
+      const float se = 2.0f * ((e.x + e.y) + e.z);
+      r.hb = (q2 * rq - sup) - E * (1.0f + se * rq);
+   }
+   const int off = ok ? 0 : -1; // (all ones is a NaN: hs > closest is false)
+   r.hs = __int_as_float(__float_as_int(r.hs) | off);
+   r.hb = __int_as_float(__float_as_int(r.hb) | off);
+   return r;
 }
 // closest_primitive_info (scenes.adb:631-674): kinds in SCENE order (the arg-min keeps the
 // first of equal distances).  Evaluated at hit points only -- twice per pixel of the screen pass.
@@ -1343,6 +1421,13 @@ template <int PART> MDH_DEV float sdf(const KScene &sc, f3 x, const SdfRegs &reg
    MDH_WORK(2);
    if (PART & MDH_PF_PART) return partitioning_closest_bits<(PART & MDH_PF_CUSTOM) != 0, MDH_PF_HAS_FALLBACK(PART), (PART & MDH_PF_PSMALL) != 0, (PART & MDH_PF_GTAB) != 0>(sc, x);
    return closest_primitive<(PART & MDH_PF_CUSTOM) != 0, (PART & MDH_PF_ROOM) != 0, (PART & MDH_PF_GTAB) != 0, (PART & MDH_PF_BVH) != 0>(sc, x, &regs);
+}
+// ... and with the march's ray constants (ray_bounds): the brute-force scan over the rooms' census only
+template <int PART> MDH_DEV float sdf(const KScene &sc, f3 x, const SdfRegs &regs, const RayBounds &rb)
+{
+   static_assert((PART & ~MDH_PF_POW2) == MDH_PF_ROOM, "ray bounds: the rooms' census, no partition, no global residency");
+   MDH_WORK(2);
+   return closest_primitive<false, true, false, false>(sc, x, &regs, &rb);
 }
 template <int PART> MDH_DEV float sdf_info(const KScene &sc, f3 x, int &index)
 {

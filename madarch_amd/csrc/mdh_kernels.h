@@ -193,7 +193,9 @@ __global__ __launch_bounds__(MDH_BLOCK, MDH_OCC(PART, MODE)) void k_screen(KScen
       constexpr bool NULLB = null_brdf_screen(PART, MODE, GBUF, ALT, REC); // (mdh_march.h: which instantiations shade every light)
       // (mdh_march.h: which instantiations fetch every lane's taps -- 0 -- and which of the others take a folded corner's weight from its twin -- 2)
       // ... and which search the second point's best probe best first -- 4 beside either)
-      constexpr int SHARET = (!share_taps_screen(PART, GBUF, REC) ? 0 : folded_twins_screen(PART, GBUF, REC) ? 2 : 1) | (best_first_screen(PART, GBUF, REC) ? 4 : 0);
+      // ... and which bound the sphere's and the box's distance once per ray in front of their two marches -- 8)
+      constexpr int SHARET = (!share_taps_screen(PART, GBUF, REC) ? 0 : folded_twins_screen(PART, GBUF, REC) ? 2 : 1) | (best_first_screen(PART, GBUF, REC) ? 4 : 0) |
+                             (ray_bounds_screen(PART, GBUF, REC) ? 8 : 0);
       if (REC == 2) {
          RayRecord rec = {0u, 0u, -1, 0u}, rec2 = {0u, 0u, -1, 0u};
          if (valid) {

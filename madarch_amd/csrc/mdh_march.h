@@ -113,7 +113,10 @@ struct DiagWaveTimer {
 #endif
 
 // raymarching.glsl:25-51: plain sphere trace until a hit or tmax; `steps` counts SDF evaluations
-template <int PART> MDH_DEV bool march_plain(const KScene &sc, f3 o, f3 d, float tmax, float &t_out, int &steps)
+// BOUNDS (MDH_RAY_BOUNDS, the screen pass's fixed mode over the rooms' census): the sphere's and the box's distance bounded from
+// below along the whole ray, once, in front of the loop (mdh_device.h: ray_bounds) -- closest_primitive skips a solid's block
+// where the bound exceeds the running minimum in every live lane.  The same positions, the same values, the same steps.
+template <int PART, bool BOUNDS = false> MDH_DEV bool march_plain(const KScene &sc, f3 o, f3 d, float tmax, float &t_out, int &steps)
 {
    int n = 0;
    bool h = false;
@@ -121,11 +124,15 @@ template <int PART> MDH_DEV bool march_plain(const KScene &sc, f3 o, f3 d, float
    // the first sphere and box stay in registers for the whole march (measured: +0.7 %; the same in the shadow,
    // visibility-queue and occlusion marches ±0, in the per-corner visibility march -1 %: register pressure)
    const SdfRegs regs = sdf_regs<(PART & MDH_PF_GTAB) != 0>(sc);
+   RayBounds rb;
+   if (BOUNDS) rb = ray_bounds(regs, o, d, tmax);
    MDH_WORK(0);
    while (total < tmax) {
       MDH_DIAG_STEP(0);
       MDH_WORK(1);
-      float dist = sdf<PART>(sc, o + d * total, regs);
+      float dist;
+      if constexpr (BOUNDS) dist = sdf<PART>(sc, o + d * total, regs, rb);
+      else dist = sdf<PART>(sc, o + d * total, regs);
       ++n;
       if (dist < MDH_EPS) { h = true; break; }
       total += dist;
@@ -549,6 +556,13 @@ constexpr bool best_first_screen(int PART, bool GBUF, int REC)
 {
    return REC != 2 && !(GBUF && ((PART == 0 && REC == 0) || (PART == MDH_PF_POW2 && REC == 1) || (PART == MDH_PF_ROOM && REC == 1)));
 }
+// MDH_RAY_BOUNDS (item 19 of "Exact work elimination", at march_plain above): the primary and the reflection march of the screen
+// family's fixed mode over the rooms' census, marching and recording, with and without the geometry buffer.  No variant paid for the
+// two registers in scratch memory or wavefronts (resource_usage.sh).  k_ray_shade and k_point_shade are left as they are.
+constexpr bool ray_bounds_screen(int PART, bool GBUF, int REC)
+{
+   return REC != 2 && (PART & ~MDH_PF_POW2) == MDH_PF_ROOM;
+}
 // POINT (k_point_shade, mdh_kernels.h: mdh_shade_points): the first shaded point is the caller's -- `from` is the point itself,
 // `dir_in` the direction it is seen along, `pt_normal` and `pt_material` what primitive_info would have said -- and context 0
 // runs no primary march, no arg-min scan and no primitive_info: every valid lane "hits" at its point with index -1, t 0 and
@@ -588,6 +602,9 @@ MDH_DEV f3 shade_structured(const KScene &sc, const KProbes &pr, const MachineCf
    // marching and recording -- every other instantiation is the code it was
    constexpr bool BEST_FIRST = MDH_BEST_FIRST != 0 && (SHARET & 4) != 0 && MDH_SHARE_FIRST_STEP != 0 && MDH_REUSE_FOLDED != 0 && SPEC == 1 && !QVIS && MODE == 0 &&
                                (PART & ~(MDH_PF_ROOM | MDH_PF_POW2)) == 0 && REC != 2;
+   // the sphere's and the box's distance bounded once per ray in front of the primary and the reflection march (item 19 of "Exact
+   // work elimination", at march_plain): the screen family's fixed mode over the rooms' census, marching and recording
+   constexpr bool RAY_BOUNDS = MDH_RAY_BOUNDS != 0 && (SHARET & 8) != 0 && SPEC == 1 && !QVIS && MODE == 0 && !POINT && REC != 2 && (PART & ~MDH_PF_POW2) == MDH_PF_ROOM;
    // the space-partition variants of the screen pass: the shaded point and its normal come back from park rows behind every
    // corner's visibility march (the second point's wait in the rows of its colour and in three rows of their own) and the probe's grid position is derived again there:
    // the lookups of that march need the registers -- kept live across it, these values went to scratch memory eight times per
@@ -627,7 +644,7 @@ MDH_DEV f3 shade_structured(const KScene &sc, const KProbes &pr, const MachineCf
             t = 0.0f;
             steps = 0;
          } else
-         h = march_plain<PART>(sc, ro, rd, sc.max_dist, t, steps);
+         h = march_plain<PART, RAY_BOUNDS>(sc, ro, rd, sc.max_dist, t, steps);
          if (REC == 1 && !(SREC && ctx)) park_store1<MDH_PARK_REC + 4>(pk, wb, __int_as_float(steps)); // (hit or miss: the sort key needs them)
          if (REC == 1 && SREC && ctx) park_store1<MDH_PARK_REC2 + 4>(pk, wb, __int_as_float(h ? 3 : 1)); // traced, and hit
          PH_ADD(pt, 0);
