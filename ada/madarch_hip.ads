@@ -283,6 +283,53 @@ package Madarch_HIP is
       Sample, Bounce : int; Dir_Out : System.Address) return Status
      with Import, Convention => C, External_Name => "mdh_path_scatter";
 
+   --  A path-traced frame (madarch_hip.h, mdh_path_frame_begin): Path_Trace's estimator over the
+   --  pixels of a frame of the camera, the sums kept on the device from call to call.  Begin
+   --  captures the camera and fixes Seed, Bounces (0 .. 6) and Jitter (0 / 1); Accumulate adds the
+   --  next Sample_Count samples and does not wait; Read is the resolve on the device, every output
+   --  may be Null_Address; restarting after an edit of the scene is the caller's business.
+   Path_Frame_Max_Pixels : constant int := 67_108_864;
+
+   function Path_Frame_Begin
+     (R : Handle; Width, Height : int; Seed : Interfaces.Unsigned_32; Bounces, Jitter : int)
+      return Status
+     with Import, Convention => C, External_Name => "mdh_path_frame_begin";
+
+   function Path_Frame_Accumulate (R : Handle; Sample_Count : int) return Status
+     with Import, Convention => C, External_Name => "mdh_path_frame_accumulate";
+
+   function Path_Frame_Read
+     (R : Handle; Tone_Map : int; RGB_Out, RGBA8_Out, Sums_Out : System.Address;
+      Samples_Out : access int) return Status
+     with Import, Convention => C, External_Name => "mdh_path_frame_read";
+
+   function Path_Frame_Read_Device
+     (R : Handle; Tone_Map : int; RGB_Out, RGBA8_Out, Sums_Out : System.Address;
+      Samples_Out : access int; Stream : System.Address) return Status
+     with Import, Convention => C, External_Name => "mdh_path_frame_read_device";
+
+   function Path_Frame_Rays
+     (R : Handle; Sample : int; Org_Out, Dir_Out : System.Address) return Status
+     with Import, Convention => C, External_Name => "mdh_path_frame_rays";
+
+   function Path_Frame_Rays_Device
+     (R : Handle; Sample : int; Org_Out, Dir_Out : System.Address; Stream : System.Address)
+      return Status
+     with Import, Convention => C, External_Name => "mdh_path_frame_rays_device";
+
+   function Path_Frame_Info
+     (R : Handle; Width, Height, Samples, Bounces, Jitter : access int) return Status
+     with Import, Convention => C, External_Name => "mdh_path_frame_info";
+
+   function Path_Frame_End (R : Handle) return Status
+     with Import, Convention => C, External_Name => "mdh_path_frame_end";
+
+   --  The jitter by itself, on the host: no launch and no renderer.  UV_Out: 2 N floats.
+   function Path_Pixel_Uv
+     (Width, Height : int; Seed, Id_First : Interfaces.Unsigned_32; N, Sample, Jitter : int;
+      UV_Out : System.Address) return Status
+     with Import, Convention => C, External_Name => "mdh_path_pixel_uv";
+
    --  The lights' fog at N points and along N rays of the host's (madarch_hip.h,
    --  mdh_inscatter_points, mdh_inscatter_rays): the integrand of the visibility pass evaluated
    --  anywhere, and the scattering pass's serial sum along any ray.  F, Len_Out and Steps_Out may

@@ -2,18 +2,33 @@
 // frame (FRAMES frames of probe feedback, then the pixel program along the frame's rays, linear) and by the path tracer
 // (Renderer.Path_Trace: SAMPLES samples a pixel in slices of SLICE, BOUNCES bounces), the ground truth the probes approximate.
 // Prints the mean absolute difference between the two linear images, per channel and over the pixels whose ray hits the scene:
-// a number to look at, held against nothing.  Usage: path_trace W H [SAMPLES [BOUNCES [SEED [FRAMES [SLICE [out.ppm]]]]]]
+// a number to look at, held against nothing.  Then the same view as a path-traced FRAME: the renderer's own accumulator
+// (Path_Frame_Begin, Path_Frame_Accumulate in the same slices, Path_Frame_Read) -- no rays fetched, the sums stay on the device,
+// the resolve runs there.  Without --jitter its sums are the first image's bit for bit (the program says how many pixels
+// differ: none); with --jitter every sample goes through its own point of its pixel and the edges are anti-aliased.  out.ppm
+// is the accumulator's image, the window's bytes as Path_Frame_Read hands them out.
+// Usage: path_trace [--jitter] W H [SAMPLES [BOUNCES [SEED [FRAMES [SLICE [out.ppm]]]]]]
 #include "madarch.hpp"
 
 #include <algorithm>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
+#include <cstring>
 
 using namespace Madarch;
 
 int main(int argc, char **argv)
 {
+   bool jitter = false;
+   { // --jitter, wherever it stands
+      int kept = 1;
+      for (int q = 1; q < argc; ++q) {
+         if (!strcmp(argv[q], "--jitter")) jitter = true;
+         else argv[kept++] = argv[q];
+      }
+      argc = kept;
+   }
    const int W = argc > 1 ? atoi(argv[1]) : 256, H = argc > 2 ? atoi(argv[2]) : 256;
    const int samples = argc > 3 ? atoi(argv[3]) : 64, bounces = argc > 4 ? atoi(argv[4]) : 3;
    const uint32_t seed = argc > 5 ? (uint32_t)strtoul(argv[5], nullptr, 10) : 1u;
@@ -58,16 +73,29 @@ int main(int argc, char **argv)
       printf("path_trace %dx%d: %d samples, %d bounces, seed %u, %d frames of DDGI; %zu of %zu pixels hit\n", W, H, samples, bounces, seed, frames, hits, n);
       printf("mean |path traced - DDGI frame| over the hit pixels, linear: r %.6f g %.6f b %.6f\n", hits ? diff[0] / hits : 0.0, hits ? diff[1] / hits : 0.0,
              hits ? diff[2] / hits : 0.0);
-      if (argc > 8) { // the path-traced image through draw_screen.glsl:29
-         FILE *out = fopen(argv[8], "wb");
-         if (!out) return 2;
-         fprintf(out, "P6\n%d %d\n255\n", W, H);
+      // the same view in the renderer's own accumulator
+      Renderer.Path_Frame_Begin(W, H, seed, bounces, jitter);
+      for (int first = 0; first < samples; first += slice) Renderer.Path_Frame_Accumulate(std::min(slice, samples - first)); // (nothing waits)
+      if (samples > 0) {
+         const Renderers::Renderer::Path_Frame_Image Image = Renderer.Path_Frame_Read(true, false, true, true); // tone-mapped bytes and the raw sums
+         size_t differ = 0;
+         double moved = 0.0;
          for (size_t q = 0; q < 3 * n; ++q) {
-            const double x = std::max(0.0, (double)Paths.Rgb[q] / std::max(samples, 1));
-            fputc((int)std::lround(255.0 * std::min(1.0, std::pow(x / (x + 1.0), 0.4545))), out);
+            differ += memcmp(&Image.Sums[q], &Paths.Rgb[q], 4) != 0;
+            moved += std::fabs((double)Image.Sums[q] - (double)Paths.Rgb[q]) / samples;
          }
-         fclose(out);
+         printf("path-traced frame, %s: %d samples in the accumulator; %zu of %zu sums differ from the rays' (mean |difference| %.6f)\n",
+                jitter ? "jittered" : "pixel centres", Image.Samples, differ, 3 * n, moved / (3.0 * n));
+         if (argc > 8) { // the window's bytes
+            FILE *out = fopen(argv[8], "wb");
+            if (!out) return 2;
+            fprintf(out, "P6\n%d %d\n255\n", W, H);
+            for (size_t q = 0; q < n; ++q)
+               for (int c = 0; c < 3; ++c) fputc((int)((Image.Rgba8[q] >> (8 * c)) & 255u), out);
+            fclose(out);
+         }
       }
+      Renderer.Path_Frame_End();
    } catch (const std::exception &e) {
       fprintf(stderr, "path_trace: %s\n", e.what());
       return 1;

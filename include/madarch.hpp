@@ -483,6 +483,66 @@ class Renderer {
       Check(mdh_path_scatter((int32_t)n, Directions.data(), Normals.data(), Roughness.data(), Seed, Id_First, Sample, Bounce, Out.data()));
       return Out;
    }
+   // ---- a path-traced frame: Path_Trace's estimator over the pixels of a frame of the camera, the sums kept on the device from call
+   // to call.  Begin captures the camera and fixes Seed, Bounces and Jitter; Accumulate adds the next samples and does not wait;
+   // Read is the resolve on the device (sums / samples, the tone map, the window's bytes); restarting after an edit is the caller's
+   struct Path_Frame_State { int32_t Width = 0, Height = 0, Samples = 0, Bounces = 0, Jitter = 0; };
+   struct Path_Frame_Image { int32_t Width = 0, Height = 0, Samples = 0; std::vector<float> Rgb; std::vector<uint32_t> Rgba8; std::vector<float> Sums; };
+   void Path_Frame_Begin(int32_t Width, int32_t Height, uint32_t Seed = 0, int32_t Bounces = 3, bool Jitter = true) const
+   {
+      Check(mdh_path_frame_begin(h_.get(), Width, Height, Seed, Bounces, Jitter ? 1 : 0));
+   }
+   void Path_Frame_Accumulate(int32_t Sample_Count = 1) const { Check(mdh_path_frame_accumulate(h_.get(), Sample_Count)); }
+   Path_Frame_State Path_Frame_Info() const
+   {
+      Path_Frame_State S;
+      Check(mdh_path_frame_info(h_.get(), &S.Width, &S.Height, &S.Samples, &S.Bounces, &S.Jitter));
+      return S;
+   }
+   // rows top first; 3 floats a pixel in Rgb and Sums, one word (R in the low byte) in Rgba8; only what is asked for is computed
+   Path_Frame_Image Path_Frame_Read(bool Tone_Map = false, bool Rgb = true, bool Rgba8 = false, bool Sums = false) const
+   {
+      const Path_Frame_State S = Path_Frame_Info();
+      Path_Frame_Image Out;
+      Out.Width = S.Width; Out.Height = S.Height;
+      const size_t n = (size_t)S.Width * (size_t)S.Height;
+      if (Rgb) Out.Rgb.resize(3 * n);
+      if (Rgba8) Out.Rgba8.resize(n);
+      if (Sums) Out.Sums.resize(3 * n);
+      Check(mdh_path_frame_read(h_.get(), Tone_Map ? 1 : 0, Out.Rgb.empty() ? nullptr : Out.Rgb.data(), Out.Rgba8.empty() ? nullptr : Out.Rgba8.data(),
+                                Out.Sums.empty() ? nullptr : Out.Sums.data(), &Out.Samples));
+      return Out;
+   }
+   // ... into arrays the device addresses, asynchronous and ordered with Stream (a hipStream_t); returns the samples
+   int32_t Path_Frame_Read_Device(float *Rgb, uint32_t *Rgba8 = nullptr, float *Sums = nullptr, bool Tone_Map = false, void *Stream = nullptr) const
+   {
+      int32_t Samples = 0;
+      Check(mdh_path_frame_read_device(h_.get(), Tone_Map ? 1 : 0, Rgb, Rgba8, Sums, &Samples, Stream));
+      return Samples;
+   }
+   // the rays the accumulator gives its pixels for one sample: (origins, directions), 3 floats a pixel
+   std::pair<std::vector<float>, std::vector<float>> Path_Frame_Rays(int32_t Sample = 0) const
+   {
+      const Path_Frame_State S = Path_Frame_Info();
+      const size_t n = (size_t)S.Width * (size_t)S.Height;
+      std::vector<float> Org(3 * n + 3), Dir(3 * n + 3); // (never null: without an accumulator the library says so)
+      Check(mdh_path_frame_rays(h_.get(), Sample, Org.data(), Dir.data()));
+      Org.resize(3 * n); Dir.resize(3 * n);
+      return {Org, Dir};
+   }
+   void Path_Frame_Rays_Device(float *Origins, float *Directions, int32_t Sample = 0, void *Stream = nullptr) const
+   {
+      Check(mdh_path_frame_rays_device(h_.get(), Sample, Origins, Directions, Stream));
+   }
+   void Path_Frame_End() const { Check(mdh_path_frame_end(h_.get())); }
+   // the jitter by itself, on the host, the lanes' bits: (u, v) of N pixels from Id_First on, 2 floats a pixel; no launch, no renderer
+   static std::vector<float> Path_Pixel_Uv(int32_t Width, int32_t Height, uint32_t Seed, uint32_t Id_First, int32_t N, int32_t Sample = 0, bool Jitter = true)
+   {
+      std::vector<float> Uv(2 * (size_t)(N > 0 ? N : 0) + 2);
+      Check(mdh_path_pixel_uv(Width, Height, Seed, Id_First, N, Sample, Jitter ? 1 : 0, Uv.data()));
+      Uv.resize(2 * (size_t)(N > 0 ? N : 0));
+      return Uv;
+   }
    // ---- the lights' fog at points and along rays of the host's (compute_frustrum_visibility.glsl:8-19, accumulate_scattering.glsl:17-28),
    // without the froxel grid or the camera it is bound to.  Points: sample_lights (position, direction), times exp (-F tau) where F
    // (one distance per point) is not empty.  Rays: L = 0; for (f = 0; f < len; f += Step) L = L + inscatter ((dir * f) + org, dir) * exp (-f tau);

@@ -751,6 +751,73 @@ int32_t mdh_path_trace_device(mdh_renderer *r, int32_t n, const float *org_xyz, 
 int32_t mdh_path_scatter(int32_t n, const float *dir_xyz, const float *normal_xyz, const float *roughness, uint32_t seed,
                          uint32_t id_first, int32_t sample, int32_t bounce, float *dir_out);
 
+/* A PATH-TRACED FRAME: mdh_path_trace's estimator over the pixels of a frame of the camera, with the sums kept on the device
+ * from call to call -- no rays fetched, nothing carried in and out per slice of samples --, sub-pixel jitter, and the resolve
+ * on the device.  Pixel (i, j) of the width x height frame, row 0 at the top, has the ray id j * width + i: the numbering of
+ * mdh_camera_rays with id_first = 0.  For sample s its ray is camera_ray (u, v) (glsl/draw_screen.glsl:20-24) at
+ *     jx = jitter ? path_u01 (seed, id, s, 0, 3) : 0.5        jy = jitter ? path_u01 (seed, id, s, 0, 4) : 0.5
+ *     u = ((float)(2 i) + 2 jx) / (float) width - 1           v = -(((float)(2 j) + 2 jy) / (float) height - 1)
+ * every step one binary32 operation (path_u01: csrc/mdh_path.h; the sampler takes dimensions 0 .. 2 of every bounce, so 3 and 4
+ * of bounce 0 are taken by nobody).  A jittered ray stays inside its pixel's footprint; without jitter the numerator is
+ * (float)(2 i + 1) and the rays are mdh_camera_rays' to the bit.  NO VOLUMETRICS, as in mdh_path_trace.
+ *
+ * mdh_path_frame_begin opens, or restarts from zero, the renderer's accumulator of width x height pixels -- three fp32 sums a
+ * pixel in device memory; the size is free, not the window's, at most MDH_PATH_FRAME_MAX_PIXELS pixels -- and fixes seed,
+ * bounces (0 .. 6) and jitter (0 / 1).  It CAPTURES THE CAMERA as it stands: later mdh_set_camera_position /
+ * mdh_set_camera_orientation do not smear a running accumulation.
+ *
+ * mdh_path_frame_accumulate adds samples S .. S + sample_count - 1 to every pixel, S being the samples accumulated so far, each
+ * pixel's in sample order: a run of samples split over several calls has the bits of one call, and without jitter the sums
+ * are those of mdh_path_trace over mdh_camera_rays' rays with sample_first = S.  It runs on the query stream under
+ * mdh_path_trace's contract -- the scene committed at the call, pending edits included; nothing edited: the probe-settle run
+ * and both replays go on -- and RETURNS WITHOUT WAITING for the device: there is nothing to copy.  mdh_ray_query_time times its
+ * kernel under MDH_OPT_TIMING (after mdh_ray_query_wait, or by itself).  The accumulator does not notice an edit of the scene:
+ * RESTARTING AFTER AN EDIT IS THE HOST'S BUSINESS (mdh_path_frame_begin again).  sample_count = 0 is MDH_OK without a launch.
+ * A pixel whose ray is outside mdh_path_trace's bound (a camera moved beyond 1024) is not marched: its three sums become the
+ * quiet NaN 0x7fc00000 and stay so.
+ *
+ * mdh_path_frame_read is the resolve, on the device; every output may be NULL.  rgb_out (3 floats a pixel) = sum / (float) S,
+ * one binary32 division a channel, and with tone_map = 1 glsl/draw_screen.glsl:29 applied to it as mdh_shade_rays applies it;
+ * rgba8_out (one uint32 a pixel, R in the low byte) = that colour with alpha 1 as the window's RGBA8 pixels hold a framebuffer
+ * pixel (MDH_OPT_WINDOW; a NaN shows as 0); sums_out (3 floats a pixel) = the raw sums; samples_out = S.  Rows are top first,
+ * as in the framebuffer.  The host form waits and copies.  mdh_path_frame_read_device writes arrays the device addresses
+ * (samples_out stays the host's) under the contract of mdh_raycast_device: checked with hipPointerGetAttributes before anything
+ * is launched, asynchronous and ordered with `stream`, mdh_ray_query_wait is the host's wait.
+ *
+ * mdh_path_frame_rays gives the rays the accumulator gives its pixels for sample `sample` (3 width height floats each), computed
+ * on the device by the functions the accumulating kernel calls: a host inspects or bends them, or chains the public queries
+ * over them.  The device form is enqueued on `stream` itself, as mdh_camera_rays_device.
+ *
+ * mdh_path_frame_info reports the accumulator's state (any pointer may be NULL; all zeros while none is open);
+ * mdh_path_frame_end frees it, and so does mdh_destroy.
+ *
+ * The accumulator ignores MDH_OPT_RANK / MDH_OPT_WORLD, as every query does.  Every refusal happens before any launch or
+ * allocation:
+ *   MDH_E_INVALID  a null renderer; a width or height below 1 or more than MDH_PATH_FRAME_MAX_PIXELS pixels; bounces outside
+ *                  0 .. 6; a jitter or tone_map other than 0 / 1; a negative sample_count or sample; the samples so far and
+ *                  sample_count beyond 2^31 - 1; a null array of mdh_path_frame_rays; an array the device cannot address
+ *   MDH_E_STATE    no accumulator open (accumulate, read, rays); no sample accumulated yet (read: there is no 0 / 0 image);
+ *                  and, for begin and accumulate, what mdh_path_trace refuses: a scene with a user-defined kind, an open
+ *                  frame, a max_dist above 1024 or a light beyond 1024 */
+#define MDH_PATH_FRAME_MAX_PIXELS 67108864 /* 2^26: 805 MB of sums, room above a 4096 x 4096 frame */
+int32_t mdh_path_frame_begin(mdh_renderer *r, int32_t width, int32_t height, uint32_t seed, int32_t bounces, int32_t jitter);
+int32_t mdh_path_frame_accumulate(mdh_renderer *r, int32_t sample_count);
+int32_t mdh_path_frame_read(mdh_renderer *r, int32_t tone_map, float *rgb_out, uint32_t *rgba8_out, float *sums_out,
+                            int32_t *samples_out);
+int32_t mdh_path_frame_read_device(mdh_renderer *r, int32_t tone_map, float *rgb_out, uint32_t *rgba8_out, float *sums_out,
+                                   int32_t *samples_out, void *stream);
+int32_t mdh_path_frame_rays(mdh_renderer *r, int32_t sample, float *org_xyz_out, float *dir_xyz_out);
+int32_t mdh_path_frame_rays_device(mdh_renderer *r, int32_t sample, float *org_xyz_out, float *dir_xyz_out, void *stream);
+int32_t mdh_path_frame_info(mdh_renderer *r, int32_t *width, int32_t *height, int32_t *samples, int32_t *bounces,
+                            int32_t *jitter);
+int32_t mdh_path_frame_end(mdh_renderer *r);
+/* The jitter by itself, on the host: no launch and no renderer, the inline functions the lanes call (csrc/mdh_path.h), the
+ * same bits.  uv_out[2 q], uv_out[2 q + 1] = (u, v) above of the pixel with id id_first + q of a width x height frame for
+ * sample `sample`.  MDH_E_INVALID: a size as mdh_path_frame_begin refuses it, n or sample below 0, a jitter other than 0 / 1,
+ * ids beyond the frame's pixels, a null array with n > 0. */
+int32_t mdh_path_pixel_uv(int32_t width, int32_t height, uint32_t seed, uint32_t id_first, int32_t n, int32_t sample,
+                          int32_t jitter, float *uv_out);
+
 /* The lights' fog for points and rays of the host's: the participating medium of glsl/volumetrics.glsl without the froxel
  * grid, the screen-space scattering texture or the pinhole camera they are bound to.  All arrays are host memory; positions,
  * origins and directions are 3 n floats and a direction is used as given (not normalised), as in the shaders.

@@ -186,6 +186,18 @@ HIP_ONLY_ABI = {
     "path_trace": (_I, [_P, _I, _P, _P, C.c_uint32, C.c_uint32, _I, _I, _I, _P, _P, _P, _P]),
     "path_trace_device": (_I, [_P, _I, _P, _P, C.c_uint32, C.c_uint32, _I, _I, _I, _P, _P, _P, _P, _P]),
     "path_scatter": (_I, [_I, _P, _P, _P, C.c_uint32, C.c_uint32, _I, _I, _P]),
+    # a path-traced frame, the sums kept on the device: begin (r, width, height, seed, bounces, jitter), accumulate (r, sample_count),
+    # read (r, tone_map, rgb, rgba8, sums, samples[, stream]), rays (r, sample, org, dir[, stream]), info (r, width, height, samples,
+    # bounces, jitter), end (r); and the jitter on the host, no renderer: (width, height, seed, id_first, n, sample, jitter, uv_out)
+    "path_frame_begin": (_I, [_P, _I, _I, C.c_uint32, _I, _I]),
+    "path_frame_accumulate": (_I, [_P, _I]),
+    "path_frame_read": (_I, [_P, _I, _P, _P, _P, _PI]),
+    "path_frame_read_device": (_I, [_P, _I, _P, _P, _P, _PI, _P]),
+    "path_frame_rays": (_I, [_P, _I, _P, _P]),
+    "path_frame_rays_device": (_I, [_P, _I, _P, _P, _P]),
+    "path_frame_info": (_I, [_P, _PI, _PI, _PI, _PI, _PI]),
+    "path_frame_end": (_I, [_P]),
+    "path_pixel_uv": (_I, [_I, _I, C.c_uint32, C.c_uint32, _I, _I, _I, _P]),
     # the lights' fog at n points and along n rays of the host's: (r, n, pos, dir, f or null, rgb[, stream]) and
     # (r, n, org, dir, tmax, march, step, rgb, len, steps[, stream])
     "inscatter_points": (_I, [_P, _I, _P, _P, _P, _P]),
@@ -204,6 +216,7 @@ HIP_ONLY_ABI = {
     "surface_mesh_device": (_I, [_P, _P, _F, _P, _F, _P, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P]),
 }
 SURFACE_MAX_CORNERS = 1 << 24  # MDH_SURFACE_MAX_CORNERS
+PATH_FRAME_MAX_PIXELS = 1 << 26  # MDH_PATH_FRAME_MAX_PIXELS
 
 
 class Binding:

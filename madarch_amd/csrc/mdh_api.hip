@@ -348,6 +348,16 @@ struct mdh_renderer {
    // largest grid so far, and the host form's results of the largest capacities so far; used on the query stream alone
    DevBuf<float> d_surf_field;
    DevBuf<int> d_surf_map, d_surf_wg, d_surf_out;
+   // a path-traced frame (mdh_path_frame_begin, ..): three fp32 sums a pixel, rows top first, used on the query stream alone,
+   // and what mdh_path_frame_begin fixed -- the size, the camera as it stood, seed, bounces, jitter -- with the samples so far
+   DevBuf<float> d_path_frame;
+   struct PathFrame {
+      bool open = false;
+      int W = 0, H = 0, bounces = 0, jitter = 0;
+      uint32_t seed = 0;
+      int32_t samples = 0;
+      KCamera cam;
+   } pf;
    QueryBridge bridge; // every query's events to the caller's stream and to the frames (query_enqueue; created by the first that needs one)
    int opt_rq_refill = MDH_RAY_STREAM_REFILL_DEFAULT; // MDH_OPT_RAY_STREAM_REFILL
    int opt_rq_groups = 0;                             // MDH_OPT_RAY_STREAM_GROUPS (0: as many workgroups as are resident)
@@ -1797,7 +1807,7 @@ template <typename Args> static int jit_launch(hipFunction_t f, int blocks, int 
 // frames in flight share their CUs' instruction caches (measured: the same kernels at other addresses, each as fast by itself,
 // the headline with frames in flight 0.5 % slower).  The kernels of global residency (MDH_PF_GTAB, mdh_device.h: Geo) come
 // last there: behind everything else they move nothing.
-enum { GK_k_visibility, GK_k_scat_march, GK_k_scattering, GK_k_radiance, GK_k_screen, GK_k_partition_build, GK_k_eval_distance, GK_k_diag_segments, GK_k_ray_query, GK_k_ray_stream, GK_k_ray_shade, GK_k_camera_rays, GK_k_point_shade, GK_k_path_trace, GK_k_point_inscatter, GK_k_ray_inscatter, GK_k_listed, GK_k_surface_field, GK_k_surface_vertices, GK_k_surface_field_listed, GK_k_surface_vertices_listed };
+enum { GK_k_visibility, GK_k_scat_march, GK_k_scattering, GK_k_radiance, GK_k_screen, GK_k_partition_build, GK_k_eval_distance, GK_k_diag_segments, GK_k_ray_query, GK_k_ray_stream, GK_k_ray_shade, GK_k_camera_rays, GK_k_point_shade, GK_k_path_trace, GK_k_point_inscatter, GK_k_ray_inscatter, GK_k_listed, GK_k_surface_field, GK_k_surface_vertices, GK_k_surface_field_listed, GK_k_surface_vertices_listed, GK_k_path_frame, GK_k_path_frame_rays, GK_k_path_frame_resolve };
 // WHICH KERNEL A PASS RUNS ("One place that picks a pass's kernel"): every template argument of the
 // pass's kernel, computed once by pick_kernel; kernel_name and kernel_ptr turn the same description into the name hiprtc
 // instantiates and into the kernel of this library.
@@ -1808,7 +1818,7 @@ struct PassKernel {
    bool gbuf = false, alt = false; // ... the geometry buffer, the variant of the optional specular bodies
    bool small = false;             // k_radiance: SMALL
    int rec = 0;                    // k_radiance, k_screen: REC (0 marches, 1 marches and records, 2 replays the records: rad_replay_pick, scr_replay_pick)
-   int what = 0;                   // k_ray_query, k_ray_stream, k_listed: WHAT (MDH_RQ_*)
+   int what = 0;                   // k_ray_query, k_ray_stream, k_listed: WHAT (MDH_RQ_*); k_path_frame: REUSE (1: no jitter)
    bool ada_div = false;           // k_eval_distance: MDH_OPT_ADA_DIVISION
    bool jit = false; // a function of the scene's hiprtc module (user-defined kinds under MDH_OPT_JIT), not a kernel of this library
    int pfk = 0;      // the variant by the scene's census, before the pass's own choices, and the power-of-two addressing
@@ -1834,7 +1844,8 @@ static const void *table_kernel(const mdh_renderer *r, int family, int what = 0)
    // the ray queries march as the passes do: through the space partition (its border as a variant of its own) or the triangle
    // BVH where the scene has one -- the general variants, whose bits the census variants share (pick_kernel)
    if (family == GK_k_ray_query || family == GK_k_ray_stream || family == GK_k_ray_shade || family == GK_k_point_shade || family == GK_k_path_trace ||
-       family == GK_k_point_inscatter || family == GK_k_ray_inscatter || family == GK_k_surface_field || family == GK_k_surface_vertices) {
+       family == GK_k_point_inscatter || family == GK_k_ray_inscatter || family == GK_k_surface_field || family == GK_k_surface_vertices ||
+       family == GK_k_path_frame) {
       k.what = what;
       if (family == GK_k_ray_shade || family == GK_k_point_shade) { k.what = 0; k.mode = what; } // (mdh_shade_rays, mdh_shade_points: `what` is the call's mode)
       if (r->part.enable) k.pf |= MDH_PF_PART | (r->part.border_behavior != 0 ? MDH_PF_FALLBACK : 0);
@@ -4551,6 +4562,198 @@ extern "C" int32_t mdh_camera_rays_device(mdh_renderer *r, int32_t width, int32_
    return camera_rays_launch(r, width, height, org_out, dir_out, (hipStream_t)stream); // (on the caller's stream itself: ordered with it by being there)
 }
 
+// ------------------------------------------------------------------ a path-traced frame
+// mdh_path_frame_begin, .._accumulate, .._read, .._rays, .._info, .._end and mdh_path_pixel_uv: the path tracer's estimator over the
+// pixels of a frame, with the sums in the renderer's own memory (d_path_frame) from call to call (mdh_path_frame.h: the
+// kernels).  mdh_path_frame_accumulate goes the query path at mdh_path_trace's place among the frames and is what
+// mdh_ray_query_time times; the rays and the resolve read no scene and take neither the scene's table nor the timing pair.
+// No settle_bump anywhere: nothing is edited.  Every refusal happens before a launch or an allocation.
+// what begin and accumulate refuse of the renderer's state: mdh_path_trace's list
+static int path_frame_state_check(const mdh_renderer *r)
+{
+   if (has_custom_kinds(r)) return seterr(MDH_E_STATE, "ray queries answer scenes of built-in kinds only");
+   if (r->in_frame) return seterr(MDH_E_STATE, "a frame is open");
+   return scene_extent_check(r, "traced paths", false);
+}
+static int path_frame_open_check(const mdh_renderer *r)
+{
+   if (!r) return seterr(MDH_E_INVALID, "null renderer");
+   if (!r->pf.open) return seterr(MDH_E_STATE, "no path-traced frame is open (mdh_path_frame_begin)");
+   return MDH_OK;
+}
+extern "C" int32_t mdh_path_frame_begin(mdh_renderer *r, int32_t width, int32_t height, uint32_t seed, int32_t bounces, int32_t jitter)
+{
+   if (!r) return seterr(MDH_E_INVALID, "null renderer");
+   if (!path_frame_size_valid(width, height)) return seterr(MDH_E_INVALID, "a path-traced frame has 1 to 2^26 pixels");
+   if (!path_bounces_valid(bounces)) return seterr(MDH_E_INVALID, "paths take 0 to 6 bounces");
+   if (jitter != 0 && jitter != 1) return seterr(MDH_E_INVALID, "jitter is 0 or 1");
+   int rc = path_frame_state_check(r);
+   if (rc != MDH_OK) return rc;
+   hipStream_t qs = nullptr;
+   if ((rc = query_stream_get(r, &qs)) != MDH_OK) return rc;
+   const size_t words = (size_t)width * height * 3;
+   r->pf.open = false; // (a failure below leaves no accumulator)
+   if ((rc = surface_room(r->d_path_frame, words, qs)) != MDH_OK) return rc;
+   HIP_TRY(hipMemsetAsync(r->d_path_frame.ptr, 0, words * 4, qs));
+   r->pf.W = width; r->pf.H = height; r->pf.bounces = bounces; r->pf.jitter = jitter; r->pf.seed = seed;
+   r->pf.samples = 0;
+   r->pf.cam = make_camera(r); // as it stands: later setters do not smear a running accumulation
+   r->pf.open = true;
+   return MDH_OK;
+}
+extern "C" int32_t mdh_path_frame_accumulate(mdh_renderer *r, int32_t sample_count)
+{
+   int rc = path_frame_open_check(r);
+   if (rc != MDH_OK) return rc;
+   if (sample_count < 0 || sample_count > INT32_MAX - r->pf.samples) return seterr(MDH_E_INVALID, "a sample count of at least 0, the samples so far and it below 2^31");
+   if ((rc = path_frame_state_check(r)) != MDH_OK || sample_count == 0) return rc;
+   hipStream_t qs = nullptr;
+   if ((rc = query_stream_get(r, &qs)) != MDH_OK || (rc = device_query_begin(r, &qs)) != MDH_OK) return rc;
+   PathFrameArgs a;
+   a.W = r->pf.W; a.H = r->pf.H;
+   a.tiles_x = (a.W + 7) / 8; a.n_tiles = a.tiles_x * ((a.H + 7) / 8);
+   a.bounces = r->pf.bounces; a.seed = r->pf.seed; a.jitter = r->pf.jitter;
+   a.sample_first = r->pf.samples; a.sample_count = sample_count;
+   a.sums = r->d_path_frame.ptr;
+   // the recorded primary segment where it can be used again: without jitter, in a launch of more than one sample (one sample
+   // has nothing to reuse and the record's registers cost it time: DESIGN.md section 4, "A path-traced frame"; the same bits)
+   const void *kernel = table_kernel(r, GK_k_path_frame, !r->pf.jitter && sample_count > 1 ? 1 : 0);
+   if (!kernel) return seterr(MDH_E_INVALID, "no kernel built for this variant");
+   const KCamera cam = r->pf.cam;
+   const unsigned blocks = (unsigned)((a.n_tiles + MDH_BLOCK / 64 - 1) / (MDH_BLOCK / 64));
+   if ((rc = query_enqueue(r, qs, qs, true, [&] { return launch_kernel_ptr(kernel, dim3(blocks), dim3(MDH_BLOCK), lds_bytes(r), qs, r->ks, cam, a); })) != MDH_OK) return rc;
+   r->pf.samples += sample_count;
+   return MDH_OK; // (nothing to copy: nothing waits)
+}
+static int path_frame_read_check(const mdh_renderer *r, int32_t tone_map)
+{
+   const int rc = path_frame_open_check(r);
+   if (rc != MDH_OK) return rc;
+   if (tone_map != 0 && tone_map != 1) return seterr(MDH_E_INVALID, "tone_map is 0 or 1");
+   if (r->pf.samples == 0) return seterr(MDH_E_STATE, "no sample has been accumulated: there is no 0 / 0 image");
+   return MDH_OK;
+}
+// the resolve on the query stream, where the sums are written, for arrays `caller`'s stream holds
+static int path_frame_resolve(mdh_renderer *r, int32_t tone_map, float *rgb, unsigned *rgba8, float *sums, hipStream_t qs, hipStream_t caller)
+{
+   if (!rgb && !rgba8 && !sums) return MDH_OK;
+   PathFrameResolveArgs a;
+   a.n = r->pf.W * r->pf.H; a.samples = r->pf.samples; a.tone_map = tone_map;
+   a.sums = r->d_path_frame.ptr; a.rgb = rgb; a.rgba8 = rgba8; a.sums_out = sums;
+   PassKernel k;
+   k.family = GK_k_path_frame_resolve;
+   if (caller != qs) HIP_TRY(r->bridge.create());
+   HIP_TRY(r->bridge.enter(qs, caller, nullptr));
+   const int rc = launch_kernel_ptr(kernel_ptr(k), dim3((unsigned)(((size_t)a.n + 255) / 256)), dim3(256), 0, qs, a);
+   if (rc != MDH_OK) return rc;
+   HIP_TRY(hipGetLastError());
+   HIP_TRY(r->bridge.leave(qs, caller, nullptr));
+   return MDH_OK;
+}
+extern "C" int32_t mdh_path_frame_read(mdh_renderer *r, int32_t tone_map, float *rgb_out, uint32_t *rgba8_out, float *sums_out, int32_t *samples_out)
+{
+   int rc = path_frame_read_check(r, tone_map);
+   if (rc != MDH_OK) return rc;
+   hipStream_t qs = nullptr;
+   RayStage st;
+   const size_t n = (size_t)r->pf.W * r->pf.H;
+   if ((rc = query_stream_get(r, &qs)) != MDH_OK || (rc = rays_stage(r, n, qs, st)) != MDH_OK) return rc;
+   if ((rc = path_frame_resolve(r, tone_map, rgb_out ? st.at(SLOT_RGB) : nullptr, rgba8_out ? st.at<unsigned>(SLOT_HIT) : nullptr, nullptr, qs, qs)) != MDH_OK) return rc;
+   st.down(rgb_out, SLOT_RGB, 3); st.down(rgba8_out, SLOT_HIT, 1);
+   HIP_TRY(st.err);
+   if (sums_out) HIP_TRY(hipMemcpyAsync(sums_out, r->d_path_frame.ptr, n * 12, hipMemcpyDeviceToHost, qs)); // (the raw sums: no kernel)
+   if ((rc = ray_query_wait(r)) != MDH_OK) return rc;
+   if (samples_out) *samples_out = r->pf.samples;
+   return MDH_OK;
+}
+extern "C" int32_t mdh_path_frame_read_device(mdh_renderer *r, int32_t tone_map, float *rgb_out, uint32_t *rgba8_out, float *sums_out, int32_t *samples_out,
+                                              void *stream)
+{
+   int rc = path_frame_read_check(r, tone_map);
+   if (rc != MDH_OK) return rc;
+   const size_t w = (size_t)r->pf.W * r->pf.H * 4;
+   const RayArray arrays[] = {{rgb_out, 3 * w, "colours"}, {rgba8_out, w, "rgba8"}, {sums_out, 3 * w, "colour sums"}};
+   if ((rc = ray_arrays_check(r, arrays)) != MDH_OK) return rc;
+   hipStream_t qs = nullptr;
+   if ((rc = query_stream_get(r, &qs, true)) != MDH_OK) return rc;
+   if ((rc = path_frame_resolve(r, tone_map, rgb_out, rgba8_out, sums_out, qs, (hipStream_t)stream)) != MDH_OK) return rc;
+   if (samples_out) *samples_out = r->pf.samples; // (the host's: the count is no result of the device)
+   return MDH_OK;
+}
+static int path_frame_rays_check(const mdh_renderer *r, int32_t sample, const float *org, const float *dir)
+{
+   const int rc = path_frame_open_check(r);
+   if (rc != MDH_OK) return rc;
+   if (sample < 0 || !org || !dir) return seterr(MDH_E_INVALID, "bad argument");
+   return MDH_OK;
+}
+static int path_frame_rays_launch(mdh_renderer *r, int32_t sample, float *d_org, float *d_dir, hipStream_t st)
+{
+   PassKernel k;
+   k.family = GK_k_path_frame_rays;
+   PathFrameRayArgs a = {r->pf.W, r->pf.H, r->pf.seed, sample, r->pf.jitter, d_org, d_dir};
+   const size_t n = (size_t)r->pf.W * r->pf.H;
+   const int rc = launch_kernel_ptr(kernel_ptr(k), dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, r->pf.cam, a);
+   if (rc != MDH_OK) return rc;
+   HIP_TRY(hipGetLastError());
+   return MDH_OK;
+}
+extern "C" int32_t mdh_path_frame_rays(mdh_renderer *r, int32_t sample, float *org_out, float *dir_out)
+{
+   int rc = path_frame_rays_check(r, sample, org_out, dir_out);
+   if (rc != MDH_OK) return rc;
+   hipStream_t qs = nullptr;
+   RayStage st;
+   if ((rc = query_stream_get(r, &qs)) != MDH_OK || (rc = rays_stage(r, (size_t)r->pf.W * r->pf.H, qs, st)) != MDH_OK) return rc;
+   if ((rc = path_frame_rays_launch(r, sample, st.at(SLOT_ORG), st.at(SLOT_DIR), qs)) != MDH_OK) return rc;
+   st.down(org_out, SLOT_ORG, 3); st.down(dir_out, SLOT_DIR, 3);
+   HIP_TRY(st.err);
+   HIP_TRY(hipStreamSynchronize(qs));
+   return MDH_OK;
+}
+extern "C" int32_t mdh_path_frame_rays_device(mdh_renderer *r, int32_t sample, float *org_out, float *dir_out, void *stream)
+{
+   int rc = path_frame_rays_check(r, sample, org_out, dir_out);
+   if (rc != MDH_OK) return rc;
+   const size_t bytes = (size_t)r->pf.W * r->pf.H * 12;
+   const RayArray arrays[] = {{org_out, bytes, "origins"}, {dir_out, bytes, "directions"}};
+   if ((rc = ray_arrays_check(r, arrays)) != MDH_OK) return rc;
+   return path_frame_rays_launch(r, sample, org_out, dir_out, (hipStream_t)stream); // (on the caller's stream itself, as mdh_camera_rays_device)
+}
+extern "C" int32_t mdh_path_frame_info(mdh_renderer *r, int32_t *width, int32_t *height, int32_t *samples, int32_t *bounces, int32_t *jitter)
+{
+   if (!r) return seterr(MDH_E_INVALID, "null renderer");
+   const bool open = r->pf.open; // (none open: zeros)
+   if (width) *width = open ? r->pf.W : 0;
+   if (height) *height = open ? r->pf.H : 0;
+   if (samples) *samples = open ? r->pf.samples : 0;
+   if (bounces) *bounces = open ? r->pf.bounces : 0;
+   if (jitter) *jitter = open ? r->pf.jitter : 0;
+   return MDH_OK;
+}
+extern "C" int32_t mdh_path_frame_end(mdh_renderer *r)
+{
+   if (!r) return seterr(MDH_E_INVALID, "null renderer");
+   r->pf.open = false;
+   r->pf.samples = 0;
+   if (!r->d_path_frame.ptr) return MDH_OK;
+   HIP_TRY(hipSetDevice(r->device));
+   if (r->query_stream) HIP_TRY(hipStreamSynchronize(r->query_stream)); // (whatever still reads or writes the sums)
+   HIP_TRY(r->d_path_frame.release());
+   return MDH_OK;
+}
+// the jitter by itself, on the host over the functions the lanes call (mdh_path.h): no launch, no renderer
+extern "C" int32_t mdh_path_pixel_uv(int32_t width, int32_t height, uint32_t seed, uint32_t id_first, int32_t n, int32_t sample, int32_t jitter, float *uv_out)
+{
+   if (!path_frame_size_valid(width, height) || n < 0 || sample < 0 || (jitter != 0 && jitter != 1) || (n > 0 && !uv_out)) return seterr(MDH_E_INVALID, "bad argument");
+   if ((uint64_t)id_first + (uint64_t)n > (uint64_t)width * (uint64_t)height) return seterr(MDH_E_INVALID, "the ids id_first .. id_first + n - 1 are pixels of the frame");
+   for (size_t q = 0; q < (size_t)n; ++q) {
+      const uint32_t id = id_first + (uint32_t)q;
+      path_pixel_uv((int)(id % (uint32_t)width), (int)(id / (uint32_t)width), width, height, seed, (uint32_t)sample, jitter != 0, uv_out[2 * q], uv_out[2 * q + 1]);
+   }
+   return MDH_OK;
+}
+
 
 // the hierarchy of the committed scene (pending edits are committed first): its nodes, leaves, depth and the length of the
 // always-evaluated list; all 0 while MDH_OPT_TRIANGLE_BVH is off or the scene declares no triangles
@@ -4822,8 +5025,10 @@ static const void *kernel_ptr_path(const PassKernel &k);
 static const void *kernel_ptr_inscatter(const PassKernel &k);
 static const void *kernel_ptr_sweep(const PassKernel &k);
 static const void *kernel_ptr_surface(const PassKernel &k);
+static const void *kernel_ptr_path_frame(const PassKernel &k);
 static const void *kernel_ptr(const PassKernel &k)
 {
+   if (k.family >= GK_k_path_frame && k.family <= GK_k_path_frame_resolve) return kernel_ptr_path_frame(k);
    if (k.family >= GK_k_surface_field && k.family <= GK_k_surface_vertices_listed) return kernel_ptr_surface(k);
    if (k.family == GK_k_listed || ((k.family == GK_k_ray_query || k.family == GK_k_ray_stream) && k.what >= MDH_RQ_SPHERECAST)) return kernel_ptr_sweep(k);
    if (k.family == GK_k_path_trace) return kernel_ptr_path(k); // (the newer families, named behind this function)
@@ -4945,3 +5150,16 @@ static const void *kernel_ptr_surface(const PassKernel &k)
    if (k.family == GK_k_surface_vertices_listed) return k.pf == 0 ? (const void *)k_surface_vertices_listed<false> : k.pf == MDH_PF_GTAB ? (const void *)k_surface_vertices_listed<true> : nullptr;
    return nullptr;
 }
+// ... and behind that a path-traced frame (mdh_path_frame_accumulate, .._rays, .._read; mdh_path_frame.h): k_path_trace's estimator
+// over a captured camera's pixels in the queries' variants, with and without the recorded primary segment, first named here;
+// the kernels of the rays and of the resolve read no scene and have no variants
+static const void *kernel_ptr_path_frame(const PassKernel &k)
+{
+#define MDH_PFR(PF) if (k.family == GK_k_path_frame && k.pf == (PF)) return k.what ? (const void *)k_path_frame<PF, true> : (const void *)k_path_frame<PF, false>;
+   MDH_PFR(0) MDH_PFR(1) MDH_PFR(9) MDH_PFR(64) MDH_PFR(65) MDH_PFR(73) MDH_PFR(192)
+#undef MDH_PFR
+   if (k.family == GK_k_path_frame_rays) return (const void *)k_path_frame_rays<>;
+   if (k.family == GK_k_path_frame_resolve) return (const void *)k_path_frame_resolve<>;
+   return nullptr;
+}
+

@@ -2423,6 +2423,8 @@ template <bool GTAB, int WHAT> __global__ __launch_bounds__(MDH_BLOCK) void k_li
 // the counts, their scan, the vertices and the quads, every slot a function of the grid alone.  The definition and the
 // kernels: mdh_surface.h.
 #include "mdh_surface.h"
+// ... and a path-traced frame: k_path_trace's estimator over the pixels of a captured camera, its rays and its resolve
+#include "mdh_path_frame.h"
 #endif
 
 // ---------------------------------------------------------------------- the window's pixels

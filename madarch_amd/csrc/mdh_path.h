@@ -34,6 +34,15 @@
 // rounding, so a bounce moves the shaded point by less than max_dist + 0.25, and up to MDH_PATH_MAX_BOUNCES bounces keep every
 // shadow ray below 13 246.  The scene's half is the host's path_scene_check (mdh_api.hip), which is shade_scene_check without
 // the probe grid: no probe is read.
+//
+// THE PIXELS OF A PATH-TRACED FRAME (mdh_path_frame_*, mdh_path_frame.h).  Pixel (i, j) of a W x H frame, row 0 at the top, has the
+// ray id j W + i -- the numbering of mdh_camera_rays -- and for sample s the screen position
+//    jx = jitter ? path_u01 (seed, id, s, 0, 3) : 0.5,   jy = jitter ? path_u01 (seed, id, s, 0, 4) : 0.5
+//    u = ((float)(2 i) + 2 jx) / (float) W - 1,   v = -(((float)(2 j) + 2 jy) / (float) H - 1)
+// each step one binary32 operation: dimensions 3 and 4 of bounce 0 are taken by nobody, path_scatter takes 0 .. 2 of every
+// bounce.  2 jx is exact and below 2, so a jittered position stays inside its pixel's footprint, and with 0.5 the numerator
+// is (float)(2 i + 1) -- which is how it is formed without jitter: tile_pixel's centre (mdh_kernels.h) and mdh_camera_rays'
+// rays to the bit at every size.
 #pragma once
 
 #include "mdh_ray_stream.h"
@@ -41,6 +50,11 @@
 #define MDH_PATH_FN MDH_RS_FN
 #define MDH_PATH_MAX_BOUNCES 6 // 5 322 + 6 x 1 025 + 1 774 = 13 246 < 2^14
 #define MDH_PATH_DIMS 3        // the numbers path_scatter takes per bounce
+#define MDH_PATH_DIM_JX 3      // ... and behind them, at bounce 0, the two of a frame's sub-pixel jitter
+#define MDH_PATH_DIM_JY 4
+#ifndef MDH_PATH_FRAME_MAX_PIXELS
+#define MDH_PATH_FRAME_MAX_PIXELS 67108864 // (madarch_hip.h) a frame's cap, 2^26: 805 MB of sums, every index of its kernels below 2^28
+#endif
 
 // ---------------------------------------------------------------------- the random numbers
 MDH_PATH_FN unsigned path_pcg(unsigned v)
@@ -61,6 +75,24 @@ MDH_PATH_FN float path_u01(unsigned seed, unsigned ray_id, unsigned sample, unsi
 {
    return (float)(path_hash(seed, ray_id, sample, bounce, dimension) >> 8) * 0x1p-24f; // (both exact)
 }
+
+// ---------------------------------------------------------------------- the pixels of a frame
+// one axis: pixel k of n, its jitter in [0, 1) or none
+MDH_PATH_FN float path_pixel_axis(int k, int n, bool jitter, float jk)
+{
+   const float num = jitter ? (float)(2 * k) + 2.0f * jk : (float)(2 * k + 1);
+   return num / (float)n - 1.0f;
+}
+// (u, v) of pixel (i, j) of a W x H frame for sample `sample`; row 0 = top
+MDH_PATH_FN void path_pixel_uv(int i, int j, int W, int H, unsigned seed, unsigned sample, bool jitter, float &u, float &v)
+{
+   const unsigned id = (unsigned)j * (unsigned)W + (unsigned)i;
+   const float jx = jitter ? path_u01(seed, id, sample, 0u, MDH_PATH_DIM_JX) : 0.5f;
+   const float jy = jitter ? path_u01(seed, id, sample, 0u, MDH_PATH_DIM_JY) : 0.5f;
+   u = path_pixel_axis(i, W, jitter, jx);
+   v = -path_pixel_axis(j, H, jitter, jy);
+}
+MDH_PATH_FN bool path_frame_size_valid(int W, int H) { return W >= 1 && H >= 1 && (long long)W * H <= (long long)MDH_PATH_FRAME_MAX_PIXELS; }
 
 // ---------------------------------------------------------------------- which rays are traced
 MDH_PATH_FN bool path_bounces_valid(int bounces) { return bounces >= 0 && bounces <= MDH_PATH_MAX_BOUNCES; }

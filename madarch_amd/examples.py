@@ -350,6 +350,24 @@ def path_traced_view(R, Width, Height, Samples=64, Bounces=3, Seed=1, Slice=16):
     return tone(traced), tone(frame), traced.reshape(Height, Width, 3), frame.reshape(Height, Width, 3)
 
 
+def path_traced_frame(R, Width, Height, Samples=64, Bounces=3, Seed=1, Jitter=True, Slice=16):
+    """What renderer R's camera sees, path traced into the renderer's own accumulator: Path_Frame_Begin, Path_Frame_Accumulate in
+    slices of `Slice` samples -- nothing is fetched or carried in between, the sums stay on the device -- and the resolve on the
+    device.  With Jitter every sample goes through its own point of its pixel, so edges are anti-aliased; without it the image is
+    path_traced_view's.  -> (tone-mapped (Height, Width, 3) float32, the window's bytes (Height, Width, 4) uint8, the linear
+    image (Height, Width, 3) float32)"""
+    R.Path_Frame_Begin(Width, Height, Seed=Seed, Bounces=Bounces, Jitter=Jitter)
+    first = 0
+    while first < Samples:
+        count = min(int(Slice), Samples - first)
+        R.Path_Frame_Accumulate(count)
+        first += count
+    shown = R.Path_Frame_Read(Tone_Map=True, Rgb=True, Rgba8=True)
+    linear = R.Path_Frame_Read(Tone_Map=False)["rgb"]
+    R.Path_Frame_End()
+    return shown["rgb"], shown["rgba8"], linear
+
+
 def scene_mesh(Path=None, R=None, Spacing=0.1, Binding=None):
     """The sphere and the box of the global_illumination room as a quad mesh, without the room's walls: Renderer.Surface_Mesh
     over the kinds (Sphere, Box) on a grid of `Spacing` round the two bodies, written to `Path` as Wavefront OBJ where one is

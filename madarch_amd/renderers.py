@@ -539,6 +539,125 @@ class Renderer:
         b.check(b.path_scatter(n, _fp(drs), _fp(nrm), _fp(rough), int(Seed), int(Id_First), int(Sample), int(Bounce), _fp(out)))
         return out
 
+    # ---- a path-traced frame: Path_Trace's estimator over the pixels of a frame of the camera, the sums kept on the device
+    @staticmethod
+    def _path_frame_args(Width, Height, Seed, Bounces, Jitter):
+        """ValueError before any library call"""
+        w, h = Renderer._frame_size(Width, Height)
+        if w * h > B.PATH_FRAME_MAX_PIXELS:
+            raise ValueError("a path-traced frame has at most 2^26 pixels, not %d x %d" % (w, h))
+        if not 0 <= int(Bounces) <= Renderer.MAX_BOUNCES:
+            raise ValueError("Bounces: paths take 0 to %d bounces, not %s" % (Renderer.MAX_BOUNCES, Bounces))
+        if not 0 <= int(Seed) < 2 ** 32:
+            raise ValueError("Seed: a 32-bit unsigned word, not %s" % (Seed,))
+        return w, h, int(Seed), int(Bounces), Renderer._flag(Jitter, "Jitter")
+
+    @staticmethod
+    def _flag(Value, What):
+        if isinstance(Value, (bool, np.bool_)) or (isinstance(Value, (int, np.integer)) and int(Value) in (0, 1)):
+            return int(Value)
+        raise ValueError("%s: True or False (0 or 1), not %r" % (What, Value))
+
+    def Path_Frame_Begin(self, Width, Height, Seed=0, Bounces=3, Jitter=True):
+        """opens, or restarts from zero, the renderer's accumulator of Width x Height pixels (any size, not the window's; at most
+        2^26 pixels): three float32 sums a pixel on the device.  The camera is captured as it stands, and Seed, Bounces and
+        Jitter are fixed.  Pixel (i, j), row 0 at the top, has the ray id j * Width + i; with Jitter every sample's ray goes
+        through its own point of the pixel's footprint, without it through the centre: Camera_Rays' rays to the bit."""
+        w, h, seed, nb, jit = self._path_frame_args(Width, Height, Seed, Bounces, Jitter)
+        self._b.check(self._b.path_frame_begin(self._h, w, h, seed, nb, jit))
+
+    def Path_Frame_Accumulate(self, Sample_Count=1):
+        """adds the next Sample_Count samples to every pixel and returns without waiting for the device.  The scene is the one
+        committed at the call; nothing is edited.  Restarting after an edit (Path_Frame_Begin again) is the caller's business.
+        Under OPT_TIMING Ray_Query_Time gives the kernel's time."""
+        if int(Sample_Count) < 0 or int(Sample_Count) > 2 ** 31 - 1:
+            raise ValueError("Sample_Count: %s samples" % (Sample_Count,))
+        self._b.check(self._b.path_frame_accumulate(self._h, int(Sample_Count)))
+
+    def Path_Frame_Info(self):
+        """{width, height, samples, bounces, jitter} of the accumulator; all 0 while none is open"""
+        v = [C.c_int32(0) for _ in range(5)]
+        self._b.check(self._b.path_frame_info(self._h, *[C.byref(x) for x in v]))
+        return dict(zip(("width", "height", "samples", "bounces", "jitter"), (x.value for x in v)))
+
+    def Path_Frame_Read(self, Tone_Map=False, Rgb=True, Rgba8=False, Sums=False):
+        """the resolve, on the device: {rgb (H, W, 3) float32 = sums / samples, with Tone_Map draw_screen.glsl:29 applied as
+        Shade_Rays applies it; rgba8 (H, W, 4) uint8 = that colour as the window's pixels hold it; sums (H, W, 3) the raw sums;
+        samples}, rows top first; only what was asked for is computed and copied"""
+        tm = self._flag(Tone_Map, "Tone_Map")
+        info = self.Path_Frame_Info()
+        w, h = info["width"], info["height"]
+        out = {}
+        if Rgb:
+            out["rgb"] = np.zeros((h, w, 3), np.float32)
+        if Rgba8:
+            out["rgba8"] = np.zeros((h, w, 4), np.uint8)
+        if Sums:
+            out["sums"] = np.zeros((h, w, 3), np.float32)
+        n = C.c_int32(0)
+        ptr = [_fp(out[k]) if k in out and out[k].size else None for k in ("rgb", "rgba8", "sums")]
+        self._b.check(self._b.path_frame_read(self._h, tm, ptr[0], ptr[1], ptr[2], C.byref(n)))
+        out["samples"] = n.value
+        return out
+
+    def Path_Frame_Read_Device(self, Width, Height, Rgb=None, Rgba8=None, Sums=None, Tone_Map=False, Stream=0):
+        """Path_Frame_Read into device memory, asynchronous and ordered with `Stream` as Shade_Rays_Device is; Width and Height
+        are the accumulator's (what the arrays are checked against here).  Rgb and Sums hold 3 float32 a pixel, Rgba8 one
+        int32 (the four bytes) a pixel; each may be None.  Returns the number of samples."""
+        tm = self._flag(Tone_Map, "Tone_Map")
+        w, h = self._frame_size(Width, Height)
+        dev = self._device_array
+        args = [dev(Rgb, "Rgb", 3 * w * h, "float32", True), dev(Rgba8, "Rgba8", w * h, "int32", True), dev(Sums, "Sums", 3 * w * h, "float32", True)]
+        n = C.c_int32(0)
+        self._b.check(self._b.path_frame_read_device(self._h, tm, *args, C.byref(n), C.c_void_p(int(Stream))))
+        return n.value
+
+    @staticmethod
+    def _sample(Sample):
+        if not 0 <= int(Sample) <= 2 ** 31 - 1:
+            raise ValueError("Sample: %s" % (Sample,))
+        return int(Sample)
+
+    def Path_Frame_Rays(self, Sample=0):
+        """(origins, directions), each (Width * Height, 3): the rays the accumulator gives its pixels for sample `Sample`,
+        computed on the device by the functions the accumulating kernel calls"""
+        s = self._sample(Sample)
+        info = self.Path_Frame_Info()
+        n = info["width"] * info["height"]
+        org = np.zeros((n, 3), np.float32)
+        drs = np.zeros((n, 3), np.float32)
+        self._b.check(self._b.path_frame_rays(self._h, s, _fp(org) if n else None, _fp(drs) if n else None))
+        return org, drs
+
+    def Path_Frame_Rays_Device(self, Width, Height, Origins, Directions, Sample=0, Stream=0):
+        """Path_Frame_Rays into device memory, enqueued on `Stream`; Width and Height are the accumulator's"""
+        s = self._sample(Sample)
+        w, h = self._frame_size(Width, Height)
+        dev = self._device_array
+        org, drs = dev(Origins, "Origins", 3 * w * h, "float32"), dev(Directions, "Directions", 3 * w * h, "float32")
+        self._b.check(self._b.path_frame_rays_device(self._h, s, org, drs, C.c_void_p(int(Stream))))
+
+    def Path_Frame_End(self):
+        """frees the accumulator (Destroy does too)"""
+        self._b.check(self._b.path_frame_end(self._h))
+
+    @staticmethod
+    def Path_Pixel_Uv(Width, Height, Seed=0, Id_First=0, N=None, Sample=0, Jitter=True, Binding=None):
+        """(N, 2) screen positions (u, v) of the pixels with ids Id_First .. Id_First + N - 1 (default: to the frame's end) of a
+        Width x Height frame for sample `Sample`: the jitter of Path_Frame_Accumulate by itself, on the host, the same bits --
+        no launch and no renderer"""
+        w, h, seed, _, jit = Renderer._path_frame_args(Width, Height, Seed, 0, Jitter)
+        s = Renderer._sample(Sample)
+        if not 0 <= int(Id_First) <= w * h:
+            raise ValueError("Id_First: a pixel of the frame, not %s" % (Id_First,))
+        n = w * h - int(Id_First) if N is None else int(N)
+        if n < 0 or int(Id_First) + n > w * h:
+            raise ValueError("N: %s pixels from %s on in a frame of %d" % (N, Id_First, w * h))
+        b = Binding or B.hip_binding()
+        uv = np.zeros((n, 2), np.float32)
+        b.check(b.path_pixel_uv(w, h, seed, int(Id_First), n, s, jit, _fp(uv) if n else None))
+        return uv
+
     # ---- the lights' fog at points and along rays of the host's (compute_frustrum_visibility.glsl:8-19,
     # accumulate_scattering.glsl:17-28), without the froxel grid or the camera it is bound to; ray-query plumbing, nothing edited
     INSCATTER_MAX_STEPS = 4096
