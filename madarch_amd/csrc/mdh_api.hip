@@ -274,16 +274,7 @@ extern "C" int32_t mdh_bvh_build(const float *tri_xyz, int32_t n_tris, void *nod
 #ifndef MDH_ATLAS_SETS
 #define MDH_ATLAS_SETS 3 // sets of probe atlases (and volumetric textures) that pipelined frames rotate through
 #endif
-// how often the probe rays (MDH_OPT_RADIANCE_ORDER) and the screen tiles (MDH_OPT_SCREEN_ORDER) are sorted again: every
-// MDH_RAD_RESORT passes, and after MDH_RAD_RESORT_MOVING passes when the geometry (or, for the tiles, the camera) changed
 #define MDH_LDS_WORKGROUP_BUDGET ((size_t)64 * 1024) // the LDS a workgroup may allocate: commit_scene fits the scene table into it, rad_replay_pick the recording kernel's rows
-#ifndef MDH_RAD_RESORT
-#define MDH_RAD_RESORT 64
-#endif
-#ifndef MDH_RAD_RESORT_MOVING
-#define MDH_RAD_RESORT_MOVING 8
-#endif
-
 
 struct mdh_renderer {
    int W = 0, H = 0, device = 0;
@@ -376,10 +367,8 @@ struct mdh_renderer {
    DevBuf<float> d_irr_taps;     // k_irradiance's scratch: the taps of the pass's probes (mdh_kernels.h)
    DevBuf<unsigned char> d_rad_steps;      // one group, sized for d_rad_steps.cap rays (pass_radiance)
    DevBuf<unsigned> d_rad_order, d_rad_hist;
-   long rad_order_rays = 0;                // rays the stored order is of (0: none)
-   int rad_order_begin = -1;               // ... and the first probe of their slice
-   int rad_order_age = 0;                  // radiance passes since the rays were sorted
-   unsigned long rad_order_scene = 0, geometry_edits = 0; // primitives set or added when the rays were sorted / so far
+   ResortClock<RadOrderOf> rad_order;      // when they are sorted again, and what the stored order is of (pass_radiance)
+   unsigned long geometry_edits = 0;       // primitives set or added so far
    int opt_rad_order = MDH_RAD_ORDER_DEFAULT;
    // MDH_OPT_RADIANCE_REPLAY (mdh_march.h: RayRecord): one record per probe ray of the slice, indexed by the ray.
    // ONE buffer serves all three atlas sets: a record holds nothing of an atlas, and it is written and read by radiance
@@ -388,26 +377,8 @@ struct mdh_renderer {
    // frames go in flight again) -- the order that d_rad_order relies on between the pass that sorts and the pass that reads.
    // It is allocated, grown and freed like d_rad_steps / d_rad_order: with both streams drained.
    DevBuf<RayRecord> d_rad_rec;            // (its capacity: rays)
-   struct RadRecKey {                      // everything a probe ray's marches read (rad_rec_key): records are valid for one value of it
-      unsigned long geometry, inputs;      // geometry_edits, march_inputs
-      unsigned long long part_version;     // Update_Partitioning's builds
-      long rays;
-      int grid[3], res[2], pc[2], probe_begin, probe_end;
-      float spacing[3], max_dist;
-      int pf, small, jit, residency, bvh, table_f4, part_bits_f4;
-      bool operator==(const RadRecKey &o) const
-      {
-         return geometry == o.geometry && inputs == o.inputs && part_version == o.part_version && rays == o.rays &&
-                memcmp(grid, o.grid, sizeof grid) == 0 && memcmp(res, o.res, sizeof res) == 0 && memcmp(pc, o.pc, sizeof pc) == 0 &&
-                probe_begin == o.probe_begin && probe_end == o.probe_end && memcmp(spacing, o.spacing, sizeof spacing) == 0 && // (bits: a NaN spacing still equals itself)
-                memcmp(&max_dist, &o.max_dist, sizeof max_dist) == 0 && pf == o.pf && small == o.small && jit == o.jit && residency == o.residency &&
-                bvh == o.bvh && table_f4 == o.table_f4 && part_bits_f4 == o.part_bits_f4;
-      }
-   };
-   RadRecKey rad_rec_key, rad_seen_key;    // what the records are of / what the previous radiance pass marched through
-   bool rad_rec_valid = false, rad_seen_valid = false;
+   ReplaySchedule<RadRecKey> rad_replay;   // march, record or replay (rad_replay_pick chooses, pass_radiance reports)
    unsigned long march_inputs = 0;         // edits besides geometry_edits that change what a march kernel reads or which one runs (options, partition builds)
-   long long rad_replay_stats[3] = {0, 0, 0}; // radiance passes launched marching, recording, replaying
    int opt_rad_replay = 1;
    // MDH_OPT_SCREEN_REPLAY (mdh_march.h: PixelRecord): one record per pixel of the rank's tiles, indexed by the pixel
    // (mdh_kernels.h: screen_record_index).  ONE buffer: a record holds nothing of an atlas, a framebuffer or a light.  Screen
@@ -418,33 +389,15 @@ struct mdh_renderer {
    DevBuf<PixelRecord> d_scr_rec;          // (its capacity: pixels, own tiles * 64)
    Fence scr_rec_written;                  // one group, created with the first records (pass_screen)
    RingUse<1> scr_rec_reads;
-   struct ScrRecKey {                      // everything a screen march reads, and what decides which pixel holds what (scr_rec_key)
-      RadRecKey march;                     // geometry, probe grid, max_dist, table layout, residency, BVH, JIT, the kernel's variant word
-      float cam[12];                       // position and orientation BY VALUE: setting the camera to where it is changes nothing
-      int W, H, rank, world, mode, spec, ao, gbuffer, window, split;
-      unsigned long reflect_edits;         // Set_Material calls that took a material in use below the reflection's roughness threshold
-      bool operator==(const ScrRecKey &o) const
-      {
-         return march == o.march && memcmp(cam, o.cam, sizeof cam) == 0 && W == o.W && H == o.H && rank == o.rank && world == o.world && mode == o.mode &&
-                spec == o.spec && ao == o.ao && gbuffer == o.gbuffer && window == o.window && split == o.split && reflect_edits == o.reflect_edits;
-      }
-   };
-   ScrRecKey scr_rec_key, scr_seen_key;    // what the records are of / what the previous screen pass marched through
-   bool scr_rec_valid = false, scr_seen_valid = false;
+   ReplaySchedule<ScrRecKey> scr_replay;   // march, record or replay (scr_replay_pick chooses, pass_screen reports); alone in surviving a failed allocation of its records
    unsigned long reflect_edits = 0;
-   bool scr_rec_no_memory = false;         // the records' allocation failed: no further attempt until the key or the option changes
-   long long scr_replay_stats[3] = {0, 0, 0}; // screen passes launched marching, recording, replaying
    int opt_scr_replay = 0;
    // MDH_OPT_SCREEN_ORDER (ScreenArgs, mdh_kernels.h): the screen pass's tiles in the order of their wavefronts' durations
    // (the three buffers and the two events are one group, created by the first pass that sorts: pass_screen)
    DevBuf<unsigned char> d_scr_cost;             // [tiles] sort keys, written by the pass that is followed by a sort
    DevBuf<unsigned> d_scr_order[2];              // [tiles] two buffers: passes in flight keep reading the one they were launched with
    DevBuf<unsigned> d_scr_hist;
-   int scr_order_cur = -1;                       // the buffer that holds the order (-1: none)
-   int scr_order_n = 0, scr_order_rank = -1, scr_order_world = -1; // what that order is of
-   int scr_order_age = 0;                        // screen passes since the tiles were sorted
-   unsigned long scr_order_geom = 0;             // geometry_edits when they were
-   float scr_order_cam[12] = {0};                // the camera then
+   ResortClock<ScrOrderOf> scr_order;            // when they are sorted again, and what the stored order is of (pass_screen, screen_sort_tiles)
    Fence scr_sorted;                             // the last sort
    Event ev_scr_other;
    int opt_scr_order = 1;
@@ -1256,13 +1209,13 @@ extern "C" int32_t mdh_set_option(mdh_renderer *r, int32_t option, int32_t value
       break;
    case MDH_OPT_FRAME_OVERLAP:
       if (value < 0 || value > 2) return seterr(MDH_E_INVALID, "frame overlap is 0, 1 or 2");
-      if ((value != 0) != (r->opt_overlap != 0)) r->scr_order_age = MDH_RAD_RESORT; // (how much of the screen pass is sorted follows the schedule: sort again)
+      if ((value != 0) != (r->opt_overlap != 0)) r->scr_order.force(); // (how much of the screen pass is sorted follows the schedule: sort again)
       r->opt_overlap = value;
       break;
    case MDH_OPT_INDIRECT_SPECULAR: if (value < 0 || value > 3) return seterr(MDH_E_INVALID, "indirect specular mode is 0 .. 3"); r->opt_spec = value; break;
    case MDH_OPT_HYSTERESIS_PERMILLE: if (value < 0 || value > 999) return seterr(MDH_E_INVALID, "hysteresis is 0 .. 999 per mille"); r->opt_hyst = value; break;
-   case MDH_OPT_RADIANCE_ORDER: r->opt_rad_order = value ? 1 : 0; r->rad_order_rays = 0; break;
-   case MDH_OPT_SCREEN_ORDER: r->opt_scr_order = value ? 1 : 0; r->scr_order_cur = -1; break;
+   case MDH_OPT_RADIANCE_ORDER: r->opt_rad_order = value ? 1 : 0; r->rad_order.forget(); break;
+   case MDH_OPT_SCREEN_ORDER: r->opt_scr_order = value ? 1 : 0; r->scr_order.forget(); break;
    case MDH_OPT_SCREEN_SPLIT: if (value < 0) return seterr(MDH_E_INVALID, "MDH_OPT_SCREEN_SPLIT: a number of wavefronts"); r->opt_scr_split = value; break;
    case MDH_OPT_NUMERICS: if (value != (MDH_FAST_NUMERICS ? 1 : (MDH_HYBRID_NUMERICS ? 2 : 0))) return seterr(MDH_E_STATE, "the numerics are a property of the library build (make fast builds the experiment)"); break;
    case MDH_OPT_TABLE_RESIDENCY:
@@ -1294,8 +1247,8 @@ extern "C" int32_t mdh_set_option(mdh_renderer *r, int32_t option, int32_t value
    }
    case MDH_OPT_RADIANCE_REPLAY:
       r->opt_rad_replay = value ? 1 : 0;
+      r->rad_replay.option_set(r->opt_rad_replay != 0, false); // (the previous pass stays seen: a key that stands is recorded by the first pass after the option comes back on)
       if (!r->opt_rad_replay) { // the records are dropped (the buffer itself with the streams drained: never under an open frame)
-         r->rad_rec_valid = false;
          if (r->d_rad_rec.ptr && !r->in_frame) {
             HIP_TRY(hipSetDevice(r->device));
             { int sr = sync_streams(r, SYNC_PROBE | SYNC_MAIN); if (sr != MDH_OK) return sr; }
@@ -1305,10 +1258,8 @@ extern "C" int32_t mdh_set_option(mdh_renderer *r, int32_t option, int32_t value
       break;
    case MDH_OPT_SCREEN_REPLAY:
       r->opt_scr_replay = value ? 1 : 0;
-      r->scr_rec_no_memory = false;
+      r->scr_replay.option_set(r->opt_scr_replay != 0, true); // (off forgets the previous pass too: the first pass after the option comes back on marches plainly)
       if (!r->opt_scr_replay) { // the records are dropped (the buffer itself with the streams drained: never under an open frame)
-         r->scr_rec_valid = false;
-         r->scr_seen_valid = false;
          if (r->d_scr_rec.ptr && !r->in_frame) {
             HIP_TRY(hipSetDevice(r->device));
             int drc = drain_streams(r);
@@ -1956,9 +1907,9 @@ static bool rad_mips_used(const mdh_renderer *r, int set) { return r->opt_mips &
 #define MDH_RAD_REPLAY_BUILT (MDH_RAD_REPLAY && MDH_RAD_QVIS && MDH_SHARE_FIRST_STEP)
 static bool rad_replay_built(const PassKernel &k) { return MDH_RAD_REPLAY_BUILT && !k.jit && (k.pf & ~(MDH_PF_ROOM | MDH_PF_POW2)) == 0; }
 // everything the marches of this renderer's probe rays read, and the kernel that runs them
-static mdh_renderer::RadRecKey rad_rec_key(const mdh_renderer *r, const PassKernel &k)
+static RadRecKey rad_rec_key(const mdh_renderer *r, const PassKernel &k)
 {
-   mdh_renderer::RadRecKey q = {};
+   RadRecKey q = {};
    const KProbes p = make_probes(r);
    q.geometry = r->geometry_edits; q.inputs = r->march_inputs; q.part_version = r->part_fence.version;
    q.grid[0] = p.gx; q.grid[1] = p.gy; q.grid[2] = p.gz;
@@ -1971,19 +1922,15 @@ static mdh_renderer::RadRecKey rad_rec_key(const mdh_renderer *r, const PassKern
    q.table_f4 = r->ks.table_f4; q.part_bits_f4 = r->ks.part_bits_f4;
    return q;
 }
-// The schedule: geometry that changed since the previous radiance pass is marched by the plain kernel; geometry that stood
-// still for one pass is marched once more, by the recording kernel; valid records are replayed.
+// The schedule is ReplaySchedule's (mdh_host.h); here, what makes the recording kernel admissible.
 static int rad_replay_pick(const mdh_renderer *r, const PassKernel &k)
 {
-   if (!r->opt_rad_replay || !rad_replay_built(k)) return 0;
-   const mdh_renderer::RadRecKey now = rad_rec_key(r, k);
-   if (r->rad_rec_valid && r->d_rad_rec.ptr && now == r->rad_rec_key) return 2;
+   const RadRecKey now = rad_rec_key(r, k);
    // (the recording kernel parks five rows more than the marching one: a table that commit_scene fitted into the workgroup's LDS
    //  budget beside MDH_PARK_DWORDS rows may not fit beside these -- such a scene keeps marching, and the counters say so)
-   if (r->rad_seen_valid && now == r->rad_seen_key && now.rays > 0 && now.rays < (1l << 31) &&
-       lds_bytes(r) + (size_t)MDH_RECORD_PARK_ROWS * MDH_BLOCK * sizeof(float) <= MDH_LDS_WORKGROUP_BUDGET)
-      return 1;
-   return 0;
+   const bool admissible = now.rays > 0 && now.rays < (1l << 31) &&
+                           lds_bytes(r) + (size_t)MDH_RECORD_PARK_ROWS * MDH_BLOCK * sizeof(float) <= MDH_LDS_WORKGROUP_BUDGET;
+   return r->rad_replay.choose(now, r->opt_rad_replay && rad_replay_built(k), r->d_rad_rec.ptr != nullptr, admissible);
 }
 
 // MDH_OPT_SCREEN_REPLAY ("Exact work elimination", item 12).  The variants built with record and replay
@@ -2001,9 +1948,9 @@ static bool scr_replay_built(const PassKernel &k) { return MDH_SCR_REPLAY_BUILT 
 //   mdh_add_material, mdh_set_light, mdh_write_texture, mdh_write_atlas_slice, MDH_OPT_ATLAS_FORMAT, _HYSTERESIS_PERMILLE,
 //   _SCREEN_ORDER, _FRAME_OVERLAP, _TIMING, _RADIANCE_*   nothing: a record holds nothing they change
 // (width, height, probe grid, spacing, resolutions and max_dist are fixed at mdh_create; the key holds them all the same)
-static mdh_renderer::ScrRecKey scr_rec_key(const mdh_renderer *r, const PassKernel &k)
+static ScrRecKey scr_rec_key(const mdh_renderer *r, const PassKernel &k)
 {
-   mdh_renderer::ScrRecKey q = {};
+   ScrRecKey q = {};
    q.march = rad_rec_key(r, k);
    q.march.small = k.gbuf ? 1 : 0; // (k_radiance's SMALL has no meaning here: the kernel's other template argument)
    q.march.probe_begin = q.march.probe_end = 0; q.march.rays = 0; // (the radiance pass's slice: a screen march reads every probe's place, none of its rays)
@@ -2018,21 +1965,15 @@ static long scr_rec_pixels(const mdh_renderer *r)
    const long tiles = (long)((r->W + 7) / 8) * ((r->H + 7) / 8);
    return r->opt_rank < r->opt_world ? (tiles - r->opt_rank + r->opt_world - 1) / r->opt_world * 64 : 0;
 }
-// The schedule: what changed since the previous screen pass is marched by the plain kernel; what stood still for one pass is
-// marched once more, by the recording kernel; valid records are replayed.
+// The schedule is ReplaySchedule's (mdh_host.h); here, what makes the recording kernel admissible.
 static int scr_replay_pick(const mdh_renderer *r, const PassKernel &k)
 {
-   if (!r->opt_scr_replay || !scr_replay_built(k)) return 0;
-   const mdh_renderer::ScrRecKey now = scr_rec_key(r, k);
-   if (r->scr_rec_valid && r->d_scr_rec.ptr && now == r->scr_rec_key) return 2;
-   if (r->scr_rec_no_memory && r->scr_seen_valid && now == r->scr_seen_key) return 0; // (the allocation failed for this key: not tried again, and no stream drained, in every frame)
    // (the recording kernel parks eleven rows more than the marching one: a table that commit_scene fitted into the workgroup's
    //  LDS budget beside MDH_PARK_DWORDS rows may not fit beside these -- such a scene keeps marching, and the counters say so;
    //  the second point's arg-min index shares a word: tables of 2^22 entries and more keep marching too)
-   if (r->scr_seen_valid && now == r->scr_seen_key && scr_rec_pixels(r) > 0 && r->ks.table_f4 < (int)MDH_REC2_INDEX_MASK &&
-       lds_bytes(r) + (size_t)MDH_SCR_RECORD_PARK_ROWS * MDH_BLOCK * sizeof(float) <= MDH_LDS_WORKGROUP_BUDGET)
-      return 1;
-   return 0;
+   const bool admissible = scr_rec_pixels(r) > 0 && r->ks.table_f4 < (int)MDH_REC2_INDEX_MASK &&
+                           lds_bytes(r) + (size_t)MDH_SCR_RECORD_PARK_ROWS * MDH_BLOCK * sizeof(float) <= MDH_LDS_WORKGROUP_BUDGET;
+   return r->scr_replay.choose(scr_rec_key(r, k), r->opt_scr_replay && scr_replay_built(k), r->d_scr_rec.ptr != nullptr, admissible);
 }
 
 static PassKernel pick_kernel(const mdh_renderer *r, int pass, int set)
@@ -2204,7 +2145,7 @@ static int pass_radiance(PassRun &p)
    // MDH_OPT_RADIANCE_REPLAY: the pass that writes the rays' records, or reads them (pick_kernel chose: p.k.rec)
    if (p.k.rec == 1 && (size_t)rays > r->d_rad_rec.cap) { // (the buffer is only ever used by radiance passes, on the probe stream or the main stream)
       { int sr = sync_streams(r, SYNC_PROBE | SYNC_MAIN); if (sr != MDH_OK) return sr; }
-      r->rad_rec_valid = false;
+      r->rad_replay.records_gone();
       HIP_TRY(r->d_rad_rec.grow((size_t)rays));
    }
    if (p.k.rec) ro.rec = r->d_rad_rec.ptr;
@@ -2215,17 +2156,16 @@ static int pass_radiance(PassRun &p)
       if ((size_t)rays > r->d_rad_steps.cap) {
          // (the buffers are only ever used by radiance passes, on the probe stream or the main stream)
          { int sr = sync_streams(r, SYNC_PROBE | SYNC_MAIN); if (sr != MDH_OK) return sr; }
-         r->rad_order_rays = 0;
+         r->rad_order.forget();
          HIP_TRY(create_all(r->d_rad_steps.sized((size_t)rays), r->d_rad_order.sized((size_t)rays), r->d_rad_hist.sized(256 * MDH_RO_MAX_CHUNKS)));
       }
-      const bool have = r->rad_order_rays == rays && r->rad_order_begin == pr.probe_begin;
+      const bool have = r->rad_order.ordered && r->rad_order.of.rays == rays && r->rad_order.of.begin == pr.probe_begin;
       if (have) { ro.order = r->d_rad_order.ptr; n = rays; }
       // A probe ray's march changes with the scene's geometry, not with time, lights or materials: the rays are sorted
       // again when primitives were set or added since (at most every MDH_RAD_RESORT_MOVING passes: a stale order costs
       // speed only, and three more launches per frame cost the host of a 0.4 ms frame 10 %) and every MDH_RAD_RESORT
       // passes besides -- the sort kernels (20 us) are out of almost every frame.
-      ++r->rad_order_age;
-      if (!have || r->rad_order_age >= MDH_RAD_RESORT || (r->rad_order_scene != r->geometry_edits && r->rad_order_age >= MDH_RAD_RESORT_MOVING)) ro.steps = r->d_rad_steps.ptr;
+      if (r->rad_order.due(have, r->rad_order.of.scene != r->geometry_edits)) ro.steps = r->d_rad_steps.ptr;
    }
    n = (n + 63) / 64 * 64;
    const int blocks = (int)((n + MDH_BLOCK - 1) / MDH_BLOCK);
@@ -2234,24 +2174,15 @@ static int pass_radiance(PassRun &p)
    struct Args { KScene sc; KProbes pr; int first_round; RadOrder ro; };
    const int rc = launch_pass<Args>(p, blocks, lds, r->ks, pr, rad_first_round(r, p.kernel, p.fn, lds, blocks), ro);
    if (rc != MDH_OK) return rc;
-   { // what this pass marched through (or replayed), for the next pass's choice
-      const mdh_renderer::RadRecKey now = rad_rec_key(r, p.k);
-      if (p.k.rec == 1) { r->rad_rec_key = now; r->rad_rec_valid = true; }
-      else if (p.k.rec == 0) r->rad_rec_valid = false; // (the geometry moved, the option is off or this variant only marches)
-      r->rad_seen_key = now;
-      r->rad_seen_valid = true;
-      ++r->rad_replay_stats[p.k.rec];
-   }
+   r->rad_replay.ran(p.k.rec, rad_rec_key(r, p.k), true); // what this pass marched through (or replayed), for the next pass's choice
    if (ro.steps) { // the next pass's order from this pass's step counts
       hipLaunchKernelGGL(k_rad_hist, dim3(ro_chunks), dim3(256), 0, st, (const unsigned char *)r->d_rad_steps.ptr, (int)rays, (int)ro_chunk, r->d_rad_hist.ptr);
       hipLaunchKernelGGL(k_rad_scan, dim3(1), dim3(256), 0, st, r->d_rad_hist.ptr, ro_chunks);
       hipLaunchKernelGGL(k_rad_scatter, dim3(ro_chunks), dim3(256), 0, st, (const unsigned char *)r->d_rad_steps.ptr, (int)rays, (int)ro_chunk, (const unsigned *)r->d_rad_hist.ptr, r->d_rad_order.ptr);
-      r->rad_order_rays = rays;
-      r->rad_order_begin = pr.probe_begin;
-      r->rad_order_age = 0;
-      r->rad_order_scene = r->geometry_edits;
+      r->rad_order.of = {rays, pr.probe_begin, r->geometry_edits};
+      r->rad_order.sorted();
    } else if (!ro.order)
-      r->rad_order_rays = 0;
+      r->rad_order.forget();
    return MDH_OK;
 }
 
@@ -2362,11 +2293,12 @@ static int screen_sort_tiles(PassRun &p, const ScreenArgs &a)
       r->pending.push_back({p.pass, p.e0, p.e1});
       p.e0 = p.e1 = nullptr;
    }
-   const int nb = r->scr_order_cur == 0 ? 1 : 0;
+   ScrOrderOf &of = r->scr_order.of;
+   const int nb = r->scr_order.ordered && of.buf == 0 ? 1 : 0;
    // (passes that read that buffer were launched before the previous sort; on the other screen stream nothing
    //  orders them against this stream when no probe passes run: wait for what that stream holds)
    hipStream_t other = st == r->alt_stream ? r->stream : r->alt_stream;
-   if (other && other != st && r->scr_order_cur >= 0) {
+   if (other && other != st && r->scr_order.ordered) {
       HIP_TRY(hipEventRecord(r->ev_scr_other.ev, other));
       HIP_TRY(hipStreamWaitEvent(st, r->ev_scr_other.ev, 0));
    }
@@ -2391,10 +2323,9 @@ static int screen_sort_tiles(PassRun &p, const ScreenArgs &a)
    hipLaunchKernelGGL(k_order_scatter_stable, dim3(chunks), dim3(256), 0, st, (const unsigned char *)r->d_scr_cost.ptr, own_tiles, (int)chunk, (const unsigned *)r->d_scr_hist.ptr, r->d_scr_order[nb].ptr);
    HIP_TRY(hipGetLastError());
    HIP_TRY(r->scr_sorted.signal(st, si_st));
-   r->scr_order_cur = nb;
-   r->scr_order_n = own_tiles; r->scr_order_rank = a.rank; r->scr_order_world = a.world;
-   r->scr_order_age = 0;
-   r->scr_order_geom = r->geometry_edits;
+   of.buf = nb; of.n = own_tiles; of.rank = a.rank; of.world = a.world;
+   of.geom = r->geometry_edits; // (the camera was stamped when the sort was decided: pass_screen)
+   r->scr_order.sorted();
    return MDH_OK;
 }
 
@@ -2440,22 +2371,22 @@ static int pass_screen(PassRun &p)
                             r->d_scr_hist.sized(256 * MDH_RO_MAX_CHUNKS), r->scr_sorted, r->ev_scr_other));
       float cam_now[12];
       memcpy(cam_now, r->cam_pos, 12); memcpy(cam_now + 3, r->cam_m, 36);
-      const bool have = r->scr_order_cur >= 0 && r->scr_order_n == own_tiles && r->scr_order_rank == a.rank && r->scr_order_world == a.world;
+      ScrOrderOf &of = r->scr_order.of;
+      const bool have = r->scr_order.ordered && of.n == own_tiles && of.rank == a.rank && of.world == a.world;
       if (have) {
-         a.order = r->d_scr_order[r->scr_order_cur].ptr;
+         a.order = r->d_scr_order[of.buf].ptr;
          HIP_TRY(r->scr_sorted.wait(st, si_st)); // (the sort may have run on another stream)
       }
       // which tiles are slow follows the camera and the geometry: sorted again when either changed since (at most every
       // MDH_RAD_RESORT_MOVING passes: a stale order costs speed only) and every MDH_RAD_RESORT passes besides
-      ++r->scr_order_age;
-      const bool moved = memcmp(cam_now, r->scr_order_cam, sizeof cam_now) != 0 || r->scr_order_geom != r->geometry_edits;
-      if (!have || r->scr_order_age >= MDH_RAD_RESORT || (moved && r->scr_order_age >= MDH_RAD_RESORT_MOVING)) {
+      const bool moved = memcmp(cam_now, of.cam, sizeof cam_now) != 0 || of.geom != r->geometry_edits;
+      if (r->scr_order.due(have, moved)) {
          sort_after = true;
          a.cost = r->d_scr_cost.ptr;
-         memcpy(r->scr_order_cam, cam_now, sizeof cam_now);
+         memcpy(of.cam, cam_now, sizeof cam_now);
       }
    } else
-      r->scr_order_cur = -1;
+      r->scr_order.forget();
    // MDH_OPT_SCREEN_SPLIT (ScreenArgs::split): launches that leave most of the chip's wavefront slots empty give a tile to
    // two or four wavefronts; never with a tile order (launches of 2 048 tiles and more)
    a.split = 0;
@@ -2469,11 +2400,11 @@ static int pass_screen(PassRun &p)
    if (p.k.rec == 1 && (size_t)own_tiles * 64 > r->d_scr_rec.cap) {
       int drc = drain_streams(r);
       if (drc != MDH_OK) return drc;
-      r->scr_rec_valid = false;
+      r->scr_replay.records_gone();
       r->scr_rec_reads.forget();
       HIP_TRY(create_all(r->scr_rec_written, r->scr_rec_reads)); // (only with the first records: events are scarce, mdh_create)
       if (r->d_scr_rec.grow((size_t)own_tiles * 64) != hipSuccess) { // no memory for the records: the renderer keeps marching, and the counters say so
-         r->scr_rec_no_memory = true;
+         r->scr_replay.allocation_failed();
          (void)hipGetLastError();
          p.k.rec = 0;
          if (!(p.kernel = kernel_ptr(p.k))) return seterr(MDH_E_INVALID, "no kernel built for this pass's variant");
@@ -2495,17 +2426,9 @@ static int pass_screen(PassRun &p)
    }
    { // what this pass marched through (or replayed), for the next pass's choice
       const int si_st = stream_index(r, st);
-      const mdh_renderer::ScrRecKey now = scr_rec_key(r, p.k);
-      if (p.k.rec == 1) {
-         r->scr_rec_key = now; r->scr_rec_valid = true;
-         HIP_TRY(r->scr_rec_written.signal(st, si_st));
-      } else if (p.k.rec == 2) {
-         HIP_TRY(r->scr_rec_reads.mark(0, st, si_st));
-      } else r->scr_rec_valid = false; // (something moved, the option is off or this variant only marches)
-      if (!(r->scr_seen_valid && now == r->scr_seen_key)) r->scr_rec_no_memory = false; // (a new key: the allocation may be tried again)
-      r->scr_seen_key = now;
-      r->scr_seen_valid = r->opt_scr_replay != 0;
-      ++r->scr_replay_stats[p.k.rec];
+      if (p.k.rec == 1) HIP_TRY(r->scr_rec_written.signal(st, si_st));
+      else if (p.k.rec == 2) HIP_TRY(r->scr_rec_reads.mark(0, st, si_st));
+      r->scr_replay.ran(p.k.rec, scr_rec_key(r, p.k), r->opt_scr_replay != 0); // (with the option off the next pass marches plainly whatever its key)
    }
    return sort_after ? screen_sort_tiles(p, a) : MDH_OK;
 }
@@ -2839,7 +2762,7 @@ static void peer_leave(mdh_renderer *r)
       p->active = false;
       r->opt_rank = 0;
       r->opt_world = 1;
-      r->rad_order_rays = 0;
+      r->rad_order.forget();
       r->fb_owner[0][0] = r->fb_owner[1][0] = -1;
    }
 }
@@ -2928,7 +2851,7 @@ extern "C" int32_t mdh_peer_init(mdh_renderer *r, const uint8_t *blobs, int32_t 
    p->active = true;
    r->opt_rank = rank;
    r->opt_world = world;
-   r->rad_order_rays = 0;
+   r->rad_order.forget();
    return MDH_OK;
 }
 static int peer_exchange(mdh_renderer *r, int tex)
@@ -3002,7 +2925,7 @@ extern "C" int32_t mdh_comm_init(mdh_renderer *r, const uint8_t id_in[MDH_COMM_I
    r->comm = comm;
    r->opt_rank = rank;
    r->opt_world = world;
-   r->rad_order_rays = 0; // (the stored ray order is of another slice)
+   r->rad_order.forget(); // (the stored ray order is of another slice)
    return MDH_OK;
 }
 // the renderer is rank 0 of 1 again (the handle itself is the caller's business)
@@ -3013,7 +2936,7 @@ static void comm_forget(mdh_renderer *r)
    r->comm_aborted = false;
    r->opt_rank = 0;
    r->opt_world = 1;
-   r->rad_order_rays = 0;
+   r->rad_order.forget();
    r->fb_owner[0][0] = r->fb_owner[1][0] = -1; // (the framebuffers hold a rank's tiles: cleared before they are drawn whole)
 }
 static int comm_drop(mdh_renderer *r, bool abort)
@@ -4800,9 +4723,9 @@ extern "C" int32_t mdh_diag_best_first(unsigned long long *out4)
 extern "C" int32_t mdh_screen_replay_stats(mdh_renderer *r, int64_t *plain, int64_t *recording, int64_t *replaying)
 {
    if (!r) return seterr(MDH_E_INVALID, "null renderer");
-   if (plain) *plain = r->scr_replay_stats[0];
-   if (recording) *recording = r->scr_replay_stats[1];
-   if (replaying) *replaying = r->scr_replay_stats[2];
+   if (plain) *plain = r->scr_replay.stats[0];
+   if (recording) *recording = r->scr_replay.stats[1];
+   if (replaying) *replaying = r->scr_replay.stats[2];
    return MDH_OK;
 }
 // the size of a pixel's record (tests/test_screen_replay_host.py holds DESIGN.md's figure against it)
@@ -4822,9 +4745,9 @@ extern "C" int32_t mdh_probe_settle_stats(mdh_renderer *r, int64_t *run, int64_t
 extern "C" int32_t mdh_radiance_replay_stats(mdh_renderer *r, int64_t *plain, int64_t *recording, int64_t *replaying)
 {
    if (!r) return seterr(MDH_E_INVALID, "null renderer");
-   if (plain) *plain = r->rad_replay_stats[0];
-   if (recording) *recording = r->rad_replay_stats[1];
-   if (replaying) *replaying = r->rad_replay_stats[2];
+   if (plain) *plain = r->rad_replay.stats[0];
+   if (recording) *recording = r->rad_replay.stats[1];
+   if (replaying) *replaying = r->rad_replay.stats[2];
    return MDH_OK;
 }
 extern "C" int32_t mdh_pass_time(mdh_renderer *r, int32_t pass, double *ms, int64_t *launches)

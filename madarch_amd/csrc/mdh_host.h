@@ -1,6 +1,7 @@
 // mdh_host.h -- the owners of what the host side of mdh_api.hip holds on the device: buffers, events, and the two
-// orderings it keeps between its streams.  Host only: no device code, nothing of the MDH_* error plumbing; every
-// function returns the runtime's own hipError_t and the caller wraps it (HIP_TRY).
+// orderings it keeps between its streams; and of what it carries from one pass to the next: the settle tracker, the replay
+// schedule and the re-sort clock, which make no runtime call at all.  Host only: no device code, nothing of the MDH_* error
+// plumbing; every function returns the runtime's own hipError_t and the caller wraps it (HIP_TRY).
 //
 // An owner that holds nothing makes no runtime call, neither when it is released nor when it is destroyed: a renderer
 // that never reached a device is deleted without one (mdh_create).  Owners are members, never copied.
@@ -8,6 +9,7 @@
 #include <hip/hip_runtime_api.h>
 
 #include <cstddef>
+#include <cstring>
 
 constexpr int HOST_NSTREAMS = 5; // the streams of a renderer that launch kernels (stream_index, mdh_api.hip)
 
@@ -279,3 +281,104 @@ struct SettleTracker {
    }
    void untracked_pass() { ++issued; } // a probe pass outside the frame's one-radiance-then-one-irradiance pattern: the chain breaks
 };
+
+// "March, record or replay?" (MDH_OPT_RADIANCE_REPLAY, MDH_OPT_SCREEN_REPLAY; DESIGN.md section 4, "Exact work elimination",
+// items 11 and 12).  A pass whose kernel has a REC argument marches (0), marches and records (1) or replays the records (2).
+// The key is everything the marches read: what changed since the previous pass is marched plainly; what stood still for one
+// pass is marched once more, by the recording kernel; valid records of the key are replayed while it holds.
+// Key: plain data with operator== (RadRecKey, ScrRecKey).  No runtime call in here and no device memory: the records' buffer,
+// its fences and what makes a recording kernel admissible are the caller's (mdh_api.hip; tests/schedule_check.cpp has none).
+template <class Key>
+struct ReplaySchedule {
+   Key rec{}, seen{};                               // what the records are of / what the previous pass marched through
+   bool rec_valid = false, seen_valid = false;
+   bool no_memory = false;                          // the records' allocation failed: no further attempt until the key or the option changes
+   long long stats[3] = {0, 0, 0};                  // passes launched marching, recording, replaying
+   // `enabled`: the option is on and this variant is built with the recording kernels; `have_buffer`: the records' buffer
+   // exists; `admissible`: a recording kernel may run (LDS, sizes)
+   int choose(const Key &now, bool enabled, bool have_buffer, bool admissible) const
+   {
+      if (!enabled) return 0;
+      if (rec_valid && have_buffer && now == rec) return 2;
+      const bool stood = seen_valid && now == seen;
+      if (no_memory && stood) return 0; // (not tried again, and no stream drained, in every frame)
+      return stood && admissible ? 1 : 0;
+   }
+   void records_gone() { rec_valid = false; }       // the buffer is about to be regrown
+   void allocation_failed() { no_memory = true; }   // ... and was not: the pass runs as 0
+   // Behind the launch of a pass that ran as REC.  `seen_counts`: may the next pass record when its key is this one?
+   void ran(int REC, const Key &now, bool seen_counts)
+   {
+      if (REC == 1) { rec = now; rec_valid = true; }
+      else if (REC == 0) rec_valid = false; // (something moved, the option is off or this variant only marches)
+      if (!(seen_valid && now == seen)) no_memory = false; // (a new key: the allocation may be tried again)
+      seen = now;
+      seen_valid = seen_counts;
+      ++stats[REC];
+   }
+   // The option was set: the allocation may be tried again; off drops the records and, with `forget_seen`, the previous pass
+   // too -- the first pass after the option comes back on then marches plainly, whatever its key.
+   void option_set(bool on, bool forget_seen)
+   {
+      no_memory = false;
+      if (!on) { rec_valid = false; if (forget_seen) seen_valid = false; }
+   }
+};
+// everything a probe ray's marches read (rad_rec_key, mdh_api.hip)
+struct RadRecKey {
+   unsigned long geometry, inputs;      // geometry_edits, march_inputs
+   unsigned long long part_version;     // Update_Partitioning's builds
+   long rays;
+   int grid[3], res[2], pc[2], probe_begin, probe_end;
+   float spacing[3], max_dist;
+   int pf, small, jit, residency, bvh, table_f4, part_bits_f4;
+   bool operator==(const RadRecKey &o) const
+   {
+      return geometry == o.geometry && inputs == o.inputs && part_version == o.part_version && rays == o.rays &&
+             memcmp(grid, o.grid, sizeof grid) == 0 && memcmp(res, o.res, sizeof res) == 0 && memcmp(pc, o.pc, sizeof pc) == 0 &&
+             probe_begin == o.probe_begin && probe_end == o.probe_end && memcmp(spacing, o.spacing, sizeof spacing) == 0 && // (bits: a NaN spacing still equals itself)
+             memcmp(&max_dist, &o.max_dist, sizeof max_dist) == 0 && pf == o.pf && small == o.small && jit == o.jit && residency == o.residency &&
+             bvh == o.bvh && table_f4 == o.table_f4 && part_bits_f4 == o.part_bits_f4;
+   }
+};
+// everything a screen march reads, and what decides which pixel holds what (scr_rec_key, mdh_api.hip)
+struct ScrRecKey {
+   RadRecKey march;                     // geometry, probe grid, max_dist, table layout, residency, BVH, JIT, the kernel's variant word
+   float cam[12];                       // position and orientation BY VALUE: setting the camera to where it is changes nothing
+   int W, H, rank, world, mode, spec, ao, gbuffer, window, split;
+   unsigned long reflect_edits;         // Set_Material calls that took a material in use below the reflection's roughness threshold
+   bool operator==(const ScrRecKey &o) const
+   {
+      return march == o.march && memcmp(cam, o.cam, sizeof cam) == 0 && W == o.W && H == o.H && rank == o.rank && world == o.world && mode == o.mode &&
+             spec == o.spec && ao == o.ao && gbuffer == o.gbuffer && window == o.window && split == o.split && reflect_edits == o.reflect_edits;
+   }
+};
+
+// "Is the stored order due for another sort?" (MDH_OPT_RADIANCE_ORDER: the probe rays; MDH_OPT_SCREEN_ORDER: the screen's
+// tiles).  An order is sorted again every MDH_RAD_RESORT passes, and after MDH_RAD_RESORT_MOVING passes when what it follows
+// moved since -- a stale order costs speed only, and the sort's launches are out of almost every frame.
+// Of: the pass's own notes of what the stored order is of and what it was sorted under -- plain data that the pass writes and
+// compares; whether the order at hand is that one ("have") and whether anything moved are the pass's to say.
+#ifndef MDH_RAD_RESORT
+#define MDH_RAD_RESORT 64
+#endif
+#ifndef MDH_RAD_RESORT_MOVING
+#define MDH_RAD_RESORT_MOVING 8
+#endif
+template <class Of>
+struct ResortClock {
+   Of of{};
+   bool ordered = false; // there is a stored order (forget)
+   int age = 0;          // passes since it was sorted
+   // asked once by every pass that could use an order: does this one sort?
+   bool due(bool have, bool moved)
+   {
+      ++age;
+      return !have || age >= MDH_RAD_RESORT || (moved && age >= MDH_RAD_RESORT_MOVING);
+   }
+   void sorted() { ordered = true; age = 0; } // (the pass has written `of`)
+   void force() { age = MDH_RAD_RESORT; }     // the next pass that asks sorts
+   void forget() { ordered = false; }         // the stored order is of something else, or its buffers are gone
+};
+struct RadOrderOf { long rays; int begin; unsigned long scene; };                      // the slice's rays, its first probe; geometry_edits when they were sorted
+struct ScrOrderOf { int buf, n, rank, world; unsigned long geom; float cam[12]; };     // the buffer that holds the order, its tiles and their owner; geometry_edits when they were sorted; the camera when the sort was decided
