@@ -146,6 +146,10 @@ package Madarch_HIP is
    --  workgroups such a query may launch, 0 (default) = as many as the device holds at once.
    Opt_Ray_Stream_Refill : constant int := 24;
    Opt_Ray_Stream_Groups : constant int := 25;
+   --  Opt_Path_Frame_Compact: 1 = a round of an adaptive path-traced frame compacts the pixels
+   --  still running; 0 (default, the measured one) = a retired pixel keeps its lane and idles.
+   --  The same bits.
+   Opt_Path_Frame_Compact : constant int := 26;
 
    function Set_Option (R : Handle; Option, Value : int) return Status
      with Import, Convention => C, External_Name => "mdh_set_option";
@@ -329,6 +333,33 @@ package Madarch_HIP is
      (Width, Height : int; Seed, Id_First : Interfaces.Unsigned_32; N, Sample, Jitter : int;
       UV_Out : System.Address) return Status
      with Import, Convention => C, External_Name => "mdh_path_pixel_uv";
+
+   --  An adaptive path-traced frame (madarch_hip.h, mdh_path_frame_begin_adaptive): beside its sums a
+   --  pixel holds the count of its samples and two moments; Path_Frame_Accumulate is then one round
+   --  for the pixels the stopping rule keeps running (evaluated at round boundaries only), and Read
+   --  divides by the pixel's own count.  1 <= Min_Samples <= Max_Samples <= 2^24; Tolerance and
+   --  Floor finite and >= 0.  A stopping rule on a biased variance estimate.
+   function Path_Frame_Begin_Adaptive
+     (R : Handle; Width, Height : int; Seed : Interfaces.Unsigned_32; Bounces, Jitter : int;
+      Min_Samples, Max_Samples : int; Tolerance, Floor : C_float) return Status
+     with Import, Convention => C, External_Name => "mdh_path_frame_begin_adaptive";
+
+   --  Count_Out: Width Height ints; Moments_Out: 2 Width Height floats; Active, Total_Samples:
+   --  one 64-bit integer each.  Any address may be Null_Address.
+   function Path_Frame_Stats
+     (R : Handle; Count_Out, Moments_Out, Active, Total_Samples : System.Address) return Status
+     with Import, Convention => C, External_Name => "mdh_path_frame_stats";
+
+   function Path_Frame_Stats_Device
+     (R : Handle; Count_Out, Moments_Out, Active, Total_Samples : System.Address;
+      Stream : System.Address) return Status
+     with Import, Convention => C, External_Name => "mdh_path_frame_stats_device";
+
+   --  The rule by itself, on the host: no launch and no renderer.  Active_Out: N_Pixels bytes.
+   function Path_Pixel_Active
+     (N_Pixels : int; Count, M1, M2 : System.Address; Min_Samples, Max_Samples : int;
+      Tolerance, Floor : C_float; Active_Out : System.Address) return Status
+     with Import, Convention => C, External_Name => "mdh_path_pixel_active";
 
    --  The lights' fog at N points and along N rays of the host's (madarch_hip.h,
    --  mdh_inscatter_points, mdh_inscatter_rays): the integrand of the visibility pass evaluated

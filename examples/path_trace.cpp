@@ -6,8 +6,10 @@
 // (Path_Frame_Begin, Path_Frame_Accumulate in the same slices, Path_Frame_Read) -- no rays fetched, the sums stay on the device,
 // the resolve runs there.  Without --jitter its sums are the first image's bit for bit (the program says how many pixels
 // differ: none); with --jitter every sample goes through its own point of its pixel and the edges are anti-aliased.  out.ppm
-// is the accumulator's image, the window's bytes as Path_Frame_Read hands them out.
-// Usage: path_trace [--jitter] W H [SAMPLES [BOUNCES [SEED [FRAMES [SLICE [out.ppm]]]]]]
+// is the accumulator's image, the window's bytes as Path_Frame_Read hands them out.  With --adaptive TOLERANCE the accumulator is
+// an adaptive one (Path_Frame_Begin_Adaptive: at least SLICE and at most SAMPLES samples a pixel, every slice a round for the pixels
+// whose noise is still above the tolerance) and the program prints how many samples were taken instead of W H SAMPLES.
+// Usage: path_trace [--jitter] [--adaptive TOLERANCE] W H [SAMPLES [BOUNCES [SEED [FRAMES [SLICE [out.ppm]]]]]]
 #include "madarch.hpp"
 
 #include <algorithm>
@@ -20,11 +22,13 @@ using namespace Madarch;
 
 int main(int argc, char **argv)
 {
-   bool jitter = false;
-   { // --jitter, wherever it stands
+   bool jitter = false, adaptive = false;
+   float tolerance = 0.0f;
+   { // --jitter and --adaptive TOLERANCE, wherever they stand
       int kept = 1;
       for (int q = 1; q < argc; ++q) {
          if (!strcmp(argv[q], "--jitter")) jitter = true;
+         else if (!strcmp(argv[q], "--adaptive") && q + 1 < argc) { adaptive = true; tolerance = (float)atof(argv[++q]); }
          else argv[kept++] = argv[q];
       }
       argc = kept;
@@ -74,7 +78,8 @@ int main(int argc, char **argv)
       printf("mean |path traced - DDGI frame| over the hit pixels, linear: r %.6f g %.6f b %.6f\n", hits ? diff[0] / hits : 0.0, hits ? diff[1] / hits : 0.0,
              hits ? diff[2] / hits : 0.0);
       // the same view in the renderer's own accumulator
-      Renderer.Path_Frame_Begin(W, H, seed, bounces, jitter);
+      if (adaptive && samples > 0) Renderer.Path_Frame_Begin_Adaptive(W, H, seed, bounces, jitter, std::min(slice, samples), samples, tolerance, 0.01f);
+      else Renderer.Path_Frame_Begin(W, H, seed, bounces, jitter);
       for (int first = 0; first < samples; first += slice) Renderer.Path_Frame_Accumulate(std::min(slice, samples - first)); // (nothing waits)
       if (samples > 0) {
          const Renderers::Renderer::Path_Frame_Image Image = Renderer.Path_Frame_Read(true, false, true, true); // tone-mapped bytes and the raw sums
@@ -84,8 +89,15 @@ int main(int argc, char **argv)
             differ += memcmp(&Image.Sums[q], &Paths.Rgb[q], 4) != 0;
             moved += std::fabs((double)Image.Sums[q] - (double)Paths.Rgb[q]) / samples;
          }
-         printf("path-traced frame, %s: %d samples in the accumulator; %zu of %zu sums differ from the rays' (mean |difference| %.6f)\n",
-                jitter ? "jittered" : "pixel centres", Image.Samples, differ, 3 * n, moved / (3.0 * n));
+         if (!adaptive)
+            printf("path-traced frame, %s: %d samples in the accumulator; %zu of %zu sums differ from the rays' (mean |difference| %.6f)\n",
+                   jitter ? "jittered" : "pixel centres", Image.Samples, differ, 3 * n, moved / (3.0 * n));
+         if (adaptive) { // (every pixel has its own count: its sums are not the rays' sums over SAMPLES, and are not held against them)
+            printf("path-traced frame, %s, adaptive: at most %d samples a pixel\n", jitter ? "jittered" : "pixel centres", Image.Samples);
+            const Renderers::Renderer::Path_Frame_Statistics Stats = Renderer.Path_Frame_Stats(false, false);
+            printf("adaptive, tolerance %g: %lld samples taken of %lld, %lld pixels still above the tolerance\n", (double)tolerance, (long long)Stats.Total_Samples,
+                   (long long)n * samples, (long long)Stats.Active);
+         }
          if (argc > 8) { // the window's bytes
             FILE *out = fopen(argv[8], "wb");
             if (!out) return 2;

@@ -493,6 +493,41 @@ class Renderer {
       Check(mdh_path_frame_begin(h_.get(), Width, Height, Seed, Bounces, Jitter ? 1 : 0));
    }
    void Path_Frame_Accumulate(int32_t Sample_Count = 1) const { Check(mdh_path_frame_accumulate(h_.get(), Sample_Count)); }
+   // ... an ADAPTIVE accumulator: a count and two moments a pixel; Path_Frame_Accumulate is then one round for the pixels the stopping
+   // rule keeps running (evaluated at round boundaries only: two rounds of 2 are not one round of 4), Read divides by the pixel's own
+   // count.  A stopping rule on a biased variance estimate: Min_Samples is the caller's guard
+   void Path_Frame_Begin_Adaptive(int32_t Width, int32_t Height, uint32_t Seed = 0, int32_t Bounces = 3, bool Jitter = true, int32_t Min_Samples = 4,
+                                  int32_t Max_Samples = 64, float Tolerance = 0.05f, float Floor = 0.01f) const
+   {
+      Check(mdh_path_frame_begin_adaptive(h_.get(), Width, Height, Seed, Bounces, Jitter ? 1 : 0, Min_Samples, Max_Samples, Tolerance, Floor));
+   }
+   struct Path_Frame_Statistics { std::vector<int32_t> Count; std::vector<float> Moments; int64_t Active = 0, Total_Samples = 0; };
+   // the counts (one a pixel), the moments (m1, m2 a pixel), the pixels still running and the samples taken; waits for the device
+   Path_Frame_Statistics Path_Frame_Stats(bool Count = true, bool Moments = true) const
+   {
+      const Path_Frame_State S = Path_Frame_Info();
+      const size_t n = (size_t)S.Width * (size_t)S.Height;
+      Path_Frame_Statistics Out;
+      if (Count) Out.Count.resize(n);
+      if (Moments) Out.Moments.resize(2 * n);
+      Check(mdh_path_frame_stats(h_.get(), Out.Count.empty() ? nullptr : Out.Count.data(), Out.Moments.empty() ? nullptr : Out.Moments.data(), &Out.Active, &Out.Total_Samples));
+      return Out;
+   }
+   // ... into arrays the device addresses (Active, Total_Samples: one int64 each), asynchronous and ordered with Stream
+   void Path_Frame_Stats_Device(int32_t *Count, float *Moments = nullptr, int64_t *Active = nullptr, int64_t *Total_Samples = nullptr, void *Stream = nullptr) const
+   {
+      Check(mdh_path_frame_stats_device(h_.get(), Count, Moments, Active, Total_Samples, Stream));
+   }
+   // the rule by itself, on the host, the lanes' function: no launch, no renderer
+   static std::vector<uint8_t> Path_Pixel_Active(const std::vector<int32_t> &Count, const std::vector<float> &M1, const std::vector<float> &M2, int32_t Min_Samples,
+                                                 int32_t Max_Samples, float Tolerance, float Floor)
+   {
+      if (M1.size() != Count.size() || M2.size() != Count.size()) throw std::invalid_argument("Path_Pixel_Active: one count and two moments a pixel");
+      std::vector<uint8_t> Out(Count.size() + 1);
+      Check(mdh_path_pixel_active((int32_t)Count.size(), Count.data(), M1.data(), M2.data(), Min_Samples, Max_Samples, Tolerance, Floor, Out.data()));
+      Out.resize(Count.size());
+      return Out;
+   }
    Path_Frame_State Path_Frame_Info() const
    {
       Path_Frame_State S;
@@ -645,6 +680,7 @@ class Renderer {
    }
    void Set_Option(int32_t Option, int32_t Value) const { Check(mdh_set_option(h_.get(), Option, Value)); }
    static constexpr int32_t Opt_Probe_Settle = MDH_OPT_PROBE_SETTLE; // Set_Option (.., 0): probe passes launched in every frame (default 1: left out once the atlases have stopped changing, the same bits; any edit launches them again)
+   static constexpr int32_t Opt_Path_Frame_Compact = MDH_OPT_PATH_FRAME_COMPACT; // Set_Option (.., 0 / 1): an adaptive path-traced frame compacts the pixels still running (default 0, the measured one; the same bits)
    static constexpr int32_t Opt_Ray_Stream_Refill = MDH_OPT_RAY_STREAM_REFILL; // Set_Option (.., 1 .. 64): the idle lanes at which a device-array ray query's wavefront takes new rays (64: lock step; the same bits)
    static constexpr int32_t Opt_Ray_Stream_Groups = MDH_OPT_RAY_STREAM_GROUPS; // Set_Option (.., k): at most k workgroups for such a query (0, default: as many as the device holds at once)
    static constexpr int32_t Opt_Screen_Replay = MDH_OPT_SCREEN_REPLAY; // Set_Option (.., 1): the screen pass's marches replayed while camera and geometry stand still, the same bits (default 0)

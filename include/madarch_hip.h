@@ -353,7 +353,12 @@ enum {
    /* ... and the workgroups of 256 threads such a query may launch: 0 (default) = as many as the device holds at once (or
     * fewer, for a small batch), k > 0 = at most k -- room for the frames in flight beside a large batch.  Any number
     * serves every ray.  Negative: MDH_E_INVALID.  No pass reads it either. */
-   MDH_OPT_RAY_STREAM_GROUPS = 25
+   MDH_OPT_RAY_STREAM_GROUPS = 25,
+   /* an adaptive path-traced frame (mdh_path_frame_begin_adaptive): 1 = a round compacts the pixels still running, so that
+    * their lanes fill whole wavefronts; 0 (default, the measured one: DESIGN.md section 4, "An adaptive path-traced frame") = a
+    * retired pixel keeps its lane and idles.  Both values give every pixel the same bits.  No pass reads it: setting it
+    * ends no replay and no settle run. */
+   MDH_OPT_PATH_FRAME_COMPACT = 26
 };
 
 /* passes of Renderers.Render (madarch-renderers.adb:302-321) */
@@ -817,6 +822,65 @@ int32_t mdh_path_frame_end(mdh_renderer *r);
  * ids beyond the frame's pixels, a null array with n > 0. */
 int32_t mdh_path_pixel_uv(int32_t width, int32_t height, uint32_t seed, uint32_t id_first, int32_t n, int32_t sample,
                           int32_t jitter, float *uv_out);
+
+/* AN ADAPTIVE PATH-TRACED FRAME: the accumulator above with a per-pixel variance estimate, a stopping rule and a deterministic
+ * compaction of the pixels still running.  Beside its three sums a pixel holds an int32 count n of its completed samples and
+ * two fp32 moments m1, m2.  When a sample of a pixel completes with radiance (r, g, b), every step one binary32 operation,
+ * unfused:
+ *     y = (r + g) + b      acc = acc + rgb      m1 = m1 + y      m2 = m2 + y * y  (the product rounded, then the sum)      n = n + 1
+ * A pixel's k-th sample has SAMPLE INDEX k, its own count and not a global one: pixel id with count n holds exactly samples
+ * 0 .. n - 1 of (seed, id), and its sums are mdh_path_trace's over those samples.  The rule (csrc/mdh_path.h: path_pixel_active,
+ * the one inline function the lanes and mdh_path_pixel_active call):
+ *     if (n >= max_samples) return false;
+ *     if (m1 or m2 is a NaN) return false;          a pixel that was not traced does not count up: it retires here
+ *     if (n <  min_samples) return true;
+ *     c = (float) n;  mean = m1 / c;  q = m2 / c;
+ *     var = q - mean * mean;                        the product rounded, then the difference
+ *     e   = var / c;                                the variance of the mean
+ *     lim = tolerance * (mean + floor);
+ *     return e > lim * lim;                         any NaN: false -- the pixel retires
+ * A var that rounds negative retires the pixel; tolerance = 0 keeps every pixel with e > 0 running to max_samples and retires
+ * pixels of exactly zero variance at min_samples.  THIS IS A STOPPING RULE ON A BIASED VARIANCE ESTIMATE: the resolved image is
+ * not claimed to be unbiased, and min_samples is the host's guard.
+ *
+ * mdh_path_frame_begin_adaptive is mdh_path_frame_begin plus the four parameters -- the same checks, the same captured camera, the
+ * same query stream -- with 1 <= min_samples <= max_samples <= 2^24 and tolerance, floor finite and >= 0.  It opens, or
+ * restarts, the renderer's one accumulator as an adaptive one; mdh_path_frame_begin still opens a plain one.
+ *
+ * On an adaptive frame mdh_path_frame_accumulate is ONE ROUND: every pixel active under the rule at the round's start takes
+ * min (sample_count, max_samples - n) more samples, and nothing else is touched.  THE RULE IS EVALUATED AT ROUND BOUNDARIES
+ * ONLY: TWO ROUNDS OF 2 ARE NOT ONE ROUND OF 4.  It returns without waiting, and no host read-back happens between or inside
+ * rounds: the host never learns the active count unless it asks (mdh_path_frame_stats).  A pixel whose ray is outside
+ * mdh_path_trace's bound is not marched: its sums, m1 and m2 become the quiet NaN 0x7fc00000, n does not advance, and the rule
+ * retires it.  mdh_path_frame_info's samples is the largest count a pixel can hold: the rounds' sum clamped to max_samples.
+ * mdh_path_frame_read / _read_device give rgb = sum / (float) n of the pixel; sums_out is the raw sums, samples_out as _info.
+ *
+ * mdh_path_frame_stats: count_out = n (width height int32), moments_out = (m1, m2) a pixel (2 width height floats), *active = the
+ * pixels active under the rule now, *total_samples = the sum of n.  Any pointer may be NULL.  The host form waits and copies;
+ * mdh_path_frame_stats_device writes arrays the device addresses, checked before anything is launched and ordered with `stream`
+ * as mdh_path_frame_read_device -- there active and total_samples are two int64 words in device memory, aligned to 8 bytes.
+ * The two scalars cost a serial pass of one workgroup over all pixels (W H / 256 pixels a thread): a diagnostic, not
+ * something to ask behind every round of a large frame.
+ *
+ * MEMORY.  Beside the 12 bytes of sums a pixel an adaptive frame holds 12 bytes a pixel (n, m1, m2) and, for the list of running
+ * pixels, 256 bytes per 8 x 8 TILE (64 slots of 4 bytes, cut tiles included) plus 4 bytes per 256 slots: 28 bytes a pixel for a
+ * frame of whole tiles, but a frame one pixel wide pays 256 bytes for every 8 pixels -- 1 x 2^26 asks for 2 GiB of list.
+ *
+ * mdh_path_pixel_active is the rule by itself on the host, no renderer and no device: active_out[q] = 0 / 1 for the state
+ * (count[q], m1[q], m2[q]).
+ *
+ * Every refusal happens before any launch or allocation:
+ *   MDH_E_INVALID  what mdh_path_frame_begin refuses; min_samples below 1 or above max_samples, max_samples above 2^24, a
+ *                  tolerance or floor that is negative or not finite; a negative n_pixels or a null array with n_pixels > 0
+ *                  (mdh_path_pixel_active); an array the device cannot address, a 64-bit word that is not aligned (_stats_device)
+ *   MDH_E_STATE    mdh_path_frame_stats on a plain frame or with none open; for begin, what mdh_path_frame_begin refuses */
+int32_t mdh_path_frame_begin_adaptive(mdh_renderer *r, int32_t width, int32_t height, uint32_t seed, int32_t bounces, int32_t jitter,
+                                      int32_t min_samples, int32_t max_samples, float tolerance, float floor);
+int32_t mdh_path_frame_stats(mdh_renderer *r, int32_t *count_out, float *moments_out, int64_t *active, int64_t *total_samples);
+int32_t mdh_path_frame_stats_device(mdh_renderer *r, int32_t *count_out, float *moments_out, int64_t *active,
+                                    int64_t *total_samples, void *stream);
+int32_t mdh_path_pixel_active(int32_t n_pixels, const int32_t *count, const float *m1, const float *m2, int32_t min_samples,
+                              int32_t max_samples, float tolerance, float floor, uint8_t *active_out);
 
 /* The lights' fog for points and rays of the host's: the participating medium of glsl/volumetrics.glsl without the froxel
  * grid, the screen-space scattering texture or the pinhole camera they are bound to.  All arrays are host memory; positions,

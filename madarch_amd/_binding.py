@@ -29,6 +29,7 @@ OPT_PROBE_SETTLE = 23  # 1 (default): a frame's probe passes are not launched on
 OPT_SCREEN_REPLAY = 22  # 1: the screen pass's hits and cage visibility are replayed while camera and geometry stand still (the same bits; HIP library only; default 0)
 OPT_RAY_STREAM_REFILL = 24  # the device-array ray queries: a wavefront takes new rays once this many of its 64 lanes are idle (1 .. 64; 64 = lock step; the same bits; HIP library only)
 OPT_RAY_STREAM_GROUPS = 25  # ... and the workgroups such a query may launch (0, default: as many as the device holds at once)
+OPT_PATH_FRAME_COMPACT = 26  # an adaptive path-traced frame: 1 compacts the pixels still running, 0 (default, the measured one) lets retired pixels idle in their lanes (the same bits; HIP library only)
 
 PASS_RADIANCE, PASS_IRRADIANCE, PASS_VISIBILITY, PASS_SCATTERING, PASS_SCREEN, PASS_EXCHANGE = range(6)
 PASS_NAMES = ("radiance", "irradiance", "visibility", "scattering", "screen", "exchange")
@@ -198,6 +199,13 @@ HIP_ONLY_ABI = {
     "path_frame_info": (_I, [_P, _PI, _PI, _PI, _PI, _PI]),
     "path_frame_end": (_I, [_P]),
     "path_pixel_uv": (_I, [_I, _I, C.c_uint32, C.c_uint32, _I, _I, _I, _P]),
+    # ... an adaptive one, a count and two moments a pixel: begin (.., jitter, min_samples, max_samples, tolerance, floor), stats (r,
+    # count, moments, active, total_samples[, stream]); and the stopping rule on the host, no renderer: (n_pixels, count, m1, m2,
+    # min_samples, max_samples, tolerance, floor, active_out)
+    "path_frame_begin_adaptive": (_I, [_P, _I, _I, C.c_uint32, _I, _I, _I, _I, _F, _F]),
+    "path_frame_stats": (_I, [_P, _P, _P, _P, _P]),
+    "path_frame_stats_device": (_I, [_P, _P, _P, _P, _P, _P]),
+    "path_pixel_active": (_I, [_I, _P, _P, _P, _I, _I, _F, _F, _P]),
     # the lights' fog at n points and along n rays of the host's: (r, n, pos, dir, f or null, rgb[, stream]) and
     # (r, n, org, dir, tmax, march, step, rgb, len, steps[, stream])
     "inscatter_points": (_I, [_P, _I, _P, _P, _P, _P]),
@@ -217,6 +225,7 @@ HIP_ONLY_ABI = {
 }
 SURFACE_MAX_CORNERS = 1 << 24  # MDH_SURFACE_MAX_CORNERS
 PATH_FRAME_MAX_PIXELS = 1 << 26  # MDH_PATH_FRAME_MAX_PIXELS
+PATH_MAX_SAMPLES = 1 << 24  # an adaptive frame's max_samples: (float) n stays exact
 
 
 class Binding:

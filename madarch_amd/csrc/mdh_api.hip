@@ -348,7 +348,17 @@ struct mdh_renderer {
       uint32_t seed = 0;
       int32_t samples = 0;
       KCamera cam;
+      // an adaptive one (mdh_path_frame_begin_adaptive): the rule's parameters; samples is then the largest count a pixel can hold
+      bool adaptive = false;
+      int min_samples = 0, max_samples = 0;
+      float tolerance = 0.0f, floor = 0.0f;
    } pf;
+   // ... and an adaptive frame's further state (mdh_path_frame_adaptive.h), on the query stream alone: n a pixel; (m1, m2) a pixel;
+   // the list of running pixels, a slot each, with the workgroups' totals and the grand total behind it; mdh_path_frame_stats' two words
+   DevBuf<int> d_path_count, d_path_list;
+   DevBuf<float> d_path_moments;
+   DevBuf<long long> d_path_totals;
+   int opt_pf_compact = 0; // MDH_OPT_PATH_FRAME_COMPACT (0: the value that wins in front of the obj_mesh, DESIGN.md section 4, "An adaptive path-traced frame")
    QueryBridge bridge; // every query's events to the caller's stream and to the frames (query_enqueue; created by the first that needs one)
    int opt_rq_refill = MDH_RAY_STREAM_REFILL_DEFAULT; // MDH_OPT_RAY_STREAM_REFILL
    int opt_rq_groups = 0;                             // MDH_OPT_RAY_STREAM_GROUPS (0: as many workgroups as are resident)
@@ -1171,7 +1181,7 @@ extern "C" int32_t mdh_set_option(mdh_renderer *r, int32_t option, int32_t value
    switch (option) { // (the options no probe pass reads: everything else, known or not, counts as an edit)
    case MDH_OPT_TIMING: case MDH_OPT_SCREEN_ORDER: case MDH_OPT_SCREEN_SPLIT: case MDH_OPT_SCREEN_REPLAY: case MDH_OPT_GBUFFER:
    case MDH_OPT_WINDOW: case MDH_OPT_AO_STEPS: case MDH_OPT_INDIRECT_SPECULAR: case MDH_OPT_PROBE_SETTLE: break;
-   case MDH_OPT_RAY_STREAM_REFILL: case MDH_OPT_RAY_STREAM_GROUPS: break; // (the device-array ray queries' schedule: no pass reads it)
+   case MDH_OPT_RAY_STREAM_REFILL: case MDH_OPT_RAY_STREAM_GROUPS: case MDH_OPT_PATH_FRAME_COMPACT: break; // (the device-array ray queries' schedule, an adaptive path-traced frame's mapping: no pass reads it)
    default: settle_bump(r);
    }
    // what an open frame has latched (its atlas set, slice, streams and screen mode) cannot change under it
@@ -1275,6 +1285,7 @@ extern "C" int32_t mdh_set_option(mdh_renderer *r, int32_t option, int32_t value
       r->opt_rq_refill = value;
       break;
    case MDH_OPT_RAY_STREAM_GROUPS: if (value < 0) return seterr(MDH_E_INVALID, "MDH_OPT_RAY_STREAM_GROUPS: a number of workgroups, 0 = as many as are resident"); r->opt_rq_groups = value; break;
+   case MDH_OPT_PATH_FRAME_COMPACT: r->opt_pf_compact = value ? 1 : 0; break; // (read where a round is enqueued: the same bits)
    default: return seterr(MDH_E_INVALID, "unknown option");
    }
    return MDH_OK;
@@ -1308,6 +1319,7 @@ extern "C" int32_t mdh_get_option(mdh_renderer *r, int32_t option, int32_t *valu
    case MDH_OPT_PROBE_SETTLE: *value = r->opt_settle; break;
    case MDH_OPT_RAY_STREAM_REFILL: *value = r->opt_rq_refill; break;
    case MDH_OPT_RAY_STREAM_GROUPS: *value = r->opt_rq_groups; break;
+   case MDH_OPT_PATH_FRAME_COMPACT: *value = r->opt_pf_compact; break;
    case MDH_OPT_TABLE_RESIDENCY: { // of the committed scene: edits since the last commit are committed first
       if (r->table_dirty && !r->in_frame) {
          HIP_TRY(hipSetDevice(r->device));
@@ -1758,7 +1770,8 @@ template <typename Args> static int jit_launch(hipFunction_t f, int blocks, int 
 // frames in flight share their CUs' instruction caches (measured: the same kernels at other addresses, each as fast by itself,
 // the headline with frames in flight 0.5 % slower).  The kernels of global residency (MDH_PF_GTAB, mdh_device.h: Geo) come
 // last there: behind everything else they move nothing.
-enum { GK_k_visibility, GK_k_scat_march, GK_k_scattering, GK_k_radiance, GK_k_screen, GK_k_partition_build, GK_k_eval_distance, GK_k_diag_segments, GK_k_ray_query, GK_k_ray_stream, GK_k_ray_shade, GK_k_camera_rays, GK_k_point_shade, GK_k_path_trace, GK_k_point_inscatter, GK_k_ray_inscatter, GK_k_listed, GK_k_surface_field, GK_k_surface_vertices, GK_k_surface_field_listed, GK_k_surface_vertices_listed, GK_k_path_frame, GK_k_path_frame_rays, GK_k_path_frame_resolve };
+enum { GK_k_visibility, GK_k_scat_march, GK_k_scattering, GK_k_radiance, GK_k_screen, GK_k_partition_build, GK_k_eval_distance, GK_k_diag_segments, GK_k_ray_query, GK_k_ray_stream, GK_k_ray_shade, GK_k_camera_rays, GK_k_point_shade, GK_k_path_trace, GK_k_point_inscatter, GK_k_ray_inscatter, GK_k_listed, GK_k_surface_field, GK_k_surface_vertices, GK_k_surface_field_listed, GK_k_surface_vertices_listed, GK_k_path_frame, GK_k_path_frame_rays, GK_k_path_frame_resolve,
+       GK_k_path_frame_adaptive, GK_k_path_adapt_count, GK_k_path_adapt_scan, GK_k_path_adapt_compact, GK_k_path_adapt_stats, GK_k_path_frame_resolve_adaptive };
 // WHICH KERNEL A PASS RUNS ("One place that picks a pass's kernel"): every template argument of the
 // pass's kernel, computed once by pick_kernel; kernel_name and kernel_ptr turn the same description into the name hiprtc
 // instantiates and into the kernel of this library.
@@ -1769,7 +1782,7 @@ struct PassKernel {
    bool gbuf = false, alt = false; // ... the geometry buffer, the variant of the optional specular bodies
    bool small = false;             // k_radiance: SMALL
    int rec = 0;                    // k_radiance, k_screen: REC (0 marches, 1 marches and records, 2 replays the records: rad_replay_pick, scr_replay_pick)
-   int what = 0;                   // k_ray_query, k_ray_stream, k_listed: WHAT (MDH_RQ_*); k_path_frame: REUSE (1: no jitter)
+   int what = 0;                   // k_ray_query, k_ray_stream, k_listed: WHAT (MDH_RQ_*); k_path_frame: REUSE (1: no jitter); k_path_adapt_compact: COMPACT
    bool ada_div = false;           // k_eval_distance: MDH_OPT_ADA_DIVISION
    bool jit = false; // a function of the scene's hiprtc module (user-defined kinds under MDH_OPT_JIT), not a kernel of this library
    int pfk = 0;      // the variant by the scene's census, before the pass's own choices, and the power-of-two addressing
@@ -1796,7 +1809,7 @@ static const void *table_kernel(const mdh_renderer *r, int family, int what = 0)
    // BVH where the scene has one -- the general variants, whose bits the census variants share (pick_kernel)
    if (family == GK_k_ray_query || family == GK_k_ray_stream || family == GK_k_ray_shade || family == GK_k_point_shade || family == GK_k_path_trace ||
        family == GK_k_point_inscatter || family == GK_k_ray_inscatter || family == GK_k_surface_field || family == GK_k_surface_vertices ||
-       family == GK_k_path_frame) {
+       family == GK_k_path_frame || family == GK_k_path_frame_adaptive) {
       k.what = what;
       if (family == GK_k_ray_shade || family == GK_k_point_shade) { k.what = 0; k.mode = what; } // (mdh_shade_rays, mdh_shade_points: `what` is the call's mode)
       if (r->part.enable) k.pf |= MDH_PF_PART | (r->part.border_behavior != 0 ? MDH_PF_FALLBACK : 0);
@@ -4491,6 +4504,9 @@ extern "C" int32_t mdh_camera_rays_device(mdh_renderer *r, int32_t width, int32_
 // kernels).  mdh_path_frame_accumulate goes the query path at mdh_path_trace's place among the frames and is what
 // mdh_ray_query_time times; the rays and the resolve read no scene and take neither the scene's table nor the timing pair.
 // No settle_bump anywhere: nothing is edited.  Every refusal happens before a launch or an allocation.
+// mdh_path_frame_begin_adaptive opens the same accumulator with a count and two moments a pixel and a stopping rule (mdh_path.h:
+// path_pixel_active; mdh_path_frame_adaptive.h: the kernels): accumulate is then one round of four launches in one query_enqueue,
+// the resolve divides by the pixel's count, and mdh_path_frame_stats / mdh_path_pixel_active hand out the state and the rule.
 // what begin and accumulate refuse of the renderer's state: mdh_path_trace's list
 static int path_frame_state_check(const mdh_renderer *r)
 {
@@ -4504,7 +4520,11 @@ static int path_frame_open_check(const mdh_renderer *r)
    if (!r->pf.open) return seterr(MDH_E_STATE, "no path-traced frame is open (mdh_path_frame_begin)");
    return MDH_OK;
 }
-extern "C" int32_t mdh_path_frame_begin(mdh_renderer *r, int32_t width, int32_t height, uint32_t seed, int32_t bounces, int32_t jitter)
+// a frame's slots (mdh_path_frame_adaptive.h): 64 a tile of 8 x 8 pixels, and the workgroups of 256 of them
+static int path_frame_tiles(int W, int H) { return ((W + 7) / 8) * ((H + 7) / 8); } // (at most 2^23, a frame one pixel wide: 2^29 slots)
+// mdh_path_frame_begin and mdh_path_frame_begin_adaptive (rule: the four parameters, or null for a plain frame)
+struct PathRule { int min_samples, max_samples; float tolerance, floor; };
+static int path_frame_open(mdh_renderer *r, int32_t width, int32_t height, uint32_t seed, int32_t bounces, int32_t jitter, const PathRule *rule)
 {
    if (!r) return seterr(MDH_E_INVALID, "null renderer");
    if (!path_frame_size_valid(width, height)) return seterr(MDH_E_INVALID, "a path-traced frame has 1 to 2^26 pixels");
@@ -4514,14 +4534,83 @@ extern "C" int32_t mdh_path_frame_begin(mdh_renderer *r, int32_t width, int32_t 
    if (rc != MDH_OK) return rc;
    hipStream_t qs = nullptr;
    if ((rc = query_stream_get(r, &qs)) != MDH_OK) return rc;
-   const size_t words = (size_t)width * height * 3;
+   const size_t pixels = (size_t)width * height, words = pixels * 3;
    r->pf.open = false; // (a failure below leaves no accumulator)
    if ((rc = surface_room(r->d_path_frame, words, qs)) != MDH_OK) return rc;
+   if (rule) { // the count, the moments, the list with the workgroups' totals and the grand total behind it, the statistics' two words
+      const size_t slots = (size_t)path_frame_tiles(width, height) * 64, groups = (slots + MDH_BLOCK - 1) / MDH_BLOCK;
+      if ((rc = surface_room(r->d_path_count, pixels, qs)) != MDH_OK || (rc = surface_room(r->d_path_moments, 2 * pixels, qs)) != MDH_OK ||
+          (rc = surface_room(r->d_path_list, slots + groups + 1, qs)) != MDH_OK || (rc = surface_room(r->d_path_totals, 2, qs)) != MDH_OK)
+         return rc;
+      HIP_TRY(hipMemsetAsync(r->d_path_count.ptr, 0, pixels * 4, qs));
+      HIP_TRY(hipMemsetAsync(r->d_path_moments.ptr, 0, pixels * 8, qs));
+   }
    HIP_TRY(hipMemsetAsync(r->d_path_frame.ptr, 0, words * 4, qs));
    r->pf.W = width; r->pf.H = height; r->pf.bounces = bounces; r->pf.jitter = jitter; r->pf.seed = seed;
    r->pf.samples = 0;
+   r->pf.adaptive = rule != nullptr;
+   if (rule) { r->pf.min_samples = rule->min_samples; r->pf.max_samples = rule->max_samples; r->pf.tolerance = rule->tolerance; r->pf.floor = rule->floor; }
    r->pf.cam = make_camera(r); // as it stands: later setters do not smear a running accumulation
    r->pf.open = true;
+   return MDH_OK;
+}
+extern "C" int32_t mdh_path_frame_begin(mdh_renderer *r, int32_t width, int32_t height, uint32_t seed, int32_t bounces, int32_t jitter)
+{
+   return path_frame_open(r, width, height, seed, bounces, jitter, nullptr);
+}
+extern "C" int32_t mdh_path_frame_begin_adaptive(mdh_renderer *r, int32_t width, int32_t height, uint32_t seed, int32_t bounces, int32_t jitter, int32_t min_samples,
+                                                 int32_t max_samples, float tolerance, float floor)
+{
+   if (!r) return seterr(MDH_E_INVALID, "null renderer");
+   if (!path_adaptive_valid(min_samples, max_samples, tolerance, floor))
+      return seterr(MDH_E_INVALID, "1 <= min_samples <= max_samples <= 2^24, a tolerance and a floor that are finite and at least 0");
+   const PathRule rule = {min_samples, max_samples, tolerance, floor};
+   return path_frame_open(r, width, height, seed, bounces, jitter, &rule);
+}
+// the kernels' description of the open adaptive frame
+static PathAdaptArgs path_adapt_args(const mdh_renderer *r)
+{
+   PathAdaptArgs a;
+   memset(&a, 0, sizeof a);
+   a.W = r->pf.W; a.H = r->pf.H;
+   a.tiles_x = (a.W + 7) / 8; a.n_tiles = path_frame_tiles(a.W, a.H);
+   a.n_slots = a.n_tiles * 64; a.nblocks = (a.n_slots + MDH_BLOCK - 1) / MDH_BLOCK;
+   a.bounces = r->pf.bounces; a.seed = r->pf.seed; a.jitter = r->pf.jitter;
+   a.min_samples = r->pf.min_samples; a.max_samples = r->pf.max_samples; a.tolerance = r->pf.tolerance; a.floor = r->pf.floor;
+   a.compact = r->opt_pf_compact;
+   a.sums = r->d_path_frame.ptr; a.count = r->d_path_count.ptr; a.moments = r->d_path_moments.ptr;
+   a.list = r->d_path_list.ptr; a.wg = a.list + a.n_slots;
+   return a;
+}
+static const void *adapt_kernel(int family, int what = 0)
+{
+   PassKernel k;
+   k.family = family; k.what = what;
+   return kernel_ptr(k);
+}
+// one round of an adaptive frame: the pixels active under the rule now take min (sample_count, max_samples - n) more samples.
+// Four launches on the query stream inside one query_enqueue (what mdh_ray_query_time then times); the host learns no count
+static int path_frame_round(mdh_renderer *r, int32_t sample_count)
+{
+   int rc;
+   hipStream_t qs = nullptr;
+   if ((rc = query_stream_get(r, &qs)) != MDH_OK || (rc = device_query_begin(r, &qs)) != MDH_OK) return rc;
+   PathAdaptArgs a = path_adapt_args(r);
+   a.sample_count = sample_count;
+   const void *kernel = table_kernel(r, GK_k_path_frame_adaptive);
+   if (!kernel) return seterr(MDH_E_INVALID, "no kernel built for this variant");
+   const KCamera cam = r->pf.cam;
+   const dim3 grid((unsigned)a.nblocks), block(MDH_BLOCK);
+   rc = query_enqueue(r, qs, qs, true, [&] {
+      int lrc = launch_kernel_ptr(adapt_kernel(GK_k_path_adapt_count), grid, block, 0, qs, a);
+      if (lrc == MDH_OK) lrc = launch_kernel_ptr(adapt_kernel(GK_k_path_adapt_scan), dim3(1), block, 0, qs, a);
+      if (lrc == MDH_OK) lrc = launch_kernel_ptr(adapt_kernel(GK_k_path_adapt_compact, a.compact), grid, block, 0, qs, a);
+      if (lrc == MDH_OK) lrc = launch_kernel_ptr(kernel, grid, block, lds_bytes(r), qs, r->ks, cam, a);
+      return lrc;
+   });
+   if (rc != MDH_OK) return rc;
+   const int32_t left = r->pf.max_samples - r->pf.samples;
+   r->pf.samples += sample_count < left ? sample_count : left; // (the largest count a pixel can hold)
    return MDH_OK;
 }
 extern "C" int32_t mdh_path_frame_accumulate(mdh_renderer *r, int32_t sample_count)
@@ -4530,6 +4619,7 @@ extern "C" int32_t mdh_path_frame_accumulate(mdh_renderer *r, int32_t sample_cou
    if (rc != MDH_OK) return rc;
    if (sample_count < 0 || sample_count > INT32_MAX - r->pf.samples) return seterr(MDH_E_INVALID, "a sample count of at least 0, the samples so far and it below 2^31");
    if ((rc = path_frame_state_check(r)) != MDH_OK || sample_count == 0) return rc;
+   if (r->pf.adaptive) return path_frame_round(r, sample_count);
    hipStream_t qs = nullptr;
    if ((rc = query_stream_get(r, &qs)) != MDH_OK || (rc = device_query_begin(r, &qs)) != MDH_OK) return rc;
    PathFrameArgs a;
@@ -4564,10 +4654,12 @@ static int path_frame_resolve(mdh_renderer *r, int32_t tone_map, float *rgb, uns
    a.n = r->pf.W * r->pf.H; a.samples = r->pf.samples; a.tone_map = tone_map;
    a.sums = r->d_path_frame.ptr; a.rgb = rgb; a.rgba8 = rgba8; a.sums_out = sums;
    PassKernel k;
-   k.family = GK_k_path_frame_resolve;
+   k.family = r->pf.adaptive ? GK_k_path_frame_resolve_adaptive : GK_k_path_frame_resolve;
    if (caller != qs) HIP_TRY(r->bridge.create());
    HIP_TRY(r->bridge.enter(qs, caller, nullptr));
-   const int rc = launch_kernel_ptr(kernel_ptr(k), dim3((unsigned)(((size_t)a.n + 255) / 256)), dim3(256), 0, qs, a);
+   const dim3 grid((unsigned)(((size_t)a.n + 255) / 256));
+   const int *count = r->d_path_count.ptr; // (an adaptive frame: rgb = sum / (float) n of the pixel)
+   const int rc = r->pf.adaptive ? launch_kernel_ptr(kernel_ptr(k), grid, dim3(256), 0, qs, a, count) : launch_kernel_ptr(kernel_ptr(k), grid, dim3(256), 0, qs, a);
    if (rc != MDH_OK) return rc;
    HIP_TRY(hipGetLastError());
    HIP_TRY(r->bridge.leave(qs, caller, nullptr));
@@ -4663,6 +4755,70 @@ extern "C" int32_t mdh_path_frame_end(mdh_renderer *r)
    HIP_TRY(hipSetDevice(r->device));
    if (r->query_stream) HIP_TRY(hipStreamSynchronize(r->query_stream)); // (whatever still reads or writes the sums)
    HIP_TRY(r->d_path_frame.release());
+   HIP_TRY(r->d_path_count.release()); HIP_TRY(r->d_path_moments.release()); HIP_TRY(r->d_path_list.release()); HIP_TRY(r->d_path_totals.release());
+   return MDH_OK;
+}
+// mdh_path_frame_stats, mdh_path_frame_stats_device: an adaptive frame's counts and moments, the pixels active under the rule now and
+// the samples taken.  The two scalars come from one workgroup's kernel on the query stream (no scene, no timing pair).
+static int path_frame_stats_check(const mdh_renderer *r)
+{
+   const int rc = path_frame_open_check(r);
+   if (rc != MDH_OK) return rc;
+   if (!r->pf.adaptive) return seterr(MDH_E_STATE, "the open path-traced frame is a plain one (mdh_path_frame_begin_adaptive)");
+   return MDH_OK;
+}
+static int path_frame_stats_enqueue(mdh_renderer *r, int32_t *count, float *moments, long long *active, long long *total, hipMemcpyKind kind, hipStream_t qs, hipStream_t caller)
+{
+   if (!count && !moments && !active && !total) return MDH_OK;
+   const size_t n = (size_t)r->pf.W * r->pf.H;
+   if (caller != qs) HIP_TRY(r->bridge.create());
+   HIP_TRY(r->bridge.enter(qs, caller, nullptr));
+   if (active || total) {
+      PathAdaptArgs a = path_adapt_args(r);
+      a.active_out = active; a.total_out = total;
+      const int rc = launch_kernel_ptr(adapt_kernel(GK_k_path_adapt_stats), dim3(1), dim3(MDH_BLOCK), 0, qs, a);
+      if (rc != MDH_OK) return rc;
+      HIP_TRY(hipGetLastError());
+   }
+   if (count) HIP_TRY(hipMemcpyAsync(count, r->d_path_count.ptr, n * 4, kind, qs));
+   if (moments) HIP_TRY(hipMemcpyAsync(moments, r->d_path_moments.ptr, n * 8, kind, qs));
+   HIP_TRY(r->bridge.leave(qs, caller, nullptr));
+   return MDH_OK;
+}
+extern "C" int32_t mdh_path_frame_stats(mdh_renderer *r, int32_t *count_out, float *moments_out, int64_t *active, int64_t *total_samples)
+{
+   int rc = path_frame_stats_check(r);
+   if (rc != MDH_OK) return rc;
+   hipStream_t qs = nullptr;
+   if ((rc = query_stream_get(r, &qs)) != MDH_OK) return rc;
+   long long *d = r->d_path_totals.ptr;
+   if ((rc = path_frame_stats_enqueue(r, count_out, moments_out, active ? d : nullptr, total_samples ? d + 1 : nullptr, hipMemcpyDeviceToHost, qs, qs)) != MDH_OK) return rc;
+   long long both[2] = {0, 0};
+   if (active || total_samples) HIP_TRY(hipMemcpyAsync(both, d, sizeof both, hipMemcpyDeviceToHost, qs));
+   if ((rc = ray_query_wait(r)) != MDH_OK) return rc;
+   if (active) *active = both[0];
+   if (total_samples) *total_samples = both[1];
+   return MDH_OK;
+}
+extern "C" int32_t mdh_path_frame_stats_device(mdh_renderer *r, int32_t *count_out, float *moments_out, int64_t *active, int64_t *total_samples, void *stream)
+{
+   int rc = path_frame_stats_check(r);
+   if (rc != MDH_OK) return rc;
+   const size_t w = (size_t)r->pf.W * r->pf.H * 4;
+   const RayArray arrays[] = {{count_out, w, "counts"}, {moments_out, 2 * w, "moments"}, {active, 8, "the active count"}, {total_samples, 8, "the samples' total"}};
+   if ((rc = ray_arrays_check(r, arrays)) != MDH_OK) return rc;
+   if ((active && ((uintptr_t)active & 7)) || (total_samples && ((uintptr_t)total_samples & 7))) return seterr(MDH_E_INVALID, "the two 64-bit words are aligned to 8 bytes");
+   hipStream_t qs = nullptr;
+   if ((rc = query_stream_get(r, &qs, true)) != MDH_OK) return rc;
+   return path_frame_stats_enqueue(r, count_out, moments_out, (long long *)active, (long long *)total_samples, hipMemcpyDeviceToDevice, qs, (hipStream_t)stream);
+}
+// the rule by itself, on the host over the function the lanes call (mdh_path.h): no launch, no renderer
+extern "C" int32_t mdh_path_pixel_active(int32_t n_pixels, const int32_t *count, const float *m1, const float *m2, int32_t min_samples, int32_t max_samples, float tolerance,
+                                         float floor, uint8_t *active_out)
+{
+   if (n_pixels < 0 || !path_adaptive_valid(min_samples, max_samples, tolerance, floor) || (n_pixels > 0 && (!count || !m1 || !m2 || !active_out)))
+      return seterr(MDH_E_INVALID, "bad argument");
+   for (size_t q = 0; q < (size_t)n_pixels; ++q) active_out[q] = path_pixel_active(count[q], m1[q], m2[q], min_samples, max_samples, tolerance, floor) ? 1 : 0;
    return MDH_OK;
 }
 // the jitter by itself, on the host over the functions the lanes call (mdh_path.h): no launch, no renderer
@@ -4949,8 +5105,10 @@ static const void *kernel_ptr_inscatter(const PassKernel &k);
 static const void *kernel_ptr_sweep(const PassKernel &k);
 static const void *kernel_ptr_surface(const PassKernel &k);
 static const void *kernel_ptr_path_frame(const PassKernel &k);
+static const void *kernel_ptr_path_adaptive(const PassKernel &k);
 static const void *kernel_ptr(const PassKernel &k)
 {
+   if (k.family >= GK_k_path_frame_adaptive && k.family <= GK_k_path_frame_resolve_adaptive) return kernel_ptr_path_adaptive(k);
    if (k.family >= GK_k_path_frame && k.family <= GK_k_path_frame_resolve) return kernel_ptr_path_frame(k);
    if (k.family >= GK_k_surface_field && k.family <= GK_k_surface_vertices_listed) return kernel_ptr_surface(k);
    if (k.family == GK_k_listed || ((k.family == GK_k_ray_query || k.family == GK_k_ray_stream) && k.what >= MDH_RQ_SPHERECAST)) return kernel_ptr_sweep(k);
@@ -5085,4 +5243,18 @@ static const void *kernel_ptr_path_frame(const PassKernel &k)
    if (k.family == GK_k_path_frame_resolve) return (const void *)k_path_frame_resolve<>;
    return nullptr;
 }
-
+// ... and behind that an adaptive path-traced frame (mdh_path_frame_begin_adaptive; mdh_path_frame_adaptive.h): the estimator with a count
+// and two moments a pixel in the queries' variants, first named here; the kernels of a round's list, of the statistics and of
+// the resolve read no scene and have no variants
+static const void *kernel_ptr_path_adaptive(const PassKernel &k)
+{
+#define MDH_PFA(PF) if (k.family == GK_k_path_frame_adaptive && k.pf == (PF)) return (const void *)k_path_frame_adaptive<PF>;
+   MDH_PFA(0) MDH_PFA(1) MDH_PFA(9) MDH_PFA(64) MDH_PFA(65) MDH_PFA(73) MDH_PFA(192)
+#undef MDH_PFA
+   if (k.family == GK_k_path_adapt_count) return (const void *)k_path_adapt_count<>;
+   if (k.family == GK_k_path_adapt_scan) return (const void *)k_path_adapt_scan<>;
+   if (k.family == GK_k_path_adapt_compact) return k.what ? (const void *)k_path_adapt_compact<true> : (const void *)k_path_adapt_compact<false>;
+   if (k.family == GK_k_path_adapt_stats) return (const void *)k_path_adapt_stats<>;
+   if (k.family == GK_k_path_frame_resolve_adaptive) return (const void *)k_path_frame_resolve_adaptive<>;
+   return nullptr;
+}

@@ -2425,6 +2425,8 @@ template <bool GTAB, int WHAT> __global__ __launch_bounds__(MDH_BLOCK) void k_li
 #include "mdh_surface.h"
 // ... and a path-traced frame: k_path_trace's estimator over the pixels of a captured camera, its rays and its resolve
 #include "mdh_path_frame.h"
+// ... and the adaptive one: a count and two moments a pixel, the stopping rule, the compaction of the pixels still running
+#include "mdh_path_frame_adaptive.h"
 #endif
 
 // ---------------------------------------------------------------------- the window's pixels

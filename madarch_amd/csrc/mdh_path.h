@@ -94,6 +94,46 @@ MDH_PATH_FN void path_pixel_uv(int i, int j, int W, int H, unsigned seed, unsign
 }
 MDH_PATH_FN bool path_frame_size_valid(int W, int H) { return W >= 1 && H >= 1 && (long long)W * H <= (long long)MDH_PATH_FRAME_MAX_PIXELS; }
 
+// ---------------------------------------------------------------------- an adaptive frame: a pixel's moments and its stopping rule
+// (mdh_path_frame_begin_adaptive, k_path_frame_adaptive in mdh_path_frame_adaptive.h, mdh_path_pixel_active on the host.)  Beside its
+// three sums a pixel holds the count n of its completed samples and the moments m1, m2 of y = (r + g) + b.  When a sample with
+// radiance (r, g, b) completes, every step one binary32 operation, unfused:
+//    y = (r + g) + b;   acc = acc + rgb;   m1 = m1 + y;   m2 = m2 + y * y  (the product rounded, then the sum);   n = n + 1
+// path_pixel_active says whether the pixel takes further samples.  THIS IS A STOPPING RULE ON A BIASED VARIANCE ESTIMATE: the
+// variance is the plug-in one (divided by n, not n - 1) of a sum of channels, the rule looks at the samples it then stops or
+// goes on drawing, and the resolved image of an adaptive frame is NOT CLAIMED TO BE UNBIASED -- min_samples is the host's guard
+// against pixels that stop on a lucky start.  A NaN anywhere -- a pixel whose ray was not traced has NaN moments -- retires
+// the pixel: such a pixel's count does not advance, so the test for it stands in front of the one for min_samples, or it
+// would stay active for ever.  A variance that rounds negative retires it too (e > lim * lim is then false).
+#define MDH_PATH_MAX_SAMPLES 16777216 // 2^24: (float) n is exact
+MDH_PATH_FN bool path_adaptive_valid(int min_samples, int max_samples, float tolerance, float floor)
+{
+   return min_samples >= 1 && min_samples <= max_samples && max_samples <= MDH_PATH_MAX_SAMPLES && rs_finite(tolerance) && tolerance >= 0.0f && rs_finite(floor) &&
+          floor >= 0.0f;
+}
+MDH_PATH_FN void path_pixel_update(float r, float g, float b, int &n, float &m1, float &m2)
+{
+   const float y = (r + g) + b;
+   const float yy = y * y;
+   m1 = m1 + y;
+   m2 = m2 + yy;
+   n = n + 1;
+}
+MDH_PATH_FN bool path_pixel_active(int n, float m1, float m2, int min_samples, int max_samples, float tolerance, float floor)
+{
+   if (n >= max_samples) return false;
+   if (m1 != m1 || m2 != m2) return false; // (not traced, or NaN radiance: the count may stand still)
+   if (n < min_samples) return true;
+   const float c = (float)n;
+   const float mean = m1 / c, q = m2 / c;
+   const float mm = mean * mean;
+   const float var = q - mm;
+   const float e = var / c; // the variance of the mean
+   const float lim = tolerance * (mean + floor);
+   const float ll = lim * lim;
+   return e > ll; // (any NaN: false)
+}
+
 // ---------------------------------------------------------------------- which rays are traced
 MDH_PATH_FN bool path_bounces_valid(int bounces) { return bounces >= 0 && bounces <= MDH_PATH_MAX_BOUNCES; }
 MDH_PATH_FN bool path_ray_valid(float ox, float oy, float oz, float dx, float dy, float dz)

@@ -350,13 +350,19 @@ def path_traced_view(R, Width, Height, Samples=64, Bounces=3, Seed=1, Slice=16):
     return tone(traced), tone(frame), traced.reshape(Height, Width, 3), frame.reshape(Height, Width, 3)
 
 
-def path_traced_frame(R, Width, Height, Samples=64, Bounces=3, Seed=1, Jitter=True, Slice=16):
+def path_traced_frame(R, Width, Height, Samples=64, Bounces=3, Seed=1, Jitter=True, Slice=16, Adaptive=None):
     """What renderer R's camera sees, path traced into the renderer's own accumulator: Path_Frame_Begin, Path_Frame_Accumulate in
     slices of `Slice` samples -- nothing is fetched or carried in between, the sums stay on the device -- and the resolve on the
     device.  With Jitter every sample goes through its own point of its pixel, so edges are anti-aliased; without it the image is
     path_traced_view's.  -> (tone-mapped (Height, Width, 3) float32, the window's bytes (Height, Width, 4) uint8, the linear
-    image (Height, Width, 3) float32)"""
-    R.Path_Frame_Begin(Width, Height, Seed=Seed, Bounces=Bounces, Jitter=Jitter)
+    image (Height, Width, 3) float32).  Adaptive = (Min_Samples, Tolerance) or (Min_Samples, Tolerance, Floor): the accumulator
+    is an adaptive one with Max_Samples = Samples, every slice is a round for the pixels whose noise is still above the
+    tolerance, and a fourth result is the (Height, Width) int32 image of the samples each pixel took."""
+    if Adaptive is not None:
+        rule = dict(zip(("Min_Samples", "Tolerance", "Floor"), Adaptive))
+        R.Path_Frame_Begin_Adaptive(Width, Height, Seed=Seed, Bounces=Bounces, Jitter=Jitter, Max_Samples=max(int(Samples), int(rule["Min_Samples"])), **rule)
+    else:
+        R.Path_Frame_Begin(Width, Height, Seed=Seed, Bounces=Bounces, Jitter=Jitter)
     first = 0
     while first < Samples:
         count = min(int(Slice), Samples - first)
@@ -364,7 +370,10 @@ def path_traced_frame(R, Width, Height, Samples=64, Bounces=3, Seed=1, Jitter=Tr
         first += count
     shown = R.Path_Frame_Read(Tone_Map=True, Rgb=True, Rgba8=True)
     linear = R.Path_Frame_Read(Tone_Map=False)["rgb"]
+    count = R.Path_Frame_Stats(Moments=False)["count"] if Adaptive is not None else None
     R.Path_Frame_End()
+    if Adaptive is not None:
+        return shown["rgb"], shown["rgba8"], linear, count
     return shown["rgb"], shown["rgba8"], linear
 
 

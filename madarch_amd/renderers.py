@@ -566,10 +566,75 @@ class Renderer:
         w, h, seed, nb, jit = self._path_frame_args(Width, Height, Seed, Bounces, Jitter)
         self._b.check(self._b.path_frame_begin(self._h, w, h, seed, nb, jit))
 
+    @staticmethod
+    def _path_rule_args(Min_Samples, Max_Samples, Tolerance, Floor):
+        """ValueError before any library call"""
+        lo, hi = int(Min_Samples), int(Max_Samples)
+        if not 1 <= lo <= hi <= B.PATH_MAX_SAMPLES:
+            raise ValueError("1 <= Min_Samples <= Max_Samples <= 2^24, not %s and %s" % (Min_Samples, Max_Samples))
+        tol, floor = float(Tolerance), float(Floor)
+        for what, v in (("Tolerance", tol), ("Floor", floor)):
+            if not (np.isfinite(v) and 0.0 <= v <= float(np.finfo(np.float32).max)):
+                raise ValueError("%s: finite and at least 0, not %s" % (what, v))
+        return lo, hi, tol, floor
+
+    def Path_Frame_Begin_Adaptive(self, Width, Height, Seed=0, Bounces=3, Jitter=True, Min_Samples=4, Max_Samples=64, Tolerance=0.05, Floor=0.01):
+        """Path_Frame_Begin for an ADAPTIVE accumulator: beside its sums a pixel holds the count n of its samples and the moments
+        m1, m2 of y = (r + g) + b.  Path_Frame_Accumulate (k) is then one round: every pixel still active under the rule
+        takes min (k, Max_Samples - n) more samples; a pixel is active while n < Max_Samples and (n < Min_Samples or the
+        variance of its mean exceeds (Tolerance * (mean + Floor))^2), evaluated at round boundaries only -- two rounds of 2
+        are not one round of 4.  A pixel's k-th sample has sample index k.  A stopping rule on a biased variance estimate:
+        the image is not claimed to be unbiased, Min_Samples is the caller's guard."""
+        w, h, seed, nb, jit = self._path_frame_args(Width, Height, Seed, Bounces, Jitter)
+        lo, hi, tol, floor = self._path_rule_args(Min_Samples, Max_Samples, Tolerance, Floor)
+        self._b.check(self._b.path_frame_begin_adaptive(self._h, w, h, seed, nb, jit, lo, hi, tol, floor))
+
+    def Path_Frame_Stats(self, Count=True, Moments=True):
+        """{count (H, W) int32, moments (H, W, 2) float32 = (m1, m2), active, total_samples} of the adaptive accumulator: active is
+        the number of pixels the rule keeps running now, total_samples the sum of the counts.  Waits for the device."""
+        info = self.Path_Frame_Info()
+        w, h = info["width"], info["height"]
+        out = {}
+        if Count:
+            out["count"] = np.zeros((h, w), np.int32)
+        if Moments:
+            out["moments"] = np.zeros((h, w, 2), np.float32)
+        active, total = C.c_int64(0), C.c_int64(0)
+        ptr = [_fp(out[k]) if k in out and out[k].size else None for k in ("count", "moments")]
+        self._b.check(self._b.path_frame_stats(self._h, ptr[0], ptr[1], C.cast(C.byref(active), C.c_void_p), C.cast(C.byref(total), C.c_void_p)))
+        out["active"], out["total_samples"] = active.value, total.value
+        return out
+
+    def Path_Frame_Stats_Device(self, Width, Height, Count=None, Moments=None, Active=None, Total_Samples=None, Stream=0):
+        """Path_Frame_Stats into device memory, asynchronous and ordered with `Stream`; Width and Height are the accumulator's.
+        Count holds one int32 a pixel, Moments two float32, Active and Total_Samples one int64 each; each may be None."""
+        w, h = self._frame_size(Width, Height)
+        dev = self._device_array
+        args = [dev(Count, "Count", w * h, "int32", True), dev(Moments, "Moments", 2 * w * h, "float32", True), dev(Active, "Active", 1, "int64", True),
+                dev(Total_Samples, "Total_Samples", 1, "int64", True)]
+        self._b.check(self._b.path_frame_stats_device(self._h, *args, C.c_void_p(int(Stream))))
+
+    @staticmethod
+    def Path_Pixel_Active(Count, M1, M2, Min_Samples, Max_Samples, Tolerance, Floor, Binding=None):
+        """(n,) bool: the stopping rule of an adaptive frame for the states (Count[q], M1[q], M2[q]), on the host, the function
+        the lanes call -- no launch and no renderer"""
+        lo, hi, tol, floor = Renderer._path_rule_args(Min_Samples, Max_Samples, Tolerance, Floor)
+        count = np.ascontiguousarray(Count, dtype=np.int32)
+        m1, m2 = np.ascontiguousarray(M1, dtype=np.float32), np.ascontiguousarray(M2, dtype=np.float32)
+        if count.ndim != 1 or m1.shape != count.shape or m2.shape != count.shape:
+            raise ValueError("Count, M1 and M2 are (n,) arrays of one length, not %s, %s and %s" % (count.shape, m1.shape, m2.shape))
+        b = Binding or B.hip_binding()
+        n = len(count)
+        out = np.zeros(n, np.uint8)
+        b.check(b.path_pixel_active(n, _fp(count) if n else None, _fp(m1) if n else None, _fp(m2) if n else None, lo, hi, tol, floor, _fp(out) if n else None))
+        return out.astype(bool)
+
     def Path_Frame_Accumulate(self, Sample_Count=1):
         """adds the next Sample_Count samples to every pixel and returns without waiting for the device.  The scene is the one
         committed at the call; nothing is edited.  Restarting after an edit (Path_Frame_Begin again) is the caller's business.
-        Under OPT_TIMING Ray_Query_Time gives the kernel's time."""
+        Under OPT_TIMING Ray_Query_Time gives the kernel's time.  On an adaptive accumulator (Path_Frame_Begin_Adaptive) it is
+        one round: the pixels the rule keeps running take up to Sample_Count samples, and the resolve divides by each pixel's own
+        count."""
         if int(Sample_Count) < 0 or int(Sample_Count) > 2 ** 31 - 1:
             raise ValueError("Sample_Count: %s samples" % (Sample_Count,))
         self._b.check(self._b.path_frame_accumulate(self._h, int(Sample_Count)))
@@ -583,7 +648,8 @@ class Renderer:
     def Path_Frame_Read(self, Tone_Map=False, Rgb=True, Rgba8=False, Sums=False):
         """the resolve, on the device: {rgb (H, W, 3) float32 = sums / samples, with Tone_Map draw_screen.glsl:29 applied as
         Shade_Rays applies it; rgba8 (H, W, 4) uint8 = that colour as the window's pixels hold it; sums (H, W, 3) the raw sums;
-        samples}, rows top first; only what was asked for is computed and copied"""
+        samples}, rows top first; only what was asked for is computed and copied.  On an adaptive accumulator rgb = sums / the
+        pixel's own count (Path_Frame_Stats), and samples is the largest count a pixel can hold."""
         tm = self._flag(Tone_Map, "Tone_Map")
         info = self.Path_Frame_Info()
         w, h = info["width"], info["height"]
