@@ -4873,6 +4873,17 @@ extern "C" int32_t mdh_diag_best_first(unsigned long long *out4)
    if (hipMemcpyToSymbol(HIP_SYMBOL(g_best_stats), z, sizeof z) != hipSuccess) return MDH_E_DEVICE;
    return MDH_OK;
 }
+// ... and of its first round's approximate ranking (MDH_BEST_APPROX): lanes it gave a winner, lanes it gave no candidate, lanes it
+// left undecided, wavefronts that ran the exact scan because of them, since the last call
+extern "C" int32_t mdh_diag_best_approx(unsigned long long *out4)
+{
+   if (!out4) return MDH_E_INVALID;
+   if (hipDeviceSynchronize() != hipSuccess) return MDH_E_DEVICE;
+   if (hipMemcpyFromSymbol(out4, HIP_SYMBOL(g_best_approx_stats), sizeof(unsigned long long) * 4) != hipSuccess) return MDH_E_DEVICE;
+   unsigned long long z[4] = {0, 0, 0, 0};
+   if (hipMemcpyToSymbol(HIP_SYMBOL(g_best_approx_stats), z, sizeof z) != hipSuccess) return MDH_E_DEVICE;
+   return MDH_OK;
+}
 #endif
 
 // MDH_OPT_SCREEN_REPLAY: screen passes launched since creation that marched, marched and recorded, replayed

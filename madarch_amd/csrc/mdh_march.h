@@ -45,6 +45,15 @@ __device__ unsigned long long g_best_stats[4]; // wave-rounds of the fast path, 
 #else
 #define MDH_BEST_STAT(slot, n) do { } while (0)
 #endif
+#ifndef MDH_BEST_APPROX
+#define MDH_BEST_APPROX 1 // the first round of that search ranks the corners by an approximate d and directs the winner only (best_approx below)
+#endif
+#ifdef MDH_BEST_STATS // (the same build; mdh_diag_best_approx takes them)
+__device__ unsigned long long g_best_approx_stats[4]; // first-round lanes the rule gave a winner, lanes it gave no candidate, lanes it left undecided, wavefronts that ran the exact scan for them
+#define MDH_BEST_APPROX_STAT(slot, n) do { const unsigned long long n_ = (n); if ((threadIdx.x & 63) == __ffsll((long long)__ballot(1)) - 1) atomicAdd(&g_best_approx_stats[slot], n_); } while (0)
+#else
+#define MDH_BEST_APPROX_STAT(slot, n) do { } while (0)
+#endif
 
 struct MachineCfg {
    bool direct_specular;   // M_COMPUTE_DIRECT_SPECULAR
@@ -424,6 +433,91 @@ MDH_DEV KProbes probes_fresh(const KProbes &pr)
    return r;
 }
 
+// best_approx (MDH_BEST_APPROX) -- the first round of the second point's best-first search (shade_structured) without the exact
+// directions of the losers.  The exact scan computes, per unfolded corner i with h = P - pw_i (pw_i = grid_to_world (cage_probe (i))),
+//    d_i = -((v.x N.x + v.y N.y) + v.z N.z),  v = h / sqrt_ (dot2 (h))    (a correctly rounded root and three IEEE divisions)
+// and keeps the largest d_i > 0, the lowest index among equals.  Here every lane ranks the corners by
+//    a_i = -((h.x N.x + h.y N.y) + h.z N.z) * v_rsq_f32 (dot2 (h))
+// with h's three differences, their squares and their products with N formed once for the offsets 0 and 1 of each axis: the
+// same float operations on the same values as grid_to_world and the subtraction of the scan (an unfolded axis is not clamped by
+// cage_probe, so its offset-1 probe is gp + 1; a folded one takes its clamped offset-0 probe only), hence h is the scan's h bit
+// for bit and only what follows it differs.
+//
+// The bound eps on |a_i - d_i|.  u = 2^-24 (one rounding to nearest, relative), L = |h|, t = -dot (h, N) / L the real value,
+// |N| <= sqrt 3 (every component at most 1 in magnitude, tested below), terms of order u^2 left to the margin at the end.
+//   d_i:  dot2 (h) has relative error 3 u (a product and two sums of positive terms), its root 3 u / 2 + u, each quotient
+//         h.c / dist one more: 3.5 u per component of v.  The dot product with N adds a rounding per product and per sum, at
+//         most 3 u on the sum of |v.c N.c| <= |v| |N|:  |d_i - t| <= 6.5 u |v| |N| <= 6.5 sqrt 3 u < 11.3 u.
+//   a_i:  the products and sums of dot (h, N): 3 u L |N| absolute.  v_rsq_f32 is good to one ulp (2 u relative) of the inverse
+//         root of a dot2 that is 3 u off (1.5 u on the root): 3.5 u on 1 / L.  The last product one more:
+//         |a_i - t| <= (3 + 3.5 + 1) u |N| = 7.5 sqrt 3 u < 13 u.
+// Range: |P.c| <= lim, the grid's far corner within lim (so every probe considered is) and |N.c| <= 1 are tested below, a NaN fails
+// each of them, and lim <= 2^18: every h.c is finite, L <= 2 sqrt 3 lim and dot2 (h) <= 12 lim^2 < 2^40.  dot2 (h) >= 2^-40 is tested
+// for the smallest one: L >= 2^-20, dot2 and its inverse root are normal, and a product h.c N.c or v.c N.c or a square that underflows
+// is off by 2^-149 at most -- times 1 / L <= 2^20 still below 2^-129.  So no a_i is infinite or a NaN.  Together
+// |a_i - d_i| < 24.3 u (1 + 2^-20), and eps = 2^-19 = 32 u holds it.  lim does not enter eps: every error above is relative to L |N|.
+//
+// The rule, per lane, with a_1 the largest a_i (lowest index among equals) and a_2 the runner-up (-4 where there is none: every
+// a_i >= -sqrt 3 - eps):
+//   1  a_1 - a_2 > 2 eps and a_1 > eps: d of that corner exceeds every other d_i (d_1 > a_1 - eps > a_2 + eps >= a_i + eps > d_i)
+//      and is positive: the exact scan names it, whatever the order among the others.  `bi` is its index.
+//   2  a_1 < -eps: every d_i < 0: the exact scan finds no candidate.
+//   0  anything else -- a near tie, a_1 within eps of 0, a failed range test: undecided, the exact scan decides.
+// A corner folded in this lane but not in every lane of the wavefront takes its twin's dot2 and 32 lim in the place of its N product:
+// the other two products are at most 2 lim each, so dot (h, N) >= 28 lim and a <= -28 lim / (2 sqrt 3 lim) < -8: below the -4 that
+// a_1 and a_2 start from, it enters neither.  A corner folded in every lane is not computed.
+// (Inline constants, scalars and powers of two through v_ldexp_f32 only: a literal that a compare or a select cannot encode becomes a
+//  register, which the compiler holds across the pixel program's loop over its two points -- item 19's lesson.  The x and y terms are
+//  kept, the z terms formed per offset: eight registers of terms instead of twelve.)
+#define MDH_BEST_APPROX_EPS_LOG2 (-19)
+MDH_DEV int best_approx(const KProbes &pr, i3 gp, int folded, f3 P, f3 N, int &bi)
+{
+   const KProbes pq = probes_fresh(pr);
+   const float lim = __int_as_float(hdr(H_VCLEAR_LIM));
+   const int wf = (__ballot(!(folded & 1)) ? 0 : 1) | (__ballot(!(folded & 2)) ? 0 : 2) | (__ballot(!(folded & 4)) ? 0 : 4); // folded in every lane
+   bool ok = (unsigned)__float_as_int(lim) <= 0x48800000u; // 0 <= lim <= 2^18, no NaN
+   ok = ok && __builtin_fabsf(P.x) <= lim && __builtin_fabsf(P.y) <= lim && __builtin_fabsf(P.z) <= lim;
+   ok = ok && __builtin_fabsf(N.x) <= 1.0f && __builtin_fabsf(N.y) <= 1.0f && __builtin_fabsf(N.z) <= 1.0f;
+   ok = ok && __builtin_fabsf((float)(pq.gx - 1) * pq.sx) <= lim && __builtin_fabsf((float)(pq.gy - 1) * pq.sy) <= lim && __builtin_fabsf((float)(pq.gz - 1) * pq.sz) <= lim;
+   const float out = __builtin_ldexpf(lim, 5); // a folded corner's place holder
+   float sq[2][2], pn[2][2];
+   {
+      const float h0 = P.x - (float)iclamp_(gp.x, 0, pq.gx - 1) * pq.sx, h1 = P.x - (float)(gp.x + 1) * pq.sx;
+      sq[0][0] = h0 * h0; pn[0][0] = h0 * N.x;
+      sq[0][1] = (folded & 1) ? sq[0][0] : h1 * h1; pn[0][1] = (folded & 1) ? out : h1 * N.x;
+   }
+   {
+      const float h0 = P.y - (float)iclamp_(gp.y, 0, pq.gy - 1) * pq.sy, h1 = P.y - (float)(gp.y + 1) * pq.sy;
+      sq[1][0] = h0 * h0; pn[1][0] = h0 * N.y;
+      sq[1][1] = (folded & 2) ? sq[1][0] : h1 * h1; pn[1][1] = (folded & 2) ? out : h1 * N.y;
+   }
+   float a1 = -4.0f, a2 = -4.0f, dmin = 4.0f; // (dmin: the smallest dot2, or 4)
+   bi = -1;
+#pragma unroll
+   for (int bz = 0; bz < 2; ++bz) {
+      if ((bz << 2) & wf) continue;
+      const bool fz = bz && (folded & 4);
+      const float hz = P.z - (float)((bz && !fz) ? gp.z + 1 : iclamp_(gp.z, 0, pq.gz - 1)) * pq.sz;
+      const float sz = hz * hz, nz = fz ? out : hz * N.z;
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+         if (j & wf) continue;
+         const float d2 = (sq[0][j & 1] + sq[1][j >> 1]) + sz;
+         const float dn = (pn[0][j & 1] + pn[1][j >> 1]) + nz;
+         const float a = -dn * __builtin_amdgcn_rsqf(d2);
+         dmin = min_(dmin, d2);
+         if (a > a1) bi = j | (bz << 2);
+         a2 = __builtin_amdgcn_fmed3f(a, a1, a2);
+         a1 = max_(a1, a);
+      }
+   }
+   ok = ok && __builtin_ldexpf(dmin, 40) >= 1.0f;
+   const float lead = __builtin_ldexpf(a1 - a2, -MDH_BEST_APPROX_EPS_LOG2), top = __builtin_ldexpf(a1, -MDH_BEST_APPROX_EPS_LOG2); // in units of eps
+   if (ok && lead > 2.0f && top > 1.0f) return 1;
+   if (ok && top < -1.0f) return 2;
+   return 0;
+}
+
 // ---------------------------------------------------------------------------------------------
 // RayRecord -- what a probe ray's marches find, which follows from the scene's geometry alone (MDH_OPT_RADIANCE_REPLAY,
 // DESIGN.md section 4, "Exact work elimination", item 11).  A probe ray starts at a fixed probe in a fixed octahedral
@@ -602,6 +696,8 @@ MDH_DEV f3 shade_structured(const KScene &sc, const KProbes &pr, const MachineCf
    // marching and recording -- every other instantiation is the code it was
    constexpr bool BEST_FIRST = MDH_BEST_FIRST != 0 && (SHARET & 4) != 0 && MDH_SHARE_FIRST_STEP != 0 && MDH_REUSE_FOLDED != 0 && SPEC == 1 && !QVIS && MODE == 0 &&
                                (PART & ~(MDH_PF_ROOM | MDH_PF_POW2)) == 0 && REC != 2;
+   // ... its first round ranked by approximate values, the exact direction formed for the winner alone (item 20, best_approx above)
+   constexpr bool BEST_APPROX = MDH_BEST_APPROX != 0 && BEST_FIRST;
    // the sphere's and the box's distance bounded once per ray in front of the primary and the reflection march (item 19 of "Exact
    // work elimination", at march_plain): the screen family's fixed mode over the rooms' census, marching and recording
    constexpr bool RAY_BOUNDS = MDH_RAY_BOUNDS != 0 && (SHARET & 8) != 0 && SPEC == 1 && !QVIS && MODE == 0 && !POINT && REC != 2 && (PART & ~MDH_PF_POW2) == MDH_PF_ROOM;
@@ -871,6 +967,9 @@ MDH_DEV f3 shade_structured(const KScene &sc, const KProbes &pr, const MachineCf
                   // W'_c = d_c, +0 at the tried corners, and d_j at the untried ones, which are <= d_c and above index c where equal
                   // (or not positive, or NaN): it names c.  A fallback lane's record is the loop's own.
                   bool in_order = true;
+                  // (the second point's direct light waits in the rows of its colour, where it goes anyway, from here to the radiance
+                  //  tap below: three registers that the ranking's terms take)
+                  if (BEST_APPROX && ctx == 1) park_store3<MDH_PARK_SPEC>(pk, wb, specular_col);
                   if (BEST_FIRST && ctx == 1) {
                      int tried = 0; // bit i: corner i was a candidate and is blocked
                      bool searching = true;
@@ -879,11 +978,39 @@ MDH_DEV f3 shade_structured(const KScene &sc, const KProbes &pr, const MachineCf
                      float bvmax = 0.0f;
                      f3 bvd = F3(0.0f, 0.0f, 0.0f);
                      int bi = -1, bq = 0;
+                     bool round0 = true;
 #pragma unroll 1
                      for (;;) {
                         if (searching) {
                            float bd = 0.0f;
                            bi = -1;
+                           // The first round ranks the corners by best_approx's a_i where that decides in every searching lane of
+                           // the wavefront: a winner runs the scan's statements once, for its corner (the same operations on the
+                           // same values: bvd, bvmax and bq are the scan's; d is read by nobody), a lane without a candidate goes
+                           // to the in-order loop as the scan would send it.  One undecided lane, and the wavefront scans as it
+                           // did (the scan costs a wavefront the same whether one lane or all run it).  Later rounds always scan.
+                           bool scan = true;
+                           if (BEST_APPROX && round0) {
+                              int wi;
+                              const int state = best_approx(pr, gp, folded, P, N, wi);
+                              scan = __ballot(state == 0) != 0ull;
+                              MDH_BEST_APPROX_STAT(0, __popcll(__ballot(state == 1)));
+                              MDH_BEST_APPROX_STAT(1, __popcll(__ballot(state == 2)));
+                              MDH_BEST_APPROX_STAT(2, __popcll(__ballot(state == 0)));
+                              if (scan) MDH_BEST_APPROX_STAT(3, 1);
+                              if (!scan && state == 1) {
+                                 bi = wi;
+                                 const KProbes pq = probes_fresh(pr);
+                                 const i3 q = cage_probe(pq, gp, bi);
+                                 const f3 pw = grid_to_world(pq, q);
+                                 const f3 hvec = P - pw;
+                                 const float dist = length(hvec);
+                                 f3 vd = sdiv3(hvec, dist);
+                                 vd = -vd;
+                                 bvd = vd; bvmax = dist - MDH_MIN_STEP * 5.0f; bq = q.x | (q.y << 10) | (q.z << 20);
+                              }
+                           }
+                           if (scan)
 #pragma unroll 1
                            for (int i = 0; i < 8; ++i) {
                               if ((i & folded) || ((tried >> i) & 1)) continue;
@@ -899,6 +1026,7 @@ MDH_DEV f3 shade_structured(const KScene &sc, const KProbes &pr, const MachineCf
                            }
                            if (bi < 0) { in_order = true; searching = false; }
                         }
+                        round0 = false;
                         if (!__ballot(searching)) break;
                         MDH_BEST_STAT(0, 1);
                         // raycast_visibility of the candidate, as the loop runs it (a lane that is not searching has no ray: vmax 0)
@@ -1093,6 +1221,7 @@ MDH_DEV f3 shade_structured(const KScene &sc, const KProbes &pr, const MachineCf
                      f3 radiance = (SPEC == 2 && pq.rad_mips) // (MDH_OPT_RADIANCE_MIPS, in the kernel variant of the optional paths only: textureLod (.., 1.0))
                         ? radiance_lod_sample(pq, 1.0f, base.x + div_pcx<P2>(pq, brid.x), base.y + div_pcy<P2>(pq, brid.y), u8_tab)
                         : atlas_sample<P2>(pq.rad, pq.fmt, pq.pcx, pq.pcy, pq.rres, pq.rshift, pq.rad_w, pq.rad_h, base.x + div_pcx<P2>(pq, brid.x), base.y + div_pcy<P2>(pq, brid.y), u8_tab, pq.m_rres);
+                     if (BEST_APPROX) specular_col = park_load3<MDH_PARK_SPEC>(pk, wb);
                      specular_col = radiance + specular_col;
                      park_store3<MDH_PARK_SPEC>(pk, wb, specular_col);
                   }
